@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Train-step throughput of the AMContrast3D hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 
 Metric (BASELINE.json): train-step points/sec -- forward + CrossEntropyAce (cross-entropy + adaptive-margin contrast over 4
 decoder stages) + backward (+ gradient all-reduce for N > 1) + clip + AdamW step -- on synthetic S3DIS-shaped 24 000-point
@@ -12,7 +12,9 @@ Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line
 The step that is timed is the PRODUCT's: amcontrast3d_amd.pipeline.GraphPipeline (hipGraph replays on three hardware queues,
 what amcontrast3d_amd.train.train_one_epoch runs); this file only builds the model, feeds resident batches and measures.
 `--gpus N` without a torchrun environment starts the N ranks itself (a torch.distributed.run child process, launched before
-this process has made any GPU call).  Besides the contract fields the line carries
+this process has made any GPU call).  A plain run sets up, warms up, times K steps and prints the line: the contract fields,
+the configuration and the last step's loss.  `--dump-outputs DIR` writes what the last timed step computed (dump_outputs).
+With `--full` the line also carries what takes runs of its own after the timed steps:
 
   roofline        the dominant operator of the feature half (amcontrast3d_amd/roofline.py): SURVEY 8(d) algorithmic bytes (or
                   FLOPs) per launch / live HIP-event time vs 8 TB/s (157.3 TF fp32 MFMA); `traffic` = PMC bytes per launch
@@ -21,7 +23,7 @@ this process has made any GPU call).  Besides the contract fields the line carri
   latency_chain   the FPS chain (runs J..2J steps ahead on a queue of its own): microseconds per dependent iteration
   train_one_epoch_ms_per_step   the same step through train.train_one_epoch (loader batches, confusion matrix, schedule)
   ms_per_step_no_overlap, single_batch_latency_ms, pipeline_parts_alone   the parts back to back / one batch through all
-  cpu_baseline    the oracle's CPU restatement of the SAME step on this box's host cores (rank 0, N = 1 only)
+  cpu_baseline    the oracle's CPU restatement of the SAME step on this box's host cores (rank 0, N = 1 only; also `--eval`'s)
   kernels         per-operator HIP-event totals of an eager step (ms per step)
 """
 import argparse
@@ -60,6 +62,13 @@ def parse():
     ap.add_argument("--pool", type=int, default=4, help="distinct resident batches fed round-robin (different geometry every step)")
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32", help="bf16: the reference's use_amp (main_AA.py:389-394)")
     ap.add_argument("--lean", action="store_true", help="profiling runs: stop after the timed loop")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: pipeline parts alone and "
+                         "back to back, the step through train.train_one_epoch, per-operator timing + roofline, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (loss, logits, the updated parameters) "
+                         "as DIR/<name>.npy, float32, at most 64 MB in all; that step starts from the initial weights and a fresh "
+                         "optimizer state")
     ap.add_argument("--rehearse-cpu", action="store_true",
                     help="no GPU: only the multi-rank control flow on a small torch CPU model over gloo (tests/test_dist_cpu.py)")
     ap.add_argument("--ddp", action="store_true", help="N > 1: torch's SyncBatchNorm + DistributedDataParallel wrappers, eager")
@@ -233,7 +242,9 @@ def eval_main(args):
             "config": {"workload": f"PointNeXt-{args.variant}, one room of {args.room_points} points in {len(parts)} sub-clouds of "
                                    f"{len(parts[0])} points (voxel 0.04), inputs on the host"},
             "miou_whole_boundary_inner": [round(v, 3) for v in evaluate.summarize(r["cm"], r["cm_b"], r["cm_i"])[0:15:5]]}
-    if not args.no_cpu_baseline:
+    if args.dump_outputs:  # the voted per-point logits and the three confusion matrices of the last room
+        dump_outputs(args.dump_outputs, {"logits": r["logits"], **{k: torch.as_tensor(r[k].value) for k in ("cm", "cm_b", "cm_i")}})
+    if args.full and not args.no_cpu_baseline:
         from oracle import eval_ref, pointops_ref
         pointops_ref.build()
         cores = min(len(os.sched_getaffinity(0)), int(os.environ.get("AMC3D_CPU_THREADS", "16")))
@@ -245,6 +256,25 @@ def eval_main(args):
         line["cpu_baseline"] = {"value": round(2 * len(parts[0]) / dtc, 1), "unit": "points/s", "cores": cores, "kind": "port",
                                 "sample": f"2 of the {len(parts)} sub-clouds, {dtc:.1f} s (oracle/eval_ref.py, {cores} threads)"}
     print(json.dumps(line))
+
+
+DUMP_MAX_ELEMENTS = 4 << 20  # per array (16 MiB of float32); a larger output is written as a fixed seeded sample of its elements
+
+
+def dump_outputs(dirname, arrays):
+    """`--dump-outputs`: each array as DIR/<name>.npy in float32 -- flattened to a seeded sample of DUMP_MAX_ELEMENTS elements
+    (the same indices for the same size, so that two builds compare element for element) where it is larger"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))
+            a = a.reshape(-1)[idx]
+        total += a.nbytes
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    assert total <= 64 << 20, total
 
 
 def loader_batches(pool_np, n):
@@ -298,6 +328,18 @@ def main():
     params = list(model.parameters())
     flatg = (adist.FlatGradients(params, accumulate=False) if (world > 1 and not use_ddp) or os.environ.get("AMC3D_FLAT_GRADS") else None)
     amp = torch.bfloat16 if args.dtype == "bf16" else None
+    # --dump-outputs: the last timed step starts from the initial weights and a fresh optimizer state, so that its inputs are
+    # the same from run to run (float atomics in the backward make the weights of two runs drift apart step by step)
+    init_state = {k: v.detach().clone() for k, v in model.state_dict().items()} if args.dump_outputs else None
+
+    def reset_state():  # in place, on the current stream: the captured graphs read these tensors
+        with torch.no_grad():
+            for k, v in model.state_dict().items():
+                v.copy_(init_state[k])
+            for st in opt.state.values():
+                for t in st.values():
+                    if torch.is_tensor(t):
+                        t.zero_()
 
     def step_loss(data):
         if args.mm:  # examples/segmentation/main_MM.py:404-410: segmentation + regression objective
@@ -316,7 +358,7 @@ def main():
             flatg.gather()
             flatg.allreduce()
         opt.step(max_grad_norm=10) if type(opt).__name__ == "FusedAdamW" else (torch.nn.utils.clip_grad_norm_(params, 10), opt.step())
-        return loss
+        return {"loss": loss, "logits": logits}
 
     main_s = torch.cuda.Stream()  # all work of this process runs on a non-default stream (capture recipe)
     main_s.wait_stream(torch.cuda.current_stream())
@@ -343,20 +385,25 @@ def main():
             torch.cuda.synchronize()
             pipe = make_pipeline()
         runner = pipe.run(itertools.cycle(pool))
-        step = lambda: next(runner)["loss"]  # noqa: E731
+        step = lambda: next(runner)  # noqa: E731
     for _ in range(args.warmup):
-        loss = step()
+        out = step()
     torch.cuda.synchronize()
     adist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        if init_state is not None and i == args.steps - 1:
+            reset_state()
+        out = step()
     torch.cuda.synchronize()
     adist.barrier()
     torch.cuda.synchronize()
     dt = adist.max_over_ranks(time.perf_counter() - t0, dev)
-    final_loss = float(loss.detach())
+    final_loss = float(out["loss"].detach())
+    if args.dump_outputs and rank == 0:  # before anything else runs: the pipeline's result buffers are reused
+        dump_outputs(args.dump_outputs, {"loss": out["loss"], "logits": out["logits"],
+                                         "params": torch.cat([p.detach().reshape(-1).float() for p in params])})
     assert flatg is None or flatg.intact(), "a parameter gradient left the flat all-reduce buffer"
     in_sync = replicas_in_sync(params) if world > 1 else None
     ms_per_step = dt / args.steps * 1e3
@@ -366,8 +413,9 @@ def main():
         if world > 1:
             torch.distributed.destroy_process_group()
         return
-    parts = serial_ms = epoch_ms = None
-    if pipe is not None:  # on every rank: with SyncBN the feature replay contains collectives
+    parts = serial_ms = epoch_ms = kernels = roofs = None
+    ksteps = min(args.steps, 3)
+    if pipe is not None and args.full:  # on every rank: with SyncBN the feature replay contains collectives
         parts, serial_ms = pipe.parts_alone(), pipe.serial_ms()
         if world == 1 and not args.mm and amp is None:
             # the same step through the product's training loop (main_AA.py:370-428): loader batches in the reference's collated
@@ -388,21 +436,23 @@ def main():
                 train.train_one_epoch(model, loader_batches(pool_np, nb), criterion, opt, sched, None, 1 + rep, tcfg)
                 torch.cuda.synchronize()
                 epoch_ms = (time.perf_counter() - t0) / nb * 1e3
-    # per-operator HIP-event timing: the same step launched eagerly so that each C-ABI launch can be bracketed by events on its
-    # stream (events cannot bracket nodes inside a graph replay)
-    ksteps = min(args.steps, 3)
-    timing.enable(True)
-    for j in range(ksteps):
-        eager_step(dict(pool[j % len(pool)]))
-    torch.cuda.synchronize()
-    kernels = timing.collect()
-    timing.enable(False)
+    if args.full:
+        # per-operator HIP-event timing: the same step launched eagerly so that each C-ABI launch can be bracketed by events on
+        # its stream (events cannot bracket nodes inside a graph replay)
+        timing.enable(True)
+        for j in range(ksteps):
+            eager_step(dict(pool[j % len(pool)]))
+        torch.cuda.synchronize()
+        kernels = timing.collect()
+        timing.enable(False)
     if rank == 0:
-        fps = None
-        if pipe is not None:
-            fps = {"points": args.points, "levels": pipe.nlevels, "joint_ms": parts["fps_all_levels_joint_launch_ms"],
-                   "clouds": args.batch * pipe.lanes, "lanes": pipe.lanes}
-        roofs = roofline.report(kernels, ksteps, ms_per_step, args.batch * args.points, args.variant, args.mm, pipe is not None, fps)
+        if args.full:
+            fps = None
+            if pipe is not None:
+                fps = {"points": args.points, "levels": pipe.nlevels, "joint_ms": parts["fps_all_levels_joint_launch_ms"],
+                       "clouds": args.batch * pipe.lanes, "lanes": pipe.lanes}
+            roofs = roofline.report(kernels, ksteps, ms_per_step, args.batch * args.points, args.variant, args.mm, pipe is not None,
+                                    fps)
         line = {
             "metric": "train-step points/sec (fwd+bwd) on 24k-pt S3DIS clouds",
             "value": round(args.batch * args.points * world / (dt / args.steps), 1), "unit": "points/s", "n_gpus": world,
@@ -417,16 +467,19 @@ def main():
                             "parallelism": f"dp{world}" + ("+syncbn+ddp" if use_ddp else "+syncbn" if sync_bn else "")},
                            **(pipe.describe() if pipe is not None else {"launch": "eager", "pipeline": "none"})),
             "loss": round(final_loss, 6), "replicas_in_sync": in_sync, "resident_batches": len(pool),
-            "train_one_epoch_ms_per_step": round(epoch_ms, 3) if epoch_ms else None,
-            "ms_per_step_no_overlap": serial_ms,
-            "single_batch_latency_ms": round(sum(v for v in parts.values() if v), 3) if parts else None,
-            "pipeline_parts_alone": parts,
-            **roofs,
-            "kernels": {k: {"ms_per_step": round(v["total_ms"] / ksteps, 4), "launches_per_step": v["launches"] / ksteps}
-                        for k, v in kernels.items()},
-            "native_ms_per_step": round(sum(v["total_ms"] for v in kernels.values()) / ksteps, 3),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            line.update({
+                "train_one_epoch_ms_per_step": round(epoch_ms, 3) if epoch_ms else None,
+                "ms_per_step_no_overlap": serial_ms,
+                "single_batch_latency_ms": round(sum(v for v in parts.values() if v), 3) if parts else None,
+                "pipeline_parts_alone": parts,
+                **roofs,
+                "kernels": {k: {"ms_per_step": round(v["total_ms"] / ksteps, 4), "launches_per_step": v["launches"] / ksteps}
+                            for k, v in kernels.items()},
+                "native_ms_per_step": round(sum(v["total_ms"] for v in kernels.values()) / ksteps, 3),
+            })
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg, model, pool_np[0], configs.ambiguity_args("s3dis"), args.points,
                                                 small=args.cpu_baseline_batch)
         print(json.dumps(line))

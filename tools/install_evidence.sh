@@ -11,6 +11,6 @@ cp $G/${T}XLMM_steady.txt $P/round3_${V}_XLMM_steady_state.txt
 cp $G/${T}S_hbm_pmc.csv $P/round3_${V}_hbm_pmc.csv; cp $G/${T}S_hbm_pmc.csv $P/round3_hbm_pmc.csv
 cp $G/${T}S_hbm_traffic.json $P/hbm_traffic.json
 cp $G/${T}S_valu_pmc.csv $P/round3_${V}_valu_pmc.csv; cp $G/${T}S_valu_pmc.csv $P/round3_valu_pmc.csv
-tail -1 $G/${T}_bench.json > $P/round3_${V}_bench.json
+tail -1 "${EVIDENCE_OUT:-evidence}/${T}_bench.json" > $P/round3_${V}_bench.json
 cp $G/${T}_side_configs.jsonl $P/round3_${V}_side_configs.jsonl
 ls -la $P | grep "round3_${V}\|hbm_traffic\|round3_kernel\|round3_valu"
