@@ -1763,15 +1763,16 @@ class LibraryGemmConv(Function):
         timing.note("library_gemm_conv")
         import os
         # under bf16 autocast (use_amp, main_AA.py:389): bf16 operands for the three library GEMMs, fp32 accumulation inside the
-        # library, fp32 tensors outside -- cfg 5 (XL + ++, 1 x 120000): 20.7 -> 19.7 ms per step (fp32: 20.2); AMC3D_LIB_FP32=1 keeps fp32
+        # library, fp32 results (tests/test_gpu_bf16.py) -- cfg 5 (XL + ++, 1 x 120000): 16.8 ms per step, 17.1 when the
+        # results were still rounded to bf16 and widened again; AMC3D_LIB_FP32=1 keeps fp32
         ctx.bf16 = bool(torch.is_autocast_enabled() and torch.get_autocast_dtype('cuda') == torch.bfloat16
                         and not os.environ.get("AMC3D_LIB_FP32"))
         # bmm with the weight expanded along the batch (stride 0): torch.matmul(2-d, 3-d) would fold the batch into one
         # GEMM by way of a transposed copy of x.
         with torch.autocast("cuda", enabled=False):
-            if ctx.bf16:  # bf16 operands (fp32 accumulation inside the library), fp32 tensors outside
+            if ctx.bf16:  # bf16 operands, fp32 accumulation AND fp32 results (out_dtype: a bf16 result would be rounded)
                 x16, w16 = x.view(B, Cin, -1).to(torch.bfloat16), w2.to(torch.bfloat16)
-                y = torch.bmm(w16.unsqueeze(0).expand(B, Cout, Cin), x16).float()
+                y = torch.bmm(w16.unsqueeze(0).expand(B, Cout, Cin), x16, out_dtype=torch.float32)
                 ctx.save_for_backward(x16, w16)
             else:
                 y = torch.bmm(w2.unsqueeze(0).expand(B, Cout, Cin), x.view(B, Cin, -1))
@@ -1788,9 +1789,11 @@ class LibraryGemmConv(Function):
         if ctx.bf16:
             with torch.autocast("cuda", enabled=False):
                 dy16 = dy3.to(torch.bfloat16)
-                dx = (torch.bmm(w2.t().unsqueeze(0).expand(B, Cin, w2.shape[0]), dy16).float().view(ctx.xshape)
+                dx = (torch.bmm(w2.t().unsqueeze(0).expand(B, Cin, w2.shape[0]), dy16, out_dtype=torch.float32).view(ctx.xshape)
                       if ctx.needs_input_grad[0] else None)
-                dw = (torch.bmm(dy16, x.transpose(1, 2)).float().sum(0).view(ctx.wshape) if ctx.needs_input_grad[1] else None)
+                # each cloud's partial stays fp32 up to the fp32 sum over the batch
+                dw = (torch.bmm(dy16, x.transpose(1, 2), out_dtype=torch.float32).sum(0).view(ctx.wshape)
+                      if ctx.needs_input_grad[1] else None)
             return dx, dw
         with torch.autocast("cuda", enabled=False):
             dx = (torch.bmm(w2.t().unsqueeze(0).expand(B, Cin, w2.shape[0]), dy3).view(x.shape)

@@ -23,7 +23,7 @@ DEV = "cuda:0"
 B, N = 2, 2048
 
 
-def _setup(lr, fused=True, seed=0):
+def _setup(lr, fused=True, seed=0, width=16):
     import amcontrast3d_amd
     amcontrast3d_amd.activate()
     from openpoints.loss import build_criterion_from_cfg
@@ -31,7 +31,7 @@ def _setup(lr, fused=True, seed=0):
     from openpoints.optim import build_optimizer_from_cfg
     from openpoints.utils import EasyConfig
     torch.manual_seed(seed)
-    c = EasyConfig(); c.update(configs.model_cfg("S", dropout=0, width=16))
+    c = EasyConfig(); c.update(configs.model_cfg("S", dropout=0, width=width))
     model = build_model_from_cfg(c).to(DEV).train()
     cc = EasyConfig(); cc.update(configs.criterion_cfg())
     crit = build_criterion_from_cfg(cc).to(DEV)
@@ -59,9 +59,10 @@ def _pipeline(model, crit, aa, opt, example, lanes, **kw):
     return pipe, main
 
 
-def _eager_step(model, crit, aa, opt, data, clip=10):
-    logits, stage = model(dict(data))
-    loss = crit(logits, data["y"], stage, 13, None, aa)
+def _eager_step(model, crit, aa, opt, data, clip=10, amp_dtype=None):
+    with torch.autocast("cuda", dtype=amp_dtype or torch.bfloat16, enabled=amp_dtype is not None):
+        logits, stage = model(dict(data))
+        loss = crit(logits, data["y"], stage, 13, None, aa)
     opt.zero_grad()
     loss.backward()
     if type(opt).__name__ == "FusedAdamW":
@@ -103,6 +104,32 @@ def test_every_result_belongs_to_one_batch_in_order(lanes, nb):
     for i, (pos, logits) in enumerate(outs):
         assert torch.equal(pos, src2[i]["pos"])
         assert torch.equal(logits, _eager_step(model2, crit2, aa2, opt2, src2[i])[0])
+
+
+def test_captured_bf16_step_matches_the_eager_autocast_step(monkeypatch):
+    """GraphPipeline(amp_dtype=torch.bfloat16) -- the step bench.py --dtype bf16 times -- at a width where the bf16 routes
+    engage (the conv before the gather from SA1 on, the library GEMMs of the deep layers): every result belongs to one
+    batch, in order, with logits bit-identical to the eager step under autocast on that batch"""
+    from amcontrast3d_amd import ops
+    model, crit, aa, opt = _setup(0.0, fused=False, width=64)
+    src = _batches(5)
+    pipe, main = _pipeline(model, crit, aa, opt, src[0], 2, amp_dtype=torch.bfloat16)
+    got = []
+    with torch.cuda.stream(main):
+        for out in pipe.run(iter(src)):
+            got.append((out["data"]["pos"].clone(), out["logits"].clone(), float(out["loss"])))
+    torch.cuda.synchronize()
+    assert len(got) == len(src)
+    model2, crit2, aa2, opt2 = _setup(0.0, fused=False, width=64)
+    calls = []
+    orig = ops._pw
+    monkeypatch.setattr(ops, "_pw", lambda lib, bf16: calls.append(bool(bf16)) or orig(lib, bf16))
+    for i, (pos, logits, loss) in enumerate(got):
+        assert torch.equal(pos, src[i]["pos"]), f"result {i} is not batch {i}"
+        want_logits, want_loss = _eager_step(model2, crit2, aa2, opt2, src[i], amp_dtype=torch.bfloat16)
+        assert torch.equal(logits, want_logits), f"batch {i}: logits differ from the eager autocast step's (max {float((logits - want_logits).abs().max()):.2e})"
+        assert abs(loss - float(want_loss)) <= 1e-6 * abs(float(want_loss)), (i, loss, float(want_loss))
+    assert calls.count(True) > 0  # the eager step took the bf16 MFMA
 
 
 def test_every_variants_gradient_reaches_the_static_tensors():
