@@ -96,6 +96,13 @@ SIGNATURES = {
     "amc3d_voxel_select": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "amc3d_crop_nearest_workspace_bytes": (_sz, [_i]),
     "amc3d_crop_nearest": (_i, [_i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "amc3d_voxelize_f64": (_i, [_i, _vp, ctypes.c_double] + [_vp] * 7 + [_sz, _vp]),
+    "amc3d_crop_nearest_f64_workspace_bytes": (_sz, [_i]),
+    "amc3d_crop_nearest_f64": (_i, [_i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "amc3d_scannet_stats_workspace_bytes": (_sz, [_i]),
+    "amc3d_scannet_room_stats": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "amc3d_scannet_transform_rooms": (_i, [_i, _ll] + [_vp] * 9 + [_vp]),
+    "amc3d_scannet_crop_tail": (_i, [_i, _i] + [_vp] * 10 + [_vp]),
     "amc3d_local_aggregation_supported": (_i, [_i, _i]),
     "amc3d_group_moments_bytes": (_sz, [_i, _i]),
     "amc3d_group_moments": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),

@@ -10,13 +10,18 @@
 // Arithmetic as numpy does it under numpy 2 (the container's): coord (float32) / np.array(voxel_size) is a float64
 // division (a 0-d array is not a weak scalar), floor in float64, cast to uint64; squared distances in float32 without
 // contraction, ((dx^2 + dy^2) + dz^2).
+// ScanNet's chain (dataset/scannetv2/scannet.py:140-176) rotates the raw room with np.dot(pos_f32, R_f64) before crop_pc, so
+// its coordinates reach voxelize and the crop as float64: the *_f64 entry points take double coordinates (same hash of
+// floor(coord / voxel), distances ((dx^2 + dy^2) + dz^2) in double, sorted on their 64-bit patterns).
 #include "cub_kernel_memset.h"  // hipCUB with its memsets as kernels (graph-safe)
 
 #include "common.h"
 
 namespace amc {
 
-__global__ void voxel_key_kernel(int n, const float *__restrict__ coord, double voxel, unsigned long long *__restrict__ key,
+// T = float (S3DIS) or double (ScanNet): the division and floor are float64 either way
+template <typename T>
+__global__ void voxel_key_kernel(int n, const T *__restrict__ coord, double voxel, unsigned long long *__restrict__ key,
                                  int *__restrict__ iota)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -78,6 +83,21 @@ __global__ void crop_d2_kernel(int n, const float *__restrict__ coord, int init,
     iota[i] = i;
 }
 
+// the double version of crop_d2_kernel: float64 distances, their bit patterns (non-negative doubles order like them) as keys
+__global__ void crop_d2_f64_kernel(int n, const double *__restrict__ coord, int init, double *__restrict__ d2,
+                                   unsigned long long *__restrict__ bits, int *__restrict__ iota)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double dx = __dsub_rn(coord[(size_t)i * 3], coord[(size_t)init * 3]);
+    const double dy = __dsub_rn(coord[(size_t)i * 3 + 1], coord[(size_t)init * 3 + 1]);
+    const double dz = __dsub_rn(coord[(size_t)i * 3 + 2], coord[(size_t)init * 3 + 2]);
+    const double d = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+    d2[i] = d;
+    bits[i] = (unsigned long long)__double_as_longlong(d);
+    iota[i] = i;
+}
+
 __global__ void copy_i32_kernel(int n, const int *__restrict__ src, int *__restrict__ dst)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -115,17 +135,17 @@ AMC_API size_t amc3d_voxelize_workspace_bytes(int n)
     return align256((size_t)n * 8) + 3 * align256((size_t)n * 4) + sort64_temp(n) + 256;
 }
 
-// coord (n,3) fp32, shifted to its min corner.  key (n): the FNV-1a hash of every point's cell (as fnv_hash_vec);
-// idx_sort (n): point indices ordered by key (stable); voxel_idx (n): voxel id of sorted position i; start (n+1):
-// first sorted position of every voxel (start[nvox] = n); count (n): points per voxel (0 beyond nvox); nvox (1).
-AMC_API int amc3d_voxelize(int n, const float *coord, double voxel_size, unsigned long long *key, int *idx_sort, int *voxel_idx,
-                           int *start, int *count, int *nvox, void *workspace, size_t workspace_bytes, void *stream_)
+template <typename T>
+static int voxelize_impl(const char *what, int n, const T *coord, double voxel_size, unsigned long long *key, int *idx_sort,
+                         int *voxel_idx, int *start, int *count, int *nvox, void *workspace, size_t workspace_bytes,
+                         hipStream_t stream)
 {
     if (n <= 0) return 0;
     if (!coord || !(voxel_size > 0.0) || !key || !idx_sort || !voxel_idx || !start || !count || !nvox || !workspace ||
-        workspace_bytes < amc3d_voxelize_workspace_bytes(n))
-        return bad_arg("amc3d_voxelize: bad argument");
-    hipStream_t stream = (hipStream_t)stream_;
+        workspace_bytes < amc3d_voxelize_workspace_bytes(n)) {
+        set_error("%s: bad argument", what);
+        return (int)hipErrorInvalidValue;
+    }
     char *w = (char *)workspace;
     unsigned long long *ks = (unsigned long long *)w; w += align256((size_t)n * 8);
     int *iota = (int *)w; w += align256((size_t)n * 4);
@@ -133,17 +153,36 @@ AMC_API int amc3d_voxelize(int n, const float *coord, double voxel_size, unsigne
     int *incl = (int *)w; w += align256((size_t)n * 4);
     size_t temp = sort64_temp(n);
     const int blocks = div_up(n, 256);
-    hipLaunchKernelGGL(voxel_key_kernel, dim3(blocks), dim3(256), 0, stream, n, coord, voxel_size, key, iota);
+    hipLaunchKernelGGL(voxel_key_kernel<T>, dim3(blocks), dim3(256), 0, stream, n, coord, voxel_size, key, iota);
     hipError_t e = hipcub::DeviceRadixSort::SortPairs(w, temp, (const unsigned long long *)key, ks, (const int *)iota, idx_sort, n, 0, 64, stream);
-    if (e != hipSuccess) { set_error("amc3d_voxelize: radix sort: %s", hipGetErrorString(e)); return (int)e; }
+    if (e != hipSuccess) { set_error("%s: radix sort: %s", what, hipGetErrorString(e)); return (int)e; }
     hipLaunchKernelGGL(voxel_head_kernel, dim3(blocks), dim3(256), 0, stream, n, (const unsigned long long *)ks, head);
     temp = sort64_temp(n);
     e = hipcub::DeviceScan::InclusiveSum(w, temp, (const int *)head, incl, n, stream);
-    if (e != hipSuccess) { set_error("amc3d_voxelize: scan: %s", hipGetErrorString(e)); return (int)e; }
+    if (e != hipSuccess) { set_error("%s: scan: %s", what, hipGetErrorString(e)); return (int)e; }
     hipLaunchKernelGGL(voxel_start_kernel, dim3(blocks), dim3(256), 0, stream, n, (const int *)head, (const int *)incl, voxel_idx, start,
                        nvox);
     hipLaunchKernelGGL(voxel_count_kernel, dim3(blocks), dim3(256), 0, stream, n, (const int *)nvox, (const int *)start, count);
-    return launch_status("amc3d_voxelize");
+    return launch_status(what);
+}
+
+// coord (n,3) fp32, shifted to its min corner.  key (n): the FNV-1a hash of every point's cell (as fnv_hash_vec);
+// idx_sort (n): point indices ordered by key (stable); voxel_idx (n): voxel id of sorted position i; start (n+1):
+// first sorted position of every voxel (start[nvox] = n); count (n): points per voxel (0 beyond nvox); nvox (1).
+AMC_API int amc3d_voxelize(int n, const float *coord, double voxel_size, unsigned long long *key, int *idx_sort, int *voxel_idx,
+                           int *start, int *count, int *nvox, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    return voxelize_impl("amc3d_voxelize", n, coord, voxel_size, key, idx_sort, voxel_idx, start, count, nvox, workspace,
+                         workspace_bytes, (hipStream_t)stream_);
+}
+
+// the same for float64 coordinates (ScanNet's rotated rooms); workspace: amc3d_voxelize_workspace_bytes(n)
+AMC_API int amc3d_voxelize_f64(int n, const double *coord, double voxel_size, unsigned long long *key, int *idx_sort,
+                               int *voxel_idx, int *start, int *count, int *nvox, void *workspace, size_t workspace_bytes,
+                               void *stream_)
+{
+    return voxelize_impl("amc3d_voxelize_f64", n, coord, voxel_size, key, idx_sort, voxel_idx, start, count, nvox, workspace,
+                         workspace_bytes, (hipStream_t)stream_);
 }
 
 // train mode of voxelize (data_util.py:136-140): one point per voxel, idx_unique[v] = idx_sort[start[v] + rnd[v] % count[v]]
@@ -184,4 +223,34 @@ AMC_API int amc3d_crop_nearest(int n, const float *coord, int init_idx, int keep
     if (e != hipSuccess) { set_error("amc3d_crop_nearest: radix sort: %s", hipGetErrorString(e)); return (int)e; }
     hipLaunchKernelGGL(copy_i32_kernel, dim3(div_up(keep, 256)), dim3(256), 0, stream, keep, (const int *)sidx, crop_idx);
     return launch_status("amc3d_crop_nearest");
+}
+
+AMC_API size_t amc3d_crop_nearest_f64_workspace_bytes(int n)
+{
+    if (n <= 0) return 0;
+    // bits | sorted bits (8 B each) | iota | sorted idx | temp
+    return 2 * align256((size_t)n * 8) + 2 * align256((size_t)n * 4) + sort64_temp(n) + 256;
+}
+
+// crop_pc's crop on float64 coordinates: d2 (n) double, crop_idx (keep) as amc3d_crop_nearest
+AMC_API int amc3d_crop_nearest_f64(int n, const double *coord, int init_idx, int keep, double *d2, int *crop_idx, void *workspace,
+                                   size_t workspace_bytes, void *stream_)
+{
+    if (n <= 0 || keep <= 0) return 0;
+    if (!coord || init_idx < 0 || init_idx >= n || keep > n || !d2 || !crop_idx || !workspace ||
+        workspace_bytes < amc3d_crop_nearest_f64_workspace_bytes(n))
+        return bad_arg("amc3d_crop_nearest_f64: bad argument");
+    hipStream_t stream = (hipStream_t)stream_;
+    char *w = (char *)workspace;
+    unsigned long long *bits = (unsigned long long *)w; w += align256((size_t)n * 8);
+    unsigned long long *sbits = (unsigned long long *)w; w += align256((size_t)n * 8);
+    int *iota = (int *)w; w += align256((size_t)n * 4);
+    int *sidx = (int *)w; w += align256((size_t)n * 4);
+    size_t temp = sort64_temp(n);
+    hipLaunchKernelGGL(crop_d2_f64_kernel, dim3(div_up(n, 256)), dim3(256), 0, stream, n, coord, init_idx, d2, bits, iota);
+    hipError_t e = hipcub::DeviceRadixSort::SortPairs(w, temp, (const unsigned long long *)bits, sbits, (const int *)iota, sidx, n, 0,
+                                                      64, stream);
+    if (e != hipSuccess) { set_error("amc3d_crop_nearest_f64: radix sort: %s", hipGetErrorString(e)); return (int)e; }
+    hipLaunchKernelGGL(copy_i32_kernel, dim3(div_up(keep, 256)), dim3(256), 0, stream, keep, (const int *)sidx, crop_idx);
+    return launch_status("amc3d_crop_nearest_f64");
 }

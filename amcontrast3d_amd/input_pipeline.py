@@ -21,10 +21,15 @@ from . import _lib
 from .ops import _need_dtype, _need_gpu, _ptr, _stream
 
 
-def _voxel_tables(coord, voxel_size):
+def _coord_f32_or_f64(coord):
     _need_gpu(coord)
-    _need_dtype(torch.float32, coord=coord)
-    coord = coord.contiguous()
+    if coord.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f"expected coord to be torch.float32 or torch.float64, got {coord.dtype}")
+    return coord.contiguous()
+
+
+def _voxel_tables(coord, voxel_size):
+    coord = _coord_f32_or_f64(coord)
     n = coord.shape[0]
     dev = coord.device
     lib = _lib.load()
@@ -37,7 +42,8 @@ def _voxel_tables(coord, voxel_size):
     wb = int(lib.amc3d_voxelize_workspace_bytes(n))
     work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.amc3d_voxelize(n, _ptr(coord), ctypes.c_double(float(voxel_size)), _ptr(key), _ptr(idx_sort),
+        fn = lib.amc3d_voxelize_f64 if coord.dtype == torch.float64 else lib.amc3d_voxelize
+        _lib.check(fn(n, _ptr(coord), ctypes.c_double(float(voxel_size)), _ptr(key), _ptr(idx_sort),
                                       _ptr(voxel_idx), _ptr(start), _ptr(count), _ptr(nvox), _ptr(work), wb, _stream(coord)),
                    "voxelize")
     nv = int(nvox.item())  # the number of voxels sizes what follows: one read-back per cloud
@@ -45,7 +51,7 @@ def _voxel_tables(coord, voxel_size):
 
 
 def voxelize(coord, voxel_size=0.05, hash_type='fnv', mode=0, rnd=None, generator=None):
-    """coord (n,3) fp32 on the GPU, already shifted to its min corner.
+    """coord (n,3) fp32 or fp64 on the GPU, already shifted to its min corner.
     mode 0 (train): idx_unique (nvox) int64 -- one point per voxel, the rnd[v] % count[v]-th of the voxel, rnd =
     randint(0, count.max(), nvox) drawn on the device (or given);  mode 1 (val): (idx_sort, voxel_idx, count) int64."""
     if hash_type != 'fnv':
@@ -65,27 +71,35 @@ def voxelize(coord, voxel_size=0.05, hash_type='fnv', mode=0, rnd=None, generato
 
 
 def crop_nearest(coord, init_idx, keep):
-    """the `keep` points nearest to coord[init_idx], ascending distance -> (d2 (n) fp32, crop_idx (keep) int64)"""
-    _need_gpu(coord)
-    _need_dtype(torch.float32, coord=coord)
-    coord = coord.contiguous()
-    n = coord.shape[0]
-    dev = coord.device
-    lib = _lib.load()
-    d2 = torch.empty(n, dtype=torch.float32, device=dev)
-    idx = torch.empty(int(keep), dtype=torch.int32, device=dev)
-    wb = int(lib.amc3d_crop_nearest_workspace_bytes(n))
-    work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.amc3d_crop_nearest(n, _ptr(coord), int(init_idx), int(keep), _ptr(d2), _ptr(idx), _ptr(work), wb,
-                                          _stream(coord)), "crop_nearest")
+    """the `keep` points nearest to coord[init_idx], ascending distance -> (d2 (n), crop_idx (keep) int64); d2 has the
+    coordinates' dtype (fp32 or fp64)"""
+    d2, idx = _crop_nearest_i32(coord, init_idx, keep)
     return d2, idx.long()
 
 
+def _crop_nearest_i32(coord, init_idx, keep):
+    coord = _coord_f32_or_f64(coord)
+    n = coord.shape[0]
+    dev = coord.device
+    lib = _lib.load()
+    f64 = coord.dtype == torch.float64
+    d2 = torch.empty(n, dtype=coord.dtype, device=dev)
+    idx = torch.empty(int(keep), dtype=torch.int32, device=dev)
+    wb = int(lib.amc3d_crop_nearest_f64_workspace_bytes(n) if f64 else lib.amc3d_crop_nearest_workspace_bytes(n))
+    work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
+    fn = lib.amc3d_crop_nearest_f64 if f64 else lib.amc3d_crop_nearest
+    with torch.cuda.device(dev):
+        _lib.check(fn(n, _ptr(coord), int(init_idx), int(keep), _ptr(d2), _ptr(idx), _ptr(work), wb, _stream(coord)),
+                   "crop_nearest")
+    return d2, idx
+
+
 def crop_pc(coord, feat, label, split='train', voxel_size=0.04, voxel_max=None, downsample=True, variable=True,
-            shuffle=True, generator=None, rnd=None, init_idx=None, perm=None):
-    """data_util.py:146-174 on GPU tensors: coord (n,3) fp32, feat (n,c) or None, label (n[,1]) or None ->
-    (coord fp32 shifted to its min corner, feat fp32, label int64), all on the GPU."""
+            shuffle=True, generator=None, rnd=None, init_idx=None, perm=None, pad=None):
+    """data_util.py:146-174 on GPU tensors: coord (n,3) fp32 or fp64 (the arithmetic is then float64 throughout, as numpy's on
+    a float64 room), feat (n,c) or None, label (n[,1]) or None -> (coord fp32 shifted to its min corner, feat fp32, label
+    int64), all on the GPU.  Draws that can be passed in: rnd (voxelize), init_idx (crop centre), pad (the
+    np.random.choice(N, voxel_max - N) of the variable=False repetition), perm (the shuffle)."""
     if voxel_size and downsample:
         coord = coord - coord.min(0).values
         uniq = voxelize(coord, voxel_size, rnd=rnd, generator=generator)
@@ -101,7 +115,9 @@ def crop_pc(coord, feat, label, split='train', voxel_size=0.04, voxel_max=None, 
                 init_idx = int(torch.randint(N, (1,), generator=generator, device=dev).item()) if 'train' in split else N // 2
             crop_idx = crop_nearest(coord.contiguous(), init_idx, voxel_max)[1]
         elif not variable:  # fill up by repetition (batched data of a fixed size)
-            pad = torch.randint(N, (voxel_max - N,), generator=generator, device=dev)
+            if pad is None:
+                pad = torch.randint(N, (voxel_max - N,), generator=generator, device=dev)
+            pad = pad.to(device=dev, dtype=torch.int64)
             crop_idx = torch.cat([torch.arange(N, device=dev), pad])
         if crop_idx is None:
             crop_idx = torch.arange(coord.shape[0], device=dev)
@@ -114,3 +130,112 @@ def crop_pc(coord, feat, label, split='train', voxel_size=0.04, voxel_max=None, 
         label = label[crop_idx] if label is not None else None
     coord = coord - coord.min(0).values
     return coord.float(), feat.float() if feat is not None else None, label.long() if label is not None else None
+
+
+def _voxel_select_i32(start, count, idx_sort, rnd):
+    nv = count.shape[0]
+    out = torch.empty(nv, dtype=torch.int32, device=count.device)
+    rnd = rnd.to(device=count.device, dtype=torch.int32).contiguous()
+    with torch.cuda.device(count.device):
+        _lib.check(_lib.load().amc3d_voxel_select(nv, _ptr(start), _ptr(count), _ptr(idx_sort), _ptr(rnd), _ptr(out),
+                                                  _stream(count)), "voxel_select")
+    return out
+
+
+def scannet_train_batch(rooms, transform, voxel_size=0.02, voxel_max=64000, variable=False, generator=None, draws=None,
+                        gravity_dim=2):
+    """ScanNet.__getitem__ for training (dataset/scannetv2/scannet.py:140-176) plus the default collate, for a batch of raw
+    rooms on the GPU: colours (feat + 1) * 127.5, `transform` (augment.ScanNetTrainAugment) on the whole room, crop_pc in
+    float64 (min-corner shift, voxelize mode 0, nearest-voxel_max crop or, with variable=False, padding by repetition,
+    shuffle, min-corner shift, cast) and heights.
+
+    rooms: list of (coord (n,3) fp32, feat (n,3) fp32 in [-1, 1], label (n,) or (n,1)) GPU tensors, as torch.load of a
+    ScanNet .pth gives them (labels pass through unchanged, -100 included).  Returns {pos (B,N,3) fp32, x (B,N,3) fp32,
+    heights (B,N,1) fp32, y (B,N) int64}, what DataLoader(ScanNet(split='train')) yields; every room must come out with the
+    same N (always so with variable=False).
+
+    Random numbers come from `generator` (a torch.Generator on the rooms' device, or the default one) or from `draws`: a
+    dict with the transform's keys (see ScanNetTrainAugment.draw; "R" for given rotation matrices) and per-room lists
+    "rnd" (voxelize's randint(0, count.max(), nvox)), "init_idx", "pad", "perm" (entries may be None).
+    Host synchronisation: one read-back per room (its voxel count, which sizes everything after it) and up to two per
+    batch (the room-level draws -- the rotation matrix is formed on the host -- and the crop centres' uniforms)."""
+    B = len(rooms)
+    if B == 0:
+        raise ValueError("scannet_train_batch: no rooms")
+    dev = rooms[0][0].device
+    for c, f, l in rooms:
+        _need_gpu(c, f, l)
+        _need_dtype(torch.float32, coord=c, feat=f)
+        if c.dim() != 2 or c.shape[1] != 3 or f.shape != c.shape or l.numel() != c.shape[0] or c.shape[0] == 0:
+            raise ValueError("scannet_train_batch: every room needs coord (n,3), feat (n,3), label (n,) with n > 0")
+    d = dict(draws or {})
+    keys = ("scale", "mirror_u", "contrast_u", "blend", "drop_u")
+    if any(k not in d for k in keys) or ("angle" not in d and "R" not in d):
+        for k, v in transform.draw(B, generator, dev).items():
+            d.setdefault(k, v)
+    per_room = {k: list(d.get(k) or [None] * B) for k in ("rnd", "init_idx", "pad", "perm")}
+    if any(len(v) != B for v in per_room.values()):
+        raise ValueError("scannet_train_batch: per-room draws need one entry per room")
+    sizes = [int(c.shape[0]) for c, _, _ in rooms]
+    offsets = torch.tensor([0] + sizes, dtype=torch.int64).cumsum(0).to(dev)
+    pos64, x, _ = transform(torch.cat([c for c, _, _ in rooms]), torch.cat([f for _, f, _ in rooms]), offsets, draws=d,
+                            generator=generator)
+    u_init = None
+    plans = []
+    beg = 0
+    for b in range(B):
+        p = pos64[beg:beg + sizes[b]]
+        p = p - p.min(0).values  # crop_pc's `coord -= coord.min(0)`, float64
+        key, idx_sort, voxel_idx, start, count = _voxel_tables(p, voxel_size)
+        N = count.shape[0]  # the read-back of this room
+        rnd = per_room["rnd"][b]
+        if rnd is None:  # randint(0, count.max(), nvox) without reading count.max() back
+            rnd = (torch.rand(N, dtype=torch.float64, device=dev, generator=generator) * count.max().double()).int()
+        else:
+            rnd = torch.as_tensor(rnd).to(dev)
+            if rnd.shape != (N,) or bool((rnd < 0).any()):
+                raise ValueError(f"scannet_train_batch: room {b}: rnd must hold {N} non-negative draws")
+        sel = _voxel_select_i32(start, count, idx_sort, rnd)
+        crop = None
+        if N >= voxel_max:
+            init = per_room["init_idx"][b]
+            if init is None:
+                if u_init is None:
+                    u_init = torch.rand(B, dtype=torch.float64, device=dev, generator=generator).cpu()
+                init = min(int(float(u_init[b]) * N), N - 1)
+            init = int(init)
+            if not 0 <= init < N:
+                raise ValueError(f"scannet_train_batch: room {b}: init_idx {init} out of range")
+            crop = _crop_nearest_i32(p[sel.long()], init, voxel_max)[1]
+        elif not variable:
+            pad = per_room["pad"][b]
+            pad = (torch.randint(N, (voxel_max - N,), generator=generator, device=dev) if pad is None
+                   else torch.as_tensor(pad).to(dev))
+            if pad.shape != (voxel_max - N,) or (pad.numel() and bool(((pad < 0) | (pad >= N)).any())):
+                raise ValueError(f"scannet_train_batch: room {b}: pad must hold {voxel_max - N} indices below {N}")
+            crop = torch.cat([torch.arange(N, device=dev), pad.long()]).int()
+        n_out = int(crop.shape[0]) if crop is not None else N
+        perm = per_room["perm"][b]
+        perm = torch.randperm(n_out, generator=generator, device=dev) if perm is None else torch.as_tensor(perm).to(dev)
+        if perm.shape != (n_out,) or bool(((perm < 0) | (perm >= n_out)).any()):
+            raise ValueError(f"scannet_train_batch: room {b}: perm must be a permutation of {n_out}")
+        plans.append((p, sel, crop, perm.int().contiguous(), n_out, beg))
+        beg += sizes[b]
+    n_out = plans[0][4]
+    if any(pl[4] != n_out for pl in plans):
+        raise ValueError("scannet_train_batch: the rooms came out with different sizes %s (variable=True); the collate "
+                         "stacks them" % [pl[4] for pl in plans])
+    out = {"pos": torch.empty(B, n_out, 3, dtype=torch.float32, device=dev),
+           "x": torch.empty(B, n_out, 3, dtype=torch.float32, device=dev),
+           "heights": torch.empty(B, n_out, 1, dtype=torch.float32, device=dev),
+           "y": torch.empty(B, n_out, dtype=torch.int64, device=dev)}
+    lib = _lib.load()
+    P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        for b, (p, sel, crop, perm, _, beg) in enumerate(plans):
+            y = rooms[b][2].reshape(-1).to(torch.int64).contiguous()
+            xr = x[beg:beg + sizes[b]]
+            _lib.check(lib.amc3d_scannet_crop_tail(n_out, int(gravity_dim), P(p), P(xr), P(y), P(sel), P(crop), P(perm),
+                                                   P(out["pos"][b]), P(out["x"][b]), P(out["heights"][b]), P(out["y"][b]),
+                                                   _stream(p)), "scannet_crop_tail")
+    return out

@@ -361,6 +361,14 @@ int amc3d_voxel_select(int nvox, const int *start, const int *count, const int *
 size_t amc3d_crop_nearest_workspace_bytes(int n);
 int amc3d_crop_nearest(int n, const float *coord, int init_idx, int keep, float *d2, int *crop_idx, void *workspace,
                        size_t workspace_bytes, void *stream);
+/* float64 coordinates (ScanNet: np.dot(pos_f32, R_f64) makes the rooms float64 before crop_pc): the same hash of
+ * floor(coord / voxel_size), and d2 (n) double = ((dx^2+dy^2)+dz^2) in double, sorted on its 64-bit pattern.  voxelize_f64
+ * takes amc3d_voxelize_workspace_bytes(n). */
+int amc3d_voxelize_f64(int n, const double *coord, double voxel_size, unsigned long long *key, int *idx_sort, int *voxel_idx,
+                       int *start, int *count, int *nvox, void *workspace, size_t workspace_bytes, void *stream);
+size_t amc3d_crop_nearest_f64_workspace_bytes(int n);
+int amc3d_crop_nearest_f64(int n, const double *coord, int init_idx, int keep, double *d2, int *crop_idx, void *workspace,
+                           size_t workspace_bytes, void *stream);
 
 /* ---- neighbourhood aggregation with one grouped conv: "convolve first, gather after" ---------------------------------
  * LocalAggregation.forward / single-layer SetAbstraction.forward (openpoints/models/backbone/pointnext_AA.py:57-63,
@@ -632,6 +640,30 @@ int amc3d_augment_clouds(int b, int n, int gravity_dim, float jitter_sigma, floa
                          const float *color, const float *noise, const float *params, const float *color_mean,
                          const float *color_std, float *pos_out, float *x_out, float *heights, void *workspace,
                          size_t workspace_bytes, void *stream);
+
+/* ---- ScanNet training input for a batch of RAW rooms (dataset/scannetv2/scannet.py:140-176: colours (feat + 1) * 127.5, the
+ * chain RandomRotateZ, RandomScale, ChromaticAutoContrast, RandomDropFeature, NumpyChromaticNormalize -- transforms/
+ * point_transform_cpu.py:43-92,192-209,304-332 -- on the whole room, then crop_pc and `heights`).  Rooms are ragged: points
+ * concatenated, offsets (b+1) int64.  The random draws are the caller's: params (b,16) doubles per room = {rot[9] row-major
+ * (pos' = pos @ rot), scale[3] (scale * mirror), contrast 0/1, w_keep = f32(1 - blend), w_contrast = f32(blend), drop 0/1}.
+ * room_stats: stats (b,8) floats = {lo[3], hi[3] of the colours, cmax = max of the colours after contrast and drop (NaN when
+ * one is NaN, as numpy's max()), unused} -- three launches, kStatBlocks workgroups per room.
+ * transform_rooms: coord (total,3) fp32, feat (total,3) fp32 in [-1, 1] -> pos_out (total,3) DOUBLE (np.dot's dgemm order:
+ * fma(p2, R[2,j], fma(p1, R[1,j], p0 * R[0,j])), then * scale[j]), x_out (total,3) fp32 = (colour [/ 255 if cmax > 1] -
+ * mean) / std.  One launch.
+ * crop_tail: one room (one launch): slot k <- point sel[crop[perm[k]]] (crop / perm NULL: identity) of the room's float64
+ * coord (already shifted to its min corner for the voxel grid), minus the cropped cloud's float64 min corner, cast to fp32 ->
+ * pos_out (n,3), x_out (n,3), heights (n) = pos_out[:, gravity_dim] (the float32 minimum of that column is exactly 0), y_out
+ * (n) int64: the room's slot of the collated batch. */
+size_t amc3d_scannet_stats_workspace_bytes(int b);
+int amc3d_scannet_room_stats(int b, const long long *offsets, const float *feat, const double *params, float *stats,
+                             void *workspace, size_t workspace_bytes, void *stream);
+int amc3d_scannet_transform_rooms(int b, long long total, const long long *offsets, const float *coord, const float *feat,
+                                  const double *params, const float *stats, const float *color_mean, const float *color_std,
+                                  double *pos_out, float *x_out, void *stream);
+int amc3d_scannet_crop_tail(int n, int gravity_dim, const double *coord, const float *x, const long long *y, const int *sel,
+                            const int *crop, const int *perm, float *pos_out, float *x_out, float *heights, long long *y_out,
+                            void *stream);
 
 #ifdef __cplusplus
 }
