@@ -233,13 +233,44 @@ class GraphPipeline:
         from . import schedule
         self.ev_done = [torch.cuda.Event() for _ in range(schedule.SETS)]
         self._done_recorded = [False] * schedule.SETS
-        self._build(example)
+        self._static_grads = None
+        self._lr_dev = self._device_learning_rates()
+        try:
+            self._build(example)
+        finally:
+            self._float_learning_rates()
         if snapshot is not None:
             self._restore(snapshot)
         self.tick = 0
         self._set_valid = [False] * schedule.SETS
         self._lane_valid = [[False] * J, [False] * J]
         self._lr = tuple(g["lr"] for g in optimizer.param_groups)
+
+    # -- learning rates of a captured torch optimizer ------------------------------------------------------------------
+    def _device_learning_rates(self):
+        """torch's capturable optimizers bake a Python-float lr into the captured launch and read a tensor lr from device
+        memory at every replay: give every group a 0-dim device tensor for the warm-up steps and the capture (FusedAdamW keeps
+        its rates in its own device table; an optimizer that is not captured reads the dict at every eager step).
+        -> one tensor per group, or None"""
+        if type(self.opt).__name__ == "FusedAdamW" or not all(g.get("capturable", False) for g in self.opt.param_groups):
+            return None
+        held, self._lr_given = [], [g["lr"] for g in self.opt.param_groups]
+        for g in self.opt.param_groups:
+            lr = g["lr"]
+            if not (torch.is_tensor(lr) and lr.device == self.dev):  # (a device tensor of the caller's is read as it is)
+                lr = torch.tensor(float(lr), dtype=torch.float32, device=self.dev)
+            held.append(lr)
+            g["lr"] = lr
+        return held
+
+    def _float_learning_rates(self):
+        """after the capture the groups hold plain floats again (what schedulers write and loggers read): the graphs read
+        the tensors kept in self._lr_dev, which _critical_path fills whenever a group's value changed"""
+        if self._lr_dev is None:
+            return
+        for g, t, given in zip(self.opt.param_groups, self._lr_dev, self._lr_given):
+            if g["lr"] is t:
+                g["lr"] = given
 
     # -- pieces of a step --------------------------------------------------------------------------------------------
     def _fps_all(self, batch):
@@ -422,6 +453,7 @@ class GraphPipeline:
             static = [torch.zeros_like(p) if h else None for p, h in zip(self.params, has_grad)]  # (who gets one: the warm-up steps)
             for p, g0 in zip(self.params, static):
                 p.grad = g0
+            self._static_grads = static  # kept: run() points .grad at them again (torch's zero_grad() between two epochs drops them)
             if fused:
                 self.opt.prepare()  # the tensor table of the update, built outside the capture
         self.g_feat = []
@@ -499,6 +531,11 @@ class GraphPipeline:
             if lr != self._lr:  # a scheduler stepped: the captured update reads its learning rates from device memory
                 if hasattr(self.opt, "sync_hyperparameters"):
                     self.opt.sync_hyperparameters()
+                else:  # a captured torch optimizer: the tensors its launch reads (a float the scheduler wrote stays in the dict)
+                    assert self._lr_dev is not None, "a captured update whose learning rates are not in device memory"
+                    for g, t in zip(self.opt.param_groups, self._lr_dev):
+                        if g["lr"] is not t:
+                            t.fill_(float(g["lr"]))
                 self._lr = lr
         self.g_feat[v0].replay()
         if self.update_in_feature_graph:
@@ -570,6 +607,12 @@ class GraphPipeline:
         them on the current stream before taking the next-but-one result).  Ends when every batch has trained; an endless
         iterable makes an endless generator (bench.py)."""
         it = iter(batches)
+        if self._static_grads is not None:
+            # the feature graphs write the gradients into these tensors and the update, captured or eager, reads .grad: whatever
+            # the caller did to .grad since the capture (torch's zero_grad() sets it to None), it is these tensors again
+            for p, g0 in zip(self.params, self._static_grads):
+                if p.grad is not g0:
+                    p.grad = g0
         # start at a launch tick with empty buffers
         from . import schedule
         self.tick = 0

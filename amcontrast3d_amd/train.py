@@ -161,6 +161,10 @@ def _run_epoch(model, train_loader, criterion, optimizer, scheduler, scaler, epo
                     odd.append(b)
         cur = torch.cuda.current_stream(device)
         main.wait_stream(cur)
+        # `first` was produced on the caller's stream (host-to-device copies, feature assembly) and is read by the geometry
+        # queue's copy into the pipeline's buffers: that queue waits for it.  (Its tensors stay referenced by `first` until
+        # this function returns, after `cur` has waited for both queues: the allocator cannot hand them out in between.)
+        pipe.s_geo.wait_stream(cur)
         with torch.cuda.stream(main):
             in_graph = pipe.tail is not None
             if in_graph:  # the captured step keeps the books (warm-up passes and earlier epochs have written to them)
@@ -181,6 +185,11 @@ def _run_epoch(model, train_loader, criterion, optimizer, scheduler, scaler, epo
                 cm.add_counts(book["cm"], book["invalid"])
                 loss_sum.add_(book["loss"][:loss_sum.numel()])
         cur.wait_stream(main)
+        cur.wait_stream(pipe.s_geo)  # (the odd batches were produced on the geometry queue)
+        if odd:
+            # .grad is the pipeline's static tensor and holds the last replay's gradient: the loop below accumulates into it
+            # (in place: GraphPipeline.run points .grad at the same tensors again in the next epoch either way)
+            optimizer.zero_grad(set_to_none=False)
         batches = iter(odd)
     elif head is not None and prefetch_depth > 0 and not use_amp:
         batches = GeometryPrefetcher(batches, model, head, cfg.num_classes, cfg.ignore_index, cfg.ambiguity_args,
@@ -189,7 +198,9 @@ def _run_epoch(model, train_loader, criterion, optimizer, scheduler, scaler, epo
     for data in batches:
         num_iter += 1
         target = data["y"]
-        with torch.autocast("cuda", enabled=use_amp):
+        # use_amp is the bf16 route (ops.mixed_precision(): fp32 tensors between the kernels, bf16 MFMA operands inside them);
+        # torch's default, float16, would hand the native kernels half tensors, which they refuse
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_amp):
             logits, loss, parts = step_loss(data, target)
         if use_amp:
             scaler.scale(loss).backward()
