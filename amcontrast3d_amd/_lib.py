@@ -19,14 +19,11 @@ SIGNATURES = {
     "amc3d_last_error": (ctypes.c_char_p, []),
     "amc3d_stream_create_dedicated": (_i, [ctypes.POINTER(ctypes.c_void_p)]),
     "amc3d_stream_create_masked": (_i, [_vp, _i, _i]),
-    "amc3d_stream_create_cu_mask": (_i, [_vp, _vp, _i]),
-    "amc3d_probe_xcc_ids": (_i, [_i, _vp, _vp]),
     "amc3d_reserve_scratch": (_i, [_i, _vp, _vp]),
     "amc3d_stream_destroy": (_i, [_vp]),
     "amc3d_grid_search_workspace_bytes": (_sz, [_i, _i, _i]),
     "amc3d_ball_query": (_i, [_i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_group_points": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "amc3d_scatter_workspace_bytes": (_sz, [_i, _i, _i]),
     "amc3d_group_points_grad": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_gather_points": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "amc3d_gather_points_grad": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),

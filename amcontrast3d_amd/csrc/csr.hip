@@ -12,7 +12,6 @@
 //   amc3d_grouped_conv_bn_backward_csr   the collapse pass of the first SetAbstraction layer as a gather
 #include "cub_kernel_memset.h"  // hipCUB with its memsets as kernels (graph-safe)
 
-#include <stdlib.h>
 
 #include "common.h"
 
@@ -46,90 +45,6 @@ __global__ void csr_keys_kernel(int n, long P, long E, const int *__restrict__ i
     const int id = idx[e];
     key[e] = (unsigned)(b * n + (id >= 0 && id < n ? id : 0));
     val[e] = (int)(e - b * P);
-}
-
-// ---- the same lists by a counting sort (AMC3D_CSR_COUNTING_SORT=1; 0.43 ms per step against the radix sort's 0.36) ---------
-// Written when the radix sort turned out to be unsafe inside captured graphs (its hipMemsetAsync calls: cub_kernel_memset.h, which
-// is what fixed it); kept as the alternative that needs no library sort.
-__global__ void csr_degree_kernel(int n, long P, long E, const int *__restrict__ idx, int *__restrict__ deg)
-{
-    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    const long b = e / P;
-    const int id = idx[e];
-    atomicAdd(deg + b * n + (id >= 0 && id < n ? id : 0), 1);
-}
-
-__global__ void csr_fill_kernel(int n, long P, long E, const int *__restrict__ idx, const int *__restrict__ rev_start,
-                                int *__restrict__ cursor, int *__restrict__ rev_edge)
-{
-    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    const long b = e / P;
-    const int id = idx[e];
-    const long g = b * n + (id >= 0 && id < n ? id : 0);
-    rev_edge[rev_start[g] + atomicAdd(cursor + g, 1)] = (int)(e - b * P);
-}
-
-// every list in ascending order of its positions (distinct): lists of up to CSR_SORT_SHORT entries by insertion in place,
-// longer ones (hubs of a ball query) by ranks -- a wave per list, through `temp` -- so that the gathers that walk the lists
-// sum in a fixed order whatever order the fill's atomics produced
-constexpr int CSR_SORT_SHORT = 16;
-__global__ void csr_order_kernel(long G, const int *__restrict__ rev_start, int *__restrict__ rev_edge)
-{
-    const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= G) return;
-    const int e0 = rev_start[g], d = rev_start[g + 1] - e0;
-    if (d < 2 || d > CSR_SORT_SHORT) return;
-    // the list in registers, padded with INT_MAX, through a bitonic network (static indices: no scratch, no dependent round trips
-    // to global memory -- an in-place insertion sort took 250-340 us per stage: a chain of up to d^2 / 2 loads and stores)
-    int r[CSR_SORT_SHORT];
-#pragma unroll
-    for (int i = 0; i < CSR_SORT_SHORT; ++i) r[i] = i < d ? rev_edge[e0 + i] : 0x7fffffff;
-#pragma unroll
-    for (int k = 2; k <= CSR_SORT_SHORT; k <<= 1)
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1)
-#pragma unroll
-            for (int i = 0; i < CSR_SORT_SHORT; ++i) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const bool up = (i & k) == 0;
-                    const int lo = min(r[i], r[l]), hi = max(r[i], r[l]);
-                    r[i] = up ? lo : hi;
-                    r[l] = up ? hi : lo;
-                }
-            }
-#pragma unroll
-    for (int i = 0; i < CSR_SORT_SHORT; ++i)
-        if (i < d) rev_edge[e0 + i] = r[i];
-}
-
-__global__ __launch_bounds__(256) void csr_order_long_kernel(long G, const int *__restrict__ rev_start, int *__restrict__ rev_edge,
-                                                             int *__restrict__ temp)
-{
-    const long g = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (g >= G) return;
-    const int e0 = rev_start[g], d = rev_start[g + 1] - e0;
-    if (d <= CSR_SORT_SHORT) return;  // (wave-uniform)
-    if (d <= 64) {  // one entry per lane, ranks by broadcasts inside the wave: no round trip through memory
-        const int v = lane < d ? rev_edge[e0 + lane] : 0x7fffffff;
-        int r = 0;
-        for (int y = 0; y < d; ++y) r += __shfl(v, y, 64) < v;
-        if (lane < d) rev_edge[e0 + r] = v;  // (every lane has loaded before any stores: the shuffles above are the barrier)
-        return;
-    }
-    const int *l = rev_edge + e0;
-    for (int x = lane; x < d; x += 64) {  // rank = number of smaller entries (the positions of a list are distinct)
-        const int v = l[x];
-        int r = 0;
-        for (int y = 0; y < d; ++y) r += l[y] < v;
-        temp[e0 + r] = v;
-    }
-    // (the wave reads back what its own lanes stored: the stores have reached L2 after the fence, and nothing of temp is in this CU's L1)
-    __threadfence();
-    for (int x = lane; x < d; x += 64) rev_edge[e0 + x] = temp[e0 + x];
 }
 
 // rev_start[g] = first sorted edge with key >= g (g = 0 .. G inclusive): binary search, no atomics
@@ -207,19 +122,19 @@ __device__ __forceinline__ float csr_bn(float x, float mean, float invstd, float
 //   q[g][c] = sum_e d(e, c),  d = dx1_pm[position e][c] * [relu: bn(G[g][c] + W_dp[c] . dp_e) > 0]
 //   partial sums per channel {sum d, sum d xhat, sum d dp_j}.  dx1_pm is the POSITION-major gradient (b, P, C).
 // grid (point groups, channel chunks of 64, 1); a workgroup takes PTS consecutive source points per wave-group
-// Workgroup shape (BS threads, MINW = the compiler's waves-per-SIMD target).  The software pipeline below wants ~142 registers;
-// a 512-thread workgroup is two waves per SIMD, so at 142 registers only ONE fits a CU (two would need four waves per SIMD =
-// 128 registers): 8 waves per CU for a kernel that is a chain of memory round trips -- found at the end of round 3 by listing
-// registers x workgroup size for every kernel (the occupancy the compiler prints, 3, is per wave, not per workgroup).
-// AMC3D_CSR_SHAPE (measured on PointNeXt-S' four launches, real room-like neighbourhoods, 4096 workgroups; SA1 / SA2-4 avg):
-//   0: this kernel, 512 threads, 142 registers -> 8 waves per CU                                   210 / 61 us  (step 6.10 ms)
-//   (512 threads capped at 128 registers -- 15 spilled, 16 waves per CU -- and the shfl kernel capped at 96: slower, removed)
-//   2: 256 threads, 142 registers, three per CU -> 12 waves per CU                                  (synthetic lists: 182 -> 128)
-//   3: csr_collapse_shfl_kernel: records distributed over the lanes, 104 registers -> 16 waves     164 / 46 us  (step 5.985)
-//   5: csr_collapse_stream_kernel: the group's edge range as one stream                            153 / 55 us  (step 6.008)
-//   6 (default): the stream kernel below 64 channels, the shfl kernel from 64 up                    153 / 46 us  (step 5.97)
-template <int CT, int CSR_BS, int MINW>
-__global__ __launch_bounds__(CSR_BS, MINW) void csr_collapse_kernel(int C, int n, long P, long G, int relu, const float *__restrict__ dx1_pm,
+// Workgroup shape: the software pipeline below wants ~142 registers.  A 512-thread workgroup is two waves per SIMD, so at 142
+// registers only ONE fits a CU (two would need four waves per SIMD = 128 registers): 8 waves per CU for a kernel that is a chain
+// of memory round trips -- found at the end of round 3 by listing registers x workgroup size for every kernel (the occupancy
+// the compiler prints, 3, is per wave, not per workgroup).  256 threads: three per CU, 12 waves.
+// Measured on PointNeXt-S' four launches, real room-like neighbourhoods, 4096 workgroups; SA1 / SA2-4 avg:
+//   this kernel with 512 threads                                                                   210 / 61 us  (step 6.10 ms)
+//   (512 threads capped at 128 registers -- 15 spilled, 16 waves per CU -- and the shfl kernel capped at 96: slower)
+//   csr_collapse_shfl_kernel: records distributed over the lanes, 104 registers -> 16 waves        164 / 46 us  (step 5.985)
+//   csr_collapse_stream_kernel: the group's edge range as one stream                               153 / 55 us  (step 6.008)
+//   what csr_collapse launches: the stream kernel below 64 channels, the shfl kernel from 64 up    153 / 46 us  (step 5.97)
+constexpr int CSR_BS = 256;  // threads of every collapse kernel's workgroup
+template <int CT>
+__global__ __launch_bounds__(CSR_BS, 1) void csr_collapse_kernel(int C, int n, long P, long G, int relu, const float *__restrict__ dx1_pm,
                                                            const float *__restrict__ g_pm, const int *__restrict__ rev_start,
                                                            const int *__restrict__ rev_edge, const float *__restrict__ dp,
                                                            const float *__restrict__ w_dp, const float *__restrict__ mean,
@@ -726,27 +641,6 @@ AMC_API int amc3d_group_csr(int b, int n, int npoints, int nsample, const int *i
         return bad_arg("amc3d_group_csr: bad argument");
     hipStream_t stream = (hipStream_t)stream_;
     char *w = (char *)workspace;
-    {   // counting sort on request, wherever the workspace holds its arrays: G + 1 <~ E
-        size_t scan_temp = 0;
-        (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_temp, (const int *)nullptr, (int *)nullptr, (int)(G + 1));
-        const size_t need = 2 * csr_align((size_t)(G + 1) * 4) + csr_align(scan_temp) + csr_align((size_t)E * 4);
-        static const bool counting = getenv("AMC3D_CSR_COUNTING_SORT") != nullptr;
-        if (counting && need <= workspace_bytes) {
-            int *deg = (int *)w; w += csr_align((size_t)(G + 1) * 4);
-            int *cursor = (int *)w; w += csr_align((size_t)(G + 1) * 4);
-            void *st = (void *)w; w += csr_align(scan_temp);
-            int *tmp = (int *)w;
-            if (int s0 = fill_i32(deg, 0, (size_t)(cursor - deg) + G + 1, stream)) return s0;  // deg and cursor, one launch
-            hipLaunchKernelGGL(csr_degree_kernel, dim3(div_up(E, 256)), dim3(256), 0, stream, n, P, E, idx, deg);
-            const hipError_t es = hipcub::DeviceScan::ExclusiveSum(st, scan_temp, (const int *)deg, rev_start, (int)(G + 1), stream);
-            if (es != hipSuccess) { set_error("amc3d_group_csr: scan: %s", hipGetErrorString(es)); return (int)es; }
-            hipLaunchKernelGGL(csr_fill_kernel, dim3(div_up(E, 256)), dim3(256), 0, stream, n, P, E, idx, (const int *)rev_start, cursor,
-                               rev_edge);
-            hipLaunchKernelGGL(csr_order_kernel, dim3(div_up(G, 256)), dim3(256), 0, stream, G, (const int *)rev_start, rev_edge);
-            hipLaunchKernelGGL(csr_order_long_kernel, dim3(div_up(G, 4)), dim3(256), 0, stream, G, (const int *)rev_start, rev_edge, tmp);
-            return launch_status("amc3d_group_csr");
-        }
-    }
     unsigned *key = (unsigned *)w; w += csr_align((size_t)E * 4);
     unsigned *skey = (unsigned *)w; w += csr_align((size_t)E * 4);
     int *val = (int *)w; w += csr_align((size_t)E * 4);
@@ -875,19 +769,12 @@ AMC_API int amc3d_group_moments_csr(int b, int n, int npoints, int nsample, cons
     return launch_status("amc3d_group_moments_csr");
 }
 
-static int csr_shape()
-{
-    static const int v = getenv("AMC3D_CSR_SHAPE") ? atoi(getenv("AMC3D_CSR_SHAPE")) : 6;
-    return v;
-}
-static int csr_bs() { return csr_shape() >= 2 ? 256 : 512; }
-
 static int csr_pts_per_group(long G, int groups_per_wg)
 {
     // ~4096 workgroups (round 3; 2048 of 1024 threads before): a group walks its points one after the other, so what counts is
     // FEW points per group -- 3-6 at SA1 instead of 12 -- while the number of partial sums (one per workgroup) stays where the
     // finalize kernel reads them quickly (2048: 13 us per finalize instead of 19, but the step is 0.05 ms slower; 8192: slower)
-    static const long wgs = getenv("AMC3D_CSR_WGS") ? atol(getenv("AMC3D_CSR_WGS")) : 4096L;
+    const long wgs = 4096;
     long per = (G + wgs * groups_per_wg - 1) / (wgs * groups_per_wg);
     return (int)(per < 1 ? 1 : per);
 }
@@ -896,7 +783,7 @@ namespace amc {
 size_t csr_partials(int b, int cout, int n)
 {
     const int ct = cout < 64 ? cout : 64;
-    const int groups = csr_bs() / ct;
+    const int groups = CSR_BS / ct;
     const long G = (long)b * n;
     const int per = csr_pts_per_group(G, groups);
     return (size_t)div_up(G, (long)groups * per);
@@ -914,31 +801,29 @@ int csr_collapse(int b, int cout, int n, int npoints, int nsample, int relu, con
 {
     const long P = (long)npoints * nsample, G = (long)b * n;
     const int ct = cout < 64 ? cout : 64;
-    const int bs = csr_bs(), shape = csr_shape();
-    const int groups = bs / ct;
+    const int groups = CSR_BS / ct;
     const int per = csr_pts_per_group(G, groups);
     const int wgs = div_up(G, (long)groups * per);
     *nparts = wgs;
-#define AMC_CSR_(CTV, BS, MINW)                                                                                               \
-    hipLaunchKernelGGL((csr_collapse_kernel<CTV, BS, MINW>), dim3(wgs, cout / ct), dim3(BS), 0, stream, cout, n, P, G, relu,    \
-                       dx1_pm, g_pm, rev_start, rev_edge, dp, w_dp, mean, invstd, gamma, beta, Q, partial, per,                \
-                       (const float4 *)rev_dp)
+    // the stream kernel below 64 channels, the shfl kernel from 64 up (or for long groups); without the per-edge dp stream
+    // (rev_dp) the gather kernel that reads dp through the edge lists
 #define AMC_CSR(CTV)                                                                                                          \
     do {                                                                                                                      \
-        if ((shape == 5 || (shape == 6 && CTV < 64)) && rev_dp && per <= CSR_STREAM_PMAX)                                     \
-            hipLaunchKernelGGL((csr_collapse_stream_kernel<CTV>), dim3(wgs, cout / ct), dim3(256), 0, stream, cout, P, G, relu, \
-                               dx1_pm, g_pm, rev_start, w_dp, mean, invstd, gamma, beta, Q, partial, per,                      \
-                               (const float4 *)rev_dp);                                                                       \
-        else if (shape >= 3 && rev_dp)                                                                                        \
-            hipLaunchKernelGGL((csr_collapse_shfl_kernel<CTV>), dim3(wgs, cout / ct), dim3(256), 0, stream, cout, n, P, G,  \
+        if (CTV < 64 && rev_dp && per <= CSR_STREAM_PMAX)                                                                     \
+            hipLaunchKernelGGL((csr_collapse_stream_kernel<CTV>), dim3(wgs, cout / ct), dim3(CSR_BS), 0, stream, cout, P, G,  \
                                relu, dx1_pm, g_pm, rev_start, w_dp, mean, invstd, gamma, beta, Q, partial, per,                \
                                (const float4 *)rev_dp);                                                                       \
-        else if (shape >= 2) AMC_CSR_(CTV, 256, 1);                                                                           \
-        else AMC_CSR_(CTV, 512, 1);                                                                                           \
+        else if (rev_dp)                                                                                                      \
+            hipLaunchKernelGGL((csr_collapse_shfl_kernel<CTV>), dim3(wgs, cout / ct), dim3(CSR_BS), 0, stream, cout, n, P, G, \
+                               relu, dx1_pm, g_pm, rev_start, w_dp, mean, invstd, gamma, beta, Q, partial, per,                \
+                               (const float4 *)rev_dp);                                                                       \
+        else                                                                                                                  \
+            hipLaunchKernelGGL((csr_collapse_kernel<CTV>), dim3(wgs, cout / ct), dim3(CSR_BS), 0, stream, cout, n, P, G,      \
+                               relu, dx1_pm, g_pm, rev_start, rev_edge, dp, w_dp, mean, invstd, gamma, beta, Q, partial, per,  \
+                               (const float4 *)rev_dp);                                                                       \
     } while (0)
     switch (ct) { case 8: AMC_CSR(8); break; case 16: AMC_CSR(16); break; case 32: AMC_CSR(32); break; default: AMC_CSR(64); }
 #undef AMC_CSR
-#undef AMC_CSR_
     return launch_status("csr_collapse");
 }
 }  // namespace amc

@@ -18,7 +18,6 @@
 // MFMA operand convention (v_mfma_f32_32x32x2_f32): lane l supplies A[i = l & 31][kk = l >> 5] and
 // B[kk = l >> 5][j = l & 31]; step t of a chunk pairs k = t (lanes 0-31) with k = 8 + t (lanes 32-63) in both
 // operands -- any pairing is a valid order of the K sum as long as A and B agree.
-#include <stdlib.h>
 
 #include "common.h"
 
@@ -305,9 +304,8 @@ bool gemm_conv_pays(int cin, int cout) { return cin >= 64 && cout >= 64; }
 // summed in a fixed order: deterministic, and the chip is filled.
 static int gemm_short_splits(int b, int M, long N, long K)
 {
-    static const bool off = getenv("AMC3D_NO_SPLIT_K") != nullptr;
     const long tiles = (long)div_up(M, GM_T) * div_up(N, GM_T) * b;
-    if (off || tiles >= 192 || K < 128) return 1;
+    if (tiles >= 192 || K < 128) return 1;
     long s = 512 / tiles;
     if (s > 8) s = 8;
     if (s > K / 64) s = K / 64;  // at least four chunks per split
@@ -387,17 +385,13 @@ int gemm_conv_backward_data(int b, int cin, int cout, long P, const float *dy, c
     return launch_status("gemm_conv_backward_data");
 }
 
-static bool gw_streaming(int b, int cin, int cout, long P)
-{
-    static const bool off = getenv("AMC3D_NO_STREAMING_WGRAD") != nullptr;
-    return !off && P % 4 == 0 && P >= 4 * GW_KC;
-}
+static bool gw_streaming(int b, int cin, int cout, long P) { return P % 4 == 0 && P >= 4 * GW_KC; }
 
 static int gemm_wgrad_splits(int b, int cin, int cout, long P, long *kper)
 {
     if (gw_streaming(b, cin, cout, P)) {
         // ~512 workgroups (two per CU), at least `minc` chunks each; a range is a whole number of chunks
-        static const long minc = getenv("AMC3D_GW_MINCHUNKS") ? atol(getenv("AMC3D_GW_MINCHUNKS")) : 4;
+        const long minc = 4;
         const int tn = cin <= 64 ? 64 : 128;
         const long tiles = (long)div_up(cout, GW_TM) * div_up(cin, tn);
         long s = 512 / (tiles * b);
@@ -411,7 +405,7 @@ static int gemm_wgrad_splits(int b, int cin, int cout, long P, long *kper)
     // enough workgroups to fill the chip, at least 256 positions each
     const long tiles = (long)div_up(cout, GM_T) * div_up(cin, GM_T);
     long s = 1024 / (tiles * b);
-    static const long mink = getenv("AMC3D_WGRAD_MINK") ? atol(getenv("AMC3D_WGRAD_MINK")) : 64;  // (short layers: 375 positions)
+    const long mink = 64;  // (short layers: 375 positions)
     const long cap = P / mink > 1 ? P / mink : 1;
     if (s > cap) s = cap;
     if (s < 1) s = 1;

@@ -16,7 +16,6 @@
 // later (the root only decreases), so the heap sees the same insert sequence as
 // the reference's sequential scan.  The 16 waves of a workgroup share LDS tiles
 // of the support cloud.
-#include <stdlib.h>
 
 #include "common.h"
 
@@ -1194,15 +1193,14 @@ AMC_API int amc3d_knnquery(int m, int nsample, int n, int nbatch, const float *x
     char *base = (char *)workspace;
     // cell edge = scale x p80 of the ceil(k/sub)-th neighbour distance among every sub-th support point; swept on
     // the loss's seven searches (scratch/knn_sweep.sh): speed only, any value gives the same results
-    static const int kg_sub = getenv("AMC3D_KG_SUB") ? atoi(getenv("AMC3D_KG_SUB")) : 4;
-    static const int kg_extra = getenv("AMC3D_KG_EXTRA") ? atoi(getenv("AMC3D_KG_EXTRA")) : 0;
-    static const float kg_scale = getenv("AMC3D_KG_SCALE") ? (float)atof(getenv("AMC3D_KG_SCALE")) : 0.7f;
+    const int kg_sub = 4;
+    const float kg_scale = 0.7f;
     if (reuse_grid) {
         // the workspace still holds the grid of this very support set (xyz, offset) from an earlier call: its cell
         // size was calibrated for that call's k, which only steers speed.  Only the replay counter is reset.
         hipLaunchKernelGGL(kg_init_kernel, dim3(1), dim3(64), 0, stream, (int *)(base + w.bbox), (int *)(base + w.fb_count));
     } else if (int st = kg_build(w, base, n, m, nbatch, xyz, new_xyz, offset, new_offset,
-                                 (nsample + kg_sub - 1) / kg_sub + kg_extra, kg_sub, kg_scale, 0.f, stream)) {
+                                 (nsample + kg_sub - 1) / kg_sub, kg_sub, kg_scale, 0.f, stream)) {
         return st;
     }
     GridParams *gp = (GridParams *)(base + w.params);

@@ -23,7 +23,6 @@
 // M-sized and N-sized sums.  df = W_f^T dG and dW_f = dG f^T are the pointwise conv's backward on N points.
 // The geometry moments depend on coordinates only and are part of the geometry plan (computed ahead, shared by all
 // blocks of a stage).
-#include <stdlib.h>
 
 #include "common.h"
 
@@ -707,9 +706,8 @@ static int lagg_stats_tiles(int b, int C, int n)
 // on the coarse stages of PointNeXt-L)
 static int lagg_scatter_tiles(int b, int C, int M)
 {
-    static const bool off = getenv("AMC3D_LAGG_SCATTER_TILES4") != nullptr;
     const long wgs1 = (long)b * div_up(M, LAGG_MT) * div_up(C, LAGG_CT);
-    return (wgs1 <= 8192 && !off) ? 1 : LAGG_TILES;
+    return wgs1 <= 8192 ? 1 : LAGG_TILES;
 }
 
 static size_t lagg_partial_bytes(int b, int C, int n, int M)

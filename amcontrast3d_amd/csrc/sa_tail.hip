@@ -23,7 +23,6 @@
 // themselves: the first neighbour (ascending index, torch.max's rule) attaining the maximum of the normalised values --
 // exactly the element the reference's max-pool routes the gradient to, also when two raw values round to the same
 // normalised value or a ReLU clamps several to zero.  BN1's own backward (from dx1) stays with bn.hip.
-#include <stdlib.h>
 
 #include "common.h"
 
@@ -816,11 +815,7 @@ static bool sat_aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 static bool sat_supported(int C1, int C2, int K) { return K == 32 && C1 >= 2 && C1 <= SAT_MAX_C1 && C1 % 2 == 0 && C2 >= 1 && C2 <= SAT_MAX_C2; }
 // the recomputation costs 2-3x the layer's MFMA work: it pays while the layer is HBM-bound (measured on MI355X:
 // 32 -> 64 channels faster fused, 64 -> 128 faster layer by layer, also with the single forward pass)
-static bool sat_pays(int C1, int C2)
-{
-    static const long lim = getenv("AMC3D_SAT_PAYS") ? atol(getenv("AMC3D_SAT_PAYS")) : 32 * 64;
-    return (long)C1 * C2 <= lim;
-}
+static bool sat_pays(int C1, int C2) { return (long)C1 * C2 <= 32 * 64; }
 
 static size_t sat_lds(int C1, int C2, int mode)
 {
@@ -855,8 +850,7 @@ AMC_API int amc3d_sa_tail_pays(int C1, int C2) { return sat_pays(C1, C2) ? 1 : 0
 
 static bool sat_alg_supported(int C1, int C2)
 {
-    static const bool off = getenv("AMC3D_SAT_RECOMPUTE_BACKWARD") != nullptr;
-    return !off && C1 % 4 == 0 && C2 % 4 == 0 && 256 % C2 == 0 && C2 <= 128 && ((long)C1 * C2) % 256 == 0 && C1 % (256 / C2) == 0 && (C1 * C2) / 256 <= 32;
+    return C1 % 4 == 0 && C2 % 4 == 0 && 256 % C2 == 0 && C2 <= 128 && ((long)C1 * C2) % 256 == 0 && C1 % (256 / C2) == 0 && (C1 * C2) / 256 <= 32;
 }
 
 static size_t sat_al(size_t n) { return (n + 255) & ~(size_t)255; }

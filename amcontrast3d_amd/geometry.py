@@ -228,13 +228,8 @@ def copy_into(dst, src):
     for graph replay).  Views (e.g. idx[:, 1:]) are copied through their storage like any tensor.
     The copies of one call go out as multi-tensor launches (one per dtype), not one launch per tensor: a plan holds
     ~40 tensors and the pipeline's rotate step copies four plans between two steps of the training stream."""
-    import os
     pairs = []
     _pairs(dst, src, pairs)
-    if os.environ.get("AMC3D_NO_FOREACH_COPY"):
-        for d, s in pairs:
-            d.copy_(s)
-        return
     by_dtype = {}
     for d, s in pairs:
         if d.is_contiguous() and s.is_contiguous() and d.dtype == s.dtype and d.shape == s.shape:

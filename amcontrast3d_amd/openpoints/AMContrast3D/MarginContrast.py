@@ -44,14 +44,12 @@ def plan_stage(n, i, stageACE_list, target, nstride, num_classes, ignore_index, 
     # the anchors the loss keeps (0 < a <= 1, :250-252) as a compact list for the fused contrast kernels
     anchors = ops.select_anchors(a) if a.is_cuda and a.dtype == torch.float32 else None
     # Reverse structure for the loss backward, so that it GATHERS every gradient row instead of scattering rows with float
-    # atomics (0.71 ms per step at the chip's float-atomic rate in round 2).  Default (round 3): the mutual-edge form --
-    # ~90 % of the k-NN edges are mutual and need no list at all (ops.contrast_mutual: a mutual bit per edge + reverse lists
-    # of the remaining tenth).  AMC3D_CONTRAST_CSR=1: round 2's reverse lists of ALL edges (0.79 ms of integer atomics on
-    # the geometry stream); AMC3D_CONTRAST_ATOMIC=1: the float-atomic form.
+    # atomics (0.71 ms per step at the chip's float-atomic rate in round 2): the mutual-edge form -- ~90 % of the k-NN
+    # edges are mutual and need no list at all (ops.contrast_mutual: a mutual bit per edge + reverse lists of the remaining
+    # tenth; round 2's reverse lists of ALL edges, ops.contrast_csr, cost 0.79 ms of integer atomics on the geometry stream).
+    # More than 64 neighbours: neither, the backward takes the float-atomic form.
     rev = mutual = None
-    if anchors is not None and os.environ.get("AMC3D_CONTRAST_CSR"):
-        rev = ops.contrast_csr(neighbor_idx, anchors)
-    elif anchors is not None and neighbor_idx.shape[1] <= 64 and not os.environ.get("AMC3D_CONTRAST_ATOMIC"):
+    if anchors is not None and neighbor_idx.shape[1] <= 64:
         # (one segment of more than k + 1 points: every list is full, membership follows from one distance comparison)
         d2 = neighbor_d2[..., 1:] if (torch.is_tensor(neighbor_d2) and neighbor_d2.dtype == torch.float32 and o.numel() == 1
                                       and neighbor_d2.shape[0] == neighbor_idx.shape[0] > neighbor_idx.shape[1] + 2) else None
@@ -163,7 +161,7 @@ class ContrastHead(nn.Module):
         # the (B*n, C) copy of pointnext_AA.py:518-519 is not made
         stage = stageACE_list[n][i]
         f_cm = stage.channel_major() if fused and hasattr(stage, 'channel_major') else None
-        if (f_cm is not None and not os.environ.get("AMC3D_LOSS_ROWS")
+        if (f_cm is not None
                 and ops.contrast_stage_supported_cm(f_cm, g.get('anchors'), g.get('rev'), g.get('mutual'))):
             loss = ops.contrast_stage_cm(f_cm, neighbor_idx, posmask, ambiguity_soft, ambiguity_args.mu, ambiguity_args.nu,
                                          ambiguity_args.temperature, g['anchors'], g['rev'], g['mutual'])

@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from ..layers import (CHANNEL_MAP, create_act, create_convblock1d, create_convblock2d, create_grouper,
-                      feature_propagation_first_block, gather_operation,
+                      feature_propagation_first_block,
                       furthest_point_sample, fused_first_block, fused_first_conv, fused_local_aggregation,
                       get_aggregation_feautres,
                       random_sample, run_convblocks,
@@ -40,13 +40,12 @@ def _moments(convs, feature_type, idx, dp, n_support, csr=None):
 def _csr(convs, feature_type, idx, n_support, dp=None):
     """reverse adjacency of the query for layers whose backward sums dense per-position gradients into the source points
     (the multi-layer SetAbstraction MLP of PointNeXt-S): gathers over sorted edge lists instead of float atomics"""
-    import os
-    if feature_type != 'dp_fj' or not idx.is_cuda or len(convs) < 2 or os.environ.get("AMC3D_NO_CSR"):
+    if feature_type != 'dp_fj' or not idx.is_cuda or len(convs) < 2:
         return None
     from amcontrast3d_amd import ops
     start, edge = ops.group_csr(idx, n_support)
     csr = {'start': start, 'edge': edge}
-    if dp is not None and dp.dtype == torch.float32 and not os.environ.get("AMC3D_NO_CSR_DP"):
+    if dp is not None and dp.dtype == torch.float32:
         csr['edge_dp'] = ops.group_csr_dp(idx, dp, edge)  # (dp, position) per edge in list order: one stream for the backward's gather
     return csr
 
@@ -193,14 +192,9 @@ class SetAbstraction(nn.Module):
         fi = None
         res_fused = self._fused_residual(f, geom)
         if not res_fused and (self.use_res or 'df' in self.feature_type):
-            import os
-            if (f.is_cuda and f.dtype == torch.float32 and geom.get('fps_idx32') is not None
-                    and os.environ.get("AMC3D_OWN_GATHER")):
-                # gather_points kernels (the reference's GatherOperation): measured 0.24 ms/step slower than torch.gather
-                # here (its backward scatters with float atomics, torch's index-add over sorted FPS picks does not)
-                fi = gather_operation(f.contiguous(), geom['fps_idx32'])
-            else:
-                fi = torch.gather(f, -1, idx.unsqueeze(1).expand(-1, f.shape[1], -1))
+            # torch.gather, not the gather_points kernels (the reference's GatherOperation): those measured 0.24 ms/step
+            # slower here (their backward scatters with float atomics, torch's index-add over sorted FPS picks does not)
+            fi = torch.gather(f, -1, idx.unsqueeze(1).expand(-1, f.shape[1], -1))
             if self.use_res:
                 identity = run_convblocks((self.skipconv,), fi)
         fused = fused_local_aggregation(self.convs, f, geom, self.feature_type)

@@ -7,11 +7,13 @@ state-dict keys are identical: a block is ``nn.Sequential(conv[, norm][, act])``
 the conv has no bias when a norm follows it.
 """
 import copy
-
 import os
 
 import torch
+import torch.distributed as dist
 import torch.nn as nn
+
+from amcontrast3d_amd import ops
 
 
 class Conv2d(nn.Conv2d):
@@ -108,6 +110,21 @@ def create_convblock1d(*args, norm_args=None, act_args=None, order='conv-norm-ac
     return _convblock(Conv1d, '1d', args, norm_args, act_args, order, kwargs)
 
 
+def conv_bn_block(blk):
+    """(conv, bn, relu) when `blk` is nn.Sequential(conv, norm[, act]) with a 1x1 convolution of stride 1, no padding and one
+    group, one of the BatchNorm classes and, optionally, an nn.ReLU (relu: that module or None) -- the form every fused route
+    below starts from; None for anything else.  Pure module inspection: bias, widths, mode and tensors are the caller's."""
+    if not isinstance(blk, nn.Sequential) or len(blk) not in (2, 3):
+        return None
+    conv, bn, relu = blk[0], blk[1], blk[2] if len(blk) == 3 else None
+    if (not isinstance(conv, (nn.Conv1d, nn.Conv2d)) or not isinstance(bn, nn.modules.batchnorm._BatchNorm)
+            or (relu is not None and type(relu) is not nn.ReLU) or isinstance(conv.padding, str)
+            or any(v != 1 for v in conv.kernel_size) or any(v != 1 for v in conv.stride) or any(v != 0 for v in conv.padding)
+            or conv.groups != 1):
+        return None
+    return conv, bn, relu
+
+
 def _fusable_bn(bn, x):
     """plain training-mode BatchNorm1d/2d on a contiguous fp32 GPU tensor (SyncBatchNorm, eval mode and
     other norms take the ordinary torch modules)"""
@@ -126,7 +143,6 @@ def _eval_bn(bn, x):
 def _synced_bn_group(bn, x):
     """process group of a training-mode nn.SyncBatchNorm whose statistics really span several ranks (then the fused
     kernels exchange their per-channel sums: ops.SyncBatchNormFused), else None"""
-    import torch.distributed as dist
     if not (type(bn) is nn.SyncBatchNorm and bn.training and bn.affine and bn.track_running_stats and x.is_cuda
             and x.dtype == torch.float32 and dist.is_available() and dist.is_initialized()):
         return None
@@ -137,6 +153,40 @@ def _synced_bn_group(bn, x):
 _FORCE_SYNCED_BN = False  # tests: take the cross-rank path in a one-rank group too
 
 
+def batchnorm_act(bn, y, relu, pool=False, residual=None):
+    """relu(bn(y)) (relu: the block's nn.ReLU or None), then the max over the last (neighbour) dimension if `pool`, then
+    relu(. + residual) if a residual is given -- an InvResMLP block's `f += identity; act(f)`.  Inference mode outside
+    autograd: ops.bn_eval; nn.SyncBatchNorm over several ranks: ops.SyncBatchNormFused; plain training-mode BatchNorm on a
+    fp32 GPU tensor: ops.BatchNormMax / BatchNormResidualAct / BatchNormAct (statistics, normalisation, ReLU, pool or
+    residual and nn.BatchNorm's running-stat bookkeeping in the same launches, csrc/bn.hip); anything else: the stored torch
+    modules.  What the chosen kernels do not cover of pool and residual follows in torch."""
+    act = relu is not None
+    fused_pool = pool and y.dim() == 4 and y.shape[-1] <= 255
+    group = _synced_bn_group(bn, y)
+    pooled = added = False
+    if _eval_bn(bn, y):
+        x, pooled = ops.bn_eval(y, bn, act, fused_pool), fused_pool
+    elif group is not None:
+        x, pooled = ops.SyncBatchNormFused.apply(y, bn.weight, bn.bias, bn.eps, act, fused_pool, bn, group)[0], fused_pool
+    elif _fusable_bn(bn, y):
+        if fused_pool:
+            x, pooled = ops.BatchNormMax.apply(y, bn.weight, bn.bias, bn.eps, act, bn)[0], True
+        elif (residual is not None and not act and not pool and residual.shape == y.shape and residual.is_cuda
+              and residual.dtype == torch.float32 and not os.environ.get("AMC3D_NO_BN_RESIDUAL")):
+            x, added = ops.BatchNormResidualAct.apply(y, residual, bn.weight, bn.bias, bn.eps, bn)[0], True
+        else:
+            x = ops.BatchNormAct.apply(y, bn.weight, bn.bias, bn.eps, act, bn)[0]
+    else:
+        x = bn(y)
+        if act:
+            x = relu(x)
+    if pool and not pooled:
+        x = torch.max(x, dim=-1, keepdim=False)[0]
+    if residual is not None and not added:
+        x = torch.relu(x + residual)
+    return x
+
+
 def conv1x1(conv, x):
     """conv(x); a plain 1x1 convolution on a contiguous fp32 GPU tensor runs on the MFMA kernels of
     csrc/pwconv.hip (same parameters, same autograd contract), anything else on the stored torch module."""
@@ -144,26 +194,19 @@ def conv1x1(conv, x):
             and conv.groups == 1 and conv.padding_mode == 'zeros'
             and all(k == 1 for k in conv.kernel_size) and all(v == 1 for v in conv.stride)
             and all(v == 0 for v in conv.padding) and x.dim() == conv.weight.dim()):
-        from amcontrast3d_amd.ops import mixed_precision
-        if mixed_precision() and _bf16_pays(conv, x):
+        if ops.mixed_precision() and _bf16_pays(conv, x):
             # use_amp (main_AA.py:389-394): bf16 operands, fp32 accumulation on the bf16 MFMA; activations, BatchNorm,
             # searches and the loss stay fp32 (tensors are never stored in bf16)
-            from amcontrast3d_amd.ops import pointwise_conv
-            return pointwise_conv(x, conv.weight, conv.bias, True)
+            return ops.pointwise_conv(x, conv.weight, conv.bias, True)
         if _pw_pays(conv, x):
-            from amcontrast3d_amd.ops import pointwise_conv
-            return pointwise_conv(x, conv.weight, conv.bias)
+            return ops.pointwise_conv(x, conv.weight, conv.bias)
         if (conv.bias is None and min(conv.in_channels, conv.out_channels) >= 64 and conv.in_channels % 4 == 0
-                and torch.is_grad_enabled() and not os.environ.get("AMC3D_NO_LIBRARY_GEMM")):
+                and torch.is_grad_enabled()):
             # deep and short (SA4, coarse FP stages): three plain library GEMMs instead of the convolution library,
             # whose weight gradient is wrapped in layout transposes (scratch/pw_bench3.py: 30-50 us per layer)
-            from amcontrast3d_amd.ops import library_gemm_conv
-            return library_gemm_conv(x, conv.weight)
-        # what is left (small layers with a bias: the skip convs of SA2-4): this library's kernel too -- the convolution
-        # library answers them with layout transposes around implicit-GEMM kernels (and a find-mode search at first use)
-        if os.environ.get("AMC3D_SMALL_CONV_OWN"):  # measured: 0.35 ms/step slower than the convolution library on these three layers
-            from amcontrast3d_amd.ops import pointwise_conv
-            return pointwise_conv(x, conv.weight, conv.bias)
+            return ops.library_gemm_conv(x, conv.weight)
+        # what is left (small layers with a bias: the skip convs of SA2-4): the convolution library -- this library's own
+        # kernel measured 0.35 ms/step slower on these three layers
         with torch.autocast("cuda", enabled=False):
             return conv(x)
     return conv(x)
@@ -172,14 +215,12 @@ def conv1x1(conv, x):
 def conv1x1_weight(x, w):
     """1x1 convolution of x (B,Cin,P) with an explicit bias-free weight w (Cout,Cin): the routing of conv1x1 for a slice
     of a module's weight (the two halves of a FeaturePropogation conv)"""
-    from amcontrast3d_amd import ops
     cin, cout = w.shape[1], w.shape[0]
     positions = x.numel() // x.shape[1]
     w3 = w.reshape(cout, cin, 1)
     if ops.mixed_precision() and min(cin, cout) >= 64 and positions >= _BF16_MIN_POSITIONS:
         return ops.pointwise_conv(x, w3, None, True)
-    if (min(cin, cout) >= 64 and positions < 65536 and cin % 4 == 0 and torch.is_grad_enabled()
-            and not os.environ.get("AMC3D_NO_LIBRARY_GEMM")):
+    if min(cin, cout) >= 64 and positions < 65536 and cin % 4 == 0 and torch.is_grad_enabled():
         return ops.library_gemm_conv(x, w3)
     return ops.pointwise_conv(x, w3, None)
 
@@ -191,32 +232,22 @@ def feature_propagation_first_block(blk, f1, f2, geom):
     (the 3-NN interpolation is linear and mixes points, the 1x1 conv mixes channels: they commute).  The interpolated
     tensor has Cout instead of C2 channels (half at every level), its conv runs on the coarse cloud (4x fewer points), and
     no concatenated (B, C1+C2, n) tensor exists.  -> the block's output, or None when it is not of that form."""
-    from amcontrast3d_amd import ops
-    if (not isinstance(blk, nn.Sequential) or len(blk) != 3 or type(blk[0]) not in (nn.Conv1d, Conv1d)
-            or not isinstance(blk[1], nn.modules.batchnorm._BatchNorm) or type(blk[2]) is not nn.ReLU
-            or f1 is None or not f1.is_cuda or f1.dtype != torch.float32 or f2.dtype != torch.float32
-            or os.environ.get("AMC3D_NO_FP_SPLIT")):
+    m = conv_bn_block(blk)
+    if (m is None or m[2] is None or type(m[0]) not in (nn.Conv1d, Conv1d) or f1 is None or not f1.is_cuda
+            or f1.dtype != torch.float32 or f2.dtype != torch.float32):
         return None
-    conv, bn = blk[0], blk[1]
+    conv, bn, relu = m
     c1 = f1.shape[1]
-    if (conv.bias is not None or conv.kernel_size != (1,) or conv.stride != (1,) or conv.groups != 1
-            or conv.in_channels != c1 + f2.shape[1]):
+    if conv.bias is not None or conv.in_channels != c1 + f2.shape[1]:
         return None
     w1, w2 = ops.split_weight(conv.weight, c1)
     y = ops.three_interpolate_add(conv1x1_weight(f2, w2), geom['idx'], geom['weight'], conv1x1_weight(f1, w1))
-    group = _synced_bn_group(bn, y)
-    if _eval_bn(bn, y):
-        return ops.bn_eval(y, bn, True, False)
-    if group is not None:
-        return ops.SyncBatchNormFused.apply(y, bn.weight, bn.bias, bn.eps, True, False, bn, group)[0]
-    if _fusable_bn(bn, y):
-        return ops.BatchNormAct.apply(y, bn.weight, bn.bias, bn.eps, True, bn)[0]
-    return blk[2](bn(y))
+    return batchnorm_act(bn, y, relu)
 
 
 # (round 3, cfg 5 = XL + ++ at 1 x 120000: threshold 4096 -> 19.8 ms per step, 16384 -> 19.1, 65536 -> 19.4, never -> 19.3; the
 # shorter deep layers take the library GEMMs, which run on bf16 operands under autocast: ops.LibraryGemmConv)
-_BF16_MIN_POSITIONS = int(os.environ.get("AMC3D_BF16_MIN_POSITIONS", 16384))
+_BF16_MIN_POSITIONS = 16384
 
 
 def _bf16_pays(conv, x):
@@ -239,191 +270,140 @@ def _pw_pays(conv, x):
 
 def run_convblocks(blocks, x, pool_max=False, pre=None, activated=False, residual=None):
     """Evaluate a stack of conv blocks (the nn.Sequential the factories above build), optionally followed by
-    the max over the last (neighbour) dimension.  Where a block is conv -> plain BatchNorm [-> ReLU] in
-    training mode, BatchNorm statistics, normalisation, ReLU and (for the last block) the max-pool run as
-    fused gfx950 kernels (amcontrast3d_amd/csrc/bn.hip); everything else runs the stored modules as they are.
-    Parameters, buffers and their bookkeeping stay those of the nn modules.
+    the max over the last (neighbour) dimension.  Where a block is conv -> BatchNorm [-> ReLU] (conv_bn_block), the conv
+    takes conv1x1's route and BatchNorm, ReLU and (for the last block) the max-pool batchnorm_act's; everything else runs
+    the stored modules as they are.  Parameters, buffers and their bookkeeping stay those of the nn modules.
     `pre`: the already computed output of the first block's convolution (the fused gather+conv kernel).
     `activated`: x is the activated output of a first block evaluated elsewhere (fused_first_block); `blocks` are the rest.
     `residual`: the result is relu(stack(x) + residual) -- an InvResMLP block's `f += identity; act(f)` -- inside the last
     block's BatchNorm kernels where that block is conv -> plain training-mode BatchNorm without activation."""
-    from amcontrast3d_amd.ops import BatchNormAct, BatchNormMax, BatchNormResidualAct, SyncBatchNormFused
-    res_done = False
     mods = list(blocks)
-    pooled = False
     fused = _sa_tail_activated(mods, x, pool_max) if activated else _sa_tail(mods, pool_max, pre)
     if fused is not None:
         return fused
+    finished = False  # the last block's batchnorm_act has pooled and added the residual
     for bi, blk in enumerate(mods):
         last = bi == len(mods) - 1
-        sub = list(blk) if isinstance(blk, nn.Sequential) else None
-        if (sub is not None and len(sub) in (2, 3) and isinstance(sub[0], (nn.Conv1d, nn.Conv2d))
-                and isinstance(sub[1], nn.modules.batchnorm._BatchNorm)
-                and (len(sub) == 2 or type(sub[2]) is nn.ReLU)):
-            y = pre if (bi == 0 and pre is not None) else conv1x1(sub[0], x)
-            bn = sub[1]
-            group = _synced_bn_group(bn, y)
-            if _eval_bn(bn, y):
-                from amcontrast3d_amd.ops import bn_eval
-                pool = last and pool_max and y.dim() == 4 and y.shape[-1] <= 255
-                x = bn_eval(y, bn, len(sub) == 3, pool)
-                pooled = pooled or pool
-            elif group is not None:
-                pool = last and pool_max and y.dim() == 4 and y.shape[-1] <= 255
-                x, _, _ = SyncBatchNormFused.apply(y, bn.weight, bn.bias, bn.eps, len(sub) == 3, pool, bn, group)
-                pooled = pooled or pool
-            elif _fusable_bn(bn, y):
-                relu = len(sub) == 3
-                # the kernels also do nn.BatchNorm's running-stat bookkeeping (same launch)
-                if last and pool_max and y.dim() == 4 and y.shape[-1] <= 255:
-                    x, _, _ = BatchNormMax.apply(y, bn.weight, bn.bias, bn.eps, relu, bn)
-                    pooled = True
-                elif (last and residual is not None and not relu and not pool_max and residual.shape == y.shape
-                      and residual.is_cuda and residual.dtype == torch.float32 and not os.environ.get("AMC3D_NO_BN_RESIDUAL")):
-                    x, _, _ = BatchNormResidualAct.apply(y, residual, bn.weight, bn.bias, bn.eps, bn)
-                    res_done = True
-                else:
-                    x, _, _ = BatchNormAct.apply(y, bn.weight, bn.bias, bn.eps, relu, bn)
-            else:
-                x = bn(y)
-                if len(sub) == 3:
-                    x = sub[2](x)
+        m = conv_bn_block(blk)
+        if m is not None:
+            conv, bn, relu = m
+            y = pre if (bi == 0 and pre is not None) else conv1x1(conv, x)
+            x = batchnorm_act(bn, y, relu, last and pool_max, residual if last else None)
+            finished = last
         else:
             assert not (bi == 0 and pre is not None), "pre needs a conv -> norm block"
+            sub = list(blk) if isinstance(blk, nn.Sequential) else None
             if sub is not None and len(sub) >= 1 and isinstance(sub[0], (nn.Conv1d, nn.Conv2d)):
                 x = conv1x1(sub[0], x)
                 for mod in sub[1:]:
                     x = mod(x)
             else:
                 x = blk(x)
-    if pool_max and not pooled:
-        x = torch.max(x, dim=-1, keepdim=False)[0]
-    if residual is not None and not res_done:
-        x = torch.relu(x + residual)
+    if not finished:
+        if pool_max:
+            x = torch.max(x, dim=-1, keepdim=False)[0]
+        if residual is not None:
+            x = torch.relu(x + residual)
     return x
+
+
+def _sa_tail_conv(blk, x1):
+    """(conv2, bn2, relu) of a second block the kernels of csrc/sa_tail.hip cover on the (B,C1,M,32) tensor x1 -- bias-free
+    1x1 conv from C1 channels, plain training-mode BatchNorm, widths the kernels support and for which recomputing pays --
+    or None"""
+    m = conv_bn_block(blk)
+    if (m is None or x1.dim() != 4 or not _fusable_bn(m[1], x1) or m[0].bias is not None or m[0].in_channels != x1.shape[1]
+            or not ops.sa_tail_supported(x1.shape[1], m[0].out_channels, x1.shape[-1])
+            or not ops.sa_tail_pays(x1.shape[1], m[0].out_channels)):
+        return None
+    return m
 
 
 def _sa_tail(mods, pool_max, pre):
     """[conv0 (already applied: `pre`), BN, ReLU] -> [1x1 conv, BN (, ReLU)] -> max over 32 neighbours as one recomputing
     kernel family (csrc/sa_tail.hip), or None when the stack is not of that form."""
-    import os
-    if pre is None or not pool_max or len(mods) != 2 or os.environ.get("AMC3D_NO_SA_TAIL"):
+    if pre is None or not pool_max or len(mods) != 2:
         return None
-    s0 = list(mods[0]) if isinstance(mods[0], nn.Sequential) else None
-    s1 = list(mods[1]) if isinstance(mods[1], nn.Sequential) else None
-    if (s0 is None or s1 is None or len(s0) != 3 or type(s0[2]) is not nn.ReLU or len(s1) not in (2, 3)
-            or (len(s1) == 3 and type(s1[2]) is not nn.ReLU) or not isinstance(s1[0], nn.Conv2d)):
+    m0 = conv_bn_block(mods[0])
+    if m0 is None or m0[2] is None or not _fusable_bn(m0[1], pre):
         return None
-    bn1, conv2, bn2 = s0[1], s1[0], s1[1]
-    if (pre.dim() != 4 or not _fusable_bn(bn1, pre) or not _fusable_bn(bn2, pre) or conv2.bias is not None
-            or conv2.kernel_size != (1, 1) or conv2.stride != (1, 1) or conv2.groups != 1
-            or any(v != 0 for v in conv2.padding) or conv2.in_channels != pre.shape[1]):
+    m1 = _sa_tail_conv(mods[1], pre)
+    if m1 is None:
         return None
-    from amcontrast3d_amd import ops
-    if not (ops.sa_tail_supported(pre.shape[1], conv2.out_channels, pre.shape[-1])
-            and ops.sa_tail_pays(pre.shape[1], conv2.out_channels)):
-        return None
+    bn1, (conv2, bn2, relu) = m0[1], m1
     return ops.SATail.apply(pre, bn1.weight, bn1.bias, bn1.eps, conv2.weight, bn2.weight, bn2.bias, bn2.eps,
-                            len(s1) == 3, bn1, bn2)
+                            relu is not None, bn1, bn2)
+
+
+def _sa_tail_activated(mods, x1, pool_max):
+    """[1x1 conv, BN (, ReLU)] -> max over 32 neighbours on the activated first-layer output x1, as the recomputing
+    kernel family of csrc/sa_tail.hip (ops.SATailActivated), or None"""
+    if not pool_max or len(mods) != 1:
+        return None
+    m = _sa_tail_conv(mods[0], x1)
+    if m is None:
+        return None
+    conv2, bn2, relu = m
+    return ops.SATailActivated.apply(x1, conv2.weight, bn2.weight, bn2.bias, bn2.eps, relu is not None, bn2)
+
+
+def _grouped_first_block(blocks, f, geom, feature_type):
+    """(conv, bn, relu) of blocks[0] when the layer convolves [dp ; f[idx]] -- feature recipe 'dp_fj', a query in the plan,
+    fp32 features on the GPU, a bias-free conv_bn_block from C + 3 channels -- so that the conv can run on the source points
+    before the gather; else None"""
+    if feature_type != 'dp_fj' or geom is None or 'idx' not in geom or f is None or not f.is_cuda or f.dtype != torch.float32:
+        return None
+    m = conv_bn_block(blocks[0])
+    if m is None or m[0].bias is not None or m[0].in_channels != f.shape[1] + 3:
+        return None
+    return m
 
 
 def fused_local_aggregation(blocks, f, geom, feature_type):
     """A stack of ONE conv block -- Conv2d 1x1 -> BatchNorm2d [-> ReLU] -- followed by the max over the neighbours (every
     LocalAggregation of InvResMLP, the single-layer SetAbstraction of PointNeXt-B/L/XL) as convolve-before-gather
     (amcontrast3d_amd/csrc/lagg.hip): the pooled (B,C,M) output, or None when the layer is not of that form."""
-    from amcontrast3d_amd import ops
-    import os
-    if (feature_type != 'dp_fj' or geom is None or 'idx' not in geom or geom.get('mom') is None or f is None or not f.is_cuda
-            or f.dtype != torch.float32 or len(blocks) != 1
-            or os.environ.get("AMC3D_NO_LOCAL_AGGREGATION")):
+    m = _grouped_first_block(blocks, f, geom, feature_type) if len(blocks) == 1 else None
+    if m is None or geom.get('mom') is None or not ops.local_aggregation_supported(m[0].out_channels, geom['idx'].shape[-1]):
         return None
-    blk = blocks[0]
-    if (not isinstance(blk, nn.Sequential) or len(blk) not in (2, 3) or not isinstance(blk[0], nn.Conv2d)
-            or not isinstance(blk[1], nn.modules.batchnorm._BatchNorm) or (len(blk) == 3 and type(blk[2]) is not nn.ReLU)):
-        return None
-    conv, bn = blk[0], blk[1]
-    idx = geom['idx']
-    if (conv.bias is not None or conv.kernel_size != (1, 1) or conv.stride != (1, 1) or conv.groups != 1
-            or any(v != 0 for v in conv.padding) or conv.in_channels != f.shape[1] + 3
-            or not ops.local_aggregation_supported(conv.out_channels, idx.shape[-1])):
-        return None
-    relu = len(blk) == 3
+    conv, bn, relu = m
     if _eval_bn(bn, f):
-        return ops.local_aggregation_eval(f, geom['dp'], idx, conv.weight, bn, relu)
+        return ops.local_aggregation_eval(f, geom['dp'], geom['idx'], conv.weight, bn, relu is not None)
     group = _synced_bn_group(bn, f)  # nn.SyncBatchNorm over several ranks: the statistics are exchanged between two phases
     if group is None and not _fusable_bn(bn, f):
         return None
-    return ops.LocalAggregationFused.apply(f, geom['dp'], idx, geom['mom'], conv.weight, bn.weight, bn.bias, bn.eps, relu, bn,
-                                           group)
+    return ops.LocalAggregationFused.apply(f, geom['dp'], geom['idx'], geom['mom'], conv.weight, bn.weight, bn.bias, bn.eps,
+                                           relu is not None, bn, group)
 
 
 def fused_first_block(blocks, f, geom, feature_type):
     """First block -- Conv2d 1x1 -> BatchNorm2d -> ReLU -- of a multi-layer neighbourhood MLP (PointNeXt-S'
     SetAbstraction, sa_layers = 2) convolved before the gather, its ACTIVATED output x1 (B,C,M,32) materialised for the
     blocks that follow (ops.GroupedConvBN), or None when the stack is not of that form."""
-    from amcontrast3d_amd import ops
-    import os
-    if (feature_type != 'dp_fj' or geom is None or 'idx' not in geom or geom.get('mom') is None or f is None or not f.is_cuda
-            or f.dtype != torch.float32 or len(blocks) < 2 or os.environ.get("AMC3D_NO_LOCAL_AGGREGATION")):
+    m = _grouped_first_block(blocks, f, geom, feature_type) if len(blocks) >= 2 else None
+    if (m is None or m[2] is None or geom.get('mom') is None
+            or not ops.grouped_conv_bn_supported(m[0].out_channels, geom['idx'].shape[-1])):
         return None
-    blk = blocks[0]
-    if (not isinstance(blk, nn.Sequential) or len(blk) != 3 or not isinstance(blk[0], nn.Conv2d)
-            or not isinstance(blk[1], nn.modules.batchnorm._BatchNorm) or type(blk[2]) is not nn.ReLU):
-        return None
-    conv, bn = blk[0], blk[1]
-    idx = geom['idx']
-    if (conv.bias is not None or conv.kernel_size != (1, 1) or conv.stride != (1, 1) or conv.groups != 1
-            or any(v != 0 for v in conv.padding) or conv.in_channels != f.shape[1] + 3
-            or not ops.grouped_conv_bn_supported(conv.out_channels, idx.shape[-1])):
-        return None
+    conv, bn, _ = m
     if _eval_bn(bn, f):
-        return ops.grouped_conv_bn_eval(f, geom['dp'], idx, conv.weight, bn, True)
+        return ops.grouped_conv_bn_eval(f, geom['dp'], geom['idx'], conv.weight, bn, True)
     group = _synced_bn_group(bn, f)
     if group is None and not _fusable_bn(bn, f):
         return None
     csr = geom.get('csr')
     if csr is not None:
         csr = (csr['start'], csr['edge'], csr.get('edge_dp'))
-    return ops.GroupedConvBN.apply(f, geom['dp'], idx, geom['mom'], conv.weight, bn.weight, bn.bias, bn.eps, True, bn, csr,
-                                   group)
-
-
-def _sa_tail_activated(mods, x1, pool_max):
-    """[1x1 conv, BN (, ReLU)] -> max over 32 neighbours on the activated first-layer output x1, as the recomputing
-    kernel family of csrc/sa_tail.hip (ops.SATailActivated), or None"""
-    import os
-    if not pool_max or len(mods) != 1 or x1.dim() != 4 or os.environ.get("AMC3D_NO_SA_TAIL"):
-        return None
-    s1 = list(mods[0]) if isinstance(mods[0], nn.Sequential) else None
-    if (s1 is None or len(s1) not in (2, 3) or (len(s1) == 3 and type(s1[2]) is not nn.ReLU) or not isinstance(s1[0], nn.Conv2d)
-            or not isinstance(s1[1], nn.modules.batchnorm._BatchNorm)):
-        return None
-    conv2, bn2 = s1[0], s1[1]
-    if (not _fusable_bn(bn2, x1) or conv2.bias is not None or conv2.kernel_size != (1, 1) or conv2.stride != (1, 1)
-            or conv2.groups != 1 or any(v != 0 for v in conv2.padding) or conv2.in_channels != x1.shape[1]):
-        return None
-    from amcontrast3d_amd import ops
-    if not (ops.sa_tail_supported(x1.shape[1], conv2.out_channels, x1.shape[-1])
-            and ops.sa_tail_pays(x1.shape[1], conv2.out_channels)):
-        return None
-    return ops.SATailActivated.apply(x1, conv2.weight, bn2.weight, bn2.bias, bn2.eps, len(s1) == 3, bn2)
+    return ops.GroupedConvBN.apply(f, geom['dp'], geom['idx'], geom['mom'], conv.weight, bn.weight, bn.bias, bn.eps, True, bn,
+                                   csr, group)
 
 
 def fused_first_conv(blocks, f, geom, feature_type):
     """Output of the first block's 1x1 conv on [dp ; f[idx]] from the fused gather+conv MFMA kernel, or None
     when the layer is not of that form (then the caller groups, concatenates and convolves as usual)."""
-    from amcontrast3d_amd import ops
-    blk = blocks[0]
-    if (feature_type != 'dp_fj' or geom is None or 'idx' not in geom or f is None or not f.is_cuda
-            or f.dtype != torch.float32 or not isinstance(blk, nn.Sequential)
-            or len(blk) < 2 or not isinstance(blk[0], nn.Conv2d)
-            or not isinstance(blk[1], nn.modules.batchnorm._BatchNorm)):
+    m = _grouped_first_block(blocks, f, geom, feature_type)
+    if m is None or not ops.grouped_conv_supported(f.shape[1], m[0].out_channels):
         return None
-    conv = blk[0]
-    if (conv.bias is not None or conv.kernel_size != (1, 1) or conv.stride != (1, 1) or conv.groups != 1
-            or conv.in_channels != f.shape[1] + 3 or not ops.grouped_conv_supported(f.shape[1], conv.out_channels)):
-        return None
-    return ops.grouped_conv(f, geom['dp'], geom['idx'], conv.weight)
+    return ops.grouped_conv(f, geom['dp'], geom['idx'], m[0].weight)
 
 
 # input width of the first grouped conv for each neighbourhood feature recipe

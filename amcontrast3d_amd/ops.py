@@ -1121,8 +1121,7 @@ class PointMajorRows(Function):
 
 def point_major_rows(f):
     """(B,C,n) -> (B*n,C); the fused transpose on fp32 GPU tensors, torch's flatten(transpose) otherwise"""
-    import os
-    if f.is_cuda and f.dtype == torch.float32 and f.dim() == 3 and not os.environ.get("AMC3D_NO_PM_ROWS"):
+    if f.is_cuda and f.dtype == torch.float32 and f.dim() == 3:
         return PointMajorRows.apply(f)
     return torch.flatten(f.transpose(1, 2), start_dim=0, end_dim=1)
 
@@ -1761,12 +1760,10 @@ class LibraryGemmConv(Function):
         Cout = weight.shape[0]
         w2 = weight.reshape(Cout, Cin)
         timing.note("library_gemm_conv")
-        import os
         # under bf16 autocast (use_amp, main_AA.py:389): bf16 operands for the three library GEMMs, fp32 accumulation inside the
         # library, fp32 results (tests/test_gpu_bf16.py) -- cfg 5 (XL + ++, 1 x 120000): 16.8 ms per step, 17.1 when the
-        # results were still rounded to bf16 and widened again; AMC3D_LIB_FP32=1 keeps fp32
-        ctx.bf16 = bool(torch.is_autocast_enabled() and torch.get_autocast_dtype('cuda') == torch.bfloat16
-                        and not os.environ.get("AMC3D_LIB_FP32"))
+        # results were still rounded to bf16 and widened again
+        ctx.bf16 = bool(torch.is_autocast_enabled() and torch.get_autocast_dtype('cuda') == torch.bfloat16)
         # bmm with the weight expanded along the batch (stride 0): torch.matmul(2-d, 3-d) would fold the batch into one
         # GEMM by way of a transposed copy of x.
         with torch.autocast("cuda", enabled=False):

@@ -218,11 +218,9 @@ class GraphPipeline:
         # are background work with slack and slow the feature half more than they gain when they spread over the chip)
         ncu = torch.cuda.get_device_properties(self.dev).multi_processor_count
         if geometry_cus is None:
-            import os
             # (sweeps.  End of round 3, feature graph 4.84 ms: 9/16 6.47 ms -- the next batch's geometry becomes the critical path --
             # 10/16 6.02-6.03, 11/16 6.03, 12/16 6.04: one sixteenth of margin to that cliff for a box whose geometry runs slower)
-            sixteenths = int(os.environ.get("AMC3D_GEO_CUS_16THS", "11"))
-            geometry_cus = sixteenths * ncu // 16 if self.N <= 24576 else 0
+            geometry_cus = 11 * ncu // 16 if self.N <= 24576 else 0
         self.s_fps, self.s_geo = _dedicated_queues(self.dev, geometry_cus)
         self.geometry_cus = geometry_cus
         self.ev_lane = [torch.cuda.Event(), torch.cuda.Event()]
@@ -442,8 +440,7 @@ class GraphPipeline:
         # (gloo rehearsals) cut the feature graph at every collective and issue the gradient all-reduce between two graphs
         self.collectives_captured = dist_on and _graphs.collectives_capturable()
         inline = self.collectives_captured or (self.flatg is None and not self.sync_bn)
-        self.update_in_feature_graph = (inline and not os.environ.get("AMC3D_SEPARATE_UPDATE")
-                                        and (fused or all(g.get("capturable", False) for g in self.opt.param_groups)))
+        self.update_in_feature_graph = inline and (fused or all(g.get("capturable", False) for g in self.opt.param_groups))
         n_coll0 = _graphs.captured_collectives
         # feature variants.  Both deliver their gradients in ONE set of static .grad tensors (what the update reads, captured or
         # not): backward runs with .grad = None -- captured with .grad set, autograd would ACCUMULATE into it, last step's
@@ -551,9 +548,6 @@ class GraphPipeline:
         """one tick: train the batch in input set v0 (if it holds one), prepare the next one's geometry, every J ticks
         load J new batches and launch their sampling.  -> (result dict or None, pipeline still holds batches)"""
         from . import schedule
-        import os
-        # diagnostic: leave parts out once every buffer holds results (they go stale; timing only, with one resident batch)
-        skip = os.environ.get("AMC3D_PIPE_SKIP", "") if self.tick > 6 * self.lanes else ""
         J, t = self.lanes, self.tick % schedule.period(self.lanes)
         self.tick += 1
         plan = schedule.tick_plan(t, J)
@@ -572,8 +566,7 @@ class GraphPipeline:
             self.ev_done[v1].synchronize()
         with torch.cuda.stream(self.s_geo):
             self.s_geo.wait_event(self.ev_lane[jc])
-            if "side" not in skip:
-                self.g_side[t].replay()
+            self.g_side[t].replay()
             self._set_valid[v1], self._lane_valid[jc][l] = self._lane_valid[jc][l], False
             launch = False
             if jl is not None:  # J new batches into the buffer whose lanes were all consumed J ticks ago
@@ -592,12 +585,10 @@ class GraphPipeline:
         if launch:
             with torch.cuda.stream(self.s_fps):
                 self.s_fps.wait_event(self.ev_rot)
-                if "fps" not in skip:
-                    self.g_fps[jl].replay()
+                self.g_fps[jl].replay()
                 self.ev_lane[jl].record(self.s_fps)
         with torch.cuda.stream(self.s_geo):
-            if "geo" not in skip:
-                self.g_geo[v1].replay()
+            self.g_geo[v1].replay()
             self.ev_geo.record(self.s_geo)
         return out, self._set_valid[v1] or any(self._lane_valid[0]) or any(self._lane_valid[1])
 

@@ -47,10 +47,6 @@ const char *amc3d_last_error(void);
 int amc3d_stream_create_dedicated(void **stream);
 /* the same with a CU mask that enables bits [first_cu, first_cu + n_cus) only (n_cus <= 0: every CU) */
 int amc3d_stream_create_masked(void **stream, int first_cu, int n_cus);
-/* the same with an arbitrary mask (word i, bit j enables CU 32 i + j), and a diagnostic for planning such masks:
- * out[b] = the XCD (0-7) workgroup b of an nblocks-wide launch on `stream` ran on */
-int amc3d_stream_create_cu_mask(void **stream, const unsigned int *mask, int words);
-int amc3d_probe_xcc_ids(int nblocks, int *out, void *stream);
 /* Raise the device's scratch (private segment) high-water mark to bytes_per_lane (256 / 1024 / 4096 / 16384) with one launch, BEFORE
  * graphs are captured: the runtime re-allocates scratch when a kernel asks for more than any before it, and graph nodes
  * instantiated earlier keep the old allocation (a replay then faults).  scratch_out: any device int (not written). */
@@ -78,13 +74,10 @@ int amc3d_ball_query(int b, int n, int m, float radius, int nsample,
 int amc3d_group_points(int b, int c, int n, int npoints, int nsample,
                        const float *points, const int *idx, float *out, void *stream);
 
-/* bytes of the optional scratch of the two scatter-add gradients below (one (b,n,c) fp32 image) */
-size_t amc3d_scatter_workspace_bytes(int b, int c, int n);
-
 /* replaces group_points_grad_wrapper_fast (group_points_gpu.cu:14-50):
  * grad_points (b,c,n) += scatter(grad_out (b,c,npoints,nsample)); the caller
  * zero-initialises grad_points (group.py:111).  With a workspace of
- * amc3d_scatter_workspace_bytes(b,c,n) the adds go through a point-major image (full-rate atomic
+ * b*c*n floats (one (b,n,c) fp32 image) the adds go through a point-major image (full-rate atomic
  * shape) and are transposed back; workspace = NULL selects the reference's direct per-element
  * atomics. */
 int amc3d_group_points_grad(int b, int c, int n, int npoints, int nsample,
@@ -128,7 +121,7 @@ int amc3d_three_interpolate_add(int b, int c, int m, int n, const float *points,
                                 const float *base, float *out, void *stream);
 /* replaces three_interpolate_grad_wrapper_fast (interpolate_gpu.cu:127-169):
  * grad_points (b,c,m) += ...; caller zero-initialises (upsampling.py:82).
- * Optional workspace: amc3d_scatter_workspace_bytes(b,c,m), as above. */
+ * Optional workspace: b*c*m floats, as above. */
 int amc3d_three_interpolate_grad(int b, int c, int n, int m, const float *grad_out,
                                  const int *idx, const float *weight, float *grad_points,
                                  void *workspace, size_t workspace_bytes, void *stream);

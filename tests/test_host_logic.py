@@ -547,3 +547,56 @@ def test_main_AA_imports_and_call_sites_resolve_against_this_package(tmp_path):
     assert res["sig:criterion"][:7] == ["self", "logit", "target", "stageACE_list", "num_classes", "ignore_index", "ambiguity_args"], res["sig:criterion"]
     assert res["sig:model"][:2] == ["self", "data"], res["sig:model"]
     assert len(res["registered"]) == 5
+
+
+def test_environment_switches_are_exactly_the_documented_ones():
+    """every AMC3D_* name in the package's .py / .hip / .h sources has its row in INTEGRATION.md's table, and nothing else has:
+    a new lever needs a documented reason to exist"""
+    found = set()
+    for base in (os.path.join(ROOT, "amcontrast3d_amd"), os.path.join(ROOT, "include")):
+        for d, _, files in os.walk(base):
+            for name in files:
+                if name.endswith((".py", ".hip", ".h")):
+                    found |= set(re.findall(r"AMC3D_[A-Z0-9_]+", open(os.path.join(d, name), errors="replace").read()))
+    found.discard("AMC3D_H")  # the header's include guard
+    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = text.split("## Environment variables", 1)[1].split("\n## ", 1)[0]
+    table = set(re.findall(r"^\| `(AMC3D_[A-Z0-9_]+)` \|", section, flags=re.M))
+    assert table and found == table, sorted(found ^ table)
+
+
+def _conv_bn_block_cases():
+    from openpoints.models.layers import create_convblock1d, create_convblock2d
+    bn, relu = {"norm": "bn"}, {"act": "relu"}
+    return [  # (block, matches, has relu, conv has a bias)
+        (create_convblock2d(7, 16, norm_args=bn, act_args=relu), True, True, False),
+        (create_convblock1d(7, 16, norm_args=bn, act_args=relu), True, True, False),
+        (create_convblock2d(7, 16, norm_args=bn, act_args=None), True, False, False),
+        (create_convblock1d(7, 16, norm_args=bn, act_args=None, bias=True), True, False, False),  # a norm drops the bias
+        (torch.nn.Sequential(torch.nn.Conv1d(7, 16, 1, bias=False), torch.nn.SyncBatchNorm(16), torch.nn.ReLU()), True, True, False),
+        (create_convblock1d(7, 16, norm_args=None, act_args=relu), False, None, None),            # conv (+ bias) -> ReLU
+        (create_convblock1d(7, 16, norm_args=None, act_args=None), False, None, None),            # bare conv: the skip convs
+        (create_convblock2d(7, 16, norm_args=bn, act_args={"act": "gelu"}), False, None, None),
+        (create_convblock2d(7, 16, norm_args={"norm": "in"}, act_args=relu), False, None, None),
+        (create_convblock2d(7, 16, 3, norm_args=bn, act_args=relu), False, None, None),           # 3-wide kernel
+        (create_convblock1d(7, 16, 3, norm_args=bn, act_args=relu, padding=1), False, None, None),
+        (create_convblock1d(7, 16, norm_args=bn, act_args=relu, stride=2), False, None, None),
+        (create_convblock1d(8, 16, norm_args=bn, act_args=relu, groups=2), False, None, None),
+        (create_convblock2d(7, 16, norm_args=bn, act_args=relu, order="norm-act-conv"), False, None, None),
+        (create_convblock2d(7, 16, norm_args=bn, act_args=relu, order="conv-act-norm"), False, None, None),
+        (torch.nn.Linear(7, 16), False, None, None),
+    ]
+
+
+@pytest.mark.parametrize("case", range(16))
+def test_conv_bn_block_matches_only_pointwise_conv_batchnorm_relu(case):
+    from openpoints.models.layers import blocks
+    blk, matches, has_relu, has_bias = _conv_bn_block_cases()[case]
+    m = blocks.conv_bn_block(blk)
+    if not matches:
+        assert m is None
+        return
+    conv, bn, relu = m
+    assert conv is blk[0] and bn is blk[1] and (relu is blk[2] if has_relu else relu is None)
+    assert isinstance(bn, torch.nn.modules.batchnorm._BatchNorm) and (conv.bias is not None) == has_bias
+    assert all(k == 1 for k in conv.kernel_size)
