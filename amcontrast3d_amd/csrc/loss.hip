@@ -899,6 +899,99 @@ __global__ __launch_bounds__(CE_THREADS) void ce_backward_kernel(int C, long N, 
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The general form: F.cross_entropy(logits, target, weight, ignore_index, reduction='mean', label_smoothing=eps), what the
+// plain PointNeXt trainer builds (examples/segmentation/main.py:224-230: label_smoothing 0.2, class weights on request).
+// With lp = log_softmax over C, w = 1 without weights, V = the counted points (target in [0, C) and not ignored):
+//     loss = [ (1-eps) sum_V w[y_i] (-lp_i[y_i])  +  (eps/C) sum_V sum_c w[c] (-lp_i[c]) ] / sum_V w[y_i]
+// Same layout as the plain kernels above: one thread per point, class planes read coalesced along N, any C >= 1 (nothing
+// is held per class: one walk for the maximum, one for the sum of exponentials, one for the smoothing term when eps > 0).
+// Per point the terms are fp32 sums over the classes combined in fp64; the points are summed in fp64 in the fixed order of
+// the plain kernel (wave shuffle tree, the block's waves in order, then ce_finalize_kernel over the blocks' partials).
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(CE_THREADS) void ce_general_forward_kernel(int C, long N, const float *__restrict__ logits,
+                                                                        const long long *__restrict__ target, long long ignore,
+                                                                        int has_ignore, float eps, const float *__restrict__ weight,
+                                                                        float *__restrict__ lse, double *__restrict__ partial)
+{
+    __shared__ double s_num[CE_THREADS / 64], s_den[CE_THREADS / 64];
+    const int b = blockIdx.y;
+    const long n = (long)blockIdx.x * CE_THREADS + threadIdx.x;
+    double num = 0.0, den = 0.0;
+    if (n < N) {
+        const float *x = logits + (size_t)b * C * N + n;
+        float mx = -__builtin_inff();
+        for (int c = 0; c < C; ++c) mx = fmaxf(mx, x[(size_t)c * N]);
+        float se = 0.f;
+        for (int c = 0; c < C; ++c) se += expf(x[(size_t)c * N] - mx);
+        const float l = mx + logf(se);
+        lse[(size_t)b * N + n] = l;
+        const long long t = target[(size_t)b * N + n];
+        if (!(has_ignore && t == ignore) && t >= 0 && t < C) {
+            const float wy = weight ? weight[t] : 1.f;
+            den = (double)wy;
+            num = (1.0 - (double)eps) * (double)wy * (double)(l - x[(size_t)t * N]);
+            if (eps > 0.f) {
+                float sm = 0.f;  // sum_c w[c] * (-lp[c])
+                for (int c = 0; c < C; ++c) {
+                    const float nlp = l - x[(size_t)c * N];
+                    sm += weight ? weight[c] * nlp : nlp;
+                }
+                num += (double)eps / (double)C * (double)sm;
+            }
+        }
+    }
+    for (int s = 32; s >= 1; s >>= 1) {
+        num += __shfl_xor(num, s, 64);
+        den += __shfl_xor(den, s, 64);
+    }
+    if ((threadIdx.x & 63) == 0) { s_num[threadIdx.x >> 6] = num; s_den[threadIdx.x >> 6] = den; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0, d = 0.0;
+        for (int w = 0; w < CE_THREADS / 64; ++w) { t += s_num[w]; d += s_den[w]; }
+        const size_t slot = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+        partial[slot * 2] = t;
+        partial[slot * 2 + 1] = d;
+    }
+}
+
+// dlogits[b,c,n] = g / den * [ (1-eps) w[y] (p[c] - [c == y]) + (eps/C) (p[c] sum_c w[c] - w[c]) ] for counted targets, 0 otherwise;
+// den = loss_den[1], the forward's sum of w[y_i]
+__global__ __launch_bounds__(CE_THREADS) void ce_general_backward_kernel(int C, long N, const float *__restrict__ logits,
+                                                                         const long long *__restrict__ target, long long ignore,
+                                                                         int has_ignore, float eps, const float *__restrict__ weight,
+                                                                         const float *__restrict__ lse,
+                                                                         const float *__restrict__ loss_den,
+                                                                         const float *__restrict__ grad_out,
+                                                                         float *__restrict__ dlogits)
+{
+    const int b = blockIdx.y;
+    const long n = (long)blockIdx.x * CE_THREADS + threadIdx.x;
+    if (n >= N) return;
+    const float *x = logits + (size_t)b * C * N + n;
+    float *d = dlogits + (size_t)b * C * N + n;
+    const long long t = target[(size_t)b * N + n];
+    if ((has_ignore && t == ignore) || t < 0 || t >= C) {
+        for (int c = 0; c < C; ++c) d[(size_t)c * N] = 0.f;
+        return;
+    }
+    float wsum = (float)C;
+    if (weight) {
+        wsum = 0.f;
+        for (int c = 0; c < C; ++c) wsum += weight[c];
+    }
+    const float scale = grad_out[0] / loss_den[1];
+    const float hard = (1.f - eps) * (weight ? weight[t] : 1.f);
+    const float soft = eps / (float)C;
+    const float l = lse[(size_t)b * N + n];
+    for (int c = 0; c < C; ++c) {
+        const float p = expf(x[(size_t)c * N] - l);
+        const float wc = weight ? weight[c] : 1.f;
+        d[(size_t)c * N] = scale * (hard * (p - (c == (int)t ? 1.f : 0.f)) + soft * (p * wsum - wc));
+    }
+}
+
 }  // namespace amc
 
 using namespace amc;
@@ -1195,4 +1288,37 @@ AMC_API int amc3d_cross_entropy_backward(int B, int C, long N, const float *logi
     hipLaunchKernelGGL(ce_backward_kernel, dim3(div_up(N, CE_THREADS), B), dim3(CE_THREADS), 0, (hipStream_t)stream, C, N,
                        logits, target, ignore_index, lse, mean_cnt, grad_out, dlogits);
     return launch_status("amc3d_cross_entropy_backward");
+}
+
+AMC_API size_t amc3d_cross_entropy_general_workspace_bytes(int B, long N) { return amc3d_cross_entropy_workspace_bytes(B, N); }
+
+AMC_API int amc3d_cross_entropy_general_forward(int B, int C, long N, const float *logits, const long long *target,
+                                                long long ignore_index, int has_ignore, float label_smoothing,
+                                                const float *weight, float *lse, float *loss_den, void *workspace,
+                                                size_t workspace_bytes, void *stream_)
+{
+    if (B <= 0 || N <= 0) return 0;
+    if (C <= 0 || !logits || !target || !lse || !loss_den || !workspace || !(label_smoothing >= 0.f && label_smoothing < 1.f) ||
+        workspace_bytes < amc3d_cross_entropy_general_workspace_bytes(B, N))
+        return bad_arg("amc3d_cross_entropy_general_forward: bad argument (label_smoothing must be in [0, 1))");
+    hipStream_t stream = (hipStream_t)stream_;
+    const int gx = div_up(N, CE_THREADS);
+    hipLaunchKernelGGL(ce_general_forward_kernel, dim3(gx, B), dim3(CE_THREADS), 0, stream, C, N, logits, target, ignore_index,
+                       has_ignore, label_smoothing, weight, lse, (double *)workspace);
+    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(1024), 0, stream, gx * B, (const double *)workspace, loss_den);
+    return launch_status("amc3d_cross_entropy_general_forward");
+}
+
+AMC_API int amc3d_cross_entropy_general_backward(int B, int C, long N, const float *logits, const long long *target,
+                                                 long long ignore_index, int has_ignore, float label_smoothing,
+                                                 const float *weight, const float *lse, const float *loss_den,
+                                                 const float *grad_out, float *dlogits, void *stream)
+{
+    if (B <= 0 || N <= 0) return 0;
+    if (C <= 0 || !logits || !target || !lse || !loss_den || !grad_out || !dlogits ||
+        !(label_smoothing >= 0.f && label_smoothing < 1.f))
+        return bad_arg("amc3d_cross_entropy_general_backward: bad argument (label_smoothing must be in [0, 1))");
+    hipLaunchKernelGGL(ce_general_backward_kernel, dim3(div_up(N, CE_THREADS), B), dim3(CE_THREADS), 0, (hipStream_t)stream, C, N,
+                       logits, target, ignore_index, has_ignore, label_smoothing, weight, lse, loss_den, grad_out, dlogits);
+    return launch_status("amc3d_cross_entropy_general_backward");
 }

@@ -93,6 +93,14 @@ def scatter_mean(src, index, size=None):
     return out / cnt.clamp(min=1).unsqueeze(1)
 
 
+def _logits(out):
+    """the AMContrast3D models return (logits, stageACE_list); the plain PointNeXt baseline (BaseSeg) the logits alone"""
+    if torch.is_tensor(out):
+        return out
+    logits, _ = out
+    return logits
+
+
 def _matrices(num_classes, ignore_index):
     activate()
     from openpoints.utils import ConfusionMatrix
@@ -121,12 +129,13 @@ def summarize(cm, cm_b=None, cm_i=None, distributed=False):
 def validate_boundary_inner(model, batches, num_classes, ignore_index, nsample, miou_B_I=True, distributed=False):
     """Validation pass over batches of ONE cloud each (the reference's val loader uses batch size 1;
     `data['pos'].squeeze()` at main_AA.py:469 assumes it): dicts with pos (1,N,3), x (1,C,N), y (1,N) on the GPU.
-    Returns summarize(...) of the whole / boundary / inner confusion matrices."""
+    Returns summarize(...) of the whole / boundary / inner confusion matrices.  miou_B_I=False is the plain trainer's
+    `validate` (examples/segmentation/main.py:392-433): one matrix over all points, any batch size, five values."""
     model.eval()
     cm, cm_b, cm_i = _matrices(num_classes, ignore_index)
     for data in batches:
         target = data["y"].reshape(data["y"].shape[0], -1)
-        logits, _ = model(data)
+        logits = _logits(model(data))
         pred = logits.argmax(dim=1)
         cm.update(pred, target)
         if miou_B_I:
@@ -198,7 +207,7 @@ def test_cloud_boundary_inner(model, coord, feat, label, parts, num_classes, ign
             pos = (pos - pos.amin(dim=1, keepdim=True)).float()
             cols = ([room_f[sel]] if room_f is not None else []) + [pos[..., 2:3]]
             data = {"pos": pos.contiguous(), "x": torch.cat(cols, dim=2).transpose(1, 2).contiguous()}
-            logits, _ = model(data)
+            logits = _logits(model(data))
             all_logits.append(logits)
             if miou_B_I:
                 split_by_boundary(logits.argmax(dim=1), label[sel],
@@ -216,7 +225,7 @@ def test_cloud_boundary_inner(model, coord, feat, label, parts, num_classes, ign
         for j0 in range(0, len(parts), step):
             chunk = inputs[j0:j0 + step]
             data = chunk[0] if len(chunk) == 1 else {k: torch.cat([d[k] for d in chunk], dim=0) for k in chunk[0]}
-            logits, _ = model(data)
+            logits = _logits(model(data))
             all_logits.append(logits)
             if miou_B_I:
                 for j, d in enumerate(chunk):

@@ -86,7 +86,8 @@ def precompute_fps_levels(model, p, first, last):
 @torch.no_grad()
 def precompute_rest(model, contrast_head, data, fps, num_classes, ignore_index, ambiguity_args):
     """Everything that hangs off a finished sampling `fps` (from precompute_fps): ball queries, relative
-    positions, 3-NN, loss geometry.  -> a full plan whose per-stage dicts also hold fps's tensors."""
+    positions, 3-NN, loss geometry.  -> a full plan whose per-stage dicts also hold fps's tensors.
+    contrast_head None (the plain PointNeXt baseline, whose criterion has no contrastive part): no 'loss' entry."""
     m = _unwrap(model)
     p, enc = [data["pos"]], []
     for i, stage in enumerate(m.encoder.encoder):
@@ -102,6 +103,8 @@ def precompute_rest(model, contrast_head, data, fps, num_classes, ignore_index, 
             blocks.append(cache[key])
         enc.append(blocks)
     plan = {"encoder": enc, "decoder": m.decoder.plan_geometry(p)}
+    if contrast_head is None:
+        return plan
     from . import ops
     with ops.knn_grid_reuse():  # the refinement's k-NN searches the same clouds as the loss: shared cell grids
         plan["loss"] = precompute_loss(contrast_head, plan, data["y"], num_classes, ignore_index, ambiguity_args)
@@ -139,18 +142,20 @@ def split(plan):
     fps = [{k: b[0][k] for k in _FPS_KEYS if k in b[0]} for b in plan["encoder"]]
     rest = {"encoder": [[{k: v for k, v in b[0].items() if k not in _FPS_KEYS}] + list(b[1:])
                         for b in plan["encoder"]],
-            "decoder": plan["decoder"], "loss": plan["loss"]}
-    if "refine" in plan:
-        rest["refine"] = plan["refine"]
+            "decoder": plan["decoder"]}
+    for k in ("loss", "refine"):
+        if k in plan:
+            rest[k] = plan[k]
     return fps, rest
 
 
 def join(fps, rest):
     """Inverse of split(): a full plan whose dicts reference the tensors of `fps` and `rest` (no copies)."""
     plan = {"encoder": [[dict(f, **b[0])] + list(b[1:]) for f, b in zip(fps, rest["encoder"])],
-            "decoder": rest["decoder"], "loss": rest["loss"]}
-    if "refine" in rest:
-        plan["refine"] = rest["refine"]
+            "decoder": rest["decoder"]}
+    for k in ("loss", "refine"):
+        if k in rest:
+            plan[k] = rest[k]
     return plan
 
 
@@ -175,8 +180,11 @@ def precompute_loss(contrast_head, plan, y, num_classes, ignore_index, ambiguity
 
 @torch.no_grad()
 def precompute(model, contrast_head, data, num_classes, ignore_index, ambiguity_args, aux_stream=None, join=True):
-    """-> {'encoder', 'decoder', 'loss'}: the whole coordinate-only half of a step for `data` (pos, y)."""
+    """-> {'encoder', 'decoder', 'loss'}: the whole coordinate-only half of a step for `data` (pos, y); without 'loss'
+    for contrast_head None (the plain PointNeXt baseline)."""
     plan = precompute_sampling(model, data, aux_stream=aux_stream, join=True if aux_stream is None else join)
+    if contrast_head is None:
+        return plan
     if aux_stream is not None and not join:
         with torch.cuda.stream(aux_stream):
             plan["loss"] = precompute_loss(contrast_head, plan, data["y"], num_classes, ignore_index, ambiguity_args)

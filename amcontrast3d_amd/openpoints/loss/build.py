@@ -1,7 +1,8 @@
 """LOSS registry and the cross-entropy + adaptive-margin-contrast criterion.
 
 Drop-in for openpoints/loss/build.py: ``LOSS`` (:9-12), ``CrossEntropyAce`` (:324-346),
-``build_criterion_from_cfg`` (:348-357).
+``build_criterion_from_cfg`` (:348-357).  The reference's other losses (SmoothCrossEntropy, MaskedCrossEntropy, Focal,
+Poly1, ...: :14-278) are not built.
 """
 import torch
 from torch.nn import BCEWithLogitsLoss, CrossEntropyLoss
@@ -10,8 +11,28 @@ from openpoints.AMContrast3D.MarginContrast import ContrastHead
 from openpoints.utils import registry
 
 LOSS = registry.Registry('loss')
-LOSS.register_module(name='CrossEntropy', module=CrossEntropyLoss)
-LOSS.register_module(name='CrossEntropyLoss', module=CrossEntropyLoss)
+
+
+class CrossEntropy(CrossEntropyLoss):
+    """What the registry builds for 'CrossEntropy' / 'CrossEntropyLoss' (loss/build.py:10-11 registers torch's class): the
+    criterion of the plain PointNeXt trainer, `criterion(logits, target)` on the model's (B, ncls, N) logits
+    (examples/segmentation/main.py:224-230, 357-358).  With label smoothing and / or class weights, mean reduction, fp32 CUDA
+    logits and (B, N) int64 targets it is one fused pass (ops.cross_entropy_general); every other input is torch's forward,
+    unchanged -- the module without smoothing and weights included.  CrossEntropyAce / CrossEntropyAcePre construct torch's
+    class themselves and never come here."""
+
+    def forward(self, input, target):
+        if ((self.label_smoothing > 0.0 or self.weight is not None) and self.reduction == 'mean' and input.is_cuda
+                and input.dtype == torch.float32 and input.dim() == 3 and input.is_contiguous()
+                and target.dtype == torch.int64 and target.shape == (input.shape[0], input.shape[2])
+                and (self.weight is None or (self.weight.is_cuda and self.weight.dtype == torch.float32))):
+            from amcontrast3d_amd.ops import cross_entropy_general
+            return cross_entropy_general(input, target, self.ignore_index, self.label_smoothing, self.weight)
+        return super().forward(input, target)
+
+
+LOSS.register_module(name='CrossEntropy', module=CrossEntropy)
+LOSS.register_module(name='CrossEntropyLoss', module=CrossEntropy)
 LOSS.register_module(name='BCEWithLogitsLoss', module=BCEWithLogitsLoss)
 
 

@@ -4,6 +4,7 @@ Drop-in for openpoints/models/segmentation/base_seg.py:
     BaseSeg_M_AMContrast3D :17-94    encoder -> APM (predicted ambiguity per resolution) -> decoder with masked
                                      refinement -> head, returns (logits, stageACE_list, refine rate)
     BaseSeg_AMContrast3D   :97-126   encoder -> decoder -> head, returns (logits, stageACE_list)
+    BaseSeg                :130-166  the plain PointNeXt baseline: encoder -> decoder -> head, returns logits
     SegHead                :207-267  Conv1d+BN+ReLU(+Dropout) ... Conv1d, optional global max/avg concat
 """
 import copy
@@ -100,6 +101,25 @@ class BaseSeg_AMContrast3D(nn.Module):
         p, f, stageACE_list = self.encoder.forward(data)
         f, stageACE_list = self.decoder.forward(p, f, stageACE_list)
         return self.head(f), stageACE_list
+
+
+@MODELS.register_module()
+class BaseSeg(nn.Module):
+    """The plain PointNeXt segmentor (base_seg.py:130-166): forward(data) returns the logits alone."""
+
+    def __init__(self, encoder_args=None, decoder_args=None, cls_args=None, **kwargs):
+        super().__init__()
+        _build_enc_dec(self, encoder_args, decoder_args)
+        _build_head(self, cls_args)
+
+    def forward(self, data):
+        plan = data.get('_geometry', None) if hasattr(data, 'keys') else None
+        p, f = self.encoder.forward_seg_feat(data)
+        if self.decoder is not None:
+            f = self.decoder(p, f, None if plan is None else plan['decoder']).squeeze(-1)
+        if self.head is not None:
+            f = self.head(f)
+        return f
 
 
 @MODELS.register_module()

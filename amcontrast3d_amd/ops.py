@@ -1864,6 +1864,58 @@ def cross_entropy_mean(logits, target, ignore_index=-100):
     return CrossEntropyMean.apply(logits, target, ignore_index)
 
 
+class CrossEntropyGeneral(Function):
+    """F.cross_entropy(logits, target, weight, ignore_index=..., reduction='mean', label_smoothing=...) on channel-major
+    logits (B, C, N) with targets (B, N): the plain PointNeXt trainer's criterion (examples/segmentation/main.py:224-230),
+    one pass forward and one backward (csrc/loss.hip, ce_general_*)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, label_smoothing, weight):
+        _need_gpu(logits, target, *([weight] if weight is not None else []))
+        _need_dtype(torch.float32, logits=logits, **({"weight": weight} if weight is not None else {}))
+        _need_dtype(torch.int64, target=target)
+        logits = logits.contiguous()
+        B, C = logits.shape[0], logits.shape[1]
+        N = logits[0, 0].numel()
+        target = target.reshape(B, N).contiguous()
+        if weight is not None:
+            weight = weight.contiguous()
+            assert weight.shape == (C,), f"weight must hold one value per class: {tuple(weight.shape)} for {C} classes"
+        dev = logits.device
+        lse = torch.empty(B, N, dtype=torch.float32, device=dev)
+        loss_den = torch.empty(2, dtype=torch.float32, device=dev)
+        lib = _lib.load()
+        wb = int(lib.amc3d_cross_entropy_general_workspace_bytes(B, N))
+        work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
+        ctx.args = (int(ignore_index if ignore_index is not None else 0), int(ignore_index is not None), float(label_smoothing))
+        with torch.cuda.device(dev), timing.span("cross_entropy_general_forward", B * N * (4 * C * (3 if label_smoothing else 2) + 12)):
+            _lib.check(lib.amc3d_cross_entropy_general_forward(B, C, N, _ptr(logits), _ptr(target), *ctx.args,
+                                                               _ptr(weight) if weight is not None else None, _ptr(lse),
+                                                               _ptr(loss_den), _ptr(work), wb, _stream(logits)),
+                       "cross_entropy_general_forward")
+        ctx.save_for_backward(logits, target, lse, loss_den, weight)
+        return loss_den[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, lse, loss_den, weight = ctx.saved_tensors
+        B, C = logits.shape[0], logits.shape[1]
+        N = logits[0, 0].numel()
+        g = g.contiguous().to(torch.float32)
+        d = torch.empty_like(logits)
+        with torch.cuda.device(logits.device), timing.span("cross_entropy_general_backward", B * N * (8 * C + 12)):
+            _lib.check(_lib.load().amc3d_cross_entropy_general_backward(B, C, N, _ptr(logits), _ptr(target), *ctx.args,
+                                                                        _ptr(weight) if weight is not None else None,
+                                                                        _ptr(lse), _ptr(loss_den), _ptr(g), _ptr(d),
+                                                                        _stream(logits)), "cross_entropy_general_backward")
+        return d, None, None, None, None
+
+
+def cross_entropy_general(logits, target, ignore_index=-100, label_smoothing=0.0, weight=None):
+    """ignore_index None: no target is ignored.  The class weights take no gradient."""
+    return CrossEntropyGeneral.apply(logits, target, ignore_index, label_smoothing, weight)
+
+
 class SATail(Function):
     """pooled (B,C2,M) = max_k [relu2](bn2(conv2(relu(bn1(y1)))))  -- the tail of a two-layer SetAbstraction block
     (pointnext_AA.py:104-127, 164-166) from the first conv's raw output y1 (B,C1,M,32), with batch statistics for both

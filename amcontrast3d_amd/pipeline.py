@@ -85,7 +85,8 @@ def _side_streams(dev):
 
 class GeometryPrefetcher:
     """Iterate `batches` (dicts with 'pos' (B,N,3) and 'y' (B,N) on the GPU), `depth` batches ahead of the
-    consumer: FPS chains on one side stream, everything hanging off them on a second one."""
+    consumer: FPS chains on one side stream, everything hanging off them on a second one.  contrast_head None (the plain
+    PointNeXt baseline): sampling, ball queries and 3-NN only."""
 
     def __init__(self, batches, model, contrast_head, num_classes, ignore_index, ambiguity_args, depth=2):
         assert depth >= 1
@@ -180,7 +181,8 @@ class GraphPipeline:
             out["loss"], out["logits"], out["target"], out["parts"]   # static tensors, valid until the next-but-one batch
 
     `step_loss(data) -> (logits, loss, parts)` is the model + criterion call (parts: extra scalars to report);
-    `head` = criterion.contrast_head.  The optimizer step is captured when the optimizer can be (FusedAdamW, or torch's
+    `head` = criterion.contrast_head, or None for a criterion without one (the plain PointNeXt baseline: the geometry queue
+    then plans no loss geometry).  The optimizer step is captured when the optimizer can be (FusedAdamW, or torch's
     capturable ones), else it runs eagerly after the feature graph.  Building the pipeline runs three warm-up steps on
     `example`; parameters, buffers and optimizer state are restored afterwards (`keep_state=True`) so that training starts
     from the state it was given.  With `flat_grads` (N > 1) the gradient exchange is one all-reduce between the feature

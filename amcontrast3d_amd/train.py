@@ -78,10 +78,20 @@ def train_one_epoch_mm(model, train_loader, criterion, optimizer, scheduler, sca
 def train_one_epoch(model, train_loader, criterion, optimizer, scheduler, scaler, epoch, cfg, prefetch_depth=2,
                     device=None):
     """One pass over `train_loader`.  cfg needs num_classes, ignore_index, ambiguity_args, feature_keys, use_amp,
-    step_per_update, grad_norm_clip (None / 0: off), sched_on_epoch -- the fields main_AA.py reads."""
-    def step_loss(data, target):
-        logits, stage = model(data)
-        return logits, criterion(logits, target, stage, cfg.num_classes, cfg.ignore_index, cfg.ambiguity_args), ()
+    step_per_update, grad_norm_clip (None / 0: off), sched_on_epoch -- the fields main_AA.py reads.
+
+    A criterion without a `contrast_head` selects the plain PointNeXt step (examples/segmentation/main.py:338-390):
+    `logits = model(data); loss = criterion(logits, target)` with a model that returns the logits alone (BaseSeg); cfg then
+    needs no ambiguity_args, no loss geometry is planned, and everything else -- the captured pipeline, its eager fallbacks,
+    the return value -- is the same."""
+    if getattr(criterion, "contrast_head", None) is None:
+        def step_loss(data, target):
+            logits = model(data)
+            return logits, criterion(logits, target), ()
+    else:
+        def step_loss(data, target):
+            logits, stage = model(data)
+            return logits, criterion(logits, target, stage, cfg.num_classes, cfg.ignore_index, cfg.ambiguity_args), ()
 
     return _run_epoch(model, train_loader, criterion, optimizer, scheduler, scaler, epoch, cfg, prefetch_depth, device,
                       step_loss, extras=0)
@@ -118,8 +128,8 @@ def _graph_pipeline(model, criterion, optimizer, cfg, step_loss, first, clip, ex
         if v > 64 or os.environ.get("AMC3D_EAGER_BOOKKEEPING"):  # (ops.confusion_update's histogram holds 64 x 64 bins)
             tail = None
         with torch.cuda.stream(main):
-            pipe = GraphPipeline(model, lambda data: step_loss(data, data["y"]), criterion.contrast_head, optimizer, first,
-                                 cfg.num_classes, cfg.ignore_index, cfg.ambiguity_args, max_grad_norm=clip, flat_grads=flat,
+            pipe = GraphPipeline(model, lambda data: step_loss(data, data["y"]), getattr(criterion, "contrast_head", None), optimizer,
+                                 first, cfg.num_classes, cfg.ignore_index, _cfg(cfg, "ambiguity_args"), max_grad_norm=clip, flat_grads=flat,
                                  sync_bn=sync_bn, lanes=int(_cfg(cfg, "fps_lanes", 0) or 0),
                                  tail=tail)
         hit = _PIPELINES[key] = (pipe, main, book)
@@ -133,14 +143,14 @@ def _run_epoch(model, train_loader, criterion, optimizer, scheduler, scaler, epo
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     cm = ConfusionMatrix(num_classes=cfg.num_classes, ignore_index=cfg.ignore_index)
     model.train()
-    head = getattr(criterion, "contrast_head", None)
+    head = getattr(criterion, "contrast_head", None)  # None: the plain PointNeXt step, which plans no loss geometry
     batches = _to_device_batches(train_loader, cfg, device)
     use_amp = bool(_cfg(cfg, "use_amp", False))
     clip = _cfg(cfg, "grad_norm_clip", None)
     clip = clip if (clip is not None and clip > 0.) else None
     loss_sum = torch.zeros(1 + extras, dtype=torch.float64, device=device)
     n_batches = 0
-    graphs_ok = (head is not None and not use_amp and cfg.step_per_update == 1 and _cfg(cfg, "graph_pipeline", True)
+    graphs_ok = (not use_amp and cfg.step_per_update == 1 and _cfg(cfg, "graph_pipeline", True)
                  and not os.environ.get("AMC3D_EAGER_TRAIN")
                  and not isinstance(model, (torch.nn.parallel.DistributedDataParallel, torch.nn.DataParallel)))
     if graphs_ok:
@@ -191,8 +201,8 @@ def _run_epoch(model, train_loader, criterion, optimizer, scheduler, scaler, epo
             # (in place: GraphPipeline.run points .grad at the same tensors again in the next epoch either way)
             optimizer.zero_grad(set_to_none=False)
         batches = iter(odd)
-    elif head is not None and prefetch_depth > 0 and not use_amp:
-        batches = GeometryPrefetcher(batches, model, head, cfg.num_classes, cfg.ignore_index, cfg.ambiguity_args,
+    elif prefetch_depth > 0 and not use_amp:
+        batches = GeometryPrefetcher(batches, model, head, cfg.num_classes, cfg.ignore_index, _cfg(cfg, "ambiguity_args"),
                                      depth=prefetch_depth)
     num_iter = 0
     for data in batches:

@@ -287,6 +287,24 @@ int amc3d_cross_entropy_forward(int B, int C, long N, const float *logits, const
 int amc3d_cross_entropy_backward(int B, int C, long N, const float *logits, const long long *target,
                                  long long ignore_index, const float *lse, const float *mean_cnt,
                                  const float *grad_out, float *dlogits, void *stream);
+/* The general form, torch.nn.functional.cross_entropy(logits, target, weight, ignore_index, reduction='mean',
+ * label_smoothing) -- the criterion of the plain PointNeXt trainer (examples/segmentation/main.py:224-230, label_smoothing 0.2
+ * and class weights on request).  weight (C) fp32 or NULL (all ones); label_smoothing eps in [0, 1); has_ignore = 0: no target
+ * is ignored.  V = the points whose target is in [0, C) and not ignored, lp = log_softmax over C, p = softmax:
+ *   loss = [ (1-eps) sum_V w[y_i] (-lp_i[y_i]) + (eps/C) sum_V sum_c w[c] (-lp_i[c]) ] / sum_V w[y_i]
+ *   dlogits_i[c] = grad_out[0] / den * [ (1-eps) w[y_i] (p_i[c] - [c == y_i]) + (eps/C) (p_i[c] sum_c w[c] - w[c]) ], zero rows outside V
+ * loss_den[2] = {loss, den = sum_V w[y_i]}; lse (B,N) out (saved for backward).  Any C >= 1.  Two launches forward, one
+ * backward; fixed summation order (fp64 over the points), so equal inputs give equal bits.  With V empty the loss is
+ * 0/0 = NaN, as torch's, and dlogits is all zero (torch's is too: no row is counted). */
+size_t amc3d_cross_entropy_general_workspace_bytes(int B, long N);
+int amc3d_cross_entropy_general_forward(int B, int C, long N, const float *logits, const long long *target,
+                                        long long ignore_index, int has_ignore, float label_smoothing,
+                                        const float *weight, float *lse, float *loss_den, void *workspace,
+                                        size_t workspace_bytes, void *stream);
+int amc3d_cross_entropy_general_backward(int B, int C, long N, const float *logits, const long long *target,
+                                         long long ignore_index, int has_ignore, float label_smoothing,
+                                         const float *weight, const float *lse, const float *loss_den,
+                                         const float *grad_out, float *dlogits, void *stream);
 
 /* ---- pointwise (1x1) convolution on fp32 MFMA -----------------------------------------------------
  * Replaces the nn.Conv1d / nn.Conv2d (kernel size 1) layers of the path, which the reference builds in
