@@ -13,7 +13,8 @@
 //     mode 0  forward: statistics of BN2 (per-workgroup partial sums, fp64) AND the raw max / min of every
 //             (b, c2, centroid) over its 32 neighbours.  BN2's affine and the ReLU are monotone in fp32 (every
 //             operation of ((x - mean) * invstd) * gamma + beta rounds monotonically), so
-//             max_k relu(bn2(z_k)) = relu(bn2(max_k z_k)) for gamma >= 0 and relu(bn2(min_k z_k)) for gamma < 0:
+//             max_k relu(bn2(z_k)) = relu(bn2(max_k z_k)) for gamma > 0 and relu(bn2(min_k z_k)) for gamma < 0
+//             (gamma == 0: all 32 values are beta and neighbour 0 is the one torch.max routes to, so its z is kept):
 //             the finalize kernel that turns the sums into mean / invstd also writes the pooled (B, C2, M) output
 //             from the raw extrema -- one recomputation pass forward, not two
 //     mode 2  backward statistics                -> sum dq, sum dq * xhat (dq: pooled gradient at the arg-max)
@@ -47,7 +48,7 @@ struct SatArgs {
     // mode 0 / 2: per-workgroup partial sums, [c2][part][2] doubles
     double *partial;
     // mode 0: per (b, c2, centroid) the raw extreme over the 32 neighbours that BN2 + max-pool select (the maximum for
-    // gamma2 >= 0, the minimum otherwise), (B, C2, M), and optionally the first neighbour attaining it (bytes)
+    // gamma2 > 0, the minimum for gamma2 < 0, neighbour 0's for gamma2 == 0), (B, C2, M), and optionally the first neighbour attaining it (bytes)
     float *zext;
     unsigned char *arg_ext;
     // mode 2 / 3
@@ -224,6 +225,9 @@ __global__ __launch_bounds__(256, (MODE == 0 && NCT <= 2) ? 3 : 1) void sat_kern
                     const int os = __shfl_xor(as, 32, 64);
                     if ((up ? oe > ex : oe < ex) || (oe == ex && os < as)) { ex = oe; as = os; }
                 }
+                // gamma == 0 (either sign of zero): every normalised value is beta, torch.max keeps neighbour 0 -- the backward
+                // takes xhat for dgamma from this z (only the kh == 0 lane, which holds neighbour 0, writes below)
+                if (g2[ct] == 0.f) { ex = acc[ct][0]; as = 4 * kh; }
                 const int c2 = ct * 32 + pl;
                 if (live && kh == 0 && c2 < C2) {
                     a.zext[((size_t)b * C2 + c2) * M + m] = ex;
@@ -282,8 +286,9 @@ __global__ __launch_bounds__(256, (MODE == 0 && NCT <= 2) ? 3 : 1) void sat_kern
                 sat_f32x16 accd = sat_f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
                 const int c1 = it * 32 + pl;
                 for (int k2 = 0; k2 < C2; k2 += 2) {
-                    const float av = c1 < C1 ? ws[(k2 + kh) * WS + c1] : 0.f;
-                    const float bv = ts[(k2 + kh) * SAT_XS + wave * 32 + pl];
+                    const bool in = k2 + kh < C2;  // odd C2: the last step has one channel, rows C2 of ws / ts are not theirs
+                    const float av = (in && c1 < C1) ? ws[(k2 + kh) * WS + c1] : 0.f;
+                    const float bv = in ? ts[(k2 + kh) * SAT_XS + wave * 32 + pl] : 0.f;
                     accd = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, accd, 0, 0, 0);
                 }
                 const long p = p0 + wave * 32 + pl;
@@ -423,7 +428,7 @@ __global__ __launch_bounds__(256) void sat_finalize_kernel(int C2, int nparts, d
     for (int i = blockIdx.y * 256 + threadIdx.x; i < B * M; i += 256 * gridDim.y) {
         const int bb = i / M, m = i - bb * M;
         const size_t q = ((size_t)bb * C2 + c) * M + m;
-        float y = sat_bn(zext[q], mf, isf, g, bt);  // (mode 0 kept the maximum for gamma >= 0, the minimum otherwise)
+        float y = sat_bn(zext[q], mf, isf, g, bt);  // (mode 0 kept the maximum for gamma > 0, the minimum for gamma < 0)
         pooled[q] = relu2 ? fmaxf(y, 0.f) : y;
     }
 }
@@ -541,9 +546,11 @@ struct SatAlgArgs {
     float *dx1;                       // (B, C1, M, 32), or (B, M, 32, C1) when dx1_pm
     int dx1_pm;
     float *partial;                   // [part][C2*C1 (sparse dW2) | C1*C1 (Gram) | C1 (sums of x1)]
+    int wr;                           // C1 * C2 / 256
 };
 
-// WR = C1 * C2 / 256: dW2 entries a lane owns (lane = (channel c2 of the wave's quarter, chunk of WR input channels))
+// a.wr = C1 * C2 / 256: dW2 entries a lane owns (lane = (channel c2 of the wave's quarter, chunk of wr input channels));
+// WR: the registers that hold them, wr rounded up to a power of two (equal to it whenever FULL)
 // FULL: C1 == 32 * NIT and C2 % 16 == 0 -- every range guard below is then constant (a guarded LDS read is a branch of its own:
 // the eight reads ahead of eight products would not be issued together)
 template <int NIT, int WR, bool FULL>
@@ -572,7 +579,8 @@ __global__ __launch_bounds__(256, NIT == 1 ? SAT_ALG_WGS : 1) void sat_bwd_alg_k
     // dW2 (sparse part): this lane's channel and input-channel chunk
     const int q4n = C2 / 4;                       // channels per wave
     const int wj = lane % q4n, wc = lane / q4n;   // (256 / C2 chunks of WR channels: q4n * (256 / C2) = 64 lanes)
-    const int wc2 = wave * q4n + wj, wc1 = wc * WR;
+    const int wr = FULL ? WR : a.wr;
+    const int wc2 = wave * q4n + wj, wc1 = wc * wr;
     float accw[WR];
 #pragma unroll
     for (int i = 0; i < WR; ++i) accw[i] = 0.f;
@@ -709,7 +717,8 @@ __global__ __launch_bounds__(256, NIT == 1 ? SAT_ALG_WGS : 1) void sat_bwd_alg_k
             const float v = r.x;
             const int pos = ce * 32 + __float_as_int(r.y);
 #pragma unroll
-            for (int i = 0; i < WR; ++i) accw[i] = __fmaf_rn(v, xs[(wc1 + i) * SAT_XS + pos], accw[i]);
+            for (int i = 0; i < WR; ++i)  // (registers past wr re-read the chunk's last channel and are never written out)
+                accw[i] = __fmaf_rn(v, xs[(wc1 + ((FULL || i < wr) ? i : wr - 1)) * SAT_XS + pos], accw[i]);
         }
         // ---- dx1 = (sparse - A x1) - c -----------------------------------------------------------------------------------------
         const long p = p0 + wave * 32 + pl;
@@ -738,7 +747,8 @@ __global__ __launch_bounds__(256, NIT == 1 ? SAT_ALG_WGS : 1) void sat_bwd_alg_k
     const int part = blockIdx.y * gridDim.x + blockIdx.x;
     float *out = a.partial + (size_t)part * ((size_t)C2 * C1 + (size_t)C1 * C1 + C1);
 #pragma unroll
-    for (int i = 0; i < WR; ++i) out[(size_t)wc2 * C1 + wc1 + i] = accw[i];  // every entry has one owner in the workgroup
+    for (int i = 0; i < WR; ++i)
+        if (FULL || i < wr) out[(size_t)wc2 * C1 + wc1 + i] = accw[i];  // every entry has one owner in the workgroup
     __syncthreads();
     float *red = sat_smem;  // [C1][C1]
     for (int i = threadIdx.x; i < C1 * C1; i += 256) red[i] = 0.f;
@@ -924,7 +934,10 @@ namespace amc {
 template <int NIT>
 static int sat_alg_launch(const SatAlgArgs &a, int groups, size_t lds, hipStream_t stream)
 {
-    const int wr = a.C1 * a.C2 / 256;
+    // the caller has checked sat_alg_supported, which bounds a.wr = C1 * C2 / 256 by 32 (today: any of 1 .. 16 or an even number up
+    // to 32): six register capacities serve them.  Should that predicate ever admit more, the switch below refuses the shape
+    int cap = 1;
+    while (cap < a.wr) cap *= 2;
     const bool full = a.C1 == 32 * NIT && a.C2 % 16 == 0;
 #define AMC_SATA2(W, F)                                                                                                          \
     (void)hipFuncSetAttribute((const void *)sat_bwd_alg_kernel<NIT, W, F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
@@ -932,10 +945,10 @@ static int sat_alg_launch(const SatAlgArgs &a, int groups, size_t lds, hipStream
 #define AMC_SATA(W)                  \
     if (full) { AMC_SATA2(W, true); } \
     else { AMC_SATA2(W, false); }
-    switch (wr) {
+    switch (cap) {
         case 1: AMC_SATA(1); break; case 2: AMC_SATA(2); break; case 4: AMC_SATA(4); break; case 8: AMC_SATA(8); break;
         case 16: AMC_SATA(16); break; case 32: AMC_SATA(32); break;
-        default: return bad_arg("amc3d_sa_tail_backward: unsupported C1 * C2");
+        default: return bad_arg("amc3d_sa_tail_backward: C1 * C2 / 256 > 32 (sat_alg_supported and this switch disagree)");
     }
 #undef AMC_SATA
 #undef AMC_SATA2
@@ -980,7 +993,7 @@ AMC_API int amc3d_sa_tail_backward(int B, int C1, int C2, int M, int K, const fl
         SatAlgArgs g{};
         g.B = B; g.C1 = C1; g.C2 = C2; g.M = M; g.y1 = y1; g.mean1 = mean1; g.invstd1 = invstd1; g.g1 = gamma1; g.b1 = beta1;
         g.w2 = w2; g.coefA = (const float *)(w + l.coefA); g.coefc = (const float *)(w + l.coefc); g.vT = vT; g.argT = argT;
-        g.dx1 = dx1; g.dx1_pm = dx1_position_major ? 1 : 0; g.partial = (float *)(w + l.partial);
+        g.dx1 = dx1; g.dx1_pm = dx1_position_major ? 1 : 0; g.partial = (float *)(w + l.partial); g.wr = C1 * C2 / 256;
         const int WSd = C1 + 1;
         const size_t lds = ((size_t)C1 * SAT_XS + (size_t)C1 * WSd + (size_t)C2 * WSd + 5 * (size_t)C1 + 2 + 8 * (size_t)C2) * sizeof(float) + 16;
         if (int st = C1 > 32 ? sat_alg_launch<2>(g, groups, lds, stream) : sat_alg_launch<1>(g, groups, lds, stream)) return st;

@@ -499,8 +499,8 @@ int amc3d_sa_tail_forward(int B, int C1, int C2, int M, int K, const float *y1, 
                           float *running_mean2, float *running_var2, long long *num_batches_tracked2,
                           float *zext_out, unsigned char *arg_out, void *workspace, size_t workspace_bytes, void *stream);
 /* zext_out (B,C2,M) fp32 and arg_out (B,C2,M) bytes -- both or neither: per (b, c2, centroid) the raw extreme of conv2's output
- * over the 32 neighbours that BN2 + max-pool select (the maximum for gamma2 >= 0, the minimum otherwise) and the first
- * neighbour attaining it (torch.max's rule on the raw values).  Handed to amc3d_sa_tail_backward they replace its two
+ * over the 32 neighbours that BN2 + max-pool select (the maximum for gamma2 > 0, the minimum for gamma2 < 0, neighbour 0's
+ * value for gamma2 == 0, where all 32 normalised values equal beta2) and the first neighbour attaining it (torch.max's rule on the raw values).  Handed to amc3d_sa_tail_backward they replace its two
  * recomputation passes by the algebraic form: q is sparse (one neighbour per pooled element) and BatchNorm's backward adds
  * terms affine in z = W2 x1, so  dx1 = W2^T Dq q - (W2^T E W2) x1 - c  and  dW2 = Dq q x1^T - E W2 (x1 x1^T) - t (x1 1)^T
  * (csrc/sa_tail.hip): one pass over x1 with a C1 x C1 product and the Gram matrix on the MFMA and C2 rank-1 terms per centroid. */
