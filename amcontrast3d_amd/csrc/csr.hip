@@ -467,7 +467,7 @@ __global__ __launch_bounds__(256) void csr_collapse_stream_kernel(int C, long P,
 
 
 // ---- reverse lists of the loss stages' k-NN edges (anchor i, neighbour slot j) restricted to the selected anchors -------
-// Counting sort (in-degree by integer atomics, exclusive scan, cursor fill), then every short list is put in ascending
+// Counting sort (in-degree by integer atomics, exclusive scan, cursor fill), then every list is put in ascending
 // order so the gather that uses it sums in a fixed order.  E = (selected anchors) * k, a device-side quantity: the launch
 // covers m * k slots and the surplus threads leave at once.
 __global__ void nbr_degree_kernel(int m, int k, int nbr_stride, const int *__restrict__ nbr, const int *__restrict__ sel,
@@ -603,14 +603,41 @@ __global__ void nbr_fill_nonmutual_kernel(int m, int k, int nbr_stride, const in
     rev_edge[rev_start[x] + atomicAdd(cursor + x, 1)] = (int)t;
 }
 
-constexpr int NBR_SORT_MAX = 96;  // longer lists (degenerate clouds) keep their fill order
+constexpr int NBR_SORT_MAX = 96;  // longer lists (degenerate clouds: hubs, padded searches) take the heap sort
+// l[root] sinks to its place in the max-heap l[0 .. end)
+__device__ __forceinline__ void nbr_sift_down(int *l, long root, long end)
+{
+    const int v = l[root];
+    for (;;) {
+        long child = 2 * root + 1;
+        if (child >= end) break;
+        if (child + 1 < end && l[child + 1] > l[child]) ++child;
+        if (l[child] <= v) break;
+        l[root] = l[child];
+        root = child;
+    }
+    l[root] = v;
+}
+
+// every list in ascending order, whatever order the atomic cursors filled it in: the gathering backward forms then add in
+// a fixed order at every length
 __global__ void nbr_order_kernel(int m, const int *__restrict__ rev_start, int *__restrict__ rev_edge)
 {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= m) return;
     const int e0 = rev_start[n], d = rev_start[n + 1] - e0;
-    if (d < 2 || d > NBR_SORT_MAX) return;
+    if (d < 2) return;
     int *l = rev_edge + e0;
+    if (d > NBR_SORT_MAX) {  // in place, d log d: a list may hold every edge of the stage
+        for (long r = d / 2 - 1; r >= 0; --r) nbr_sift_down(l, r, d);
+        for (long end = d - 1; end > 0; --end) {
+            const int top = l[0];
+            l[0] = l[end];
+            l[end] = top;
+            nbr_sift_down(l, 0, end);
+        }
+        return;
+    }
     for (int x = 1; x < d; ++x) {  // insertion sort: the lists hold ~k entries
         const int v = l[x];
         int y = x - 1;

@@ -264,7 +264,7 @@ __global__ __launch_bounds__(256) void contrast_forward_unit_kernel(
     const float margin = __fadd_rn(__fmul_rn(mu, ai), nu);
     const float4 *h4 = reinterpret_cast<const float4 *>(unit);
     const float4 u = h4[(size_t)i * LPR + q];
-    float psum = 0.f, tsum = 0.f;
+    float psum = 0.f, tsum = 0.f, nsum = 0.f;
     for (int j0 = 0; j0 < k; j0 += U * R) {
         int nb[U];
         float4 v[U];
@@ -290,6 +290,7 @@ __global__ __launch_bounds__(256) void contrast_forward_unit_kernel(
             if (sim) sim[(size_t)i * k + jq] = s;
             const float e = expf(__fdiv_rn(pos ? __fsub_rn(s, margin) : s, temperature));
             psum += pos ? e : 0.f;
+            nsum += pos ? 0.f : e;
             tsum += e;
         }
     }
@@ -298,9 +299,13 @@ __global__ __launch_bounds__(256) void contrast_forward_unit_kernel(
         psum += __shfl_xor(psum, d, 64);
         tsum += __shfl_xor(tsum, d, 64);
     }
+    if (stats) {  // (kernel-uniform) the negatives' sum on its own: tsum - psum would lose it where the positives dominate
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) nsum += __shfl_xor(nsum, d, 64);
+    }
     if (lane == 0) {
         loss_pt[i] = -logf(__fadd_rn(__fdiv_rn(psum, tsum), 1e-12f));
-        if (stats) { stats[(size_t)i * 2] = psum; stats[(size_t)i * 2 + 1] = tsum; }  // what the backward's records need of this pass
+        if (stats) { stats[(size_t)i * 2] = psum; stats[(size_t)i * 2 + 1] = nsum; }  // what the backward's records need of this pass
     }
 }
 
@@ -338,19 +343,29 @@ __global__ __launch_bounds__(256) void contrast_forward_kernel(
             const int nb = nbr[(size_t)i * nbr_stride + j];
             const float nj = norm[nb];
             const float *fj = f + (size_t)nb * C;
-            float acc = 0.f;
+            // four partial sums (a chain of C / 4 additions each, not of C: the cosine's rounding error is multiplied by 1 / T
+            // in the exponent)
+            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
             if ((C & 3) == 0) {
                 for (int c = 0; c < C; c += 4) {
                     const float4 u = *reinterpret_cast<const float4 *>(fi + c);
                     const float4 v = *reinterpret_cast<const float4 *>(fj + c);
-                    acc += __fdiv_rn(u.x, ni) * __fdiv_rn(v.x, nj);
-                    acc += __fdiv_rn(u.y, ni) * __fdiv_rn(v.y, nj);
-                    acc += __fdiv_rn(u.z, ni) * __fdiv_rn(v.z, nj);
-                    acc += __fdiv_rn(u.w, ni) * __fdiv_rn(v.w, nj);
+                    a0 += __fdiv_rn(u.x, ni) * __fdiv_rn(v.x, nj);
+                    a1 += __fdiv_rn(u.y, ni) * __fdiv_rn(v.y, nj);
+                    a2 += __fdiv_rn(u.z, ni) * __fdiv_rn(v.z, nj);
+                    a3 += __fdiv_rn(u.w, ni) * __fdiv_rn(v.w, nj);
                 }
             } else {
-                for (int c = 0; c < C; ++c) acc += __fdiv_rn(fi[c], ni) * __fdiv_rn(fj[c], nj);
+                int c = 0;
+                for (; c + 3 < C; c += 4) {
+                    a0 += __fdiv_rn(fi[c], ni) * __fdiv_rn(fj[c], nj);
+                    a1 += __fdiv_rn(fi[c + 1], ni) * __fdiv_rn(fj[c + 1], nj);
+                    a2 += __fdiv_rn(fi[c + 2], ni) * __fdiv_rn(fj[c + 2], nj);
+                    a3 += __fdiv_rn(fi[c + 3], ni) * __fdiv_rn(fj[c + 3], nj);
+                }
+                for (; c < C; ++c) a0 += __fdiv_rn(fi[c], ni) * __fdiv_rn(fj[c], nj);
             }
+            const float acc = (a0 + a1) + (a2 + a3);
             sim[(size_t)i * k + j] = acc;
             pos = posmask[(size_t)i * k + j] != 0;
             const float s = pos ? __fsub_rn(acc, margin) : acc;
@@ -421,6 +436,10 @@ __global__ __launch_bounds__(1024) void masked_mean_kernel(int m, const float *_
 // of one row (the shape global float atomics run at full rate for).
 //   l = -log(r + eps), r = P/S, e_j = exp(s'_j / T):  dl/ds_j = -(e_j (pos_j S - P)) / ((r+eps) S^2 T)
 //   ds_j/df_i = (fhat_j - s_j fhat_i)/|f_i|,  ds_j/df_j = (fhat_i - s_j fhat_j)/|f_j|
+// A row below the norm clamp (|f| < eps: norm[] holds eps) has fhat = f / eps, linear in f: its derivative is fhat_j / eps, with
+// no projection term -- what autograd gives for x / clamp_min(|x|, eps).  All backward forms drop s_j fhat there.  They
+// see the clamped norm only (the test is norm > eps), so a row whose norm is eps to the bit counts as clamped, where
+// clamp_min's gradient would still pass: one fp32 value of the norm.
 // Where the time goes (scratch/contrast_diag.sh + contrast_bench.py, S3DIS-like batch, 66-99 % of the anchors listed): the
 // kernel adds 387 / 229 / 134 / 73 MB of rows at the four stages in 0.33 / 0.20 / 0.12 / 0.06 ms = 1.15-1.17 TB/s, the
 // chip-wide float-atomic rate (MI355X_MICROARCH.md: 1.26-1.36 TB/s); without the neighbour-row atomics it takes a third
@@ -470,16 +489,19 @@ __global__ __launch_bounds__(256) void contrast_backward_kernel(
             e_l = expf(__fdiv_rn(pos_l ? __fsub_rn(sj_l, margin) : sj_l, temperature));
         }
     };
-    // P and S over all neighbours
-    float psum = 0.f, tsum = 0.f;
+    // P and S over all neighbours, and the negatives' share S - P summed on its own: a positive's coefficient is
+    // proportional to it, and tsum - psum loses it to cancellation when the positives dominate (low temperature, r near 1)
+    float psum = 0.f, tsum = 0.f, nsum = 0.f;
     for (int j0 = (k - 1) / LPA * LPA; j0 >= 0; j0 -= LPA) {  // ends on chunk 0, which the walk starts with
         load_chunk(j0);
         psum += pos_l ? e_l : 0.f;
+        nsum += pos_l ? 0.f : e_l;
         tsum += e_l;
     }
 #pragma unroll
     for (int s = LPA / 2; s >= 1; s >>= 1) {
         psum += __shfl_xor(psum, s, 64);
+        nsum += __shfl_xor(nsum, s, 64);
         tsum += __shfl_xor(tsum, s, 64);
     }
     const float r = psum / tsum;
@@ -488,7 +510,7 @@ __global__ __launch_bounds__(256) void contrast_backward_kernel(
 
     for (int j0 = 0; j0 < k; j0 += LPA) {
         if (j0 > 0) load_chunk(j0);
-        const float g_l = coef * e_l * ((pos_l ? tsum : 0.f) - psum);  // dL/ds_j
+        const float g_l = coef * e_l * (pos_l ? nsum : -psum);  // dL/ds_j
         const int cnt = min(LPA, k - j0);
         for (int jj = 0; jj < cnt; jj += U) {
             int nb[U];
@@ -516,14 +538,15 @@ __global__ __launch_bounds__(256) void contrast_backward_kernel(
                 const float g = __shfl(g_l, src, LPA), sj = __shfl(sj_l, src, LPA), nj = __shfl(nj_l, src, LPA);
                 if (nb[u] < 0) continue;
                 const float gin = g / ni, gjn = g / nj;
+                const float si = ni > 1e-8f ? sj : 0.f, sx = nj > 1e-8f ? sj : 0.f;  // (no projection below the clamp)
 #pragma unroll
                 for (int v = 0; v < VPT; ++v) {
                     const int c = sub + v * LPA;
                     if (c < C) {
                         const float fhj = __fdiv_rn(fj[u][v], nj);
-                        gi[v] += gin * (fhj - sj * fhi[v]);
+                        gi[v] += gin * (fhj - si * fhi[v]);
 #if AMC_CONTRAST_DIAG != 1  // diagnostic build 1: no neighbour-row atomics (timing only)
-                        atomicAdd(grad_f + (size_t)nb[u] * C + c, gjn * (fhi[v] - sj * fhj));
+                        atomicAdd(grad_f + (size_t)nb[u] * C + c, gjn * (fhi[v] - sx * fhj));
 #endif
                     }
                 }
@@ -558,16 +581,18 @@ __global__ __launch_bounds__(256) void contrast_coef_kernel(
     const float ai = a[i];
     const float scale = grad_out[0] / mean_cnt[1];
     const float margin = __fadd_rn(__fmul_rn(mu, ai), nu);
-    float psum = 0.f, tsum = 0.f;
+    float psum = 0.f, tsum = 0.f, nsum = 0.f;  // nsum: the negatives' share, summed on its own (no tsum - psum cancellation)
     for (int j = sub; j < k; j += 32) {
         const bool pos = posmask[(size_t)i * k + j] != 0;
         const float sj = sim[(size_t)i * k + j];
         const float e = expf(__fdiv_rn(pos ? __fsub_rn(sj, margin) : sj, temperature));
         psum += pos ? e : 0.f;
+        nsum += pos ? 0.f : e;
         tsum += e;
     }
     for (int s = 16; s >= 1; s >>= 1) {
         psum += __shfl_xor(psum, s, 64);
+        nsum += __shfl_xor(nsum, s, 64);
         tsum += __shfl_xor(tsum, s, 64);
     }
     const float r = psum / tsum;
@@ -576,7 +601,7 @@ __global__ __launch_bounds__(256) void contrast_coef_kernel(
         const bool pos = posmask[(size_t)i * k + j] != 0;
         const float sj = sim[(size_t)i * k + j];
         const float e = expf(__fdiv_rn(pos ? __fsub_rn(sj, margin) : sj, temperature));
-        gco[(size_t)i * k + j] = psum == 0.f ? 0.f : coef * e * ((pos ? tsum : 0.f) - psum);
+        gco[(size_t)i * k + j] = psum == 0.f ? 0.f : coef * e * (pos ? nsum : -psum);
     }
 }
 
@@ -627,10 +652,11 @@ __global__ __launch_bounds__(256) void contrast_backward_rows_kernel(
             for (int u = 0; u < U; ++u) {
                 if (x[u] < 0) continue;
                 const float gn = g[u] / nn;
-                acc.x += gn * (__fdiv_rn(v[u].x, nx[u]) - sv[u] * fn.x);
-                acc.y += gn * (__fdiv_rn(v[u].y, nx[u]) - sv[u] * fn.y);
-                acc.z += gn * (__fdiv_rn(v[u].z, nx[u]) - sv[u] * fn.z);
-                acc.w += gn * (__fdiv_rn(v[u].w, nx[u]) - sv[u] * fn.w);
+                const float sn = nn > 1e-8f ? sv[u] : 0.f;  // (no projection below the clamp)
+                acc.x += gn * (__fdiv_rn(v[u].x, nx[u]) - sn * fn.x);
+                acc.y += gn * (__fdiv_rn(v[u].y, nx[u]) - sn * fn.y);
+                acc.z += gn * (__fdiv_rn(v[u].z, nx[u]) - sn * fn.z);
+                acc.w += gn * (__fdiv_rn(v[u].w, nx[u]) - sn * fn.w);
             }
         }
 #pragma unroll
@@ -652,12 +678,13 @@ __global__ __launch_bounds__(256) void contrast_backward_rows_kernel(
 // directions of a mutual edge need:
 //     dL/df_n = sum_{x in N(n)} (g_nx [n selected] + g_xn [x selected, edge mutual]) / |f_n| * (fhat_x - s_nx fhat_n)
 //             + sum over the non-mutual incoming edges (x -> n), listed in rev (amc3d_contrast_mutual: a tenth of all edges)
-// with g_ix = dL/ds_ix = coef_i e_ix ([pos] S_i - P_i), e_ix = exp((s - [pos] margin_i)/T), from a 32-byte record per anchor
-// (norm, coef, S, P, margin: contrast_record_kernel).  Every neighbour row is fetched ONCE per (n, x) pair -- the traffic of
+// with g_ix = dL/ds_ix = coef_i e_ix ([pos] N_i - [neg] P_i), e_ix = exp((s - [pos] margin_i)/T), N_i = S_i - P_i the negatives'
+// sum (added up on its own: the difference would cancel), from a 32-byte record per anchor (norm, coef, S, P, margin, N:
+// contrast_record_kernel; the backward reads norm, coef, P, margin and N).  Every neighbour row is fetched ONCE per (n, x) pair -- the traffic of
 // the forward kernel -- every gradient row is written once with a plain store, the summation order is fixed, and no float
 // atomic is left (the atomic form added 387 / 229 / 134 / 73 MB of rows per step at the chip's float-atomic rate of 1.15 TB/s).
 // ---------------------------------------------------------------------------------------------
-struct __attribute__((aligned(16))) ContrastRecord { float norm, coef, tsum, psum, margin, pad0, pad1, pad2; };
+struct __attribute__((aligned(16))) ContrastRecord { float norm, coef, tsum, psum, margin, nsum, pad1, pad2; };  // nsum = S - P, summed on its own
 
 __global__ __launch_bounds__(256) void contrast_record_kernel(
     int m, int k, const float *__restrict__ norm, const unsigned char *__restrict__ posmask, const float *__restrict__ a,
@@ -670,7 +697,7 @@ __global__ __launch_bounds__(256) void contrast_record_kernel(
     const float ai = a[i];
     const bool selected = 0.f < ai && ai <= 1.f;
     const float margin = __fadd_rn(__fmul_rn(mu, ai), nu);
-    float psum = 0.f, tsum = 0.f;
+    float psum = 0.f, tsum = 0.f, nsum = 0.f;
     if (selected) {  // wave-uniform per half-wave: sim holds values for the selected anchors only
         // the forward's order: slot-local sums over the rounds, then a tree over the slots (contrast_forward_rows_kernel
         // folds 64/LPR slots; any fixed order is within rounding of it)
@@ -679,11 +706,13 @@ __global__ __launch_bounds__(256) void contrast_record_kernel(
             const float sj = sim[(size_t)i * k + j];
             const float e = expf(__fdiv_rn(pos ? __fsub_rn(sj, margin) : sj, temperature));
             psum += pos ? e : 0.f;
+            nsum += pos ? 0.f : e;
             tsum += e;
         }
     }
     for (int s = 16; s >= 1; s >>= 1) {
         psum += __shfl_xor(psum, s, 64);
+        nsum += __shfl_xor(nsum, s, 64);
         tsum += __shfl_xor(tsum, s, 64);
     }
     if (sub == 0) {
@@ -692,7 +721,7 @@ __global__ __launch_bounds__(256) void contrast_record_kernel(
         ContrastRecord o;
         o.norm = norm[i];
         o.coef = (selected && psum != 0.f) ? -scale / ((r + 1e-12f) * tsum * tsum * temperature) : 0.f;
-        o.tsum = tsum; o.psum = psum; o.margin = margin; o.pad0 = o.pad1 = o.pad2 = 0.f;
+        o.tsum = tsum; o.psum = psum; o.margin = margin; o.nsum = nsum; o.pad1 = o.pad2 = 0.f;
         rec[i] = o;
     }
 }
@@ -701,7 +730,7 @@ __global__ __launch_bounds__(256) void contrast_record_kernel(
 // row's slot of round q -- index, mask, mutual count, the record of x, the two exponentials -- once, and hands x down to /
 // the finished coefficient back to the row's lanes by shuffles)
 // the same records from the two sums the forward pass kept per anchor (stats[2 i] = sum of the positives' exponentials,
-// stats[2 i + 1] = sum of all): nothing to recompute, no similarities to read; one thread per anchor
+// stats[2 i + 1] = sum of the negatives'): nothing to recompute, no similarities to read; one thread per anchor
 __global__ __launch_bounds__(256) void contrast_record_stats_kernel(int m, const float *__restrict__ norm, const float *__restrict__ a,
                                                                     float mu, float nu, float temperature,
                                                                     const float *__restrict__ stats, const float *__restrict__ mean_cnt,
@@ -711,13 +740,14 @@ __global__ __launch_bounds__(256) void contrast_record_stats_kernel(int m, const
     if (i >= m) return;
     const float ai = a[i];
     const bool selected = 0.f < ai && ai <= 1.f;  // (the forward visited the selected anchors only: the others' stats are unwritten)
-    const float psum = selected ? stats[(size_t)i * 2] : 0.f, tsum = selected ? stats[(size_t)i * 2 + 1] : 1.f;
+    const float psum = selected ? stats[(size_t)i * 2] : 0.f, nsum = selected ? stats[(size_t)i * 2 + 1] : 1.f;
+    const float tsum = __fadd_rn(psum, nsum);
     const float scale = grad_out[0] / mean_cnt[1];
     const float r = psum / tsum;
     ContrastRecord o;
     o.norm = norm[i];
     o.coef = (selected && psum != 0.f) ? -scale / ((r + 1e-12f) * tsum * tsum * temperature) : 0.f;
-    o.tsum = tsum; o.psum = psum; o.margin = __fadd_rn(__fmul_rn(mu, ai), nu); o.pad0 = o.pad1 = o.pad2 = 0.f;
+    o.tsum = tsum; o.psum = psum; o.margin = __fadd_rn(__fmul_rn(mu, ai), nu); o.nsum = nsum; o.pad1 = o.pad2 = 0.f;
     rec[i] = o;
 }
 
@@ -734,9 +764,10 @@ __global__ __launch_bounds__(256) void contrast_backward_mutual_kernel(
     if (n >= m) return;
     const float4 *h4 = reinterpret_cast<const float4 *>(unit);
     const float4 *rec4 = reinterpret_cast<const float4 *>(rec);
-    const float4 rn0 = rec4[(size_t)n * 2];       // norm, coef, tsum, psum
-    const float margin_n = rec[n].margin;
-    const float nn = rn0.x, coef_n = rn0.y, tsum_n = rn0.z, psum_n = rn0.w;
+    const float4 rn0 = rec4[(size_t)n * 2];       // norm, coef, (tsum: not read here), psum
+    const float4 rn1 = rec4[(size_t)n * 2 + 1];   // margin, nsum
+    const float margin_n = rn1.x, nsum_n = rn1.y;
+    const float nn = rn0.x, coef_n = rn0.y, psum_n = rn0.w;
     const float4 fn = h4[(size_t)n * LPR + q];
     const int e0 = rev[n], deg = rev[n + 1] - e0;
     const int *rev_edge = rev + m + 1;
@@ -766,8 +797,9 @@ __global__ __launch_bounds__(256) void contrast_backward_mutual_kernel(
         float4 v[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) x[u] = __shfl(myx, row0 | u, 64);
-        const float4 rx = myx >= 0 ? rec4[(size_t)myx * 2] : make_float4(1.f, 0.f, 1.f, 0.f);
-        const float mx = myx >= 0 ? rec[myx].margin : 0.f;
+        const float4 rx = myx >= 0 ? rec4[(size_t)myx * 2] : make_float4(1.f, 0.f, 1.f, 0.f);  // (only coef = 0 matters for an empty slot)
+        const float4 rx1 = myx >= 0 ? rec4[(size_t)myx * 2 + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float mx = rx1.x;
 #pragma unroll
         for (int u = 0; u < U; ++u) v[u] = x[u] >= 0 ? h4[(unsigned)x[u] * (unsigned)LPR + (unsigned)q] : make_float4(0.f, 0.f, 0.f, 0.f);
         float s[U], smine = 0.f;
@@ -784,21 +816,22 @@ __global__ __launch_bounds__(256) void contrast_backward_mutual_kernel(
             float g = 0.f;
             if (own) {
                 const float e = expf(__fdiv_rn(pos ? __fsub_rn(smine, margin_n) : smine, temperature));
-                g += coef_n * e * ((pos ? tsum_n : 0.f) - psum_n);
+                g += coef_n * e * (pos ? nsum_n : -psum_n);
             }
             if (inc != 0.f && rx.y != 0.f) {
                 const float e = expf(__fdiv_rn(pos ? __fsub_rn(smine, mx) : smine, temperature));
-                g += inc * (rx.y * e * ((pos ? rx.z : 0.f) - rx.w));
+                g += inc * (rx.y * e * (pos ? rx1.y : -rx.w));
             }
             gn = g / nn;
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const float gu = __shfl(gn, row0 | u, 64);
-            acc.x = __fmaf_rn(gu, __fmaf_rn(-s[u], fn.x, v[u].x), acc.x);
-            acc.y = __fmaf_rn(gu, __fmaf_rn(-s[u], fn.y, v[u].y), acc.y);
-            acc.z = __fmaf_rn(gu, __fmaf_rn(-s[u], fn.z, v[u].z), acc.z);
-            acc.w = __fmaf_rn(gu, __fmaf_rn(-s[u], fn.w, v[u].w), acc.w);
+            const float sn = nn > 1e-8f ? s[u] : 0.f;  // (no projection below the clamp)
+            acc.x = __fmaf_rn(gu, __fmaf_rn(-sn, fn.x, v[u].x), acc.x);
+            acc.y = __fmaf_rn(gu, __fmaf_rn(-sn, fn.y, v[u].y), acc.y);
+            acc.z = __fmaf_rn(gu, __fmaf_rn(-sn, fn.z, v[u].z), acc.z);
+            acc.w = __fmaf_rn(gu, __fmaf_rn(-sn, fn.w, v[u].w), acc.w);
         }
     }
 #pragma unroll

@@ -546,7 +546,10 @@ def contrast_mutual(neighbor_idx, a, dist2=None):
     0 < a <= 1 that point at it.  Coordinates and labels only: part of a stage's plan; ContrastStage's backward then
     gathers every gradient row (no float atomics).  dist2: the squared distances knnquery returned with neighbor_idx (the
     same view of them) when the lists are the self-search of the stage's cloud -- membership then follows from one distance
-    comparison per edge; None scans the neighbours' lists (any lists)."""
+    comparison per edge; None scans the neighbours' lists (any lists).
+    Precondition of the backward that uses this plan: the stage's posmask is SYMMETRIC on mutual edges (posmask[i, s] ==
+    posmask[x, j] when x = nidx[i, s] and nidx[x, j] = i), as every label-derived mask is (posmask_from_labels) -- the
+    receiving row reads the mask of an incoming mutual edge from its own list."""
     _need_gpu(neighbor_idx, a)
     _need_dtype(torch.float32, a=a)
     nptr, k, stride, keep = _nbr_view(neighbor_idx)
@@ -570,7 +573,9 @@ def contrast_mutual(neighbor_idx, a, dist2=None):
 class ContrastStage(Function):
     """Stage loss of ContrastHead.point_contrast_margin (MarginContrast.py:250-257): mean over the
     anchors with 0 < a <= 1 of the margin soft-NN loss on cosine similarities.  anchors: select_anchors(a) of
-    the same a, or None (every anchor is then visited and tested)."""
+    the same a, or None (every anchor is then visited and tested).  With `mutual` (the plan of contrast_mutual) the backward
+    gathers over mutual edges and needs posmask symmetric on them (equal classes: posmask_from_labels); without it, or with
+    rev = contrast_csr(...) alone, any mask is differentiated correctly."""
 
     @staticmethod
     def forward(ctx, features, neighbor_idx, posmask, a, mu, nu, temperature, anchors=None, rev=None, mutual=None):
@@ -653,7 +658,8 @@ class ContrastStageChannelMajor(Function):
     """contrast_stage on the decoder's channel-major embeddings f_cm (B, C, n) -- what the reference flattens into (B*n, C) rows
     first (pointnext_AA.py:518-519).  The point-major copy of f is never made: the forward writes the unit rows f_i / |f_i|
     through an LDS tile, the mutual-edge backward reads only those; its gradient rows go back through one tiled transpose.
-    Needs the mutual-edge plan (anchors, rev, mutual) and C in {16, 32, 64, 128, 256}: contrast_stage_supported_cm()."""
+    Needs the mutual-edge plan (anchors, rev, mutual) and C in {16, 32, 64, 128, 256}: contrast_stage_supported_cm() -- and,
+    with that plan, a posmask that is symmetric on mutual edges (label-derived: posmask_from_labels; see contrast_mutual)."""
 
     @staticmethod
     def forward(ctx, f_cm, neighbor_idx, posmask, a, mu, nu, temperature, anchors, rev, mutual):
@@ -671,8 +677,8 @@ class ContrastStageChannelMajor(Function):
         dev = f_cm.device
         norm = torch.empty(m, dtype=torch.float32, device=dev)
         unit = torch.empty(m, C, dtype=torch.float32, device=dev)
-        # the two sums of exponentials per anchor, kept for the backward's records; the cosines themselves are not stored (the
-        # mutual-edge backward recomputes the ones it needs from the unit rows it fetches anyway)
+        # two sums of exponentials per anchor (the positives', the negatives'), kept for the backward's records; the cosines
+        # themselves are not stored (the mutual-edge backward recomputes the ones it needs from the unit rows it fetches anyway)
         stats = torch.empty(m, 2, dtype=torch.float32, device=dev)
         loss_pt = torch.empty(m, dtype=torch.float32, device=dev)
         mean_cnt = torch.empty(2, dtype=torch.float32, device=dev)
