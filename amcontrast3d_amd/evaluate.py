@@ -11,6 +11,8 @@ files; what they compute is restated here on arrays the caller already holds:
     scatter_mean                torch_scatter.scatter(..., reduce='mean') of main_AA.py:662 (package absent here)
     validate_boundary_inner     main_AA.py:431-513
     test_cloud_boundary_inner   one iteration of the cloud loop of main_AA.py:556-684
+    test_room_scannet           the same iteration for a raw ScanNet room, split / gathered / voted on the device
+    scannet_benchmark_ids       main.py:652-659 (the label ids of the benchmark's submission files)
     summarize                   main_AA.py:484-506 / 746-770 (get_mious over the accumulated matrices)
 
 The model runs with model.eval(): BatchNorm uses its running statistics on the fused inference kernels
@@ -240,6 +242,80 @@ def test_cloud_boundary_inner(model, coord, feat, label, parts, num_classes, ign
         voted = scatter_mean(flat, index, size=label.shape[0]) if len(parts) > 1 else flat[torch.argsort(index)]
     pred = voted.argmax(dim=1)
     cm.update(pred, label)
+    if miou_B_I:
+        cm_b.update(torch.cat(pb), torch.cat(tb))
+        cm_i.update(torch.cat(pi), torch.cat(ti))
+    return {"pred": pred, "logits": voted, "cm": cm, "cm_b": cm_b, "cm_i": cm_i}
+
+
+# the benchmark's label id of each of the 20 training classes (dataset/scannetv2/scannet.py VALID_CLASS_IDS)
+SCANNET_VALID_CLASS_IDS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 24, 28, 33, 34, 36, 39)
+
+
+def scannet_benchmark_ids(pred):
+    """class indices 0..19 -> the ScanNet benchmark's label ids, as the `save_pred` text files hold them
+    (examples/segmentation/main.py:652-659).  pred: integer tensor or array; the result has its type."""
+    if torch.is_tensor(pred):
+        if pred.numel() and (int(pred.min()) < 0 or int(pred.max()) >= len(SCANNET_VALID_CLASS_IDS)):
+            raise ValueError("scannet_benchmark_ids: predictions must be class indices 0..19")
+        return torch.tensor(SCANNET_VALID_CLASS_IDS, dtype=pred.dtype, device=pred.device)[pred.long()]
+    pred = np.asarray(pred)
+    if pred.size and (pred.min() < 0 or pred.max() >= len(SCANNET_VALID_CLASS_IDS)):
+        raise ValueError("scannet_benchmark_ids: predictions must be class indices 0..19")
+    return np.asarray(SCANNET_VALID_CLASS_IDS, dtype=pred.dtype)[pred]
+
+
+@torch.no_grad()
+def test_room_scannet(model, coord, feat, label, voxel_size, num_classes, ignore_index, nsample,
+                      feature_keys="pos,x,heights", color_mean=None, color_std=None, gravity_dim=2, miou_B_I=False,
+                      batch=8, perm=None, generator=None, variable=False):
+    """One whole ScanNet room through the test loop (main.py:512-660 / main_AA.py:517-684 with `load_data`'s scannet
+    branch, `feature_keys: pos,x,heights`, `test: [PointsToTensor, NumpyChromaticNormalize]`), everything after the upload
+    on the device: coord - min, input_pipeline.room_parts, part_batch over `batch` sub-clouds at a time, the model,
+    ops.vote_parts.
+
+    coord (n,3) fp32, feat (n,3) fp32 in [-1, 1], label (n[,1]) or None (the `test` split): the raw .pth arrays (numpy or
+    tensors).  perm / generator: the shuffles of the sub-clouds (room_parts).  Confusion matrices as
+    test_cloud_boundary_inner fills them: all points from the voted prediction, boundary / inner from the per-sub-cloud
+    predictions.  The one deviation from the reference: the vote adds a point's logits in ascending sub-cloud order where
+    torch_scatter's atomics add them in any order.  Returns dict(pred, logits, cm, cm_b, cm_i); the matrices are None
+    without labels."""
+    from . import input_pipeline as ip
+    from . import ops
+    if variable:
+        raise ValueError("test_room_scannet: `variable: True` batches are not built (the ScanNet configs stack sub-clouds)")
+    model.eval()
+    dev = next(model.parameters()).device
+    up = lambda a: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dev)  # noqa: E731
+    coord, feat = up(coord), up(feat)
+    label = None if label is None else up(label).reshape(-1).long()
+    if miou_B_I and label is None:
+        raise ValueError("test_room_scannet: the boundary / inner split needs labels")
+    coord = coord - coord.min(0).values  # load_data: coord -= coord.min(0), in the array's own precision
+    rp = ip.room_parts(coord, voxel_size, perm=perm, generator=generator)
+    P, nvox = rp["parts"].shape
+    kw = {"gravity_dim": gravity_dim, "feature_keys": feature_keys}
+    if color_mean is not None:
+        kw["color_mean"] = color_mean
+    if color_std is not None:
+        kw["color_std"] = color_std
+    cm = cm_b = cm_i = None
+    if label is not None:
+        cm, cm_b, cm_i = _matrices(num_classes, ignore_index)
+    step = max(1, int(batch))
+    logits_all = torch.empty(P, num_classes, nvox, dtype=torch.float32, device=dev)
+    pb, pi, tb, ti = [], [], [], []
+    for j0 in range(0, P, step):
+        data = ip.part_batch(rp["parts"][j0:j0 + step], coord, feat, label, "test", **kw)
+        logits = _logits(model(data))
+        logits_all[j0:j0 + step] = logits
+        if miou_B_I:
+            b = boundary_masks_stacked(data["pos"], data["y"], nsample, num_classes, ignore_index)
+            pred_stack = logits.argmax(dim=1)
+            pb.append(pred_stack[b]); pi.append(pred_stack[~b]); tb.append(data["y"][b]); ti.append(data["y"][~b])
+    voted, pred = ops.vote_parts(logits_all, rp)
+    if label is not None:
+        cm.update(pred, label)
     if miou_B_I:
         cm_b.update(torch.cat(pb), torch.cat(tb))
         cm_i.update(torch.cat(pi), torch.cat(ti))

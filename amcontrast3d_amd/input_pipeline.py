@@ -28,7 +28,8 @@ def _coord_f32_or_f64(coord):
     return coord.contiguous()
 
 
-def _voxel_tables(coord, voxel_size):
+def _voxel_tables_raw(coord, voxel_size):
+    """the voxel tables at their allocated size (n) and the voxel count still on the device: no read-back"""
     coord = _coord_f32_or_f64(coord)
     n = coord.shape[0]
     dev = coord.device
@@ -46,6 +47,11 @@ def _voxel_tables(coord, voxel_size):
         _lib.check(fn(n, _ptr(coord), ctypes.c_double(float(voxel_size)), _ptr(key), _ptr(idx_sort),
                                       _ptr(voxel_idx), _ptr(start), _ptr(count), _ptr(nvox), _ptr(work), wb, _stream(coord)),
                    "voxelize")
+    return key, idx_sort, voxel_idx, start, count, nvox
+
+
+def _voxel_tables(coord, voxel_size):
+    key, idx_sort, voxel_idx, start, count, nvox = _voxel_tables_raw(coord, voxel_size)
     nv = int(nvox.item())  # the number of voxels sizes what follows: one read-back per cloud
     return key, idx_sort, voxel_idx, start[:nv + 1], count[:nv]
 
@@ -239,3 +245,126 @@ def scannet_train_batch(rooms, transform, voxel_size=0.02, voxel_max=64000, vari
                                                    P(out["pos"][b]), P(out["x"][b]), P(out["heights"][b]), P(out["y"][b]),
                                                    _stream(p)), "scannet_crop_tail")
     return out
+
+
+_SEG_KINDS = {"pos": 0, "x": 1, "heights": 2}
+SCANNET_COLOR_MEAN = (0.46259782, 0.46253258, 0.46253258)  # dataset/scannetv2/scannet.py:73-74
+SCANNET_COLOR_STD = (0.693565, 0.6852543, 0.68061745)
+
+
+_colour_cache = {}
+
+
+def _colour_constants(mean, std, dev):
+    """color_mean / color_std on the device, uploaded once per value and device (part_batch runs once per model call)"""
+    key = (mean, std, str(dev))
+    if key not in _colour_cache:
+        if len(mean) != 3 or len(std) != 3:
+            raise ValueError("part_batch: color_mean and color_std hold three values")
+        _colour_cache[key] = (torch.tensor(mean, dtype=torch.float32).to(dev), torch.tensor(std, dtype=torch.float32).to(dev))
+    return _colour_cache[key]
+
+
+def room_parts(coord, voxel_size, perm=None, generator=None, tables=None):
+    """The split of a whole room into sub-clouds of one point per voxel (`load_data`, main_AA.py:95-113, test_mode
+    'multi_voxel') on the device.  coord (n,3) fp32 or fp64 on the GPU, already shifted to its min corner.
+
+    Returns a dict: idx_sort (n), voxel_idx (n), start (nvox+1), count (nvox) int32 (the voxel tables), parts (P,nvox) int32
+    with P = count.max() -- part i holds the (i mod count)-th point of every voxel -- and where (P,nvox) int32, the position
+    of voxel v's point in part i.  perm (P,nvox): row i is the order of part i's voxels, the stand-in for the reference's
+    np.random.shuffle(idx_part); None draws the rows on the device from `generator`.  tables: given idx_sort / count
+    [/ start / voxel_idx] instead of a voxelisation (numpy's argsort is unstable, so the order inside a voxel is the
+    reference's to choose; the tests pass its own).  One read-back: nvox and count.max() together."""
+    _need_gpu(coord)
+    dev = coord.device
+    n = coord.shape[0]
+    if tables is None:
+        _, idx_sort, voxel_idx, start, count, nvox = _voxel_tables_raw(coord, voxel_size)
+        live = torch.arange(n, device=dev, dtype=torch.int32) < nvox
+        nv, P = torch.cat([nvox, torch.where(live, count, 0).max().reshape(1)]).tolist()
+        start, count = start[:nv + 1], count[:nv]
+    else:
+        as_i32 = lambda t: torch.as_tensor(t).to(device=dev, dtype=torch.int32).contiguous()  # noqa: E731
+        idx_sort, count = as_i32(tables["idx_sort"]), as_i32(tables["count"])
+        nv = count.shape[0]
+        ends = count.cumsum(0, dtype=torch.int32)
+        start = as_i32(tables["start"]) if tables.get("start") is not None else torch.cat([ends.new_zeros(1), ends])
+        voxel_idx = (as_i32(tables["voxel_idx"]) if tables.get("voxel_idx") is not None else
+                     torch.repeat_interleave(torch.arange(nv, device=dev, dtype=torch.int32), count.long()))
+        P = int(count.max().item())
+        if idx_sort.shape != (n,) or voxel_idx.shape != (n,) or start.shape != (nv + 1,):
+            raise ValueError("room_parts: tables need idx_sort (n), voxel_idx (n), start (nvox+1), count (nvox)")
+    if perm is None:
+        perm = torch.rand(P, nv, device=dev, generator=generator).argsort(dim=1).int()
+    else:
+        perm = torch.as_tensor(perm).to(device=dev, dtype=torch.int32).contiguous()
+        if perm.shape != (P, nv) or not bool((perm.sort(dim=1).values == torch.arange(nv, device=dev, dtype=torch.int32)).all()):
+            raise ValueError(f"room_parts: perm must hold {P} permutations of the {nv} voxel ids")
+    parts = torch.empty(P, nv, dtype=torch.int32, device=dev)
+    where = torch.empty(P, nv, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().amc3d_room_parts(P, nv, n, _ptr(start), _ptr(count), _ptr(idx_sort), _ptr(perm), _ptr(parts),
+                                                _ptr(where), _stream(coord)), "room_parts")
+    return {"idx_sort": idx_sort, "voxel_idx": voxel_idx, "start": start, "count": count, "parts": parts, "where": where}
+
+
+def part_batch(idx, coord, feat, label=None, mode="test", color_mean=SCANNET_COLOR_MEAN, color_std=SCANNET_COLOR_STD,
+               gravity_dim=2, feature_keys="pos,x,heights"):
+    """Sub-clouds of a room as a model batch (csrc/room_eval.hip).  idx (R,n) int32 rows of point indices into coord (N,3)
+    fp32, feat (N,3) fp32 in [-1, 1] (the .pth colours), label (N) int64 or None.  Per row: pos = coordinate minus the
+    row's minimum corner; colours `mode` 'test' clip((f + 1) / 2, 0, 1) (`load_data`) or 'val' (f + 1) * 127.5
+    (ScanNet.__getitem__), then NumpyChromaticNormalize per row; heights = pos[..., gravity_dim]; x assembled channel-major
+    from `feature_keys` (get_features_by_keys).  Returns {pos (R,n,3), x (R,Cx,n), heights (R,n,1)[, y (R,n) int64]}."""
+    _need_gpu(idx, coord, feat)
+    _need_dtype(torch.int32, idx=idx)
+    _need_dtype(torch.float32, coord=coord, feat=feat)
+    if mode not in ("test", "val"):
+        raise ValueError(f"part_batch: mode {mode!r} (test or val)")
+    keys = [k.strip() for k in feature_keys.split(",")]
+    if not 1 <= len(keys) <= 3 or any(k not in _SEG_KINDS for k in keys):
+        raise ValueError(f"part_batch: feature_keys {feature_keys!r}: up to three of pos, x, heights")
+    if idx.dim() != 2 or coord.dim() != 2 or coord.shape[1] != 3 or feat.shape != coord.shape:
+        raise ValueError("part_batch: idx (R,n), coord (N,3), feat (N,3)")
+    dev = coord.device
+    idx, coord, feat = idx.contiguous(), coord.contiguous(), feat.contiguous()
+    R, n = idx.shape
+    N = coord.shape[0]
+    cx = sum(1 if k == "heights" else 3 for k in keys)
+    out = {"pos": torch.empty(R, n, 3, dtype=torch.float32, device=dev),
+           "x": torch.empty(R, cx, n, dtype=torch.float32, device=dev),
+           "heights": torch.empty(R, n, 1, dtype=torch.float32, device=dev)}
+    y = None
+    if label is not None:
+        _need_gpu(label)
+        label = label.reshape(-1).to(torch.int64).contiguous()
+        if label.shape[0] != N:
+            raise ValueError("part_batch: one label per room point")
+        y = out["y"] = torch.empty(R, n, dtype=torch.int64, device=dev)
+    lib = _lib.load()
+    wb = int(lib.amc3d_part_batch_workspace_bytes(R))
+    work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
+    kinds = (ctypes.c_int * 3)(*([_SEG_KINDS[k] for k in keys] + [0] * (3 - len(keys))))
+    mean, std = _colour_constants(tuple(float(v) for v in color_mean), tuple(float(v) for v in color_std), dev)
+    P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(lib.amc3d_part_batch(R, n, N, 1 if mode == "val" else 0, int(gravity_dim), len(keys),
+                                        ctypes.cast(kinds, ctypes.c_void_p), P(idx), P(coord), P(feat), P(label), P(mean), P(std),
+                                        P(out["pos"]), P(out["x"]), P(out["heights"]), P(y), P(work), wb, _stream(coord)),
+                   "part_batch")
+    return out
+
+
+def scannet_val_cloud(room, voxel_size=0.02, rnd=None, generator=None, color_mean=SCANNET_COLOR_MEAN,
+                      color_std=SCANNET_COLOR_STD, gravity_dim=2, feature_keys="pos,x,heights"):
+    """The val item of ScanNet.__getitem__ with `presample: True`, `voxel_max: null`, `val: [NumpyChromaticNormalize]`
+    (dataset/scannetv2/scannet.py:114-176): crop_pc at load time (min-corner shift, voxelize mode 0, min-corner shift; no
+    crop and no shuffle without voxel_max), then colours (f + 1) * 127.5, the normalisation and heights.
+    room: (coord (n,3) fp32, feat (n,3) fp32 in [-1, 1], label (n[,1])) GPU tensors.  rnd: voxelize's randint(0, count.max(),
+    nvox), drawn from `generator` when None.  Returns {pos (1,n,3), x (1,Cx,n), heights (1,n,1), y (1,n)}: one batch of
+    evaluate.validate_boundary_inner."""
+    coord, feat, label = room
+    _need_gpu(coord, feat, label)
+    _need_dtype(torch.float32, coord=coord, feat=feat)
+    coord = coord - coord.min(0).values
+    sel = voxelize(coord, voxel_size, rnd=rnd, generator=generator).int()
+    return part_batch(sel.view(1, -1), coord, feat, label, "val", color_mean, color_std, gravity_dim, feature_keys)

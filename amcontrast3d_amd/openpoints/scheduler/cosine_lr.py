@@ -1,4 +1,4 @@
-"""Learning-rate schedule of the trainer: cosine decay with optional linear warm-up
+"""Learning-rate schedule of the trainer: cosine decay with optional linear warm-up, and the factory of both schedules
 (openpoints/scheduler/cosine_lr.py:18-119, scheduler_factory.py:12-60; the shipped configs: ``sched: cosine``,
 ``epochs: 100``, ``min_lr: 1e-5``, ``warmup_epochs: 0``, cfgs/s3dis/default.yaml:71-76).
 
@@ -88,14 +88,23 @@ class CosineLRScheduler:
 
 
 def build_scheduler_from_cfg(args, optimizer, return_epochs=False):
-    """scheduler_factory.py:12-60 for ``sched: cosine``"""
-    if getattr(args, "sched", "cosine") != "cosine":
-        raise NotImplementedError(f"scheduler {args.sched!r}: the AMContrast3D configs use 'cosine'")
+    """scheduler_factory.py:12-86 for ``sched: cosine`` and ``sched: multistep``"""
+    name = getattr(args, "sched", "cosine")
+    if name not in ("cosine", "multistep"):
+        raise NotImplementedError(f"scheduler {name!r}: the AMContrast3D configs use 'cosine' and 'multistep'")
+    if getattr(args, "lr_noise", None) is not None:
+        raise NotImplementedError("lr noise is not part of the AMContrast3D configs")
     num_epochs = args.epochs
+    warmup = dict(warmup_lr_init=getattr(args, "warmup_lr", 1.0e-6), warmup_t=getattr(args, "warmup_epochs", 0))
+    if name == "multistep":
+        from .multistep_lr import MultiStepLRScheduler
+        decay_rate = getattr(args, "decay_rate", None) or getattr(args, "final_decay_rate", 0.01) ** (1 / num_epochs)
+        sched = MultiStepLRScheduler(optimizer, decay_t=getattr(args, "decay_epochs", 1), decay_rate=decay_rate, **warmup)
+        return (sched, num_epochs) if return_epochs else sched
     min_lr = args.min_lr if getattr(args, "min_lr", False) else args.lr / 1000.
     sched = CosineLRScheduler(optimizer, t_initial=getattr(args, "t_max", num_epochs), lr_min=min_lr,
-                              warmup_lr_init=getattr(args, "warmup_lr", 1.0e-6), warmup_t=getattr(args, "warmup_epochs", 0),
                               k_decay=getattr(args, "lr_k_decay", 1.0), cycle_mul=getattr(args, "lr_cycle_mul", 1.),
-                              cycle_decay=getattr(args, "lr_cycle_decay", 0.1), cycle_limit=getattr(args, "lr_cycle_limit", 1))
+                              cycle_decay=getattr(args, "lr_cycle_decay", 0.1), cycle_limit=getattr(args, "lr_cycle_limit", 1),
+                              **warmup)
     num_epochs = sched.get_cycle_length() + getattr(args, "cooldown_epochs", 0)
     return (sched, num_epochs) if return_epochs else sched

@@ -2081,3 +2081,30 @@ def sa_tail_supported(c1, c2, k):
 
 def sa_tail_pays(c1, c2):
     return bool(_lib.load().amc3d_sa_tail_pays(int(c1), int(c2)))
+
+
+def vote_parts(logits, parts_tables):
+    """The vote of whole-room testing over a voxel partition (csrc/room_eval.hip): logits (P,C,nvox) fp32, the stacked
+    model outputs of the P sub-clouds of input_pipeline.room_parts, whose result is `parts_tables` -> (voted (N,C) fp32,
+    pred (N) int64).  A point of rank r in a voxel of count c lies in parts r, r + c, ... < P; its logits are summed in
+    that order and divided by their number, so the bits do not change from run to run (torch_scatter's mean, main_AA.py:662,
+    sums in the order its atomics land).  pred = argmax as torch.argmax (first maximum, NaN counts as maximum)."""
+    t = parts_tables
+    _need_gpu(logits, t["where"], t["start"], t["count"], t["idx_sort"], t["voxel_idx"])
+    _need_dtype(torch.float32, logits=logits)
+    _need_dtype(torch.int32, where=t["where"], start=t["start"], count=t["count"], idx_sort=t["idx_sort"],
+                voxel_idx=t["voxel_idx"])
+    logits = logits.contiguous()
+    P, C, nvox = logits.shape
+    N = t["idx_sort"].shape[0]
+    if t["where"].shape != (P, nvox) or t["count"].shape != (nvox,) or t["start"].shape[0] < nvox or t["voxel_idx"].shape != (N,):
+        raise ValueError(f"vote_parts: logits {tuple(logits.shape)} do not belong to these tables "
+                         f"(where {tuple(t['where'].shape)}, {t['count'].shape[0]} voxels)")
+    voted = torch.empty(N, C, dtype=torch.float32, device=logits.device)
+    pred = torch.empty(N, dtype=torch.int64, device=logits.device)
+    with torch.cuda.device(logits.device), timing.span("vote_parts", logits.numel() * 4 + N * C * 4 + N * 28):
+        _lib.check(_lib.load().amc3d_vote_parts(N, P, C, nvox, _ptr(logits), _ptr(t["where"].contiguous()),
+                                                _ptr(t["start"].contiguous()), _ptr(t["count"].contiguous()),
+                                                _ptr(t["idx_sort"].contiguous()), _ptr(t["voxel_idx"].contiguous()),
+                                                _ptr(voted), _ptr(pred), _stream(logits)), "vote_parts")
+    return voted, pred

@@ -676,6 +676,28 @@ int amc3d_scannet_crop_tail(int n, int gravity_dim, const double *coord, const f
                             const int *crop, const int *perm, float *pos_out, float *x_out, float *heights, long long *y_out,
                             void *stream);
 
+/* ---- ScanNet validation / whole-room testing (main_AA.py:71-116 `load_data`, :574-611 the sub-cloud loop, :662-671 the vote;
+ * dataset/scannetv2/scannet.py:140-176 the val item).  Voxel tables as amc3d_voxelize writes them for a room of npts points.
+ * room_parts: p = count.max() sub-clouds of one point per voxel; perm (p,nvox): row i a permutation of the voxel ids (the
+ * stand-in for np.random.shuffle) -> parts[i,j] = idx_sort[start[v] + i % count[v]], v = perm[i,j]; where[i,v] = j.  One launch.
+ * part_batch: rows of an index matrix idx (rows,n) into coord (npts,3), feat (npts,3) [, label (npts) int64] -> pos (rows,n,3) =
+ * coordinate - the row's fp32 minimum corner; colours by mode (0 test: clip((f + 1) / 2, 0, 1); 1 val: (f + 1) * 127.5), / 255
+ * when the row's maximum exceeds 1 (NaN propagates: then not), (x - mean) / std; heights (rows,n) = pos[..., gravity_dim];
+ * x (rows,Cx,n) channel-major = nseg <= 3 segments in the caller's order, seg_kinds[i] in {0 pos, 1 x, 2 heights}
+ * (get_features_by_keys); y (rows,n) int64 when y_out is not NULL.  Two launches through the workspace.
+ * vote_parts: logits (p,num_classes,nvox) = the stacked model outputs -> voted (npts,num_classes) = the mean over the parts that
+ * hold the point (rank r of count c: parts r, r + c, ... < p), summed in ascending part order in fp32 and divided by their
+ * number; pred (npts) int64 = the first maximum, a NaN counting as the maximum (torch.argmax).  No atomics: reproducible bits. */
+int amc3d_room_parts(int p, int nvox, int npts, const int *start, const int *count, const int *idx_sort, const int *perm,
+                     int *parts, int *where, void *stream);
+size_t amc3d_part_batch_workspace_bytes(int rows);
+int amc3d_part_batch(int rows, int n, int npts, int mode, int gravity_dim, int nseg, const int *seg_kinds, const int *idx,
+                     const float *coord, const float *feat, const long long *label, const float *color_mean,
+                     const float *color_std, float *pos_out, float *x_out, float *heights, long long *y_out, void *workspace,
+                     size_t workspace_bytes, void *stream);
+int amc3d_vote_parts(int npts, int p, int num_classes, int nvox, const float *logits, const int *where, const int *start,
+                     const int *count, const int *idx_sort, const int *voxel_idx, float *voted, long long *pred, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
