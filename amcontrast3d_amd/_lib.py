@@ -107,6 +107,10 @@ SIGNATURES = {
     "amc3d_part_batch_workspace_bytes": (_sz, [_i]),
     "amc3d_part_batch": (_i, [_i] * 6 + [_vp] * 12 + [_sz, _vp]),
     "amc3d_vote_parts": (_i, [_i, _i, _i, _i] + [_vp] * 8 + [_vp]),
+    "amc3d_s3dis_part_batch_workspace_bytes": (_sz, [_i]),
+    "amc3d_s3dis_part_batch": (_i, [_i] * 7 + [_vp] * 14 + [_sz, _vp]),
+    "amc3d_room_representatives": (_i, [_i, _i] + [_vp] * 7 + [_vp]),
+    "amc3d_expand_parts": (_i, [_i, _i, _i] + [_vp] * 6 + [_vp]),
     "amc3d_local_aggregation_supported": (_i, [_i, _i]),
     "amc3d_group_moments_bytes": (_sz, [_i, _i]),
     "amc3d_group_moments": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),

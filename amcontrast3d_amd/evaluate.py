@@ -13,6 +13,7 @@ files; what they compute is restated here on arrays the caller already holds:
     test_cloud_boundary_inner   one iteration of the cloud loop of main_AA.py:556-684
     test_room_scannet           the same iteration for a raw ScanNet room, split / gathered / voted on the device
     scannet_benchmark_ids       main.py:652-659 (the label ids of the benchmark's submission files)
+    test_room_s3dis             the same iteration for a raw S3DIS room with the config's evaluation transforms, on the device
     summarize                   main_AA.py:484-506 / 746-770 (get_mious over the accumulated matrices)
 
 The model runs with model.eval(): BatchNorm uses its running statistics on the fused inference kernels
@@ -314,6 +315,72 @@ def test_room_scannet(model, coord, feat, label, voxel_size, num_classes, ignore
             pred_stack = logits.argmax(dim=1)
             pb.append(pred_stack[b]); pi.append(pred_stack[~b]); tb.append(data["y"][b]); ti.append(data["y"][~b])
     voted, pred = ops.vote_parts(logits_all, rp)
+    if label is not None:
+        cm.update(pred, label)
+    if miou_B_I:
+        cm_b.update(torch.cat(pb), torch.cat(tb))
+        cm_i.update(torch.cat(pi), torch.cat(ti))
+    return {"pred": pred, "logits": voted, "cm": cm, "cm_b": cm_b, "cm_i": cm_i}
+
+
+@torch.no_grad()
+def test_room_s3dis(model, cdata, voxel_size, num_classes, ignore_index, nsample, feature_keys="x,heights", color_mean=None,
+                    color_std=None, gravity_dim=2, miou_B_I=False, batch=8, test_mode="multi_voxel", perm=None, rnd=None,
+                    generator=None, variable=False):
+    """One whole S3DIS room through the test loop (main.py:512-612 / main_AA.py:517-684 with `load_data`'s s3dis branch and
+    the transforms of cfgs/s3dis/default.yaml, `val: [PointsToTensor, PointCloudXYZAlign, ChromaticNormalize]`, which test()
+    uses for want of a `test` list), everything after the upload on the device: coord - min, input_pipeline.room_parts or
+    room_representatives, s3dis_part_batch over `batch` sub-clouds at a time, the model, ops.vote_parts or expand_parts.
+
+    cdata (n,7) or (n,6): the raw .npy array, float64 or float32 (numpy or tensor): xyz, rgb 0..255 [, label]; the arithmetic
+    before the cast to float32 is in its dtype, as numpy's is.  test_mode 'multi_voxel' (perm / generator: the shuffles, as in
+    room_parts) or 'nearest_neighbor' (rnd, perm, generator: room_representatives).  Confusion matrices as
+    test_cloud_boundary_inner fills them.  Deviations from the reference: the xy-centre of a sub-cloud is the fixed-order fp64
+    mean rounded once (torch.mean's last bit depends on the host), the vote adds in ascending sub-cloud order, and a room
+    whose voxels all hold one point is voted over its one part (the reference then takes its nearest-neighbour branch with
+    tables it never built).  6-fold testing is `all_cm.value += r["cm"].value` over the rooms of every area.
+    Returns dict(pred, logits, cm, cm_b, cm_i); the matrices are None without labels."""
+    from . import input_pipeline as ip
+    from . import ops
+    if variable:
+        raise ValueError("test_room_s3dis: `variable: True` batches are not built (sub-clouds of one room are stacked)")
+    if test_mode not in ("multi_voxel", "nearest_neighbor"):
+        raise ValueError(f"test_room_s3dis: test_mode {test_mode!r} (multi_voxel or nearest_neighbor)")
+    model.eval()
+    dev = next(model.parameters()).device
+    cdata = (cdata if torch.is_tensor(cdata) else torch.from_numpy(np.ascontiguousarray(cdata))).to(dev)
+    if cdata.dim() != 2 or cdata.shape[1] not in (6, 7) or cdata.dtype not in (torch.float32, torch.float64):
+        raise ValueError("test_room_s3dis: cdata (n,7) or (n,6), float32 or float64: xyz, rgb [, label]")
+    label = cdata[:, 6].long() if cdata.shape[1] == 7 else None
+    if miou_B_I and label is None:
+        raise ValueError("test_room_s3dis: the boundary / inner split needs labels")
+    coord = cdata[:, :3] - cdata[:, :3].min(0).values  # load_data: coord -= coord.min(0), in the file's own precision
+    colour = cdata[:, 3:6].contiguous()
+    if test_mode == "nearest_neighbor":
+        rp = ip.room_representatives(coord, voxel_size, rnd=rnd, perm=perm, generator=generator)
+    else:
+        rp = ip.room_parts(coord, voxel_size, perm=perm, generator=generator)
+    P, nvox = rp["parts"].shape
+    kw = {"gravity_dim": gravity_dim, "feature_keys": feature_keys}
+    if color_mean is not None:
+        kw["color_mean"] = color_mean
+    if color_std is not None:
+        kw["color_std"] = color_std
+    cm = cm_b = cm_i = None
+    if label is not None:
+        cm, cm_b, cm_i = _matrices(num_classes, ignore_index)
+    step = max(1, int(batch))
+    logits_all = torch.empty(P, num_classes, nvox, dtype=torch.float32, device=dev)
+    pb, pi, tb, ti = [], [], [], []
+    for j0 in range(0, P, step):
+        data = ip.s3dis_part_batch(rp["parts"][j0:j0 + step], coord, colour, label, "test", **kw)
+        logits = _logits(model(data))
+        logits_all[j0:j0 + step] = logits
+        if miou_B_I:
+            b = boundary_masks_stacked(data["pos"], data["y"], nsample, num_classes, ignore_index)
+            pred_stack = logits.argmax(dim=1)
+            pb.append(pred_stack[b]); pi.append(pred_stack[~b]); tb.append(data["y"][b]); ti.append(data["y"][~b])
+    voted, pred = ops.expand_parts(logits_all, rp) if test_mode == "nearest_neighbor" else ops.vote_parts(logits_all, rp)
     if label is not None:
         cm.update(pred, label)
     if miou_B_I:

@@ -255,26 +255,18 @@ SCANNET_COLOR_STD = (0.693565, 0.6852543, 0.68061745)
 _colour_cache = {}
 
 
-def _colour_constants(mean, std, dev):
+def _colour_constants(mean, std, dev, who="part_batch"):
     """color_mean / color_std on the device, uploaded once per value and device (part_batch runs once per model call)"""
     key = (mean, std, str(dev))
     if key not in _colour_cache:
         if len(mean) != 3 or len(std) != 3:
-            raise ValueError("part_batch: color_mean and color_std hold three values")
+            raise ValueError(f"{who}: color_mean and color_std hold three values")
         _colour_cache[key] = (torch.tensor(mean, dtype=torch.float32).to(dev), torch.tensor(std, dtype=torch.float32).to(dev))
     return _colour_cache[key]
 
 
-def room_parts(coord, voxel_size, perm=None, generator=None, tables=None):
-    """The split of a whole room into sub-clouds of one point per voxel (`load_data`, main_AA.py:95-113, test_mode
-    'multi_voxel') on the device.  coord (n,3) fp32 or fp64 on the GPU, already shifted to its min corner.
-
-    Returns a dict: idx_sort (n), voxel_idx (n), start (nvox+1), count (nvox) int32 (the voxel tables), parts (P,nvox) int32
-    with P = count.max() -- part i holds the (i mod count)-th point of every voxel -- and where (P,nvox) int32, the position
-    of voxel v's point in part i.  perm (P,nvox): row i is the order of part i's voxels, the stand-in for the reference's
-    np.random.shuffle(idx_part); None draws the rows on the device from `generator`.  tables: given idx_sort / count
-    [/ start / voxel_idx] instead of a voxelisation (numpy's argsort is unstable, so the order inside a voxel is the
-    reference's to choose; the tests pass its own).  One read-back: nvox and count.max() together."""
+def _room_tables(coord, voxel_size, tables, who):
+    """the voxel tables of a room, from the device's voxelisation or from `tables`, with nvox and count.max() (one read-back)"""
     _need_gpu(coord)
     dev = coord.device
     n = coord.shape[0]
@@ -293,7 +285,23 @@ def room_parts(coord, voxel_size, perm=None, generator=None, tables=None):
                      torch.repeat_interleave(torch.arange(nv, device=dev, dtype=torch.int32), count.long()))
         P = int(count.max().item())
         if idx_sort.shape != (n,) or voxel_idx.shape != (n,) or start.shape != (nv + 1,):
-            raise ValueError("room_parts: tables need idx_sort (n), voxel_idx (n), start (nvox+1), count (nvox)")
+            raise ValueError(f"{who}: tables need idx_sort (n), voxel_idx (n), start (nvox+1), count (nvox)")
+    return idx_sort, voxel_idx, start, count, nv, P
+
+
+def room_parts(coord, voxel_size, perm=None, generator=None, tables=None):
+    """The split of a whole room into sub-clouds of one point per voxel (`load_data`, main_AA.py:95-113, test_mode
+    'multi_voxel') on the device.  coord (n,3) fp32 or fp64 on the GPU, already shifted to its min corner.
+
+    Returns a dict: idx_sort (n), voxel_idx (n), start (nvox+1), count (nvox) int32 (the voxel tables), parts (P,nvox) int32
+    with P = count.max() -- part i holds the (i mod count)-th point of every voxel -- and where (P,nvox) int32, the position
+    of voxel v's point in part i.  perm (P,nvox): row i is the order of part i's voxels, the stand-in for the reference's
+    np.random.shuffle(idx_part); None draws the rows on the device from `generator`.  tables: given idx_sort / count
+    [/ start / voxel_idx] instead of a voxelisation (numpy's argsort is unstable, so the order inside a voxel is the
+    reference's to choose; the tests pass its own).  One read-back: nvox and count.max() together."""
+    idx_sort, voxel_idx, start, count, nv, P = _room_tables(coord, voxel_size, tables, "room_parts")
+    dev = coord.device
+    n = coord.shape[0]
     if perm is None:
         perm = torch.rand(P, nv, device=dev, generator=generator).argsort(dim=1).int()
     else:
@@ -368,3 +376,136 @@ def scannet_val_cloud(room, voxel_size=0.02, rnd=None, generator=None, color_mea
     coord = coord - coord.min(0).values
     sel = voxelize(coord, voxel_size, rnd=rnd, generator=generator).int()
     return part_batch(sel.view(1, -1), coord, feat, label, "val", color_mean, color_std, gravity_dim, feature_keys)
+
+
+S3DIS_COLOR_MEAN = (0.5136457, 0.49523646, 0.44921124)  # transforms/point_transformer_gpu.py:398-399 (ChromaticNormalize)
+S3DIS_COLOR_STD = (0.18308958, 0.18415008, 0.19252081)
+
+
+def s3dis_part_batch(idx, coord, colour, label=None, mode="test", color_mean=S3DIS_COLOR_MEAN, color_std=S3DIS_COLOR_STD,
+                     gravity_dim=2, feature_keys="x,heights", centre=None):
+    """Sub-clouds of an S3DIS room as a model batch with the config's evaluation transforms `[PointsToTensor,
+    PointCloudXYZAlign, ChromaticNormalize]` (csrc/s3dis_eval.hip).  idx (R,n) int32 rows of point indices into coord (N,3),
+    fp32 or fp64 and already at the room's minimum corner, colour (N,3) raw 0..255 in coord's dtype, label (N) or None.
+    mode 'test' (`load_data` + the sub-cloud loop, main.py:73, 563-576): colour clip(f / 255, 0, 1) and coordinates minus the
+    row's minimum corner, both in coord's dtype, then float32; 'val' (S3DIS.__getitem__, fp32 only): both as they are.
+    heights = that coordinate's gravity column, before the alignment; pos = it minus the row's centre, then the gravity column
+    minus its minimum; colours / 255 if the row's maximum exceeds 1, then (x - color_mean) / color_std; x assembled
+    channel-major from `feature_keys` (get_features_by_keys).
+    centre: the reference's torch.mean sums in an order that depends on the host's vector width and thread count, so its last
+    bit is not specified; here it is the fp64 column sum in a fixed order, divided by n and rounded once to float32 (the same
+    bits on every run, within 2 ulp of torch.mean on the fixture's sub-clouds).  A given centre (R,3) fp32 replaces it.
+    Returns {pos (R,n,3), x (R,Cx,n), heights (R,n,1)[, y (R,n) int64], centre (R,3)}."""
+    _need_gpu(idx, coord, colour)
+    _need_dtype(torch.int32, idx=idx)
+    if coord.dtype not in (torch.float32, torch.float64) or colour.dtype != coord.dtype:
+        raise RuntimeError(f"s3dis_part_batch: coord and colour are both float32 or both float64, got {coord.dtype} and {colour.dtype}")
+    if mode not in ("test", "val"):
+        raise ValueError(f"s3dis_part_batch: mode {mode!r} (test or val)")
+    f64 = coord.dtype == torch.float64
+    if mode == "val" and f64:
+        raise ValueError("s3dis_part_batch: the val item is float32 (S3DIS casts the room when it loads it)")
+    keys = [k.strip() for k in feature_keys.split(",")]
+    if not 1 <= len(keys) <= 3 or any(k not in _SEG_KINDS for k in keys):
+        raise ValueError(f"s3dis_part_batch: feature_keys {feature_keys!r}: up to three of pos, x, heights")
+    if idx.dim() != 2 or coord.dim() != 2 or coord.shape[1] != 3 or colour.shape != coord.shape:
+        raise ValueError("s3dis_part_batch: idx (R,n), coord (N,3), colour (N,3)")
+    if gravity_dim not in (0, 1, 2):
+        raise ValueError("s3dis_part_batch: gravity_dim is 0, 1 or 2")
+    dev = coord.device
+    idx, coord, colour = idx.contiguous(), coord.contiguous(), colour.contiguous()
+    R, n = idx.shape
+    N = coord.shape[0]
+    cx = sum(1 if k == "heights" else 3 for k in keys)
+    out = {"pos": torch.empty(R, n, 3, dtype=torch.float32, device=dev),
+           "x": torch.empty(R, cx, n, dtype=torch.float32, device=dev),
+           "heights": torch.empty(R, n, 1, dtype=torch.float32, device=dev)}
+    y = None
+    if label is not None:
+        _need_gpu(label)
+        label = label.reshape(-1).to(torch.int64).contiguous()
+        if label.shape[0] != N:
+            raise ValueError("s3dis_part_batch: one label per room point")
+        y = out["y"] = torch.empty(R, n, dtype=torch.int64, device=dev)
+    if centre is not None:
+        _need_gpu(centre)
+        _need_dtype(torch.float32, centre=centre)
+        if centre.shape != (R, 3):
+            raise ValueError("s3dis_part_batch: centre (R,3)")
+        centre = centre.contiguous()
+    out["centre"] = torch.empty(R, 3, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    wb = int(lib.amc3d_s3dis_part_batch_workspace_bytes(R))
+    work = torch.empty(max(wb, 8) // 8, dtype=torch.float64, device=dev)
+    kinds = (ctypes.c_int * 3)(*([_SEG_KINDS[k] for k in keys] + [0] * (3 - len(keys))))
+    mean, std = _colour_constants(tuple(float(v) for v in color_mean), tuple(float(v) for v in color_std), dev,
+                                  "s3dis_part_batch")
+    P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(lib.amc3d_s3dis_part_batch(R, n, N, 1 if mode == "val" else 0, int(f64), int(gravity_dim), len(keys),
+                                              ctypes.cast(kinds, ctypes.c_void_p), P(idx), P(coord), P(colour), P(label), P(mean),
+                                              P(std), P(centre), P(out["pos"]), P(out["x"]), P(out["heights"]), P(y),
+                                              P(out["centre"]), P(work), wb, _stream(coord)), "s3dis_part_batch")
+    return out
+
+
+def room_representatives(coord, voxel_size, rnd=None, perm=None, generator=None, tables=None):
+    """The single sub-cloud of `test_mode: nearest_neighbor` (`load_data`, main.py:96-104) on the device: one point of every
+    voxel, the (rnd[v] % count[v])-th, in the order of `perm`.  coord (n,3) fp32 or fp64 on the GPU, already shifted to its
+    min corner.  rnd (nvox): the reference's np.random.randint(0, count.max(), count.size); perm (nvox): its
+    np.random.permutation; both drawn on the device from `generator` when None.  tables: as in room_parts.
+    Returns the voxel tables idx_sort (n), voxel_idx (n), start (nvox+1), count (nvox) plus parts (1,nvox) and where (1,nvox),
+    the inverse of perm (the reference's reverse_idx_part), all int32: what s3dis_part_batch and ops.expand_parts take."""
+    idx_sort, voxel_idx, start, count, nv, P = _room_tables(coord, voxel_size, tables, "room_representatives")
+    dev = coord.device
+    n = coord.shape[0]
+    if rnd is None:
+        rnd = torch.randint(0, max(P, 1), (nv,), device=dev, generator=generator, dtype=torch.int32)
+    else:
+        rnd = torch.as_tensor(rnd).to(device=dev, dtype=torch.int32).contiguous()
+        if rnd.shape != (nv,) or (nv and int(rnd.min()) < 0):
+            raise ValueError(f"room_representatives: rnd holds one draw >= 0 for each of the {nv} voxels")
+    if perm is None:
+        perm = torch.rand(nv, device=dev, generator=generator).argsort().int()
+    else:
+        perm = torch.as_tensor(perm).to(device=dev, dtype=torch.int32).contiguous()
+        if perm.shape != (nv,) or not bool((perm.sort().values == torch.arange(nv, device=dev, dtype=torch.int32)).all()):
+            raise ValueError(f"room_representatives: perm must be a permutation of the {nv} voxel ids")
+    parts = torch.empty(1, nv, dtype=torch.int32, device=dev)
+    where = torch.empty(1, nv, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().amc3d_room_representatives(nv, n, _ptr(start), _ptr(count), _ptr(idx_sort), _ptr(rnd), _ptr(perm),
+                                                          _ptr(parts), _ptr(where), _stream(coord)), "room_representatives")
+    return {"idx_sort": idx_sort, "voxel_idx": voxel_idx, "start": start, "count": count, "parts": parts, "where": where}
+
+
+def s3dis_val_cloud(cdata, voxel_size=0.04, rnd=None, generator=None, color_mean=S3DIS_COLOR_MEAN, color_std=S3DIS_COLOR_STD,
+                    gravity_dim=2, feature_keys="x,heights", centre=None, tables=None):
+    """The val item of S3DIS.__getitem__ with `presample: True`, `voxel_max: null`, `val: [PointsToTensor, PointCloudXYZAlign,
+    ChromaticNormalize]` (dataset/s3dis/s3dis.py:94-144): the raw room cast to float32, shifted to its minimum corner,
+    voxelize mode 0 (one random point per voxel), then the three transforms on the selected points and heights = the
+    gravity column before the alignment.  There is no second min-corner shift, and the colours are still 0..255, so
+    ChromaticNormalize's / 255 is the live branch.
+    cdata (n,7) GPU tensor, fp32 or fp64: xyz, rgb 0..255, label.  rnd: voxelize's randint(0, count.max(), nvox), drawn from
+    `generator` when None.  centre (1,3): see s3dis_part_batch.  tables: idx_sort / count [/ start] of the reference's own
+    voxelisation (its unstable sort chooses the order inside a voxel; the tests pass it).
+    Returns {pos (1,n,3), x (1,Cx,n), heights (1,n,1), y (1,n), centre (1,3)}: one batch of evaluate.validate_boundary_inner."""
+    _need_gpu(cdata)
+    if cdata.dim() != 2 or cdata.shape[1] != 7:
+        raise ValueError("s3dis_val_cloud: cdata (n,7): xyz, rgb, label")
+    cdata = cdata.float()
+    coord = cdata[:, :3] - cdata[:, :3].min(0).values
+    colour, label = cdata[:, 3:6].contiguous(), cdata[:, 6].long()
+    if tables is None:
+        sel = voxelize(coord, voxel_size, rnd=rnd, generator=generator).int()
+    else:
+        idx_sort, _, start, count, nv, P = _room_tables(coord, voxel_size, tables, "s3dis_val_cloud")
+        if rnd is None:
+            rnd = torch.randint(0, max(P, 1), (nv,), device=coord.device, generator=generator, dtype=torch.int32)
+        rnd = torch.as_tensor(rnd).to(device=coord.device, dtype=torch.int32).contiguous()
+        sel = torch.empty(nv, dtype=torch.int32, device=coord.device)
+        with torch.cuda.device(coord.device):
+            _lib.check(_lib.load().amc3d_voxel_select(nv, _ptr(start), _ptr(count), _ptr(idx_sort), _ptr(rnd), _ptr(sel),
+                                                      _stream(coord)), "voxel_select")
+    return s3dis_part_batch(sel.view(1, -1), coord, colour, label, "val", color_mean, color_std, gravity_dim, feature_keys,
+                            centre)

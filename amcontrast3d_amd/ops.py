@@ -2108,3 +2108,29 @@ def vote_parts(logits, parts_tables):
                                                 _ptr(t["idx_sort"].contiguous()), _ptr(t["voxel_idx"].contiguous()),
                                                 _ptr(voted), _ptr(pred), _stream(logits)), "vote_parts")
     return voted, pred
+
+
+def expand_parts(logits, tables):
+    """`test_mode: nearest_neighbor` (main.py:605, all_logits[reverse_idx_part][voxel_idx][reverse_idx]) as one gather
+    (csrc/s3dis_eval.hip): logits (1,C,nvox) fp32, the model output of the single sub-cloud of
+    input_pipeline.room_representatives, whose result is `tables` -> (voted (N,C) fp32, pred (N) int64).  Every room point
+    takes the logits of its voxel's representative; pred = argmax as torch.argmax (first maximum, NaN counts as maximum)."""
+    t = tables
+    _need_gpu(logits, t["where"], t["idx_sort"], t["voxel_idx"])
+    _need_dtype(torch.float32, logits=logits)
+    _need_dtype(torch.int32, where=t["where"], idx_sort=t["idx_sort"], voxel_idx=t["voxel_idx"])
+    logits = logits.contiguous()
+    if logits.dim() != 3 or logits.shape[0] != 1:
+        raise ValueError(f"expand_parts: logits (1,C,nvox) of the one sub-cloud of representatives, got {tuple(logits.shape)}")
+    _, C, nvox = logits.shape
+    N = t["idx_sort"].shape[0]
+    if t["where"].shape != (1, nvox) or t["count"].shape != (nvox,) or t["voxel_idx"].shape != (N,):
+        raise ValueError(f"expand_parts: logits {tuple(logits.shape)} do not belong to these tables "
+                         f"(where {tuple(t['where'].shape)}, {t['count'].shape[0]} voxels)")
+    voted = torch.empty(N, C, dtype=torch.float32, device=logits.device)
+    pred = torch.empty(N, dtype=torch.int64, device=logits.device)
+    with torch.cuda.device(logits.device), timing.span("expand_parts", nvox * C * 4 + N * C * 4 + N * 20):
+        _lib.check(_lib.load().amc3d_expand_parts(N, C, nvox, _ptr(logits), _ptr(t["where"].contiguous()),
+                                                  _ptr(t["idx_sort"].contiguous()), _ptr(t["voxel_idx"].contiguous()),
+                                                  _ptr(voted), _ptr(pred), _stream(logits)), "expand_parts")
+    return voted, pred

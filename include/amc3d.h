@@ -698,6 +698,34 @@ int amc3d_part_batch(int rows, int n, int npts, int mode, int gravity_dim, int n
 int amc3d_vote_parts(int npts, int p, int num_classes, int nvox, const float *logits, const int *where, const int *start,
                      const int *count, const int *idx_sort, const int *voxel_idx, float *voted, long long *pred, void *stream);
 
+/* ---- S3DIS validation / whole-room testing (examples/segmentation/main.py:68-113 `load_data`, :559-588 the sub-cloud loop with
+ * `val: [PointsToTensor, PointCloudXYZAlign, ChromaticNormalize]`, :605 the nearest-neighbour expansion;
+ * dataset/s3dis/s3dis.py:94-144 the val item).  Voxel tables as amc3d_voxelize writes them for a room of npts points.
+ * s3dis_part_batch: rows of an index matrix idx (rows,n) into coord (npts,3) and colour (npts,3), both fp32 (coord_f64 = 0) or
+ * both fp64 (1), colour raw 0..255 [, label (npts) int64].  mode 0 (test): colour = fl32(clip(f / 255, 0, 1)), q = fl32(c - the
+ * row's minimum corner), division, minimum and subtraction in the input's precision; mode 1 (val, fp32 only): colour = f, q = c.
+ * heights (rows,n) = q[gravity_dim]; centre (rows,3) = the column sums of q in fp64 in a fixed order (per-chunk partials folded
+ * in ascending order, no atomics), divided by n in fp64 and rounded once to fp32, or centre_in (rows,3) when it is not NULL;
+ * pos (rows,n,3) = fl32(q - centre), then pos[gravity_dim] -= its row minimum; colours / 255 when the row's maximum exceeds 1
+ * (a NaN maximum: not), then (x - mean) / std; x (rows,Cx,n) channel-major = nseg <= 3 segments in the caller's order,
+ * seg_kinds[i] in {0 pos, 1 x, 2 heights}; y (rows,n) int64 when y_out is not NULL; centre_out (rows,3) always.  An index outside
+ * [0, npts) is never read: its slot is left unwritten and it takes no part in the statistics (the centre is the mean of the
+ * others).  NaN stays inside its own row.  Three launches through the workspace (8-byte aligned), two when centre_in is given.
+ * room_representatives (test_mode nearest_neighbor): parts[j] = idx_sort[start[v] + rnd[v] % count[v]], v = perm[j], perm a
+ * permutation of the voxel ids, rnd (nvox) >= 0; where[v] = j; a perm entry that is no voxel id, a negative rnd or an empty voxel gives parts[j] = -1
+ * (and a bad perm entry leaves its where slot unwritten): nothing is read through them.  One launch.
+ * expand_parts: logits (num_classes,nvox) of that one sub-cloud -> voted (npts,num_classes): every room point takes the logits
+ * of its voxel's representative; pred (npts) int64 = the first maximum, a NaN counting as the maximum (torch.argmax). */
+size_t amc3d_s3dis_part_batch_workspace_bytes(int rows);
+int amc3d_s3dis_part_batch(int rows, int n, int npts, int mode, int coord_f64, int gravity_dim, int nseg, const int *seg_kinds,
+                           const int *idx, const void *coord, const void *colour, const long long *label, const float *color_mean,
+                           const float *color_std, const float *centre_in, float *pos_out, float *x_out, float *heights,
+                           long long *y_out, float *centre_out, void *workspace, size_t workspace_bytes, void *stream);
+int amc3d_room_representatives(int nvox, int npts, const int *start, const int *count, const int *idx_sort, const int *rnd,
+                               const int *perm, int *parts, int *where, void *stream);
+int amc3d_expand_parts(int npts, int num_classes, int nvox, const float *logits, const int *where, const int *idx_sort,
+                       const int *voxel_idx, float *voted, long long *pred, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
