@@ -12,6 +12,9 @@ Randomness: the reference draws from numpy's global RandomState (np.random.randi
 draws come from a torch.Generator on the device, or are passed in (`rnd`, `init_idx`, `perm`) -- the tests pass the very
 numbers the reference drew.  numpy's argsort is not stable, so WHICH point of a voxel the reference's mode-0 pick lands on
 (and the order of equidistant points in the crop) is unspecified by the reference itself; the stable order is used here.
+
+Batch-level calls: scannet_train_batch (ScanNet's training item), s3dis_train_batch / S3DISTrainFeed (S3DIS's training item for
+a whole batch of raw rooms on csrc/s3dis_input.hip, one read-back per batch), and the validation / whole-room testing items.
 """
 import ctypes
 
@@ -509,3 +512,271 @@ def s3dis_val_cloud(cdata, voxel_size=0.04, rnd=None, generator=None, color_mean
                                                       _stream(coord)), "voxel_select")
     return s3dis_part_batch(sel.view(1, -1), coord, colour, label, "val", color_mean, color_std, gravity_dim, feature_keys,
                             centre)
+
+
+def _upload(values, dtype, dev):
+    """a small host table on the device without a blocking copy: pinned staging, asynchronous on the current stream"""
+    return torch.tensor(values, dtype=dtype).pin_memory().to(dev, non_blocking=True)
+
+
+_S3DIS_TRANSFORM_KEYS = {"contrast": (), "blend": (), "scale_u": (3,), "theta": (3,), "drop": ()}
+
+
+def _s3dis_transform_draws(t, B, N, dev, generator):
+    """S3DISTrainAugment.draw -- the same draws in the same order -- without its blocking upload of the angle bounds (a
+    pageable host-to-device copy waits for everything queued on the stream: here, the whole voxelisation)"""
+    import math
+    r = lambda *s: torch.rand(*s, device=dev, generator=generator)  # noqa: E731
+    d = {"contrast": r(B) < t.contrast_p,
+         "blend": r(B) if t.blend_factor is None else torch.full((B,), float(t.blend_factor), device=dev),
+         "scale_u": r(B, 3)}
+    u = r(B, 3).double() * 2 - 1
+    d["theta"] = torch.stack([u[:, j] * (t.angle[j] * math.pi) for j in range(3)], 1)
+    d["noise"] = torch.randn(B, N, 3, device=dev, generator=generator)
+    d["drop"] = r(B) < t.color_drop
+    return d
+
+
+def _s3dis_augment(t, pos, colour, d):
+    """S3DISTrainAugment.__call__ on given draws -- the same records for the same amc3d_augment_clouds, bit for bit -- with the
+    scale bounds as host scalars instead of uploaded tensors: no blocking copy"""
+    B, N, dev = pos.shape[0], pos.shape[1], pos.device
+    lo, hi = torch.tensor(t.scale[0], dtype=torch.float32), torch.tensor(t.scale[1], dtype=torch.float32)
+    scale = d["scale_u"].float() * float(hi - lo) + float(lo)  # point_transformer_gpu.py:151-152, in float32
+    th = d["theta"].double()
+    c, s = torch.cos(th), torch.sin(th)
+    one, zero = torch.ones(B, dtype=torch.float64, device=dev), torch.zeros(B, dtype=torch.float64, device=dev)
+    rx = torch.stack([one, zero, zero, zero, c[:, 0], -s[:, 0], zero, s[:, 0], c[:, 0]], 1).view(B, 3, 3)
+    ry = torch.stack([c[:, 1], zero, s[:, 1], zero, one, zero, -s[:, 1], zero, c[:, 1]], 1).view(B, 3, 3)
+    rz = torch.stack([c[:, 2], -s[:, 2], zero, s[:, 2], c[:, 2], zero, zero, zero, one], 1).view(B, 3, 3)
+    par = torch.zeros(B, 24, dtype=torch.float32, device=dev)
+    par[:, 0] = d["contrast"].float()
+    par[:, 1] = d["blend"].float()
+    par[:, 2:5] = scale
+    par[:, 5:14] = (rx @ ry @ rz).float().reshape(B, 9)
+    par[:, 14] = d["drop"].float()
+    noise = d["noise"].to(torch.float32).contiguous()
+    mean, std = _colour_constants(tuple(float(v) for v in t.color_mean), tuple(float(v) for v in t.color_std), dev,
+                                  "s3dis_train_batch")
+    pos_out, x_out = torch.empty_like(pos), torch.empty_like(colour)
+    heights = torch.empty(B, N, 1, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    wb = int(lib.amc3d_augment_workspace_bytes(B))
+    work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.amc3d_augment_clouds(B, N, t.g, t.sigma, t.clip, _ptr(pos), _ptr(colour), _ptr(noise), _ptr(par), _ptr(mean),
+                                            _ptr(std), _ptr(pos_out), _ptr(x_out), _ptr(heights), _ptr(work), wb, _stream(pos)),
+                   "augment_clouds")
+    return pos_out, x_out, heights
+
+
+def _s3dis_batch(raw, src, sizes, transform, voxel_size, voxel_max, variable, shuffle, generator, draws, gravity_dim):
+    """s3dis_train_batch on rooms that are row ranges [src[b], src[b] + sizes[b]) of one (rows,7) GPU array"""
+    who = "s3dis_train_batch"
+    B, dev, total = len(sizes), raw.device, sum(sizes)
+    if voxel_max is None or int(voxel_max) <= 0:
+        raise ValueError(f"{who}: voxel_max is the size of a training cloud (validation goes through s3dis_val_cloud)")
+    if gravity_dim not in (0, 1, 2) or not float(voxel_size) > 0:
+        raise ValueError(f"{who}: gravity_dim is 0, 1 or 2 and voxel_size is positive")
+    if total >= 2 ** 31:
+        raise ValueError(f"{who}: {total} points in one batch (at most 2^31 - 1)")
+    voxel_max = int(voxel_max)
+    lib = _lib.load()
+    P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    f64 = int(raw.dtype == torch.float64)
+    offsets = [0]
+    for n in sizes:
+        offsets.append(offsets[-1] + n)
+    table = _upload(list(src) + offsets, torch.int64, dev)
+    src_t, off_t = table[:B], table[B:]
+    coord = torch.empty(total, 3, dtype=torch.float32, device=dev)
+    key = torch.empty(total, dtype=torch.int64, device=dev)  # uint64 bit patterns
+    idx_sort = torch.empty(total, dtype=torch.int32, device=dev)
+    start = torch.empty(total + 1, dtype=torch.int32, device=dev)
+    count = torch.empty(total, dtype=torch.int32, device=dev)
+    small = torch.empty(2 * B + 1, dtype=torch.int32, device=dev)
+    vbase, cmax = small[:B + 1], small[B + 1:]
+    corner = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    wb = int(lib.amc3d_s3dis_voxelize_workspace_bytes(B, total))
+    work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.amc3d_s3dis_voxelize_rooms(B, total, f64, P(raw), P(src_t), P(off_t), ctypes.c_double(float(voxel_size)),
+                                                  P(coord), P(key), P(idx_sort), P(start), P(count), P(vbase), P(cmax), P(corner),
+                                                  P(work), wb, stream), "s3dis_voxelize_rooms")
+    vb = vbase.tolist()  # the batch's one read-back: the voxel counts size everything after the voxelisation
+    nv = [vb[b + 1] - vb[b] for b in range(B)]
+    nvt = vb[B]
+    outs = [voxel_max if (n >= voxel_max or not variable) else n for n in nv]
+    n_out = outs[0]
+    if any(n != n_out for n in outs):
+        raise ValueError(f"{who}: the rooms came out with different sizes {outs} (variable=True); the collate stacks them")
+    cropped = [n >= voxel_max for n in nv]
+    padded = [n < n_out for n in nv]
+
+    d = dict(draws or {})
+    per_room = {}
+    for k in ("rnd", "init_idx", "pad", "perm"):
+        v = d.pop(k, None)
+        per_room[k] = list(v) if v is not None else [None] * B
+        if len(per_room[k]) != B:
+            raise ValueError(f"{who}: per-room draws need one entry per room")
+    given = lambda v: torch.as_tensor(v).to(dev)  # noqa: E731
+    # voxelize's randint(0, count.max(), nvox)
+    rnd_t = rnd_u = None
+    if any(r is not None for r in per_room["rnd"]):
+        rnd_t = torch.full((nvt,), -1, dtype=torch.int32, device=dev)
+        for b, r in enumerate(per_room["rnd"]):
+            if r is not None:
+                r = given(r)
+                if r.shape != (nv[b],) or r.is_floating_point() or bool((r < 0).any()):
+                    raise ValueError(f"{who}: room {b}: rnd must hold {nv[b]} non-negative draws")
+                rnd_t[vb[b]:vb[b + 1]] = r
+    if any(r is None for r in per_room["rnd"]):
+        rnd_u = torch.rand(nvt, dtype=torch.float64, device=dev, generator=generator)
+    # crop_pc's randint(N)
+    init_t = init_u = None
+    if any(cropped):
+        inits = []
+        for b, v in enumerate(per_room["init_idx"]):
+            v = -1 if (v is None or not cropped[b]) else int(v)
+            if per_room["init_idx"][b] is not None and cropped[b] and not 0 <= v < nv[b]:
+                raise ValueError(f"{who}: room {b}: init_idx {v} out of range")
+            inits.append(v)
+        if any(v >= 0 for v in inits):
+            init_t = _upload(inits, torch.int32, dev)
+        if any(v < 0 and c for v, c in zip(inits, cropped)):
+            init_u = torch.rand(B, dtype=torch.float64, device=dev, generator=generator)
+    # its np.random.choice(N, voxel_max - N) and its permutation
+    pad_t = perm_t = None
+    if any(padded):
+        if any(p and per_room["pad"][b] is None for b, p in enumerate(padded)):
+            nvd = (vbase[1:] - vbase[:-1]).view(B, 1)
+            pad_t = (torch.rand(B, n_out, dtype=torch.float64, device=dev, generator=generator) * nvd).int()
+        else:
+            pad_t = torch.zeros(B, n_out, dtype=torch.int32, device=dev)
+        for b, v in enumerate(per_room["pad"]):
+            if v is not None and padded[b]:
+                v = given(v)
+                if v.shape != (n_out - nv[b],) or v.is_floating_point() or bool(((v < 0) | (v >= nv[b])).any()):
+                    raise ValueError(f"{who}: room {b}: pad must hold {n_out - nv[b]} indices below {nv[b]}")
+                pad_t[b, nv[b]:] = v
+    if shuffle:
+        if any(v is None for v in per_room["perm"]):
+            perm_t = torch.rand(B, n_out, device=dev, generator=generator).argsort(dim=1).int()
+        else:
+            perm_t = torch.empty(B, n_out, dtype=torch.int32, device=dev)
+        for b, v in enumerate(per_room["perm"]):
+            if v is not None:
+                v = given(v)
+                if v.shape != (n_out,) or v.is_floating_point() or not bool((v.sort().values == torch.arange(n_out, device=dev)).all()):
+                    raise ValueError(f"{who}: room {b}: perm must be a permutation of {n_out}")
+                perm_t[b] = v
+    # the transform's draws (S3DISTrainAugment.draw's keys)
+    if any(k not in d for k in list(_S3DIS_TRANSFORM_KEYS) + ["noise"]):
+        for k, v in _s3dis_transform_draws(transform, B, n_out, dev, generator).items():
+            d.setdefault(k, v)
+    for k, shape in list(_S3DIS_TRANSFORM_KEYS.items()) + [("noise", (n_out, 3))]:
+        d[k] = given(d[k])
+        if d[k].shape != (B,) + shape:
+            raise ValueError(f"{who}: draws[{k!r}] has shape {tuple(d[k].shape)}, not {(B,) + shape}")
+
+    sel = torch.empty(max(nvt, 1), dtype=torch.int32, device=dev)
+    d2 = order = work2 = None
+    wb2 = 0
+    if any(cropped):
+        d2 = torch.empty(nvt, dtype=torch.float32, device=dev)
+        order = torch.empty(nvt, dtype=torch.int32, device=dev)
+        wb2 = int(lib.amc3d_s3dis_crop_workspace_bytes(nvt))
+        work2 = torch.empty(max(wb2, 8), dtype=torch.uint8, device=dev)
+    pos0 = torch.empty(B, n_out, 3, dtype=torch.float32, device=dev)
+    colour = torch.empty(B, n_out, 3, dtype=torch.float32, device=dev)
+    y = torch.empty(B, n_out, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.amc3d_s3dis_select_crop(B, nvt, voxel_max, int(any(cropped)), P(coord), P(idx_sort), P(start), P(count),
+                                               P(vbase), P(cmax), P(rnd_t), P(rnd_u), P(init_t), P(init_u), P(sel), P(d2), P(order),
+                                               P(work2), wb2, stream), "s3dis_select_crop")
+        _lib.check(lib.amc3d_s3dis_crop_tail(B, n_out, voxel_max, f64, P(raw), P(src_t), P(off_t), P(coord), P(vbase), P(sel),
+                                             P(order), P(pad_t), P(perm_t), P(pos0), P(colour), P(y), stream), "s3dis_crop_tail")
+    pos, x, heights = _s3dis_augment(transform, pos0, colour, d)
+    if gravity_dim != transform.g:
+        heights = pos0[:, :, gravity_dim:gravity_dim + 1].contiguous()
+    return {"pos": pos, "x": x, "heights": heights, "y": y}
+
+
+def _s3dis_rooms(rooms, who):
+    rooms = list(rooms)
+    if len(rooms) == 0:
+        raise ValueError(f"{who}: no rooms")
+    for r in rooms:
+        if not (torch.is_tensor(r) and r.is_cuda and r.dim() == 2 and r.shape[1] == 7 and r.shape[0] > 0
+                and r.dtype in (torch.float32, torch.float64) and r.device == rooms[0].device):
+            raise ValueError(f"{who}: every room is an (n,7) float32 or float64 tensor on one GPU with n > 0: xyz, rgb, label")
+    return rooms
+
+
+def s3dis_train_batch(rooms, transform, voxel_size=0.04, voxel_max=24000, variable=False, shuffle=True, generator=None,
+                      draws=None, gravity_dim=2):
+    """S3DIS.__getitem__ for training with presample=False (dataset/s3dis/s3dis.py:122-144) plus the default collate, for a
+    batch of raw rooms on the GPU (csrc/s3dis_input.hip): every room cast to float32, xyz -= min, crop_pc (min-corner shift,
+    voxelize mode 0, the voxel_max representatives nearest to representative init_idx or, with variable=False, padding by
+    repetition, shuffle, min-corner shift), then `transform` (augment.S3DISTrainAugment) on the cropped clouds; heights is the
+    gravity coordinate of the cropped cloud before the transforms.  Bit for bit what crop_pc per room, torch.stack and
+    `transform` give from the same draws, in a handful of launches for the whole batch instead of about twenty per room.
+
+    rooms: list of (n_b,7) GPU tensors, float32 or float64, as np.load of an Area_*.npy gives them: xyz, rgb 0..255, label
+    (rooms of both dtypes in one batch are promoted to float64, which changes nothing: the first step is the float32 cast).
+    Returns {pos (B,N,3) fp32, x (B,N,3) fp32, heights (B,N,1) fp32, y (B,N) int64}, what DataLoader(S3DIS(split='train'))
+    yields; every room must come out with the same N (always so with variable=False).
+
+    Random numbers come from `generator` (a torch.Generator on the rooms' device, or the default one) or from `draws`: a
+    dict with the transform's keys (S3DISTrainAugment.draw) and per-room lists "rnd" (voxelize's randint(0, count.max(),
+    nvox)), "init_idx", "pad", "perm" (entries may be None).  Device draws are floor(u * range) of a float64 uniform, as in
+    scannet_train_batch; the shuffle is the argsort of uniforms.
+    Host synchronisation: one read-back per batch (the B voxel counts, after all the voxelise work is enqueued), none per
+    room; draws that are passed in are validated, which reads their verdicts back."""
+    rooms = _s3dis_rooms(rooms, "s3dis_train_batch")
+    sizes = [int(r.shape[0]) for r in rooms]
+    src = [0]
+    for n in sizes[:-1]:
+        src.append(src[-1] + n)
+    raw = rooms[0].contiguous() if len(rooms) == 1 else torch.cat(rooms)
+    return _s3dis_batch(raw, src, sizes, transform, voxel_size, voxel_max, variable, shuffle, generator, draws, gravity_dim)
+
+
+class S3DISTrainFeed:
+    """An epoch of S3DIS training batches from rooms resident on the device: what DataLoader(S3DIS(split='train', loop=loop,
+    presample=False), batch_size, shuffle=shuffle, drop_last=drop_last) yields.  Every epoch (every `iter`) draws a
+    permutation of the len(rooms) * loop item ids from `generator` (one read-back per epoch); item id -> room id % len(rooms)
+    (s3dis.py:123,146-147).  Every batch is one s3dis_train_batch call (variable=False) on the current stream, at the moment
+    the consumer asks for it: no side stream, no prefetch.  The rooms are kept as one concatenated array, so a batch copies
+    nothing.  train.train_one_epoch takes it as `train_loader`."""
+
+    def __init__(self, rooms, transform, batch_size, loop=1, voxel_size=0.04, voxel_max=24000, shuffle=True, drop_last=True,
+                 generator=None):
+        rooms = _s3dis_rooms(rooms, "S3DISTrainFeed")
+        if int(batch_size) <= 0 or int(loop) <= 0:
+            raise ValueError("S3DISTrainFeed: batch_size and loop are positive")
+        if voxel_max is None:
+            raise ValueError("S3DISTrainFeed: voxel_max is the size of a training cloud")
+        self.sizes = [int(r.shape[0]) for r in rooms]
+        self.starts = [0]
+        for n in self.sizes[:-1]:
+            self.starts.append(self.starts[-1] + n)
+        self.raw = rooms[0].contiguous() if len(rooms) == 1 else torch.cat(rooms)
+        self.transform, self.batch_size, self.loop = transform, int(batch_size), int(loop)
+        self.voxel_size, self.voxel_max, self.shuffle, self.drop_last = voxel_size, voxel_max, bool(shuffle), bool(drop_last)
+        self.generator = generator
+
+    def __len__(self):
+        items = len(self.sizes) * self.loop
+        return items // self.batch_size if self.drop_last else -(-items // self.batch_size)
+
+    def __iter__(self):
+        items = len(self.sizes) * self.loop
+        ids = (torch.randperm(items, device=self.raw.device, generator=self.generator).tolist() if self.shuffle
+               else list(range(items)))
+        for i in range(len(self)):
+            pick = [j % len(self.sizes) for j in ids[i * self.batch_size:(i + 1) * self.batch_size]]
+            yield _s3dis_batch(self.raw, [self.starts[j] for j in pick], [self.sizes[j] for j in pick], self.transform,
+                               self.voxel_size, self.voxel_max, False, True, self.generator, None, 2)

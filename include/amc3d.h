@@ -726,6 +726,40 @@ int amc3d_room_representatives(int nvox, int npts, const int *start, const int *
 int amc3d_expand_parts(int npts, int num_classes, int nvox, const float *logits, const int *where, const int *idx_sort,
                        const int *voxel_idx, float *voted, long long *pred, void *stream);
 
+/* ---- S3DIS training input for a batch of RAW rooms (dataset/s3dis/s3dis.py:122-144 with presample=False: the room cast to fp32,
+ * xyz -= min, then crop_pc, dataset/data_util.py:146-174; the transform chain that follows is amc3d_augment_clouds).  Rooms are
+ * ragged: raw (rows,7) = {xyz, rgb 0..255, label}, fp32 (raw_f64 = 0) or fp64 (1); room r is rows [src[r], src[r] + its size)
+ * of raw and points [offsets[r], offsets[r+1]) of the batch (src (rooms), offsets (rooms+1) int64, device memory; total =
+ * offsets[rooms] < 2^31, no empty room).  Everything is exact arithmetic: the results equal amc3d_voxelize / amc3d_voxel_select /
+ * amc3d_crop_nearest run room by room, bit for bit.
+ * voxelize_rooms: corner (rooms,3) = the fp32 minimum of fl32(xyz); coord (total,3) = fl32(xyz) - corner; key (total) as
+ * amc3d_voxelize; idx_sort (total) = batch point indices ordered by (room, key), stable (two device-wide radix sorts: 64 key
+ * bits, then the room-id bits); voxels numbered through the batch, a room boundary always starting one: start (total+1),
+ * count (total; written for the voxels only), vbase (rooms+1) = first voxel of every room, vbase[rooms] = their number,
+ * cmax (rooms) = count.max() per room.  Nothing is read back.
+ * select_crop (nvox = vbase[rooms], read back by the caller): sel (nvox) = idx_sort[start[v] + rnd[v] % count[v]], where
+ * rnd[v] < 0 or rnd NULL takes (int)(rnd_u[v] * cmax[room]); with any_crop, for every room with at least voxel_max voxels d2
+ * (nvox) = ((dx^2 + dy^2) + dz^2) in fp32 from its representative number init[r] (init[r] < 0 or init NULL:
+ * min((int)(init_u[r] * its voxel count), that - 1)), and order (nvox) = voxel numbers sorted by (room, d2 bits), stable (one
+ * device-wide radix sort): a room's crop is the first voxel_max entries of its range of order.
+ * crop_tail: one launch, one workgroup per room: slot k of room r <- representative c = perm[r,k] (perm (rooms,n) or NULL:
+ * identity) of the crop order, or, for a room below voxel_max, voxel c for c below its voxel count and voxel pad[r,c] above
+ * (pad (rooms,n), only those slots read); pos_out (rooms,n,3) = coord minus the fp32 min corner of the room's n slots,
+ * colour_out (rooms,n,3) = fl32(rgb), y_out (rooms,n) int64 = the label. */
+size_t amc3d_s3dis_voxelize_workspace_bytes(int rooms, long long total);
+int amc3d_s3dis_voxelize_rooms(int rooms, long long total, int raw_f64, const void *raw, const long long *src,
+                               const long long *offsets, double voxel_size, float *coord, unsigned long long *key,
+                               int *idx_sort, int *start, int *count, int *vbase, int *cmax, float *corner, void *workspace,
+                               size_t workspace_bytes, void *stream);
+size_t amc3d_s3dis_crop_workspace_bytes(int nvox);
+int amc3d_s3dis_select_crop(int rooms, int nvox, int voxel_max, int any_crop, const float *coord, const int *idx_sort,
+                            const int *start, const int *count, const int *vbase, const int *cmax, const int *rnd,
+                            const double *rnd_u, const int *init, const double *init_u, int *sel, float *d2, int *order,
+                            void *workspace, size_t workspace_bytes, void *stream);
+int amc3d_s3dis_crop_tail(int rooms, int n, int voxel_max, int raw_f64, const void *raw, const long long *src,
+                          const long long *offsets, const float *coord, const int *vbase, const int *sel, const int *order,
+                          const int *pad, const int *perm, float *pos_out, float *colour_out, long long *y_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
