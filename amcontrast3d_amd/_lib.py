@@ -50,6 +50,10 @@ SIGNATURES = {
     "amc3d_contrast_backward_mutual_workspace_bytes": (_sz, [_i]),
     "amc3d_contrast_backward_mutual": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz,
                                             _vp, _vp]),
+    "amc3d_contrast_variant_forward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp,
+                                            _vp, _vp]),
+    "amc3d_contrast_variant_backward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp,
+                                             _vp, _vp, _vp, _vp]),
     "amc3d_adamw_chunk": (_i, []),
     "amc3d_adamw_step": (_i, [_vp, _vp, _i, ctypes.c_double, ctypes.c_double, _f, _f, _vp, _vp, _vp]),
     "amc3d_select_anchors_ints": (_sz, [_i]),

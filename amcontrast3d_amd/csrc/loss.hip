@@ -845,6 +845,324 @@ __global__ __launch_bounds__(256) void contrast_backward_mutual_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------
+// The other forms of contrast_softnn_margin (MarginContrast.py:117-174): margin constant / adaptive / learned, decision
+// boundary none / -m / +m, Method1 / Method2, with or without a temperature.  The form is four run-time integers
+// (kernel-uniform branches, no template per combination); the kernels of the default form above are untouched, what is
+// shared with them is copied.  Three steps forward -- the cosines alone (contrast_sim_*), the per-anchor loss from the
+// stored cosines (contrast_variant_loss_kernel), masked_mean_kernel -- and two backward: g_ij = dL/ds_ij
+// (contrast_variant_coef_kernel), then the gradient rows from g by contrast_backward_rows_kernel (a gather over reverse
+// lists, which knows nothing of the loss's form) or by contrast_backward_edges_kernel (float atomics, any C <= 512).
+//
+// Per anchor, with z_j = (s_j - [pos] m) / T  (-m),  (s_j + [neg] m) / T  (+m),  s_j / T  (none), e_j = exp(z_j),
+// P = sum_pos e, N = sum_neg e (each summed on its own, see contrast_backward_kernel), S = P + N, q_j = dl/dz_j:
+//   Method1  l = -log(P/S + eps):       q_j = -e_j (N/S) / ((P/S + eps) S)  on positives,  +e_j (P/S) / ((P/S + eps) S)  on negatives
+//   Method2  l = -log(Y / (npos + eps)),  Y = sum_j (e_j [pos] / (e_j [pos] + N) + eps)  over ALL k slots:
+//            q_j = -(e_j / (e_j + N)) (N / (e_j + N)) / Y  on positives,  +e_j W / Y  on negatives,
+//            W = sum_pos e_j / (e_j + N)^2
+//   dl/dm = -(1/T) sum_pos q  (-m),  +(1/T) sum_neg q  (+m),  0 (none);  sum_pos q = -sum_neg q = -N W / Y  (Method2),
+//            -(N/S)(P/S) / (P/S + eps)  (Method1)
+//   learned margin m = (u - 1) a + v, u = (1/k) sum_neg s, v = (1/k) sum_pos s:  dm/ds_j = 1/k on positives, a/k on negatives
+//   dl/ds_j = q_j / T + dl/dm * dm/ds_j
+// ---------------------------------------------------------------------------------------------
+template <int LPR>
+__global__ __launch_bounds__(256) void contrast_sim_unit_kernel(
+    int m, int k, int nbr_stride, const float *__restrict__ unit, const int *__restrict__ nbr, const float *__restrict__ a,
+    const int *__restrict__ sel, float *__restrict__ sim)
+{
+    // the gather of contrast_forward_unit_kernel: the same rounds, products and tree, so the cosines agree to the bit
+    constexpr int R = 64 / LPR;
+    constexpr int U = 4;
+    const int lane = threadIdx.x & 63, q = lane & (LPR - 1), r = lane / LPR;
+    const int cnt = sel ? sel[0] : m;
+    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= cnt) return;
+    const int i = sel ? sel[1 + w] : w;
+    const float ai = a[i];
+    if (!(0.f < ai && ai <= 1.f)) return;
+    const float4 *h4 = reinterpret_cast<const float4 *>(unit);
+    const float4 u = h4[(size_t)i * LPR + q];
+    for (int j0 = 0; j0 < k; j0 += U * R) {
+        int nb[U];
+        float4 v[U];
+#pragma unroll
+        for (int t = 0; t < U; ++t) {
+            const int j = j0 + t * R + r;
+            nb[t] = j < k ? nbr[(size_t)i * nbr_stride + j] : -1;
+        }
+        const int jq = j0 + q * R + r;  // the slot this lane writes
+        const bool mine = q < U && jq < k;
+#pragma unroll
+        for (int t = 0; t < U; ++t) v[t] = nb[t] >= 0 ? h4[(unsigned)nb[t] * (unsigned)LPR + (unsigned)q] : make_float4(0.f, 0.f, 0.f, 0.f);
+        float s = 0.f;
+#pragma unroll
+        for (int t = 0; t < U; ++t) {
+            float acc = unit_dot4(u, v[t]);
+#pragma unroll
+            for (int d = LPR / 2; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+            s = q == t ? acc : s;
+        }
+        if (mine) sim[(size_t)i * k + jq] = s;
+    }
+}
+
+// the gather of contrast_forward_kernel (any C): 32 lanes per anchor, lane j owns neighbour j
+__global__ __launch_bounds__(256) void contrast_sim_kernel(
+    int m, int C, int k, int nbr_stride, const float *__restrict__ f, const float *__restrict__ norm,
+    const int *__restrict__ nbr, const float *__restrict__ a, const int *__restrict__ sel, float *__restrict__ sim)
+{
+    const int sub = threadIdx.x & 31;
+    const int w = (blockIdx.x * blockDim.x + threadIdx.x) >> 5;
+    if (w >= (sel ? sel[0] : m)) return;
+    const int i = sel ? sel[1 + w] : w;
+    const float ai = a[i];
+    if (!(0.f < ai && ai <= 1.f)) return;
+    const float ni = norm[i];
+    const float *fi = f + (size_t)i * C;
+    for (int j = sub; j < k; j += 32) {
+        const int nb = nbr[(size_t)i * nbr_stride + j];
+        const float nj = norm[nb];
+        const float *fj = f + (size_t)nb * C;
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+        if ((C & 3) == 0) {
+            for (int c = 0; c < C; c += 4) {
+                const float4 u = *reinterpret_cast<const float4 *>(fi + c);
+                const float4 v = *reinterpret_cast<const float4 *>(fj + c);
+                a0 += __fdiv_rn(u.x, ni) * __fdiv_rn(v.x, nj);
+                a1 += __fdiv_rn(u.y, ni) * __fdiv_rn(v.y, nj);
+                a2 += __fdiv_rn(u.z, ni) * __fdiv_rn(v.z, nj);
+                a3 += __fdiv_rn(u.w, ni) * __fdiv_rn(v.w, nj);
+            }
+        } else {
+            int c = 0;
+            for (; c + 3 < C; c += 4) {
+                a0 += __fdiv_rn(fi[c], ni) * __fdiv_rn(fj[c], nj);
+                a1 += __fdiv_rn(fi[c + 1], ni) * __fdiv_rn(fj[c + 1], nj);
+                a2 += __fdiv_rn(fi[c + 2], ni) * __fdiv_rn(fj[c + 2], nj);
+                a3 += __fdiv_rn(fi[c + 3], ni) * __fdiv_rn(fj[c + 3], nj);
+            }
+            for (; c < C; ++c) a0 += __fdiv_rn(fi[c], ni) * __fdiv_rn(fj[c], nj);
+        }
+        sim[(size_t)i * k + j] = (a0 + a1) + (a2 + a3);
+    }
+}
+
+struct ContrastForm { int margin_mode, db, method, has_temperature; float mu, nu, temperature; };
+
+// sum over the 32 lanes of an anchor's group (two groups per wave; xor below 32 stays inside one)
+__device__ __forceinline__ float group32_sum(float v)
+{
+#pragma unroll
+    for (int s = 16; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
+    return v;
+}
+
+// z_j: the exponent of slot j (MarginContrast.py:140-149)
+__device__ __forceinline__ float variant_arg(const ContrastForm &F, float s, bool pos, float margin)
+{
+    float z = s;
+    if (F.db == 1) z = pos ? __fsub_rn(s, margin) : s;
+    else if (F.db == 2) z = pos ? s : __fadd_rn(s, margin);
+    return F.has_temperature ? __fdiv_rn(z, F.temperature) : z;
+}
+
+// what both variant kernels need of one anchor; every lane of the group returns the same values
+struct ContrastAnchorSums { float margin, psum, nsum, npos, ysum, wsum; };
+
+__device__ __forceinline__ ContrastAnchorSums variant_anchor_sums(const ContrastForm &F, int k, int sub, float ai,
+                                                                 const float *__restrict__ sim_i,
+                                                                 const unsigned char *__restrict__ pm_i)
+{
+    ContrastAnchorSums r;
+    r.margin = F.nu;
+    if (F.margin_mode == 1) r.margin = __fadd_rn(__fmul_rn(F.mu, ai), F.nu);
+    if (F.margin_mode == 2) {  // u, v: means over all k slots of the masked cosines (:128-130)
+        float su = 0.f, sv = 0.f;
+        for (int j = sub; j < k; j += 32) {
+            const bool pos = pm_i[j] != 0;
+            const float s = sim_i[j];
+            su += pos ? 0.f : s;
+            sv += pos ? s : 0.f;
+        }
+        const float u = __fdiv_rn(group32_sum(su), (float)k), v = __fdiv_rn(group32_sum(sv), (float)k);
+        r.margin = __fadd_rn(__fmul_rn(__fsub_rn(u, 1.f), ai), v);
+    }
+    float psum = 0.f, nsum = 0.f, npos = 0.f;
+    for (int j = sub; j < k; j += 32) {
+        const bool pos = pm_i[j] != 0;
+        const float e = expf(variant_arg(F, sim_i[j], pos, r.margin));
+        psum += pos ? e : 0.f;
+        nsum += pos ? 0.f : e;
+        npos += pos ? 1.f : 0.f;
+    }
+    r.psum = group32_sum(psum);
+    r.nsum = group32_sum(nsum);
+    r.npos = group32_sum(npos);
+    r.ysum = r.wsum = 0.f;
+    if (F.method == 2) {  // (:165-171, literally: a negative slot contributes 0 / (0 + N) + eps)
+        float y = 0.f, wv = 0.f;
+        for (int j = sub; j < k; j += 32) {
+            const bool pos = pm_i[j] != 0;
+            const float ep = pos ? expf(variant_arg(F, sim_i[j], pos, r.margin)) : 0.f;
+            const float den = ep + r.nsum;
+            y += __fadd_rn(__fdiv_rn(ep, den), 1e-12f);
+            wv += pos ? __fdiv_rn(__fdiv_rn(ep, den), den) : 0.f;
+        }
+        r.ysum = group32_sum(y);
+        r.wsum = group32_sum(wv);
+    }
+    return r;
+}
+
+__global__ __launch_bounds__(256) void contrast_variant_loss_kernel(
+    int m, int k, const unsigned char *__restrict__ posmask, const float *__restrict__ a, const int *__restrict__ sel,
+    ContrastForm F, const float *__restrict__ sim, float *__restrict__ loss_pt)
+{
+    const int sub = threadIdx.x & 31;
+    const int w = (blockIdx.x * blockDim.x + threadIdx.x) >> 5;
+    if (w >= (sel ? sel[0] : m)) return;
+    const int i = sel ? sel[1 + w] : w;
+    const float ai = a[i];
+    if (!(0.f < ai && ai <= 1.f)) {
+        if (sub == 0) loss_pt[i] = 0.f;
+        return;
+    }
+    const ContrastAnchorSums r = variant_anchor_sums(F, k, sub, ai, sim + (size_t)i * k, posmask + (size_t)i * k);
+    if (sub == 0) {
+        const float ratio = F.method == 2 ? __fdiv_rn(r.ysum, __fadd_rn(r.npos, 1e-12f))
+                                          : __fadd_rn(__fdiv_rn(r.psum, __fadd_rn(r.psum, r.nsum)), 1e-12f);
+        loss_pt[i] = -logf(ratio);
+    }
+}
+
+// gco[i,j] = (grad_out / count) * dl_i/ds_ij for the visited anchors (the header above); an anchor without a positive
+// neighbour under Method1 gets exact zeros, as in contrast_coef_kernel
+__global__ __launch_bounds__(256) void contrast_variant_coef_kernel(
+    int m, int k, const unsigned char *__restrict__ posmask, const float *__restrict__ a, const int *__restrict__ sel,
+    ContrastForm F, const float *__restrict__ sim, const float *__restrict__ mean_cnt,
+    const float *__restrict__ grad_out, float *__restrict__ gco)
+{
+    const int sub = threadIdx.x & 31;
+    const int w = (blockIdx.x * blockDim.x + threadIdx.x) >> 5;
+    if (w >= (sel ? sel[0] : m)) return;
+    const int i = sel ? sel[1 + w] : w;
+    const float ai = a[i];
+    if (!(0.f < ai && ai <= 1.f)) return;
+    const float *sim_i = sim + (size_t)i * k;
+    const unsigned char *pm_i = posmask + (size_t)i * k;
+    const ContrastAnchorSums r = variant_anchor_sums(F, k, sub, ai, sim_i, pm_i);
+    const float scale = grad_out[0] / mean_cnt[1];
+    const float inv_t = F.has_temperature ? 1.f / F.temperature : 1.f;
+    // q_j = cp * e_j * (Method2: N / (e_j + N)^2) on positives, cn * e_j on negatives
+    float cp, cn, qpos;  // qpos = sum_pos q = -sum_neg q
+    bool dead = false;
+    if (F.method == 2) {
+        cp = -1.f / r.ysum;
+        cn = r.wsum / r.ysum;
+        qpos = -r.nsum * cn;
+    } else {
+        const float S = r.psum + r.nsum, rp = r.psum / S, rn = r.nsum / S;
+        const float den = (rp + 1e-12f) * S;
+        cp = -rn / den;
+        cn = rp / den;
+        qpos = -rn * rp / (rp + 1e-12f);
+        dead = r.psum == 0.f;
+    }
+    const float dm = F.db != 0 ? -inv_t * qpos : 0.f;  // dl/dm; -m: -sum_pos q / T;  +m: sum_neg q / T, the same number
+    const float dm_pos = F.margin_mode == 2 ? dm / (float)k : 0.f, dm_neg = dm_pos * ai;
+    for (int j = sub; j < k; j += 32) {
+        const bool pos = pm_i[j] != 0;
+        const float e = expf(variant_arg(F, sim_i[j], pos, r.margin));
+        float q;
+        if (!pos) q = cn * e;
+        else if (F.method == 2) {
+            const float den = e + r.nsum;
+            q = cp * (e / den) * (r.nsum / den);
+        } else q = cp * e;
+        const float g = scale * (q * inv_t + (pos ? dm_pos : dm_neg));
+        gco[(size_t)i * k + j] = dead ? 0.f : g;
+    }
+}
+
+// Gradient rows from g = gco by float atomics: the walk of contrast_backward_kernel (LPA lanes per anchor, lane owns
+// channels c, c + LPA, ...; U neighbour rows in flight; no projection below the norm clamp) with the edge coefficient
+// read instead of computed.  grad_f zero-initialised by the caller; C <= LPA * VPT.
+template <int LPA, int VPT>
+__global__ __launch_bounds__(256) void contrast_backward_edges_kernel(
+    int m, int C, int k, int nbr_stride, const float *__restrict__ f, const float *__restrict__ norm,
+    const int *__restrict__ nbr, const float *__restrict__ a, const int *__restrict__ sel, const float *__restrict__ sim,
+    const float *__restrict__ gco, float *__restrict__ grad_f)
+{
+    constexpr int U = VPT >= 8 ? 2 : (VPT >= 4 ? 4 : 8);  // neighbour rows in flight
+    const int sub = threadIdx.x & (LPA - 1);
+    const int w = (blockIdx.x * blockDim.x + threadIdx.x) / LPA;
+    if (w >= (sel ? sel[0] : m)) return;
+    const int i = sel ? sel[1 + w] : w;
+    const float ai = a[i];
+    if (!(0.f < ai && ai <= 1.f)) return;
+    const float ni = norm[i];
+
+    float fhi[VPT], gi[VPT];
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) {
+        const int c = sub + v * LPA;
+        fhi[v] = c < C ? __fdiv_rn(f[(size_t)i * C + c], ni) : 0.f;
+        gi[v] = 0.f;
+    }
+    for (int j0 = 0; j0 < k; j0 += LPA) {
+        // lane `sub` holds neighbour j0 + sub of this chunk of LPA neighbours
+        const int j = j0 + sub;
+        int nb_l = -1;
+        float sj_l = 0.f, nj_l = 1.f, g_l = 0.f;
+        if (j < k) {
+            nb_l = nbr[(size_t)i * nbr_stride + j];
+            sj_l = sim[(size_t)i * k + j];
+            g_l = gco[(size_t)i * k + j];
+            nj_l = norm[nb_l];
+        }
+        const int cnt = min(LPA, k - j0);
+        for (int jj = 0; jj < cnt; jj += U) {
+            int nb[U];
+            float fj[U][VPT];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int src = min(jj + u, LPA - 1);
+                const int t = __shfl(nb_l, src, LPA);
+                nb[u] = jj + u < cnt ? t : -1;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int v = 0; v < VPT; ++v) {
+                    const int c = sub + v * LPA;
+                    fj[u][v] = (nb[u] >= 0 && c < C) ? f[(size_t)nb[u] * C + c] : 0.f;
+                }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int src = min(jj + u, LPA - 1);
+                const float g = __shfl(g_l, src, LPA), sj = __shfl(sj_l, src, LPA), nj = __shfl(nj_l, src, LPA);
+                if (nb[u] < 0) continue;
+                const float gin = g / ni, gjn = g / nj;
+                const float si = ni > 1e-8f ? sj : 0.f, sx = nj > 1e-8f ? sj : 0.f;  // (no projection below the clamp)
+#pragma unroll
+                for (int v = 0; v < VPT; ++v) {
+                    const int c = sub + v * LPA;
+                    if (c < C) {
+                        const float fhj = __fdiv_rn(fj[u][v], nj);
+                        gi[v] += gin * (fhj - si * fhi[v]);
+                        atomicAdd(grad_f + (size_t)nb[u] * C + c, gjn * (fhi[v] - sx * fhj));
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) {
+        const int c = sub + v * LPA;
+        if (c < C) atomicAdd(grad_f + (size_t)i * C + c, gi[v]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Cross entropy over channel-major logits (B, C, N) with class targets (B, N), mean over the targets
 // != ignore_index: nn.CrossEntropyLoss() with its defaults, as loss/build.py:328,338 applies it after a
 // transpose + reshape copy of the logits to (B*N, C).  One thread per point walks the classes (coalesced
@@ -1203,6 +1521,91 @@ AMC_API int amc3d_contrast_backward_csr(int m, int C, int k, int nbr_stride, con
     else AMC_BWD(64);
 #undef AMC_BWD
     return launch_status("amc3d_contrast_backward_csr");
+}
+
+static bool contrast_form_ok(int margin_mode, int db, int method, int has_temperature, float temperature)
+{
+    return margin_mode >= 0 && margin_mode <= 2 && db >= 0 && db <= 2 && (method == 1 || method == 2) &&
+           (has_temperature == 0 || (has_temperature == 1 && temperature != 0.f));
+}
+
+AMC_API int amc3d_contrast_variant_forward(int m, int C, int k, int nbr_stride, const float *f, const int *nbr,
+                                           const unsigned char *posmask, const float *a, const int *sel, int margin_mode,
+                                           int db, int method, int has_temperature, float mu, float nu, float temperature,
+                                           float *norm, float *unit, float *sim, float *loss_pt, float *mean_cnt,
+                                           void *stream_)
+{
+    if (m <= 0) return 0;
+    if (C <= 0 || k <= 0 || nbr_stride < k || !f || !nbr || !posmask || !a || !norm || !sim || !loss_pt || !mean_cnt ||
+        !contrast_form_ok(margin_mode, db, method, has_temperature, temperature))
+        return bad_arg("amc3d_contrast_variant_forward: bad argument (margin_mode 0..2, db 0..2, method 1..2, has_temperature 0..1)");
+    hipStream_t stream = (hipStream_t)stream_;
+    const ContrastForm F{margin_mode, db, method, has_temperature, mu, nu, temperature};
+    // (the same choice of kernels as amc3d_contrast_forward makes: the cosines then agree with its to the bit)
+    const bool rows = unit && ((((uintptr_t)f) | ((uintptr_t)unit)) & 15) == 0 && amc3d_contrast_backward_csr_supported(C) &&
+                      (long)m * C < (1L << 34);
+#define AMC_SIM(LPR)                                                                                                       \
+    do {                                                                                                                   \
+        hipLaunchKernelGGL((row_unit_kernel<LPR>), dim3(div_up((long)m * LPR, 256)), dim3(256), 0, stream, m, f, norm, unit); \
+        hipLaunchKernelGGL((contrast_sim_unit_kernel<LPR>), dim3(div_up(m, 4)), dim3(256), 0, stream, m, k, nbr_stride,    \
+                           (const float *)unit, nbr, a, sel, sim);                                                         \
+    } while (0)
+    if (rows && C == 16) AMC_SIM(4);
+    else if (rows && C == 32) AMC_SIM(8);
+    else if (rows && C == 64) AMC_SIM(16);
+    else if (rows && C == 128) AMC_SIM(32);
+    else if (rows && C == 256) AMC_SIM(64);
+    else {
+        hipLaunchKernelGGL(row_norm_kernel, dim3(div_up(m, 4)), dim3(256), 0, stream, m, C, f, norm);
+        hipLaunchKernelGGL(contrast_sim_kernel, dim3(div_up((long)m * 32, 256)), dim3(256), 0, stream, m, C, k, nbr_stride, f,
+                           (const float *)norm, nbr, a, sel, sim);
+    }
+#undef AMC_SIM
+    hipLaunchKernelGGL(contrast_variant_loss_kernel, dim3(div_up((long)m * 32, 256)), dim3(256), 0, stream, m, k, posmask, a, sel,
+                       F, (const float *)sim, loss_pt);
+    hipLaunchKernelGGL(masked_mean_kernel, dim3(1), dim3(1024), 0, stream, m, loss_pt, a, mean_cnt);
+    return launch_status("amc3d_contrast_variant_forward");
+}
+
+AMC_API int amc3d_contrast_variant_backward(int m, int C, int k, int nbr_stride, const float *f, const float *norm,
+                                            const int *nbr, const unsigned char *posmask, const float *a, const int *sel,
+                                            const int *rev, int margin_mode, int db, int method, int has_temperature,
+                                            float mu, float nu, float temperature, const float *sim, const float *mean_cnt,
+                                            const float *grad_out, float *gco, float *grad_f, void *stream_)
+{
+    if (m <= 0) return 0;
+    if (C <= 0 || C > 512 || k <= 0 || nbr_stride < k || !f || !norm || !nbr || !posmask || !a || !sim || !mean_cnt ||
+        !grad_out || !gco || !grad_f || !contrast_form_ok(margin_mode, db, method, has_temperature, temperature))
+        return bad_arg("amc3d_contrast_variant_backward: bad argument (C in 1..512, margin_mode 0..2, db 0..2, method 1..2)");
+    if (rev && (!sel || !amc3d_contrast_backward_csr_supported(C) || (((uintptr_t)f | (uintptr_t)grad_f) & 15) ||
+                (long)m * k > 0x7fffffffL))
+        return bad_arg("amc3d_contrast_variant_backward: rev needs sel, C in {16, 32, 64, 128, 256} and 16-byte aligned rows");
+    hipStream_t stream = (hipStream_t)stream_;
+    const ContrastForm F{margin_mode, db, method, has_temperature, mu, nu, temperature};
+    hipLaunchKernelGGL(contrast_variant_coef_kernel, dim3(div_up((long)m * 32, 256)), dim3(256), 0, stream, m, k, posmask, a, sel,
+                       F, sim, mean_cnt, grad_out, gco);
+    if (rev) {
+#define AMC_BWD(LPR)                                                                                                  \
+    hipLaunchKernelGGL((contrast_backward_rows_kernel<LPR>), dim3(div_up(m, 4)), dim3(256), 0, stream, m, k, nbr_stride, f, \
+                       norm, nbr, a, rev, sim, (const float *)gco, grad_f)
+        if (C == 16) AMC_BWD(4);
+        else if (C == 32) AMC_BWD(8);
+        else if (C == 64) AMC_BWD(16);
+        else if (C == 128) AMC_BWD(32);
+        else AMC_BWD(64);
+#undef AMC_BWD
+    } else {
+#define AMC_BWD(LPA, VPT)                                                                                                 \
+    hipLaunchKernelGGL((contrast_backward_edges_kernel<LPA, VPT>), dim3(div_up((long)m * LPA, 256)), dim3(256), 0, stream, \
+                       m, C, k, nbr_stride, f, norm, nbr, a, sel, sim, (const float *)gco, grad_f)
+        if (C <= 32) AMC_BWD(32, 1);
+        else if (C <= 64) AMC_BWD(64, 1);
+        else if (C <= 128) AMC_BWD(64, 2);
+        else if (C <= 256) AMC_BWD(64, 4);
+        else AMC_BWD(64, 8);
+#undef AMC_BWD
+    }
+    return launch_status("amc3d_contrast_variant_backward");
 }
 
 AMC_API size_t amc3d_contrast_backward_mutual_workspace_bytes(int m) { return (size_t)(m > 0 ? m : 0) * sizeof(ContrastRecord) + 64; }

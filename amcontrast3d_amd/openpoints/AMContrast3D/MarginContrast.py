@@ -6,9 +6,13 @@ Drop-in for openpoints/AMContrast3D/MarginContrast.py:
                               positive mask -> a_i -> cosine similarity -> soft-NN loss
                               with margin m_i = mu * a_i + nu on the positive pairs
 
-Only the configuration the shipped configs select is implemented
-(dist_cos + contrast_softnn_margin, cfgs/*/AMContrast3D-AA.yaml:6-30); the other
-similarity / loss variants of the reference are unreachable from its configs.
+The similarity / loss pair the configs reach is implemented (dist_cos + contrast_softnn_margin,
+cfgs/*/AMContrast3D-AA.yaml:6-30), with every value of the knobs contrast_softnn_margin reads from
+ambiguity_args: margin constant / adaptive / learned, db -m / +m / none, supervisedCL Method1 / Method2,
+temperature a number or null.  The shipped combination (adaptive, -m, Method1, a temperature) runs on the
+fused stage kernels (ops.contrast_stage, ops.contrast_stage_cm), every other one on ops.contrast_stage_variant;
+on CPU tensors the torch composition below evaluates them.  The reference's other similarity and loss
+functions (contrast_softnn_temperature, ...) are unreachable from its configs and not carried over.
 """
 import os
 
@@ -49,7 +53,14 @@ def plan_stage(n, i, stageACE_list, target, nstride, num_classes, ignore_index, 
     # tenth; round 2's reverse lists of ALL edges, ops.contrast_csr, cost 0.79 ms of integer atomics on the geometry stream).
     # More than 64 neighbours: neither, the backward takes the float-atomic form.
     rev = mutual = None
-    if anchors is not None and neighbor_idx.shape[1] <= 64:
+    default_form = ops.contrast_form_is_default(getattr(ambiguity_args, 'margin', 'adaptive'), getattr(ambiguity_args, 'db', '-m'),
+                                                getattr(ambiguity_args, 'supervisedCL', 'Method1'),
+                                                getattr(ambiguity_args, 'temperature', 1.0))
+    if anchors is not None and neighbor_idx.shape[1] <= 64 and not default_form:
+        # the other loss forms (ops.contrast_stage_variant) gather along the reverse lists of ALL edges of the selected
+        # anchors; the mutual-edge plan's rev holds the non-mutual edges only and must not reach that kernel
+        rev = ops.contrast_csr(neighbor_idx, anchors)
+    elif anchors is not None and neighbor_idx.shape[1] <= 64:
         # (one segment of more than k + 1 points: every list is full, membership follows from one distance comparison)
         d2 = neighbor_d2[..., 1:] if (torch.is_tensor(neighbor_d2) and neighbor_d2.dtype == torch.float32 and o.numel() == 1
                                       and neighbor_d2.shape[0] == neighbor_idx.shape[0] > neighbor_idx.shape[1] + 2) else None
@@ -177,7 +188,16 @@ class ContrastHead(nn.Module):
                                       ambiguity_args.nu, ambiguity_args.temperature, g.get('anchors'), g.get('rev'),
                                       g.get('mutual'))
             return loss, output_ai, target_ai
-        # other margin / decision-boundary / Method2 variants: composed from the torch-level pieces
+        if features.is_cuda:
+            # every other margin / decision-boundary / Method2 / temperature form: cosines, per-anchor loss and mean on the
+            # form-generic kernels (no (m, k, C) neighbour tensor, no boolean-mask indexing: capturable).  A plan made for
+            # the default form carries contrast_mutual's lists, which are not the reverse lists this route takes.
+            rev = g.get('rev') if g.get('mutual') is None else None
+            loss = ops.contrast_stage_variant(features, neighbor_idx, posmask, ambiguity_soft, ambiguity_args.margin,
+                                              ambiguity_args.db, ambiguity_args.supervisedCL, ambiguity_args.mu,
+                                              ambiguity_args.nu, ambiguity_args.temperature, g.get('anchors'), rev)
+            return loss, output_ai, target_ai
+        # CPU tensors: the same forms composed from the torch-level pieces
         keep = torch.logical_and(0 < ambiguity_soft, ambiguity_soft <= 1)
         m = neighbor_idx.shape[0]
         neighbor_feature = features[neighbor_idx.reshape(-1).long(), :].view(m, k, features.shape[1])

@@ -654,6 +654,107 @@ class ContrastStage(Function):
 contrast_stage = ContrastStage.apply
 
 
+_MARGIN_MODE = {"constant": 0, "adaptive": 1, "learned": 2}
+_SUPERVISED_CL = {"Method1": 1, "Method2": 2}
+
+
+def contrast_form(margin, db, supervisedCL, temperature):
+    """The config's own values (ambiguity_args.margin / db / supervisedCL / temperature) -> (margin_mode, db, method,
+    has_temperature, temperature) of include/amc3d.h.  Any db other than '-m' / '+m' means no shift, as the reference's
+    `else` (MarginContrast.py:144-145); an unknown margin or supervisedCL leaves the reference without a value and is an error."""
+    if margin not in _MARGIN_MODE:
+        raise ValueError(f"ambiguity_args.margin must be one of {sorted(_MARGIN_MODE)} (got {margin!r})")
+    if supervisedCL not in _SUPERVISED_CL:
+        raise ValueError(f"ambiguity_args.supervisedCL must be one of {sorted(_SUPERVISED_CL)} (got {supervisedCL!r})")
+    return (_MARGIN_MODE[margin], {"-m": 1, "+m": 2}.get(db, 0), _SUPERVISED_CL[supervisedCL],
+            0 if temperature is None else 1, 1.0 if temperature is None else float(temperature))
+
+
+def contrast_form_is_default(margin, db, supervisedCL, temperature):
+    """the one form ContrastStage / ContrastStageChannelMajor evaluate"""
+    return margin == "adaptive" and db == "-m" and supervisedCL == "Method1" and temperature is not None
+
+
+def contrast_variant_forward(features, neighbor_idx, posmask, a, form, mu, nu, anchors=None):
+    """Forward of ContrastStageVariant as its buffers: form = contrast_form(...) -> dict with f, norm, unit (None where the
+    width has no row kernels), sim (m,k: the cosines of the visited anchors, the bits contrast_stage's forward stores),
+    loss_pt (m: the per-anchor loss of the selected anchors; the rest of it is not written when `anchors` is given),
+    mean_cnt (2: stage loss, number of selected anchors), nbr (the index tensor the pointers refer to), k, stride."""
+    _need_gpu(features, neighbor_idx, posmask, a)
+    f = features.contiguous()
+    assert f.dtype == torch.float32 and posmask.dtype == torch.bool and posmask.is_contiguous()
+    _need_dtype(torch.float32, a=a)
+    if anchors is not None:
+        _need_dtype(torch.int32, anchors=anchors)
+        assert anchors.is_contiguous() and anchors.numel() >= f.shape[0] + 1 and anchors.device == f.device
+    nptr, k, stride, keep = _nbr_view(neighbor_idx)
+    m, C = f.shape
+    assert posmask.shape == (m, k) and a.shape == (m,) and a.is_contiguous() and neighbor_idx.shape[0] == m
+    dev = f.device
+    lib = _lib.load()
+    norm = torch.empty(m, dtype=torch.float32, device=dev)
+    unit = torch.empty_like(f) if lib.amc3d_contrast_backward_csr_supported(C) else None
+    sim = torch.empty(m, k, dtype=torch.float32, device=dev)
+    loss_pt = torch.empty(m, dtype=torch.float32, device=dev)
+    mean_cnt = torch.empty(2, dtype=torch.float32, device=dev)
+    mode, dbv, method, has_t, T = form
+    with torch.cuda.device(dev), timing.span("contrast_variant_forward", m * C * 4 + m * k * 13 + m * 12,
+                                             moved=m * C * 4 * (3 + k) + m * k * 13 + m * 12):
+        _lib.check(lib.amc3d_contrast_variant_forward(m, C, k, stride, _ptr(f), nptr, _ptr(posmask), _ptr(a),
+                                                      _ptr(anchors) if anchors is not None else None,
+                                                      mode, dbv, method, has_t, float(mu), float(nu), T, _ptr(norm),
+                                                      _ptr(unit) if unit is not None else None, _ptr(sim), _ptr(loss_pt),
+                                                      _ptr(mean_cnt), _stream(f)), "contrast_variant_forward")
+    return {"f": f, "norm": norm, "unit": unit, "sim": sim, "loss_pt": loss_pt, "mean_cnt": mean_cnt, "nbr": keep, "k": k,
+            "stride": stride}
+
+
+class ContrastStageVariant(Function):
+    """ContrastStage for every form of contrast_softnn_margin (MarginContrast.py:117-174): margin 'constant' / 'adaptive' /
+    'learned', db '-m' / '+m' / anything else (no shift), supervisedCL 'Method1' / 'Method2', temperature a number or None --
+    the config's own values.  anchors: select_anchors(a) or None.  rev: contrast_csr(neighbor_idx, anchors), the reverse lists
+    of ALL edges of the selected anchors (never contrast_mutual's, which hold the non-mutual edges only); with it and a width
+    of the row kernels the backward gathers every gradient row, otherwise it scatters with float atomics."""
+
+    @staticmethod
+    def forward(ctx, features, neighbor_idx, posmask, a, margin, db, supervisedCL, mu, nu, temperature, anchors=None, rev=None):
+        form = contrast_form(margin, db, supervisedCL, temperature)
+        b = contrast_variant_forward(features, neighbor_idx, posmask, a, form, mu, nu, anchors)
+        f, k = b["f"], b["k"]
+        m = f.shape[0]
+        if rev is not None:
+            _need_dtype(torch.int32, rev=rev)
+            assert anchors is not None and rev.is_contiguous() and rev.numel() == m + 1 + m * k and rev.device == f.device
+        ctx.save_for_backward(f, b["norm"], b["nbr"], posmask, a, b["sim"], b["mean_cnt"], anchors, rev)
+        ctx.args = (form, float(mu), float(nu), k, b["stride"])
+        return b["mean_cnt"][0].clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        f, norm, nbr, posmask, a, sim, mean_cnt, anchors, rev = ctx.saved_tensors
+        (mode, dbv, method, has_t, T), mu, nu, k, stride = ctx.args
+        m, C = f.shape
+        g = grad_out.detach().to(torch.float32).reshape(1).contiguous()
+        lib = _lib.load()
+        gather = rev is not None and bool(lib.amc3d_contrast_backward_csr_supported(C)) and f.data_ptr() % 16 == 0
+        grad_f = torch.empty_like(f) if gather else torch.zeros_like(f)  # (the gather writes every row)
+        gco = torch.empty(m * k, dtype=torch.float32, device=f.device)
+        name = "contrast_variant_backward_csr" if gather else "contrast_variant_backward"
+        with torch.cuda.device(f.device), timing.span(name, m * C * 8 + m * k * 17, moved=m * C * 4 * (2 + 2 * k) + m * k * 17):
+            _lib.check(lib.amc3d_contrast_variant_backward(m, C, k, stride, _ptr(f), _ptr(norm), _ptr(nbr), _ptr(posmask), _ptr(a),
+                                                           _ptr(anchors) if anchors is not None else None,
+                                                           _ptr(rev) if gather else None, mode, dbv, method, has_t, mu, nu, T,
+                                                           _ptr(sim), _ptr(mean_cnt), _ptr(g), _ptr(gco), _ptr(grad_f),
+                                                           _stream(f)), name)
+        return (grad_f,) + (None,) * 11
+
+
+def contrast_stage_variant(features, neighbor_idx, posmask, a, margin, db, supervisedCL, mu, nu, temperature, anchors=None,
+                           rev=None):
+    return ContrastStageVariant.apply(features, neighbor_idx, posmask, a, margin, db, supervisedCL, mu, nu, temperature,
+                                      anchors, rev)
+
+
 class ContrastStageChannelMajor(Function):
     """contrast_stage on the decoder's channel-major embeddings f_cm (B, C, n) -- what the reference flattens into (B*n, C) rows
     first (pointnext_AA.py:518-519).  The point-major copy of f is never made: the forward writes the unit rows f_i / |f_i|

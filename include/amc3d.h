@@ -249,6 +249,35 @@ int amc3d_contrast_backward_mutual(int m, int C, int k, int nbr_stride, const fl
                                    const float *mean_cnt, const float *grad_out, void *workspace, size_t workspace_bytes,
                                    float *grad_f, void *stream);
 
+/* The other forms of the loss, openpoints/AMContrast3D/MarginContrast.py:117-174 as a whole (what the ambiguity_args knobs
+ * margin / db / supervisedCL / temperature select) on the stage of :250-257; the entry points above are the one form the
+ * shipped configs use.  A form is four integers, passed at run time:
+ *   margin_mode      0 constant (m = nu, :120-121)   1 adaptive (m = mu a_i + nu, :122-125)
+ *                    2 learned  (m = (u_i - 1) a_i + v_i, u_i / v_i the means over all k slots of the negatives' / positives'
+ *                      cosines, :127-130; the margin is differentiated through, as autograd does there)
+ *   db               0 none (:144-145)   1 "-m": positives minus m (:140-141)   2 "+m": negatives plus m (:142-143)
+ *   method           1 Method1 -log(P / (P + N) + 1e-12) (:163-164)
+ *                    2 Method2 -log(sum_j (e_j pos_j / (e_j pos_j + N) + 1e-12) / (npos + 1e-12)), j over all k slots (:165-171)
+ *   has_temperature  0: no division (temperature: null, :148-149); 1: the exponent is divided by `temperature`
+ * Any other value is a bad argument.  mu is read by margin_mode 1 only, nu by 0 and 1.
+ * forward: norm (m), unit (m,C) or NULL, sel as in amc3d_contrast_forward, and with the same choice of kernels, so that sim
+ *   (m,k) -- required here -- holds the same bits; loss_pt (m) and mean_cnt (2) as there.
+ * backward: gco (m*k floats of scratch) receives dL/ds per edge of the visited anchors; then
+ *   rev != NULL (from amc3d_contrast_csr: ALL edges of the selected anchors; never the lists of amc3d_contrast_mutual):
+ *     the gather of amc3d_contrast_backward_csr -- needs sel, C in {16, 32, 64, 128, 256} and 16-byte aligned rows; every row
+ *     of grad_f is written, no zero-initialisation;
+ *   rev == NULL: float atomics as amc3d_contrast_backward, C <= 512, the caller zero-initialises grad_f.
+ * No allocation, no synchronisation. */
+int amc3d_contrast_variant_forward(int m, int C, int k, int nbr_stride, const float *f, const int *nbr,
+                                   const unsigned char *posmask, const float *a, const int *sel, int margin_mode, int db,
+                                   int method, int has_temperature, float mu, float nu, float temperature, float *norm,
+                                   float *unit /* or NULL */, float *sim, float *loss_pt, float *mean_cnt, void *stream);
+int amc3d_contrast_variant_backward(int m, int C, int k, int nbr_stride, const float *f, const float *norm, const int *nbr,
+                                    const unsigned char *posmask, const float *a, const int *sel, const int *rev /* or NULL */,
+                                    int margin_mode, int db, int method, int has_temperature, float mu, float nu,
+                                    float temperature, const float *sim, const float *mean_cnt, const float *grad_out,
+                                    float *gco, float *grad_f, void *stream);
+
 /* ---- grouped 1x1 convolution fused with its gather (fp32 MFMA) ------------------------------------
  * Replaces, for the first layer of a SetAbstraction / LocalAggregation MLP, the chain
  *   grouping_operation(features, idx) -> torch.cat([dp, fj], 1) -> nn.Conv2d 1x1 (bias-free)
