@@ -47,6 +47,15 @@ __device__ __forceinline__ float dist2_ref(float qx, float qy, float qz, float x
 __global__ void fill_i32_kernel(int *__restrict__ p, int value, size_t count);
 int fill_i32(int *p, int value, size_t count, hipStream_t stream);
 
+// the dp columns W_dp (cout,3) of a neighbourhood layer's weight [W_dp | W_f] where they lie: row c at p + c * ld (ld = 3 for a
+// contiguous copy, cin + 3 inside the layer's own weight matrix)
+struct WDp {
+    const float *p;
+    long ld;
+    __host__ __device__ explicit operator bool() const { return p != nullptr; }
+    __device__ __forceinline__ float at(int c, int j) const { return p[c * ld + j]; }
+};
+
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
 // number of set bits of `mask` below this lane

@@ -137,7 +137,7 @@ template <int CT>
 __global__ __launch_bounds__(CSR_BS, 1) void csr_collapse_kernel(int C, int n, long P, long G, int relu, const float *__restrict__ dx1_pm,
                                                            const float *__restrict__ g_pm, const int *__restrict__ rev_start,
                                                            const int *__restrict__ rev_edge, const float *__restrict__ dp,
-                                                           const float *__restrict__ w_dp, const float *__restrict__ mean,
+                                                           WDp w_dp, const float *__restrict__ mean,
                                                            const float *__restrict__ invstd, const float *__restrict__ gamma,
                                                            const float *__restrict__ beta, float *__restrict__ Q,
                                                            double *__restrict__ partial, int pts_per_group,
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(CSR_BS, 1) void csr_collapse_kernel(int C, int n, l
     const int c0 = blockIdx.y * 64;
     const int cl = threadIdx.x % CT, grp = threadIdx.x / CT;
     const int c = c0 + cl;
-    const float w0 = w_dp[c * 3 + 0], w1 = w_dp[c * 3 + 1], w2 = w_dp[c * 3 + 2];
+    const float w0 = w_dp.at(c, 0), w1 = w_dp.at(c, 1), w2 = w_dp.at(c, 2);
     const float mu = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
     double a0 = 0, a1 = 0, a2 = 0, a3 = 0, a4 = 0;
     const long g_begin = ((long)blockIdx.x * GROUPS + grp) * pts_per_group;
@@ -282,7 +282,7 @@ __global__ __launch_bounds__(CSR_BS, 1) void csr_collapse_kernel(int C, int n, l
 template <int CT>
 __global__ __launch_bounds__(256) void csr_collapse_shfl_kernel(int C, int n, long P, long G, int relu, const float *__restrict__ dx1_pm,
                                                                      const float *__restrict__ g_pm, const int *__restrict__ rev_start,
-                                                                     const float *__restrict__ w_dp, const float *__restrict__ mean,
+                                                                     WDp w_dp, const float *__restrict__ mean,
                                                                      const float *__restrict__ invstd, const float *__restrict__ gamma,
                                                                      const float *__restrict__ beta, float *__restrict__ Q,
                                                                      double *__restrict__ partial, int pts_per_group,
@@ -294,7 +294,7 @@ __global__ __launch_bounds__(256) void csr_collapse_shfl_kernel(int C, int n, lo
     const int cl = threadIdx.x % CT, grp = threadIdx.x / CT;
     const int c = c0 + cl;
     const int slot = cl & 7;  // the record of a batch of eight that this lane keeps
-    const float w0 = w_dp[c * 3 + 0], w1 = w_dp[c * 3 + 1], w2 = w_dp[c * 3 + 2];
+    const float w0 = w_dp.at(c, 0), w1 = w_dp.at(c, 1), w2 = w_dp.at(c, 2);
     const float mu = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
     double a0 = 0, a1 = 0, a2 = 0, a3 = 0, a4 = 0;
     const long g_begin = ((long)blockIdx.x * GROUPS + grp) * pts_per_group;
@@ -374,7 +374,7 @@ constexpr int CSR_STREAM_PMAX = 16;
 template <int CT>
 __global__ __launch_bounds__(256) void csr_collapse_stream_kernel(int C, long P, long G, int relu, const float *__restrict__ dx1_pm,
                                                                   const float *__restrict__ g_pm, const int *__restrict__ rev_start,
-                                                                  const float *__restrict__ w_dp, const float *__restrict__ mean,
+                                                                  WDp w_dp, const float *__restrict__ mean,
                                                                   const float *__restrict__ invstd, const float *__restrict__ gamma,
                                                                   const float *__restrict__ beta, float *__restrict__ Q,
                                                                   double *__restrict__ partial, int pts_per_group,
@@ -388,7 +388,7 @@ __global__ __launch_bounds__(256) void csr_collapse_stream_kernel(int C, long P,
     const int cl = threadIdx.x % CT, grp = threadIdx.x / CT;
     const int c = c0 + cl;
     const int slot = cl & 7;
-    const float w0 = w_dp[c * 3 + 0], w1 = w_dp[c * 3 + 1], w2 = w_dp[c * 3 + 2];
+    const float w0 = w_dp.at(c, 0), w1 = w_dp.at(c, 1), w2 = w_dp.at(c, 2);
     const float mu = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
     const long g_begin = ((long)blockIdx.x * GROUPS + grp) * pts_per_group;
     const int npts = (int)max(0L, min((long)pts_per_group, G - g_begin));
@@ -822,7 +822,7 @@ size_t csr_partials(int b, int cout, int n)
 // finalize / apply kernels of lagg.hip (amc3d_grouped_conv_bn_backward does all of it when given rev lists)
 namespace amc {
 int csr_collapse(int b, int cout, int n, int npoints, int nsample, int relu, const float *dx1_pm, const float *g_pm,
-                 const int *rev_start, const int *rev_edge, const float *rev_dp, const float *dp, const float *w_dp,
+                 const int *rev_start, const int *rev_edge, const float *rev_dp, const float *dp, WDp w_dp,
                  const float *mean, const float *invstd, const float *gamma, const float *beta, float *Q, double *partial,
                  int *nparts, hipStream_t stream)
 {

@@ -279,8 +279,10 @@ __global__ __launch_bounds__(256) void gcc_bwd_weight_kernel(int cin, int cout, 
 
 // dW (Cout, Cin+3) = sum of the partials in a fixed order (deterministic): a workgroup owns 64
 // consecutive elements, its 16 slices each sum every 16th partial, then the slices are added in order.
+// Element i = (row, col) of a (total / cols, cols) matrix goes to dW[row * ld + col]: ld > cols writes a column block of a wider
+// matrix and leaves the other columns alone (cols = 0: dW[i]).
 __global__ __launch_bounds__(1024) void gcc_reduce_partials_kernel(int total, int nparts, const float *__restrict__ partial,
-                                                                   float *__restrict__ dW)
+                                                                   float *__restrict__ dW, int cols, long ld)
 {
     __shared__ float red[16][64];
     const int e = threadIdx.x & 63, sl = threadIdx.x >> 6;
@@ -305,7 +307,7 @@ __global__ __launch_bounds__(1024) void gcc_reduce_partials_kernel(int total, in
         float t = red[0][e];
 #pragma unroll
         for (int k = 1; k < 16; ++k) t += red[k][e];
-        dW[i] = t;
+        if (cols) dW[(long)(i / cols) * ld + i % cols] = t; else dW[i] = t;
     }
 }
 
@@ -332,7 +334,17 @@ int reduce_partials(int total, int nparts, const float *partial, float *out, hip
                            (const float4 *)partial, (float4 *)out);
         return launch_status("reduce_partials");
     }
-    hipLaunchKernelGGL(gcc_reduce_partials_kernel, dim3(div_up(total, 64)), dim3(1024), 0, stream, total, nparts, partial, out);
+    hipLaunchKernelGGL(gcc_reduce_partials_kernel, dim3(div_up(total, 64)), dim3(1024), 0, stream, total, nparts, partial, out, 0, 0L);
+    return launch_status("reduce_partials");
+}
+
+// the same sums written into rows of stride ld >= cols
+int reduce_partials_rows(int rows, int cols, long ld, int nparts, const float *partial, float *out, hipStream_t stream)
+{
+    if (ld == cols) return reduce_partials(rows * cols, nparts, partial, out, stream);
+    const int total = rows * cols;
+    hipLaunchKernelGGL(gcc_reduce_partials_kernel, dim3(div_up(total, 64)), dim3(1024), 0, stream, total, nparts, partial, out, cols,
+                       ld);
     return launch_status("reduce_partials");
 }
 
@@ -419,7 +431,7 @@ AMC_API int amc3d_grouped_conv_backward(int b, int cin, int cout, int n, int npo
 #undef AMC_WRW
         const int total = cout * (cin + 3);
         hipLaunchKernelGGL(gcc_reduce_partials_kernel, dim3(div_up(total, 64)), dim3(1024), 0, stream, total, groups * b,
-                           (const float *)partial, dweight);
+                           (const float *)partial, dweight, 0, 0L);
     }
     return launch_status("amc3d_grouped_conv_backward");
 }

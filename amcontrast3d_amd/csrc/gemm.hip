@@ -31,6 +31,7 @@ constexpr int GM_S = 20;     // LDS row stride in floats
 constexpr int GM_STAGE = 2 * GM_T * GM_S;  // floats per stage (A then B)
 
 int reduce_partials(int total, int nparts, const float *partial, float *out, hipStream_t stream);  // gcc.hip
+int reduce_partials_rows(int rows, int cols, long ld, int nparts, const float *partial, float *out, hipStream_t stream);
 
 struct GemmView {  // element (r, k) of an operand at base[r * sr + k * sk]; exactly one of sr, sk is 1
     const float *base;
@@ -90,11 +91,13 @@ __device__ __forceinline__ void gm_store(const GmRegs &r, float *lds)
 
 // grid: (N tiles, M tiles, batch * splits).  Per z: batch b = z / splits, split s = z % splits owns K range
 // [s * kper, min(K, (s+1) * kper)).  Output C = cbase + z * czstride (forward/backward-data: splits = 1 and
-// czstride = M * ldc; backward-weight: one partial (M, N) per z).
+// czstride = M * ldc; backward-weight: one partial (M, N) per z).  pm != 0: C is stored transposed, C[n][m] with row length M
+// (backward-data as position-major rows): the four consecutive rows of an accumulator's (r >> 2) group are one 16-byte store
+// when pm == 2 (M % 4 == 0, aligned base), four 4-byte stores otherwise.
 template <bool A_KCONT, bool B_KCONT>
 __global__ __launch_bounds__(256) void gm_gemm_kernel(int M, int N, long K, int splits, long kper, GemmView A, long a_bstride,
                                                       GemmView B, long b_bstride, float *__restrict__ cbase, long czstride,
-                                                      long ldc, int vec_a, int vec_b)
+                                                      long ldc, int vec_a, int vec_b, int pm)
 {
     extern __shared__ __attribute__((aligned(16))) float gm_smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, pl = lane & 31, kh = lane >> 5;
@@ -172,7 +175,22 @@ __global__ __launch_bounds__(256) void gm_gemm_kernel(int M, int N, long K, int 
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int n = n0 + wn * 64 + j * 32 + pl;
-            if (n < N) {
+            if (n < N && pm) {
+                float *row = C + (long)n * M;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int m = m0 + wm * 64 + i * 32 + 8 * g + 4 * kh;
+                    if (pm == 2) {
+                        if (m < M)
+                            *reinterpret_cast<float4 *>(row + m) =
+                                make_float4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
+                    } else {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)
+                            if (m + q < M) row[m + q] = acc[i][j][4 * g + q];
+                    }
+                }
+            } else if (n < N) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
@@ -288,11 +306,12 @@ static int aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 template <bool AK, bool BK>
 static void gm_launch(int M, int N, long K, int batch, int splits, long kper, GemmView A, long abs_, GemmView B, long bbs,
-                      float *c, long czs, long ldc, int va, int vb, hipStream_t stream)
+                      float *c, long czs, long ldc, int va, int vb, hipStream_t stream, int pm = 0)
 {
     const size_t lds = 2 * GM_STAGE * sizeof(float);
+    if (pm) pm = (M % 4 == 0 && aligned16(c) && czs % 4 == 0) ? 2 : 1;
     hipLaunchKernelGGL((gm_gemm_kernel<AK, BK>), dim3(div_up(N, GM_T), div_up(M, GM_T), batch * splits), dim3(256), lds, stream, M,
-                       N, K, splits, kper, A, abs_, B, bbs, c, czs, ldc, va, vb);
+                       N, K, splits, kper, A, abs_, B, bbs, c, czs, ldc, va, vb, pm);
 }
 
 bool gemm_conv_pays(int cin, int cout) { return cin >= 64 && cout >= 64; }
@@ -344,11 +363,11 @@ size_t gemm_conv_backward_data_workspace_bytes(int b, int cin, int cout, long P)
     return sp > 1 ? (size_t)b * sp * cin * P * sizeof(float) : 0;
 }
 
-int gemm_conv_forward(int b, int cin, int cout, long P, const float *x, const float *w, const float *bias, float *y,
+int gemm_conv_forward(int b, int cin, int cout, long P, const float *x, const float *w, long ldw, const float *bias, float *y,
                       float *partial, hipStream_t stream)
 {
-    GemmView A{w, cin, 1}, B{x, 1, P};  // A(m=co,k=ci) k-contiguous; B(n=p,k=ci) at x[k*P + n]: n-contiguous
-    const int va = cin % 4 == 0 && aligned16(w), vb = P % 4 == 0 && aligned16(x);
+    GemmView A{w, ldw, 1}, B{x, 1, P};  // A(m=co,k=ci) k-contiguous; B(n=p,k=ci) at x[k*P + n]: n-contiguous
+    const int va = cin % 4 == 0 && ldw % 4 == 0 && aligned16(w), vb = P % 4 == 0 && aligned16(x);
     const int sp = partial ? gemm_short_splits(b, cout, P, cin) : 1;
     if (sp > 1) {
         const long kper = (((long)cin + sp - 1) / sp + GM_KC - 1) / GM_KC * GM_KC;
@@ -367,21 +386,23 @@ int gemm_conv_forward(int b, int cin, int cout, long P, const float *x, const fl
 }
 
 // dx (b,cin,P) = W^T . dy (b,cout,P)
-int gemm_conv_backward_data(int b, int cin, int cout, long P, const float *dy, const float *w, float *dx, float *partial,
-                            hipStream_t stream)
+// dx_pm: dx as (b,P,cin) rows; the split-K partials then have that layout too and their sum is elementwise
+int gemm_conv_backward_data(int b, int cin, int cout, long P, const float *dy, const float *w, long ldw, float *dx, int dx_pm,
+                            float *partial, hipStream_t stream)
 {
-    GemmView A{w, 1, cin}, B{dy, 1, P};  // A(m=ci,k=co) = w[k*cin + m]: m-contiguous
-    const int va = cin % 4 == 0 && aligned16(w), vb = P % 4 == 0 && aligned16(dy);
+    GemmView A{w, 1, ldw}, B{dy, 1, P};  // A(m=ci,k=co) = w[k*ldw + m]: m-contiguous
+    const int va = cin % 4 == 0 && ldw % 4 == 0 && aligned16(w), vb = P % 4 == 0 && aligned16(dy);
     const int sp = partial ? gemm_short_splits(b, cin, P, cout) : 1;
     if (sp > 1) {
         const long kper = (((long)cout + sp - 1) / sp + GM_KC - 1) / GM_KC * GM_KC;
-        gm_launch<false, false>(cin, (int)P, cout, b, sp, kper, A, 0, B, (long)cout * P, partial, (long)cin * P, P, va, vb, stream);
+        gm_launch<false, false>(cin, (int)P, cout, b, sp, kper, A, 0, B, (long)cout * P, partial, (long)cin * P, P, va, vb, stream,
+                                dx_pm);
         const long total = (long)cin * P;
         hipLaunchKernelGGL(gm_split_reduce_kernel, dim3(div_up(total, 256), b), dim3(256), 0, stream, total, P, sp,
                            (const float *)partial, (const float *)nullptr, dx);
         return launch_status("gemm_conv_backward_data");
     }
-    gm_launch<false, false>(cin, (int)P, cout, b, 1, cout, A, 0, B, (long)cout * P, dx, (long)cin * P, P, va, vb, stream);
+    gm_launch<false, false>(cin, (int)P, cout, b, 1, cout, A, 0, B, (long)cout * P, dx, (long)cin * P, P, va, vb, stream, dx_pm);
     return launch_status("gemm_conv_backward_data");
 }
 
@@ -422,8 +443,8 @@ size_t gemm_conv_wgrad_workspace_bytes(int b, int cin, int cout, long P)
 }
 
 // dw (cout,cin) = sum_b dy[b] . x[b]^T, deterministic (partials summed in a fixed order)
-int gemm_conv_backward_weight(int b, int cin, int cout, long P, const float *x, const float *dy, float *dw, float *partial,
-                              hipStream_t stream)
+int gemm_conv_backward_weight(int b, int cin, int cout, long P, const float *x, const float *dy, float *dw, long lddw,
+                              float *partial, hipStream_t stream)
 {
     long kper;
     const int s = gemm_wgrad_splits(b, cin, cout, P, &kper);
@@ -439,14 +460,14 @@ int gemm_conv_backward_weight(int b, int cin, int cout, long P, const float *x, 
                                cout, cin, P, s, kper, dy, x, partial);
         }
         if (int st = launch_status("gemm_conv_backward_weight")) return st;
-        return reduce_partials(cout * cin, b * s, partial, dw, stream);
+        return reduce_partials_rows(cout, cin, lddw, b * s, partial, dw, stream);
     }
     GemmView A{dy, P, 1}, B{x, P, 1};  // A(m=co,k=p), B(n=ci,k=p): both k-contiguous
     const int va = P % 4 == 0 && aligned16(dy), vb = P % 4 == 0 && aligned16(x);
     gm_launch<true, true>(cout, cin, P, b, s, kper, A, (long)cout * P, B, (long)cin * P, partial, (long)cout * cin, cin, va, vb,
                           stream);
     if (int st = launch_status("gemm_conv_backward_weight")) return st;
-    return reduce_partials(cout * cin, b * s, partial, dw, stream);
+    return reduce_partials_rows(cout, cin, lddw, b * s, partial, dw, stream);
 }
 
 }  // namespace amc

@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256) void lagg_stats_kernel(int C, int n, const flo
 // doubles) for the caller to all-reduce, mode 2 derives mean / invstd from the reduced sums.
 __global__ __launch_bounds__(256) void lagg_stats_finalize_kernel(int C, int nparts, double count, float eps, float momentum,
                                                                   const double *__restrict__ partial, const long long *__restrict__ mom,
-                                                                  const float *__restrict__ w_dp, float *__restrict__ mean,
+                                                                  WDp w_dp, float *__restrict__ mean,
                                                                   float *__restrict__ invstd, float *__restrict__ var_unbiased,
                                                                   double *__restrict__ gd, float *__restrict__ running_mean,
                                                                   float *__restrict__ running_var, long long *__restrict__ tracked,
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256) void lagg_stats_finalize_kernel(int C, int npa
     double m[9];
 #pragma unroll
     for (int j = 0; j < 9; ++j) m[j] = (double)mom[j] * (1.0 / LAGG_FX_M);
-    const double w0 = w_dp[c * 3 + 0], w1 = w_dp[c * 3 + 1], w2 = w_dp[c * 3 + 2];
+    const double w0 = w_dp.at(c, 0), w1 = w_dp.at(c, 1), w2 = w_dp.at(c, 2);
     const double sy = a[0] + w0 * m[0] + w1 * m[1] + w2 * m[2];
     const double quad = w0 * w0 * m[3] + w1 * w1 * m[6] + w2 * w2 * m[8] + 2.0 * (w0 * w1 * m[4] + w0 * w2 * m[5] + w1 * w2 * m[7]);
     double sy2 = a[1] + 2.0 * (w0 * a[2] + w1 * a[3] + w2 * a[4]) + quad, sy1 = sy;
@@ -212,7 +212,7 @@ __device__ __forceinline__ float lagg_bn(float x, float mean, float invstd, floa
 template <int LPR>
 __global__ __launch_bounds__(256) void lagg_pool_kernel(int C, int n, int M, int K, int cpw, int relu,
                                                         const float *__restrict__ g_pm, const int *__restrict__ idx,
-                                                        const float *__restrict__ dp, const float *__restrict__ w_dp,
+                                                        const float *__restrict__ dp, WDp w_dp,
                                                         const float *__restrict__ mean, const float *__restrict__ invstd,
                                                         const float *__restrict__ gamma, const float *__restrict__ beta,
                                                         float *__restrict__ pooled, unsigned char *__restrict__ arg,
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void lagg_pool_kernel(int C, int n, int M, int
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int c = cq + j;
-        w[j][0] = w_dp[c * 3 + 0]; w[j][1] = w_dp[c * 3 + 1]; w[j][2] = w_dp[c * 3 + 2];
+        w[j][0] = w_dp.at(c, 0); w[j][1] = w_dp.at(c, 1); w[j][2] = w_dp.at(c, 2);
         mu[j] = mean[c]; is[j] = invstd[c]; ga[j] = gamma[c]; be[j] = beta[c];
     }
     const long P = (long)M * K;
@@ -416,10 +416,10 @@ __global__ __launch_bounds__(256) void lagg_bwd_scatter_kernel(int C, int n, int
 // (*count_dev), dW_dp from the local sums (parameter gradients stay rank-local, as torch's SyncBatchNorm leaves them)
 __global__ __launch_bounds__(256) void lagg_bwd_finalize_kernel(int C, int nparts, double count, double *__restrict__ partial,
                                                                 const long long *__restrict__ mom, const double *__restrict__ gd,
-                                                                const float *__restrict__ w_dp, const float *__restrict__ mean,
+                                                                WDp w_dp, const float *__restrict__ mean,
                                                                 const float *__restrict__ invstd, const float *__restrict__ gamma,
                                                                 float *__restrict__ dgamma, float *__restrict__ dbeta,
-                                                                float *__restrict__ dw_dp, float *__restrict__ coef, int mode,
+                                                                float *__restrict__ dw_dp, long lddw, float *__restrict__ coef, int mode,
                                                                 double *__restrict__ dsums, const double *__restrict__ count_dev)
 {
     __shared__ double red[4][5];
@@ -470,12 +470,12 @@ __global__ __launch_bounds__(256) void lagg_bwd_finalize_kernel(int C, int npart
     double sa = a[0], sb = a[1];
     if (mode == 2) { sa = dsums[2 * c]; sb = dsums[2 * c + 1]; count = *count_dev; }
     const double ma = sa / count, mb = sb / count, gi = g * is;
-    const double w[3] = {w_dp[c * 3 + 0], w_dp[c * 3 + 1], w_dp[c * 3 + 2]};
+    const double w[3] = {w_dp.at(c, 0), w_dp.at(c, 1), w_dp.at(c, 2)};
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         // sum_p xhat_p dp_p[j] = is * ( sum_n G D_j + sum_j' w_j' S2[j'][j] - mu S1[j] )
         const double sxd = is * (gd[c * 3 + j] + w[0] * S2[0][j] + w[1] * S2[1][j] + w[2] * S2[2][j] - mu * m[j]);
-        dw_dp[c * 3 + j] = (float)(gi * (a[2 + j] - ma * m[j] - mb * sxd));
+        dw_dp[c * lddw + j] = (float)(gi * (a[2 + j] - ma * m[j] - mb * sxd));
     }
     coef[c * 4 + 0] = (float)gi; coef[c * 4 + 1] = (float)ma; coef[c * 4 + 2] = (float)(mb * is); coef[c * 4 + 3] = (float)mu;
 }
@@ -485,7 +485,7 @@ __global__ __launch_bounds__(256) void lagg_bwd_finalize_kernel(int C, int npart
 // grid (n tiles of 64, channel chunks of 64, b)
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void lagg_bwd_apply_kernel(int C, int n, const float *__restrict__ Q, const float *__restrict__ g_pm,
-                                                             LaggMoments gm, const float *__restrict__ w_dp,
+                                                             LaggMoments gm, WDp w_dp,
                                                              const float *__restrict__ coef, float *__restrict__ dg_cm)
 {
     __shared__ float tile[64][LAGG_NT + 1];
@@ -495,7 +495,7 @@ __global__ __launch_bounds__(256) void lagg_bwd_apply_kernel(int C, int n, const
     float gi = 0.f, ma = 0.f, mbis = 0.f, mu = 0.f, w0 = 0.f, w1 = 0.f, w2 = 0.f;
     if (c < C) {
         gi = coef[c * 4 + 0]; ma = coef[c * 4 + 1]; mbis = coef[c * 4 + 2]; mu = coef[c * 4 + 3];
-        w0 = w_dp[c * 3 + 0]; w1 = w_dp[c * 3 + 1]; w2 = w_dp[c * 3 + 2];
+        w0 = w_dp.at(c, 0); w1 = w_dp.at(c, 1); w2 = w_dp.at(c, 2);
     }
     for (int i = 0; i < 16; ++i) {
         const int nl = wave * 16 + i, nn = n0 + nl;
@@ -534,7 +534,7 @@ constexpr int LAGG_XC = 64;   // channels per workgroup
 template <int LPR>
 __global__ __launch_bounds__(256) void lagg_expand_kernel(int C, int n, long P, int relu, const float *__restrict__ g_pm,
                                                           const int *__restrict__ idx, const float *__restrict__ dp,
-                                                          const float *__restrict__ w_dp, const float *__restrict__ mean,
+                                                          WDp w_dp, const float *__restrict__ mean,
                                                           const float *__restrict__ invstd, const float *__restrict__ gamma,
                                                           const float *__restrict__ beta, float *__restrict__ x1)
 {
@@ -550,7 +550,7 @@ __global__ __launch_bounds__(256) void lagg_expand_kernel(int C, int n, long P, 
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int c = cq + j;
-        w[j][0] = w_dp[c * 3 + 0]; w[j][1] = w_dp[c * 3 + 1]; w[j][2] = w_dp[c * 3 + 2];
+        w[j][0] = w_dp.at(c, 0); w[j][1] = w_dp.at(c, 1); w[j][2] = w_dp.at(c, 2);
         mu[j] = mean[c]; is[j] = invstd[c]; ga[j] = gamma[c]; be[j] = beta[c];
     }
     // this wave's 32 positions: lane l < 32 fetches index and dp of position wave*32 + l
@@ -587,7 +587,7 @@ __global__ __launch_bounds__(256) void lagg_expand_kernel(int C, int n, long P, 
 template <int LPR>
 __global__ __launch_bounds__(256) void lagg_collapse_kernel(int C, int n, long P, int relu, const float *__restrict__ dx1,
                                                             const float *__restrict__ g_pm, const int *__restrict__ idx,
-                                                            const float *__restrict__ dp, const float *__restrict__ w_dp,
+                                                            const float *__restrict__ dp, WDp w_dp,
                                                             const float *__restrict__ mean, const float *__restrict__ invstd,
                                                             const float *__restrict__ gamma, const float *__restrict__ beta,
                                                             float *__restrict__ Q, double *__restrict__ partial, int nparts_per_b,
@@ -604,7 +604,7 @@ __global__ __launch_bounds__(256) void lagg_collapse_kernel(int C, int n, long P
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int c = cq + j;
-        w[j][0] = w_dp[c * 3 + 0]; w[j][1] = w_dp[c * 3 + 1]; w[j][2] = w_dp[c * 3 + 2];
+        w[j][0] = w_dp.at(c, 0); w[j][1] = w_dp.at(c, 1); w[j][2] = w_dp.at(c, 2);
         mu[j] = mean[c]; is[j] = invstd[c]; ga[j] = gamma[c]; be[j] = beta[c];
     }
     double acc[4][5];
@@ -764,13 +764,16 @@ AMC_API size_t amc3d_local_aggregation_workspace_bytes(int b, int cout, int n, i
 // g_cm (b,cout,n) = W_f . f, computed by the caller (amc3d_pointwise_conv_forward).  Outputs: g_pm (b,n,cout) the
 // point-major copy (kept for backward), pooled / ystar (b,cout,npoints) fp32, arg (b,cout,npoints) bytes, mean / invstd /
 // var_unbiased (cout), gd (cout,3) doubles.  training == 0: mean / invstd are INPUTS (running statistics), no statistics pass.
-AMC_API int amc3d_local_aggregation_forward(int b, int cout, int n, int npoints, int nsample, int training, int relu, float eps,
-                                            float momentum, const float *g_cm, const int *idx, const float *dp,
-                                            const float *w_dp, const void *moments, const float *gamma, const float *beta,
-                                            float *g_pm, float *pooled, unsigned char *arg, float *ystar, float *mean,
-                                            float *invstd, float *var_unbiased, double *gd, float *running_mean,
-                                            float *running_var, long long *num_batches_tracked, int phase, double *sums,
-                                            void *workspace, size_t workspace_bytes, void *stream_)
+static int local_aggregation_forward_impl(int b, int cout, int n, int npoints, int nsample, int training,
+                                              int relu, float eps, float momentum, const float *g_cm,
+                                              const int *idx, const float *dp, WDp w_dp, const void *moments,
+                                              const float *gamma, const float *beta, float *g_pm, float *pooled,
+                                              unsigned char *arg, float *ystar, float *mean, float *invstd,
+                                              float *var_unbiased, double *gd, float *running_mean,
+                                              float *running_var, long long *num_batches_tracked, int phase,
+                                              double *sums, void *workspace, size_t workspace_bytes,
+                                              void *stream_)
+
 {
     if (training && phase != 0 && !sums) return bad_arg("amc3d_local_aggregation_forward: phase 1 / 2 need the sums buffer");
     if (b <= 0 || npoints <= 0) return 0;
@@ -812,14 +815,48 @@ AMC_API int amc3d_local_aggregation_forward(int b, int cout, int n, int npoints,
     return launch_status("amc3d_local_aggregation_forward");
 }
 
+AMC_API int amc3d_local_aggregation_forward(int b, int cout, int n, int npoints, int nsample, int training, int relu, float eps,
+                                            float momentum, const float *g_cm, const int *idx, const float *dp,
+                                            const float *w_dp, const void *moments, const float *gamma, const float *beta,
+                                            float *g_pm, float *pooled, unsigned char *arg, float *ystar, float *mean,
+                                            float *invstd, float *var_unbiased, double *gd, float *running_mean,
+                                            float *running_var, long long *num_batches_tracked, int phase, double *sums,
+                                            void *workspace, size_t workspace_bytes, void *stream_)
+{
+    return local_aggregation_forward_impl(b, cout, n, npoints, nsample, training, relu, eps, momentum, g_cm, idx, dp, WDp{w_dp, 3}, moments, gamma,
+        beta, g_pm, pooled, arg, ystar, mean, invstd, var_unbiased, gd, running_mean, running_var,
+        num_batches_tracked, phase, sums, workspace, workspace_bytes, stream_);
+}
+
+// the same with w_dp addressed at a row stride (floats): the dp columns inside the layer's own (cout, cin + 3) weight
+AMC_API int amc3d_local_aggregation_forward_strided(int b, int cout, int n, int npoints, int nsample,
+                                                    int training, int relu, float eps, float momentum,
+                                                    const float *g_cm, const int *idx, const float *dp,
+                                                    const float *w_dp, long ldw, const void *moments,
+                                                    const float *gamma, const float *beta, float *g_pm,
+                                                    float *pooled, unsigned char *arg, float *ystar, float *mean,
+                                                    float *invstd, float *var_unbiased, double *gd,
+                                                    float *running_mean, float *running_var,
+                                                    long long *num_batches_tracked, int phase, double *sums,
+                                                    void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (ldw < 3) return bad_arg("amc3d_local_aggregation_forward_strided: row stride below 3");
+    return local_aggregation_forward_impl(b, cout, n, npoints, nsample, training, relu, eps, momentum, g_cm, idx, dp, WDp{w_dp, ldw}, moments,
+        gamma, beta, g_pm, pooled, arg, ystar, mean, invstd, var_unbiased, gd, running_mean, running_var,
+        num_batches_tracked, phase, sums, workspace, workspace_bytes, stream_);
+}
+
 // dg_cm (b,cout,n): gradient w.r.t. G = W_f . f (the caller runs the pointwise conv's backward on it);
 // dw_dp (cout,3), dgamma, dbeta (cout)
-AMC_API int amc3d_local_aggregation_backward(int b, int cout, int n, int npoints, int nsample, int relu, const float *dpooled,
-                                             const float *ystar, const unsigned char *arg, const float *g_pm, const int *idx,
-                                             const float *dp, const float *w_dp, const void *moments, const double *gd,
-                                             const float *mean, const float *invstd, const float *gamma, const float *beta,
-                                             float *dg_cm, float *dw_dp, float *dgamma, float *dbeta, int phase, double *dsums,
-                                             const double *count_dev, void *workspace, size_t workspace_bytes, void *stream_)
+static int local_aggregation_backward_impl(int b, int cout, int n, int npoints, int nsample, int relu,
+                                               const float *dpooled, const float *ystar, const unsigned char *arg,
+                                               const float *g_pm, const int *idx, const float *dp, WDp w_dp,
+                                               const void *moments, const double *gd, const float *mean,
+                                               const float *invstd, const float *gamma, const float *beta,
+                                               float *dg_cm, float *dw_dp, long lddw, float *dgamma, float *dbeta,
+                                               int phase, double *dsums, const double *count_dev, void *workspace,
+                                               size_t workspace_bytes, void *stream_)
+
 {
     if (b <= 0 || npoints <= 0) return 0;
     if (phase != 0 && (!dsums || (phase == 2 && !count_dev))) return bad_arg("amc3d_local_aggregation_backward: phase 1 / 2 need dsums (and the count)");
@@ -847,23 +884,56 @@ AMC_API int amc3d_local_aggregation_backward(int b, int cout, int n, int npoints
     }
     hipLaunchKernelGGL(lagg_bwd_finalize_kernel, dim3(cout), dim3(256), 0, stream, cout, nparts_b * b,
                        (double)b * (double)npoints * (double)nsample, partial, gm.mom, gd, w_dp, mean, invstd,
-                       gamma, dgamma, dbeta, dw_dp, coef, phase, dsums, count_dev);
+                       gamma, dgamma, dbeta, dw_dp, lddw, coef, phase, dsums, count_dev);
     if (phase == 1) return launch_status("amc3d_local_aggregation_backward");
     hipLaunchKernelGGL(lagg_bwd_apply_kernel, dim3(div_up(n, LAGG_NT), div_up(cout, 64), b), dim3(256), 0, stream, cout, n,
                        (const float *)Q, g_pm, gm, w_dp, (const float *)coef, dg_cm);
     return launch_status("amc3d_local_aggregation_backward");
 }
 
+AMC_API int amc3d_local_aggregation_backward(int b, int cout, int n, int npoints, int nsample, int relu, const float *dpooled,
+                                             const float *ystar, const unsigned char *arg, const float *g_pm, const int *idx,
+                                             const float *dp, const float *w_dp, const void *moments, const double *gd,
+                                             const float *mean, const float *invstd, const float *gamma, const float *beta,
+                                             float *dg_cm, float *dw_dp, float *dgamma, float *dbeta, int phase, double *dsums,
+                                             const double *count_dev, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    return local_aggregation_backward_impl(b, cout, n, npoints, nsample, relu, dpooled, ystar, arg, g_pm, idx, dp, WDp{w_dp, 3}, moments, gd, mean,
+        invstd, gamma, beta, dg_cm, dw_dp, 3, dgamma, dbeta, phase, dsums, count_dev, workspace, workspace_bytes,
+        stream_);
+}
+
+// the same with w_dp and dw_dp addressed at a row stride (floats): the dp columns inside the layer's own (cout, cin + 3) weight and its gradient
+AMC_API int amc3d_local_aggregation_backward_strided(int b, int cout, int n, int npoints, int nsample, int relu,
+                                                     const float *dpooled, const float *ystar,
+                                                     const unsigned char *arg, const float *g_pm, const int *idx,
+                                                     const float *dp, const float *w_dp, long ldw,
+                                                     const void *moments, const double *gd, const float *mean,
+                                                     const float *invstd, const float *gamma, const float *beta,
+                                                     float *dg_cm, float *dw_dp, long lddw, float *dgamma,
+                                                     float *dbeta, int phase, double *dsums,
+                                                     const double *count_dev, void *workspace,
+                                                     size_t workspace_bytes, void *stream_)
+{
+    if (ldw < 3 || lddw < 3) return bad_arg("amc3d_local_aggregation_backward_strided: row stride below 3");
+    return local_aggregation_backward_impl(b, cout, n, npoints, nsample, relu, dpooled, ystar, arg, g_pm, idx, dp, WDp{w_dp, ldw}, moments, gd, mean,
+        invstd, gamma, beta, dg_cm, dw_dp, lddw, dgamma, dbeta, phase, dsums, count_dev, workspace,
+        workspace_bytes, stream_);
+}
+
 // ---- first layer of a multi-layer SetAbstraction MLP: conv (before the gather) + BatchNorm + ReLU, x1 materialised ----
 AMC_API int amc3d_grouped_conv_bn_supported(int cout, int nsample) { return lagg_expand_supported(cout, nsample) ? 1 : 0; }
 
 // x1 (b,cout,npoints,32) = [relu](bn(G[idx] + W_dp . dp)); other arguments as amc3d_local_aggregation_forward
-AMC_API int amc3d_grouped_conv_bn_forward(int b, int cout, int n, int npoints, int nsample, int training, int relu, float eps,
-                                          float momentum, const float *g_cm, const int *idx, const float *dp, const float *w_dp,
-                                          const void *moments, const float *gamma, const float *beta, float *g_pm, float *x1,
-                                          float *mean, float *invstd, float *var_unbiased, double *gd, float *running_mean,
-                                          float *running_var, long long *num_batches_tracked, int phase, double *sums,
-                                          void *workspace, size_t workspace_bytes, void *stream_)
+static int grouped_conv_bn_forward_impl(int b, int cout, int n, int npoints, int nsample, int training,
+                                            int relu, float eps, float momentum, const float *g_cm,
+                                            const int *idx, const float *dp, WDp w_dp, const void *moments,
+                                            const float *gamma, const float *beta, float *g_pm, float *x1,
+                                            float *mean, float *invstd, float *var_unbiased, double *gd,
+                                            float *running_mean, float *running_var,
+                                            long long *num_batches_tracked, int phase, double *sums,
+                                            void *workspace, size_t workspace_bytes, void *stream_)
+
 {
     if (training && phase != 0 && !sums) return bad_arg("amc3d_grouped_conv_bn_forward: phase 1 / 2 need the sums buffer");
     if (b <= 0 || npoints <= 0) return 0;
@@ -898,13 +968,44 @@ AMC_API int amc3d_grouped_conv_bn_forward(int b, int cout, int n, int npoints, i
     return launch_status("amc3d_grouped_conv_bn_forward");
 }
 
+AMC_API int amc3d_grouped_conv_bn_forward(int b, int cout, int n, int npoints, int nsample, int training, int relu, float eps,
+                                          float momentum, const float *g_cm, const int *idx, const float *dp, const float *w_dp,
+                                          const void *moments, const float *gamma, const float *beta, float *g_pm, float *x1,
+                                          float *mean, float *invstd, float *var_unbiased, double *gd, float *running_mean,
+                                          float *running_var, long long *num_batches_tracked, int phase, double *sums,
+                                          void *workspace, size_t workspace_bytes, void *stream_)
+{
+    return grouped_conv_bn_forward_impl(b, cout, n, npoints, nsample, training, relu, eps, momentum, g_cm, idx, dp, WDp{w_dp, 3}, moments, gamma,
+        beta, g_pm, x1, mean, invstd, var_unbiased, gd, running_mean, running_var, num_batches_tracked, phase,
+        sums, workspace, workspace_bytes, stream_);
+}
+
+// the same with w_dp addressed at a row stride (floats): the dp columns inside the layer's own (cout, cin + 3) weight
+AMC_API int amc3d_grouped_conv_bn_forward_strided(int b, int cout, int n, int npoints, int nsample, int training,
+                                                  int relu, float eps, float momentum, const float *g_cm,
+                                                  const int *idx, const float *dp, const float *w_dp, long ldw,
+                                                  const void *moments, const float *gamma, const float *beta,
+                                                  float *g_pm, float *x1, float *mean, float *invstd,
+                                                  float *var_unbiased, double *gd, float *running_mean,
+                                                  float *running_var, long long *num_batches_tracked, int phase,
+                                                  double *sums, void *workspace, size_t workspace_bytes,
+                                                  void *stream_)
+{
+    if (ldw < 3) return bad_arg("amc3d_grouped_conv_bn_forward_strided: row stride below 3");
+    return grouped_conv_bn_forward_impl(b, cout, n, npoints, nsample, training, relu, eps, momentum, g_cm, idx, dp, WDp{w_dp, ldw}, moments,
+        gamma, beta, g_pm, x1, mean, invstd, var_unbiased, gd, running_mean, running_var, num_batches_tracked,
+        phase, sums, workspace, workspace_bytes, stream_);
+}
+
 // from dx1 (b,cout,npoints,32): dg_cm (b,cout,n), dw_dp (cout,3), dgamma, dbeta
-AMC_API int amc3d_grouped_conv_bn_backward(int b, int cout, int n, int npoints, int nsample, int relu, const float *dx1,
-                                           const float *g_pm, const int *idx, const float *dp, const float *w_dp,
-                                           const void *moments, const double *gd, const float *mean, const float *invstd,
-                                           const float *gamma, const float *beta, float *dg_cm, float *dw_dp, float *dgamma,
-                                           float *dbeta, int phase, double *dsums, const double *count_dev, void *workspace,
-                                           size_t workspace_bytes, void *stream_)
+static int grouped_conv_bn_backward_impl(int b, int cout, int n, int npoints, int nsample, int relu,
+                                             const float *dx1, const float *g_pm, const int *idx, const float *dp,
+                                             WDp w_dp, const void *moments, const double *gd, const float *mean,
+                                             const float *invstd, const float *gamma, const float *beta,
+                                             float *dg_cm, float *dw_dp, long lddw, float *dgamma, float *dbeta,
+                                             int phase, double *dsums, const double *count_dev, void *workspace,
+                                             size_t workspace_bytes, void *stream_)
+
 {
     if (b <= 0 || npoints <= 0) return 0;
     if (phase != 0 && (!dsums || (phase == 2 && !count_dev))) return bad_arg("amc3d_grouped_conv_bn_backward: phase 1 / 2 need dsums (and the count)");
@@ -931,11 +1032,38 @@ AMC_API int amc3d_grouped_conv_bn_backward(int b, int cout, int n, int npoints, 
     }
     hipLaunchKernelGGL(lagg_bwd_finalize_kernel, dim3(cout), dim3(256), 0, stream, cout, nparts_b * b,
                        (double)b * (double)npoints * (double)nsample, partial, gm.mom, gd, w_dp, mean, invstd,
-                       gamma, dgamma, dbeta, dw_dp, coef, phase, dsums, count_dev);
+                       gamma, dgamma, dbeta, dw_dp, lddw, coef, phase, dsums, count_dev);
     if (phase == 1) return launch_status("amc3d_grouped_conv_bn_backward");
     hipLaunchKernelGGL(lagg_bwd_apply_kernel, dim3(div_up(n, LAGG_NT), div_up(cout, 64), b), dim3(256), 0, stream, cout, n,
                        (const float *)Q, g_pm, gm, w_dp, (const float *)coef, dg_cm);
     return launch_status("amc3d_grouped_conv_bn_backward");
+}
+
+AMC_API int amc3d_grouped_conv_bn_backward(int b, int cout, int n, int npoints, int nsample, int relu, const float *dx1,
+                                           const float *g_pm, const int *idx, const float *dp, const float *w_dp,
+                                           const void *moments, const double *gd, const float *mean, const float *invstd,
+                                           const float *gamma, const float *beta, float *dg_cm, float *dw_dp, float *dgamma,
+                                           float *dbeta, int phase, double *dsums, const double *count_dev, void *workspace,
+                                           size_t workspace_bytes, void *stream_)
+{
+    return grouped_conv_bn_backward_impl(b, cout, n, npoints, nsample, relu, dx1, g_pm, idx, dp, WDp{w_dp, 3}, moments, gd, mean, invstd, gamma,
+        beta, dg_cm, dw_dp, 3, dgamma, dbeta, phase, dsums, count_dev, workspace, workspace_bytes, stream_);
+}
+
+// the same with w_dp and dw_dp addressed at a row stride (floats): the dp columns inside the layer's own (cout, cin + 3) weight and its gradient
+AMC_API int amc3d_grouped_conv_bn_backward_strided(int b, int cout, int n, int npoints, int nsample, int relu,
+                                                   const float *dx1, const float *g_pm, const int *idx,
+                                                   const float *dp, const float *w_dp, long ldw,
+                                                   const void *moments, const double *gd, const float *mean,
+                                                   const float *invstd, const float *gamma, const float *beta,
+                                                   float *dg_cm, float *dw_dp, long lddw, float *dgamma,
+                                                   float *dbeta, int phase, double *dsums,
+                                                   const double *count_dev, void *workspace,
+                                                   size_t workspace_bytes, void *stream_)
+{
+    if (ldw < 3 || lddw < 3) return bad_arg("amc3d_grouped_conv_bn_backward_strided: row stride below 3");
+    return grouped_conv_bn_backward_impl(b, cout, n, npoints, nsample, relu, dx1, g_pm, idx, dp, WDp{w_dp, ldw}, moments, gd, mean, invstd, gamma,
+        beta, dg_cm, dw_dp, lddw, dgamma, dbeta, phase, dsums, count_dev, workspace, workspace_bytes, stream_);
 }
 
 // the same backward without float atomics: rev_start / rev_edge are the reverse lists of amc3d_group_csr; dx1 is first
@@ -943,7 +1071,7 @@ AMC_API int amc3d_grouped_conv_bn_backward(int b, int cout, int n, int npoints, 
 // (csrc/csr.hip): deterministic, and ~2.5x faster than the atomic scatter.  workspace: amc3d_grouped_conv_bn_csr_workspace_bytes
 namespace amc {
 int csr_collapse(int b, int cout, int n, int npoints, int nsample, int relu, const float *dx1_pm, const float *g_pm,
-                 const int *rev_start, const int *rev_edge, const float *rev_dp, const float *dp, const float *w_dp,
+                 const int *rev_start, const int *rev_edge, const float *rev_dp, const float *dp, WDp w_dp,
                  const float *mean, const float *invstd, const float *gamma, const float *beta, float *Q, double *partial,
                  int *nparts, hipStream_t stream);
 size_t csr_partials(int b, int cout, int n);
@@ -958,13 +1086,16 @@ AMC_API size_t amc3d_grouped_conv_bn_csr_workspace_bytes(int b, int cout, int n,
            (size_t)b * npoints * nsample * cout * sizeof(float);
 }
 
-AMC_API int amc3d_grouped_conv_bn_backward_csr(int b, int cout, int n, int npoints, int nsample, int relu, const float *dx1,
-                                               int dx1_position_major, const float *g_pm, const int *rev_start, const int *rev_edge,
-                                               const float *rev_dp, const float *dp,
-                                               const float *w_dp, const void *moments, const double *gd, const float *mean,
-                                               const float *invstd, const float *gamma, const float *beta, float *dg_cm,
-                                               float *dw_dp, float *dgamma, float *dbeta, int phase, double *dsums,
-                                               const double *count_dev, void *workspace, size_t workspace_bytes, void *stream_)
+static int grouped_conv_bn_backward_csr_impl(int b, int cout, int n, int npoints, int nsample, int relu,
+                                                 const float *dx1, int dx1_position_major, const float *g_pm,
+                                                 const int *rev_start, const int *rev_edge, const float *rev_dp,
+                                                 const float *dp, WDp w_dp, const void *moments, const double *gd,
+                                                 const float *mean, const float *invstd, const float *gamma,
+                                                 const float *beta, float *dg_cm, float *dw_dp, long lddw,
+                                                 float *dgamma, float *dbeta, int phase, double *dsums,
+                                                 const double *count_dev, void *workspace, size_t workspace_bytes,
+                                                 void *stream_)
+
 {
     if (b <= 0 || npoints <= 0) return 0;
     if (phase != 0 && (!dsums || (phase == 2 && !count_dev))) return bad_arg("amc3d_grouped_conv_bn_backward_csr: phase 1 / 2 need dsums (and the count)");
@@ -996,9 +1127,40 @@ AMC_API int amc3d_grouped_conv_bn_backward_csr(int b, int cout, int n, int npoin
     }
     hipLaunchKernelGGL(lagg_bwd_finalize_kernel, dim3(cout), dim3(256), 0, stream, cout, nparts,
                        (double)b * (double)npoints * (double)nsample, partial, gm.mom, gd, w_dp, mean, invstd,
-                       gamma, dgamma, dbeta, dw_dp, coef, phase, dsums, count_dev);
+                       gamma, dgamma, dbeta, dw_dp, lddw, coef, phase, dsums, count_dev);
     if (phase == 1) return launch_status("amc3d_grouped_conv_bn_backward_csr");
     hipLaunchKernelGGL(lagg_bwd_apply_kernel, dim3(div_up(n, LAGG_NT), div_up(cout, 64), b), dim3(256), 0, stream, cout, n,
                        (const float *)Q, g_pm, gm, w_dp, (const float *)coef, dg_cm);
     return launch_status("amc3d_grouped_conv_bn_backward_csr");
+}
+
+AMC_API int amc3d_grouped_conv_bn_backward_csr(int b, int cout, int n, int npoints, int nsample, int relu, const float *dx1,
+                                               int dx1_position_major, const float *g_pm, const int *rev_start, const int *rev_edge,
+                                               const float *rev_dp, const float *dp,
+                                               const float *w_dp, const void *moments, const double *gd, const float *mean,
+                                               const float *invstd, const float *gamma, const float *beta, float *dg_cm,
+                                               float *dw_dp, float *dgamma, float *dbeta, int phase, double *dsums,
+                                               const double *count_dev, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    return grouped_conv_bn_backward_csr_impl(b, cout, n, npoints, nsample, relu, dx1, dx1_position_major, g_pm, rev_start, rev_edge, rev_dp, dp,
+        WDp{w_dp, 3}, moments, gd, mean, invstd, gamma, beta, dg_cm, dw_dp, 3, dgamma, dbeta, phase, dsums,
+        count_dev, workspace, workspace_bytes, stream_);
+}
+
+// the same with w_dp and dw_dp addressed at a row stride (floats): the dp columns inside the layer's own (cout, cin + 3) weight and its gradient
+AMC_API int amc3d_grouped_conv_bn_backward_csr_strided(int b, int cout, int n, int npoints, int nsample, int relu,
+                                                       const float *dx1, int dx1_position_major,
+                                                       const float *g_pm, const int *rev_start,
+                                                       const int *rev_edge, const float *rev_dp, const float *dp,
+                                                       const float *w_dp, long ldw, const void *moments,
+                                                       const double *gd, const float *mean, const float *invstd,
+                                                       const float *gamma, const float *beta, float *dg_cm,
+                                                       float *dw_dp, long lddw, float *dgamma, float *dbeta,
+                                                       int phase, double *dsums, const double *count_dev,
+                                                       void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (ldw < 3 || lddw < 3) return bad_arg("amc3d_grouped_conv_bn_backward_csr_strided: row stride below 3");
+    return grouped_conv_bn_backward_csr_impl(b, cout, n, npoints, nsample, relu, dx1, dx1_position_major, g_pm, rev_start, rev_edge, rev_dp, dp,
+        WDp{w_dp, ldw}, moments, gd, mean, invstd, gamma, beta, dg_cm, dw_dp, lddw, dgamma, dbeta, phase, dsums,
+        count_dev, workspace, workspace_bytes, stream_);
 }

@@ -28,12 +28,15 @@ constexpr int PWW_TP = 64;          // positions per tile in the weight-gradient
 constexpr int PWW_LD = PWW_TP + 1;
 
 int reduce_partials(int total, int nparts, const float *partial, float *out, hipStream_t stream);  // gcc.hip
+int reduce_partials_rows(int rows, int cols, long ld, int nparts, const float *partial, float *out, hipStream_t stream);
 
 // Y[b][m][p] = sum_k A(m,k) X[b][k][p] (+ bias[m]),  A(m,k) = a[m*sam + k*sak]
+// pm != 0: Y is written as position-major rows Y[b][p][m] (no bias): a lane holds four consecutive channels of its position per
+// (r >> 2) group -- one 16-byte store when pm == 2 (M % 4 == 0, aligned base), four 4-byte stores otherwise
 template <int NCT>
 __global__ __launch_bounds__(256) void pw_gemm_kernel(int M, int K, long P, const float *__restrict__ a, long sam,
                                                       long sak, const float *__restrict__ bias,
-                                                      const float *__restrict__ x, float *__restrict__ y, int vec)
+                                                      const float *__restrict__ x, float *__restrict__ y, int vec, int pm)
 {
     __shared__ float as[NCT * 32 * PW_LDA];
     __shared__ __attribute__((aligned(16))) float xs[PW_KC * PW_TP];
@@ -99,7 +102,22 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(int M, int K, long P, cons
     }
     // accumulator layout: column = lane & 31 (position), row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
     const long p = p0 + wave * 32 + pl;
-    if (p < P) {
+    if (p < P && pm) {
+        float *row = Y + (size_t)p * M;
+#pragma unroll
+        for (int c = 0; c < NCT; ++c)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int m = m0 + c * 32 + 8 * g + 4 * kh;
+                if (pm == 2) {
+                    if (m < M) *(float4 *)(row + m) = make_float4(acc[c][4 * g], acc[c][4 * g + 1], acc[c][4 * g + 2], acc[c][4 * g + 3]);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (m + j < M) row[m + j] = acc[c][4 * g + j];
+                }
+            }
+    } else if (p < P) {
 #pragma unroll
         for (int c = 0; c < NCT; ++c)
 #pragma unroll
@@ -288,20 +306,21 @@ static PwSplit pw_split(int b, int cin, int cout, long P)
 
 template <int NCT>
 static void launch_pw_gemm(int b, int M, int K, long P, const float *a, long sam, long sak, const float *bias,
-                           const float *x, float *y, hipStream_t stream)
+                           const float *x, float *y, int pm, hipStream_t stream)
 {
     const int vec = (P % 4 == 0) && (((uintptr_t)x & 15) == 0);
+    if (pm) pm = (M % 4 == 0 && ((uintptr_t)y & 15) == 0) ? 2 : 1;
     hipLaunchKernelGGL((pw_gemm_kernel<NCT>), dim3(div_up(P, PW_TP), div_up(M, NCT * 32), b), dim3(256), 0, stream, M, K, P,
-                       a, sam, sak, bias, x, y, vec);
+                       a, sam, sak, bias, x, y, vec, pm);
 }
 
 static void pw_gemm(int b, int M, int K, long P, const float *a, long sam, long sak, const float *bias, const float *x,
-                    float *y, hipStream_t stream)
+                    float *y, int pm, hipStream_t stream)
 {
-    if (M <= 32) launch_pw_gemm<1>(b, M, K, P, a, sam, sak, bias, x, y, stream);
-    else if (M <= 64) launch_pw_gemm<2>(b, M, K, P, a, sam, sak, bias, x, y, stream);
-    else if (M <= 96) launch_pw_gemm<3>(b, M, K, P, a, sam, sak, bias, x, y, stream);
-    else launch_pw_gemm<4>(b, M, K, P, a, sam, sak, bias, x, y, stream);
+    if (M <= 32) launch_pw_gemm<1>(b, M, K, P, a, sam, sak, bias, x, y, pm, stream);
+    else if (M <= 64) launch_pw_gemm<2>(b, M, K, P, a, sam, sak, bias, x, y, pm, stream);
+    else if (M <= 96) launch_pw_gemm<3>(b, M, K, P, a, sam, sak, bias, x, y, pm, stream);
+    else launch_pw_gemm<4>(b, M, K, P, a, sam, sak, bias, x, y, pm, stream);
 }
 
 template <int NCT, int NIT>
@@ -317,8 +336,8 @@ static void launch_pw_wgrad(const PwSplit &s, int M, int K, long P, const float 
 
 // gemm.hip: the MFMA-bound variant for layers with >= 64 channels on both sides
 bool gemm_conv_pays(int cin, int cout);
-int gemm_conv_forward(int b, int cin, int cout, long P, const float *x, const float *w, const float *bias, float *y, float *partial,
-                      hipStream_t stream);
+int gemm_conv_forward(int b, int cin, int cout, long P, const float *x, const float *w, long ldw, const float *bias, float *y,
+                      float *partial, hipStream_t stream);
 bool gemm_conv_short(int b, int rows, long P);
 // the 128 x 128-tile GEMM (gemm.hip) instead of the streaming kernel above: deep layers without a bias, and -- with or without
 // one -- deep layers so short that the streaming kernel's one-workgroup-per-tile walk of the whole K axis leaves the chip empty
@@ -329,25 +348,37 @@ static bool pw_forward_deep(int b, int cin, int cout, long P, bool has_bias)
 }
 size_t gemm_conv_forward_workspace_bytes(int b, int cin, int cout, long P);
 size_t gemm_conv_backward_data_workspace_bytes(int b, int cin, int cout, long P);
-int gemm_conv_backward_data(int b, int cin, int cout, long P, const float *dy, const float *w, float *dx, float *partial, hipStream_t stream);
+int gemm_conv_backward_data(int b, int cin, int cout, long P, const float *dy, const float *w, long ldw, float *dx, int dx_pm,
+                            float *partial, hipStream_t stream);
 size_t gemm_conv_wgrad_workspace_bytes(int b, int cin, int cout, long P);
-int gemm_conv_backward_weight(int b, int cin, int cout, long P, const float *x, const float *dy, float *dw, float *partial,
-                              hipStream_t stream);
+int gemm_conv_backward_weight(int b, int cin, int cout, long P, const float *x, const float *dy, float *dw, long lddw,
+                              float *partial, hipStream_t stream);
 
 }  // namespace amc
 
 using namespace amc;
 
+// forward with a row stride for the weight (ldw >= cin): a column block of a wider matrix is an operand where it lies
+static int pw_forward(const char *what, int b, int cin, int cout, long P, const float *x, const float *weight, long ldw,
+                      const float *bias, float *y, void *workspace, size_t workspace_bytes, hipStream_t stream)
+{
+    if (b <= 0 || P <= 0 || cout <= 0) return 0;
+    if (cin <= 0 || !x || !weight || !y || ldw < cin) return bad_arg(what);
+    if (pw_forward_deep(b, cin, cout, P, bias != nullptr)) {
+        const size_t need = gemm_conv_forward_workspace_bytes(b, cin, cout, P);
+        return gemm_conv_forward(b, cin, cout, P, x, weight, ldw, bias, y,
+                                 (need && workspace && workspace_bytes >= need) ? (float *)workspace : nullptr, stream);
+    }
+    pw_gemm(b, cout, cin, P, weight, ldw, 1, bias, x, y, 0, stream);
+    return launch_status(what);
+}
+
 // y (b,cout,P) = weight (cout,cin) . x (b,cin,P) (+ bias)
 AMC_API int amc3d_pointwise_conv_forward(int b, int cin, int cout, long P, const float *x, const float *weight,
                                          const float *bias, float *y, void *stream)
 {
-    if (b <= 0 || P <= 0 || cout <= 0) return 0;
-    if (cin <= 0 || !x || !weight || !y) return bad_arg("amc3d_pointwise_conv_forward: bad argument");
-    if (pw_forward_deep(b, cin, cout, P, bias != nullptr))
-        return gemm_conv_forward(b, cin, cout, P, x, weight, bias, y, nullptr, (hipStream_t)stream);
-    pw_gemm(b, cout, cin, P, weight, cin, 1, bias, x, y, (hipStream_t)stream);
-    return launch_status("amc3d_pointwise_conv_forward");
+    return pw_forward("amc3d_pointwise_conv_forward: bad argument", b, cin, cout, P, x, weight, cin, bias, y, nullptr, 0,
+                      (hipStream_t)stream);
 }
 
 // the same with scratch for the short deep layers (a few hundred positions per cloud), whose K axis is then split over
@@ -365,10 +396,22 @@ AMC_API int amc3d_pointwise_conv_forward_ws(int b, int cin, int cout, long P, co
     if (cin <= 0 || !x || !weight || !y) return bad_arg("amc3d_pointwise_conv_forward_ws: bad argument");
     const size_t need = amc3d_pointwise_conv_forward_workspace_bytes(b, cin, cout, P, bias != nullptr);
     if (need && (!workspace || workspace_bytes < need)) return bad_arg("amc3d_pointwise_conv_forward_ws: workspace too small");
-    if (pw_forward_deep(b, cin, cout, P, bias != nullptr))
-        return gemm_conv_forward(b, cin, cout, P, x, weight, bias, y, need ? (float *)workspace : nullptr, (hipStream_t)stream);
-    pw_gemm(b, cout, cin, P, weight, cin, 1, bias, x, y, (hipStream_t)stream);
-    return launch_status("amc3d_pointwise_conv_forward_ws");
+    return pw_forward("amc3d_pointwise_conv_forward_ws: bad argument", b, cin, cout, P, x, weight, cin, bias, y, workspace,
+                      workspace_bytes, (hipStream_t)stream);
+}
+
+// the same with weight (cout, cin) at row stride ldw floats (ldw >= cin): e.g. weight = W + 3, ldw = cin + 3 for the feature
+// columns of a neighbourhood layer's [W_dp | W_f].  A view that is not 16-byte aligned takes scalar loads for the weight only.
+AMC_API int amc3d_pointwise_conv_forward_strided(int b, int cin, int cout, long P, const float *x, const float *weight, long ldw,
+                                                 const float *bias, float *y, void *workspace, size_t workspace_bytes,
+                                                 void *stream)
+{
+    if (b > 0 && P > 0 && cin > 0 && cout > 0) {
+        const size_t need = amc3d_pointwise_conv_forward_workspace_bytes(b, cin, cout, P, bias != nullptr);
+        if (need && (!workspace || workspace_bytes < need)) return bad_arg("amc3d_pointwise_conv_forward_strided: workspace too small");
+    }
+    return pw_forward("amc3d_pointwise_conv_forward_strided: bad argument", b, cin, cout, P, x, weight, ldw, bias, y, workspace,
+                      workspace_bytes, (hipStream_t)stream);
 }
 
 AMC_API size_t amc3d_pointwise_conv_workspace_bytes(int b, int cin, int cout, long P)
@@ -383,27 +426,25 @@ AMC_API size_t amc3d_pointwise_conv_workspace_bytes(int b, int cin, int cout, lo
     return (size_t)s.groups * cout * cin * sizeof(float);
 }
 
-// dx (b,cin,P) = weight^T . dy   (when dx != NULL);  dweight (cout,cin) = sum_{b,p} dy x^T   (when dweight != NULL)
-AMC_API int amc3d_pointwise_conv_backward(int b, int cin, int cout, long P, const float *x, const float *weight,
-                                          const float *dy, float *dx, float *dweight, void *workspace,
-                                          size_t workspace_bytes, void *stream_)
+static int pw_backward(int b, int cin, int cout, long P, const float *x, const float *weight, long ldw, const float *dy, float *dx,
+                       int dx_pm, float *dweight, long lddw, void *workspace, size_t workspace_bytes, hipStream_t stream)
 {
     if (b <= 0 || P <= 0) return 0;
-    if (cin <= 0 || cout <= 0 || !dy || (dx && !weight)) return bad_arg("amc3d_pointwise_conv_backward: bad argument");
-    hipStream_t stream = (hipStream_t)stream_;
+    if (cin <= 0 || cout <= 0 || !dy || (dx && (!weight || ldw < cin)) || (dweight && lddw < cin))
+        return bad_arg("amc3d_pointwise_conv_backward: bad argument");
     const bool deep = gemm_conv_pays(cin, cout) && P < (1L << 31);
     if (dx) {
         if (deep && (cout > 128 || gemm_conv_short(b, cin, P))) {
             const size_t need = gemm_conv_backward_data_workspace_bytes(b, cin, cout, P);
             float *part = (need && workspace && workspace_bytes >= need) ? (float *)workspace : nullptr;
-            if (int st = gemm_conv_backward_data(b, cin, cout, P, dy, weight, dx, part, stream)) return st;
+            if (int st = gemm_conv_backward_data(b, cin, cout, P, dy, weight, ldw, dx, dx_pm, part, stream)) return st;
         }
-        else pw_gemm(b, cin, cout, P, weight, 1, cin, nullptr, dy, dx, stream);
+        else pw_gemm(b, cin, cout, P, weight, 1, ldw, nullptr, dy, dx, dx_pm, stream);
     }
     if (dweight) {
         if (!x || !workspace || workspace_bytes < amc3d_pointwise_conv_workspace_bytes(b, cin, cout, P))
             return bad_arg("amc3d_pointwise_conv_backward: null pointer or workspace too small");
-        if (deep) return gemm_conv_backward_weight(b, cin, cout, P, x, dy, dweight, (float *)workspace, stream);
+        if (deep) return gemm_conv_backward_weight(b, cin, cout, P, x, dy, dweight, lddw, (float *)workspace, stream);
         const PwSplit s = pw_split(b, cin, cout, P);
         float *partial = (float *)workspace;
 #define AMC_PWW(A, B) launch_pw_wgrad<A, B>(s, cout, cin, P, dy, x, partial, stream)
@@ -413,10 +454,29 @@ AMC_API int amc3d_pointwise_conv_backward(int b, int cin, int cout, long P, cons
             if (s.nct == 1) AMC_PWW(1, 2); else if (s.nct == 2) AMC_PWW(2, 2); else if (s.nct == 3) AMC_PWW(3, 2); else AMC_PWW(4, 2);
         }
 #undef AMC_PWW
-        const int st = reduce_partials(cout * cin, s.groups, partial, dweight, stream);
+        const int st = reduce_partials_rows(cout, cin, lddw, s.groups, partial, dweight, stream);
         if (st) return st;
     }
     return launch_status("amc3d_pointwise_conv_backward");
+}
+
+// dx (b,cin,P) = weight^T . dy   (when dx != NULL);  dweight (cout,cin) = sum_{b,p} dy x^T   (when dweight != NULL)
+AMC_API int amc3d_pointwise_conv_backward(int b, int cin, int cout, long P, const float *x, const float *weight,
+                                          const float *dy, float *dx, float *dweight, void *workspace,
+                                          size_t workspace_bytes, void *stream)
+{
+    return pw_backward(b, cin, cout, P, x, weight, cin, dy, dx, 0, dweight, cin, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// the same with row strides ldw / lddw (floats, >= cin) for weight and dweight -- column blocks of wider matrices; the columns
+// of dweight's rows outside the block are not touched -- and, with dx_position_major != 0, dx written as (b,P,cin) rows (the
+// layout amc3d_grouped_conv_bn_backward_csr gathers from) instead of (b,cin,P).  Same sums in the same order as above.
+AMC_API int amc3d_pointwise_conv_backward_strided(int b, int cin, int cout, long P, const float *x, const float *weight, long ldw,
+                                                  const float *dy, float *dx, int dx_position_major, float *dweight, long lddw,
+                                                  void *workspace, size_t workspace_bytes, void *stream)
+{
+    return pw_backward(b, cin, cout, P, x, weight, ldw, dy, dx, dx_position_major != 0, dweight, lddw, workspace, workspace_bytes,
+                       (hipStream_t)stream);
 }
 
 // dbias (c) = sum_{b,p} dy (b,c,P): the bias gradient of a 1x1 convolution (fixed order -> deterministic)

@@ -187,9 +187,11 @@ def batchnorm_act(bn, y, relu, pool=False, residual=None):
     return x
 
 
-def conv1x1(conv, x):
+def conv1x1(conv, x, rows_grad=False):
     """conv(x); a plain 1x1 convolution on a contiguous fp32 GPU tensor runs on the MFMA kernels of
-    csrc/pwconv.hip (same parameters, same autograd contract), anything else on the stored torch module."""
+    csrc/pwconv.hip (same parameters, same autograd contract), anything else on the stored torch module.
+    `rows_grad`: the only consumer of x's gradient reads position-major rows (wants_rows_grad): the backward-data product
+    then stores (B,*spatial,Cin) and hands over the permuted view, where the route has that form."""
     if (type(conv) in (nn.Conv1d, nn.Conv2d, Conv1d, Conv2d) and x.is_cuda and x.dtype == torch.float32
             and conv.groups == 1 and conv.padding_mode == 'zeros'
             and all(k == 1 for k in conv.kernel_size) and all(v == 1 for v in conv.stride)
@@ -199,12 +201,12 @@ def conv1x1(conv, x):
             # searches and the loss stay fp32 (tensors are never stored in bf16)
             return ops.pointwise_conv(x, conv.weight, conv.bias, True)
         if _pw_pays(conv, x):
-            return ops.pointwise_conv(x, conv.weight, conv.bias)
+            return ops.pointwise_conv(x, conv.weight, conv.bias, False, rows_grad)
         if (conv.bias is None and min(conv.in_channels, conv.out_channels) >= 64 and conv.in_channels % 4 == 0
                 and torch.is_grad_enabled()):
             # deep and short (SA4, coarse FP stages): three plain library GEMMs instead of the convolution library,
             # whose weight gradient is wrapped in layout transposes (scratch/pw_bench3.py: 30-50 us per layer)
-            return ops.library_gemm_conv(x, conv.weight)
+            return ops.library_gemm_conv(x, conv.weight, rows_grad)
         # what is left (small layers with a bias: the skip convs of SA2-4): the convolution library -- this library's own
         # kernel measured 0.35 ms/step slower on these three layers
         with torch.autocast("cuda", enabled=False):
@@ -287,7 +289,7 @@ def run_convblocks(blocks, x, pool_max=False, pre=None, activated=False, residua
         m = conv_bn_block(blk)
         if m is not None:
             conv, bn, relu = m
-            y = pre if (bi == 0 and pre is not None) else conv1x1(conv, x)
+            y = pre if (bi == 0 and pre is not None) else conv1x1(conv, x, bi == 0 and activated and wants_rows_grad(x))
             x = batchnorm_act(bn, y, relu, last and pool_max, residual if last else None)
             finished = last
         else:
@@ -305,6 +307,12 @@ def run_convblocks(blocks, x, pool_max=False, pre=None, activated=False, residua
         if residual is not None:
             x = torch.relu(x + residual)
     return x
+
+
+def wants_rows_grad(x1):
+    """x1 is the output of an ops.GroupedConvBN that walks reverse edge lists in its backward (fused_first_block marks it):
+    that gather reads the gradient as position-major (B,M,K,C) rows, and transposes any other layout first"""
+    return bool(getattr(x1, '_amc3d_rows_grad', False))
 
 
 def _sa_tail_conv(blk, x1):
@@ -393,8 +401,11 @@ def fused_first_block(blocks, f, geom, feature_type):
     csr = geom.get('csr')
     if csr is not None:
         csr = (csr['start'], csr['edge'], csr.get('edge_dp'))
-    return ops.GroupedConvBN.apply(f, geom['dp'], geom['idx'], geom['mom'], conv.weight, bn.weight, bn.bias, bn.eps, True, bn,
-                                   csr, group)
+    x1 = ops.GroupedConvBN.apply(f, geom['dp'], geom['idx'], geom['mom'], conv.weight, bn.weight, bn.bias, bn.eps, True, bn,
+                                 csr, group)
+    if csr is not None and x1.requires_grad:
+        x1._amc3d_rows_grad = True  # run_convblocks: the conv that consumes x1 writes its gradient as rows
+    return x1
 
 
 def fused_first_conv(blocks, f, geom, feature_type):

@@ -76,6 +76,12 @@ def _pw_forward(lib, bf16, B, Cin, Cout, P, x, w2, bias, y, what="pointwise_conv
     """y = w2 . x (+ bias) through the fp32 or bf16-compute kernels; the fp32 short deep layers get scratch for their
     split-K partial products (amc3d_pointwise_conv_forward_ws)"""
     bptr = _ptr(bias) if bias is not None else None
+    if not bf16 and _ld(w2) != Cin:  # a column block of a wider matrix, used where it lies
+        wsf = int(lib.amc3d_pointwise_conv_forward_workspace_bytes(B, Cin, Cout, P, int(bias is not None)))
+        work = torch.empty(wsf, dtype=torch.uint8, device=x.device) if wsf else None
+        _lib.check(lib.amc3d_pointwise_conv_forward_strided(B, Cin, Cout, P, _ptr(x), _ptr(w2), _ld(w2), bptr, _ptr(y),
+                                                            _ptr(work) if wsf else None, wsf, _stream(x)), what)
+        return
     if not bf16:
         wsf = int(lib.amc3d_pointwise_conv_forward_workspace_bytes(B, Cin, Cout, P, int(bias is not None)))
         if wsf:
@@ -84,6 +90,19 @@ def _pw_forward(lib, bf16, B, Cin, Cout, P, x, w2, bias, y, what="pointwise_conv
                                                            _stream(x)), what)
             return
     _lib.check(_pw(lib, bf16)[0](B, Cin, Cout, P, _ptr(x), _ptr(w2), bptr, _ptr(y), _stream(x)), what)
+
+
+def _ld(w2):
+    """row stride of a (rows, cols) weight view with unit column stride (one row: no stride to speak of)"""
+    return w2.stride(0) if w2.shape[0] > 1 else w2.shape[1]
+
+
+def _weight_rows(w2, bf16):
+    """w2 (Cout,Cin) as the kernels take it: rows at a stride >= Cin with unit column stride (a column block of a wider
+    matrix stays a view; the bf16-compute kernels take contiguous weights only)"""
+    if not bf16 and w2.dim() == 2 and w2.stride(1) == 1 and _ld(w2) >= w2.shape[1]:
+        return w2
+    return w2.contiguous()
 
 
 def _pw(lib, bf16):
@@ -1319,6 +1338,37 @@ def _sync(group, buf):
     graphs.collective(lambda: dist.all_reduce(buf, group=group))
 
 
+def _dp_f_blocks(w2, bf16):
+    """(W_dp, its row stride, W_f) of a neighbourhood layer's weight w2 = [W_dp | W_f] (C, 3 + Cin): the two column blocks
+    where they lie (the kernels take a row stride); contiguous copies for the bf16-compute conv, which takes no stride"""
+    if bf16:
+        w_dp, w_f = _split_columns(w2, 3)
+        return w_dp, 3, w_f
+    return w2, w2.shape[1], w2[:, 3:]
+
+
+def _dp_f_grad(C, Cin, dev, bf16):
+    """(dW or None, dW_dp, its row stride, dW_f, its row stride): the two gradient blocks inside one (C, 3 + Cin) matrix -- the
+    layer kernel writes columns 0-2, the conv's backward columns 3 onwards -- or apart (bf16: joined afterwards)"""
+    if bf16:
+        return (None, torch.empty(C, 3, dtype=torch.float32, device=dev), 3,
+                torch.empty(C, Cin, dtype=torch.float32, device=dev), Cin)
+    dw = torch.empty(C, Cin + 3, dtype=torch.float32, device=dev)
+    return dw, dw, Cin + 3, dw[:, 3:], Cin + 3
+
+
+def _pw_backward_blocks(lib, bf16, B, Cin, C, N, f, w_f, dg_cm, df, dw_f, lddw, work2, wb2):
+    """backward of the conv on the source points: the weight a column block of the layer's weight, its gradient one of dW"""
+    if bf16:
+        _lib.check(lib.amc3d_pointwise_conv_backward_bf16(B, Cin, C, N, _ptr(f), _ptr(w_f), _ptr(dg_cm),
+                                                          _ptr(df) if df is not None else None, _ptr(dw_f), _ptr(work2), wb2,
+                                                          _stream(f)), "pointwise_conv_backward")
+        return
+    _lib.check(lib.amc3d_pointwise_conv_backward_strided(B, Cin, C, N, _ptr(f), _ptr(w_f), _ld(w_f), _ptr(dg_cm),
+                                                         _ptr(df) if df is not None else None, 0, _ptr(dw_f), lddw,
+                                                         _ptr(work2), wb2, _stream(f)), "pointwise_conv_backward")
+
+
 class LocalAggregationFused(Function):
     """pooled (B,C,M) = max_k [relu](bn(conv1x1([dp ; f[idx]]))) -- grouping_operation + cat + Conv2d + BatchNorm2d (batch
     statistics) [+ ReLU] + max of LocalAggregation / single-layer SetAbstraction (pointnext_AA.py:57-63, 139-170) -- with
@@ -1339,8 +1389,9 @@ class LocalAggregationFused(Function):
         assert weight.numel() == C * (Cin + 3)
         dev = f.device
         lib = _lib.load()
-        w2 = weight.reshape(C, Cin + 3)
-        w_dp, w_f = _split_columns(w2, 3)
+        ctx.bf16 = mixed_precision() and min(Cin, C) >= 64 and B * N >= 4096  # the conv on the source points on the bf16 MFMA
+        w2 = weight.detach().reshape(C, Cin + 3).contiguous()
+        w_dp, ldw, w_f = _dp_f_blocks(w2, ctx.bf16)
         g_cm = torch.empty(B, C, N, dtype=torch.float32, device=dev)
         g_pm = torch.empty(B, N, C, dtype=torch.float32, device=dev)
         pooled = torch.empty(B, C, M, dtype=torch.float32, device=dev)
@@ -1353,11 +1404,10 @@ class LocalAggregationFused(Function):
         wb = int(lib.amc3d_local_aggregation_workspace_bytes(B, C, N, M))
         work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
         mom, rm, rv, nbt = _bn_running_args(bn)
-        ctx.bf16 = mixed_precision() and min(Cin, C) >= 64 and B * N >= 4096  # the conv on the source points on the bf16 MFMA
 
         def call(phase):
-            _lib.check(lib.amc3d_local_aggregation_forward(
-                B, C, N, M, K, 1, int(bool(relu)), float(eps), mom, _ptr(g_cm), _ptr(idx), _ptr(dp), _ptr(w_dp),
+            _lib.check(lib.amc3d_local_aggregation_forward_strided(
+                B, C, N, M, K, 1, int(bool(relu)), float(eps), mom, _ptr(g_cm), _ptr(idx), _ptr(dp), _ptr(w_dp), ldw,
                 _ptr(moments), _ptr(gamma), _ptr(beta), _ptr(g_pm), _ptr(pooled), _ptr(arg), _ptr(ystar), _ptr(mean),
                 _ptr(invstd), _ptr(var_u), _ptr(gd), rm, rv, nbt, phase, _ptr(sums), _ptr(work), wb, _stream(f)),
                 "local_aggregation_forward")
@@ -1377,6 +1427,7 @@ class LocalAggregationFused(Function):
         if bn is not None and bn.track_running_stats and bn.running_mean is not None and bn.momentum is None:
             bn_update_running(bn, mean, var_u)  # cumulative average: its own launch
         ctx.save_for_backward(f, w_f, w_dp, g_pm, idx, dp, moments, gamma, beta, mean, invstd, gd, ystar, arg, sums)
+        ctx.ldw = ldw
         ctx.relu, ctx.wshape, ctx.group = bool(relu), tuple(weight.shape), group
         if _pool_log is not None:
             _pool_log[_next_pool_seq()] = arg
@@ -1392,7 +1443,7 @@ class LocalAggregationFused(Function):
         lib = _lib.load()
         dpooled = dpooled.contiguous()
         dg_cm = torch.empty(B, C, N, dtype=torch.float32, device=dev)
-        dw_dp = torch.empty(C, 3, dtype=torch.float32, device=dev)
+        dw, dw_dp, lddw, dw_f, lddw_f = _dp_f_grad(C, Cin, dev, ctx.bf16)
         dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
         dsums = torch.empty(2 * C, dtype=torch.float64, device=dev)
         count = ctypes.c_void_p(sums.data_ptr() + 16 * C)
@@ -1400,16 +1451,15 @@ class LocalAggregationFused(Function):
         work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
         need_f = ctx.needs_input_grad[0]
         df = torch.empty_like(f) if need_f else None
-        dw_f = torch.empty(C, Cin, dtype=torch.float32, device=dev)
-        _, pw_wbytes, pw_bwd = _pw(lib, ctx.bf16)
+        _, pw_wbytes, _ = _pw(lib, ctx.bf16)
         wb2 = int(pw_wbytes(B, Cin, C, N))
         work2 = torch.empty(max(wb2, 4), dtype=torch.uint8, device=dev)
 
         def call(phase):
-            _lib.check(lib.amc3d_local_aggregation_backward(
+            _lib.check(lib.amc3d_local_aggregation_backward_strided(
                 B, C, N, M, K, int(ctx.relu), _ptr(dpooled), _ptr(ystar), _ptr(arg), _ptr(g_pm), _ptr(idx), _ptr(dp),
-                _ptr(w_dp), _ptr(moments), _ptr(gd), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(dg_cm),
-                _ptr(dw_dp), _ptr(dgamma), _ptr(dbeta), phase, _ptr(dsums), count, _ptr(work), wb, _stream(f)),
+                _ptr(w_dp), ctx.ldw, _ptr(moments), _ptr(gd), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(dg_cm),
+                _ptr(dw_dp), lddw, _ptr(dgamma), _ptr(dbeta), phase, _ptr(dsums), count, _ptr(work), wb, _stream(f)),
                 "local_aggregation_backward")
 
         with torch.cuda.device(dev):
@@ -1422,9 +1472,8 @@ class LocalAggregationFused(Function):
                     call(2)
             with timing.span("pointwise_conv_backward", 4 * B * N * (Cin + C + Cin * int(need_f)),
                              2.0 * B * N * Cin * C * (1 + int(need_f)), moved=4 * B * N * (Cin + C) * (1 + int(need_f))):
-                _lib.check(pw_bwd(B, Cin, C, N, _ptr(f), _ptr(w_f), _ptr(dg_cm), _ptr(df) if need_f else None, _ptr(dw_f),
-                                  _ptr(work2), wb2, _stream(f)), "pointwise_conv_backward")
-        dw = _join_columns(dw_dp, dw_f).view(ctx.wshape)
+                _pw_backward_blocks(lib, ctx.bf16, B, Cin, C, N, f, w_f, dg_cm, df, dw_f, lddw_f, work2, wb2)
+        dw = (_join_columns(dw_dp, dw_f) if dw is None else dw).view(ctx.wshape)
         return df, None, None, None, dw, dgamma, dbeta, None, None, None, None
 
 
@@ -1448,8 +1497,9 @@ class GroupedConvBN(Function):
         dev = f.device
         lib = _lib.load()
         ctx.csr = csr  # (rev_start, rev_edge[, group_csr_dp's stream]) of ops.group_csr, or None: backward then scatters with float atomics
-        w2 = weight.reshape(C, Cin + 3)
-        w_dp, w_f = _split_columns(w2, 3)
+        ctx.bf16 = mixed_precision() and min(Cin, C) >= 64 and B * N >= 4096
+        w2 = weight.detach().reshape(C, Cin + 3).contiguous()
+        w_dp, ldw, w_f = _dp_f_blocks(w2, ctx.bf16)
         g_cm = torch.empty(B, C, N, dtype=torch.float32, device=dev)
         g_pm = torch.empty(B, N, C, dtype=torch.float32, device=dev)
         x1 = torch.empty(B, C, M, K, dtype=torch.float32, device=dev)
@@ -1460,11 +1510,10 @@ class GroupedConvBN(Function):
         wb = int(lib.amc3d_local_aggregation_workspace_bytes(B, C, N, M))
         work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
         mom, rm, rv, nbt = _bn_running_args(bn)
-        ctx.bf16 = mixed_precision() and min(Cin, C) >= 64 and B * N >= 4096
 
         def call(phase):
-            _lib.check(lib.amc3d_grouped_conv_bn_forward(
-                B, C, N, M, K, 1, int(bool(relu)), float(eps), mom, _ptr(g_cm), _ptr(idx), _ptr(dp), _ptr(w_dp),
+            _lib.check(lib.amc3d_grouped_conv_bn_forward_strided(
+                B, C, N, M, K, 1, int(bool(relu)), float(eps), mom, _ptr(g_cm), _ptr(idx), _ptr(dp), _ptr(w_dp), ldw,
                 _ptr(moments), _ptr(gamma), _ptr(beta), _ptr(g_pm), _ptr(x1), _ptr(mean), _ptr(invstd), _ptr(var_u),
                 _ptr(gd), rm, rv, nbt, phase, _ptr(sums), _ptr(work), wb, _stream(f)), "grouped_conv_bn_forward")
 
@@ -1481,6 +1530,7 @@ class GroupedConvBN(Function):
         if bn is not None and bn.track_running_stats and bn.running_mean is not None and bn.momentum is None:
             bn_update_running(bn, mean, var_u)
         ctx.save_for_backward(f, w_f, w_dp, g_pm, idx, dp, moments, gamma, beta, mean, invstd, gd, sums)
+        ctx.ldw = ldw
         ctx.relu, ctx.wshape, ctx.group = bool(relu), tuple(weight.shape), group
         return x1
 
@@ -1498,7 +1548,7 @@ class GroupedConvBN(Function):
         if not dx1_pm:
             dx1 = dx1.contiguous()
         dg_cm = torch.empty(B, C, N, dtype=torch.float32, device=dev)
-        dw_dp = torch.empty(C, 3, dtype=torch.float32, device=dev)
+        dw, dw_dp, lddw, dw_f, lddw_f = _dp_f_grad(C, Cin, dev, ctx.bf16)
         dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
         dsums = torch.empty(2 * C, dtype=torch.float64, device=dev)
         count = ctypes.c_void_p(sums.data_ptr() + 16 * C)
@@ -1508,23 +1558,22 @@ class GroupedConvBN(Function):
         work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
         need_f = ctx.needs_input_grad[0]
         df = torch.empty_like(f) if need_f else None
-        dw_f = torch.empty(C, Cin, dtype=torch.float32, device=dev)
-        _, pw_wbytes, pw_bwd = _pw(lib, ctx.bf16)
+        _, pw_wbytes, _ = _pw(lib, ctx.bf16)
         wb2 = int(pw_wbytes(B, Cin, C, N))
         work2 = torch.empty(max(wb2, 4), dtype=torch.uint8, device=dev)
 
         def call(phase):
             if csr is not None:
-                _lib.check(lib.amc3d_grouped_conv_bn_backward_csr(
+                _lib.check(lib.amc3d_grouped_conv_bn_backward_csr_strided(
                     B, C, N, M, K, int(ctx.relu), _ptr(dx1), int(dx1_pm), _ptr(g_pm), _ptr(csr[0]), _ptr(csr[1]),
-                    _ptr(csr[2]) if len(csr) > 2 and csr[2] is not None else None, _ptr(dp), _ptr(w_dp),
-                    _ptr(moments), _ptr(gd), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(dg_cm), _ptr(dw_dp),
+                    _ptr(csr[2]) if len(csr) > 2 and csr[2] is not None else None, _ptr(dp), _ptr(w_dp), ctx.ldw,
+                    _ptr(moments), _ptr(gd), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(dg_cm), _ptr(dw_dp), lddw,
                     _ptr(dgamma), _ptr(dbeta), phase, _ptr(dsums), count, _ptr(work), wb, _stream(f)),
                     "grouped_conv_bn_backward_csr")
             else:
-                _lib.check(lib.amc3d_grouped_conv_bn_backward(
-                    B, C, N, M, K, int(ctx.relu), _ptr(dx1), _ptr(g_pm), _ptr(idx), _ptr(dp), _ptr(w_dp), _ptr(moments),
-                    _ptr(gd), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(dg_cm), _ptr(dw_dp), _ptr(dgamma),
+                _lib.check(lib.amc3d_grouped_conv_bn_backward_strided(
+                    B, C, N, M, K, int(ctx.relu), _ptr(dx1), _ptr(g_pm), _ptr(idx), _ptr(dp), _ptr(w_dp), ctx.ldw, _ptr(moments),
+                    _ptr(gd), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(dg_cm), _ptr(dw_dp), lddw, _ptr(dgamma),
                     _ptr(dbeta), phase, _ptr(dsums), count, _ptr(work), wb, _stream(f)), "grouped_conv_bn_backward")
 
         with torch.cuda.device(dev):
@@ -1537,9 +1586,8 @@ class GroupedConvBN(Function):
                     call(2)
             with timing.span("pointwise_conv_backward", 4 * B * N * (Cin + C + Cin * int(need_f)),
                              2.0 * B * N * Cin * C * (1 + int(need_f)), moved=4 * B * N * (Cin + C) * (1 + int(need_f))):
-                _lib.check(pw_bwd(B, Cin, C, N, _ptr(f), _ptr(w_f), _ptr(dg_cm), _ptr(df) if need_f else None, _ptr(dw_f),
-                                  _ptr(work2), wb2, _stream(f)), "pointwise_conv_backward")
-        dw = _join_columns(dw_dp, dw_f).view(ctx.wshape)
+                _pw_backward_blocks(lib, ctx.bf16, B, Cin, C, N, f, w_f, dg_cm, df, dw_f, lddw_f, work2, wb2)
+        dw = (_join_columns(dw_dp, dw_f) if dw is None else dw).view(ctx.wshape)
         return df, None, None, None, dw, dgamma, dbeta, None, None, None, None, None
 
 
@@ -1552,16 +1600,16 @@ def grouped_conv_bn_eval(f, dp, idx, weight, bn, relu):
     C = weight.shape[0]
     dev = f.device
     lib = _lib.load()
-    w2 = weight.reshape(C, Cin + 3)
-    w_dp, w_f = _split_columns(w2, 3)
+    w2 = weight.detach().reshape(C, Cin + 3).contiguous()
+    w_dp, ldw, w_f = _dp_f_blocks(w2, False)
     g_cm = torch.empty(B, C, N, dtype=torch.float32, device=dev)
     g_pm = torch.empty(B, N, C, dtype=torch.float32, device=dev)
     x1 = torch.empty(B, C, M, K, dtype=torch.float32, device=dev)
     invstd = torch.rsqrt(bn.running_var + bn.eps)
     with torch.cuda.device(dev):
         _pw_forward(lib, False, B, Cin, C, N, f, w_f, None, g_cm)
-        _lib.check(lib.amc3d_grouped_conv_bn_forward(
-            B, C, N, M, K, 0, int(bool(relu)), float(bn.eps), 0.0, _ptr(g_cm), _ptr(idx), _ptr(dp), _ptr(w_dp), None,
+        _lib.check(lib.amc3d_grouped_conv_bn_forward_strided(
+            B, C, N, M, K, 0, int(bool(relu)), float(bn.eps), 0.0, _ptr(g_cm), _ptr(idx), _ptr(dp), _ptr(w_dp), ldw, None,
             _ptr(bn.weight), _ptr(bn.bias), _ptr(g_pm), _ptr(x1), _ptr(bn.running_mean), _ptr(invstd), None, None, None,
             None, None, 0, None, None, 0, _stream(f)), "grouped_conv_bn_forward")
     return x1
@@ -1580,8 +1628,8 @@ def local_aggregation_eval(f, dp, idx, weight, bn, relu):
     C = weight.shape[0]
     dev = f.device
     lib = _lib.load()
-    w2 = weight.reshape(C, Cin + 3)
-    w_dp, w_f = _split_columns(w2, 3)
+    w2 = weight.detach().reshape(C, Cin + 3).contiguous()
+    w_dp, ldw, w_f = _dp_f_blocks(w2, False)
     g_cm = torch.empty(B, C, N, dtype=torch.float32, device=dev)
     g_pm = torch.empty(B, N, C, dtype=torch.float32, device=dev)
     pooled = torch.empty(B, C, M, dtype=torch.float32, device=dev)
@@ -1590,8 +1638,8 @@ def local_aggregation_eval(f, dp, idx, weight, bn, relu):
     invstd = torch.rsqrt(bn.running_var + bn.eps)
     with torch.cuda.device(dev):
         _pw_forward(lib, False, B, Cin, C, N, f, w_f, None, g_cm)
-        _lib.check(lib.amc3d_local_aggregation_forward(
-            B, C, N, M, K, 0, int(bool(relu)), float(bn.eps), 0.0, _ptr(g_cm), _ptr(idx), _ptr(dp), _ptr(w_dp), None,
+        _lib.check(lib.amc3d_local_aggregation_forward_strided(
+            B, C, N, M, K, 0, int(bool(relu)), float(bn.eps), 0.0, _ptr(g_cm), _ptr(idx), _ptr(dp), _ptr(w_dp), ldw, None,
             _ptr(bn.weight), _ptr(bn.bias), _ptr(g_pm), _ptr(pooled), _ptr(arg), _ptr(ystar), _ptr(bn.running_mean),
             _ptr(invstd), None, None, None, None, None, 0, None, None, 0, _stream(f)), "local_aggregation_forward")
     return pooled
@@ -1602,7 +1650,7 @@ class PointwiseConv(Function):
     fp32 MFMA kernels of csrc/pwconv.hip.  x (B,Cin,*spatial) fp32, weight (Cout,Cin,1[,1]), bias (Cout) or None."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, bf16=False):
+    def forward(ctx, x, weight, bias, bf16=False, dx_position_major=False):
         _need_gpu(x, weight)
         _need_dtype(torch.float32, x=x, weight=weight, bias=bias)
         x = x.contiguous()
@@ -1610,7 +1658,7 @@ class PointwiseConv(Function):
         P = x[0, 0].numel()
         Cout = weight.shape[0]
         assert weight.numel() == Cout * Cin, "pointwise_conv needs a 1x1 kernel"
-        w2 = weight.reshape(Cout, Cin).contiguous()
+        w2 = _weight_rows(weight.reshape(Cout, Cin), bf16)
         y = torch.empty((B, Cout) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
         lib = _lib.load()
         with torch.cuda.device(x.device), timing.span("pointwise_conv_forward", 4 * B * P * (Cin + Cout),
@@ -1620,6 +1668,9 @@ class PointwiseConv(Function):
         ctx.wshape = tuple(weight.shape)
         ctx.has_bias = bias is not None
         ctx.bf16 = bool(bf16)
+        # dx as position-major rows (B,*spatial,Cin), returned as the permuted (B,Cin,*spatial) view: what the reverse-list
+        # gather of GroupedConvBN.backward reads directly (fp32 kernels only)
+        ctx.dx_pm = bool(dx_position_major) and not ctx.bf16 and Cin > 1
         return y
 
     @staticmethod
@@ -1632,6 +1683,8 @@ class PointwiseConv(Function):
         dev = dy.device
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         dx = torch.empty_like(x) if need_x else None
+        if need_x and ctx.dx_pm:
+            dx = torch.empty((B,) + tuple(x.shape[2:]) + (Cin,), dtype=torch.float32, device=dev)
         dw = torch.empty(Cout, Cin, dtype=torch.float32, device=dev) if need_w else None
         _, wbytes, bwd = _pw(_lib.load(), ctx.bf16)
         wb = int(wbytes(B, Cin, Cout, P))  # weight-gradient partials and / or the split-K partials of dx
@@ -1640,18 +1693,25 @@ class PointwiseConv(Function):
         with torch.cuda.device(dev), timing.span("pointwise_conv_backward",
                                                  4 * B * P * (Cout + Cin * int(need_x) + Cin * int(need_w)), flops,
                                                  moved=4 * B * P * ((Cin + Cout) * int(need_x) + (Cin + Cout) * int(need_w))):
-            _lib.check(bwd(B, Cin, Cout, P, _ptr(x), _ptr(w2), _ptr(dy), _ptr(dx) if need_x else None,
-                           _ptr(dw) if need_w else None, _ptr(work), wb, _stream(dy)), "pointwise_conv_backward")
+            if ctx.dx_pm or _ld(w2) != Cin:
+                _lib.check(_lib.load().amc3d_pointwise_conv_backward_strided(
+                    B, Cin, Cout, P, _ptr(x), _ptr(w2), _ld(w2), _ptr(dy), _ptr(dx) if need_x else None, int(ctx.dx_pm),
+                    _ptr(dw) if need_w else None, Cin, _ptr(work), wb, _stream(dy)), "pointwise_conv_backward")
+            else:
+                _lib.check(bwd(B, Cin, Cout, P, _ptr(x), _ptr(w2), _ptr(dy), _ptr(dx) if need_x else None,
+                               _ptr(dw) if need_w else None, _ptr(work), wb, _stream(dy)), "pointwise_conv_backward")
+        if need_x and ctx.dx_pm:
+            dx = dx.permute(0, dx.dim() - 1, *range(1, dx.dim() - 1))
         db = None
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = torch.empty(Cout, dtype=torch.float32, device=dev)
             with torch.cuda.device(dev):
                 _lib.check(_lib.load().amc3d_bias_grad(B, Cout, P, _ptr(dy), _ptr(db), _stream(dy)), "bias_grad")
-        return dx, (dw.view(ctx.wshape) if need_w else None), db, None
+        return dx, (dw.view(ctx.wshape) if need_w else None), db, None, None
 
 
-def pointwise_conv(x, weight, bias=None, bf16=False):
-    return PointwiseConv.apply(x, weight, bias, bf16)
+def pointwise_conv(x, weight, bias=None, bf16=False, dx_position_major=False):
+    return PointwiseConv.apply(x, weight, bias, bf16, dx_position_major)
 
 
 def _split_columns(w2, c1):
@@ -1676,7 +1736,7 @@ def _join_columns(a, b):
 
 
 class SplitWeight(Function):
-    """(w[:, :c1], w[:, c1:]) of a 1x1-conv weight (Cout, C1+C2, 1) as two contiguous (Cout, C) matrices -- the two halves of a
+    """(w[:, :c1], w[:, c1:]) of a 1x1-conv weight (Cout, C1+C2, 1) as two (Cout, C) column views -- the two halves of a
     FeaturePropogation conv applied to the skip features and to the coarse features separately.  As torch slices the
     backward is zeros + copy per slice, an add, and zeros + copy for the select (7 launches per decoder level); here it is
     one concatenation."""
@@ -1685,8 +1745,9 @@ class SplitWeight(Function):
     def forward(ctx, weight, c1):
         w = weight.reshape(weight.shape[0], -1)
         ctx.wshape = tuple(weight.shape)
-        if w.is_cuda and w.dtype == torch.float32:
-            return _split_columns(w, c1)
+        if w.is_cuda and w.dtype == torch.float32 and w.stride(1) == 1:
+            # the two column blocks where they lie: the conv kernels take a row stride, the library GEMMs a leading dimension
+            return w[:, :c1], w[:, c1:]
         return w[:, :c1].contiguous(), w[:, c1:].contiguous()
 
     @staticmethod
@@ -1861,11 +1922,12 @@ class LibraryGemmConv(Function):
     x (B,Cin,*spatial) fp32 contiguous, weight (Cout,Cin,1[,1]), no bias."""
 
     @staticmethod
-    def forward(ctx, x, weight):
+    def forward(ctx, x, weight, dx_position_major=False):
         x = x.contiguous()
         B, Cin = x.shape[0], x.shape[1]
         Cout = weight.shape[0]
         w2 = weight.reshape(Cout, Cin)
+        ctx.dx_pm = bool(dx_position_major)
         timing.note("library_gemm_conv")
         # under bf16 autocast (use_amp, main_AA.py:389): bf16 operands for the three library GEMMs, fp32 accumulation inside the
         # library, fp32 results (tests/test_gpu_bf16.py) -- cfg 5 (XL + ++, 1 x 120000): 16.8 ms per step, 17.1 when the
@@ -1898,16 +1960,22 @@ class LibraryGemmConv(Function):
                 # each cloud's partial stays fp32 up to the fp32 sum over the batch
                 dw = (torch.bmm(dy16, x.transpose(1, 2), out_dtype=torch.float32).sum(0).view(ctx.wshape)
                       if ctx.needs_input_grad[1] else None)
-            return dx, dw
+            return dx, dw, None
         with torch.autocast("cuda", enabled=False):
-            dx = (torch.bmm(w2.t().unsqueeze(0).expand(B, Cin, w2.shape[0]), dy3).view(x.shape)
-                  if ctx.needs_input_grad[0] else None)
+            dx = None
+            if ctx.needs_input_grad[0] and ctx.dx_pm:
+                # dy^T . W = (B,P,Cin) position-major rows, handed over as the permuted (B,Cin,*spatial) view
+                rows = torch.bmm(dy3.transpose(1, 2), w2.unsqueeze(0).expand(B, w2.shape[0], Cin))
+                rows = rows.view((B,) + tuple(x.shape[2:]) + (Cin,))
+                dx = rows.permute(0, rows.dim() - 1, *range(1, rows.dim() - 1))
+            elif ctx.needs_input_grad[0]:
+                dx = torch.bmm(w2.t().unsqueeze(0).expand(B, Cin, w2.shape[0]), dy3).view(x.shape)
             dw = _library_wgrad(dy3, x.view(B, Cin, -1)).view(ctx.wshape) if ctx.needs_input_grad[1] else None
-        return dx, dw
+        return dx, dw, None
 
 
-def library_gemm_conv(x, weight):
-    return LibraryGemmConv.apply(x, weight)
+def library_gemm_conv(x, weight, dx_position_major=False):
+    return LibraryGemmConv.apply(x, weight, dx_position_major)
 
 
 def confusion_update(cm, invalid, logits, target, ignore_index=None):

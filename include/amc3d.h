@@ -353,6 +353,18 @@ size_t amc3d_pointwise_conv_workspace_bytes(int b, int cin, int cout, long P);
 int amc3d_pointwise_conv_backward(int b, int cin, int cout, long P, const float *x, const float *weight,
                                   const float *dy, float *dx, float *dweight, void *workspace,
                                   size_t workspace_bytes, void *stream);
+/* The same two calls with a row stride (in floats, >= cin) for weight and for dweight, so that a column block of a wider
+ * matrix is an operand where it lies: weight = W + c1 with ldw = c1 + c2 is the right block of W (rows, c1 + c2).  dweight's
+ * columns outside the block are left untouched.  A block that does not start on a 16-byte boundary (or whose stride is no
+ * multiple of 4) takes 4-byte loads for the weight operand only; sums and their order are those of the calls above.
+ * workspace: amc3d_pointwise_conv_forward_workspace_bytes() / amc3d_pointwise_conv_workspace_bytes() bytes.
+ * dx_position_major != 0: dx is written as (b,P,cin) rows instead of (b,cin,P) -- the same values, four consecutive channels
+ * of a position per 16-byte store -- the layout amc3d_grouped_conv_bn_backward_csr reads with dx1_position_major = 1. */
+int amc3d_pointwise_conv_forward_strided(int b, int cin, int cout, long P, const float *x, const float *weight, long ldw,
+                                         const float *bias, float *y, void *workspace, size_t workspace_bytes, void *stream);
+int amc3d_pointwise_conv_backward_strided(int b, int cin, int cout, long P, const float *x, const float *weight, long ldw,
+                                          const float *dy, float *dx, int dx_position_major, float *dweight, long lddw,
+                                          void *workspace, size_t workspace_bytes, void *stream);
 
 /* a weight matrix cut into two column blocks / two gradient blocks joined (the [W_dp | W_f] weight of a neighbourhood layer,
  * the [W_skip | W_up] weight of a FeaturePropagation conv): w (rows, c1 + c2) <-> a (rows, c1), b (rows, c2), one launch */
@@ -507,6 +519,52 @@ int amc3d_grouped_conv_bn_backward_csr(int b, int cout, int n, int npoints, int 
                                        const float *invstd, const float *gamma, const float *beta, float *dg_cm, float *dw_dp,
                                        float *dgamma, float *dbeta, int phase, double *dsums, const double *count,
                                        void *workspace, size_t workspace_bytes, void *stream);
+/* The five layer calls above with w_dp (and dw_dp) addressed at a row stride in floats (>= 3): w_dp = W, ldw = cin + 3 reads
+ * the dp columns inside the layer's own (cout, cin + 3) weight, and dw_dp = dW, lddw = cin + 3 writes columns 0-2 of its gradient
+ * (amc3d_pointwise_conv_backward_strided writes columns 3 onwards): no split of the weight, no join of the gradient. */
+int amc3d_local_aggregation_forward_strided(int b, int cout, int n, int npoints, int nsample, int training,
+                                            int relu, float eps, float momentum, const float *g_cm,
+                                            const int *idx, const float *dp, const float *w_dp, long ldw,
+                                            const void *moments, const float *gamma, const float *beta,
+                                            float *g_pm, float *pooled, unsigned char *arg, float *ystar,
+                                            float *mean, float *invstd, float *var_unbiased, double *gd,
+                                            float *running_mean, float *running_var,
+                                            long long *num_batches_tracked, int phase, double *sums,
+                                            void *workspace, size_t workspace_bytes, void *stream);
+int amc3d_local_aggregation_backward_strided(int b, int cout, int n, int npoints, int nsample, int relu,
+                                             const float *dpooled, const float *ystar, const unsigned char *arg,
+                                             const float *g_pm, const int *idx, const float *dp,
+                                             const float *w_dp, long ldw, const void *moments, const double *gd,
+                                             const float *mean, const float *invstd, const float *gamma,
+                                             const float *beta, float *dg_cm, float *dw_dp, long lddw,
+                                             float *dgamma, float *dbeta, int phase, double *dsums,
+                                             const double *count_dev, void *workspace, size_t workspace_bytes,
+                                             void *stream);
+int amc3d_grouped_conv_bn_forward_strided(int b, int cout, int n, int npoints, int nsample, int training,
+                                          int relu, float eps, float momentum, const float *g_cm, const int *idx,
+                                          const float *dp, const float *w_dp, long ldw, const void *moments,
+                                          const float *gamma, const float *beta, float *g_pm, float *x1,
+                                          float *mean, float *invstd, float *var_unbiased, double *gd,
+                                          float *running_mean, float *running_var, long long *num_batches_tracked,
+                                          int phase, double *sums, void *workspace, size_t workspace_bytes,
+                                          void *stream);
+int amc3d_grouped_conv_bn_backward_strided(int b, int cout, int n, int npoints, int nsample, int relu,
+                                           const float *dx1, const float *g_pm, const int *idx, const float *dp,
+                                           const float *w_dp, long ldw, const void *moments, const double *gd,
+                                           const float *mean, const float *invstd, const float *gamma,
+                                           const float *beta, float *dg_cm, float *dw_dp, long lddw,
+                                           float *dgamma, float *dbeta, int phase, double *dsums,
+                                           const double *count_dev, void *workspace, size_t workspace_bytes,
+                                           void *stream);
+int amc3d_grouped_conv_bn_backward_csr_strided(int b, int cout, int n, int npoints, int nsample, int relu,
+                                               const float *dx1, int dx1_position_major, const float *g_pm,
+                                               const int *rev_start, const int *rev_edge, const float *rev_dp,
+                                               const float *dp, const float *w_dp, long ldw, const void *moments,
+                                               const double *gd, const float *mean, const float *invstd,
+                                               const float *gamma, const float *beta, float *dg_cm, float *dw_dp,
+                                               long lddw, float *dgamma, float *dbeta, int phase, double *dsums,
+                                               const double *count_dev, void *workspace, size_t workspace_bytes,
+                                               void *stream);
 
 /* ---- tail of a two-layer SetAbstraction block, recomputed instead of materialised -----------------------------
  * BN1 -> ReLU -> Conv2d 1x1 (C1 -> C2) -> BN2 [-> ReLU] -> max over the K = 32 neighbours
