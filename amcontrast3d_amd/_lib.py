@@ -114,6 +114,12 @@ SIGNATURES = {
     "amc3d_s3dis_crop_workspace_bytes": (_sz, [_i]),
     "amc3d_s3dis_select_crop": (_i, [_i, _i, _i, _i] + [_vp] * 13 + [_vp, _sz, _vp]),
     "amc3d_s3dis_crop_tail": (_i, [_i, _i, _i, _i] + [_vp] * 12 + [_vp]),
+    "amc3d_scannet_voxelize_workspace_bytes": (_sz, [_i, _ll]),
+    "amc3d_scannet_voxelize_rooms": (_i, [_i, _ll, _vp, _vp, ctypes.c_double] + [_vp] * 8 + [_vp, _sz, _vp]),
+    "amc3d_scannet_crop_workspace_bytes": (_sz, [_i]),
+    "amc3d_scannet_select_crop": (_i, [_i, _i, _i, _i] + [_vp] * 13 + [_vp, _sz, _vp]),
+    "amc3d_scannet_crop_tail_workspace_bytes": (_sz, [_i]),
+    "amc3d_scannet_crop_tail_rooms": (_i, [_i, _i, _i, _i] + [_vp] * 12 + [_vp, _sz, _vp]),
     "amc3d_room_parts": (_i, [_i, _i, _i] + [_vp] * 6 + [_vp]),
     "amc3d_part_batch_workspace_bytes": (_sz, [_i]),
     "amc3d_part_batch": (_i, [_i] * 6 + [_vp] * 12 + [_sz, _vp]),

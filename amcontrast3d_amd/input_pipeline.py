@@ -13,8 +13,10 @@ draws come from a torch.Generator on the device, or are passed in (`rnd`, `init_
 numbers the reference drew.  numpy's argsort is not stable, so WHICH point of a voxel the reference's mode-0 pick lands on
 (and the order of equidistant points in the crop) is unspecified by the reference itself; the stable order is used here.
 
-Batch-level calls: scannet_train_batch (ScanNet's training item), s3dis_train_batch / S3DISTrainFeed (S3DIS's training item for
-a whole batch of raw rooms on csrc/s3dis_input.hip, one read-back per batch), and the validation / whole-room testing items.
+Batch-level calls: scannet_train_batch (ScanNet's training item, room by room after the transform), scannet_train_rooms /
+ScanNetTrainFeed (the same item for the whole batch at once on csrc/scannet_rooms.hip, one read-back per batch),
+s3dis_train_batch / S3DISTrainFeed (S3DIS's training item for a whole batch of raw rooms on csrc/s3dis_input.hip, one read-back
+per batch), and the validation / whole-room testing items.
 """
 import ctypes
 
@@ -780,3 +782,247 @@ class S3DISTrainFeed:
             pick = [j % len(self.sizes) for j in ids[i * self.batch_size:(i + 1) * self.batch_size]]
             yield _s3dis_batch(self.raw, [self.starts[j] for j in pick], [self.sizes[j] for j in pick], self.transform,
                                self.voxel_size, self.voxel_max, False, True, self.generator, None, 2)
+
+
+_SCANNET_TRANSFORM_KEYS = ("scale", "mirror_u", "contrast_u", "blend", "drop_u")
+
+
+def _scannet_rooms(rooms, who):
+    """the rooms of a ScanNet batch or feed, checked -> (coord (T,3), feat (T,3), label (T) int64, sizes)"""
+    rooms = list(rooms)
+    if len(rooms) == 0:
+        raise ValueError(f"{who}: no rooms")
+    for c, f, l in rooms:
+        _need_gpu(c, f, l)
+        _need_dtype(torch.float32, coord=c, feat=f)
+        if (c.dim() != 2 or c.shape[1] != 3 or f.shape != c.shape or l.numel() != c.shape[0] or c.shape[0] == 0
+                or c.device != rooms[0][0].device):
+            raise ValueError(f"{who}: every room needs coord (n,3), feat (n,3), label (n,) with n > 0, on one GPU")
+    one = len(rooms) == 1
+    coord = rooms[0][0].contiguous() if one else torch.cat([c for c, _, _ in rooms])
+    feat = rooms[0][1].contiguous() if one else torch.cat([f for _, f, _ in rooms])
+    label = torch.cat([l.reshape(-1).to(torch.int64) for _, _, l in rooms])
+    return coord, feat, label, [int(c.shape[0]) for c, _, _ in rooms]
+
+
+def _scannet_transform(t, coord, feat, off_t, d):
+    """ScanNetTrainAugment.__call__ on given draws -- the same records for the same two entry points, bit for bit -- with the
+    records going up through pinned staging instead of a blocking copy"""
+    B, T, dev = off_t.shape[0] - 1, coord.shape[0], coord.device
+    par = t.params(d).pin_memory().to(dev, non_blocking=True)
+    mean, std = _colour_constants(t.color_mean if t.color_mean is not None else (0.0, 0.0, 0.0),  # (x - 0) / 1 == x exactly
+                                  t.color_std if t.color_std is not None else (1.0, 1.0, 1.0), dev, "scannet_train_rooms")
+    pos = torch.empty(T, 3, dtype=torch.float64, device=dev)
+    x = torch.empty(T, 3, dtype=torch.float32, device=dev)
+    stats = torch.empty(B, 8, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    wb = int(lib.amc3d_scannet_stats_workspace_bytes(B))
+    work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.amc3d_scannet_room_stats(B, _ptr(off_t), _ptr(feat), _ptr(par), _ptr(stats), _ptr(work), wb, _stream(coord)),
+                   "scannet_room_stats")
+        _lib.check(lib.amc3d_scannet_transform_rooms(B, T, _ptr(off_t), _ptr(coord), _ptr(feat), _ptr(par), _ptr(stats), _ptr(mean),
+                                                     _ptr(std), _ptr(pos), _ptr(x), _stream(coord)), "scannet_transform_rooms")
+    return pos, x
+
+
+def _scannet_batch(coord, feat, label, sizes, transform, voxel_size, voxel_max, variable, generator, draws, gravity_dim,
+                   who="scannet_train_rooms"):
+    """scannet_train_rooms on rooms that are already concatenated: coord (T,3) fp32, feat (T,3) fp32, label (T) int64"""
+    B, dev, total = len(sizes), coord.device, sum(sizes)
+    if voxel_max is None or int(voxel_max) <= 0:
+        raise ValueError(f"{who}: voxel_max is the size of a training cloud")
+    if gravity_dim not in (0, 1, 2) or not float(voxel_size) > 0:
+        raise ValueError(f"{who}: gravity_dim is 0, 1 or 2 and voxel_size is positive")
+    if total >= 2 ** 31:
+        raise ValueError(f"{who}: {total} points in one batch (at most 2^31 - 1)")
+    voxel_max = int(voxel_max)
+    d = dict(draws or {})
+    per_room = {}
+    for k in ("rnd", "init_idx", "pad", "perm"):
+        v = d.pop(k, None)
+        per_room[k] = list(v) if v is not None else [None] * B
+        if len(per_room[k]) != B:
+            raise ValueError(f"{who}: per-room draws need one entry per room")
+    if any(k not in d for k in _SCANNET_TRANSFORM_KEYS) or ("angle" not in d and "R" not in d):
+        for k, v in transform.draw(B, generator, dev).items():  # a read-back when the generator lives on the device
+            d.setdefault(k, v)
+    lib = _lib.load()
+    P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    offsets = [0]
+    for n in sizes:
+        offsets.append(offsets[-1] + n)
+    off_t = _upload(offsets, torch.int64, dev)
+    pos64, x = _scannet_transform(transform, coord, feat, off_t, d)
+    p = torch.empty(total, 3, dtype=torch.float64, device=dev)
+    key = torch.empty(total, dtype=torch.int64, device=dev)  # uint64 bit patterns
+    idx_sort = torch.empty(total, dtype=torch.int32, device=dev)
+    start = torch.empty(total + 1, dtype=torch.int32, device=dev)
+    count = torch.empty(total, dtype=torch.int32, device=dev)
+    small = torch.empty(2 * B + 1, dtype=torch.int32, device=dev)
+    vbase, cmax = small[:B + 1], small[B + 1:]
+    corner = torch.empty(B, 3, dtype=torch.float64, device=dev)
+    wb = int(lib.amc3d_scannet_voxelize_workspace_bytes(B, total))
+    work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.amc3d_scannet_voxelize_rooms(B, total, P(pos64), P(off_t), ctypes.c_double(float(voxel_size)), P(p), P(key),
+                                                    P(idx_sort), P(start), P(count), P(vbase), P(cmax), P(corner), P(work), wb,
+                                                    stream), "scannet_voxelize_rooms")
+    # the device's own draws, enqueued before the read-back in tables sized by the point count (a room has at most as many
+    # voxels as points), so the stream does not depend on the voxel counts: voxelize's randint, crop_pc's randint(N), its
+    # np.random.choice(N, voxel_max - N) and its permutation, in this order
+    rnd_u = init_u = pad_t = perm_t = None
+    if any(r is None for r in per_room["rnd"]):
+        rnd_u = torch.rand(total, dtype=torch.float64, device=dev, generator=generator)
+    if any(v is None for v in per_room["init_idx"]):
+        init_u = torch.rand(B, dtype=torch.float64, device=dev, generator=generator)
+    if not variable:
+        if any(v is None for v in per_room["pad"]):
+            nvd = (vbase[1:] - vbase[:-1]).view(B, 1)
+            pad_t = (torch.rand(B, voxel_max, dtype=torch.float64, device=dev, generator=generator) * nvd).int()
+        if any(v is None for v in per_room["perm"]):
+            perm_t = torch.rand(B, voxel_max, device=dev, generator=generator).argsort(dim=1).int()
+    vb = vbase.tolist()  # the batch's one read-back: the voxel counts size everything after the voxelisation
+    nv = [vb[b + 1] - vb[b] for b in range(B)]
+    nvt = vb[B]
+    outs = [voxel_max if (n >= voxel_max or not variable) else n for n in nv]
+    n_out = outs[0]
+    if any(n != n_out for n in outs):
+        raise ValueError(f"{who}: the rooms came out with different sizes {outs} (variable=True); the collate stacks them")
+    cropped = [n >= voxel_max for n in nv]
+    padded = [n < n_out for n in nv]
+    given = lambda v: torch.as_tensor(v).to(dev)  # noqa: E731
+    rnd_t = None
+    if any(r is not None for r in per_room["rnd"]):
+        rnd_t = torch.full((nvt,), -1, dtype=torch.int32, device=dev)
+        for b, r in enumerate(per_room["rnd"]):
+            if r is not None:
+                r = given(r)
+                if r.shape != (nv[b],) or r.is_floating_point() or bool((r < 0).any()):
+                    raise ValueError(f"{who}: room {b}: rnd must hold {nv[b]} non-negative draws")
+                rnd_t[vb[b]:vb[b + 1]] = r
+    init_t = None
+    if any(cropped):
+        inits = []
+        for b, v in enumerate(per_room["init_idx"]):
+            v = -1 if (v is None or not cropped[b]) else int(v)
+            if per_room["init_idx"][b] is not None and cropped[b] and not 0 <= v < nv[b]:
+                raise ValueError(f"{who}: room {b}: init_idx {v} out of range")
+            inits.append(v)
+        if any(v >= 0 for v in inits):
+            init_t = _upload(inits, torch.int32, dev)
+    if any(padded):
+        if pad_t is None:
+            pad_t = torch.zeros(B, n_out, dtype=torch.int32, device=dev)
+        for b, v in enumerate(per_room["pad"]):
+            if v is not None and padded[b]:
+                v = given(v)
+                if v.shape != (n_out - nv[b],) or v.is_floating_point() or bool(((v < 0) | (v >= nv[b])).any()):
+                    raise ValueError(f"{who}: room {b}: pad must hold {n_out - nv[b]} indices below {nv[b]}")
+                pad_t[b, nv[b]:] = v
+    if perm_t is None:
+        if any(v is None for v in per_room["perm"]):  # variable=True: the size of the shuffle is the voxel count
+            perm_t = torch.rand(B, n_out, device=dev, generator=generator).argsort(dim=1).int()
+        else:
+            perm_t = torch.empty(B, n_out, dtype=torch.int32, device=dev)
+    for b, v in enumerate(per_room["perm"]):
+        if v is not None:
+            v = given(v)
+            if v.shape != (n_out,) or v.is_floating_point() or not bool((v.sort().values == torch.arange(n_out, device=dev)).all()):
+                raise ValueError(f"{who}: room {b}: perm must be a permutation of {n_out}")
+            perm_t[b] = v
+    sel = torch.empty(max(nvt, 1), dtype=torch.int32, device=dev)
+    d2 = order = work2 = None
+    wb2 = 0
+    if any(cropped):
+        d2 = torch.empty(nvt, dtype=torch.float64, device=dev)
+        order = torch.empty(nvt, dtype=torch.int32, device=dev)
+        wb2 = int(lib.amc3d_scannet_crop_workspace_bytes(nvt))
+        work2 = torch.empty(max(wb2, 8), dtype=torch.uint8, device=dev)
+    wb3 = int(lib.amc3d_scannet_crop_tail_workspace_bytes(B))
+    work3 = torch.empty(max(wb3, 8) // 8, dtype=torch.float64, device=dev)
+    out = {"pos": torch.empty(B, n_out, 3, dtype=torch.float32, device=dev),
+           "x": torch.empty(B, n_out, 3, dtype=torch.float32, device=dev),
+           "heights": torch.empty(B, n_out, 1, dtype=torch.float32, device=dev),
+           "y": torch.empty(B, n_out, dtype=torch.int64, device=dev)}
+    with torch.cuda.device(dev):
+        _lib.check(lib.amc3d_scannet_select_crop(B, nvt, voxel_max, int(any(cropped)), P(p), P(idx_sort), P(start), P(count),
+                                                 P(vbase), P(cmax), P(rnd_t), P(rnd_u), P(init_t), P(init_u), P(sel), P(d2), P(order),
+                                                 P(work2), wb2, stream), "scannet_select_crop")
+        _lib.check(lib.amc3d_scannet_crop_tail_rooms(B, n_out, voxel_max, int(gravity_dim), P(p), P(x), P(label), P(vbase), P(sel),
+                                                     P(order), P(pad_t), P(perm_t), P(out["pos"]), P(out["x"]), P(out["heights"]),
+                                                     P(out["y"]), P(work3), wb3, stream), "scannet_crop_tail_rooms")
+    return out
+
+
+def scannet_train_rooms(rooms, transform, voxel_size=0.02, voxel_max=64000, variable=False, generator=None, draws=None,
+                        gravity_dim=2):
+    """scannet_train_batch with everything after the transform chain done for the whole batch at once (csrc/scannet_rooms.hip):
+    the same arguments, the same `draws` dictionary -- the transform's keys, "R" included, and the per-room lists "rnd",
+    "init_idx", "pad", "perm" (entries may be None) -- and the same return value.  For the same draws every output equals
+    scannet_train_batch's bit for bit, in about twenty launches for the batch instead of about twenty per room.
+
+    With a generator the draws are made on the device, the way s3dis_train_batch makes them: floor(u * range) of float64
+    uniforms (voxelize's randint, the crop centre, the padding) and the shuffle as the argsort of uniforms.  They are enqueued
+    before the read-back, in tables sized by the point count (voxels <= points) and by voxel_max, so the random stream does not
+    depend on the voxel counts -- and therefore differs from scannet_train_batch's, which draws room by room at the voxel
+    count's size.  (variable=True: the shuffle has the voxel count's size and is drawn after the read-back.)
+    Host synchronisation: one read-back per batch (the B voxel counts, after the voxelisation is enqueued), none per room; one
+    more only when the room-level draws have to come from a device generator (the rotation is formed on the host from cos /
+    sin); draws that are passed in are validated, which reads their verdicts back.  Small host tables (offsets, the transform's
+    records, the crop centres) go up through pinned staging.
+    variable=True: a room below voxel_max keeps its own size; rooms that come out with different sizes raise ValueError."""
+    coord, feat, label, sizes = _scannet_rooms(rooms, "scannet_train_rooms")
+    return _scannet_batch(coord, feat, label, sizes, transform, voxel_size, voxel_max, variable, generator, draws, gravity_dim)
+
+
+def feed_picks(ids, n_rooms, batch_size, drop_last):
+    """the rooms of every batch of an epoch: item ids (in the epoch's order) -> [[room, ...], ...], what
+    BatchSampler(ids, batch_size, drop_last) groups and ScanNet.__getitem__'s `idx % len(data_list)` maps to rooms"""
+    ids = [int(i) for i in ids]
+    if int(n_rooms) <= 0 or int(batch_size) <= 0:
+        raise ValueError("feed_picks: n_rooms and batch_size are positive")
+    end = len(ids) - len(ids) % batch_size if drop_last else len(ids)
+    return [[j % n_rooms for j in ids[i:i + batch_size]] for i in range(0, end, batch_size)]
+
+
+class ScanNetTrainFeed:
+    """An epoch of ScanNet training batches from rooms resident on the device: what DataLoader(ScanNet(split='train',
+    loop=loop), batch_size, shuffle=shuffle, drop_last=drop_last) yields.  rooms: list of (coord (n,3) fp32, feat (n,3) fp32,
+    label (n[,1])) GPU tensors, kept as three concatenated arrays.  Every epoch (every `iter`) draws a permutation of the
+    len(rooms) * loop item ids and the room-level transform uniforms of all its items from `generator` (at most two read-backs
+    per epoch); item id -> room id % len(rooms) (scannet.py:137-138).  Every batch is one scannet_train_rooms call
+    (variable=False) with those room-level draws passed in, on the current stream, at the moment the consumer asks for it: one
+    read-back per batch, no side stream, no prefetch.  The transform kernels take contiguous rooms, so a batch first
+    concatenates the picked slices (one torch.cat per array).  train.train_one_epoch takes it as `train_loader`."""
+
+    def __init__(self, rooms, transform, batch_size, loop=1, voxel_size=0.02, voxel_max=64000, shuffle=True, drop_last=True,
+                 generator=None):
+        self.coord, self.feat, self.label, self.sizes = _scannet_rooms(rooms, "ScanNetTrainFeed")
+        if int(batch_size) <= 0 or int(loop) <= 0:
+            raise ValueError("ScanNetTrainFeed: batch_size and loop are positive")
+        if voxel_max is None:
+            raise ValueError("ScanNetTrainFeed: voxel_max is the size of a training cloud")
+        self.starts = [0]
+        for n in self.sizes[:-1]:
+            self.starts.append(self.starts[-1] + n)
+        self.transform, self.batch_size, self.loop = transform, int(batch_size), int(loop)
+        self.voxel_size, self.voxel_max, self.shuffle, self.drop_last = voxel_size, voxel_max, bool(shuffle), bool(drop_last)
+        self.generator = generator
+
+    def __len__(self):
+        items = len(self.sizes) * self.loop
+        return items // self.batch_size if self.drop_last else -(-items // self.batch_size)
+
+    def __iter__(self):
+        items, dev = len(self.sizes) * self.loop, self.coord.device
+        ids = torch.randperm(items, device=dev, generator=self.generator).tolist() if self.shuffle else list(range(items))
+        room_draws = self.transform.draw(items, self.generator, dev)  # host tensors, one row per item in the epoch's order
+        for i, pick in enumerate(feed_picks(ids, len(self.sizes), self.batch_size, self.drop_last)):
+            lo = i * self.batch_size
+            d = {k: v[lo:lo + len(pick)] for k, v in room_draws.items()}
+            cut = lambda t: (t[self.starts[pick[0]]:self.starts[pick[0]] + self.sizes[pick[0]]] if len(pick) == 1 else  # noqa: E731
+                             torch.cat([t[self.starts[j]:self.starts[j] + self.sizes[j]] for j in pick]))
+            yield _scannet_batch(cut(self.coord), cut(self.feat), cut(self.label), [self.sizes[j] for j in pick], self.transform,
+                                 self.voxel_size, self.voxel_max, False, self.generator, d, 2, "ScanNetTrainFeed")

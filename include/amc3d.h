@@ -847,6 +847,43 @@ int amc3d_s3dis_crop_tail(int rooms, int n, int voxel_max, int raw_f64, const vo
                           const long long *offsets, const float *coord, const int *vbase, const int *sel, const int *order,
                           const int *pad, const int *perm, float *pos_out, float *colour_out, long long *y_out, void *stream);
 
+/* ---- ScanNet training input for a batch of rooms, the part after the transform chain (dataset/scannetv2/scannet.py:166-176:
+ * crop_pc in float64, dataset/data_util.py:146-174, then heights).  The float64 sibling of the S3DIS block above.  Rooms are
+ * ragged: pos (total,3) double, x (total,3) fp32 and y (total) int64 as amc3d_scannet_transform_rooms leaves them for the
+ * concatenated rooms; room r is points [offsets[r], offsets[r+1]) (offsets (rooms+1) int64, device memory; total =
+ * offsets[rooms] < 2^31, no empty room).  Everything is exact arithmetic: the results equal amc3d_voxelize_f64 /
+ * amc3d_voxel_select / amc3d_crop_nearest_f64 / amc3d_scannet_crop_tail run room by room, bit for bit.
+ * voxelize_rooms: corner (rooms,3) = the fp64 minimum of pos; coord (total,3) = pos - corner; key (total) as
+ * amc3d_voxelize_f64; idx_sort (total) = batch point indices ordered by (room, key), stable (two device-wide radix sorts: 64 key
+ * bits, then the room-id bits; one room: the first only); voxels numbered through the batch, a room boundary always starting
+ * one: start (total+1), count (total; written for the voxels only), vbase (rooms+1) = first voxel of every room,
+ * vbase[rooms] = their number, cmax (rooms) = count.max() per room.  Nothing is read back.
+ * select_crop (nvox = vbase[rooms], read back by the caller): sel (nvox) = idx_sort[start[v] + rnd[v] % count[v]], where
+ * rnd[v] < 0 or rnd NULL takes (int)(rnd_u[v] * cmax[room]); with any_crop, for every room with at least voxel_max voxels d2
+ * (nvox) = ((dx^2 + dy^2) + dz^2) in fp64 from its representative number init[r] (init[r] < 0 or init NULL:
+ * min((int)(init_u[r] * its voxel count), that - 1)), and order (nvox) = voxel numbers sorted by (room, the 64 bits of d2),
+ * stable (the composite key is wider than 64 bits: one device-wide radix sort over the d2 bits, then the stable pass over the
+ * room-id bits): a room's crop is the first voxel_max entries of its range of order.  d2 is 0 in the other rooms.
+ * crop_tail_rooms: two launches for the batch, several workgroups per room (partial minima, then fold and gather): slot k of
+ * room r <- representative c = perm[r,k] (perm (rooms,n) or NULL: identity) of the crop order, or, for a room below voxel_max,
+ * voxel c for c below its voxel count and voxel pad[r,c] above (pad (rooms,n), only those slots read); pos_out (rooms,n,3) =
+ * fl32(coord - the fp64 min corner of the room's n slots), x_out (rooms,n,3) = x, heights (rooms,n) = pos_out[..., gravity_dim],
+ * y_out (rooms,n) int64 = y. */
+size_t amc3d_scannet_voxelize_workspace_bytes(int rooms, long long total);
+int amc3d_scannet_voxelize_rooms(int rooms, long long total, const double *pos, const long long *offsets, double voxel_size,
+                                 double *coord, unsigned long long *key, int *idx_sort, int *start, int *count, int *vbase,
+                                 int *cmax, double *corner, void *workspace, size_t workspace_bytes, void *stream);
+size_t amc3d_scannet_crop_workspace_bytes(int nvox);
+int amc3d_scannet_select_crop(int rooms, int nvox, int voxel_max, int any_crop, const double *coord, const int *idx_sort,
+                              const int *start, const int *count, const int *vbase, const int *cmax, const int *rnd,
+                              const double *rnd_u, const int *init, const double *init_u, int *sel, double *d2, int *order,
+                              void *workspace, size_t workspace_bytes, void *stream);
+size_t amc3d_scannet_crop_tail_workspace_bytes(int rooms);
+int amc3d_scannet_crop_tail_rooms(int rooms, int n, int voxel_max, int gravity_dim, const double *coord, const float *x,
+                                  const long long *y, const int *vbase, const int *sel, const int *order, const int *pad,
+                                  const int *perm, float *pos_out, float *x_out, float *heights, long long *y_out,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
