@@ -136,6 +136,12 @@ SIGNATURES = {
     "amc3d_local_aggregation_forward_strided": (_i, [_i] * 7 + [_f, _f] + [_vp] * 4 + [_l] + [_vp] * 14 + [_i, _vp, _vp, _sz, _vp]),
     "amc3d_local_aggregation_backward": (_i, [_i] * 6 + [_vp] * 17 + [_i, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_local_aggregation_backward_strided": (_i, [_i] * 6 + [_vp] * 7 + [_l] + [_vp] * 8 + [_l] + [_vp] * 2 + [_i, _vp, _vp, _vp, _sz, _vp]),
+    "amc3d_local_aggregation_csr_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "amc3d_local_aggregation_workspace_q_offset": (_sz, [_i, _i, _i, _i]),
+    "amc3d_local_aggregation_backward_csr": (_i, [_i] * 6 + [_vp] * 19 + [_i, _vp, _vp, _vp, _sz, _vp]),
+    "amc3d_local_aggregation_backward_csr_strided": (_i, [_i] * 6 + [_vp] * 7 + [_l] + [_vp] * 10 + [_l] + [_vp] * 2 + [_i, _vp, _vp, _vp, _sz, _vp]),
+    "amc3d_three_interpolate_grad_csr": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "amc3d_masked_refine_backward_csr": (_i, [_i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "amc3d_pointwise_conv_forward_bf16": (_i, [_i, _i, _i, _l, _vp, _vp, _vp, _vp, _vp]),
     "amc3d_pointwise_conv_workspace_bytes_bf16": (_sz, [_i, _i, _i, _l]),
     "amc3d_pointwise_conv_backward_bf16": (_i, [_i, _i, _i, _l, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -115,6 +115,55 @@ __global__ void three_interpolate_grad_kernel(int c, int n, int m, const float *
     }
 }
 
+// The same gradient as a gather over the reverse lists of idx (amc3d_group_csr with npoints = n, nsample = 3), no atomics:
+//   grad_points[b,ch,t] = the sum over the positions p = u*3 + j of t's list, in list order (ascending p), of
+//   __fmul_rn(grad_out[b,ch,u], weight[b,u,j]), by sequential __fadd_rn from +0.0f.
+// A thread per (known point t, group of INTERP_CPT channels): the list is walked once for the group, the stores are contiguous
+// over t.  Every element is written (an empty list: +0.0f).  grid (m tiles, channel groups, b)
+constexpr int INTERP_CPT = 8;
+__global__ __launch_bounds__(256) void three_interpolate_grad_csr_kernel(int c, int n, int m, const float *__restrict__ grad_out,
+                                                                         const float *__restrict__ weight,
+                                                                         const int *__restrict__ rev_start,
+                                                                         const int *__restrict__ rev_edge,
+                                                                         float *__restrict__ grad_points)
+{
+    const int bs = blockIdx.z;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= m) return;
+    const int ch0 = blockIdx.y * INTERP_CPT;
+    const int nch = min(INTERP_CPT, c - ch0);
+    const int s = rev_start[(size_t)bs * m + t], e = rev_start[(size_t)bs * m + t + 1];
+    const float *ww = weight + (size_t)bs * n * 3;
+    const float *src = grad_out + ((size_t)bs * c + ch0) * n;
+    float acc[INTERP_CPT];
+#pragma unroll
+    for (int k = 0; k < INTERP_CPT; ++k) acc[k] = 0.f;
+    for (int i = s; i < e; i += 4) {  // four positions' loads in flight (a chain of dependent round trips otherwise); the adds
+        int u[4];                     // keep the list order
+        float w[4], g[4][INTERP_CPT];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int p = rev_edge[min(i + j, e - 1)];
+            u[j] = p / 3;
+            w[j] = ww[p];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int k = 0; k < INTERP_CPT; ++k) g[j][k] = src[(size_t)(k < nch ? k : 0) * n + u[j]];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (i + j < e) {
+#pragma unroll
+                for (int k = 0; k < INTERP_CPT; ++k) acc[k] = __fadd_rn(acc[k], __fmul_rn(g[j][k], w[j]));
+            }
+    }
+    float *dst = grad_points + ((size_t)bs * c + ch0) * m + t;
+#pragma unroll
+    for (int k = 0; k < INTERP_CPT; ++k)
+        if (k < nch) dst[(size_t)k * m] = acc[k];
+}
+
 }  // namespace amc
 
 using namespace amc;
@@ -187,4 +236,20 @@ AMC_API int amc3d_three_interpolate_grad(int b, int c, int n, int m, const float
     hipLaunchKernelGGL(three_interpolate_grad_kernel, dim3(div_up(n, 256), b), dim3(256), 0, (hipStream_t)stream, c, n,
                        m, grad_out, idx, weight, grad_points);
     return launch_status("amc3d_three_interpolate_grad");
+}
+
+// amc3d_three_interpolate_grad without atomics: rev_start (b*m + 1) / rev_edge (b*n*3) = amc3d_group_csr(b, m, n, 3, idx).
+// grad_points (b,c,m) is written whole (no zero fill needed); the summation order is fixed (see the kernel, include/amc3d.h).
+AMC_API int amc3d_three_interpolate_grad_csr(int b, int c, int n, int m, const float *grad_out, const int *idx,
+                                             const float *weight, const int *rev_start, const int *rev_edge,
+                                             float *grad_points, void *stream)
+{
+    (void)idx;  // the lists carry everything the indices say
+    if (b <= 0 || c <= 0 || m <= 0) return 0;
+    if (n < 0 || (n > 0 && (!grad_out || !weight)) || !rev_start || !rev_edge || !grad_points || b > 65535 ||
+        div_up(c, INTERP_CPT) > 65535 || (long)n * 3 >= (1L << 31))
+        return bad_arg("amc3d_three_interpolate_grad_csr: bad argument");
+    hipLaunchKernelGGL(three_interpolate_grad_csr_kernel, dim3(div_up(m, 256), div_up(c, INTERP_CPT), b), dim3(256), 0,
+                       (hipStream_t)stream, c, n, m, grad_out, weight, rev_start, rev_edge, grad_points);
+    return launch_status("amc3d_three_interpolate_grad_csr");
 }

@@ -314,13 +314,18 @@ __global__ __launch_bounds__(256) void lagg_pool_kernel(int C, int n, int M, int
 // backward 1: per (b,c,m): dq = dpooled * [relu: bn(ystar) > 0], scatter into Q[b, idx[b,m,arg], c]; per-channel partial sums
 //   {sum dq, sum dq xhat, sum dq dp_j}.  grid (m-tile groups, channel chunks of 128, b)
 // ---------------------------------------------------------------------------------------------------------------
+// LISTS: the deterministic form (amc3d_local_aggregation_backward_csr).  No atomics: the masked gradient dq and its arg go out
+// point-major -- dq_pm (b, M, C) floats behind Q, arg_pm (b, M, C) bytes -- for lagg_bwd_gather_kernel, which forms Q from the
+// reverse lists; the tile is already transposed in LDS here, so both stores are contiguous over the channels of a wave.
+template <bool LISTS>
 __global__ __launch_bounds__(256) void lagg_bwd_scatter_kernel(int C, int n, int M, int K, int relu,
                                                                const float *__restrict__ dpooled, const float *__restrict__ ystar,
                                                                const unsigned char *__restrict__ arg, const int *__restrict__ idx,
                                                                const float *__restrict__ dp, const float *__restrict__ mean,
                                                                const float *__restrict__ invstd, const float *__restrict__ gamma,
                                                                const float *__restrict__ beta, float *__restrict__ Q,
-                                                               double *__restrict__ partial, int nparts_per_b, int tiles_per_wg)
+                                                               double *__restrict__ partial, int nparts_per_b, int tiles_per_wg,
+                                                               float *__restrict__ dq_pm, unsigned char *__restrict__ arg_pm)
 {
     extern __shared__ float lagg_smem[];
     const int ct = min(LAGG_CT, C - (int)blockIdx.y * LAGG_CT);
@@ -381,6 +386,11 @@ __global__ __launch_bounds__(256) void lagg_bwd_scatter_kernel(int C, int n, int
                 const int k = __float_as_int(sa[cl * (LAGG_MT + 1) + ml]);
                 const float xh = __fmul_rn(__fsub_rn(y, mu[h]), is[h]);
                 if (relu && !(__fadd_rn(__fmul_rn(xh, ga[h]), be[h]) > 0.f)) dq = 0.f;
+                if constexpr (LISTS) {
+                    const size_t o = ((size_t)b * M + m) * C + c0 + cl;
+                    dq_pm[o] = dq;
+                    arg_pm[o] = (unsigned char)k;
+                }
                 if (dq != 0.f) {
                     const int slot = ml * K + k;
                     const int id = sidx[slot];
@@ -388,7 +398,7 @@ __global__ __launch_bounds__(256) void lagg_bwd_scatter_kernel(int C, int n, int
                     acc[h][0] += dd; acc[h][1] += dd * (double)xh;
                     acc[h][2] += dd * (double)sdp[slot]; acc[h][3] += dd * (double)sdp[LAGG_MT * K + slot];
                     acc[h][4] += dd * (double)sdp[2 * LAGG_MT * K + slot];
-                    atomicAdd(Q + ((size_t)b * n + id) * C + c0 + cl, dq);
+                    if constexpr (!LISTS) atomicAdd(Q + ((size_t)b * n + id) * C + c0 + cl, dq);
                 }
             }
         }
@@ -408,6 +418,44 @@ __global__ __launch_bounds__(256) void lagg_bwd_scatter_kernel(int C, int n, int
                          (red[((size_t)2 * ct + cl) * 5 + j] + red[((size_t)3 * ct + cl) * 5 + j]);
         partial[(((size_t)b * nparts_per_b + blockIdx.x) * C + c0 + cl) * 5 + j] = v;
     }
+}
+
+// Q from the reverse lists (amc3d_group_csr), no atomics: Q[b,j,c] = the sum of dq[b,c,m] over the positions (m,k) of j's list
+// with arg[b,c,m] == k, taken in list order (ascending position) by sequential fp32 adds from +0.0f.  A thread per (source
+// point, channel), the channel on the lane: the list entries are wave-wide broadcasts, dq_pm / arg_pm rows contiguous reads.
+// A padded ball-query row holds j at several k of one m: only the position that equals arg carries the gradient.  Every
+// element of Q is written (an empty list: +0.0f).
+__global__ __launch_bounds__(256) void lagg_bwd_gather_kernel(int C, int n, int M, int K, long total,
+                                                              const float *__restrict__ dq_pm,
+                                                              const unsigned char *__restrict__ arg_pm,
+                                                              const int *__restrict__ rev_start, const int *__restrict__ rev_edge,
+                                                              float *__restrict__ Q)
+{
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const long g = t / C;
+    const int c = (int)(t - g * C);
+    const long b = g / n;
+    const int s = rev_start[g], e = rev_start[g + 1];
+    const float *drow = dq_pm + (size_t)b * M * C + c;
+    const unsigned char *arow = arg_pm + (size_t)b * M * C + c;
+    float q = 0.f;
+    for (int i = s; i < e; i += 4) {  // four positions' loads in flight; the adds keep the list order
+        int m[4], k[4], a[4];
+        float d[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int p = rev_edge[min(i + u, e - 1)];
+            m[u] = p / K;
+            k[u] = p - m[u] * K;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { a[u] = arow[(size_t)m[u] * C]; d[u] = drow[(size_t)m[u] * C]; }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (i + u < e && a[u] == k[u]) q = __fadd_rn(q, d[u]);
+    }
+    Q[t] = q;
 }
 
 // dgamma, dbeta, dW_dp and the per-channel coefficients of dG: coef[c] = {g*is, ma, mb*is, mu}
@@ -754,6 +802,24 @@ AMC_API int amc3d_group_moments(int b, int n, int npoints, int nsample, const in
     return launch_status("amc3d_group_moments");
 }
 
+// coef (cout, 4) floats, rounded up so that what follows it in the workspace stays 16-byte aligned
+static size_t lagg_coef_floats(int cout) { return ((size_t)cout * 4 + 3) & ~(size_t)3; }
+
+// the workspace of amc3d_local_aggregation_backward_csr: that of the atomic form | dq_pm (b, npoints, cout) floats | arg_pm bytes
+AMC_API size_t amc3d_local_aggregation_csr_workspace_bytes(int b, int cout, int n, int npoints)
+{
+    if (b <= 0 || cout <= 0 || n <= 0 || npoints <= 0) return 0;
+    return lagg_partial_bytes(b, cout, n, npoints) + (size_t)b * n * cout * sizeof(float) + lagg_coef_floats(cout) * sizeof(float) +
+           (size_t)b * npoints * cout * 5 + 64;
+}
+
+// where both backward forms leave Q (b, n, cout) in their workspace, in bytes (tests and tools check the summation order on it)
+AMC_API size_t amc3d_local_aggregation_workspace_q_offset(int b, int cout, int n, int npoints)
+{
+    if (b <= 0 || cout <= 0 || n <= 0 || npoints <= 0) return 0;
+    return lagg_partial_bytes(b, cout, n, npoints);
+}
+
 AMC_API size_t amc3d_local_aggregation_workspace_bytes(int b, int cout, int n, int npoints)
 {
     if (b <= 0 || cout <= 0 || n <= 0 || npoints <= 0) return 0;
@@ -855,14 +921,18 @@ static int local_aggregation_backward_impl(int b, int cout, int n, int npoints, 
                                                const float *invstd, const float *gamma, const float *beta,
                                                float *dg_cm, float *dw_dp, long lddw, float *dgamma, float *dbeta,
                                                int phase, double *dsums, const double *count_dev, void *workspace,
-                                               size_t workspace_bytes, void *stream_)
+                                               size_t workspace_bytes, void *stream_, const int *rev_start = nullptr,
+                                               const int *rev_edge = nullptr)
 
 {
     if (b <= 0 || npoints <= 0) return 0;
+    const bool lists = rev_start != nullptr;
     if (phase != 0 && (!dsums || (phase == 2 && !count_dev))) return bad_arg("amc3d_local_aggregation_backward: phase 1 / 2 need dsums (and the count)");
     if (!lagg_supported(cout, nsample) || n <= 0 || !dpooled || !ystar || !arg || !g_pm || !idx || !dp || !w_dp || !moments || !gd ||
-        !mean || !invstd || !gamma || !beta || !dg_cm || !dw_dp || !dgamma || !dbeta || !workspace ||
-        workspace_bytes < amc3d_local_aggregation_workspace_bytes(b, cout, n, npoints))
+        !mean || !invstd || !gamma || !beta || !dg_cm || !dw_dp || !dgamma || !dbeta || !workspace || (lists && !rev_edge) ||
+        workspace_bytes < (lists ? amc3d_local_aggregation_csr_workspace_bytes(b, cout, n, npoints)
+                                 : amc3d_local_aggregation_workspace_bytes(b, cout, n, npoints)) ||
+        (lists && ((long)b * n * cout >= (1L << 39) || (long)npoints * nsample >= (1L << 31))))
         return bad_arg("amc3d_local_aggregation_backward: unsupported shape, null pointer or workspace too small");
     hipStream_t stream = (hipStream_t)stream_;
     const LaggMoments gm = lagg_views(moments, b, n);
@@ -873,14 +943,28 @@ static int local_aggregation_backward_impl(int b, int cout, int n, int npoints, 
     const int stiles = lagg_scatter_tiles(b, cout, npoints);
     const int nparts_b = div_up(div_up(npoints, LAGG_MT), stiles);
     if (phase != 2) {
-        if (int st = fill_i32((int *)Q, 0, (size_t)b * n * cout, stream)) return st;
         size_t lds = ((size_t)3 * ct * (LAGG_MT + 1) + (size_t)4 * LAGG_MT * nsample) * sizeof(float);
         const size_t red = (size_t)4 * ct * 5 * sizeof(double);
         if (lds < red) lds = red;
-        if (lds > 65536)  // (128 channels x 33 x 3 images + the idx / dp rows: 67 KB; gfx950 has 160 KB per workgroup)
-            (void)hipFuncSetAttribute((const void *)lagg_bwd_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(lagg_bwd_scatter_kernel, dim3(nparts_b, cout / ct, b), dim3(256), lds, stream, cout, n, npoints, nsample,
-                           relu, dpooled, ystar, arg, idx, dp, mean, invstd, gamma, beta, Q, partial, nparts_b, stiles);
+        if (lists) {  // no atomics, no zero fill: the gather writes every element of Q
+            float *dq_pm = coef + lagg_coef_floats(cout);
+            unsigned char *arg_pm = (unsigned char *)(dq_pm + (size_t)b * npoints * cout);
+            if (lds > 65536)
+                (void)hipFuncSetAttribute((const void *)lagg_bwd_scatter_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(lagg_bwd_scatter_kernel<true>, dim3(nparts_b, cout / ct, b), dim3(256), lds, stream, cout, n, npoints,
+                               nsample, relu, dpooled, ystar, arg, idx, dp, mean, invstd, gamma, beta, Q, partial, nparts_b, stiles,
+                               dq_pm, arg_pm);
+            const long total = (long)b * n * cout;
+            hipLaunchKernelGGL(lagg_bwd_gather_kernel, dim3((unsigned)div_up(total, 256L)), dim3(256), 0, stream, cout, n, npoints,
+                               nsample, total, (const float *)dq_pm, (const unsigned char *)arg_pm, rev_start, rev_edge, Q);
+        } else {
+            if (int st = fill_i32((int *)Q, 0, (size_t)b * n * cout, stream)) return st;
+            if (lds > 65536)  // (128 channels x 33 x 3 images + the idx / dp rows: 67 KB; gfx950 has 160 KB per workgroup)
+                (void)hipFuncSetAttribute((const void *)lagg_bwd_scatter_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(lagg_bwd_scatter_kernel<false>, dim3(nparts_b, cout / ct, b), dim3(256), lds, stream, cout, n, npoints,
+                               nsample, relu, dpooled, ystar, arg, idx, dp, mean, invstd, gamma, beta, Q, partial, nparts_b, stiles,
+                               (float *)nullptr, (unsigned char *)nullptr);
+        }
     }
     hipLaunchKernelGGL(lagg_bwd_finalize_kernel, dim3(cout), dim3(256), 0, stream, cout, nparts_b * b,
                        (double)b * (double)npoints * (double)nsample, partial, gm.mom, gd, w_dp, mean, invstd,
@@ -919,6 +1003,41 @@ AMC_API int amc3d_local_aggregation_backward_strided(int b, int cout, int n, int
     return local_aggregation_backward_impl(b, cout, n, npoints, nsample, relu, dpooled, ystar, arg, g_pm, idx, dp, WDp{w_dp, ldw}, moments, gd, mean,
         invstd, gamma, beta, dg_cm, dw_dp, lddw, dgamma, dbeta, phase, dsums, count_dev, workspace,
         workspace_bytes, stream_);
+}
+
+// The same backward with Q formed from the reverse lists of idx (amc3d_group_csr) instead of float atomics: bit-reproducible.
+// Summation order of Q: see lagg_bwd_gather_kernel and include/amc3d.h.  Workspace: amc3d_local_aggregation_csr_workspace_bytes.
+AMC_API int amc3d_local_aggregation_backward_csr(int b, int cout, int n, int npoints, int nsample, int relu, const float *dpooled,
+                                                 const float *ystar, const unsigned char *arg, const float *g_pm, const int *idx,
+                                                 const float *dp, const float *w_dp, const void *moments, const double *gd,
+                                                 const float *mean, const float *invstd, const float *gamma, const float *beta,
+                                                 const int *rev_start, const int *rev_edge, float *dg_cm, float *dw_dp,
+                                                 float *dgamma, float *dbeta, int phase, double *dsums, const double *count_dev,
+                                                 void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (!rev_start || !rev_edge) return bad_arg("amc3d_local_aggregation_backward_csr: null reverse lists");
+    return local_aggregation_backward_impl(b, cout, n, npoints, nsample, relu, dpooled, ystar, arg, g_pm, idx, dp, WDp{w_dp, 3}, moments, gd, mean,
+        invstd, gamma, beta, dg_cm, dw_dp, 3, dgamma, dbeta, phase, dsums, count_dev, workspace, workspace_bytes,
+        stream_, rev_start, rev_edge);
+}
+
+AMC_API int amc3d_local_aggregation_backward_csr_strided(int b, int cout, int n, int npoints, int nsample, int relu,
+                                                         const float *dpooled, const float *ystar,
+                                                         const unsigned char *arg, const float *g_pm, const int *idx,
+                                                         const float *dp, const float *w_dp, long ldw,
+                                                         const void *moments, const double *gd, const float *mean,
+                                                         const float *invstd, const float *gamma, const float *beta,
+                                                         const int *rev_start, const int *rev_edge,
+                                                         float *dg_cm, float *dw_dp, long lddw, float *dgamma,
+                                                         float *dbeta, int phase, double *dsums,
+                                                         const double *count_dev, void *workspace,
+                                                         size_t workspace_bytes, void *stream_)
+{
+    if (ldw < 3 || lddw < 3) return bad_arg("amc3d_local_aggregation_backward_csr_strided: row stride below 3");
+    if (!rev_start || !rev_edge) return bad_arg("amc3d_local_aggregation_backward_csr_strided: null reverse lists");
+    return local_aggregation_backward_impl(b, cout, n, npoints, nsample, relu, dpooled, ystar, arg, g_pm, idx, dp, WDp{w_dp, ldw}, moments, gd, mean,
+        invstd, gamma, beta, dg_cm, dw_dp, lddw, dgamma, dbeta, phase, dsums, count_dev, workspace,
+        workspace_bytes, stream_, rev_start, rev_edge);
 }
 
 // ---- first layer of a multi-layer SetAbstraction MLP: conv (before the gather) + BatchNorm + ReLU, x1 materialised ----

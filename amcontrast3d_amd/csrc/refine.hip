@@ -170,3 +170,49 @@ AMC_API int amc3d_masked_refine_backward(int B, int D, int n, float gamma, const
                        best, mask, df);
     return launch_status("amc3d_masked_refine_backward");
 }
+
+namespace amc {
+// The backward without atomics, from the reverse lists of best (amc3d_group_csr on the B*n rows as one cloud, nsample = 1:
+// rev_edge[rev_start[r'] .. rev_start[r' + 1]) = the rows r with best[r] == r', ascending).  Element t = r'*D + d of df:
+//   S  = the sum over those rows r, in list order, of __fmul_rn(gamma, dout[r*D + d]) where the mask covers element r*D + d,
+//        by sequential __fadd_rn from +0.0f
+//   df = __fadd_rn(direct term of refine_backward_direct_kernel, S)
+// A thread per element, d on the lane: contiguous reads of every listed row.
+__global__ __launch_bounds__(256) void refine_backward_csr_kernel(long total, int D, int n, float gamma, float one_minus_gamma,
+                                                                  const float *__restrict__ dout, const unsigned char *__restrict__ mask,
+                                                                  const int *__restrict__ rev_start, const int *__restrict__ rev_edge,
+                                                                  float *__restrict__ df)
+{
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const long bd = t / n;
+    const long bn = (bd / D) * n + (t - bd * n);
+    const float g = dout[t];
+    const float direct = __fadd_rn(__fmul_rn(__fmul_rn(gamma, g), mask[bn] ? 0.f : 1.f), __fmul_rn(one_minus_gamma, g));
+    const long row = t / D;
+    const int d = (int)(t - row * D);
+    const int s = rev_start[row], e = rev_start[row + 1];
+    float sum = 0.f;
+    for (int i = s; i < e; ++i) {
+        const long tt = (long)rev_edge[i] * D + d;
+        const long bd2 = tt / n;
+        const long bn2 = (bd2 / D) * n + (tt - bd2 * n);
+        if (mask[bn2]) sum = __fadd_rn(sum, __fmul_rn(gamma, dout[tt]));
+    }
+    df[t] = __fadd_rn(direct, sum);
+}
+}  // namespace amc
+
+AMC_API int amc3d_masked_refine_backward_csr(int B, int D, int n, float gamma, const float *dout, const int *best,
+                                             const unsigned char *mask, const int *rev_start, const int *rev_edge, float *df,
+                                             void *stream_)
+{
+    (void)best;  // the lists carry everything best says
+    if (B <= 0 || D <= 0 || n <= 0) return 0;
+    const long total = (long)B * n * D;
+    if (!dout || !mask || !rev_start || !rev_edge || !df || (long)B * n >= (1L << 31) || total >= (1L << 39))
+        return bad_arg("amc3d_masked_refine_backward_csr: bad argument");
+    hipLaunchKernelGGL(amc::refine_backward_csr_kernel, dim3((unsigned)div_up(total, 256L)), dim3(256), 0, (hipStream_t)stream_, total, D,
+                       n, gamma, (float)(1.0 - (double)gamma), dout, mask, rev_start, rev_edge, df);
+    return launch_status("amc3d_masked_refine_backward_csr");
+}

@@ -40,12 +40,13 @@ def _moments(convs, feature_type, idx, dp, n_support, csr=None):
 def _csr(convs, feature_type, idx, n_support, dp=None):
     """reverse adjacency of the query for layers whose backward sums dense per-position gradients into the source points
     (the multi-layer SetAbstraction MLP of PointNeXt-S): gathers over sorted edge lists instead of float atomics"""
-    if feature_type != 'dp_fj' or not idx.is_cuda or len(convs) < 2:
-        return None
     from amcontrast3d_amd import ops
+    # (deterministic mode: the single-layer stacks too -- ops.LocalAggregationFused then gathers over the lists)
+    if feature_type != 'dp_fj' or not idx.is_cuda or len(convs) < (1 if ops.deterministic() else 2):
+        return None
     start, edge = ops.group_csr(idx, n_support)
     csr = {'start': start, 'edge': edge}
-    if dp is not None and dp.dtype == torch.float32:
+    if len(convs) >= 2 and dp is not None and dp.dtype == torch.float32:
         csr['edge_dp'] = ops.group_csr_dp(idx, dp, edge)  # (dp, position) per edge in list order: one stream for the backward's gather
     return csr
 
@@ -87,7 +88,11 @@ class LocalAggregation(nn.Module):
             return None
         idx = self.grouper.query(p, p)
         dp = self.grouper.relative_positions(idx, p, p)
-        return {'idx': idx, 'dp': dp, 'mom': _moments(self.convs, self.feature_type, idx, dp, p.shape[1])}
+        g = {'idx': idx, 'dp': dp, 'mom': _moments(self.convs, self.feature_type, idx, dp, p.shape[1])}
+        from amcontrast3d_amd import ops
+        if ops.deterministic() and g['mom'] is not None:  # the lists the deterministic backward gathers over
+            g['csr'] = _csr(self.convs, self.feature_type, idx, p.shape[1])
+        return g
 
     def forward(self, pf, geom=None):
         p, f = pf
@@ -259,7 +264,11 @@ class FeaturePropogation(nn.Module):
         dist, idx = three_nn(p1, p2)
         dist_recip = 1.0 / (dist + 1e-8)
         weight = dist_recip / torch.sum(dist_recip, dim=2, keepdim=True)
-        return {'idx': idx, 'weight': weight}
+        g = {'idx': idx, 'weight': weight}
+        from amcontrast3d_amd import ops
+        if ops.deterministic() and idx.is_cuda and idx.dtype == torch.int32:
+            g['csr'] = ops.group_csr(idx, p2.shape[1])  # the interpolation's backward gathers over these (no float atomics)
+        return g
 
     def forward(self, pf1, pf2=None, geom=None):
         if pf2 is None:  # global branch (not used by the segmentation decoder)
@@ -273,7 +282,7 @@ class FeaturePropogation(nn.Module):
         first = feature_propagation_first_block(self.convs[0], f1, f2, geom) if len(self.convs) else None
         if first is not None:  # the first conv on both branches before the interpolation: no concatenated tensor
             return run_convblocks(list(self.convs)[1:], first)
-        up = three_interpolate(f2, geom['idx'], geom['weight'])
+        up = three_interpolate(f2, geom['idx'], geom['weight'], geom.get('csr'))
         return run_convblocks(self.convs, up if f1 is None else torch.cat((f1, up), dim=1))
 
 

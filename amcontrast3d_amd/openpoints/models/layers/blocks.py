@@ -208,7 +208,10 @@ def conv1x1(conv, x, rows_grad=False):
             # whose weight gradient is wrapped in layout transposes (scratch/pw_bench3.py: 30-50 us per layer)
             return ops.library_gemm_conv(x, conv.weight, rows_grad)
         # what is left (small layers with a bias: the skip convs of SA2-4): the convolution library -- this library's own
-        # kernel measured 0.35 ms/step slower on these three layers
+        # kernel measured 0.35 ms/step slower on these three layers (deterministic mode takes it: its sums have a fixed order,
+        # the convolution library's are not this library's to fix)
+        if ops.deterministic():
+            return ops.pointwise_conv(x, conv.weight, conv.bias, False, rows_grad)
         with torch.autocast("cuda", enabled=False):
             return conv(x)
     return conv(x)
@@ -243,7 +246,7 @@ def feature_propagation_first_block(blk, f1, f2, geom):
     if conv.bias is not None or conv.in_channels != c1 + f2.shape[1]:
         return None
     w1, w2 = ops.split_weight(conv.weight, c1)
-    y = ops.three_interpolate_add(conv1x1_weight(f2, w2), geom['idx'], geom['weight'], conv1x1_weight(f1, w1))
+    y = ops.three_interpolate_add(conv1x1_weight(f2, w2), geom['idx'], geom['weight'], conv1x1_weight(f1, w1), geom.get('csr'))
     return batchnorm_act(bn, y, relu)
 
 
@@ -380,8 +383,9 @@ def fused_local_aggregation(blocks, f, geom, feature_type):
     group = _synced_bn_group(bn, f)  # nn.SyncBatchNorm over several ranks: the statistics are exchanged between two phases
     if group is None and not _fusable_bn(bn, f):
         return None
+    csr = geom.get('csr')  # deterministic mode: the plan's reverse lists, which the backward gathers over
     return ops.LocalAggregationFused.apply(f, geom['dp'], geom['idx'], geom['mom'], conv.weight, bn.weight, bn.bias, bn.eps,
-                                           relu is not None, bn, group)
+                                           relu is not None, bn, group, (csr['start'], csr['edge']) if csr is not None else None)
 
 
 def fused_first_block(blocks, f, geom, feature_type):

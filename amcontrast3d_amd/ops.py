@@ -66,6 +66,46 @@ def _need_gpu(*ts):
                                "there is no CPU fallback" % t.device)
 
 
+_deterministic = False
+
+
+def deterministic():
+    """True while deterministic mode is on: no kernel that adds floats with atomics is launched, so a train step on one GPU
+    is a pure function of its inputs (same bits on every run).  An operator then takes an atomic-free route -- the
+    reverse-list gathers of csrc/csr.hip and the *_csr entries, this library's fixed-order GEMMs instead of the BLAS
+    library -- or raises RuntimeError("<op>: no deterministic route ..."); it never falls back silently.  Integer and
+    fixed-point atomics are independent of their order and stay.  Off by default; the default routes do not change."""
+    return _deterministic
+
+
+def set_deterministic(flag):
+    """switch deterministic mode on or off for the whole process"""
+    global _deterministic
+    _deterministic = bool(flag)
+
+
+class deterministic_mode:
+    """with deterministic_mode(flag=True): the mode set for the block, the previous state restored on leaving it.  Autograd
+    runs backward outside the block of forward: every Function records the mode it was built under (ctx.det) and its
+    backward honours that record, not the mode at the time backward runs."""
+
+    def __init__(self, flag=True):
+        self.flag = bool(flag)
+
+    def __enter__(self):
+        self.prev = deterministic()
+        set_deterministic(self.flag)
+        return self
+
+    def __exit__(self, *exc):
+        set_deterministic(self.prev)
+        return False
+
+
+def _no_route(op, why):
+    return RuntimeError(f"{op}: no deterministic route ({why}); see amcontrast3d_amd.ops.deterministic")
+
+
 def mixed_precision():
     """True inside torch.autocast('cuda', dtype=torch.bfloat16): the pointwise convolutions then run in bf16 compute /
     fp32 accumulate (csrc/gemm_bf16.hip) while every tensor stays fp32 in memory (main_AA.py:389-394 use_amp)"""
@@ -190,12 +230,15 @@ class GroupingOperation(Function):
             _lib.check(_lib.load().amc3d_group_points(B, C, N, nfeatures, nsample, _ptr(features), _ptr(idx),
                                                       _ptr(output), _stream(features)), "group_points")
         ctx.for_backwards = (idx, N)
+        ctx.det = deterministic()
         return output
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_out):
         idx, N = ctx.for_backwards
+        if ctx.det:
+            raise _no_route("group_points_grad", "the scatter adds floats with atomics; the fused layers gather over reverse lists")
         B, C, npoint, nsample = grad_out.size()
         grad_features = torch.zeros(B, C, N, dtype=torch.float32, device=grad_out.device)
         grad_out_data = grad_out.detach().contiguous()
@@ -227,6 +270,7 @@ class GatherOperation(Function):
             _lib.check(_lib.load().amc3d_gather_points(B, C, N, npoint, _ptr(features), _ptr(idx), _ptr(output),
                                                        _stream(features)), "gather_points")
         ctx.for_backwards = (idx, C, N)
+        ctx.det = deterministic()
         return output
 
     @staticmethod
@@ -234,6 +278,9 @@ class GatherOperation(Function):
     def backward(ctx, grad_out):
         idx, C, N = ctx.for_backwards
         B, npoint = idx.size()
+        if ctx.det and not torch.cuda.is_current_stream_capturing() and int(index_duplicates(idx, N)):
+            # one atomic per address is deterministic (furthest-point picks are unique); several are not
+            raise _no_route("gather_points_grad", "idx repeats an index")
         grad_features = torch.zeros(B, C, N, dtype=torch.float32, device=grad_out.device)
         grad_out_data = grad_out.detach().contiguous()
         with torch.cuda.device(grad_out.device), timing.span("gather_points_grad", grad_out_data.numel() * 4 + idx.numel() * 4 + grad_features.numel() * 4):
@@ -308,8 +355,9 @@ three_nn = ThreeNN.apply
 class ThreeInterpolate(Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, features, idx, weight):
-        """features (B,C,M), idx (B,n,3) int32, weight (B,n,3) -> (B,C,n)"""
+    def forward(ctx, features, idx, weight, csr=None):
+        """features (B,C,M), idx (B,n,3) int32, weight (B,n,3) -> (B,C,n).  csr: group_csr(idx, M) of the geometry plan, or
+        None (deterministic mode then builds the lists in backward)"""
         assert features.is_contiguous()
         assert idx.is_contiguous()
         assert weight.is_contiguous()
@@ -319,6 +367,7 @@ class ThreeInterpolate(Function):
         B, c, m = features.size()
         n = idx.size(1)
         ctx.three_interpolate_for_backward = (idx, weight, m)
+        ctx.det, ctx.csr = deterministic(), csr
         output = torch.empty(B, c, n, dtype=torch.float32, device=features.device)
         with torch.cuda.device(features.device), timing.span("three_interpolate", features.numel() * 4 + idx.numel() * 8 + output.numel() * 4):
             _lib.check(_lib.load().amc3d_three_interpolate(B, c, m, n, _ptr(features), _ptr(idx), _ptr(weight),
@@ -330,6 +379,8 @@ class ThreeInterpolate(Function):
     def backward(ctx, grad_out):
         idx, weight, m = ctx.three_interpolate_for_backward
         B, c, n = grad_out.size()
+        if ctx.det:
+            return _three_interpolate_grad_csr(grad_out.detach().contiguous(), idx, weight, m, ctx.csr), None, None, None
         grad_features = torch.zeros(B, c, m, dtype=torch.float32, device=grad_out.device)
         grad_out_data = grad_out.detach().contiguous()
         with torch.cuda.device(grad_out.device), timing.span("three_interpolate_grad", grad_out_data.numel() * 4 + idx.numel() * 8 + grad_features.numel() * 4):
@@ -338,7 +389,20 @@ class ThreeInterpolate(Function):
                                                                 _ptr(weight), _ptr(grad_features), _ptr(work),
                                                                 work.numel() * 4, _stream(grad_out)),
                        "three_interpolate_grad")
-        return grad_features, None, None
+        return grad_features, None, None, None
+
+
+def _three_interpolate_grad_csr(grad_out, idx, weight, m, csr):
+    """grad of three_interpolate without atomics: a gather over the reverse lists of idx (built here unless the plan has them)"""
+    B, c, n = grad_out.size()
+    if csr is None:
+        csr = group_csr(idx, m)
+    grad_features = torch.empty(B, c, m, dtype=torch.float32, device=grad_out.device)  # written whole
+    with torch.cuda.device(grad_out.device), timing.span("three_interpolate_grad_csr", grad_out.numel() * 4 + idx.numel() * 12 + grad_features.numel() * 4):
+        _lib.check(_lib.load().amc3d_three_interpolate_grad_csr(B, c, n, m, _ptr(grad_out), _ptr(idx), _ptr(weight), _ptr(csr[0]),
+                                                                _ptr(csr[1]), _ptr(grad_features), _stream(grad_out)),
+                   "three_interpolate_grad_csr")
+    return grad_features
 
 
 three_interpolate = ThreeInterpolate.apply
@@ -349,7 +413,7 @@ class ThreeInterpolateAdd(Function):
     conv added onto the skip branch in the interpolation kernel itself (no (B,C1+C2,n) concatenation is ever built)"""
 
     @staticmethod
-    def forward(ctx, features, idx, weight, base):
+    def forward(ctx, features, idx, weight, base, csr=None):
         _need_gpu(features, idx, weight, base)
         _need_dtype(torch.float32, features=features, weight=weight, base=base)
         _need_dtype(torch.int32, idx=idx)
@@ -359,6 +423,7 @@ class ThreeInterpolateAdd(Function):
         assert base.shape == (B, c, n)
         ctx.save_for_backward(idx, weight)
         ctx.m = m
+        ctx.det, ctx.csr = deterministic(), csr
         output = torch.empty(B, c, n, dtype=torch.float32, device=features.device)
         with torch.cuda.device(features.device), timing.span("three_interpolate", features.numel() * 4 + idx.numel() * 8 + output.numel() * 8):
             _lib.check(_lib.load().amc3d_three_interpolate_add(B, c, m, n, _ptr(features), _ptr(idx), _ptr(weight), _ptr(base),
@@ -371,13 +436,15 @@ class ThreeInterpolateAdd(Function):
         m = ctx.m
         B, c, n = grad_out.size()
         grad_out_data = grad_out.detach().contiguous()
+        if ctx.det:
+            return _three_interpolate_grad_csr(grad_out_data, idx, weight, m, ctx.csr), None, None, grad_out, None
         grad_features = torch.zeros(B, c, m, dtype=torch.float32, device=grad_out.device)
         with torch.cuda.device(grad_out.device), timing.span("three_interpolate_grad", grad_out_data.numel() * 4 + idx.numel() * 8 + grad_features.numel() * 4):
             work = torch.empty(B * c * m, dtype=torch.float32, device=grad_out.device)
             _lib.check(_lib.load().amc3d_three_interpolate_grad(B, c, n, m, _ptr(grad_out_data), _ptr(idx), _ptr(weight),
                                                                 _ptr(grad_features), _ptr(work), work.numel() * 4,
                                                                 _stream(grad_out)), "three_interpolate_grad")
-        return grad_features, None, None, grad_out
+        return grad_features, None, None, grad_out, None
 
 
 three_interpolate_add = ThreeInterpolateAdd.apply
@@ -629,6 +696,7 @@ class ContrastStage(Function):
             assert rev is not None and mutual.is_contiguous() and mutual.shape == (m, k) and mutual.device == dev
         ctx.save_for_backward(f, norm, keep, posmask, a, sim, mean_cnt, anchors, rev, mutual, unit)
         ctx.args = (float(mu), float(nu), float(temperature), k, stride)
+        ctx.det = deterministic()
         return mean_cnt[0].clone()
 
     @staticmethod
@@ -652,6 +720,8 @@ class ContrastStage(Function):
             return (grad_f,) + (None,) * 9
         if mutual is not None:
             rev = None  # (a width the row kernels do not cover: the atomic form below; rev holds non-mutual edges only)
+        if ctx.det:
+            anchors, rev = _contrast_lists("contrast_backward", C, nbr, a, anchors, rev)
         if rev is not None and lib.amc3d_contrast_backward_csr_supported(C):
             grad_f = torch.empty_like(f)  # every row is written
             gco = torch.empty(m * k, dtype=torch.float32, device=f.device)
@@ -668,6 +738,18 @@ class ContrastStage(Function):
                                                            mu, nu, temperature, _ptr(sim), _ptr(mean_cnt),
                                                            _ptr(g), _ptr(grad_f), _stream(f)), "contrast_backward")
         return (grad_f,) + (None,) * 9
+
+
+def _contrast_lists(op, C, nbr, a, anchors, rev):
+    """deterministic mode: the (anchors, reverse lists of all their edges) a gathering contrast backward needs, built here
+    where the stage's plan has none; a width without row kernels has only the atomic form"""
+    if not _lib.load().amc3d_contrast_backward_csr_supported(C):
+        raise _no_route(op, f"the reverse-list backward does not cover {C} channels")
+    if rev is None:
+        if anchors is None:
+            anchors = select_anchors(a)
+        rev = contrast_csr(nbr, anchors)
+    return anchors, rev
 
 
 contrast_stage = ContrastStage.apply
@@ -746,6 +828,7 @@ class ContrastStageVariant(Function):
             assert anchors is not None and rev.is_contiguous() and rev.numel() == m + 1 + m * k and rev.device == f.device
         ctx.save_for_backward(f, b["norm"], b["nbr"], posmask, a, b["sim"], b["mean_cnt"], anchors, rev)
         ctx.args = (form, float(mu), float(nu), k, b["stride"])
+        ctx.det = deterministic()
         return b["mean_cnt"][0].clone()
 
     @staticmethod
@@ -755,6 +838,10 @@ class ContrastStageVariant(Function):
         m, C = f.shape
         g = grad_out.detach().to(torch.float32).reshape(1).contiguous()
         lib = _lib.load()
+        if ctx.det:
+            if f.data_ptr() % 16:
+                raise _no_route("contrast_variant_backward", "the reverse-list backward needs 16-byte aligned rows")
+            anchors, rev = _contrast_lists("contrast_variant_backward", C, nbr, a, anchors, rev)
         gather = rev is not None and bool(lib.amc3d_contrast_backward_csr_supported(C)) and f.data_ptr() % 16 == 0
         grad_f = torch.empty_like(f) if gather else torch.zeros_like(f)  # (the gather writes every row)
         gco = torch.empty(m * k, dtype=torch.float32, device=f.device)
@@ -1187,11 +1274,15 @@ class GroupedConv(Function):
                                                       _ptr(y), _stream(features)), "grouped_conv_forward")
         ctx.save_for_backward(f_pm, dp, idx, w2)
         ctx.wshape = tuple(weight.shape)
+        ctx.det = deterministic()
         return y
 
     @staticmethod
     def backward(ctx, dy):
         f_pm, dp, idx, w2 = ctx.saved_tensors
+        if ctx.det:
+            raise _no_route("grouped_conv_backward", "its backward-data product scatters with float atomics; "
+                            "GroupedConvBN / LocalAggregationFused gather over reverse lists")
         B, N, C = f_pm.shape
         _, M, K = idx.shape
         Cout = w2.shape[0]
@@ -1378,7 +1469,7 @@ class LocalAggregationFused(Function):
     statistics are taken (nn.SyncBatchNorm semantics: one all-reduce of 2C+1 doubles forward, 2C backward), or None."""
 
     @staticmethod
-    def forward(ctx, f, dp, idx, moments, weight, gamma, beta, eps, relu, bn=None, group=None):
+    def forward(ctx, f, dp, idx, moments, weight, gamma, beta, eps, relu, bn=None, group=None, csr=None):
         _need_gpu(f, dp, idx, moments, weight, gamma, beta)
         _need_dtype(torch.float32, f=f, dp=dp, weight=weight)
         _need_dtype(torch.int32, idx=idx)
@@ -1389,6 +1480,9 @@ class LocalAggregationFused(Function):
         assert weight.numel() == C * (Cin + 3)
         dev = f.device
         lib = _lib.load()
+        # deterministic mode: the backward gathers over the reverse lists of idx (csr = group_csr(idx, N) of the plan, or
+        # built in backward) instead of scattering with float atomics
+        ctx.det, ctx.csr = deterministic(), csr
         ctx.bf16 = mixed_precision() and min(Cin, C) >= 64 and B * N >= 4096  # the conv on the source points on the bf16 MFMA
         w2 = weight.detach().reshape(C, Cin + 3).contiguous()
         w_dp, ldw, w_f = _dp_f_blocks(w2, ctx.bf16)
@@ -1447,7 +1541,11 @@ class LocalAggregationFused(Function):
         dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
         dsums = torch.empty(2 * C, dtype=torch.float64, device=dev)
         count = ctypes.c_void_p(sums.data_ptr() + 16 * C)
-        wb = int(lib.amc3d_local_aggregation_workspace_bytes(B, C, N, M))
+        csr = None
+        if ctx.det:
+            csr = ctx.csr if ctx.csr is not None else group_csr(idx, N)
+        wb = int(lib.amc3d_local_aggregation_csr_workspace_bytes(B, C, N, M) if ctx.det
+                 else lib.amc3d_local_aggregation_workspace_bytes(B, C, N, M))
         work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
         need_f = ctx.needs_input_grad[0]
         df = torch.empty_like(f) if need_f else None
@@ -1456,6 +1554,13 @@ class LocalAggregationFused(Function):
         work2 = torch.empty(max(wb2, 4), dtype=torch.uint8, device=dev)
 
         def call(phase):
+            if csr is not None:
+                _lib.check(lib.amc3d_local_aggregation_backward_csr_strided(
+                    B, C, N, M, K, int(ctx.relu), _ptr(dpooled), _ptr(ystar), _ptr(arg), _ptr(g_pm), _ptr(idx), _ptr(dp),
+                    _ptr(w_dp), ctx.ldw, _ptr(moments), _ptr(gd), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta),
+                    _ptr(csr[0]), _ptr(csr[1]), _ptr(dg_cm), _ptr(dw_dp), lddw, _ptr(dgamma), _ptr(dbeta), phase, _ptr(dsums),
+                    count, _ptr(work), wb, _stream(f)), "local_aggregation_backward_csr")
+                return
             _lib.check(lib.amc3d_local_aggregation_backward_strided(
                 B, C, N, M, K, int(ctx.relu), _ptr(dpooled), _ptr(ystar), _ptr(arg), _ptr(g_pm), _ptr(idx), _ptr(dp),
                 _ptr(w_dp), ctx.ldw, _ptr(moments), _ptr(gd), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(dg_cm),
@@ -1463,7 +1568,9 @@ class LocalAggregationFused(Function):
                 "local_aggregation_backward")
 
         with torch.cuda.device(dev):
-            with timing.span("local_aggregation_backward", 5 * B * M * C + 8 * B * N * C + 16 * B * M * K, moved=17 * B * M * C + 12 * B * N * C + 16 * B * M * K):
+            with timing.span("local_aggregation_backward_csr" if csr is not None else "local_aggregation_backward",
+                             5 * B * M * C + 8 * B * N * C + 16 * B * M * K,
+                             moved=(17 + (10 + 5 * K if csr is not None else 0)) * B * M * C + 12 * B * N * C + 16 * B * M * K):
                 if ctx.group is None:
                     call(0)
                 else:
@@ -1474,7 +1581,7 @@ class LocalAggregationFused(Function):
                              2.0 * B * N * Cin * C * (1 + int(need_f)), moved=4 * B * N * (Cin + C) * (1 + int(need_f))):
                 _pw_backward_blocks(lib, ctx.bf16, B, Cin, C, N, f, w_f, dg_cm, df, dw_f, lddw_f, work2, wb2)
         dw = (_join_columns(dw_dp, dw_f) if dw is None else dw).view(ctx.wshape)
-        return df, None, None, None, dw, dgamma, dbeta, None, None, None, None
+        return df, None, None, None, dw, dgamma, dbeta, None, None, None, None, None
 
 
 class GroupedConvBN(Function):
@@ -1497,6 +1604,7 @@ class GroupedConvBN(Function):
         dev = f.device
         lib = _lib.load()
         ctx.csr = csr  # (rev_start, rev_edge[, group_csr_dp's stream]) of ops.group_csr, or None: backward then scatters with float atomics
+        ctx.det = deterministic()  # (deterministic mode: backward builds the lists it was not given)
         ctx.bf16 = mixed_precision() and min(Cin, C) >= 64 and B * N >= 4096
         w2 = weight.detach().reshape(C, Cin + 3).contiguous()
         w_dp, ldw, w_f = _dp_f_blocks(w2, ctx.bf16)
@@ -1544,7 +1652,10 @@ class GroupedConvBN(Function):
         lib = _lib.load()
         # SATailActivated hands the gradient over as position-major rows (a (B,C,M,K) view of a (B,M,K,C) buffer): the
         # gather along the reverse lists reads those directly; any other layout is made channel-major and transposed
-        dx1_pm = ctx.csr is not None and dx1.dim() == 4 and dx1.permute(0, 2, 3, 1).is_contiguous() and C > 1
+        csr = ctx.csr
+        if csr is None and ctx.det:  # deterministic mode: always the gather, with lists built here when the plan has none
+            csr = group_csr(idx, N)
+        dx1_pm = csr is not None and dx1.dim() == 4 and dx1.permute(0, 2, 3, 1).is_contiguous() and C > 1
         if not dx1_pm:
             dx1 = dx1.contiguous()
         dg_cm = torch.empty(B, C, N, dtype=torch.float32, device=dev)
@@ -1552,7 +1663,6 @@ class GroupedConvBN(Function):
         dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
         dsums = torch.empty(2 * C, dtype=torch.float64, device=dev)
         count = ctypes.c_void_p(sums.data_ptr() + 16 * C)
-        csr = ctx.csr
         wb = int(lib.amc3d_grouped_conv_bn_csr_workspace_bytes(B, C, N, M, K) if csr is not None
                  else lib.amc3d_local_aggregation_workspace_bytes(B, C, N, M))
         work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
@@ -1790,6 +1900,7 @@ class MaskedRefineDual(Function):
                                                        _ptr(count), _ptr(work), _stream(f)), "masked_refine_forward")
         ctx.save_for_backward(best, mask)
         ctx.gamma = float(gamma)
+        ctx.det = deterministic()
         ctx.mark_non_differentiable(count)
         return out, count
 
@@ -1799,6 +1910,14 @@ class MaskedRefineDual(Function):
         dout = dout.contiguous()
         B, D, n = dout.shape
         df = torch.empty_like(dout)
+        if ctx.det:
+            # the lists of best depend on the predicted ambiguity: built in the step itself, the B*n rows as one cloud
+            rev_start, rev_edge = group_csr(best.view(1, B * n, 1), B * n)
+            with torch.cuda.device(dout.device), timing.span("masked_refine_backward_csr", dout.numel() * 12 + B * n * 9):
+                _lib.check(_lib.load().amc3d_masked_refine_backward_csr(B, D, n, ctx.gamma, _ptr(dout), _ptr(best), _ptr(mask),
+                                                                        _ptr(rev_start), _ptr(rev_edge), _ptr(df), _stream(dout)),
+                           "masked_refine_backward_csr")
+            return df, None, None, None, None, None
         with torch.cuda.device(dout.device), timing.span("masked_refine_backward", dout.numel() * 12):
             _lib.check(_lib.load().amc3d_masked_refine_backward(B, D, n, ctx.gamma, _ptr(dout), _ptr(best), _ptr(mask), _ptr(df),
                                                                 _stream(dout)), "masked_refine_backward")
@@ -1836,6 +1955,7 @@ class SAResidual(Function):
         if keep:
             ctx.save_for_backward(out, fi, fps_idx, w2, *([dup_flag] if dup_flag is not None else []))
         ctx.n, ctx.wshape, ctx.has_bias = N, tuple(weight.shape), bias is not None
+        ctx.det = deterministic()
         ctx.mark_non_differentiable(fps_idx)
         return out
 
@@ -1849,6 +1969,12 @@ class SAResidual(Function):
         dev = dout.device
         need_f, need_w = ctx.needs_input_grad[1], ctx.needs_input_grad[3]
         need_b = ctx.has_bias and ctx.needs_input_grad[4]
+        if ctx.det and need_f:
+            # unique picks take plain stores; duplicate picks (or picks nobody checked) add with float atomics
+            if dup_flag is None:
+                dup_flag = index_duplicates(fps_idx, N)
+            if not torch.cuda.is_current_stream_capturing() and int(dup_flag):
+                raise _no_route("sa_residual_backward", "fps_idx repeats an index")
         g = torch.empty_like(out)
         df = torch.empty(B, Cin, N, dtype=torch.float32, device=dev) if need_f else None
         dw = torch.empty(Cout, Cin, dtype=torch.float32, device=dev) if need_w else None
@@ -1975,6 +2101,10 @@ class LibraryGemmConv(Function):
 
 
 def library_gemm_conv(x, weight, dx_position_major=False):
+    if deterministic():
+        # the BLAS library's reduction order is not this library's to fix: csrc/gemm.hip (fp32) or gemm_bf16.hip (autocast),
+        # both fixed-order
+        return pointwise_conv(x, weight, None, mixed_precision(), dx_position_major)
     return LibraryGemmConv.apply(x, weight, dx_position_major)
 
 

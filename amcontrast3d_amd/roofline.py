@@ -46,6 +46,9 @@ OPERATOR_KERNELS = {
     "bn_act_forward": ("bn_stats", "bn_act_kernel", "bn_fwd_channel"), "bn_act_backward": ("bn_bwd",),
     "bn_max_forward": ("bn_stats", "bn_max"), "bn_max_backward": ("bn_max_bwd", "bn_bwd"),
     "three_interpolate": ("three_interpolate",), "three_interpolate_grad": ("three_interpolate_grad", "scatter_pm"),
+    # deterministic mode (ops.deterministic): the reverse-list gathers that stand in for the float-atomic scatters
+    "local_aggregation_backward_csr": ("lagg_bwd_scatter", "lagg_bwd_gather", "lagg_bwd_apply"),
+    "three_interpolate_grad_csr": ("three_interpolate_grad_csr",), "masked_refine_backward_csr": ("refine_backward_csr",),
     "sa_residual_forward": ("sa_res_fwd",), "sa_residual_backward": ("sa_res_mask", "sa_res_bwd"),
     "cross_entropy_forward": ("ce_forward",), "cross_entropy_backward": ("ce_backward",),
     "furthest_point_sampling": ("fps_kernel",), "knnquery": ("kg_", "knn_"),

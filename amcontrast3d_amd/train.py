@@ -104,7 +104,10 @@ def _cfg(cfg, key, default=None):
 def _graph_pipeline(model, criterion, optimizer, cfg, step_loss, first, clip, extras=0):
     """the GraphPipeline of this (model, optimizer, criterion, batch shape), built from batch `first` at first use"""
     import torch.distributed as tdist
-    key = (id(model), id(optimizer), id(criterion), tuple(first["pos"].shape), tuple(sorted(k for k, v in first.items() if torch.is_tensor(v))), extras)
+    from . import ops
+    # (the mode is part of the key: a graph captured under one mode is never replayed under the other)
+    key = (id(model), id(optimizer), id(criterion), tuple(first["pos"].shape), tuple(sorted(k for k, v in first.items() if torch.is_tensor(v))), extras,
+           ops.deterministic())
     hit = _PIPELINES.get(key)
     if hit is None:
         dev = first["pos"].device
@@ -116,7 +119,6 @@ def _graph_pipeline(model, criterion, optimizer, cfg, step_loss, first, clip, ex
             flat = FlatGradients([p for p in model.parameters() if p.requires_grad], accumulate=False)
             sync_bn = any(isinstance(m, torch.nn.SyncBatchNorm) for m in model.modules())
         # the epoch's device-side bookkeeping (main_AA.py:414-416: cm.update, loss_meter.update) as the tail of the captured step
-        from . import ops
         v = cfg.num_classes + (1 if cfg.ignore_index is not None else 0)
         book = {"cm": torch.zeros(v, v, dtype=torch.int64, device=dev), "invalid": torch.zeros(1, dtype=torch.int64, device=dev),
                 "loss": torch.zeros(1 + extras, dtype=torch.float64, device=dev)}
@@ -138,6 +140,16 @@ def _graph_pipeline(model, criterion, optimizer, cfg, step_loss, first, clip, ex
 
 def _run_epoch(model, train_loader, criterion, optimizer, scheduler, scaler, epoch, cfg, prefetch_depth, device, step_loss,
                extras):
+    """cfg.deterministic (default False): ops.deterministic_mode for the duration of the epoch -- capture, replays and the
+    eager steps alike"""
+    from . import ops
+    with ops.deterministic_mode(bool(_cfg(cfg, "deterministic", False)) or ops.deterministic()):
+        return _run_epoch_body(model, train_loader, criterion, optimizer, scheduler, scaler, epoch, cfg, prefetch_depth, device,
+                               step_loss, extras)
+
+
+def _run_epoch_body(model, train_loader, criterion, optimizer, scheduler, scaler, epoch, cfg, prefetch_depth, device, step_loss,
+                    extras):
     activate()
     from openpoints.utils import ConfusionMatrix
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)

@@ -125,6 +125,16 @@ int amc3d_three_interpolate_add(int b, int c, int m, int n, const float *points,
 int amc3d_three_interpolate_grad(int b, int c, int n, int m, const float *grad_out,
                                  const int *idx, const float *weight, float *grad_points,
                                  void *workspace, size_t workspace_bytes, void *stream);
+/* The same gradient without atomics (deterministic mode), from the reverse lists of idx seen as a query of n points with 3
+ * samples into the m known points: rev_start (b*m + 1), rev_edge (b*n*3) = amc3d_group_csr(b, m, n, 3, idx, ...).
+ * SUMMATION ORDER (part of the contract, shared by the three *_csr gathers of deterministic mode): every target takes its
+ * incoming positions in ascending position order -- the order of its list -- and adds them by sequential fp32 __fadd_rn
+ * starting from +0.0f; a term that is a product is rounded first by __fmul_rn; nothing is reassociated, the work is spread
+ * over channels and targets only.  Here: grad_points[b,ch,t] = sum over p = u*3 + j in t's list of
+ * __fmul_rn(grad_out[b,ch,u], weight[b,u,j]).  Every element of grad_points (b,c,m) is written: a target without incoming
+ * positions gets exactly +0.0f, so the caller need not zero-initialise.  No workspace. */
+int amc3d_three_interpolate_grad_csr(int b, int c, int n, int m, const float *grad_out, const int *idx, const float *weight,
+                                     const int *rev_start, const int *rev_edge, float *grad_points, void *stream);
 
 /* ---- pointops surface --------------------------------------------------------- */
 
@@ -565,6 +575,33 @@ int amc3d_grouped_conv_bn_backward_csr_strided(int b, int cout, int n, int npoin
                                                long lddw, float *dgamma, float *dbeta, int phase, double *dsums,
                                                const double *count_dev, void *workspace, size_t workspace_bytes,
                                                void *stream);
+/* amc3d_local_aggregation_backward without float atomics (deterministic mode): same arguments and outputs, plus the reverse
+ * lists of idx, rev_start (b*n + 1) / rev_edge (b*npoints*nsample) of amc3d_group_csr.  Only the scatter into Q changes:
+ * Q[b,j,c] = the sum, over the positions (m,k) of j's list in list order (ascending m*nsample + k), of dq[b,c,m] where
+ * arg[b,c,m] == k -- dq the ReLU-masked pooled gradient; of the several k at which a padded ball-query row holds j only the
+ * one that equals arg carries it -- by sequential fp32 __fadd_rn from +0.0f (the summation order stated at
+ * amc3d_three_interpolate_grad_csr).  The five per-channel fp64 partial sums, the finalize / apply passes and both
+ * SyncBatchNorm phases are those of the atomic form.  Workspace: amc3d_local_aggregation_csr_workspace_bytes (the atomic
+ * form's plus the point-major (b,npoints,cout) copies of dq and arg that the gather reads). */
+size_t amc3d_local_aggregation_csr_workspace_bytes(int b, int cout, int n, int npoints);
+/* byte offset of Q (b,n,cout) fp32 in the workspace after either backward form (phase 0 or 1): what the order above is checked on */
+size_t amc3d_local_aggregation_workspace_q_offset(int b, int cout, int n, int npoints);
+int amc3d_local_aggregation_backward_csr(int b, int cout, int n, int npoints, int nsample, int relu, const float *dpooled,
+                                         const float *ystar, const unsigned char *arg, const float *g_pm, const int *idx,
+                                         const float *dp, const float *w_dp, const void *moments, const double *gd,
+                                         const float *mean, const float *invstd, const float *gamma, const float *beta,
+                                         const int *rev_start, const int *rev_edge, float *dg_cm, float *dw_dp,
+                                         float *dgamma, float *dbeta, int phase, double *dsums, const double *count,
+                                         void *workspace, size_t workspace_bytes, void *stream);
+int amc3d_local_aggregation_backward_csr_strided(int b, int cout, int n, int npoints, int nsample, int relu,
+                                                 const float *dpooled, const float *ystar, const unsigned char *arg,
+                                                 const float *g_pm, const int *idx, const float *dp,
+                                                 const float *w_dp, long ldw, const void *moments, const double *gd,
+                                                 const float *mean, const float *invstd, const float *gamma,
+                                                 const float *beta, const int *rev_start, const int *rev_edge,
+                                                 float *dg_cm, float *dw_dp, long lddw, float *dgamma, float *dbeta,
+                                                 int phase, double *dsums, const double *count_dev, void *workspace,
+                                                 size_t workspace_bytes, void *stream);
 
 /* ---- tail of a two-layer SetAbstraction block, recomputed instead of materialised -----------------------------
  * BN1 -> ReLU -> Conv2d 1x1 (C1 -> C2) -> BN2 [-> ReLU] -> max over the K = 32 neighbours
@@ -692,6 +729,13 @@ int amc3d_masked_refine_forward(int B, int D, int n, int k, int nbr_stride, cons
                                 int *count, int *workspace, void *stream);
 int amc3d_masked_refine_backward(int B, int D, int n, float gamma, const float *dout, const int *best, const unsigned char *mask,
                                  float *df, void *stream);
+/* The backward without atomics (deterministic mode).  rev_start (B*n + 1), rev_edge (B*n) = amc3d_group_csr(1, B*n, B*n, 1,
+ * best, ...): the rows as one cloud, as the forward sees them.  For element r'*D + d of df: S = the masked elements'
+ * __fmul_rn(gamma, dout[r*D + d]) over the rows r of r''s list in list order (ascending r), sequential __fadd_rn from +0.0f
+ * (the summation order of amc3d_three_interpolate_grad_csr); df = __fadd_rn(direct term, S).  Writes every element. */
+int amc3d_masked_refine_backward_csr(int B, int D, int n, float gamma, const float *dout, const int *best,
+                                     const unsigned char *mask, const int *rev_start, const int *rev_edge, float *df,
+                                     void *stream);
 
 /* y = sigmoid(batch_norm(x)) with batch statistics -- nn.BatchNorm1d -> nn.Sigmoid of the APM towers of AMContrast3D++
  * (openpoints/AMContrast3D/APM/concatenation.py:20-60) -- in the two launches of a plain BatchNorm layer; backward from the saved
