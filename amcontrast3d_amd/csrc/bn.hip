@@ -153,8 +153,9 @@ __device__ __forceinline__ void bn_channel_stats(const BnFused &f, int c, bool w
     m = s_stat[0]; is = s_stat[1];
 }
 
-// y = [relu](bn(x)), elementwise over (B, C, L); 4 elements per thread when L % 4 == 0
-__global__ __launch_bounds__(BN_THREADS) void bn_act_kernel(int C, long L, int relu, const float *__restrict__ x,
+// y = [relu](bn(x)), elementwise over (B, C, L); 4 elements per thread when `vec` (the host's decision: L % 4 == 0 and
+// x, y and res 16-byte aligned)
+__global__ __launch_bounds__(BN_THREADS) void bn_act_kernel(int C, long L, int relu, int vec, const float *__restrict__ x,
                                                             const float *__restrict__ mean,
                                                             const float *__restrict__ invstd,
                                                             const float *__restrict__ gamma,
@@ -169,7 +170,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_act_kernel(int C, long L, int r
     const float *xr = x + (size_t)bc * L;
     float *yr = y + (size_t)bc * L;
     const float *rr = res ? res + (size_t)bc * L : nullptr;  // y = [relu](bn(x) + res): the residual of an InvResMLP block
-    if ((L & 3) == 0) {
+    if (vec) {
         for (long i = ((long)blockIdx.x * BN_THREADS + threadIdx.x) * 4; i < L; i += (long)gridDim.x * BN_THREADS * 4) {
             float4 v = *reinterpret_cast<const float4 *>(xr + i);
             v.x = bn_val(v.x, m, is, g, bt); v.y = bn_val(v.y, m, is, g, bt);
@@ -193,7 +194,8 @@ __global__ __launch_bounds__(BN_THREADS) void bn_act_kernel(int C, long L, int r
 }
 
 // y[b,c,m] = max_k [relu](bn(x[b,c,m,k])), arg[b,c,m] = first k attaining it (torch.max returns the first)
-__global__ __launch_bounds__(BN_THREADS) void bn_max_kernel(int C, int M, int K, int relu, const float *__restrict__ x,
+// (`vec`: K % 4 == 0 and x 16-byte aligned -- the rows are then read four neighbours at a time)
+__global__ __launch_bounds__(BN_THREADS) void bn_max_kernel(int C, int M, int K, int relu, int vec, const float *__restrict__ x,
                                                             const float *__restrict__ mean,
                                                             const float *__restrict__ invstd,
                                                             const float *__restrict__ gamma,
@@ -210,7 +212,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_max_kernel(int C, int M, int K,
     const float *xr = x + ((size_t)bc * M + mi) * K;
     float best = -__builtin_inff();
     int bk = 0;
-    if ((K & 3) == 0) {
+    if (vec) {
         for (int k = 0; k < K; k += 4) {
             const float4 v4 = *reinterpret_cast<const float4 *>(xr + k);
             const float vs[4] = {v4.x, v4.y, v4.z, v4.w};
@@ -643,6 +645,16 @@ static BnSplit bn_split(int B, int C, long Lq)
 
 static int aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
+// bn_act_kernel's 16-byte loop: every row starts on a multiple of 4 elements and every pointer it reads or writes 16 bytes
+// wide is 16-byte aligned (a contiguous view at an odd storage offset is not); otherwise the scalar loop
+static int bn_act_vec(long L, const float *x, const float *y, const float *res)
+{
+    return (L % 4 == 0) && aligned16(x) && aligned16(y) && (!res || aligned16(res));
+}
+
+// the normalise and apply launches put b * C + c on the grid's y axis, which holds 65535 at most
+static bool bn_grid_y_ok(int B, int C) { return (long)B * (long)C <= 65535L; }
+
 // statistics of x (B, C, L): mean, invstd = 1/sqrt(var_biased + eps), var_unbiased (for running_var)
 AMC_API int amc3d_bn_stats(int B, int C, long L, float eps, const float *x, float *mean, float *invstd,
                            float *var_unbiased, void *workspace, size_t workspace_bytes, void *stream_)
@@ -667,10 +679,11 @@ AMC_API int amc3d_bn_act(int B, int C, long L, int relu, const float *x, const f
 {
     if (B <= 0 || C <= 0 || L <= 0) return 0;
     if (!x || !mean || !invstd || !gamma || !beta || !y) return bad_arg("amc3d_bn_act: null pointer");
+    if (!bn_grid_y_ok(B, C)) return bad_arg("amc3d_bn_act: B * C must not exceed 65535");
     const long per_block = BN_THREADS * 4 * 4;
     const int gx = (int)min((L + per_block - 1) / per_block, (long)4096);
-    hipLaunchKernelGGL(bn_act_kernel, dim3(gx, B * C), dim3(BN_THREADS), 0, (hipStream_t)stream, C, L, relu, x, mean,
-                       invstd, gamma, beta, y, BnFused{}, (const float *)nullptr);
+    hipLaunchKernelGGL(bn_act_kernel, dim3(gx, B * C), dim3(BN_THREADS), 0, (hipStream_t)stream, C, L, relu,
+                       bn_act_vec(L, x, y, nullptr), x, mean, invstd, gamma, beta, y, BnFused{}, (const float *)nullptr);
     return launch_status("amc3d_bn_act");
 }
 
@@ -688,8 +701,9 @@ static int launch_bn_max(int B, int C, int M, int K, int relu, const float *x, c
 #undef AMC_BNMAX
         return launch_status("amc3d_bn_max");
     }
-    hipLaunchKernelGGL(bn_max_kernel, dim3(div_up(M, BN_THREADS), B * C), dim3(BN_THREADS), 0, stream, C, M, K, relu, x, mean,
-                       invstd, gamma, beta, y, arg, f);
+    // y and arg are written one element at a time by both kernels: only x is read 16 bytes wide
+    hipLaunchKernelGGL(bn_max_kernel, dim3(div_up(M, BN_THREADS), B * C), dim3(BN_THREADS), 0, stream, C, M, K, relu,
+                       (int)(K % 4 == 0 && aligned16(x)), x, mean, invstd, gamma, beta, y, arg, f);
     return launch_status("amc3d_bn_max");
 }
 
@@ -700,6 +714,7 @@ AMC_API int amc3d_bn_max(int B, int C, int M, int K, int relu, const float *x, c
     if (B <= 0 || C <= 0 || M <= 0) return 0;
     if (K <= 0 || K > 255 || !x || !mean || !invstd || !gamma || !beta || !y || !arg)
         return bad_arg("amc3d_bn_max: bad argument (K must be in 1..255)");
+    if (!bn_grid_y_ok(B, C)) return bad_arg("amc3d_bn_max: B * C must not exceed 65535");
     return launch_bn_max(B, C, M, K, relu, x, mean, invstd, gamma, beta, y, arg, BnFused{}, (hipStream_t)stream);
 }
 
@@ -726,6 +741,7 @@ AMC_API int amc3d_bn_forward(int B, int C, long L, int K, int relu, float eps, f
                            num_batches_tracked);
         return launch_status("amc3d_bn_forward");
     }
+    if (!bn_grid_y_ok(B, C)) return bad_arg("amc3d_bn_forward: B * C must not exceed 65535");
     hipLaunchKernelGGL(bn_stats_kernel, dim3(sp.nchunks, C), dim3(BN_THREADS), 0, stream, B, C, L, sp, vec, x,
                        (double *)workspace);
     BnFused f{};
@@ -740,8 +756,8 @@ AMC_API int amc3d_bn_forward(int B, int C, long L, int K, int relu, float eps, f
     if (K == 0) {
         const long per_block = BN_THREADS * 4 * 4;
         const int gx = (int)min((L + per_block - 1) / per_block, (long)4096);
-        hipLaunchKernelGGL(bn_act_kernel, dim3(gx, B * C), dim3(BN_THREADS), 0, stream, C, L, relu, x, mean, invstd, gamma,
-                           beta, y, f, (const float *)nullptr);
+        hipLaunchKernelGGL(bn_act_kernel, dim3(gx, B * C), dim3(BN_THREADS), 0, stream, C, L, relu, bn_act_vec(L, x, y, nullptr),
+                           x, mean, invstd, gamma, beta, y, f, (const float *)nullptr);
         st = launch_status("amc3d_bn_forward");
     } else {
         st = launch_bn_max(B, C, (int)(L / K), K, relu, x, mean, invstd, gamma, beta, y, arg, f, stream);
@@ -776,6 +792,7 @@ AMC_API int amc3d_bn_backward(int B, int C, long L, int K, int relu, const float
                            gamma, beta, dgamma, dbeta, dx);
         return launch_status("amc3d_bn_backward");
     }
+    if (!bn_grid_y_ok(B, C)) return bad_arg("amc3d_bn_backward: B * C must not exceed 65535");
     hipLaunchKernelGGL(bn_bwd_stats_kernel, dim3(nchunks, C), dim3(BN_THREADS), 0, stream, mode, B, C, L, K, relu, sp, vec, x,
                        dy, arg, mean, invstd, gamma, beta, partial, (const float *)nullptr);
     const long per_block = BN_THREADS * 16;
@@ -797,8 +814,7 @@ AMC_API int amc3d_bn_residual_forward(int B, int C, long L, float eps, float mom
     if (!x || !res || !gamma || !beta || !y || !mean || !invstd || !var_unbiased || !workspace ||
         workspace_bytes < amc3d_bn_workspace_bytes(C) || (running_mean && (!running_var || !num_batches_tracked)))
         return bad_arg("amc3d_bn_residual_forward: bad argument");
-    if ((L % 4 == 0) && !(aligned16(x) && aligned16(res) && aligned16(y)))
-        return bad_arg("amc3d_bn_residual_forward: x, res and y must be 16-byte aligned");
+    if (!bn_grid_y_ok(B, C)) return bad_arg("amc3d_bn_residual_forward: B * C must not exceed 65535");
     hipStream_t stream = (hipStream_t)stream_;
     const BnSplit sp = bn_split(B, C, L);
     const int vec = (L % 4 == 0) && aligned16(x);
@@ -814,8 +830,8 @@ AMC_API int amc3d_bn_residual_forward(int B, int C, long L, float eps, float mom
     f.running_mean = running_mean; f.running_var = running_var; f.tracked = num_batches_tracked;
     const long per_block = BN_THREADS * 4 * 4;
     const int gx = (int)min((L + per_block - 1) / per_block, (long)4096);
-    hipLaunchKernelGGL(bn_act_kernel, dim3(gx, B * C), dim3(BN_THREADS), 0, stream, C, L, 1, x, mean, invstd, gamma, beta, y, f,
-                       res);
+    hipLaunchKernelGGL(bn_act_kernel, dim3(gx, B * C), dim3(BN_THREADS), 0, stream, C, L, 1, bn_act_vec(L, x, y, res), x, mean,
+                       invstd, gamma, beta, y, f, res);
     if (running_mean && momentum < 0.f)
         hipLaunchKernelGGL(bn_running_kernel, dim3(1), dim3(1024), 0, stream, C, momentum, mean, var_unbiased, running_mean,
                            running_var, num_batches_tracked);
@@ -832,6 +848,7 @@ AMC_API int amc3d_bn_residual_backward(int B, int C, long L, const float *x, con
     if (!x || !y || !dy || !mean || !invstd || !gamma || !beta || !dx || !dres || !dgamma || !dbeta || !workspace ||
         workspace_bytes < amc3d_bn_workspace_bytes(C))
         return bad_arg("amc3d_bn_residual_backward: bad argument");
+    if (!bn_grid_y_ok(B, C)) return bad_arg("amc3d_bn_residual_backward: B * C must not exceed 65535");
     hipStream_t stream = (hipStream_t)stream_;
     const BnSplit sp = bn_split(B, C, L);
     const int vec = (L % 4 == 0) && aligned16(x) && aligned16(y) && aligned16(dy) && aligned16(dx) && aligned16(dres) &&
@@ -859,7 +876,7 @@ AMC_API int amc3d_bn_sigmoid_forward(int B, int C, long L, float eps, float mome
     if (!x || !gamma || !beta || !y || !mean || !invstd || !var_unbiased || !workspace ||
         workspace_bytes < amc3d_bn_workspace_bytes(C) || (running_mean && (!running_var || !num_batches_tracked)))
         return bad_arg("amc3d_bn_sigmoid_forward: bad argument");
-    if ((L % 4 == 0) && !(aligned16(x) && aligned16(y))) return bad_arg("amc3d_bn_sigmoid_forward: x and y must be 16-byte aligned");
+    if (!bn_grid_y_ok(B, C)) return bad_arg("amc3d_bn_sigmoid_forward: B * C must not exceed 65535");
     hipStream_t stream = (hipStream_t)stream_;
     const BnSplit sp = bn_split(B, C, L);
     const int vec = (L % 4 == 0) && aligned16(x);
@@ -875,8 +892,8 @@ AMC_API int amc3d_bn_sigmoid_forward(int B, int C, long L, float eps, float mome
     f.running_mean = running_mean; f.running_var = running_var; f.tracked = num_batches_tracked;
     const long per_block = BN_THREADS * 4 * 4;
     const int gx = (int)min((L + per_block - 1) / per_block, (long)4096);
-    hipLaunchKernelGGL(bn_act_kernel, dim3(gx, B * C), dim3(BN_THREADS), 0, stream, C, L, 2, x, mean, invstd, gamma, beta, y, f,
-                       (const float *)nullptr);
+    hipLaunchKernelGGL(bn_act_kernel, dim3(gx, B * C), dim3(BN_THREADS), 0, stream, C, L, 2, bn_act_vec(L, x, y, nullptr), x, mean,
+                       invstd, gamma, beta, y, f, (const float *)nullptr);
     if (running_mean && momentum < 0.f)
         hipLaunchKernelGGL(bn_running_kernel, dim3(1), dim3(1024), 0, stream, C, momentum, mean, var_unbiased, running_mean,
                            running_var, num_batches_tracked);
@@ -891,6 +908,7 @@ AMC_API int amc3d_bn_sigmoid_backward(int B, int C, long L, const float *x, cons
     if (!x || !y || !dy || !mean || !invstd || !gamma || !beta || !dx || !dgamma || !dbeta || !workspace ||
         workspace_bytes < amc3d_bn_workspace_bytes(C))
         return bad_arg("amc3d_bn_sigmoid_backward: bad argument");
+    if (!bn_grid_y_ok(B, C)) return bad_arg("amc3d_bn_sigmoid_backward: B * C must not exceed 65535");
     hipStream_t stream = (hipStream_t)stream_;
     const BnSplit sp = bn_split(B, C, L);
     const int vec = (L % 4 == 0) && aligned16(x) && aligned16(y) && aligned16(dy) && aligned16(dx) && L < (1L << 31);
@@ -953,6 +971,7 @@ AMC_API int amc3d_bn_forward_synced(int B, int C, long L, int K, int relu, float
     if (!x || !sums_count || !gamma || !beta || !y || !mean || !invstd || !var_unbiased || K < 0 || K > 255 ||
         (K > 0 && (!arg || L % K != 0)) || (running_mean && (!running_var || !num_batches_tracked)))
         return bad_arg("amc3d_bn_forward_synced: bad argument");
+    if (!bn_grid_y_ok(B, C)) return bad_arg("amc3d_bn_forward_synced: B * C must not exceed 65535");
     hipStream_t stream = (hipStream_t)stream_;
     BnFused f{};
     f.partial = sums_count;
@@ -966,8 +985,8 @@ AMC_API int amc3d_bn_forward_synced(int B, int C, long L, int K, int relu, float
     if (K == 0) {
         const long per_block = BN_THREADS * 4 * 4;
         const int gx = (int)min((L + per_block - 1) / per_block, (long)4096);
-        hipLaunchKernelGGL(bn_act_kernel, dim3(gx, B * C), dim3(BN_THREADS), 0, stream, C, L, relu, x, mean, invstd, gamma,
-                           beta, y, f, (const float *)nullptr);
+        hipLaunchKernelGGL(bn_act_kernel, dim3(gx, B * C), dim3(BN_THREADS), 0, stream, C, L, relu, bn_act_vec(L, x, y, nullptr),
+                           x, mean, invstd, gamma, beta, y, f, (const float *)nullptr);
         st = launch_status("amc3d_bn_forward_synced");
     } else {
         st = launch_bn_max(B, C, (int)(L / K), K, relu, x, mean, invstd, gamma, beta, y, arg, f, stream);
@@ -1010,6 +1029,7 @@ AMC_API int amc3d_bn_backward_synced(int B, int C, long L, int K, int relu, cons
     if (B <= 0 || C <= 0 || L <= 0) return 0;
     if (!x || !dy || !mean || !invstd || !gamma || !beta || !dsums || !count || !dx || K <= 0 || (arg && L % K != 0))
         return bad_arg("amc3d_bn_backward_synced: bad argument");
+    if (!bn_grid_y_ok(B, C)) return bad_arg("amc3d_bn_backward_synced: B * C must not exceed 65535");
     const int mode = arg ? 1 : 0;
     const int vec = (L % 4 == 0) && (K % 4 == 0 || !mode) && aligned16(x) && aligned16(dy) && aligned16(dx) && L < (1L << 31);
     const long per_block = BN_THREADS * 16;

@@ -125,11 +125,16 @@ def conv_bn_block(blk):
     return conv, bn, relu
 
 
+def _bn_grid_fits(x):
+    """the BatchNorm kernels put batch * channels on the grid's y axis (csrc/bn.hip refuses more than 65535)"""
+    return x.dim() >= 2 and x.shape[0] * x.shape[1] <= 65535
+
+
 def _fusable_bn(bn, x):
-    """plain training-mode BatchNorm1d/2d on a contiguous fp32 GPU tensor (SyncBatchNorm, eval mode and
-    other norms take the ordinary torch modules)"""
+    """plain training-mode BatchNorm1d/2d on a contiguous fp32 GPU tensor (SyncBatchNorm, eval mode, other norms
+    and a batch * channels beyond the kernels' grid take the ordinary torch modules)"""
     return (type(bn) in (nn.BatchNorm1d, nn.BatchNorm2d) and bn.training and bn.affine and bn.track_running_stats
-            and x.is_cuda and x.dtype == torch.float32)
+            and x.is_cuda and x.dtype == torch.float32 and _bn_grid_fits(x))
 
 
 def _eval_bn(bn, x):
@@ -137,14 +142,14 @@ def _eval_bn(bn, x):
     the fused kernels with the running statistics (ops.bn_eval)"""
     return (isinstance(bn, nn.modules.batchnorm._BatchNorm) and not bn.training and bn.affine
             and bn.track_running_stats and bn.running_mean is not None and x.is_cuda and x.dtype == torch.float32
-            and not torch.is_grad_enabled())
+            and not torch.is_grad_enabled() and _bn_grid_fits(x))
 
 
 def _synced_bn_group(bn, x):
     """process group of a training-mode nn.SyncBatchNorm whose statistics really span several ranks (then the fused
     kernels exchange their per-channel sums: ops.SyncBatchNormFused), else None"""
     if not (type(bn) is nn.SyncBatchNorm and bn.training and bn.affine and bn.track_running_stats and x.is_cuda
-            and x.dtype == torch.float32 and dist.is_available() and dist.is_initialized()):
+            and x.dtype == torch.float32 and _bn_grid_fits(x) and dist.is_available() and dist.is_initialized()):
         return None
     group = bn.process_group if bn.process_group is not None else dist.group.WORLD
     return group if dist.get_world_size(group) > 1 or _FORCE_SYNCED_BN else None
