@@ -12,9 +12,18 @@
 // Layout is the reference's channel-major (B, C, L), L = M*K contiguous; statistics are over (B, L) per
 // channel, accumulated in fp64 (sums of up to 1.5M fp32 values), normalisation as PyTorch writes it:
 // ((x - mean) * invstd) * gamma + beta with the biased variance (torch.nn.BatchNorm semantics).
-#include "common.h"
+//
+// The arithmetic itself -- sums to mean / invstd / unbiased variance, the exponential running update, the normalisation --
+// is bn_math.h's bn_moments, bn_running_update and bn_val, shared with sa_tail.hip and lagg.hip.  The host half writes the
+// launch sequence once (bn_launch_stats, bn_fused, bn_launch_normalise, bn_bwd_vec, bn_launch_bwd_stats,
+// bn_launch_bwd_apply; bn_forward_two / bn_backward_two chain them); each amc3d_bn_* entry point is its argument check plus
+// calls of these, and each route rule is stated at the helper that owns it.
+#include "bn_math.h"
 
 namespace amc {
+
+// what follows the normalisation.  With `ymask` (backward) BN_RELU means "mask from the layer's output y", not from bn(x).
+enum BnAct : int { BN_NONE = 0, BN_RELU = 1, BN_SIGMOID = 2 };
 
 constexpr int BN_THREADS = 256;
 
@@ -83,20 +92,12 @@ __global__ void bn_finalize_kernel(int C, int nchunks, double count, float eps, 
         s1 += partial[((size_t)c * nchunks + k) * 2 + 0];
         s2 += partial[((size_t)c * nchunks + k) * 2 + 1];
     }
-    const double m = s1 / count;
-    double var = s2 / count - m * m;
-    if (var < 0.0) var = 0.0;
-    mean[c] = (float)m;
-    invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-    var_unbiased[c] = (float)(count > 1.0 ? var * count / (count - 1.0) : var);
+    float mf, isf, vu;
+    bn_moments(s1, s2, count, eps, mf, isf, vu);
+    mean[c] = mf; invstd[c] = isf; var_unbiased[c] = vu;
 }
 
 __device__ __forceinline__ float bn_sigmoid(float v) { return __fdiv_rn(1.f, __fadd_rn(1.f, expf(-v))); }
-
-__device__ __forceinline__ float bn_val(float x, float mean, float invstd, float gamma, float beta)
-{
-    return __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(x, mean), invstd), gamma), beta);
-}
 
 // When `partial` is set, the consumer kernels derive mean / invstd from the statistics kernel's partial sums
 // themselves (<= 64 pairs per channel: one wave, one LDS broadcast) instead of waiting for a separate finalize
@@ -133,19 +134,12 @@ __device__ __forceinline__ void bn_channel_stats(const BnFused &f, int c, bool w
         bn_partial_sums(f.partial, c, f.nchunks, s1, s2);
         if (threadIdx.x == 0) {
             const double cnt = f.count_dev ? *f.count_dev : f.count;
-            const double mu = s1 / cnt;
-            double var = s2 / cnt - mu * mu;
-            if (var < 0.0) var = 0.0;
-            const float mf = (float)mu, isf = (float)(1.0 / sqrt(var + (double)f.eps));
+            float mf, isf, vu;
+            bn_moments(s1, s2, cnt, f.eps, mf, isf, vu);
             s_stat[0] = mf; s_stat[1] = isf;
             if (writer) {
-                const float vu = (float)(cnt > 1.0 ? var * cnt / (cnt - 1.0) : var);
                 f.mean_out[c] = mf; f.invstd_out[c] = isf; f.var_out[c] = vu;
-                if (f.running_mean && f.momentum >= 0.f) {  // running.mul_(1 - m).add_(batch, alpha=m)
-                    f.running_mean[c] = f.running_mean[c] * (1.f - f.momentum) + f.momentum * mf;
-                    f.running_var[c] = f.running_var[c] * (1.f - f.momentum) + f.momentum * vu;
-                    if (c == 0 && f.tracked) *f.tracked += 1;
-                }
+                bn_running_update(c, f.momentum, mf, vu, f.running_mean, f.running_var, f.tracked);
             }
         }
     }
@@ -155,7 +149,7 @@ __device__ __forceinline__ void bn_channel_stats(const BnFused &f, int c, bool w
 
 // y = [relu](bn(x)), elementwise over (B, C, L); 4 elements per thread when `vec` (the host's decision: L % 4 == 0 and
 // x, y and res 16-byte aligned)
-__global__ __launch_bounds__(BN_THREADS) void bn_act_kernel(int C, long L, int relu, int vec, const float *__restrict__ x,
+__global__ __launch_bounds__(BN_THREADS) void bn_act_kernel(int C, long L, int act, int vec, const float *__restrict__ x,
                                                             const float *__restrict__ mean,
                                                             const float *__restrict__ invstd,
                                                             const float *__restrict__ gamma,
@@ -179,23 +173,23 @@ __global__ __launch_bounds__(BN_THREADS) void bn_act_kernel(int C, long L, int r
                 const float4 r4 = *reinterpret_cast<const float4 *>(rr + i);
                 v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w;
             }
-            if (relu == 2) {  // sigmoid (the APM towers of AMContrast3D++: Linear -> BatchNorm1d -> Sigmoid)
+            if (act == BN_SIGMOID) {  // sigmoid (the APM towers of AMContrast3D++: Linear -> BatchNorm1d -> Sigmoid)
                 v.x = bn_sigmoid(v.x); v.y = bn_sigmoid(v.y); v.z = bn_sigmoid(v.z); v.w = bn_sigmoid(v.w);
-            } else if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+            } else if (act) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
             *reinterpret_cast<float4 *>(yr + i) = v;
         }
     } else {
         for (long i = (long)blockIdx.x * BN_THREADS + threadIdx.x; i < L; i += (long)gridDim.x * BN_THREADS) {
             float v = bn_val(xr[i], m, is, g, bt);
             if (rr) v += rr[i];
-            yr[i] = relu == 2 ? bn_sigmoid(v) : (relu ? fmaxf(v, 0.f) : v);
+            yr[i] = act == BN_SIGMOID ? bn_sigmoid(v) : (act ? fmaxf(v, 0.f) : v);
         }
     }
 }
 
 // y[b,c,m] = max_k [relu](bn(x[b,c,m,k])), arg[b,c,m] = first k attaining it (torch.max returns the first)
 // (`vec`: K % 4 == 0 and x 16-byte aligned -- the rows are then read four neighbours at a time)
-__global__ __launch_bounds__(BN_THREADS) void bn_max_kernel(int C, int M, int K, int relu, int vec, const float *__restrict__ x,
+__global__ __launch_bounds__(BN_THREADS) void bn_max_kernel(int C, int M, int K, int act, int vec, const float *__restrict__ x,
                                                             const float *__restrict__ mean,
                                                             const float *__restrict__ invstd,
                                                             const float *__restrict__ gamma,
@@ -219,14 +213,14 @@ __global__ __launch_bounds__(BN_THREADS) void bn_max_kernel(int C, int M, int K,
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float v = bn_val(vs[j], m, is, g, bt);
-                if (relu) v = fmaxf(v, 0.f);
+                if (act) v = fmaxf(v, 0.f);
                 if (v > best) { best = v; bk = k + j; }
             }
         }
     } else {
         for (int k = 0; k < K; ++k) {
             float v = bn_val(xr[k], m, is, g, bt);
-            if (relu) v = fmaxf(v, 0.f);
+            if (act) v = fmaxf(v, 0.f);
             if (v > best) { best = v; bk = k; }
         }
     }
@@ -238,7 +232,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_max_kernel(int C, int M, int K,
 // per instruction instead of 64 separate 128-byte rows; the row arg-max is combined across the LPR lanes keeping
 // the first index among equal values (torch.max semantics).
 template <int LPR>
-__global__ __launch_bounds__(BN_THREADS) void bn_max_coop_kernel(int C, int M, int relu, const float *__restrict__ x,
+__global__ __launch_bounds__(BN_THREADS) void bn_max_coop_kernel(int C, int M, int act, const float *__restrict__ x,
                                                                  const float *__restrict__ mean,
                                                                  const float *__restrict__ invstd,
                                                                  const float *__restrict__ gamma,
@@ -262,7 +256,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_max_coop_kernel(int C, int M, i
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float v = bn_val(vs[j], m, is, g, bt);
-            if (relu) v = fmaxf(v, 0.f);
+            if (act) v = fmaxf(v, 0.f);
             if (v > best) { best = v; bk = sg * 4 + j; }
         }
 #pragma unroll
@@ -281,10 +275,10 @@ __global__ __launch_bounds__(BN_THREADS) void bn_max_coop_kernel(int C, int M, i
 
 // ---- backward statistics: per channel  Sa = sum dq,  Sb = sum dq * xhat  (dq = upstream gradient w.r.t. the
 // BN output, after the ReLU mask resp. routed through the arg-max).  partial layout as in bn_stats.
-// mode 0: act.  dq = dy * (relu ? bn(x) > 0 : 1) over (B, C, L)
-// mode 1: max.  dq is nonzero only at the arg-max: dq = g[b,c,m] * (relu ? y > 0 : 1), xhat at the arg-max
+// mode 0: act.  dq = dy * (act ? bn(x) > 0 : 1) over (B, C, L)
+// mode 1: max.  dq is nonzero only at the arg-max: dq = g[b,c,m] * (act ? y > 0 : 1), xhat at the arg-max
 __global__ __launch_bounds__(BN_THREADS) void bn_bwd_stats_kernel(
-    int mode, int B, int C, long L, int K, int relu, BnSplit sp, int vec, const float *__restrict__ x,
+    int mode, int B, int C, long L, int K, int act, BnSplit sp, int vec, const float *__restrict__ x,
     const float *__restrict__ dy, const unsigned char *__restrict__ arg, const float *__restrict__ mean,
     const float *__restrict__ invstd, const float *__restrict__ gamma, const float *__restrict__ beta,
     double *__restrict__ partial, const float *__restrict__ ymask)
@@ -296,14 +290,14 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_stats_kernel(
     const long Lq = mode == 0 ? L : L / K;  // positions carrying a gradient per (b, c)
     auto term = [&](float d, float xv) {
         const float xh = __fmul_rn(__fsub_rn(xv, m), is);
-        if (relu && !(__fadd_rn(__fmul_rn(xh, g), bt) > 0.f)) d = 0.f;
+        if (act && !(__fadd_rn(__fmul_rn(xh, g), bt) > 0.f)) d = 0.f;
         sa += (double)d;
         sb += (double)d * (double)xh;
     };
     // ymask (mode 0): the layer's OUTPUT y = relu(bn(x) + residual); the ReLU passed where y > 0
     auto term_y = [&](float d, float xv, float yv) {
         const float xh = __fmul_rn(__fsub_rn(xv, m), is);
-        if (relu == 2) d = d * (yv * (1.f - yv));  // sigmoid: dy * y (1 - y), y = the layer's output
+        if (act == BN_SIGMOID) d = d * (yv * (1.f - yv));  // sigmoid: dy * y (1 - y), y = the layer's output
         else if (!(yv > 0.f)) d = 0.f;
         sa += (double)d;
         sb += (double)d * (double)xh;
@@ -346,7 +340,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_stats_kernel(
 
 // dx = gamma * invstd * (dq - mean(dq) - xhat * mean(dq * xhat))   (training-mode BN backward)
 __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply_kernel(
-    int mode, int C, long L, int K, int relu, int vec, const float *__restrict__ x, const float *__restrict__ dy,
+    int mode, int C, long L, int K, int act, int vec, const float *__restrict__ x, const float *__restrict__ dy,
     const unsigned char *__restrict__ arg, const float *__restrict__ mean, const float *__restrict__ invstd,
     const float *__restrict__ gamma, const float *__restrict__ beta, const double *__restrict__ partial, int nchunks,
     double count, const double *__restrict__ count_dev, float *__restrict__ dgamma, float *__restrict__ dbeta,
@@ -374,7 +368,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply_kernel(
     float *dr = dx + (size_t)bc * L;
     auto one = [&](float xv, float d) {
         const float xh = __fmul_rn(__fsub_rn(xv, m), is);
-        if (relu && !(__fadd_rn(__fmul_rn(xh, g), bt) > 0.f)) d = 0.f;
+        if (act && !(__fadd_rn(__fmul_rn(xh, g), bt) > 0.f)) d = 0.f;
         return gi * (d - ma - xh * mb);
     };
     if (ymask) {  // mode 0 with a residual: mask from the layer's output, the masked gradient is also the residual's
@@ -386,7 +380,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply_kernel(
                 const float4 x4 = *reinterpret_cast<const float4 *>(xr + i);
                 const float4 y4 = *reinterpret_cast<const float4 *>(yr + i);
                 float4 d4 = *reinterpret_cast<const float4 *>(dyr + i);
-                if (relu == 2) {
+                if (act == BN_SIGMOID) {
                     d4.x *= y4.x * (1.f - y4.x); d4.y *= y4.y * (1.f - y4.y); d4.z *= y4.z * (1.f - y4.z); d4.w *= y4.w * (1.f - y4.w);
                 } else {
                     if (!(y4.x > 0.f)) d4.x = 0.f;
@@ -401,7 +395,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply_kernel(
             }
         } else {
             for (long i = (long)blockIdx.x * BN_THREADS + threadIdx.x; i < L; i += (long)gridDim.x * BN_THREADS) {
-                const float d = relu == 2 ? dyr[i] * (yr[i] * (1.f - yr[i])) : (yr[i] > 0.f ? dyr[i] : 0.f);
+                const float d = act == BN_SIGMOID ? dyr[i] * (yr[i] * (1.f - yr[i])) : (yr[i] > 0.f ? dyr[i] : 0.f);
                 if (dres) rr[i] = d;
                 dr[i] = one_y(xr[i], d);
             }
@@ -460,7 +454,7 @@ __device__ __forceinline__ void block_sum2_f64(double &a, double &b, double (*s_
     for (int w = 0; w < BNC_THREADS / 64; ++w) { a += s_buf[w][0]; b += s_buf[w][1]; }
 }
 
-__global__ __launch_bounds__(BNC_THREADS) void bn_fwd_channel_kernel(int B, int C, long L, int relu, int vec, float eps,
+__global__ __launch_bounds__(BNC_THREADS) void bn_fwd_channel_kernel(int B, int C, long L, int act, int vec, float eps,
                                                                       float momentum, const float *__restrict__ x,
                                                                       const float *__restrict__ gamma,
                                                                       const float *__restrict__ beta, float *__restrict__ y,
@@ -490,19 +484,11 @@ __global__ __launch_bounds__(BNC_THREADS) void bn_fwd_channel_kernel(int B, int 
     }
     block_sum2_f64(s1, s2, s_buf);
     if (threadIdx.x == 0) {
-        const double cnt = (double)B * (double)L;
-        const double mu = s1 / cnt;
-        double var = s2 / cnt - mu * mu;
-        if (var < 0.0) var = 0.0;
-        const float mf = (float)mu, isf = (float)(1.0 / sqrt(var + (double)eps));
-        const float vu = (float)(cnt > 1.0 ? var * cnt / (cnt - 1.0) : var);
+        float mf, isf, vu;
+        bn_moments(s1, s2, (double)B * (double)L, eps, mf, isf, vu);
         s_stat[0] = mf; s_stat[1] = isf;
         mean_out[c] = mf; invstd_out[c] = isf; var_out[c] = vu;
-        if (running_mean && momentum >= 0.f) {
-            running_mean[c] = running_mean[c] * (1.f - momentum) + momentum * mf;
-            running_var[c] = running_var[c] * (1.f - momentum) + momentum * vu;
-            if (c == 0 && tracked) *tracked += 1;
-        }
+        bn_running_update(c, momentum, mf, vu, running_mean, running_var, tracked);
     }
     __syncthreads();
     const float m = s_stat[0], is = s_stat[1], g = gamma[c], bt = beta[c];
@@ -514,19 +500,19 @@ __global__ __launch_bounds__(BNC_THREADS) void bn_fwd_channel_kernel(int B, int 
                 float4 v = *reinterpret_cast<const float4 *>(xr + i);
                 v.x = bn_val(v.x, m, is, g, bt); v.y = bn_val(v.y, m, is, g, bt);
                 v.z = bn_val(v.z, m, is, g, bt); v.w = bn_val(v.w, m, is, g, bt);
-                if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+                if (act) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
                 *reinterpret_cast<float4 *>(yr + i) = v;
             }
         } else {
             for (long i = threadIdx.x; i < L; i += BNC_THREADS) {
                 const float v = bn_val(xr[i], m, is, g, bt);
-                yr[i] = relu ? fmaxf(v, 0.f) : v;
+                yr[i] = act ? fmaxf(v, 0.f) : v;
             }
         }
     }
 }
 
-__global__ __launch_bounds__(BNC_THREADS) void bn_bwd_channel_kernel(int B, int C, long L, int relu, int vec,
+__global__ __launch_bounds__(BNC_THREADS) void bn_bwd_channel_kernel(int B, int C, long L, int act, int vec,
                                                                       const float *__restrict__ x, const float *__restrict__ dy,
                                                                       const float *__restrict__ mean, const float *__restrict__ invstd,
                                                                       const float *__restrict__ gamma, const float *__restrict__ beta,
@@ -539,7 +525,7 @@ __global__ __launch_bounds__(BNC_THREADS) void bn_bwd_channel_kernel(int B, int 
     double sa = 0.0, sb = 0.0;
     auto term = [&](float d, float xv) {
         const float xh = __fmul_rn(__fsub_rn(xv, m), is);
-        if (relu && !(__fadd_rn(__fmul_rn(xh, g), bt) > 0.f)) d = 0.f;
+        if (act && !(__fadd_rn(__fmul_rn(xh, g), bt) > 0.f)) d = 0.f;
         sa += (double)d;
         sb += (double)d * (double)xh;
     };
@@ -561,7 +547,7 @@ __global__ __launch_bounds__(BNC_THREADS) void bn_bwd_channel_kernel(int B, int 
     if (threadIdx.x == 0) { dbeta[c] = (float)sa; dgamma[c] = (float)sb; }
     auto one = [&](float xv, float d) {
         const float xh = __fmul_rn(__fsub_rn(xv, m), is);
-        if (relu && !(__fadd_rn(__fmul_rn(xh, g), bt) > 0.f)) d = 0.f;
+        if (act && !(__fadd_rn(__fmul_rn(xh, g), bt) > 0.f)) d = 0.f;
         return gi * (d - ma - xh * mb);
     };
     for (int b = 0; b < B; ++b) {
@@ -643,7 +629,7 @@ static BnSplit bn_split(int B, int C, long Lq)
     return sp;
 }
 
-static int aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+static int aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }  // (a null pointer counts as aligned)
 
 // bn_act_kernel's 16-byte loop: every row starts on a multiple of 4 elements and every pointer it reads or writes 16 bytes
 // wide is 16-byte aligned (a contiguous view at an odd storage offset is not); otherwise the scalar loop
@@ -655,6 +641,138 @@ static int bn_act_vec(long L, const float *x, const float *y, const float *res)
 // the normalise and apply launches put b * C + c on the grid's y axis, which holds 65535 at most
 static bool bn_grid_y_ok(int B, int C) { return (long)B * (long)C <= 65535L; }
 
+// ---- the launch sequence of a training-mode layer, once.  The entry points below are their argument checks plus two or
+// three of these; `who` is the entry point's name for the error text.
+
+// Statistics stage: {sum, sumsq} partials of x (B, C, L) into the workspace.  16-byte loads when L % 4 == 0 and x is aligned.
+static BnSplit bn_launch_stats(int B, int C, long L, const float *x, void *workspace, hipStream_t stream)
+{
+    const BnSplit sp = bn_split(B, C, L);
+    hipLaunchKernelGGL(bn_stats_kernel, dim3(sp.nchunks, C), dim3(BN_THREADS), 0, stream, B, C, L, sp,
+                       (int)((L % 4 == 0) && aligned16(x)), x, (double *)workspace);
+    return sp;
+}
+
+// What the normalise stage needs to finish the statistics itself: the partials (local: the workspace with the host's count;
+// cross-rank: 2C sums as one "chunk" with the count in device memory), where to publish them, and the running buffers.
+static BnFused bn_fused(const double *partial, int nchunks, double count, const double *count_dev, float eps, float momentum,
+                        float *mean, float *invstd, float *var_unbiased, float *running_mean, float *running_var,
+                        long long *tracked)
+{
+    return BnFused{partial, nchunks, count, count_dev, eps, momentum, mean, invstd, var_unbiased, running_mean, running_var, tracked};
+}
+
+// y = act(bn(x) [+ res]) over (B, C, L); the 16-byte loop by bn_act_vec, `res` included when present
+static int launch_bn_act(const char *who, int B, int C, long L, int act, const float *x, const float *mean, const float *invstd,
+                         const float *gamma, const float *beta, float *y, const BnFused &f, const float *res, hipStream_t stream)
+{
+    const long per_block = BN_THREADS * 4 * 4;
+    const int gx = (int)min((L + per_block - 1) / per_block, (long)4096);
+    hipLaunchKernelGGL(bn_act_kernel, dim3(gx, B * C), dim3(BN_THREADS), 0, stream, C, L, act, bn_act_vec(L, x, y, res), x, mean,
+                       invstd, gamma, beta, y, f, res);
+    return launch_status(who);
+}
+
+static int launch_bn_max(int B, int C, int M, int K, int act, const float *x, const float *mean, const float *invstd,
+                         const float *gamma, const float *beta, float *y, unsigned char *arg, const BnFused &f,
+                         hipStream_t stream)
+{
+    const int lpr = K / 4;
+    if (K % 4 == 0 && (lpr == 2 || lpr == 4 || lpr == 8 || lpr == 16) && aligned16(x)) {
+        const int gx = (int)min((long)div_up((long)M * lpr, BN_THREADS * 4), 65535L);
+#define AMC_BNMAX(N)                                                                                                \
+    hipLaunchKernelGGL(bn_max_coop_kernel<N>, dim3(gx, B * C), dim3(BN_THREADS), 0, stream, C, M, act, x, mean, invstd, \
+                       gamma, beta, y, arg, f)
+        if (lpr == 2) AMC_BNMAX(2); else if (lpr == 4) AMC_BNMAX(4); else if (lpr == 8) AMC_BNMAX(8); else AMC_BNMAX(16);
+#undef AMC_BNMAX
+        return launch_status("amc3d_bn_max");
+    }
+    // y and arg are written one element at a time by both kernels: only x is read 16 bytes wide
+    hipLaunchKernelGGL(bn_max_kernel, dim3(div_up(M, BN_THREADS), B * C), dim3(BN_THREADS), 0, stream, C, M, K, act,
+                       (int)(K % 4 == 0 && aligned16(x)), x, mean, invstd, gamma, beta, y, arg, f);
+    return launch_status("amc3d_bn_max");
+}
+
+// Normalise stage from the fused statistics `f`: K == 0: y (B, C, L) = act(bn(x) [+ res]); K > 0: y (B, C, L / K) = max over
+// the K neighbours with the arg-max bytes.  The first workgroup of a channel does the exponential running update inside that
+// launch; the cumulative average (running buffers with momentum None, < 0 here) needs the counter before and after, so it
+// is a launch of its own behind it.
+static int bn_launch_normalise(const char *who, int B, int C, long L, int K, int act, const float *x, const float *res,
+                               const float *gamma, const float *beta, float *y, unsigned char *arg, const BnFused &f,
+                               hipStream_t stream)
+{
+    const int st = K == 0 ? launch_bn_act(who, B, C, L, act, x, f.mean_out, f.invstd_out, gamma, beta, y, f, res, stream)
+                          : launch_bn_max(B, C, (int)(L / K), K, act, x, f.mean_out, f.invstd_out, gamma, beta, y, arg, f, stream);
+    if (st) return st;
+    if (f.running_mean && f.momentum < 0.f)
+        hipLaunchKernelGGL(bn_running_kernel, dim3(1), dim3(1024), 0, stream, C, f.momentum, f.mean_out, f.var_out, f.running_mean,
+                           f.running_var, f.tracked);
+    return launch_status(who);
+}
+
+// The backward kernels' 16-byte loops (one decision for both launches of a call): L % 4 == 0, L < 2^31 (the apply kernel
+// indexes with 32 bits there), K % 4 == 0 when pooled (four elements share their pooled position), and every pointer the call
+// actually has among x, dy, dx, ymask and dres 16-byte aligned -- the absent ones are null and count as aligned.
+static int bn_bwd_vec(long L, int K, const unsigned char *arg, const float *x, const float *dy, const float *dx,
+                      const float *ymask, const float *dres)
+{
+    return (L % 4 == 0) && (K % 4 == 0 || !arg) && L < (1L << 31) && aligned16(x) && aligned16(dy) && aligned16(dx) &&
+           aligned16(ymask) && aligned16(dres);
+}
+
+// Backward statistics: {sum dq, sum dq * xhat} partials into the workspace.  arg: pooled (mode 1, dy over L / K positions);
+// ymask: the layer's saved output, from which act == BN_RELU masks and act == BN_SIGMOID differentiates.
+static BnSplit bn_launch_bwd_stats(int B, int C, long L, int K, int act, int vec, const float *x, const float *dy,
+                                   const unsigned char *arg, const float *ymask, const float *mean, const float *invstd,
+                                   const float *gamma, const float *beta, void *workspace, hipStream_t stream)
+{
+    const int mode = arg ? 1 : 0;
+    const BnSplit sp = bn_split(B, C, mode ? L / K : L);
+    hipLaunchKernelGGL(bn_bwd_stats_kernel, dim3(sp.nchunks, C), dim3(BN_THREADS), 0, stream, mode, B, C, L, K, act, sp, vec, x,
+                       dy, arg, mean, invstd, gamma, beta, (double *)workspace, ymask);
+    return sp;
+}
+
+// dx (and dres, the masked gradient, when given) from the sums: local partials with the host's count, which also publishes
+// dgamma / dbeta, or the all-reduced dsums (one "chunk") with the count in device memory and no parameter gradients.
+static int bn_launch_bwd_apply(const char *who, int B, int C, long L, int K, int act, int vec, const float *x, const float *dy,
+                               const unsigned char *arg, const float *ymask, const float *mean, const float *invstd,
+                               const float *gamma, const float *beta, const double *partial, int nchunks, double count,
+                               const double *count_dev, float *dgamma, float *dbeta, float *dx, float *dres, hipStream_t stream)
+{
+    const long per_block = BN_THREADS * 16;
+    const int gx = (int)min((L + per_block - 1) / per_block, (long)4096);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(gx, B * C), dim3(BN_THREADS), 0, stream, arg ? 1 : 0, C, L, K, act, vec, x, dy,
+                       arg, mean, invstd, gamma, beta, partial, nchunks, count, count_dev, dgamma, dbeta, dx, ymask, dres);
+    return launch_status(who);
+}
+
+// forward from local statistics: the statistics launch, then the normalise stage fed from its partials
+static int bn_forward_two(const char *who, int B, int C, long L, int K, int act, float eps, float momentum, const float *x,
+                          const float *res, const float *gamma, const float *beta, float *y, unsigned char *arg, float *mean,
+                          float *invstd, float *var_unbiased, float *running_mean, float *running_var, long long *tracked,
+                          void *workspace, hipStream_t stream)
+{
+    const BnSplit sp = bn_launch_stats(B, C, L, x, workspace, stream);
+    const BnFused f = bn_fused((const double *)workspace, sp.nchunks, (double)B * (double)L, nullptr, eps, momentum, mean, invstd,
+                               var_unbiased, running_mean, running_var, tracked);
+    return bn_launch_normalise(who, B, C, L, K, act, x, res, gamma, beta, y, arg, f, stream);
+}
+
+// backward of the same from local sums: the two launches share one `vec`
+static int bn_backward_two(const char *who, int B, int C, long L, int K, int act, const float *x, const float *dy,
+                           const unsigned char *arg, const float *ymask, const float *mean, const float *invstd,
+                           const float *gamma, const float *beta, float *dx, float *dres, float *dgamma, float *dbeta,
+                           void *workspace, hipStream_t stream)
+{
+    const int vec = bn_bwd_vec(L, K, arg, x, dy, dx, ymask, dres);
+    const BnSplit sp = bn_launch_bwd_stats(B, C, L, K, act, vec, x, dy, arg, ymask, mean, invstd, gamma, beta, workspace, stream);
+    return bn_launch_bwd_apply(who, B, C, L, K, act, vec, x, dy, arg, ymask, mean, invstd, gamma, beta, (const double *)workspace,
+                               sp.nchunks, (double)B * (double)L, nullptr, dgamma, dbeta, dx, dres, stream);
+}
+
+// Every entry point returns 0 for an empty tensor before it looks at any other argument.
+
 // statistics of x (B, C, L): mean, invstd = 1/sqrt(var_biased + eps), var_unbiased (for running_var)
 AMC_API int amc3d_bn_stats(int B, int C, long L, float eps, const float *x, float *mean, float *invstd,
                            float *var_unbiased, void *workspace, size_t workspace_bytes, void *stream_)
@@ -663,12 +781,8 @@ AMC_API int amc3d_bn_stats(int B, int C, long L, float eps, const float *x, floa
     if (!x || !mean || !invstd || !var_unbiased || !workspace || workspace_bytes < amc3d_bn_workspace_bytes(C))
         return bad_arg("amc3d_bn_stats: bad argument");
     hipStream_t stream = (hipStream_t)stream_;
-    const BnSplit sp = bn_split(B, C, L);
-    const int nchunks = sp.nchunks;
-    const int vec = (L % 4 == 0) && aligned16(x);
-    hipLaunchKernelGGL(bn_stats_kernel, dim3(nchunks, C), dim3(BN_THREADS), 0, stream, B, C, L, sp, vec, x,
-                       (double *)workspace);
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(div_up(C, 64)), dim3(64), 0, stream, C, nchunks, (double)B * (double)L,
+    const BnSplit sp = bn_launch_stats(B, C, L, x, workspace, stream);
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3(div_up(C, 64)), dim3(64), 0, stream, C, sp.nchunks, (double)B * (double)L,
                        eps, (const double *)workspace, mean, invstd, var_unbiased);
     return launch_status("amc3d_bn_stats");
 }
@@ -680,31 +794,7 @@ AMC_API int amc3d_bn_act(int B, int C, long L, int relu, const float *x, const f
     if (B <= 0 || C <= 0 || L <= 0) return 0;
     if (!x || !mean || !invstd || !gamma || !beta || !y) return bad_arg("amc3d_bn_act: null pointer");
     if (!bn_grid_y_ok(B, C)) return bad_arg("amc3d_bn_act: B * C must not exceed 65535");
-    const long per_block = BN_THREADS * 4 * 4;
-    const int gx = (int)min((L + per_block - 1) / per_block, (long)4096);
-    hipLaunchKernelGGL(bn_act_kernel, dim3(gx, B * C), dim3(BN_THREADS), 0, (hipStream_t)stream, C, L, relu,
-                       bn_act_vec(L, x, y, nullptr), x, mean, invstd, gamma, beta, y, BnFused{}, (const float *)nullptr);
-    return launch_status("amc3d_bn_act");
-}
-
-static int launch_bn_max(int B, int C, int M, int K, int relu, const float *x, const float *mean, const float *invstd,
-                         const float *gamma, const float *beta, float *y, unsigned char *arg, const BnFused &f,
-                         hipStream_t stream)
-{
-    const int lpr = K / 4;
-    if (K % 4 == 0 && (lpr == 2 || lpr == 4 || lpr == 8 || lpr == 16) && aligned16(x)) {
-        const int gx = (int)min((long)div_up((long)M * lpr, BN_THREADS * 4), 65535L);
-#define AMC_BNMAX(N)                                                                                                 \
-    hipLaunchKernelGGL(bn_max_coop_kernel<N>, dim3(gx, B * C), dim3(BN_THREADS), 0, stream, C, M, relu, x, mean, invstd, \
-                       gamma, beta, y, arg, f)
-        if (lpr == 2) AMC_BNMAX(2); else if (lpr == 4) AMC_BNMAX(4); else if (lpr == 8) AMC_BNMAX(8); else AMC_BNMAX(16);
-#undef AMC_BNMAX
-        return launch_status("amc3d_bn_max");
-    }
-    // y and arg are written one element at a time by both kernels: only x is read 16 bytes wide
-    hipLaunchKernelGGL(bn_max_kernel, dim3(div_up(M, BN_THREADS), B * C), dim3(BN_THREADS), 0, stream, C, M, K, relu,
-                       (int)(K % 4 == 0 && aligned16(x)), x, mean, invstd, gamma, beta, y, arg, f);
-    return launch_status("amc3d_bn_max");
+    return launch_bn_act("amc3d_bn_act", B, C, L, relu, x, mean, invstd, gamma, beta, y, BnFused{}, nullptr, (hipStream_t)stream);
 }
 
 // y (B, C, M) = max over the K neighbours of [relu](bn(x (B, C, M, K))); arg (B, C, M) bytes, K <= 255
@@ -722,6 +812,12 @@ AMC_API int amc3d_bn_max(int B, int C, int M, int K, int relu, const float *x, c
 // normalise [+ReLU] + max over the K neighbours (K > 0: L = M*K, y (B,C,M), arg (B,C,M)).  Writes mean, invstd,
 // var_unbiased (C each) and, when running_mean is given, performs nn.BatchNorm's buffer update
 // (momentum < 0 = None: cumulative average).
+//
+// The channel form (bn_fwd_channel_kernel here, bn_bwd_channel_kernel in amc3d_bn_backward: one launch for a short layer) is
+// reached from these two entry points only, without pooling.  The forward takes it when bn_channel_form(B, C, L) holds and
+// the layer does not keep a cumulative average (running buffers with momentum None), which that kernel cannot do.  The
+// decision comes BEFORE the B * C <= 65535 check: the channel kernels put only C on the grid.  Its 16-byte loop also writes
+// y, so y's alignment is part of its `vec`.  The residual, sigmoid and synced entry points never take it.
 AMC_API int amc3d_bn_forward(int B, int C, long L, int K, int relu, float eps, float momentum, const float *x,
                              const float *gamma, const float *beta, float *y, unsigned char *arg, float *mean,
                              float *invstd, float *var_unbiased, float *running_mean, float *running_var,
@@ -733,40 +829,15 @@ AMC_API int amc3d_bn_forward(int B, int C, long L, int K, int relu, float eps, f
         (running_mean && (!running_var || !num_batches_tracked)))
         return bad_arg("amc3d_bn_forward: bad argument");
     hipStream_t stream = (hipStream_t)stream_;
-    const BnSplit sp = bn_split(B, C, L);
-    const int vec = (L % 4 == 0) && aligned16(x);
     if (K == 0 && bn_channel_form(B, C, L) && !(running_mean && momentum < 0.f)) {
-        hipLaunchKernelGGL(bn_fwd_channel_kernel, dim3(C), dim3(BNC_THREADS), 0, stream, B, C, L, relu, vec && aligned16(y), eps,
-                           momentum, x, gamma, beta, y, mean, invstd, var_unbiased, running_mean, running_var,
-                           num_batches_tracked);
+        hipLaunchKernelGGL(bn_fwd_channel_kernel, dim3(C), dim3(BNC_THREADS), 0, stream, B, C, L, relu,
+                           (int)((L % 4 == 0) && aligned16(x) && aligned16(y)), eps, momentum, x, gamma, beta, y, mean, invstd,
+                           var_unbiased, running_mean, running_var, num_batches_tracked);
         return launch_status("amc3d_bn_forward");
     }
     if (!bn_grid_y_ok(B, C)) return bad_arg("amc3d_bn_forward: B * C must not exceed 65535");
-    hipLaunchKernelGGL(bn_stats_kernel, dim3(sp.nchunks, C), dim3(BN_THREADS), 0, stream, B, C, L, sp, vec, x,
-                       (double *)workspace);
-    BnFused f{};
-    f.partial = (const double *)workspace;
-    f.nchunks = sp.nchunks;
-    f.count = (double)B * (double)L;
-    f.eps = eps;
-    f.momentum = momentum;
-    f.mean_out = mean; f.invstd_out = invstd; f.var_out = var_unbiased;
-    f.running_mean = running_mean; f.running_var = running_var; f.tracked = num_batches_tracked;
-    int st;
-    if (K == 0) {
-        const long per_block = BN_THREADS * 4 * 4;
-        const int gx = (int)min((L + per_block - 1) / per_block, (long)4096);
-        hipLaunchKernelGGL(bn_act_kernel, dim3(gx, B * C), dim3(BN_THREADS), 0, stream, C, L, relu, bn_act_vec(L, x, y, nullptr),
-                           x, mean, invstd, gamma, beta, y, f, (const float *)nullptr);
-        st = launch_status("amc3d_bn_forward");
-    } else {
-        st = launch_bn_max(B, C, (int)(L / K), K, relu, x, mean, invstd, gamma, beta, y, arg, f, stream);
-    }
-    if (st) return st;
-    if (running_mean && momentum < 0.f)  // cumulative average: needs the counter before and after -> its own launch
-        hipLaunchKernelGGL(bn_running_kernel, dim3(1), dim3(1024), 0, stream, C, momentum, mean, var_unbiased, running_mean,
-                           running_var, num_batches_tracked);
-    return launch_status("amc3d_bn_forward");
+    return bn_forward_two("amc3d_bn_forward", B, C, L, K, relu, eps, momentum, x, nullptr, gamma, beta, y, arg, mean, invstd,
+                          var_unbiased, running_mean, running_var, num_batches_tracked, workspace, stream);
 }
 
 // Backward of y = [relu](bn(x)) (arg == NULL, K = 1, dy (B,C,L)) or of y = max_K [relu](bn(x)) (arg given,
@@ -777,30 +848,21 @@ AMC_API int amc3d_bn_backward(int B, int C, long L, int K, int relu, const float
                               size_t workspace_bytes, void *stream_)
 {
     if (B <= 0 || C <= 0 || L <= 0) return 0;
+    // This entry point alone asks for 2 C floats beyond amc3d_bn_workspace_bytes(C).  No kernel touches them (the partials
+    // end at C * BN_MAX_CHUNKS pairs of doubles; dgamma / dbeta are written in place): kept because callers size to it.
     const size_t need = amc3d_bn_workspace_bytes(C) + (size_t)C * 2 * sizeof(float);
     if (!x || !dy || !mean || !invstd || !gamma || !beta || !dx || !dgamma || !dbeta || !workspace ||
         workspace_bytes < need || K <= 0 || (arg && L % K != 0))
         return bad_arg("amc3d_bn_backward: bad argument");
     hipStream_t stream = (hipStream_t)stream_;
-    const int mode = arg ? 1 : 0;
-    const BnSplit sp = bn_split(B, C, mode ? L / K : L);
-    const int nchunks = sp.nchunks;
-    const int vec = (L % 4 == 0) && (K % 4 == 0 || !mode) && aligned16(x) && aligned16(dy) && aligned16(dx) && L < (1L << 31);
-    double *partial = (double *)workspace;
-    if (mode == 0 && bn_channel_form(B, C, L)) {
-        hipLaunchKernelGGL(bn_bwd_channel_kernel, dim3(C), dim3(BNC_THREADS), 0, stream, B, C, L, relu, vec, x, dy, mean, invstd,
-                           gamma, beta, dgamma, dbeta, dx);
+    if (!arg && bn_channel_form(B, C, L)) {  // the channel form (see amc3d_bn_forward), again ahead of the grid check
+        hipLaunchKernelGGL(bn_bwd_channel_kernel, dim3(C), dim3(BNC_THREADS), 0, stream, B, C, L, relu,
+                           bn_bwd_vec(L, K, arg, x, dy, dx, nullptr, nullptr), x, dy, mean, invstd, gamma, beta, dgamma, dbeta, dx);
         return launch_status("amc3d_bn_backward");
     }
     if (!bn_grid_y_ok(B, C)) return bad_arg("amc3d_bn_backward: B * C must not exceed 65535");
-    hipLaunchKernelGGL(bn_bwd_stats_kernel, dim3(nchunks, C), dim3(BN_THREADS), 0, stream, mode, B, C, L, K, relu, sp, vec, x,
-                       dy, arg, mean, invstd, gamma, beta, partial, (const float *)nullptr);
-    const long per_block = BN_THREADS * 16;
-    const int gx = (int)min((L + per_block - 1) / per_block, (long)4096);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(gx, B * C), dim3(BN_THREADS), 0, stream, mode, C, L, K, relu, vec, x, dy, arg,
-                       mean, invstd, gamma, beta, (const double *)partial, nchunks, (double)B * (double)L,
-                       (const double *)nullptr, dgamma, dbeta, dx, (const float *)nullptr, (float *)nullptr);
-    return launch_status("amc3d_bn_backward");
+    return bn_backward_two("amc3d_bn_backward", B, C, L, K, relu, x, dy, arg, nullptr, mean, invstd, gamma, beta, dx, nullptr,
+                           dgamma, dbeta, workspace, stream);
 }
 
 // y = relu(bn(x) + res) with batch statistics: the tail of an InvResMLP block (pointnext_AA.py:296-307: pwconv's last
@@ -815,27 +877,8 @@ AMC_API int amc3d_bn_residual_forward(int B, int C, long L, float eps, float mom
         workspace_bytes < amc3d_bn_workspace_bytes(C) || (running_mean && (!running_var || !num_batches_tracked)))
         return bad_arg("amc3d_bn_residual_forward: bad argument");
     if (!bn_grid_y_ok(B, C)) return bad_arg("amc3d_bn_residual_forward: B * C must not exceed 65535");
-    hipStream_t stream = (hipStream_t)stream_;
-    const BnSplit sp = bn_split(B, C, L);
-    const int vec = (L % 4 == 0) && aligned16(x);
-    hipLaunchKernelGGL(bn_stats_kernel, dim3(sp.nchunks, C), dim3(BN_THREADS), 0, stream, B, C, L, sp, vec, x,
-                       (double *)workspace);
-    BnFused f{};
-    f.partial = (const double *)workspace;
-    f.nchunks = sp.nchunks;
-    f.count = (double)B * (double)L;
-    f.eps = eps;
-    f.momentum = momentum;
-    f.mean_out = mean; f.invstd_out = invstd; f.var_out = var_unbiased;
-    f.running_mean = running_mean; f.running_var = running_var; f.tracked = num_batches_tracked;
-    const long per_block = BN_THREADS * 4 * 4;
-    const int gx = (int)min((L + per_block - 1) / per_block, (long)4096);
-    hipLaunchKernelGGL(bn_act_kernel, dim3(gx, B * C), dim3(BN_THREADS), 0, stream, C, L, 1, bn_act_vec(L, x, y, res), x, mean,
-                       invstd, gamma, beta, y, f, res);
-    if (running_mean && momentum < 0.f)
-        hipLaunchKernelGGL(bn_running_kernel, dim3(1), dim3(1024), 0, stream, C, momentum, mean, var_unbiased, running_mean,
-                           running_var, num_batches_tracked);
-    return launch_status("amc3d_bn_residual_forward");
+    return bn_forward_two("amc3d_bn_residual_forward", B, C, L, 0, BN_RELU, eps, momentum, x, res, gamma, beta, y, nullptr, mean,
+                          invstd, var_unbiased, running_mean, running_var, num_batches_tracked, workspace, (hipStream_t)stream_);
 }
 
 // backward of the same: dq = dy * (y > 0); dres = dq; dx, dgamma, dbeta = BatchNorm backward of dq
@@ -849,19 +892,8 @@ AMC_API int amc3d_bn_residual_backward(int B, int C, long L, const float *x, con
         workspace_bytes < amc3d_bn_workspace_bytes(C))
         return bad_arg("amc3d_bn_residual_backward: bad argument");
     if (!bn_grid_y_ok(B, C)) return bad_arg("amc3d_bn_residual_backward: B * C must not exceed 65535");
-    hipStream_t stream = (hipStream_t)stream_;
-    const BnSplit sp = bn_split(B, C, L);
-    const int vec = (L % 4 == 0) && aligned16(x) && aligned16(y) && aligned16(dy) && aligned16(dx) && aligned16(dres) &&
-                    L < (1L << 31);
-    double *partial = (double *)workspace;
-    hipLaunchKernelGGL(bn_bwd_stats_kernel, dim3(sp.nchunks, C), dim3(BN_THREADS), 0, stream, 0, B, C, L, 1, 1, sp, vec, x, dy,
-                       (const unsigned char *)nullptr, mean, invstd, gamma, beta, partial, y);
-    const long per_block = BN_THREADS * 16;
-    const int gx = (int)min((L + per_block - 1) / per_block, (long)4096);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(gx, B * C), dim3(BN_THREADS), 0, stream, 0, C, L, 1, 1, vec, x, dy,
-                       (const unsigned char *)nullptr, mean, invstd, gamma, beta, (const double *)partial, sp.nchunks,
-                       (double)B * (double)L, (const double *)nullptr, dgamma, dbeta, dx, y, dres);
-    return launch_status("amc3d_bn_residual_backward");
+    return bn_backward_two("amc3d_bn_residual_backward", B, C, L, 1, BN_RELU, x, dy, nullptr, y, mean, invstd, gamma, beta, dx,
+                           dres, dgamma, dbeta, workspace, (hipStream_t)stream_);
 }
 
 // y = sigmoid(bn(x)) with batch statistics (the APM towers of AMContrast3D++, openpoints/AMContrast3D/APM/concatenation.py:
@@ -877,27 +909,9 @@ AMC_API int amc3d_bn_sigmoid_forward(int B, int C, long L, float eps, float mome
         workspace_bytes < amc3d_bn_workspace_bytes(C) || (running_mean && (!running_var || !num_batches_tracked)))
         return bad_arg("amc3d_bn_sigmoid_forward: bad argument");
     if (!bn_grid_y_ok(B, C)) return bad_arg("amc3d_bn_sigmoid_forward: B * C must not exceed 65535");
-    hipStream_t stream = (hipStream_t)stream_;
-    const BnSplit sp = bn_split(B, C, L);
-    const int vec = (L % 4 == 0) && aligned16(x);
-    hipLaunchKernelGGL(bn_stats_kernel, dim3(sp.nchunks, C), dim3(BN_THREADS), 0, stream, B, C, L, sp, vec, x,
-                       (double *)workspace);
-    BnFused f{};
-    f.partial = (const double *)workspace;
-    f.nchunks = sp.nchunks;
-    f.count = (double)B * (double)L;
-    f.eps = eps;
-    f.momentum = momentum;
-    f.mean_out = mean; f.invstd_out = invstd; f.var_out = var_unbiased;
-    f.running_mean = running_mean; f.running_var = running_var; f.tracked = num_batches_tracked;
-    const long per_block = BN_THREADS * 4 * 4;
-    const int gx = (int)min((L + per_block - 1) / per_block, (long)4096);
-    hipLaunchKernelGGL(bn_act_kernel, dim3(gx, B * C), dim3(BN_THREADS), 0, stream, C, L, 2, bn_act_vec(L, x, y, nullptr), x, mean,
-                       invstd, gamma, beta, y, f, (const float *)nullptr);
-    if (running_mean && momentum < 0.f)
-        hipLaunchKernelGGL(bn_running_kernel, dim3(1), dim3(1024), 0, stream, C, momentum, mean, var_unbiased, running_mean,
-                           running_var, num_batches_tracked);
-    return launch_status("amc3d_bn_sigmoid_forward");
+    return bn_forward_two("amc3d_bn_sigmoid_forward", B, C, L, 0, BN_SIGMOID, eps, momentum, x, nullptr, gamma, beta, y, nullptr,
+                          mean, invstd, var_unbiased, running_mean, running_var, num_batches_tracked, workspace,
+                          (hipStream_t)stream_);
 }
 
 AMC_API int amc3d_bn_sigmoid_backward(int B, int C, long L, const float *x, const float *y, const float *dy, const float *mean,
@@ -909,18 +923,8 @@ AMC_API int amc3d_bn_sigmoid_backward(int B, int C, long L, const float *x, cons
         workspace_bytes < amc3d_bn_workspace_bytes(C))
         return bad_arg("amc3d_bn_sigmoid_backward: bad argument");
     if (!bn_grid_y_ok(B, C)) return bad_arg("amc3d_bn_sigmoid_backward: B * C must not exceed 65535");
-    hipStream_t stream = (hipStream_t)stream_;
-    const BnSplit sp = bn_split(B, C, L);
-    const int vec = (L % 4 == 0) && aligned16(x) && aligned16(y) && aligned16(dy) && aligned16(dx) && L < (1L << 31);
-    double *partial = (double *)workspace;
-    hipLaunchKernelGGL(bn_bwd_stats_kernel, dim3(sp.nchunks, C), dim3(BN_THREADS), 0, stream, 0, B, C, L, 1, 2, sp, vec, x, dy,
-                       (const unsigned char *)nullptr, mean, invstd, gamma, beta, partial, y);
-    const long per_block = BN_THREADS * 16;
-    const int gx = (int)min((L + per_block - 1) / per_block, (long)4096);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(gx, B * C), dim3(BN_THREADS), 0, stream, 0, C, L, 1, 2, vec, x, dy,
-                       (const unsigned char *)nullptr, mean, invstd, gamma, beta, (const double *)partial, sp.nchunks,
-                       (double)B * (double)L, (const double *)nullptr, dgamma, dbeta, dx, y, (float *)nullptr);
-    return launch_status("amc3d_bn_sigmoid_backward");
+    return bn_backward_two("amc3d_bn_sigmoid_backward", B, C, L, 1, BN_SIGMOID, x, dy, nullptr, y, mean, invstd, gamma, beta, dx,
+                           nullptr, dgamma, dbeta, workspace, (hipStream_t)stream_);
 }
 
 // running_mean / running_var / num_batches_tracked update of nn.BatchNorm in training mode; momentum < 0 = None
@@ -951,10 +955,7 @@ AMC_API int amc3d_bn_sums(int B, int C, long L, const float *x, double *sums, vo
     if (!x || !sums || !workspace || workspace_bytes < amc3d_bn_workspace_bytes(C))
         return bad_arg("amc3d_bn_sums: bad argument");
     hipStream_t stream = (hipStream_t)stream_;
-    const BnSplit sp = bn_split(B, C, L);
-    const int vec = (L % 4 == 0) && aligned16(x);
-    hipLaunchKernelGGL(bn_stats_kernel, dim3(sp.nchunks, C), dim3(BN_THREADS), 0, stream, B, C, L, sp, vec, x,
-                       (double *)workspace);
+    const BnSplit sp = bn_launch_stats(B, C, L, x, workspace, stream);
     hipLaunchKernelGGL(bn_reduce_partials_kernel, dim3(C), dim3(64), 0, stream, sp.nchunks, (const double *)workspace, sums,
                        (float *)nullptr, (float *)nullptr);
     return launch_status("amc3d_bn_sums");
@@ -972,30 +973,10 @@ AMC_API int amc3d_bn_forward_synced(int B, int C, long L, int K, int relu, float
         (K > 0 && (!arg || L % K != 0)) || (running_mean && (!running_var || !num_batches_tracked)))
         return bad_arg("amc3d_bn_forward_synced: bad argument");
     if (!bn_grid_y_ok(B, C)) return bad_arg("amc3d_bn_forward_synced: B * C must not exceed 65535");
-    hipStream_t stream = (hipStream_t)stream_;
-    BnFused f{};
-    f.partial = sums_count;
-    f.nchunks = 1;
-    f.count_dev = sums_count + 2 * (size_t)C;
-    f.eps = eps;
-    f.momentum = momentum;
-    f.mean_out = mean; f.invstd_out = invstd; f.var_out = var_unbiased;
-    f.running_mean = running_mean; f.running_var = running_var; f.tracked = num_batches_tracked;
-    int st;
-    if (K == 0) {
-        const long per_block = BN_THREADS * 4 * 4;
-        const int gx = (int)min((L + per_block - 1) / per_block, (long)4096);
-        hipLaunchKernelGGL(bn_act_kernel, dim3(gx, B * C), dim3(BN_THREADS), 0, stream, C, L, relu, bn_act_vec(L, x, y, nullptr),
-                           x, mean, invstd, gamma, beta, y, f, (const float *)nullptr);
-        st = launch_status("amc3d_bn_forward_synced");
-    } else {
-        st = launch_bn_max(B, C, (int)(L / K), K, relu, x, mean, invstd, gamma, beta, y, arg, f, stream);
-    }
-    if (st) return st;
-    if (running_mean && momentum < 0.f)
-        hipLaunchKernelGGL(bn_running_kernel, dim3(1), dim3(1024), 0, stream, C, momentum, mean, var_unbiased, running_mean,
-                           running_var, num_batches_tracked);
-    return launch_status("amc3d_bn_forward_synced");
+    const BnFused f = bn_fused(sums_count, 1, 0.0, sums_count + 2 * (size_t)C, eps, momentum, mean, invstd, var_unbiased,
+                               running_mean, running_var, num_batches_tracked);
+    return bn_launch_normalise("amc3d_bn_forward_synced", B, C, L, K, relu, x, nullptr, gamma, beta, y, arg, f,
+                               (hipStream_t)stream_);
 }
 
 // dsums (2C doubles): {sum dq, sum dq * xhat} over this rank; dbeta / dgamma (C floats) = the same, rank-local
@@ -1010,11 +991,8 @@ AMC_API int amc3d_bn_backward_sums(int B, int C, long L, int K, int relu, const 
         workspace_bytes < amc3d_bn_workspace_bytes(C) || K <= 0 || (arg && L % K != 0))
         return bad_arg("amc3d_bn_backward_sums: bad argument");
     hipStream_t stream = (hipStream_t)stream_;
-    const int mode = arg ? 1 : 0;
-    const BnSplit sp = bn_split(B, C, mode ? L / K : L);
-    const int vec = (L % 4 == 0) && (K % 4 == 0 || !mode) && aligned16(x) && aligned16(dy) && L < (1L << 31);
-    hipLaunchKernelGGL(bn_bwd_stats_kernel, dim3(sp.nchunks, C), dim3(BN_THREADS), 0, stream, mode, B, C, L, K, relu, sp, vec,
-                       x, dy, arg, mean, invstd, gamma, beta, (double *)workspace, (const float *)nullptr);
+    const BnSplit sp = bn_launch_bwd_stats(B, C, L, K, relu, bn_bwd_vec(L, K, arg, x, dy, nullptr, nullptr, nullptr), x, dy, arg,
+                                           nullptr, mean, invstd, gamma, beta, workspace, stream);
     hipLaunchKernelGGL(bn_reduce_partials_kernel, dim3(C), dim3(64), 0, stream, sp.nchunks, (const double *)workspace, dsums,
                        dbeta, dgamma);
     return launch_status("amc3d_bn_backward_sums");
@@ -1030,12 +1008,7 @@ AMC_API int amc3d_bn_backward_synced(int B, int C, long L, int K, int relu, cons
     if (!x || !dy || !mean || !invstd || !gamma || !beta || !dsums || !count || !dx || K <= 0 || (arg && L % K != 0))
         return bad_arg("amc3d_bn_backward_synced: bad argument");
     if (!bn_grid_y_ok(B, C)) return bad_arg("amc3d_bn_backward_synced: B * C must not exceed 65535");
-    const int mode = arg ? 1 : 0;
-    const int vec = (L % 4 == 0) && (K % 4 == 0 || !mode) && aligned16(x) && aligned16(dy) && aligned16(dx) && L < (1L << 31);
-    const long per_block = BN_THREADS * 16;
-    const int gx = (int)min((L + per_block - 1) / per_block, (long)4096);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(gx, B * C), dim3(BN_THREADS), 0, (hipStream_t)stream_, mode, C, L, K, relu,
-                       vec, x, dy, arg, mean, invstd, gamma, beta, dsums, 1, 0.0, count, (float *)nullptr, (float *)nullptr,
-                       dx, (const float *)nullptr, (float *)nullptr);
-    return launch_status("amc3d_bn_backward_synced");
+    return bn_launch_bwd_apply("amc3d_bn_backward_synced", B, C, L, K, relu, bn_bwd_vec(L, K, arg, x, dy, dx, nullptr, nullptr), x,
+                               dy, arg, nullptr, mean, invstd, gamma, beta, dsums, 1, 0.0, count, nullptr, nullptr, dx, nullptr,
+                               (hipStream_t)stream_);
 }

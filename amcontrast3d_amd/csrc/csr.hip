@@ -113,11 +113,6 @@ __global__ __launch_bounds__(256) void csr_global_moments_kernel(long P, const f
     }
 }
 
-__device__ __forceinline__ float csr_bn(float x, float mean, float invstd, float gamma, float beta)
-{
-    return __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(x, mean), invstd), gamma), beta);
-}
-
 // Collapse as a gather: a group of CT lanes owns one source point g and walks its edge list; lane = channel.
 //   q[g][c] = sum_e d(e, c),  d = dx1_pm[position e][c] * [relu: bn(G[g][c] + W_dp[c] . dp_e) > 0]
 //   partial sums per channel {sum d, sum d xhat, sum d dp_j}.  dx1_pm is the POSITION-major gradient (b, P, C).

@@ -24,7 +24,7 @@
 // The geometry moments depend on coordinates only and are part of the geometry plan (computed ahead, shared by all
 // blocks of a stage).
 
-#include "common.h"
+#include "bn_math.h"
 
 namespace amc {
 
@@ -185,23 +185,10 @@ __global__ __launch_bounds__(256) void lagg_stats_finalize_kernel(int C, int npa
         return;
     }
     if (mode == 2) { sy1 = sums[2 * c]; sy2 = sums[2 * c + 1]; count = sums[2 * C]; }
-    const double mu = sy1 / count;
-    double var = sy2 / count - mu * mu;
-    if (var < 0.0) var = 0.0;
-    const float mf = (float)mu, vu = (float)(count > 1.0 ? var * count / (count - 1.0) : var);
-    mean[c] = mf;
-    invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-    var_unbiased[c] = vu;
-    if (running_mean && momentum >= 0.f) {
-        running_mean[c] = running_mean[c] * (1.f - momentum) + momentum * mf;
-        running_var[c] = running_var[c] * (1.f - momentum) + momentum * vu;
-        if (c == 0 && tracked) *tracked += 1;
-    }
-}
-
-__device__ __forceinline__ float lagg_bn(float x, float mean, float invstd, float gamma, float beta)
-{
-    return __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(x, mean), invstd), gamma), beta);
+    float mf, isf, vu;
+    bn_moments(sy1, sy2, count, eps, mf, isf, vu);
+    mean[c] = mf; invstd[c] = isf; var_unbiased[c] = vu;
+    bn_running_update(c, momentum, mf, vu, running_mean, running_var, tracked);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -268,7 +255,7 @@ __global__ __launch_bounds__(256) void lagg_pool_kernel(int C, int n, int M, int
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float y = __fmaf_rn(w[j][0], e0, __fmaf_rn(w[j][1], e1, __fmaf_rn(w[j][2], e2, gs[j])));
-                float v = lagg_bn(y, mu[j], is[j], ga[j], be[j]);
+                float v = bn_val(y, mu[j], is[j], ga[j], be[j]);
                 if (relu) v = fmaxf(v, 0.f);
                 if (k < K && v > best[j]) { best[j] = v; bk[j] = k; by[j] = y; }
             }
@@ -620,7 +607,7 @@ __global__ __launch_bounds__(256) void lagg_expand_kernel(int C, int n, long P, 
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float y = __fmaf_rn(w[j][0], e0, __fmaf_rn(w[j][1], e1, __fmaf_rn(w[j][2], e2, gs[j])));
-            float v = lagg_bn(y, mu[j], is[j], ga[j], be[j]);
+            float v = bn_val(y, mu[j], is[j], ga[j], be[j]);
             if (relu) v = fmaxf(v, 0.f);
             tile[4 * q + j][wave * 32 + k] = v;
         }

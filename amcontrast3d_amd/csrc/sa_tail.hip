@@ -25,7 +25,7 @@
 // exactly the element the reference's max-pool routes the gradient to, also when two raw values round to the same
 // normalised value or a ReLU clamps several to zero.  BN1's own backward (from dx1) stays with bn.hip.
 
-#include "common.h"
+#include "bn_math.h"
 
 namespace amc {
 
@@ -59,11 +59,6 @@ struct SatArgs {
     unsigned char *arg_out;                // mode 2, optional: (B, C2, M) the arg-max the gradient is routed to
     float *partial_w;                      // mode 3: [part][C2][C1]
 };
-
-__device__ __forceinline__ float sat_bn(float x, float mean, float invstd, float gamma, float beta)
-{
-    return __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(x, mean), invstd), gamma), beta);
-}
 
 template <int NCT, int MODE, int NIT>  // NIT: 32-channel tiles of C1 (used by the weight gradient of mode 3)
 __global__ __launch_bounds__(256, (MODE == 0 && NCT <= 2) ? 3 : 1) void sat_kernel(SatArgs a)  // (forward: three workgroups per CU)
@@ -140,8 +135,8 @@ __global__ __launch_bounds__(256, (MODE == 0 && NCT <= 2) ? 3 : 1) void sat_kern
                     float4 v = pre[j];
                     if (p0 + c4 * 4 < P) {  // P is a multiple of 32: the four elements are in range together
                         const float mu = bn1[k], is = bn1[C1 + k], g = bn1[2 * C1 + k], bt = bn1[3 * C1 + k];
-                        v.x = fmaxf(sat_bn(v.x, mu, is, g, bt), 0.f); v.y = fmaxf(sat_bn(v.y, mu, is, g, bt), 0.f);
-                        v.z = fmaxf(sat_bn(v.z, mu, is, g, bt), 0.f); v.w = fmaxf(sat_bn(v.w, mu, is, g, bt), 0.f);
+                        v.x = fmaxf(bn_val(v.x, mu, is, g, bt), 0.f); v.y = fmaxf(bn_val(v.y, mu, is, g, bt), 0.f);
+                        v.z = fmaxf(bn_val(v.z, mu, is, g, bt), 0.f); v.w = fmaxf(bn_val(v.w, mu, is, g, bt), 0.f);
                     }
                     float *d = xs + k * SAT_XS + c4 * 4;
                     d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
@@ -156,8 +151,8 @@ __global__ __launch_bounds__(256, (MODE == 0 && NCT <= 2) ? 3 : 1) void sat_kern
                 if (p < P) {  // P is a multiple of 32: the four elements are in range together
                     v = *reinterpret_cast<const float4 *>(a.y1 + ((size_t)b * C1 + k) * P + p);
                     const float mu = bn1[k], is = bn1[C1 + k], g = bn1[2 * C1 + k], bt = bn1[3 * C1 + k];
-                    v.x = fmaxf(sat_bn(v.x, mu, is, g, bt), 0.f); v.y = fmaxf(sat_bn(v.y, mu, is, g, bt), 0.f);
-                    v.z = fmaxf(sat_bn(v.z, mu, is, g, bt), 0.f); v.w = fmaxf(sat_bn(v.w, mu, is, g, bt), 0.f);
+                    v.x = fmaxf(bn_val(v.x, mu, is, g, bt), 0.f); v.y = fmaxf(bn_val(v.y, mu, is, g, bt), 0.f);
+                    v.z = fmaxf(bn_val(v.z, mu, is, g, bt), 0.f); v.w = fmaxf(bn_val(v.w, mu, is, g, bt), 0.f);
                 }
                 float *d = xs + k * SAT_XS + c4 * 4;
                 d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
@@ -246,7 +241,7 @@ __global__ __launch_bounds__(256, (MODE == 0 && NCT <= 2) ? 3 : 1) void sat_kern
                 int as = 0;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {  // ascending s within this half: strict '>' keeps the first maximum
-                    float y = sat_bn(acc[ct][r], m2[ct], is2[ct], g2[ct], b2[ct]);
+                    float y = bn_val(acc[ct][r], m2[ct], is2[ct], g2[ct], b2[ct]);
                     if (a.relu2) y = fmaxf(y, 0.f);
                     if (y > best) { best = y; as = (r & 3) + 8 * (r >> 2) + 4 * kh; }
                 }
@@ -407,18 +402,11 @@ __global__ __launch_bounds__(256) void sat_finalize_kernel(int C2, int nparts, d
         if (backward) {  // o0 = dbeta = sum dq, o1 = dgamma = sum dq xhat, o2 / o3 = their means
             if (first) { o0[c] = (float)s1; o1[c] = (float)s2; o2[c] = (float)(s1 / count); o3[c] = (float)(s2 / count); }
         } else {
-            const double mu = s1 / count;
-            double var = s2 / count - mu * mu;
-            if (var < 0.0) var = 0.0;
-            const float mf = (float)mu, vu = (float)(count > 1.0 ? var * count / (count - 1.0) : var);
-            const float isf = (float)(1.0 / sqrt(var + (double)eps));
+            float mf, isf, vu;
+            bn_moments(s1, s2, count, eps, mf, isf, vu);
             if (first) { o0[c] = mf; o1[c] = isf; o2[c] = vu; }
             s_stat[0] = mf; s_stat[1] = isf;
-            if (first && running_mean && momentum >= 0.f) {
-                running_mean[c] = running_mean[c] * (1.f - momentum) + momentum * mf;
-                running_var[c] = running_var[c] * (1.f - momentum) + momentum * vu;
-                if (c == 0 && tracked) *tracked += 1;
-            }
+            if (first) bn_running_update(c, momentum, mf, vu, running_mean, running_var, tracked);
         }
     }
     if (backward || !pooled) return;
@@ -428,7 +416,7 @@ __global__ __launch_bounds__(256) void sat_finalize_kernel(int C2, int nparts, d
     for (int i = blockIdx.y * 256 + threadIdx.x; i < B * M; i += 256 * gridDim.y) {
         const int bb = i / M, m = i - bb * M;
         const size_t q = ((size_t)bb * C2 + c) * M + m;
-        float y = sat_bn(zext[q], mf, isf, g, bt);  // (mode 0 kept the maximum for gamma > 0, the minimum for gamma < 0)
+        float y = bn_val(zext[q], mf, isf, g, bt);  // (mode 0 kept the maximum for gamma > 0, the minimum for gamma < 0)
         pooled[q] = relu2 ? fmaxf(y, 0.f) : y;
     }
 }
@@ -633,8 +621,8 @@ __global__ __launch_bounds__(256, NIT == 1 ? SAT_ALG_WGS : 1) void sat_bwd_alg_k
                 float4 v = pre[j];
                 if (p0 + c4 * 4 < P) {  // P is a multiple of 32: the four elements are in range together
                     const float mu = bn1[k], is = bn1[C1 + k], g = bn1[2 * C1 + k], bt = bn1[3 * C1 + k];
-                    v.x = fmaxf(sat_bn(v.x, mu, is, g, bt), 0.f); v.y = fmaxf(sat_bn(v.y, mu, is, g, bt), 0.f);
-                    v.z = fmaxf(sat_bn(v.z, mu, is, g, bt), 0.f); v.w = fmaxf(sat_bn(v.w, mu, is, g, bt), 0.f);
+                    v.x = fmaxf(bn_val(v.x, mu, is, g, bt), 0.f); v.y = fmaxf(bn_val(v.y, mu, is, g, bt), 0.f);
+                    v.z = fmaxf(bn_val(v.z, mu, is, g, bt), 0.f); v.w = fmaxf(bn_val(v.w, mu, is, g, bt), 0.f);
                 }
                 float *d = xs + k * SAT_XS + c4 * 4;
                 d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;

@@ -946,6 +946,35 @@ def _bn_running_args(bn):
     return mom, _ptr(bn.running_mean), _ptr(bn.running_var), _ptr(bn.num_batches_tracked)
 
 
+def _bn_stat_bufs(C, dev):
+    """mean, invstd and unbiased variance of C channels, for a kernel to fill"""
+    mean = torch.empty(C, dtype=torch.float32, device=dev)
+    return mean, torch.empty_like(mean), torch.empty_like(mean)
+
+
+def _bn_begin(x, bn):
+    """What every fused forward starts from: x contiguous, its shape as (B, C, L), the statistics buffers, the workspace
+    (tensor, bytes) and the running-buffer arguments of `bn`."""
+    x = x.contiguous()
+    B, C = x.shape[0], x.shape[1]
+    return x, (B, C, x.numel() // (B * C)), _bn_stat_bufs(C, x.device), _bn_ws(C, x.device), _bn_running_args(bn)
+
+
+def _bn_finish(ctx, y, mean, var_u, *saved):
+    """The forward's bookkeeping: returns (y, batch mean, unbiased batch variance), the statistics without gradients."""
+    ctx.save_for_backward(*saved)
+    ctx.mark_non_differentiable(mean, var_u)
+    ctx.set_materialize_grads(False)  # no zero tensors for the statistics' (absent) gradients
+    return y, mean, var_u
+
+
+def _bn_backward_begin(x, dy, gamma, beta):
+    """(B, C, L), dy contiguous, the dx / dgamma / dbeta to fill and the workspace (tensor, bytes) of a fused backward."""
+    B, C = x.shape[0], x.shape[1]
+    return ((B, C, x.numel() // (B * C)), dy.contiguous(), torch.empty_like(x), torch.empty_like(gamma), torch.empty_like(beta),
+            _bn_ws(C, x.device, extra=C * 8))
+
+
 class BatchNormAct(Function):
     """y = [relu](batch_norm(x)) with batch statistics; x (B, C, *) contiguous fp32.  `bn`: the nn.BatchNorm module
     whose running buffers are updated in the same launch (None: no update).
@@ -954,37 +983,19 @@ class BatchNormAct(Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, relu, bn=None):
         _need_gpu(x, gamma, beta)
-        x = x.contiguous()
-        B, C = x.shape[0], x.shape[1]
-        L = x.numel() // (B * C)
-        dev = x.device
-        mean = torch.empty(C, dtype=torch.float32, device=dev)
-        invstd = torch.empty_like(mean)
-        var_u = torch.empty_like(mean)
+        x, (B, C, L), (mean, invstd, var_u), (work, wb), (mom, rm, rv, nbt) = _bn_begin(x, bn)
         y = torch.empty_like(x)
-        work, wb = _bn_ws(C, dev)
-        lib = _lib.load()
-        mom, rm, rv, nbt = _bn_running_args(bn)
-        with torch.cuda.device(dev), timing.span("bn_act_forward", x.numel() * 8, moved=x.numel() * 12):
-            _lib.check(lib.amc3d_bn_forward(B, C, L, 0, int(bool(relu)), float(eps), mom, _ptr(x), _ptr(gamma), _ptr(beta),
-                                            _ptr(y), None, _ptr(mean), _ptr(invstd), _ptr(var_u), rm, rv, nbt,
-                                            _ptr(work), wb, _stream(x)), "bn_forward")
-        ctx.save_for_backward(x, gamma, beta, mean, invstd)
+        with torch.cuda.device(x.device), timing.span("bn_act_forward", x.numel() * 8, moved=x.numel() * 12):
+            _lib.check(_lib.load().amc3d_bn_forward(B, C, L, 0, int(bool(relu)), float(eps), mom, _ptr(x), _ptr(gamma),
+                                                    _ptr(beta), _ptr(y), None, _ptr(mean), _ptr(invstd), _ptr(var_u), rm, rv,
+                                                    nbt, _ptr(work), wb, _stream(x)), "bn_forward")
         ctx.relu = bool(relu)
-        ctx.mark_non_differentiable(mean, var_u)
-        ctx.set_materialize_grads(False)  # no zero tensors for the statistics' (absent) gradients
-        return y, mean, var_u
+        return _bn_finish(ctx, y, mean, var_u, x, gamma, beta, mean, invstd)
 
     @staticmethod
     def backward(ctx, dy, _dm, _dv):
         x, gamma, beta, mean, invstd = ctx.saved_tensors
-        B, C = x.shape[0], x.shape[1]
-        L = x.numel() // (B * C)
-        dy = dy.contiguous()
-        dx = torch.empty_like(x)
-        dgamma = torch.empty_like(gamma)
-        dbeta = torch.empty_like(beta)
-        work, wb = _bn_ws(C, x.device, extra=C * 8)
+        (B, C, L), dy, dx, dgamma, dbeta, (work, wb) = _bn_backward_begin(x, dy, gamma, beta)
         with torch.cuda.device(x.device), timing.span("bn_act_backward", x.numel() * 12, moved=x.numel() * 20):
             _lib.check(_lib.load().amc3d_bn_backward(B, C, L, 1, int(ctx.relu), _ptr(x), _ptr(dy), None, _ptr(mean),
                                                      _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(dx), _ptr(dgamma),
@@ -1001,37 +1012,21 @@ class BatchNormResidualAct(Function):
     def forward(ctx, x, res, gamma, beta, eps, bn=None):
         _need_gpu(x, res, gamma, beta)
         _need_dtype(torch.float32, x=x, res=res, gamma=gamma, beta=beta)
-        x, res = x.contiguous(), res.contiguous()
+        x, (B, C, L), (mean, invstd, var_u), (work, wb), (mom, rm, rv, nbt) = _bn_begin(x, bn)
+        res = res.contiguous()
         assert x.shape == res.shape
-        B, C = x.shape[0], x.shape[1]
-        L = x.numel() // (B * C)
-        dev = x.device
-        mean = torch.empty(C, dtype=torch.float32, device=dev)
-        invstd = torch.empty_like(mean)
-        var_u = torch.empty_like(mean)
         y = torch.empty_like(x)
-        work, wb = _bn_ws(C, dev)
-        mom, rm, rv, nbt = _bn_running_args(bn)
-        with torch.cuda.device(dev), timing.span("bn_residual_forward", x.numel() * 12, moved=x.numel() * 16):
+        with torch.cuda.device(x.device), timing.span("bn_residual_forward", x.numel() * 12, moved=x.numel() * 16):
             _lib.check(_lib.load().amc3d_bn_residual_forward(B, C, L, float(eps), mom, _ptr(x), _ptr(res), _ptr(gamma), _ptr(beta),
                                                              _ptr(y), _ptr(mean), _ptr(invstd), _ptr(var_u), rm, rv, nbt,
                                                              _ptr(work), wb, _stream(x)), "bn_residual_forward")
-        ctx.save_for_backward(x, y, gamma, beta, mean, invstd)
-        ctx.mark_non_differentiable(mean, var_u)
-        ctx.set_materialize_grads(False)
-        return y, mean, var_u
+        return _bn_finish(ctx, y, mean, var_u, x, y, gamma, beta, mean, invstd)
 
     @staticmethod
     def backward(ctx, dy, _dm, _dv):
         x, y, gamma, beta, mean, invstd = ctx.saved_tensors
-        B, C = x.shape[0], x.shape[1]
-        L = x.numel() // (B * C)
-        dy = dy.contiguous()
-        dx = torch.empty_like(x)
+        (B, C, L), dy, dx, dgamma, dbeta, (work, wb) = _bn_backward_begin(x, dy, gamma, beta)
         dres = torch.empty_like(x)
-        dgamma = torch.empty_like(gamma)
-        dbeta = torch.empty_like(beta)
-        work, wb = _bn_ws(C, x.device, extra=C * 8)
         with torch.cuda.device(x.device), timing.span("bn_residual_backward", x.numel() * 20, moved=x.numel() * 28):
             _lib.check(_lib.load().amc3d_bn_residual_backward(B, C, L, _ptr(x), _ptr(y), _ptr(dy), _ptr(mean), _ptr(invstd),
                                                               _ptr(gamma), _ptr(beta), _ptr(dx), _ptr(dres), _ptr(dgamma),
@@ -1048,34 +1043,18 @@ class BatchNormSigmoid(Function):
     def forward(ctx, x, gamma, beta, eps, bn=None):
         _need_gpu(x, gamma, beta)
         _need_dtype(torch.float32, x=x, gamma=gamma, beta=beta)
-        x = x.contiguous()
-        B, C = x.shape[0], x.shape[1]
-        L = x.numel() // (B * C)
-        dev = x.device
-        mean = torch.empty(C, dtype=torch.float32, device=dev)
-        invstd = torch.empty_like(mean)
-        var_u = torch.empty_like(mean)
+        x, (B, C, L), (mean, invstd, var_u), (work, wb), (mom, rm, rv, nbt) = _bn_begin(x, bn)
         y = torch.empty_like(x)
-        work, wb = _bn_ws(C, dev)
-        mom, rm, rv, nbt = _bn_running_args(bn)
-        with torch.cuda.device(dev), timing.span("bn_sigmoid_forward", x.numel() * 8, moved=x.numel() * 12):
+        with torch.cuda.device(x.device), timing.span("bn_sigmoid_forward", x.numel() * 8, moved=x.numel() * 12):
             _lib.check(_lib.load().amc3d_bn_sigmoid_forward(B, C, L, float(eps), mom, _ptr(x), _ptr(gamma), _ptr(beta), _ptr(y),
                                                             _ptr(mean), _ptr(invstd), _ptr(var_u), rm, rv, nbt, _ptr(work), wb,
                                                             _stream(x)), "bn_sigmoid_forward")
-        ctx.save_for_backward(x, y, gamma, beta, mean, invstd)
-        ctx.mark_non_differentiable(mean, var_u)
-        ctx.set_materialize_grads(False)
-        return y, mean, var_u
+        return _bn_finish(ctx, y, mean, var_u, x, y, gamma, beta, mean, invstd)
 
     @staticmethod
     def backward(ctx, dy, _dm, _dv):
         x, y, gamma, beta, mean, invstd = ctx.saved_tensors
-        B, C = x.shape[0], x.shape[1]
-        L = x.numel() // (B * C)
-        dy = dy.contiguous()
-        dx = torch.empty_like(x)
-        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
-        work, wb = _bn_ws(C, x.device, extra=C * 8)
+        (B, C, L), dy, dx, dgamma, dbeta, (work, wb) = _bn_backward_begin(x, dy, gamma, beta)
         with torch.cuda.device(x.device), timing.span("bn_sigmoid_backward", x.numel() * 16, moved=x.numel() * 24):
             _lib.check(_lib.load().amc3d_bn_sigmoid_backward(B, C, L, _ptr(x), _ptr(y), _ptr(dy), _ptr(mean), _ptr(invstd),
                                                              _ptr(gamma), _ptr(beta), _ptr(dx), _ptr(dgamma), _ptr(dbeta),
@@ -1100,40 +1079,25 @@ class BatchNormMax(Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, relu, bn=None):
         _need_gpu(x, gamma, beta)
-        x = x.contiguous()
-        B, C, M, K = x.shape
-        dev = x.device
-        mean = torch.empty(C, dtype=torch.float32, device=dev)
-        invstd = torch.empty_like(mean)
-        var_u = torch.empty_like(mean)
-        y = torch.empty(B, C, M, dtype=torch.float32, device=dev)
-        arg = torch.empty(B, C, M, dtype=torch.uint8, device=dev)
-        work, wb = _bn_ws(C, dev)
-        lib = _lib.load()
-        mom, rm, rv, nbt = _bn_running_args(bn)
-        with torch.cuda.device(dev), timing.span("bn_max_forward", x.numel() * 4 + y.numel() * 5, moved=x.numel() * 8 + y.numel() * 5):
-            _lib.check(lib.amc3d_bn_forward(B, C, M * K, K, int(bool(relu)), float(eps), mom, _ptr(x), _ptr(gamma),
-                                            _ptr(beta), _ptr(y), _ptr(arg), _ptr(mean), _ptr(invstd), _ptr(var_u), rm, rv,
-                                            nbt, _ptr(work), wb, _stream(x)), "bn_forward")
-        ctx.save_for_backward(x, gamma, beta, mean, invstd, arg)
+        x, (B, C, L), (mean, invstd, var_u), (work, wb), (mom, rm, rv, nbt) = _bn_begin(x, bn)
+        _, _, M, K = x.shape
+        y = torch.empty(B, C, M, dtype=torch.float32, device=x.device)
+        arg = torch.empty(B, C, M, dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device), timing.span("bn_max_forward", x.numel() * 4 + y.numel() * 5, moved=x.numel() * 8 + y.numel() * 5):
+            _lib.check(_lib.load().amc3d_bn_forward(B, C, L, K, int(bool(relu)), float(eps), mom, _ptr(x), _ptr(gamma),
+                                                    _ptr(beta), _ptr(y), _ptr(arg), _ptr(mean), _ptr(invstd), _ptr(var_u), rm, rv,
+                                                    nbt, _ptr(work), wb, _stream(x)), "bn_forward")
         ctx.relu = bool(relu)
         if _pool_log is not None:
             _pool_log[_next_pool_seq()] = arg
-        ctx.mark_non_differentiable(mean, var_u)
-        ctx.set_materialize_grads(False)  # no zero tensors for the statistics' (absent) gradients
-        return y, mean, var_u
+        return _bn_finish(ctx, y, mean, var_u, x, gamma, beta, mean, invstd, arg)
 
     @staticmethod
     def backward(ctx, dy, _dm, _dv):
         x, gamma, beta, mean, invstd, arg = ctx.saved_tensors
-        B, C, M, K = x.shape
-        dy = dy.contiguous()
-        dx = torch.empty_like(x)
-        dgamma = torch.empty_like(gamma)
-        dbeta = torch.empty_like(beta)
-        work, wb = _bn_ws(C, x.device, extra=C * 8)
+        (B, C, L), dy, dx, dgamma, dbeta, (work, wb) = _bn_backward_begin(x, dy, gamma, beta)
         with torch.cuda.device(x.device), timing.span("bn_max_backward", x.numel() * 4 + dy.numel() * 9, moved=x.numel() * 8 + dy.numel() * 5):
-            _lib.check(_lib.load().amc3d_bn_backward(B, C, M * K, K, int(ctx.relu), _ptr(x), _ptr(dy), _ptr(arg),
+            _lib.check(_lib.load().amc3d_bn_backward(B, C, L, x.shape[-1], int(ctx.relu), _ptr(x), _ptr(dy), _ptr(arg),
                                                      _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(dx),
                                                      _ptr(dgamma), _ptr(dbeta), _ptr(work), wb, _stream(x)),
                        "bn_backward")
@@ -1190,9 +1154,7 @@ class SyncBatchNormFused(Function):
             _lib.check(lib.amc3d_bn_sums(B, C, L, _ptr(x), _ptr(sums), _ptr(work), wb, _stream(x)), "bn_sums")
         from . import graphs
         graphs.collective(lambda: dist.all_reduce(sums, group=group))  # eager, between two captured segments (graphs.py)
-        mean = torch.empty(C, dtype=torch.float32, device=dev)
-        invstd = torch.empty_like(mean)
-        var_u = torch.empty_like(mean)
+        mean, invstd, var_u = _bn_stat_bufs(C, dev)
         if pool:
             y = torch.empty(x.shape[:-1], dtype=torch.float32, device=dev)
             arg = torch.empty(x.shape[:-1], dtype=torch.uint8, device=dev)
@@ -1204,12 +1166,8 @@ class SyncBatchNormFused(Function):
                                                    _ptr(gamma), _ptr(beta), _ptr(y), None if arg is None else _ptr(arg),
                                                    _ptr(mean), _ptr(invstd), _ptr(var_u), rm, rv, nbt, _stream(x)),
                        "bn_forward_synced")
-        saved = [x, gamma, beta, mean, invstd, sums] + ([arg] if pool else [])
-        ctx.save_for_backward(*saved)
         ctx.relu, ctx.pool, ctx.group = bool(relu), bool(pool), group
-        ctx.mark_non_differentiable(mean, var_u)
-        ctx.set_materialize_grads(False)
-        return y, mean, var_u
+        return _bn_finish(ctx, y, mean, var_u, x, gamma, beta, mean, invstd, sums, *([arg] if pool else []))
 
     @staticmethod
     def backward(ctx, dy, _dm, _dv):
@@ -1491,8 +1449,7 @@ class LocalAggregationFused(Function):
         pooled = torch.empty(B, C, M, dtype=torch.float32, device=dev)
         ystar = torch.empty_like(pooled)
         arg = torch.empty(B, C, M, dtype=torch.uint8, device=dev)
-        mean = torch.empty(C, dtype=torch.float32, device=dev)
-        invstd, var_u = torch.empty_like(mean), torch.empty_like(mean)
+        mean, invstd, var_u = _bn_stat_bufs(C, dev)
         gd = torch.empty(C, 3, dtype=torch.float64, device=dev)
         sums = torch.empty(2 * C + 1, dtype=torch.float64, device=dev)
         wb = int(lib.amc3d_local_aggregation_workspace_bytes(B, C, N, M))
@@ -1611,8 +1568,7 @@ class GroupedConvBN(Function):
         g_cm = torch.empty(B, C, N, dtype=torch.float32, device=dev)
         g_pm = torch.empty(B, N, C, dtype=torch.float32, device=dev)
         x1 = torch.empty(B, C, M, K, dtype=torch.float32, device=dev)
-        mean = torch.empty(C, dtype=torch.float32, device=dev)
-        invstd, var_u = torch.empty_like(mean), torch.empty_like(mean)
+        mean, invstd, var_u = _bn_stat_bufs(C, dev)
         gd = torch.empty(C, 3, dtype=torch.float64, device=dev)
         sums = torch.empty(2 * C + 1, dtype=torch.float64, device=dev)
         wb = int(lib.amc3d_local_aggregation_workspace_bytes(B, C, N, M))
@@ -2237,10 +2193,8 @@ class SATail(Function):
         lib = _lib.load()
         assert w2.numel() == C2 * C1 and lib.amc3d_sa_tail_supported(C1, C2, K)
         w2f = w2.reshape(C2, C1).contiguous()
-        mean1 = torch.empty(C1, dtype=torch.float32, device=dev)
-        invstd1, var1 = torch.empty_like(mean1), torch.empty_like(mean1)
-        mean2 = torch.empty(C2, dtype=torch.float32, device=dev)
-        invstd2, var2 = torch.empty_like(mean2), torch.empty_like(mean2)
+        mean1, invstd1, var1 = _bn_stat_bufs(C1, dev)
+        mean2, invstd2, var2 = _bn_stat_bufs(C2, dev)
         pooled = torch.empty(B, C2, M, dtype=torch.float32, device=dev)
         # the raw extreme the pool selected and the neighbour that held it: the backward then recomputes nothing (csrc/sa_tail.hip)
         zext = torch.empty(B, C2, M, dtype=torch.float32, device=dev)
@@ -2320,8 +2274,7 @@ class SATailActivated(Function):
             _identity_bn[key] = (torch.zeros(C1, dtype=torch.float32, device=dev), torch.ones(C1, dtype=torch.float32, device=dev))
         zeros, ones = _identity_bn[key]
         w2f = w2.reshape(C2, C1).contiguous()
-        mean2 = torch.empty(C2, dtype=torch.float32, device=dev)
-        invstd2, var2 = torch.empty_like(mean2), torch.empty_like(mean2)
+        mean2, invstd2, var2 = _bn_stat_bufs(C2, dev)
         pooled = torch.empty(B, C2, M, dtype=torch.float32, device=dev)
         zext = torch.empty(B, C2, M, dtype=torch.float32, device=dev)
         arg = torch.empty(B, C2, M, dtype=torch.uint8, device=dev)

@@ -21,8 +21,9 @@ Route -> case that reaches it (bn_split / bn_channel_form of csrc/bn.hip; tests/
     bn_bwd_apply float4, mode 1 ((ak-k0) < 4u)  max K % 4 == 0;   scalar mode 1: K % 4 != 0
     bn_bwd_apply / bn_bwd_stats ymask loops     residual and sigmoid cases, float4 ((2,3,8200), (8,128,100)) and scalar ((3,7,65), (70,5,37))
     bn_bwd_channel_kernel                       the channel-form cases above
-    running update in bn_fwd_channel_kernel     test_running_statistics[act_channel]
-    running update in bn_channel_stats          test_running_statistics[act_two, max, residual, sigmoid]
+    running update (bn_running_update of csrc/bn_math.h, called from)
+      bn_fwd_channel_kernel                     test_running_statistics[act_channel]
+      bn_channel_stats                          test_running_statistics[act_two, max, residual, sigmoid]
     bn_running_kernel (momentum None)           the same with momentum None; c += 1024 loop: test_cumulative_average_beyond_1024_channels
     momentum None bypasses the channel form     test_running_statistics[act_channel-None] (the channel kernel has no cumulative rule:
                                                 the buffers move only if the two-launch form ran)
