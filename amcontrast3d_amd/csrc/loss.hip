@@ -670,6 +670,89 @@ __global__ __launch_bounds__(256) void contrast_backward_rows_kernel(
     if (r == 0) reinterpret_cast<float4 *>(grad_f)[(size_t)n * LPR + q] = acc;
 }
 
+// The wide form: any C = 4 * C4 up to 256 * P (the widths deterministic mode needs beyond the powers of two above, 512 of
+// PointNeXt-XL among them).  One wave per row n, ONE edge per round, lane q owns the float4 pieces q, q + 64, .. (P of them,
+// those below C4), so a wave reads a neighbour row in contiguous 1 KB pieces; U rounds of rows in flight.  No lane shares an
+// element with another, so there is no cross-lane sum: each output element is the sequential fp32 sum, from +0.0f, over
+// the row's own slots 0..k-1 (a selected anchor only) and then over its reverse list in list order.  The per-edge expression
+// is contrast_backward_rows_kernel's.
+template <int P>
+__global__ __launch_bounds__(256) void contrast_backward_rows_wide_kernel(
+    int m, int C4, int k, int nbr_stride, const float *__restrict__ f, const float *__restrict__ norm,
+    const int *__restrict__ nbr, const float *__restrict__ a, const int *__restrict__ rev,
+    const float *__restrict__ sim, const float *__restrict__ gco, float *__restrict__ grad_f)
+{
+    constexpr int U = 4;  // rounds in flight
+    const int q = threadIdx.x & 63;
+    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= m) return;
+    const float an = a[n];
+    const int own = (0.f < an && an <= 1.f) ? k : 0;
+    const int e0 = rev[n], deg = rev[n + 1] - e0;
+    const int *rev_edge = rev + m + 1;
+    const int total = own + deg;
+    const float4 *f4 = reinterpret_cast<const float4 *>(f);
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 acc[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) acc[p] = zero;
+    if (total > 0) {
+        const float nn = norm[n];
+        float4 fn[P];
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            const int piece = q + 64 * p;
+            fn[p] = piece < C4 ? f4[(size_t)n * C4 + piece] : zero;
+            fn[p].x = __fdiv_rn(fn[p].x, nn); fn[p].y = __fdiv_rn(fn[p].y, nn);
+            fn[p].z = __fdiv_rn(fn[p].z, nn); fn[p].w = __fdiv_rn(fn[p].w, nn);
+        }
+        for (int t0 = 0; t0 < total; t0 += U) {
+            int x[U];
+            float g[U], sv[U], nx[U];
+            float4 v[U][P];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int t = t0 + u;
+                x[u] = -1; g[u] = 0.f; sv[u] = 0.f;
+                if (t < total) {
+                    int pos;
+                    if (t < own) { pos = n * k + t; x[u] = nbr[(size_t)n * nbr_stride + t]; }
+                    else { pos = rev_edge[e0 + t - own]; x[u] = pos / k; }
+                    g[u] = gco[pos];
+                    sv[u] = sim[pos];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                nx[u] = x[u] >= 0 ? norm[x[u]] : 1.f;
+#pragma unroll
+                for (int p = 0; p < P; ++p) {
+                    const int piece = q + 64 * p;
+                    v[u][p] = (x[u] >= 0 && piece < C4) ? f4[(size_t)x[u] * C4 + piece] : zero;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (x[u] < 0) continue;
+                const float gn = g[u] / nn;
+                const float sn = nn > 1e-8f ? sv[u] : 0.f;  // (no projection below the clamp)
+#pragma unroll
+                for (int p = 0; p < P; ++p) {
+                    acc[p].x += gn * (__fdiv_rn(v[u][p].x, nx[u]) - sn * fn[p].x);
+                    acc[p].y += gn * (__fdiv_rn(v[u][p].y, nx[u]) - sn * fn[p].y);
+                    acc[p].z += gn * (__fdiv_rn(v[u][p].z, nx[u]) - sn * fn[p].z);
+                    acc[p].w += gn * (__fdiv_rn(v[u][p].w, nx[u]) - sn * fn[p].w);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        const int piece = q + 64 * p;
+        if (piece < C4) reinterpret_cast<float4 *>(grad_f)[(size_t)n * C4 + piece] = acc[p];
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Contrast backward over the MUTUAL edges (round 3; the default).  91 % of the edges of the stages' 24-NN graphs are mutual
 // (x in N(n) and n in N(x)), and everything an edge contributes is symmetric in its two ends: the cosine s_nx = s_xn (the
@@ -850,7 +933,7 @@ __global__ __launch_bounds__(256) void contrast_backward_mutual_kernel(
 // (kernel-uniform branches, no template per combination); the kernels of the default form above are untouched, what is
 // shared with them is copied.  Three steps forward -- the cosines alone (contrast_sim_*), the per-anchor loss from the
 // stored cosines (contrast_variant_loss_kernel), masked_mean_kernel -- and two backward: g_ij = dL/ds_ij
-// (contrast_variant_coef_kernel), then the gradient rows from g by contrast_backward_rows_kernel (a gather over reverse
+// (contrast_variant_coef_kernel), then the gradient rows from g by contrast_backward_rows_kernel or its wide form (a gather over reverse
 // lists, which knows nothing of the loss's form) or by contrast_backward_edges_kernel (float atomics, any C <= 512).
 //
 // Per anchor, with z_j = (s_j - [pos] m) / T  (-m),  (s_j + [neg] m) / T  (+m),  s_j / T  (none), e_j = exp(z_j),
@@ -1498,6 +1581,31 @@ AMC_API int amc3d_contrast_backward_csr_supported(int C)
     return C == 16 || C == 32 || C == 64 || C == 128 || C == 256;
 }
 
+AMC_API int amc3d_contrast_backward_rows_supported(int C) { return C % 4 == 0 && C >= 4 && C <= 512; }
+
+// gradient rows from gco over the reverse lists: the power-of-two widths on their kernels, every other width of
+// amc3d_contrast_backward_rows_supported on the wide one
+static void contrast_rows_launch(int m, int C, int k, int nbr_stride, const float *f, const float *norm, const int *nbr,
+                                 const float *a, const int *rev, const float *sim, const float *gco, float *grad_f,
+                                 hipStream_t stream)
+{
+#define AMC_BWD(LPR)                                                                                                  \
+    hipLaunchKernelGGL((contrast_backward_rows_kernel<LPR>), dim3(div_up(m, 4)), dim3(256), 0, stream, m, k, nbr_stride, f, \
+                       norm, nbr, a, rev, sim, gco, grad_f)
+#define AMC_BWD_WIDE(P)                                                                                               \
+    hipLaunchKernelGGL((contrast_backward_rows_wide_kernel<P>), dim3(div_up(m, 4)), dim3(256), 0, stream, m, C / 4, k,  \
+                       nbr_stride, f, norm, nbr, a, rev, sim, gco, grad_f)
+    if (C == 16) AMC_BWD(4);
+    else if (C == 32) AMC_BWD(8);
+    else if (C == 64) AMC_BWD(16);
+    else if (C == 128) AMC_BWD(32);
+    else if (C == 256) AMC_BWD(64);
+    else if (C < 256) AMC_BWD_WIDE(1);
+    else AMC_BWD_WIDE(2);
+#undef AMC_BWD_WIDE
+#undef AMC_BWD
+}
+
 AMC_API int amc3d_contrast_backward_csr(int m, int C, int k, int nbr_stride, const float *f, const float *norm,
                                         const int *nbr, const unsigned char *posmask, const float *a, const int *sel,
                                         const int *rev, float mu, float nu, float temperature, const float *sim,
@@ -1505,21 +1613,13 @@ AMC_API int amc3d_contrast_backward_csr(int m, int C, int k, int nbr_stride, con
                                         void *stream_)
 {
     if (m <= 0) return 0;
-    if (!amc3d_contrast_backward_csr_supported(C) || k <= 0 || nbr_stride < k || !f || !norm || !nbr || !posmask || !a ||
+    if (!amc3d_contrast_backward_rows_supported(C) || k <= 0 || nbr_stride < k || !f || !norm || !nbr || !posmask || !a ||
         !sel || !rev || !sim || !mean_cnt || !grad_out || !gco || !grad_f || (((uintptr_t)f | (uintptr_t)grad_f) & 15))
-        return bad_arg("amc3d_contrast_backward_csr: bad argument (C must be 16, 32, 64, 128 or 256; 16-byte aligned rows)");
+        return bad_arg("amc3d_contrast_backward_csr: bad argument (C must be a multiple of 4 in 4..512; 16-byte aligned rows)");
     hipStream_t stream = (hipStream_t)stream_;
     hipLaunchKernelGGL(contrast_coef_kernel, dim3(div_up((long)m * 32, 256)), dim3(256), 0, stream, m, k, posmask, a, sel, mu,
                        nu, temperature, sim, mean_cnt, grad_out, gco);
-#define AMC_BWD(LPR)                                                                                                  \
-    hipLaunchKernelGGL((contrast_backward_rows_kernel<LPR>), dim3(div_up(m, 4)), dim3(256), 0, stream, m, k, nbr_stride, f, \
-                       norm, nbr, a, rev, sim, (const float *)gco, grad_f)
-    if (C == 16) AMC_BWD(4);
-    else if (C == 32) AMC_BWD(8);
-    else if (C == 64) AMC_BWD(16);
-    else if (C == 128) AMC_BWD(32);
-    else AMC_BWD(64);
-#undef AMC_BWD
+    contrast_rows_launch(m, C, k, nbr_stride, f, norm, nbr, a, rev, sim, gco, grad_f, stream);
     return launch_status("amc3d_contrast_backward_csr");
 }
 
@@ -1577,23 +1677,15 @@ AMC_API int amc3d_contrast_variant_backward(int m, int C, int k, int nbr_stride,
     if (C <= 0 || C > 512 || k <= 0 || nbr_stride < k || !f || !norm || !nbr || !posmask || !a || !sim || !mean_cnt ||
         !grad_out || !gco || !grad_f || !contrast_form_ok(margin_mode, db, method, has_temperature, temperature))
         return bad_arg("amc3d_contrast_variant_backward: bad argument (C in 1..512, margin_mode 0..2, db 0..2, method 1..2)");
-    if (rev && (!sel || !amc3d_contrast_backward_csr_supported(C) || (((uintptr_t)f | (uintptr_t)grad_f) & 15) ||
+    if (rev && (!sel || !amc3d_contrast_backward_rows_supported(C) || (((uintptr_t)f | (uintptr_t)grad_f) & 15) ||
                 (long)m * k > 0x7fffffffL))
-        return bad_arg("amc3d_contrast_variant_backward: rev needs sel, C in {16, 32, 64, 128, 256} and 16-byte aligned rows");
+        return bad_arg("amc3d_contrast_variant_backward: rev needs sel, C a multiple of 4 in 4..512 and 16-byte aligned rows");
     hipStream_t stream = (hipStream_t)stream_;
     const ContrastForm F{margin_mode, db, method, has_temperature, mu, nu, temperature};
     hipLaunchKernelGGL(contrast_variant_coef_kernel, dim3(div_up((long)m * 32, 256)), dim3(256), 0, stream, m, k, posmask, a, sel,
                        F, sim, mean_cnt, grad_out, gco);
     if (rev) {
-#define AMC_BWD(LPR)                                                                                                  \
-    hipLaunchKernelGGL((contrast_backward_rows_kernel<LPR>), dim3(div_up(m, 4)), dim3(256), 0, stream, m, k, nbr_stride, f, \
-                       norm, nbr, a, rev, sim, (const float *)gco, grad_f)
-        if (C == 16) AMC_BWD(4);
-        else if (C == 32) AMC_BWD(8);
-        else if (C == 64) AMC_BWD(16);
-        else if (C == 128) AMC_BWD(32);
-        else AMC_BWD(64);
-#undef AMC_BWD
+        contrast_rows_launch(m, C, k, nbr_stride, f, norm, nbr, a, rev, sim, gco, grad_f, stream);
     } else {
 #define AMC_BWD(LPA, VPT)                                                                                                 \
     hipLaunchKernelGGL((contrast_backward_edges_kernel<LPA, VPT>), dim3(div_up((long)m * LPA, 256)), dim3(256), 0, stream, \

@@ -722,7 +722,9 @@ class ContrastStage(Function):
             rev = None  # (a width the row kernels do not cover: the atomic form below; rev holds non-mutual edges only)
         if ctx.det:
             anchors, rev = _contrast_lists("contrast_backward", C, nbr, a, anchors, rev)
-        if rev is not None and lib.amc3d_contrast_backward_csr_supported(C):
+        # (default mode keeps the atomic form at the widths without a power-of-two row kernel; the wide one is unmeasured there)
+        if rev is not None and (lib.amc3d_contrast_backward_csr_supported(C)
+                                or (ctx.det and lib.amc3d_contrast_backward_rows_supported(C))):
             grad_f = torch.empty_like(f)  # every row is written
             gco = torch.empty(m * k, dtype=torch.float32, device=f.device)
             with torch.cuda.device(f.device), timing.span("contrast_backward_csr", m * C * 8 + m * k * 17, moved=m * C * 4 * (2 + 2 * k) + m * k * 17):
@@ -742,8 +744,8 @@ class ContrastStage(Function):
 
 def _contrast_lists(op, C, nbr, a, anchors, rev):
     """deterministic mode: the (anchors, reverse lists of all their edges) a gathering contrast backward needs, built here
-    where the stage's plan has none; a width without row kernels has only the atomic form"""
-    if not _lib.load().amc3d_contrast_backward_csr_supported(C):
+    where the stage's plan has none; a width without row kernels (no multiple of 4, or above 512) has only the atomic form"""
+    if not _lib.load().amc3d_contrast_backward_rows_supported(C):
         raise _no_route(op, f"the reverse-list backward does not cover {C} channels")
     if rev is None:
         if anchors is None:
@@ -815,7 +817,8 @@ class ContrastStageVariant(Function):
     'learned', db '-m' / '+m' / anything else (no shift), supervisedCL 'Method1' / 'Method2', temperature a number or None --
     the config's own values.  anchors: select_anchors(a) or None.  rev: contrast_csr(neighbor_idx, anchors), the reverse lists
     of ALL edges of the selected anchors (never contrast_mutual's, which hold the non-mutual edges only); with it and a width
-    of the row kernels the backward gathers every gradient row, otherwise it scatters with float atomics."""
+    of the row kernels (16/32/64/128/256; in deterministic mode every multiple of 4 up to 512, lists built where rev is None)
+    the backward gathers every gradient row, otherwise it scatters with float atomics."""
 
     @staticmethod
     def forward(ctx, features, neighbor_idx, posmask, a, margin, db, supervisedCL, mu, nu, temperature, anchors=None, rev=None):
@@ -842,7 +845,8 @@ class ContrastStageVariant(Function):
             if f.data_ptr() % 16:
                 raise _no_route("contrast_variant_backward", "the reverse-list backward needs 16-byte aligned rows")
             anchors, rev = _contrast_lists("contrast_variant_backward", C, nbr, a, anchors, rev)
-        gather = rev is not None and bool(lib.amc3d_contrast_backward_csr_supported(C)) and f.data_ptr() % 16 == 0
+        gather = (rev is not None and f.data_ptr() % 16 == 0 and bool(
+            lib.amc3d_contrast_backward_csr_supported(C) or (ctx.det and lib.amc3d_contrast_backward_rows_supported(C))))
         grad_f = torch.empty_like(f) if gather else torch.zeros_like(f)  # (the gather writes every row)
         gco = torch.empty(m * k, dtype=torch.float32, device=f.device)
         name = "contrast_variant_backward_csr" if gather else "contrast_variant_backward"

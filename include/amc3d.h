@@ -227,11 +227,20 @@ int amc3d_contrast_backward(int m, int C, int k, int nbr_stride, const float *f,
  * MarginContrast.py:250-257 through autograd's index_put backward): fixed summation order, every row of grad_f WRITTEN
  * once (no zero-initialisation).  rev = [rev_start (m+1) | rev_edge (m*k)] int32 from amc3d_contrast_csr: the positions
  * i*k + j, ascending, of the selected anchors i whose neighbour j is row n; built with the stage's plan (coordinates and
- * labels only).  gco: m*k floats of scratch (dL/ds per edge).  C in {16, 32, 64, 128, 256}. */
+ * labels only).  gco: m*k floats of scratch (dL/ds per edge).  16-byte aligned rows, and a width C with
+ * amc3d_contrast_backward_rows_supported(C): C % 4 == 0 and 4 <= C <= 512.
+ * Summation order (part of the contract: deterministic mode promises the bits):
+ *   C in {16, 32, 64, 128, 256} (amc3d_contrast_backward_csr_supported; the same predicate gates the unit-row forward, the
+ *     channel-major stage and the mutual-edge backward): R = 256 / C edges per round on R groups of C/4 lanes; group r sums
+ *     the edges t = r, r + R, .. sequentially from +0.0f, then the groups' sums are added in a butterfly (xor C/4, .., 32).
+ *   every other supported width: each output element is the sequential fp32 sum from +0.0f over the edges t = 0, 1, ..
+ *   In both, the edges of row n are numbered: its own slots 0..k-1 (only if n is a selected anchor), then its reverse list
+ *   in list order, which is ascending position.  A row with no edge receives +0.0f. */
 size_t amc3d_contrast_csr_workspace_bytes(int m);
 int amc3d_contrast_csr(int m, int k, int nbr_stride, const int *nbr, const int *sel, int *rev, void *workspace,
                        size_t workspace_bytes, void *stream);
 int amc3d_contrast_backward_csr_supported(int C);
+int amc3d_contrast_backward_rows_supported(int C);
 int amc3d_contrast_backward_csr(int m, int C, int k, int nbr_stride, const float *f, const float *norm, const int *nbr,
                                 const unsigned char *posmask, const float *a, const int *sel, const int *rev, float mu,
                                 float nu, float temperature, const float *sim, const float *mean_cnt,
@@ -274,8 +283,8 @@ int amc3d_contrast_backward_mutual(int m, int C, int k, int nbr_stride, const fl
  *   (m,k) -- required here -- holds the same bits; loss_pt (m) and mean_cnt (2) as there.
  * backward: gco (m*k floats of scratch) receives dL/ds per edge of the visited anchors; then
  *   rev != NULL (from amc3d_contrast_csr: ALL edges of the selected anchors; never the lists of amc3d_contrast_mutual):
- *     the gather of amc3d_contrast_backward_csr -- needs sel, C in {16, 32, 64, 128, 256} and 16-byte aligned rows; every row
- *     of grad_f is written, no zero-initialisation;
+ *     the gather of amc3d_contrast_backward_csr, in its summation order -- needs sel, amc3d_contrast_backward_rows_supported(C)
+ *     and 16-byte aligned rows; every row of grad_f is written, no zero-initialisation;
  *   rev == NULL: float atomics as amc3d_contrast_backward, C <= 512, the caller zero-initialises grad_f.
  * No allocation, no synchronisation. */
 int amc3d_contrast_variant_forward(int m, int C, int k, int nbr_stride, const float *f, const int *nbr,

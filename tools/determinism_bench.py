@@ -1,5 +1,6 @@
-"""What deterministic mode costs: GraphPipeline ms per step with the mode off and on, and the three reverse-list kernels
-beside the float-atomic kernels they stand in for at the shapes of that step (device events, 50 calls each).
+"""What deterministic mode costs: GraphPipeline ms per step with the mode off and on, and the reverse-list kernels (three
+gathers and the contrast backward at the coarsest loss stage) beside the float-atomic kernels they stand in for at the shapes
+of that step (device events, 50 calls each).
 
     python tools/determinism_bench.py [--config S|XL|both] [--steps K] [--warmup W] [--kernels-only] [--steps-only]
 
@@ -129,6 +130,25 @@ def kernels(variant, batch, points):
             out.append({"kernel": "local_aggregation_backward (+ the conv's backward, both forms alike)", "variant": variant,
                         "shape": {"b": batch, "c": C, "n": N, "npoints": N, "nsample": 32}, **res,
                         "group_csr": timed(lambda: ops.group_csr(idx, N))})
+    # contrast loss backward at the coarsest loss stage (N / 64 points per cloud, 8 x width channels, 23 neighbours):
+    # float atomics (default mode at a width without a power-of-two row kernel) against the gather over reverse lists
+    xyz = p[3].view(-1, 3).contiguous()
+    m, C, k = xyz.shape[0], width * 8, 23
+    o = torch.arange(1, batch + 1, dtype=torch.int32, device=DEV) * p[3].shape[1]
+    nbr = ops.knnquery(k + 1, xyz, xyz, o, o)[0][:, 1:]
+    lab = torch.randint(0, 13, (m,), generator=g, dtype=torch.int32).to(DEV)
+    posmask = ops.posmask_from_labels(lab, nbr)
+    a = torch.rand(m, generator=g).to(DEV)
+    anchors = ops.select_anchors(a)
+    rev = ops.contrast_csr(nbr, anchors)
+    f = torch.randn(m, C, generator=g).to(DEV).requires_grad_(True)
+    res = {}
+    for name, det, extra in (("atomic", False, (anchors,)), ("csr", True, (anchors, rev))):
+        with ops.deterministic_mode(det):
+            y = ops.contrast_stage(f, nbr, posmask, a, -1.0, 0.5, 0.3, *extra)
+        res[name] = timed(lambda: torch.autograd.grad(y, f, retain_graph=True))
+    out.append({"kernel": "contrast_backward", "variant": variant, "shape": {"m": m, "C": C, "k": k}, **res,
+                "contrast_csr": timed(lambda: ops.contrast_csr(nbr, anchors))})
     # refinement backward at the decoder's finest level
     D, n, k = width, points, 11
     B = batch
