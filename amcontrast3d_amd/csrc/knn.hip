@@ -138,7 +138,8 @@ __global__ __launch_bounds__(KNN_WAVES * 64) void knn_exact_kernel(
 // list holds.  When two of them are EQUAL the reference's output depends on its heap history
 // (index scan order); such queries are detected (adjacent equal values in the list, or the best
 // rejected distance equal to the k-th) and recomputed by knn_exact_kernel, which replays the
-// reference's heap.  Distances are always the reference's expression (dist2_ref).
+// reference's heap.  Distances are always the reference's expression (dist2_ref).  For k <= 32 a wavefront serves
+// two queries, 32 lanes each (kg_query_group_kernel, further down): same search, same lists.
 //
 // Cell size.  h is calibrated on the data, per call: 64 sample queries get an estimate of their k-th
 // neighbour distance from a brute-force scan of every 4th support point (one workgroup each), and
@@ -150,6 +151,7 @@ __global__ __launch_bounds__(KNN_WAVES * 64) void knn_exact_kernel(
 // =============================================================================================
 constexpr int KG_SAMPLES = 64;
 constexpr int KG_MAXK = 64;
+constexpr int KGG_MAXK = 32;  // up to here a wavefront serves two queries (kg_query_group_kernel<32>)
 
 struct GridParams {
     float minx, miny, minz, h, inv_h, margin;
@@ -624,6 +626,234 @@ __global__ __launch_bounds__(256) void kg_query_kernel(int m, int k, int nb, int
         } else if (lane < k) {
             idx[(size_t)q * k + lane] = l.id;
             dist2[(size_t)q * k + lane] = l.v;
+        }
+    }
+}
+
+// ---- several queries per wavefront (k <= G) ----------------------------------------------------------------
+// kg_query_kernel holds a 64-lane wave slot per query although at most k lanes carry list entries.  Here a wave is
+// cut into 64/G groups of G lanes and every group runs kg_query_kernel's search for a query of its own: same
+// shells, same packed candidate steps (G wide), same sorted lane list (lanes 0..k-1 of the GROUP; steps with many
+// passing candidates enter it by a sort and merge, see gl_merge), same two tie conditions and the same replay list.
+// What a non-tied query stores is determined by the input alone (the k nearest in ascending distance), so both
+// kernels store the same bits.
+//
+// Every cross-lane operation stays wave-wide and every branch around one is wave-uniform (exec is always full):
+// ballots are taken over the wave and a group reads its own G bits; values that kg_query_kernel keeps wave-uniform
+// in SGPRs (tau, the rejected minimum, the query and its cell) are group-uniform VGPRs here, broadcast with
+// __shfl(x, src, G); loops run while ANY group of the wave has work and a group without work is predicated off
+// (`act`, zero-length runs, an empty pass mask), which leaves its list and its rejected minimum untouched.
+template <int G>
+__device__ __forceinline__ unsigned grp_bits(unsigned long long wave_mask, int lane)
+{
+    static_assert(G == 16 || G == 32, "group width");
+    return (unsigned)(wave_mask >> (lane & ~(G - 1))) & (G == 32 ? 0xffffffffu : 0xffffu);
+}
+
+// insert (cd, ci) into the lists of the groups with `ins` set (there cd < tau); the others keep theirs
+template <int G>
+__device__ __forceinline__ void gl_insert(LaneList &l, int k, int lane, int gl, bool ins, float cd, int ci)
+{
+    const int p = (int)__popc(grp_bits<G>(__ballot(gl < k && l.v <= cd), lane));  // first lane of the group with v > cd
+    // wave_shr:1 hands a group's lane 0 the value of the previous group's last lane; lane 0 never takes the
+    // shifted value (gl > p fails there: p >= 0), so nothing crosses from one query's list into another's
+    const float upv = lane_below_f32(l.v);
+    const int upi = lane_below_i32(l.id);
+    if (ins && gl > p) { l.v = upv; l.id = upi; }
+    if (ins && gl == p) { l.v = cd; l.id = ci; }
+    l.tau = __shfl(l.v, k - 1, G);
+}
+
+// the candidates in `mine` (this group's G bits of the pass ballot), one after the other in lane order;
+// ru / rl track rejected distances as in ll_feed
+template <int G>
+__device__ __forceinline__ void gl_feed(LaneList &l, int k, int lane, int gl, unsigned mine, float d2, int ci, float &rej_uni)
+{
+    while (__ballot(mine != 0)) {  // wave-uniform: some group still has a candidate
+        const bool has = mine != 0;
+        const int b = has ? (int)__builtin_ctz(mine) : 0;
+        mine &= mine - 1;
+        const float cd = __shfl(d2, b, G);
+        const int cc = __shfl(ci, b, G);
+        const bool ins = has && cd < l.tau;  // tau may have dropped below it since the ballot
+        const float evicted = l.tau;
+        gl_insert<G>(l, k, lane, gl, ins, cd, cc);
+        rej_uni = fminf(rej_uni, has ? (ins ? evicted : cd) : 3.4e38f);
+    }
+}
+
+// one compare-exchange stage of a bitonic network inside the groups (stride < G: the partner is in the same group).
+// The keys are the bit patterns of non-negative floats, which order as integers do: integer min / max, no branch.
+__device__ __forceinline__ void gl_cmpx(int &key, int &id, int stride, bool take_min)
+{
+    const int ok = __shfl_xor(key, stride, 64), oi = __shfl_xor(id, stride, 64);
+    const int nk = take_min ? min(key, ok) : max(key, ok);
+    id = nk != key ? oi : id;  // equal keys: both lanes keep their own entry
+    key = nk;
+}
+
+// All passing candidates of a step at once, where one-by-one insertion (kg_query_kernel's way: ~45 instructions and
+// two cross-lane round trips each here) would take longer: with G candidates per step the first steps of a query
+// pass most of theirs (the first one all).  The group's candidates are sorted DESCENDING (bitonic network, lanes
+// without a passing candidate carry 3.4e38), set against the ascending list lane by lane -- the smaller of each
+// pair are the G smallest of both and form a bitonic sequence, the larger are dropped -- and one bitonic merge
+// sorts them.  This is ll_sort_first for a list that may already hold entries: an empty list (placeholders 1e10,
+// start) needs no case of its own.  Entries beyond the k-th are dropped as well; every dropped distance goes to
+// the lane's rejected minimum, as ll_feed's rejected and evicted ones do.
+template <int G>
+__device__ __forceinline__ void gl_merge(LaneList &l, int k, int gl, bool pass, float d2, int ci, float &rej_lane)
+{
+    const int far = __float_as_int(3.4e38f);
+    int key = pass ? __float_as_int(d2) : far, id = ci;
+#pragma unroll
+    for (int size = 2; size <= G; size <<= 1) {
+        const bool up = size < G && (gl & size) == 0;  // alternating below G, the whole group descending
+#pragma unroll
+        for (int stride = size >> 1; stride > 0; stride >>= 1) gl_cmpx(key, id, stride, ((gl & stride) == 0) == up);
+    }
+    const int lk = gl < k ? __float_as_int(l.v) : far;  // lanes beyond the list hold nothing
+    const bool cand = key < lk;
+    rej_lane = fminf(rej_lane, __int_as_float(cand ? lk : key));
+    key = cand ? key : lk;
+    id = cand ? id : l.id;
+#pragma unroll
+    for (int stride = G / 2; stride > 0; stride >>= 1) gl_cmpx(key, id, stride, (gl & stride) == 0);
+    l.v = __int_as_float(key);
+    l.id = id;
+    if (gl >= k) rej_lane = fminf(rej_lane, l.v);
+    l.tau = __shfl(l.v, k - 1, G);
+}
+
+constexpr int KGG_MERGE_FROM = 4;  // passing candidates of a step (the fuller group's) from which gl_merge is used
+
+// kg_scan_packed for groups: lane gl of a group owns run [b, b + len) of that group's query (len == 0 where the
+// group is finished or the lane has no run); G candidates per group and step
+template <int G>
+__device__ __forceinline__ void gl_scan_packed(LaneList &l, int k, int lane, int gl, int b, int len, float qx, float qy,
+                                               float qz, const float4 *__restrict__ sorted, float &rl, float &ru)
+{
+    int incl = len;
+#pragma unroll
+    for (int s = 1; s < G; s <<= 1) {
+        const int o = __shfl_up(incl, s, G);
+        if (gl >= s) incl += o;
+    }
+    const int total = __shfl(incl, G - 1, G);  // group-uniform
+    const int boff = b - (incl - len);         // run start minus the run's first candidate slot
+    int wtotal = 0;                            // wave-uniform loop bound: the longest group
+#pragma unroll
+    for (int gq = 0; gq < 64 / G; ++gq) wtotal = max(wtotal, __builtin_amdgcn_readlane(incl, gq * G + G - 1));
+    for (int c0 = 0; c0 < wtotal; c0 += G) {
+        const int c = c0 + gl;
+        const bool valid = c < total;  // a group that has run out of candidates feeds nothing
+        // the run of slot c is the first lane of the group whose inclusive sum exceeds c (an empty run never is):
+        // binary search over the non-decreasing sums
+        int j = 0;
+#pragma unroll
+        for (int s = G / 2; s >= 1; s >>= 1) j += __shfl(incl, j + s - 1, G) <= c ? s : 0;
+        const int src = __shfl(boff, j, G) + c;  // j <= G - 1 where valid
+        const float4 p = sorted[valid ? src : 0];
+        const float d2 = dist2_ref(qx, qy, qz, p.x, p.y, p.z);
+        const bool pass = valid && d2 < l.tau;
+        rl = fminf(rl, (valid && !pass) ? d2 : 3.4e38f);
+        const unsigned long long wpass = __ballot(pass);
+        int most = 0;  // wave-uniform: passing candidates of the fullest group
+#pragma unroll
+        for (int gq = 0; gq < 64 / G; ++gq) most = max(most, (int)__popc(grp_bits<G>(wpass, gq * G)));
+        if (most >= KGG_MERGE_FROM) gl_merge<G>(l, k, gl, pass, d2, __float_as_int(p.w), rl);
+        else if (most > 0) gl_feed<G>(l, k, lane, gl, grp_bits<G>(wpass, lane), d2, __float_as_int(p.w), ru);
+    }
+}
+
+// (waves_per_eu: left alone the compiler takes 65 registers, one over what eight waves per SIMD allow; held to eight
+// it takes 62 and spills nothing)
+template <int G>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void kg_query_group_kernel(
+                                                             int m, int k, int nb, int self,
+                                                             const float *__restrict__ new_xyz,
+                                                             const int *__restrict__ offset,
+                                                             const int *__restrict__ new_offset,
+                                                             const GridParams *__restrict__ gp,
+                                                             const int *__restrict__ cell_start,
+                                                             const float4 *__restrict__ sorted, int *__restrict__ idx,
+                                                             float *__restrict__ dist2, int *__restrict__ fb_list,
+                                                             int *__restrict__ fb_count)
+{
+    constexpr int NG = 64 / G;
+    const int lane = threadIdx.x & 63, gl = lane & (G - 1);
+    const GridParams g = *gp;
+    for (int t0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * NG; t0 < m; t0 += gridDim.x * 4 * NG) {
+        // self searches: the wave's queries are consecutive entries of sorted[], i.e. the groups walk the same cells.
+        // The last wave's missing queries (m % NG != 0) shadow the wave's first one in lockstep and store nothing.
+        const int t = t0 + lane / G;
+        const bool live = t < m;
+        const int tq = live ? t : t0;
+        const int q = self ? __float_as_int(sorted[tq].w) : tq;
+        const int seg = nb > 1 ? seg_of(q, new_offset, nb) : 0;
+        const int start = seg == 0 ? 0 : offset[seg - 1];
+        const float qx = new_xyz[(size_t)q * 3], qy = new_xyz[(size_t)q * 3 + 1], qz = new_xyz[(size_t)q * 3 + 2];
+        const int cx = cell_coord(qx, g.minx, g.inv_h, g.nx), cy = cell_coord(qy, g.miny, g.inv_h, g.ny),
+                  cz = cell_coord(qz, g.minz, g.inv_h, g.nz);
+        const int *cs = cell_start + (size_t)seg * g.ncell;
+        LaneList l;
+        ll_init(l, start);  // a segment with fewer than k points leaves the placeholders (1e10, start) at the tail
+        float rl = 3.4e38f, ru = 3.4e38f;
+        bool act = true;  // group-uniform: this group's search goes on
+
+        for (int R = 1;; ++R) {
+            // the shell's (dz,dy) pairs as in kg_query_kernel, G per batch: the 9 pairs of R == 1 and the 25 of
+            // R == 2 fit one batch of 32
+            const int side = 2 * R + 1, npairs = side * side;
+            for (int p0 = 0; p0 < npairs; p0 += G) {
+                const int pi = p0 + gl;
+                int bA = 0, eA = 0, bB = 0, eB = 0;
+                if (act && pi < npairs) {
+                    const int dz = pi / side - R, dy = pi % side - R;
+                    const int z = cz + dz, y = cy + dy;
+                    if (z >= 0 && z < g.nz && y >= 0 && y < g.ny) {
+                        const int row = (z * g.ny + y) * g.nx;
+                        const bool rim = R == 1 || dz == -R || dz == R || dy == -R || dy == R;
+                        if (rim) {
+                            const int x0 = max(cx - R, 0), x1 = min(cx + R, g.nx - 1);
+                            bA = cs[row + x0];
+                            eA = cs[row + x1 + 1];
+                        } else {
+                            if (cx - R >= 0) { bA = cs[row + cx - R]; eA = cs[row + cx - R + 1]; }
+                            if (cx + R < g.nx) { bB = cs[row + cx + R]; eB = cs[row + cx + R + 1]; }
+                        }
+                    }
+                }
+                gl_scan_packed<G>(l, k, lane, gl, bA, eA - bA, qx, qy, qz, sorted, rl, ru);
+                if (R > 1) gl_scan_packed<G>(l, k, lane, gl, bB, eB - bB, qx, qy, qz, sorted, rl, ru);
+            }
+            float dmin = 3.4e38f;
+            bool whole = true;
+            if (cx - R > 0) { dmin = fminf(dmin, qx - (g.minx + (float)(cx - R) * g.h)); whole = false; }
+            if (cx + R + 1 < g.nx) { dmin = fminf(dmin, (g.minx + (float)(cx + R + 1) * g.h) - qx); whole = false; }
+            if (cy - R > 0) { dmin = fminf(dmin, qy - (g.miny + (float)(cy - R) * g.h)); whole = false; }
+            if (cy + R + 1 < g.ny) { dmin = fminf(dmin, (g.miny + (float)(cy + R + 1) * g.h) - qy); whole = false; }
+            if (cz - R > 0) { dmin = fminf(dmin, qz - (g.minz + (float)(cz - R) * g.h)); whole = false; }
+            if (cz + R + 1 < g.nz) { dmin = fminf(dmin, (g.minz + (float)(cz + R + 1) * g.h) - qz); whole = false; }
+            dmin -= g.margin;
+            if (whole || (dmin > 0.f && l.tau < dmin * dmin * 0.99999f)) act = false;
+            if (!__ballot(act)) break;  // the wave goes on while any of its groups does
+        }
+
+        // ties among the k+1 smallest distances -> the reference's order depends on its heap history
+#pragma unroll
+        for (int s = G / 2; s >= 1; s >>= 1) rl = fminf(rl, __shfl_xor(rl, s, 64));
+        const float rej = fminf(rl, ru);
+        const float nextv = __shfl_down(l.v, 1, G);
+        const bool tie_in = gl < k - 1 && l.v == nextv && l.v < 1e10f;
+        const bool tie_edge = gl == k - 1 && l.v < 1e10f && rej == l.v;
+        const bool tied = grp_bits<G>(__ballot(tie_in || tie_edge), lane) != 0;
+        if (live) {
+            if (tied) {
+                if (gl == 0) fb_list[atomicAdd(fb_count, 1)] = q;
+            } else if (gl < k) {
+                idx[(size_t)q * k + gl] = l.id;
+                dist2[(size_t)q * k + gl] = l.v;
+            }
         }
     }
 }
@@ -1209,8 +1439,20 @@ AMC_API int amc3d_knnquery(int m, int nsample, int n, int nbatch, const float *x
     float4 *sorted = (float4 *)(base + w.sorted);
     int *fb_list = (int *)(base + w.fb_list);
     const int self = (new_xyz == xyz && m == n && new_offset == offset) ? 1 : 0;
-    hipLaunchKernelGGL(kg_query_kernel, dim3(min(div_up(m, 4), 256 * 32)), dim3(256), 0, stream, m, nsample, nbatch, self,
-                       new_xyz, offset, new_offset, gp, cell_start, sorted, idx, dist2, fb_list, fb_count);
+    if (nsample <= KGG_MAXK) {
+        // Two queries per wavefront, 32 lanes each, for every k <= 32 whatever m: the rule is the input's k alone.
+        // Query kernel alone on the whole chip, the loss's searches at 8 x 24000 points (tools/knn_bench.py, us,
+        // wave per query -> two per wave): self k = 24 over m = 192000 / 48000 / 12000 / 3000: 416 -> 218, 103 -> 57,
+        // 44 -> 29, 27 -> 19; votes over the 192000-point grid, k = 4 m = 48000: 64 -> 45, k = 16 m = 12000: 38 -> 30.
+        // No shape class measured slower, so none keeps the wave-per-query kernel; k in 33..64 has no other.
+        constexpr int per_wg = 4 * (64 / KGG_MAXK);
+        hipLaunchKernelGGL(kg_query_group_kernel<KGG_MAXK>, dim3(min(div_up(m, per_wg), 256 * 32)), dim3(256), 0, stream, m,
+                           nsample, nbatch, self, new_xyz, offset, new_offset, gp, cell_start, sorted, idx, dist2, fb_list,
+                           fb_count);
+    } else {
+        hipLaunchKernelGGL(kg_query_kernel, dim3(min(div_up(m, 4), 256 * 32)), dim3(256), 0, stream, m, nsample, nbatch, self,
+                           new_xyz, offset, new_offset, gp, cell_start, sorted, idx, dist2, fb_list, fb_count);
+    }
     // queries with equal distances among their k+1 nearest: replay the reference's heap
     hipLaunchKernelGGL(knn_exact_list_kernel, dim3(256), dim3(1024), 0, stream, nsample, nbatch, xyz, new_xyz, offset,
                        new_offset, idx, dist2, (const int *)fb_list, (const int *)fb_count, (const GridParams *)gp,
