@@ -15,9 +15,7 @@
 //    torch 2.x's F.cosine_similarity evaluates (MarginContrast.py:77-79).
 #include "common.h"
 
-#ifndef AMC_CONTRAST_DIAG
-#define AMC_CONTRAST_DIAG 0  // 1 / 2: timing-only builds of contrast_backward_kernel (scratch/contrast_diag.sh), never shipped
-#endif
+#include <type_traits>
 
 namespace amc {
 
@@ -191,6 +189,271 @@ __global__ __launch_bounds__(256) void row_unit_cm_kernel(int n, const float *__
 }
 
 // ---------------------------------------------------------------------------------------------
+// What the contrast kernels share.  Several of them must agree to the bit -- contrast_sim_* with contrast_forward_*, the
+// mutual backward's recomputed cosine with the forward's, the per-edge gradient expressions with each other -- so every
+// expression, walk and rule below exists once and the kernels call it.  The library is built with -ffp-contract=off: what
+// is written here is what runs, in this order.
+// ---------------------------------------------------------------------------------------------
+// the anchors that enter the loss (MarginContrast.py:250-252)
+__device__ __forceinline__ bool contrast_selected(float a) { return 0.f < a && a <= 1.f; }
+
+// Prologue of a kernel that runs one lane group per anchor: group w -> anchor i and its ambiguity ai; false past the end.
+// sel = the list of select_anchors below; sel == nullptr: every anchor is visited, and the caller tests ai.
+__device__ __forceinline__ bool contrast_anchor(const int *__restrict__ sel, int m, int w, const float *__restrict__ a, int &i,
+                                                float &ai)
+{
+    if (w >= (sel ? sel[0] : m)) return false;
+    i = sel ? sel[1 + w] : w;
+    ai = a[i];
+    return true;
+}
+
+// the default form (margin 'adaptive', db '-m', Method1, a temperature): margin of an anchor, exponential of a slot, and
+// the factor of dl/ds_j common to an anchor's slots, -scale / ((r + eps) S^2 T) with r = P/S (an anchor without a positive
+// neighbour, P == 0, has a constant loss and a zero gradient: the callers test that and do not use the factor)
+__device__ __forceinline__ float contrast_margin(float mu, float a, float nu) { return __fadd_rn(__fmul_rn(mu, a), nu); }
+
+__device__ __forceinline__ float contrast_exp(float s, bool pos, float margin, float temperature)
+{
+    return expf(__fdiv_rn(pos ? __fsub_rn(s, margin) : s, temperature));
+}
+
+__device__ __forceinline__ float contrast_coef(float scale, float psum, float tsum, float temperature)
+{
+    const float r = psum / tsum;
+    return -scale / ((r + 1e-12f) * tsum * tsum * temperature);
+}
+
+// dL/ds_j of slot j: coef e_j N on a positive, -coef e_j P on a negative
+__device__ __forceinline__ float contrast_edge_g(float coef, float e, bool pos, float nsum, float psum)
+{
+    return coef * e * (pos ? nsum : -psum);
+}
+
+// sum over the 32 lanes of an anchor's group (two groups per wave; xor below 32 stays inside one)
+__device__ __forceinline__ float group32_sum(float v)
+{
+#pragma unroll
+    for (int s = 16; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
+    return v;
+}
+
+// P, N and S of one anchor from its stored cosines, 32 lanes per anchor: slot-local sums over the rounds of 32 slots, then a
+// tree over the lanes (the forward kernels fold their slots in another fixed order; any such order is within rounding of
+// this one).  N = S - P is summed on its own: a positive's coefficient is proportional to it, and tsum - psum loses it to
+// cancellation when the positives dominate (low temperature, r near 1).  Every lane of the group returns the same values.
+struct ContrastSums { float psum, nsum, tsum; };
+
+__device__ __forceinline__ ContrastSums contrast_sums32(int k, int sub, const unsigned char *__restrict__ pm_i,
+                                                        const float *__restrict__ sim_i, float margin, float temperature)
+{
+    ContrastSums r{0.f, 0.f, 0.f};
+    for (int j = sub; j < k; j += 32) {
+        const bool pos = pm_i[j] != 0;
+        const float e = contrast_exp(sim_i[j], pos, margin, temperature);
+        r.psum += pos ? e : 0.f;
+        r.nsum += pos ? 0.f : e;
+        r.tsum += e;
+    }
+    for (int s = 16; s >= 1; s >>= 1) {
+        r.psum += __shfl_xor(r.psum, s, 64);
+        r.nsum += __shfl_xor(r.nsum, s, 64);
+        r.tsum += __shfl_xor(r.tsum, s, 64);
+    }
+    return r;
+}
+
+// The cosine of two raw rows, sum_c (fi[c] / ni) * (fj[c] / nj), any C: four partial sums (a chain of C / 4 additions each,
+// not of C: the cosine's rounding error is multiplied by 1 / T in the exponent)
+__device__ __forceinline__ float row_cosine(const float *__restrict__ fi, const float *__restrict__ fj, float ni, float nj, int C)
+{
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    if ((C & 3) == 0) {
+        for (int c = 0; c < C; c += 4) {
+            const float4 u = *reinterpret_cast<const float4 *>(fi + c);
+            const float4 v = *reinterpret_cast<const float4 *>(fj + c);
+            a0 += __fdiv_rn(u.x, ni) * __fdiv_rn(v.x, nj);
+            a1 += __fdiv_rn(u.y, ni) * __fdiv_rn(v.y, nj);
+            a2 += __fdiv_rn(u.z, ni) * __fdiv_rn(v.z, nj);
+            a3 += __fdiv_rn(u.w, ni) * __fdiv_rn(v.w, nj);
+        }
+    } else {
+        int c = 0;
+        for (; c + 3 < C; c += 4) {
+            a0 += __fdiv_rn(fi[c], ni) * __fdiv_rn(fj[c], nj);
+            a1 += __fdiv_rn(fi[c + 1], ni) * __fdiv_rn(fj[c + 1], nj);
+            a2 += __fdiv_rn(fi[c + 2], ni) * __fdiv_rn(fj[c + 2], nj);
+            a3 += __fdiv_rn(fi[c + 3], ni) * __fdiv_rn(fj[c + 3], nj);
+        }
+        for (; c < C; ++c) a0 += __fdiv_rn(fi[c], ni) * __fdiv_rn(fj[c], nj);
+    }
+    return (a0 + a1) + (a2 + a3);
+}
+
+// four channels of the cosine of two unit rows: one multiply and three fused multiply-adds, the same in the forward and in
+// the backward that recomputes it
+__device__ __forceinline__ float unit_dot4(const float4 &a, const float4 &b)
+{
+    return __fmaf_rn(a.w, b.w, __fmaf_rn(a.z, b.z, __fmaf_rn(a.y, b.y, __fmul_rn(a.x, b.x))));
+}
+
+// The gather over UNIT rows (C == 4 * LPR): LPR lanes read one row as 16-byte pieces, so every wave instruction fetches
+// R = 64/LPR whole rows (full 64-byte sectors), UNIT_U such rounds in flight.  The cosine of a slot is four products and a
+// tree over the row's LPR lanes; every lane of the row then holds it.
+constexpr int UNIT_U = 4;  // rounds in flight (LPR >= UNIT_U: lane q < UNIT_U of a row owns the row's slot of round q)
+
+// rows x[0..UNIT_U) (-1: none) against the row whose piece q this lane holds in u: v = the fetched pieces, s = the cosines
+template <int LPR>
+__device__ __forceinline__ void unit_row_cosines(const float4 *__restrict__ h4, const float4 &u, int q, const int (&x)[UNIT_U],
+                                                 float4 (&v)[UNIT_U], float (&s)[UNIT_U])
+{
+#pragma unroll
+    for (int t = 0; t < UNIT_U; ++t) v[t] = x[t] >= 0 ? h4[(unsigned)x[t] * (unsigned)LPR + (unsigned)q] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int t = 0; t < UNIT_U; ++t) {
+        float acc = unit_dot4(u, v[t]);
+#pragma unroll
+        for (int d = LPR / 2; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+        s[t] = acc;
+    }
+}
+
+// One step of anchor i's walk over its neighbour list, in two halves so that a caller can issue its own per-slot loads
+// between the index loads and the row loads (the fused forward reads the slot's mask there; the order of the loads is part
+// of the generated code).  unit_gather_indices: the neighbours in the slots j0 + t * R + r of the rounds t < UNIT_U (-1 past
+// the end).  unit_gather_rows: their rows fetched, -> the cosine of the slot THIS lane owns, jq = j0 + q * R + r (meaningful
+// where q < UNIT_U and jq < k): a slot's exponential is then evaluated once, by lane q = t of row r, not by all LPR lanes of
+// the row in every round.
+template <int LPR>
+__device__ __forceinline__ void unit_gather_indices(const int *__restrict__ nbr, int i, int nbr_stride, int k, int j0, int r,
+                                                    int (&nb)[UNIT_U])
+{
+#pragma unroll
+    for (int t = 0; t < UNIT_U; ++t) {
+        const int j = j0 + t * (64 / LPR) + r;
+        nb[t] = j < k ? nbr[(size_t)i * nbr_stride + j] : -1;
+    }
+}
+
+template <int LPR>
+__device__ __forceinline__ float unit_gather_rows(const float4 *__restrict__ h4, const float4 &u, int q, const int (&nb)[UNIT_U])
+{
+    float4 v[UNIT_U];
+    float c[UNIT_U];
+    unit_row_cosines<LPR>(h4, u, q, nb, v, c);
+    float s = 0.f;
+#pragma unroll
+    for (int t = 0; t < UNIT_U; ++t) s = q == t ? c[t] : s;
+    return s;
+}
+
+// A row below the norm clamp (|f| < eps: norm[] holds eps) has fhat = f / eps, linear in f: its derivative is fhat_j / eps, with
+// no projection term -- what autograd gives for x / clamp_min(|x|, eps).  All backward forms drop s_j fhat there.  They
+// see the clamped norm only (the test is norm > eps), so a row whose norm is eps to the bit counts as clamped, where
+// clamp_min's gradient would still pass: one fp32 value of the norm.
+__device__ __forceinline__ float contrast_projection(float norm, float s) { return norm > 1e-8f ? s : 0.f; }
+
+// The float-atomic edge walk of contrast_backward_kernel and contrast_backward_edges_kernel: LPA lanes per anchor i, lane
+// `sub` owns channels sub, sub + LPA, ... (VPT of them, C <= LPA * VPT); the neighbours are walked one at a time so every
+// atomic wave-instruction adds LPA contiguous floats of one row (the shape global float atomics run at full rate for), U
+// neighbour rows in flight ahead of the atomics.  The caller produces a chunk of LPA neighbours -- lane `sub` holds what
+// neighbour j0 + sub needs that is not a row: its index nb_l, cosine sj_l, norm nj_l and coefficient g_l = dL/ds_j, one
+// round trip for the chunk -- and chunk() broadcasts those by shuffle.
+//   ds_j/df_i = (fhat_j - s_j fhat_i)/|f_i|,  ds_j/df_j = (fhat_i - s_j fhat_j)/|f_j|   (contrast_projection below the clamp)
+template <int LPA, int VPT>
+struct EdgeWalk {
+    static constexpr int U = VPT >= 8 ? 2 : (VPT >= 4 ? 4 : 8);  // neighbour rows in flight
+    float fhi[VPT], gi[VPT];
+
+    __device__ __forceinline__ void begin(int C, int sub, const float *__restrict__ f, int i, float ni)
+    {
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) {
+            const int c = sub + v * LPA;
+            fhi[v] = c < C ? __fdiv_rn(f[(size_t)i * C + c], ni) : 0.f;
+            gi[v] = 0.f;
+        }
+    }
+
+    // cnt = the chunk's neighbours (<= LPA)
+    __device__ __forceinline__ void chunk(int C, int sub, const float *__restrict__ f, float ni, int cnt, int nb_l, float sj_l,
+                                          float nj_l, float g_l, float *__restrict__ grad_f)
+    {
+        for (int jj = 0; jj < cnt; jj += U) {
+            int nb[U];
+            float fj[U][VPT];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int src = min(jj + u, LPA - 1);
+                const int t = __shfl(nb_l, src, LPA);
+                nb[u] = jj + u < cnt ? t : -1;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int v = 0; v < VPT; ++v) {
+                    const int c = sub + v * LPA;
+                    fj[u][v] = (nb[u] >= 0 && c < C) ? f[(size_t)nb[u] * C + c] : 0.f;
+                }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int src = min(jj + u, LPA - 1);
+                const float g = __shfl(g_l, src, LPA), sj = __shfl(sj_l, src, LPA), nj = __shfl(nj_l, src, LPA);
+                if (nb[u] < 0) continue;
+                const float gin = g / ni, gjn = g / nj;
+                const float si = contrast_projection(ni, sj), sx = contrast_projection(nj, sj);
+#pragma unroll
+                for (int v = 0; v < VPT; ++v) {
+                    const int c = sub + v * LPA;
+                    if (c < C) {
+                        const float fhj = __fdiv_rn(fj[u][v], nj);
+                        gi[v] += gin * (fhj - si * fhi[v]);
+                        atomicAdd(grad_f + (size_t)nb[u] * C + c, gjn * (fhi[v] - sx * fhj));
+                    }
+                }
+            }
+        }
+    }
+
+    __device__ __forceinline__ void finish(int C, int sub, int i, float *__restrict__ grad_f)
+    {
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) {
+            const int c = sub + v * LPA;
+            if (c < C) atomicAdd(grad_f + (size_t)i * C + c, gi[v]);
+        }
+    }
+};
+
+// The reverse-list gather of the rows kernels.  Edge t of row n: its own slot t < own (x = neighbour t of n), else entry
+// t - own of its reverse list (the position i * k + j of an anchor i whose j-th neighbour is n: x = i) -> the other end x,
+// g = dL/ds and s = the cosine of that edge; x = -1 past the end.
+__device__ __forceinline__ void rows_edge(int t, int total, int own, int n, int k, const int *__restrict__ nbr_n,
+                                          const int *__restrict__ rev_n, const float *__restrict__ gco,
+                                          const float *__restrict__ sim, int &x, float &g, float &s)
+{
+    x = -1; g = 0.f; s = 0.f;
+    if (t < total) {
+        int pos;
+        if (t < own) { pos = n * k + t; x = nbr_n[t]; }
+        else { pos = rev_n[t - own]; x = pos / k; }
+        g = gco[pos];
+        s = sim[pos];
+    }
+}
+
+// acc += g/|f_n| * (f_x / |f_x| - s * fhat_n) on four channels (fn = the piece of fhat_n, v of the raw row f_x)
+__device__ __forceinline__ void rows_accumulate(float4 &acc, float g, float s, float nn, const float4 &fn, const float4 &v, float nx)
+{
+    const float gn = g / nn;
+    const float sn = contrast_projection(nn, s);
+    acc.x += gn * (__fdiv_rn(v.x, nx) - sn * fn.x);
+    acc.y += gn * (__fdiv_rn(v.y, nx) - sn * fn.y);
+    acc.z += gn * (__fdiv_rn(v.z, nx) - sn * fn.z);
+    acc.w += gn * (__fdiv_rn(v.w, nx) - sn * fn.w);
+}
+
+// ---------------------------------------------------------------------------------------------
 // The anchors that enter the loss, 0 < a <= 1 (MarginContrast.py:250-252), as a compact ascending list:
 // sel[0] = count, sel[1..count] = anchor ids, sel[m+1..] = per-256-block counts (scratch).  The list depends on
 // coordinates and labels only, so it is built with the stage's plan; the contrast kernels then run one full
@@ -201,7 +464,7 @@ __global__ __launch_bounds__(256) void select_count_kernel(int m, const float *_
 {
     __shared__ int s_cnt[4];
     const int i = blockIdx.x * 256 + threadIdx.x;
-    const bool s = i < m && 0.f < a[i] && a[i] <= 1.f;
+    const bool s = i < m && contrast_selected(a[i]);
     const int c = (int)__popcll(__ballot(s));
     if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = c;
     __syncthreads();
@@ -216,7 +479,7 @@ __global__ __launch_bounds__(256) void select_write_kernel(int m, const float *_
     for (int b = threadIdx.x; b < (int)blockIdx.x; b += 256) before += bc[b];
     for (int s = 32; s >= 1; s >>= 1) before += __shfl_xor(before, s, 64);
     const int i = blockIdx.x * 256 + threadIdx.x;
-    const bool sl = i < m && 0.f < a[i] && a[i] <= 1.f;
+    const bool sl = i < m && contrast_selected(a[i]);
     const unsigned long long mask = __ballot(sl);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (lane == 0) { s_part[wv] = before; s_cnt[wv] = (int)__popcll(mask); }
@@ -229,20 +492,10 @@ __global__ __launch_bounds__(256) void select_write_kernel(int m, const float *_
 }
 
 // ---------------------------------------------------------------------------------------------
-// Contrast forward, one wave per anchor (C == 4 * LPR) over the UNIT rows: LPR lanes read one row as 16-byte pieces, so
-// every wave instruction fetches R = 64/LPR whole rows (full 64-byte sectors), U = 4 such rounds in flight.  The cosine
-// of a slot is four products and a tree over the row's LPR lanes (every lane of the row then holds it); the exponential of
-// slot (round t, row r) is evaluated ONCE, by lane q = t of row r, not by all LPR lanes of the row in every round.
+// Contrast forward, one wave per anchor (C == 4 * LPR) over the UNIT rows (unit_gather_indices / unit_gather_rows above).
 // Same per-element arithmetic as contrast_forward_kernel below (u_c / n_i * (v_c / n_x), channel order of the tree).
 // sel == nullptr: every anchor is visited and tested.
 // ---------------------------------------------------------------------------------------------
-// four channels of the cosine of two unit rows: one multiply and three fused multiply-adds, the same in the forward and in
-// the backward that recomputes it
-__device__ __forceinline__ float unit_dot4(const float4 &a, const float4 &b)
-{
-    return __fmaf_rn(a.w, b.w, __fmaf_rn(a.z, b.z, __fmaf_rn(a.y, b.y, __fmul_rn(a.x, b.x))));
-}
-
 template <int LPR>
 __global__ __launch_bounds__(256) void contrast_forward_unit_kernel(
     int m, int k, int nbr_stride, const float *__restrict__ unit, const int *__restrict__ nbr,
@@ -250,45 +503,28 @@ __global__ __launch_bounds__(256) void contrast_forward_unit_kernel(
     float temperature, float *__restrict__ sim, float *__restrict__ stats, float *__restrict__ loss_pt)
 {
     constexpr int R = 64 / LPR;  // rows per round
-    constexpr int U = 4;         // rounds in flight (LPR >= U: lane q < U of a row owns the row's slot of round q)
     const int lane = threadIdx.x & 63, q = lane & (LPR - 1), r = lane / LPR;
-    const int cnt = sel ? sel[0] : m;
-    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (w >= cnt) return;
-    const int i = sel ? sel[1 + w] : w;
-    const float ai = a[i];
-    if (!(0.f < ai && ai <= 1.f)) {
+    int i;
+    float ai;
+    if (!contrast_anchor(sel, m, blockIdx.x * 4 + (threadIdx.x >> 6), a, i, ai)) return;
+    if (!contrast_selected(ai)) {
         if (lane == 0) loss_pt[i] = 0.f;
         return;
     }
-    const float margin = __fadd_rn(__fmul_rn(mu, ai), nu);
+    const float margin = contrast_margin(mu, ai, nu);
     const float4 *h4 = reinterpret_cast<const float4 *>(unit);
     const float4 u = h4[(size_t)i * LPR + q];
     float psum = 0.f, tsum = 0.f, nsum = 0.f;
-    for (int j0 = 0; j0 < k; j0 += U * R) {
-        int nb[U];
-        float4 v[U];
-#pragma unroll
-        for (int t = 0; t < U; ++t) {
-            const int j = j0 + t * R + r;
-            nb[t] = j < k ? nbr[(size_t)i * nbr_stride + j] : -1;
-        }
+    for (int j0 = 0; j0 < k; j0 += UNIT_U * R) {
+        int nb[UNIT_U];
+        unit_gather_indices<LPR>(nbr, i, nbr_stride, k, j0, r, nb);
         const int jq = j0 + q * R + r;  // the slot this lane evaluates
-        const bool mine = q < U && jq < k;
+        const bool mine = q < UNIT_U && jq < k;
         const bool pos = mine ? posmask[(size_t)i * k + jq] != 0 : false;
-#pragma unroll
-        for (int t = 0; t < U; ++t) v[t] = nb[t] >= 0 ? h4[(unsigned)nb[t] * (unsigned)LPR + (unsigned)q] : make_float4(0.f, 0.f, 0.f, 0.f);
-        float s = 0.f;
-#pragma unroll
-        for (int t = 0; t < U; ++t) {
-            float acc = unit_dot4(u, v[t]);
-#pragma unroll
-            for (int d = LPR / 2; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-            s = q == t ? acc : s;
-        }
+        const float s = unit_gather_rows<LPR>(h4, u, q, nb);
         if (mine) {
             if (sim) sim[(size_t)i * k + jq] = s;
-            const float e = expf(__fdiv_rn(pos ? __fsub_rn(s, margin) : s, temperature));
+            const float e = contrast_exp(s, pos, margin, temperature);
             psum += pos ? e : 0.f;
             nsum += pos ? 0.f : e;
             tsum += e;
@@ -323,16 +559,15 @@ __global__ __launch_bounds__(256) void contrast_forward_kernel(
     float *__restrict__ loss_pt)
 {
     const int sub = threadIdx.x & 31;
-    const int w = (blockIdx.x * blockDim.x + threadIdx.x) >> 5;
-    if (w >= (sel ? sel[0] : m)) return;
-    const int i = sel ? sel[1 + w] : w;
-    const float ai = a[i];
-    if (!(0.f < ai && ai <= 1.f)) {
+    int i;
+    float ai;
+    if (!contrast_anchor(sel, m, (blockIdx.x * blockDim.x + threadIdx.x) >> 5, a, i, ai)) return;
+    if (!contrast_selected(ai)) {
         if (sub == 0) loss_pt[i] = 0.f;
         return;
     }
     const float ni = norm[i];
-    const float margin = __fadd_rn(__fmul_rn(mu, ai), nu);
+    const float margin = contrast_margin(mu, ai, nu);
     const float *fi = f + (size_t)i * C;
     float psum = 0.f, tsum = 0.f;
     for (int j0 = 0; j0 < k; j0 += 32) {
@@ -342,34 +577,10 @@ __global__ __launch_bounds__(256) void contrast_forward_kernel(
         if (j < k) {
             const int nb = nbr[(size_t)i * nbr_stride + j];
             const float nj = norm[nb];
-            const float *fj = f + (size_t)nb * C;
-            // four partial sums (a chain of C / 4 additions each, not of C: the cosine's rounding error is multiplied by 1 / T
-            // in the exponent)
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-            if ((C & 3) == 0) {
-                for (int c = 0; c < C; c += 4) {
-                    const float4 u = *reinterpret_cast<const float4 *>(fi + c);
-                    const float4 v = *reinterpret_cast<const float4 *>(fj + c);
-                    a0 += __fdiv_rn(u.x, ni) * __fdiv_rn(v.x, nj);
-                    a1 += __fdiv_rn(u.y, ni) * __fdiv_rn(v.y, nj);
-                    a2 += __fdiv_rn(u.z, ni) * __fdiv_rn(v.z, nj);
-                    a3 += __fdiv_rn(u.w, ni) * __fdiv_rn(v.w, nj);
-                }
-            } else {
-                int c = 0;
-                for (; c + 3 < C; c += 4) {
-                    a0 += __fdiv_rn(fi[c], ni) * __fdiv_rn(fj[c], nj);
-                    a1 += __fdiv_rn(fi[c + 1], ni) * __fdiv_rn(fj[c + 1], nj);
-                    a2 += __fdiv_rn(fi[c + 2], ni) * __fdiv_rn(fj[c + 2], nj);
-                    a3 += __fdiv_rn(fi[c + 3], ni) * __fdiv_rn(fj[c + 3], nj);
-                }
-                for (; c < C; ++c) a0 += __fdiv_rn(fi[c], ni) * __fdiv_rn(fj[c], nj);
-            }
-            const float acc = (a0 + a1) + (a2 + a3);
+            const float acc = row_cosine(fi, f + (size_t)nb * C, ni, nj, C);
             sim[(size_t)i * k + j] = acc;
             pos = posmask[(size_t)i * k + j] != 0;
-            const float s = pos ? __fsub_rn(acc, margin) : acc;
-            e = expf(__fdiv_rn(s, temperature));
+            e = contrast_exp(acc, pos, margin, temperature);
         }
         psum += pos ? e : 0.f;
         tsum += e;
@@ -408,12 +619,12 @@ __global__ __launch_bounds__(1024) void masked_mean_kernel(int m, const float *_
             const float l4[4] = {lv[u].x, lv[u].y, lv[u].z, lv[u].w}, a4[4] = {av[u].x, av[u].y, av[u].z, av[u].w};
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                if (0.f < a4[e] && a4[e] <= 1.f) { sum += (double)l4[e]; cnt += 1; }
+                if (contrast_selected(a4[e])) { sum += (double)l4[e]; cnt += 1; }
         }
     }
     for (int i = m4 + threadIdx.x; i < m; i += 1024) {
         const float ai = a[i];
-        if (0.f < ai && ai <= 1.f) { sum += (double)loss_pt[i]; cnt += 1; }
+        if (contrast_selected(ai)) { sum += (double)loss_pt[i]; cnt += 1; }
     }
     for (int s = 32; s >= 1; s >>= 1) {
         sum += __shfl_xor(sum, s, 64);
@@ -431,16 +642,9 @@ __global__ __launch_bounds__(1024) void masked_mean_kernel(int m, const float *_
 }
 
 // ---------------------------------------------------------------------------------------------
-// Contrast backward: d(mean loss)/d f.  LPA lanes per anchor, lane owns channels c, c+LPA, ...;
-// neighbours are walked one at a time so every atomic wave-instruction adds LPA contiguous floats
-// of one row (the shape global float atomics run at full rate for).
+// Contrast backward: d(mean loss)/d f by float atomics (EdgeWalk above: LPA lanes per anchor, neighbours one at a time).
 //   l = -log(r + eps), r = P/S, e_j = exp(s'_j / T):  dl/ds_j = -(e_j (pos_j S - P)) / ((r+eps) S^2 T)
-//   ds_j/df_i = (fhat_j - s_j fhat_i)/|f_i|,  ds_j/df_j = (fhat_i - s_j fhat_j)/|f_j|
-// A row below the norm clamp (|f| < eps: norm[] holds eps) has fhat = f / eps, linear in f: its derivative is fhat_j / eps, with
-// no projection term -- what autograd gives for x / clamp_min(|x|, eps).  All backward forms drop s_j fhat there.  They
-// see the clamped norm only (the test is norm > eps), so a row whose norm is eps to the bit counts as clamped, where
-// clamp_min's gradient would still pass: one fp32 value of the norm.
-// Where the time goes (scratch/contrast_diag.sh + contrast_bench.py, S3DIS-like batch, 66-99 % of the anchors listed): the
+// Where the time goes (contrast_bench.py, S3DIS-like batch, 66-99 % of the anchors listed): the
 // kernel adds 387 / 229 / 134 / 73 MB of rows at the four stages in 0.33 / 0.20 / 0.12 / 0.06 ms = 1.15-1.17 TB/s, the
 // chip-wide float-atomic rate (MI355X_MICROARCH.md: 1.26-1.36 TB/s); without the neighbour-row atomics it takes a third
 // of that, without the gathers the same.  Splitting an anchor's neighbours over several lane groups (tried for the deep
@@ -456,24 +660,17 @@ __global__ __launch_bounds__(256) void contrast_backward_kernel(
     const int *__restrict__ sel, float mu, float nu, float temperature, const float *__restrict__ sim,
     const float *__restrict__ mean_cnt, const float *__restrict__ grad_out, float *__restrict__ grad_f)
 {
-    constexpr int U = VPT >= 8 ? 2 : (VPT >= 4 ? 4 : 8);  // neighbour rows in flight
     const int sub = threadIdx.x & (LPA - 1);
-    const int w = (blockIdx.x * blockDim.x + threadIdx.x) / LPA;
-    if (w >= (sel ? sel[0] : m)) return;
-    const int i = sel ? sel[1 + w] : w;
-    const float ai = a[i];
-    if (!(0.f < ai && ai <= 1.f)) return;
+    int i;
+    float ai;
+    if (!contrast_anchor(sel, m, (blockIdx.x * blockDim.x + threadIdx.x) / LPA, a, i, ai)) return;
+    if (!contrast_selected(ai)) return;
     const float scale = grad_out[0] / mean_cnt[1];
     const float ni = norm[i];
-    const float margin = __fadd_rn(__fmul_rn(mu, ai), nu);
+    const float margin = contrast_margin(mu, ai, nu);
 
-    float fhi[VPT], gi[VPT];
-#pragma unroll
-    for (int v = 0; v < VPT; ++v) {
-        const int c = sub + v * LPA;
-        fhi[v] = c < C ? __fdiv_rn(f[(size_t)i * C + c], ni) : 0.f;
-        gi[v] = 0.f;
-    }
+    EdgeWalk<LPA, VPT> walk;
+    walk.begin(C, sub, f, i, ni);
     // lane `sub` holds neighbour j0 + sub of the current chunk of LPA neighbours
     int nb_l = -1;
     bool pos_l = false;
@@ -486,11 +683,10 @@ __global__ __launch_bounds__(256) void contrast_backward_kernel(
             pos_l = posmask[(size_t)i * k + j] != 0;
             sj_l = sim[(size_t)i * k + j];
             nj_l = norm[nb_l];
-            e_l = expf(__fdiv_rn(pos_l ? __fsub_rn(sj_l, margin) : sj_l, temperature));
+            e_l = contrast_exp(sj_l, pos_l, margin, temperature);
         }
     };
-    // P and S over all neighbours, and the negatives' share S - P summed on its own: a positive's coefficient is
-    // proportional to it, and tsum - psum loses it to cancellation when the positives dominate (low temperature, r near 1)
+    // P and S over all neighbours, and the negatives' share S - P summed on its own (see contrast_sums32)
     float psum = 0.f, tsum = 0.f, nsum = 0.f;
     for (int j0 = (k - 1) / LPA * LPA; j0 >= 0; j0 -= LPA) {  // ends on chunk 0, which the walk starts with
         load_chunk(j0);
@@ -504,60 +700,15 @@ __global__ __launch_bounds__(256) void contrast_backward_kernel(
         nsum += __shfl_xor(nsum, s, 64);
         tsum += __shfl_xor(tsum, s, 64);
     }
-    const float r = psum / tsum;
-    const float coef = -scale / ((r + 1e-12f) * tsum * tsum * temperature);
+    const float coef = contrast_coef(scale, psum, tsum, temperature);
     if (psum == 0.f) return;  // no positive neighbour: constant loss, zero gradient
 
     for (int j0 = 0; j0 < k; j0 += LPA) {
         if (j0 > 0) load_chunk(j0);
-        const float g_l = coef * e_l * (pos_l ? nsum : -psum);  // dL/ds_j
-        const int cnt = min(LPA, k - j0);
-        for (int jj = 0; jj < cnt; jj += U) {
-            int nb[U];
-            float fj[U][VPT];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int src = min(jj + u, LPA - 1);
-                const int t = __shfl(nb_l, src, LPA);
-                nb[u] = jj + u < cnt ? t : -1;
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int v = 0; v < VPT; ++v) {
-                    const int c = sub + v * LPA;
-#if AMC_CONTRAST_DIAG == 2  // diagnostic build 2: no neighbour-row gathers (timing only)
-                    fj[u][v] = (float)nb[u];
-#else
-                    fj[u][v] = (nb[u] >= 0 && c < C) ? f[(size_t)nb[u] * C + c] : 0.f;
-#endif
-                }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int src = min(jj + u, LPA - 1);
-                const float g = __shfl(g_l, src, LPA), sj = __shfl(sj_l, src, LPA), nj = __shfl(nj_l, src, LPA);
-                if (nb[u] < 0) continue;
-                const float gin = g / ni, gjn = g / nj;
-                const float si = ni > 1e-8f ? sj : 0.f, sx = nj > 1e-8f ? sj : 0.f;  // (no projection below the clamp)
-#pragma unroll
-                for (int v = 0; v < VPT; ++v) {
-                    const int c = sub + v * LPA;
-                    if (c < C) {
-                        const float fhj = __fdiv_rn(fj[u][v], nj);
-                        gi[v] += gin * (fhj - si * fhi[v]);
-#if AMC_CONTRAST_DIAG != 1  // diagnostic build 1: no neighbour-row atomics (timing only)
-                        atomicAdd(grad_f + (size_t)nb[u] * C + c, gjn * (fhi[v] - sx * fhj));
-#endif
-                    }
-                }
-            }
-        }
+        const float g_l = contrast_edge_g(coef, e_l, pos_l, nsum, psum);
+        walk.chunk(C, sub, f, ni, min(LPA, k - j0), nb_l, sj_l, nj_l, g_l, grad_f);
     }
-#pragma unroll
-    for (int v = 0; v < VPT; ++v) {
-        const int c = sub + v * LPA;
-        if (c < C) atomicAdd(grad_f + (size_t)i * C + c, gi[v]);
-    }
+    walk.finish(C, sub, i, grad_f);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -575,33 +726,19 @@ __global__ __launch_bounds__(256) void contrast_coef_kernel(
     const float *__restrict__ grad_out, float *__restrict__ gco)
 {
     const int sub = threadIdx.x & 31;
-    const int w = (blockIdx.x * blockDim.x + threadIdx.x) >> 5;
-    if (w >= sel[0]) return;
-    const int i = sel[1 + w];
-    const float ai = a[i];
+    int i;
+    float ai;
+    if (!contrast_anchor(sel, m, (blockIdx.x * blockDim.x + threadIdx.x) >> 5, a, i, ai)) return;  // (sel: the listed are selected)
     const float scale = grad_out[0] / mean_cnt[1];
-    const float margin = __fadd_rn(__fmul_rn(mu, ai), nu);
-    float psum = 0.f, tsum = 0.f, nsum = 0.f;  // nsum: the negatives' share, summed on its own (no tsum - psum cancellation)
+    const float margin = contrast_margin(mu, ai, nu);
+    const unsigned char *pm_i = posmask + (size_t)i * k;
+    const float *sim_i = sim + (size_t)i * k;
+    const ContrastSums t = contrast_sums32(k, sub, pm_i, sim_i, margin, temperature);
+    const float coef = t.psum == 0.f ? 0.f : contrast_coef(scale, t.psum, t.tsum, temperature);
     for (int j = sub; j < k; j += 32) {
-        const bool pos = posmask[(size_t)i * k + j] != 0;
-        const float sj = sim[(size_t)i * k + j];
-        const float e = expf(__fdiv_rn(pos ? __fsub_rn(sj, margin) : sj, temperature));
-        psum += pos ? e : 0.f;
-        nsum += pos ? 0.f : e;
-        tsum += e;
-    }
-    for (int s = 16; s >= 1; s >>= 1) {
-        psum += __shfl_xor(psum, s, 64);
-        nsum += __shfl_xor(nsum, s, 64);
-        tsum += __shfl_xor(tsum, s, 64);
-    }
-    const float r = psum / tsum;
-    const float coef = psum == 0.f ? 0.f : -scale / ((r + 1e-12f) * tsum * tsum * temperature);
-    for (int j = sub; j < k; j += 32) {
-        const bool pos = posmask[(size_t)i * k + j] != 0;
-        const float sj = sim[(size_t)i * k + j];
-        const float e = expf(__fdiv_rn(pos ? __fsub_rn(sj, margin) : sj, temperature));
-        gco[(size_t)i * k + j] = psum == 0.f ? 0.f : coef * e * (pos ? nsum : -psum);
+        const bool pos = pm_i[j] != 0;
+        const float e = contrast_exp(sim_i[j], pos, margin, temperature);
+        gco[(size_t)i * k + j] = t.psum == 0.f ? 0.f : contrast_edge_g(coef, e, pos, t.nsum, t.psum);
     }
 }
 
@@ -617,7 +754,7 @@ __global__ __launch_bounds__(256) void contrast_backward_rows_kernel(
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (n >= m) return;
     const float an = a[n];
-    const int own = (0.f < an && an <= 1.f) ? k : 0;
+    const int own = contrast_selected(an) ? k : 0;
     const int e0 = rev[n], deg = rev[n + 1] - e0;
     const int *rev_edge = rev + m + 1;
     const int total = own + deg;
@@ -632,17 +769,8 @@ __global__ __launch_bounds__(256) void contrast_backward_rows_kernel(
             float g[U], sv[U], nx[U];
             float4 v[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int t = t0 + u * R + r;
-                x[u] = -1; g[u] = 0.f; sv[u] = 0.f;
-                if (t < total) {
-                    int pos;
-                    if (t < own) { pos = n * k + t; x[u] = nbr[(size_t)n * nbr_stride + t]; }
-                    else { pos = rev_edge[e0 + t - own]; x[u] = pos / k; }
-                    g[u] = gco[pos];
-                    sv[u] = sim[pos];
-                }
-            }
+            for (int u = 0; u < U; ++u)
+                rows_edge(t0 + u * R + r, total, own, n, k, nbr + (size_t)n * nbr_stride, rev_edge + e0, gco, sim, x[u], g[u], sv[u]);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 nx[u] = x[u] >= 0 ? norm[x[u]] : 1.f;
@@ -651,12 +779,7 @@ __global__ __launch_bounds__(256) void contrast_backward_rows_kernel(
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 if (x[u] < 0) continue;
-                const float gn = g[u] / nn;
-                const float sn = nn > 1e-8f ? sv[u] : 0.f;  // (no projection below the clamp)
-                acc.x += gn * (__fdiv_rn(v[u].x, nx[u]) - sn * fn.x);
-                acc.y += gn * (__fdiv_rn(v[u].y, nx[u]) - sn * fn.y);
-                acc.z += gn * (__fdiv_rn(v[u].z, nx[u]) - sn * fn.z);
-                acc.w += gn * (__fdiv_rn(v[u].w, nx[u]) - sn * fn.w);
+                rows_accumulate(acc, g[u], sv[u], nn, fn, v[u], nx[u]);
             }
         }
 #pragma unroll
@@ -674,8 +797,8 @@ __global__ __launch_bounds__(256) void contrast_backward_rows_kernel(
 // PointNeXt-XL among them).  One wave per row n, ONE edge per round, lane q owns the float4 pieces q, q + 64, .. (P of them,
 // those below C4), so a wave reads a neighbour row in contiguous 1 KB pieces; U rounds of rows in flight.  No lane shares an
 // element with another, so there is no cross-lane sum: each output element is the sequential fp32 sum, from +0.0f, over
-// the row's own slots 0..k-1 (a selected anchor only) and then over its reverse list in list order.  The per-edge expression
-// is contrast_backward_rows_kernel's.
+// the row's own slots 0..k-1 (a selected anchor only) and then over its reverse list in list order.  Edge decode and per-edge
+// expression are contrast_backward_rows_kernel's (rows_edge, rows_accumulate).
 template <int P>
 __global__ __launch_bounds__(256) void contrast_backward_rows_wide_kernel(
     int m, int C4, int k, int nbr_stride, const float *__restrict__ f, const float *__restrict__ norm,
@@ -687,7 +810,7 @@ __global__ __launch_bounds__(256) void contrast_backward_rows_wide_kernel(
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (n >= m) return;
     const float an = a[n];
-    const int own = (0.f < an && an <= 1.f) ? k : 0;
+    const int own = contrast_selected(an) ? k : 0;
     const int e0 = rev[n], deg = rev[n + 1] - e0;
     const int *rev_edge = rev + m + 1;
     const int total = own + deg;
@@ -711,17 +834,8 @@ __global__ __launch_bounds__(256) void contrast_backward_rows_wide_kernel(
             float g[U], sv[U], nx[U];
             float4 v[U][P];
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int t = t0 + u;
-                x[u] = -1; g[u] = 0.f; sv[u] = 0.f;
-                if (t < total) {
-                    int pos;
-                    if (t < own) { pos = n * k + t; x[u] = nbr[(size_t)n * nbr_stride + t]; }
-                    else { pos = rev_edge[e0 + t - own]; x[u] = pos / k; }
-                    g[u] = gco[pos];
-                    sv[u] = sim[pos];
-                }
-            }
+            for (int u = 0; u < U; ++u)
+                rows_edge(t0 + u, total, own, n, k, nbr + (size_t)n * nbr_stride, rev_edge + e0, gco, sim, x[u], g[u], sv[u]);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 nx[u] = x[u] >= 0 ? norm[x[u]] : 1.f;
@@ -734,15 +848,8 @@ __global__ __launch_bounds__(256) void contrast_backward_rows_wide_kernel(
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 if (x[u] < 0) continue;
-                const float gn = g[u] / nn;
-                const float sn = nn > 1e-8f ? sv[u] : 0.f;  // (no projection below the clamp)
 #pragma unroll
-                for (int p = 0; p < P; ++p) {
-                    acc[p].x += gn * (__fdiv_rn(v[u][p].x, nx[u]) - sn * fn[p].x);
-                    acc[p].y += gn * (__fdiv_rn(v[u][p].y, nx[u]) - sn * fn[p].y);
-                    acc[p].z += gn * (__fdiv_rn(v[u][p].z, nx[u]) - sn * fn[p].z);
-                    acc[p].w += gn * (__fdiv_rn(v[u][p].w, nx[u]) - sn * fn[p].w);
-                }
+                for (int p = 0; p < P; ++p) rows_accumulate(acc[p], g[u], sv[u], nn, fn[p], v[u][p], nx[u]);
             }
         }
     }
@@ -778,40 +885,20 @@ __global__ __launch_bounds__(256) void contrast_record_kernel(
     const int i = (blockIdx.x * blockDim.x + threadIdx.x) >> 5;
     if (i >= m) return;
     const float ai = a[i];
-    const bool selected = 0.f < ai && ai <= 1.f;
-    const float margin = __fadd_rn(__fmul_rn(mu, ai), nu);
-    float psum = 0.f, tsum = 0.f, nsum = 0.f;
-    if (selected) {  // wave-uniform per half-wave: sim holds values for the selected anchors only
-        // the forward's order: slot-local sums over the rounds, then a tree over the slots (contrast_forward_rows_kernel
-        // folds 64/LPR slots; any fixed order is within rounding of it)
-        for (int j = sub; j < k; j += 32) {
-            const bool pos = posmask[(size_t)i * k + j] != 0;
-            const float sj = sim[(size_t)i * k + j];
-            const float e = expf(__fdiv_rn(pos ? __fsub_rn(sj, margin) : sj, temperature));
-            psum += pos ? e : 0.f;
-            nsum += pos ? 0.f : e;
-            tsum += e;
-        }
-    }
-    for (int s = 16; s >= 1; s >>= 1) {
-        psum += __shfl_xor(psum, s, 64);
-        nsum += __shfl_xor(nsum, s, 64);
-        tsum += __shfl_xor(tsum, s, 64);
-    }
+    const bool selected = contrast_selected(ai);
+    const float margin = contrast_margin(mu, ai, nu);
+    // (uniform per half-wave) sim holds values for the selected anchors only: the others sum over no slot
+    const ContrastSums t = contrast_sums32(selected ? k : 0, sub, posmask + (size_t)i * k, sim + (size_t)i * k, margin, temperature);
     if (sub == 0) {
         const float scale = grad_out[0] / mean_cnt[1];
-        const float r = psum / tsum;
         ContrastRecord o;
         o.norm = norm[i];
-        o.coef = (selected && psum != 0.f) ? -scale / ((r + 1e-12f) * tsum * tsum * temperature) : 0.f;
-        o.tsum = tsum; o.psum = psum; o.margin = margin; o.nsum = nsum; o.pad1 = o.pad2 = 0.f;
+        o.coef = (selected && t.psum != 0.f) ? contrast_coef(scale, t.psum, t.tsum, temperature) : 0.f;
+        o.tsum = t.tsum; o.psum = t.psum; o.margin = margin; o.nsum = t.nsum; o.pad1 = o.pad2 = 0.f;
         rec[i] = o;
     }
 }
 
-// (unit rows, see row_unit_kernel: hx = f_x / n_x is fetched, not recomputed; lane q < U of a row decodes and evaluates the
-// row's slot of round q -- index, mask, mutual count, the record of x, the two exponentials -- once, and hands x down to /
-// the finished coefficient back to the row's lanes by shuffles)
 // the same records from the two sums the forward pass kept per anchor (stats[2 i] = sum of the positives' exponentials,
 // stats[2 i + 1] = sum of the negatives'): nothing to recompute, no similarities to read; one thread per anchor
 __global__ __launch_bounds__(256) void contrast_record_stats_kernel(int m, const float *__restrict__ norm, const float *__restrict__ a,
@@ -822,18 +909,20 @@ __global__ __launch_bounds__(256) void contrast_record_stats_kernel(int m, const
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= m) return;
     const float ai = a[i];
-    const bool selected = 0.f < ai && ai <= 1.f;  // (the forward visited the selected anchors only: the others' stats are unwritten)
+    const bool selected = contrast_selected(ai);  // (the forward visited the selected anchors only: the others' stats are unwritten)
     const float psum = selected ? stats[(size_t)i * 2] : 0.f, nsum = selected ? stats[(size_t)i * 2 + 1] : 1.f;
     const float tsum = __fadd_rn(psum, nsum);
     const float scale = grad_out[0] / mean_cnt[1];
-    const float r = psum / tsum;
     ContrastRecord o;
     o.norm = norm[i];
-    o.coef = (selected && psum != 0.f) ? -scale / ((r + 1e-12f) * tsum * tsum * temperature) : 0.f;
-    o.tsum = tsum; o.psum = psum; o.margin = __fadd_rn(__fmul_rn(mu, ai), nu); o.nsum = nsum; o.pad1 = o.pad2 = 0.f;
+    o.coef = (selected && psum != 0.f) ? contrast_coef(scale, psum, tsum, temperature) : 0.f;
+    o.tsum = tsum; o.psum = psum; o.margin = contrast_margin(mu, ai, nu); o.nsum = nsum; o.pad1 = o.pad2 = 0.f;
     rec[i] = o;
 }
 
+// The mutual-edge gather (unit rows, see row_unit_kernel: hx = f_x / n_x is fetched, not recomputed; lane q < UNIT_U of a row
+// decodes and evaluates the row's slot of round q -- index, mask, mutual count, the record of x, the two exponentials --
+// once, and hands x down to / the finished coefficient back to the row's lanes by shuffles)
 template <int LPR>
 __global__ __launch_bounds__(256) void contrast_backward_mutual_kernel(
     int m, int k, int nbr_stride, const float *__restrict__ unit, const int *__restrict__ nbr,
@@ -841,7 +930,7 @@ __global__ __launch_bounds__(256) void contrast_backward_mutual_kernel(
     const ContrastRecord *__restrict__ rec, float temperature, float *__restrict__ grad_f)
 {
     constexpr int R = 64 / LPR;  // rows per round
-    constexpr int U = 4;         // rounds in flight
+    constexpr int U = UNIT_U;    // rounds in flight
     const int lane = threadIdx.x & 63, q = lane & (LPR - 1), r = lane / LPR, row0 = lane & ~(LPR - 1);
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (n >= m) return;
@@ -883,34 +972,25 @@ __global__ __launch_bounds__(256) void contrast_backward_mutual_kernel(
         const float4 rx = myx >= 0 ? rec4[(size_t)myx * 2] : make_float4(1.f, 0.f, 1.f, 0.f);  // (only coef = 0 matters for an empty slot)
         const float4 rx1 = myx >= 0 ? rec4[(size_t)myx * 2 + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
         const float mx = rx1.x;
-#pragma unroll
-        for (int u = 0; u < U; ++u) v[u] = x[u] >= 0 ? h4[(unsigned)x[u] * (unsigned)LPR + (unsigned)q] : make_float4(0.f, 0.f, 0.f, 0.f);
         float s[U], smine = 0.f;
+        unit_row_cosines<LPR>(h4, fn, q, x, v, s);  // the forward's loads, products and tree: s_nx to the bit
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            float t = unit_dot4(fn, v[u]);   // the forward's expression and order (contrast_forward_unit_kernel)
-#pragma unroll
-            for (int d = LPR / 2; d >= 1; d >>= 1) t += __shfl_xor(t, d, 64);
-            s[u] = t;
-            smine = q == u ? t : smine;
-        }
+        for (int u = 0; u < U; ++u) smine = q == u ? s[u] : smine;
         float gn = 0.f;
         if (myx >= 0) {
             float g = 0.f;
             if (own) {
-                const float e = expf(__fdiv_rn(pos ? __fsub_rn(smine, margin_n) : smine, temperature));
-                g += coef_n * e * (pos ? nsum_n : -psum_n);
+                g += contrast_edge_g(coef_n, contrast_exp(smine, pos, margin_n, temperature), pos, nsum_n, psum_n);
             }
             if (inc != 0.f && rx.y != 0.f) {
-                const float e = expf(__fdiv_rn(pos ? __fsub_rn(smine, mx) : smine, temperature));
-                g += inc * (rx.y * e * (pos ? rx1.y : -rx.w));
+                g += inc * contrast_edge_g(rx.y, contrast_exp(smine, pos, mx, temperature), pos, rx1.y, rx.w);
             }
             gn = g / nn;
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const float gu = __shfl(gn, row0 | u, 64);
-            const float sn = nn > 1e-8f ? s[u] : 0.f;  // (no projection below the clamp)
+            const float sn = contrast_projection(nn, s[u]);
             acc.x = __fmaf_rn(gu, __fmaf_rn(-sn, fn.x, v[u].x), acc.x);
             acc.y = __fmaf_rn(gu, __fmaf_rn(-sn, fn.y, v[u].y), acc.y);
             acc.z = __fmaf_rn(gu, __fmaf_rn(-sn, fn.z, v[u].z), acc.z);
@@ -930,14 +1010,14 @@ __global__ __launch_bounds__(256) void contrast_backward_mutual_kernel(
 // ---------------------------------------------------------------------------------------------
 // The other forms of contrast_softnn_margin (MarginContrast.py:117-174): margin constant / adaptive / learned, decision
 // boundary none / -m / +m, Method1 / Method2, with or without a temperature.  The form is four run-time integers
-// (kernel-uniform branches, no template per combination); the kernels of the default form above are untouched, what is
-// shared with them is copied.  Three steps forward -- the cosines alone (contrast_sim_*), the per-anchor loss from the
+// (kernel-uniform branches, no template per combination); the pieces shared with the default form's kernels
+// are the helpers at the top of the contrast part.  Three steps forward -- the cosines alone (contrast_sim_*), the per-anchor loss from the
 // stored cosines (contrast_variant_loss_kernel), masked_mean_kernel -- and two backward: g_ij = dL/ds_ij
 // (contrast_variant_coef_kernel), then the gradient rows from g by contrast_backward_rows_kernel or its wide form (a gather over reverse
 // lists, which knows nothing of the loss's form) or by contrast_backward_edges_kernel (float atomics, any C <= 512).
 //
 // Per anchor, with z_j = (s_j - [pos] m) / T  (-m),  (s_j + [neg] m) / T  (+m),  s_j / T  (none), e_j = exp(z_j),
-// P = sum_pos e, N = sum_neg e (each summed on its own, see contrast_backward_kernel), S = P + N, q_j = dl/dz_j:
+// P = sum_pos e, N = sum_neg e (each summed on its own, see contrast_sums32), S = P + N, q_j = dl/dz_j:
 //   Method1  l = -log(P/S + eps):       q_j = -e_j (N/S) / ((P/S + eps) S)  on positives,  +e_j (P/S) / ((P/S + eps) S)  on negatives
 //   Method2  l = -log(Y / (npos + eps)),  Y = sum_j (e_j [pos] / (e_j [pos] + N) + eps)  over ALL k slots:
 //            q_j = -(e_j / (e_j + N)) (N / (e_j + N)) / Y  on positives,  +e_j W / Y  on negatives,
@@ -952,92 +1032,44 @@ __global__ __launch_bounds__(256) void contrast_sim_unit_kernel(
     int m, int k, int nbr_stride, const float *__restrict__ unit, const int *__restrict__ nbr, const float *__restrict__ a,
     const int *__restrict__ sel, float *__restrict__ sim)
 {
-    // the gather of contrast_forward_unit_kernel: the same rounds, products and tree, so the cosines agree to the bit
+    // the gather of contrast_forward_unit_kernel (unit_gather_indices / unit_gather_rows): the cosines agree to the bit
     constexpr int R = 64 / LPR;
-    constexpr int U = 4;
     const int lane = threadIdx.x & 63, q = lane & (LPR - 1), r = lane / LPR;
-    const int cnt = sel ? sel[0] : m;
-    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (w >= cnt) return;
-    const int i = sel ? sel[1 + w] : w;
-    const float ai = a[i];
-    if (!(0.f < ai && ai <= 1.f)) return;
+    int i;
+    float ai;
+    if (!contrast_anchor(sel, m, blockIdx.x * 4 + (threadIdx.x >> 6), a, i, ai)) return;
+    if (!contrast_selected(ai)) return;
     const float4 *h4 = reinterpret_cast<const float4 *>(unit);
     const float4 u = h4[(size_t)i * LPR + q];
-    for (int j0 = 0; j0 < k; j0 += U * R) {
-        int nb[U];
-        float4 v[U];
-#pragma unroll
-        for (int t = 0; t < U; ++t) {
-            const int j = j0 + t * R + r;
-            nb[t] = j < k ? nbr[(size_t)i * nbr_stride + j] : -1;
-        }
+    for (int j0 = 0; j0 < k; j0 += UNIT_U * R) {
+        int nb[UNIT_U];
+        unit_gather_indices<LPR>(nbr, i, nbr_stride, k, j0, r, nb);
         const int jq = j0 + q * R + r;  // the slot this lane writes
-        const bool mine = q < U && jq < k;
-#pragma unroll
-        for (int t = 0; t < U; ++t) v[t] = nb[t] >= 0 ? h4[(unsigned)nb[t] * (unsigned)LPR + (unsigned)q] : make_float4(0.f, 0.f, 0.f, 0.f);
-        float s = 0.f;
-#pragma unroll
-        for (int t = 0; t < U; ++t) {
-            float acc = unit_dot4(u, v[t]);
-#pragma unroll
-            for (int d = LPR / 2; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-            s = q == t ? acc : s;
-        }
-        if (mine) sim[(size_t)i * k + jq] = s;
+        const float s = unit_gather_rows<LPR>(h4, u, q, nb);
+        if (q < UNIT_U && jq < k) sim[(size_t)i * k + jq] = s;
     }
 }
 
-// the gather of contrast_forward_kernel (any C): 32 lanes per anchor, lane j owns neighbour j
+// the gather of contrast_forward_kernel (any C, row_cosine): 32 lanes per anchor, lane j owns neighbour j
 __global__ __launch_bounds__(256) void contrast_sim_kernel(
     int m, int C, int k, int nbr_stride, const float *__restrict__ f, const float *__restrict__ norm,
     const int *__restrict__ nbr, const float *__restrict__ a, const int *__restrict__ sel, float *__restrict__ sim)
 {
     const int sub = threadIdx.x & 31;
-    const int w = (blockIdx.x * blockDim.x + threadIdx.x) >> 5;
-    if (w >= (sel ? sel[0] : m)) return;
-    const int i = sel ? sel[1 + w] : w;
-    const float ai = a[i];
-    if (!(0.f < ai && ai <= 1.f)) return;
+    int i;
+    float ai;
+    if (!contrast_anchor(sel, m, (blockIdx.x * blockDim.x + threadIdx.x) >> 5, a, i, ai)) return;
+    if (!contrast_selected(ai)) return;
     const float ni = norm[i];
     const float *fi = f + (size_t)i * C;
     for (int j = sub; j < k; j += 32) {
         const int nb = nbr[(size_t)i * nbr_stride + j];
         const float nj = norm[nb];
-        const float *fj = f + (size_t)nb * C;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        if ((C & 3) == 0) {
-            for (int c = 0; c < C; c += 4) {
-                const float4 u = *reinterpret_cast<const float4 *>(fi + c);
-                const float4 v = *reinterpret_cast<const float4 *>(fj + c);
-                a0 += __fdiv_rn(u.x, ni) * __fdiv_rn(v.x, nj);
-                a1 += __fdiv_rn(u.y, ni) * __fdiv_rn(v.y, nj);
-                a2 += __fdiv_rn(u.z, ni) * __fdiv_rn(v.z, nj);
-                a3 += __fdiv_rn(u.w, ni) * __fdiv_rn(v.w, nj);
-            }
-        } else {
-            int c = 0;
-            for (; c + 3 < C; c += 4) {
-                a0 += __fdiv_rn(fi[c], ni) * __fdiv_rn(fj[c], nj);
-                a1 += __fdiv_rn(fi[c + 1], ni) * __fdiv_rn(fj[c + 1], nj);
-                a2 += __fdiv_rn(fi[c + 2], ni) * __fdiv_rn(fj[c + 2], nj);
-                a3 += __fdiv_rn(fi[c + 3], ni) * __fdiv_rn(fj[c + 3], nj);
-            }
-            for (; c < C; ++c) a0 += __fdiv_rn(fi[c], ni) * __fdiv_rn(fj[c], nj);
-        }
-        sim[(size_t)i * k + j] = (a0 + a1) + (a2 + a3);
+        sim[(size_t)i * k + j] = row_cosine(fi, f + (size_t)nb * C, ni, nj, C);
     }
 }
 
 struct ContrastForm { int margin_mode, db, method, has_temperature; float mu, nu, temperature; };
-
-// sum over the 32 lanes of an anchor's group (two groups per wave; xor below 32 stays inside one)
-__device__ __forceinline__ float group32_sum(float v)
-{
-#pragma unroll
-    for (int s = 16; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
-    return v;
-}
 
 // z_j: the exponent of slot j (MarginContrast.py:140-149)
 __device__ __forceinline__ float variant_arg(const ContrastForm &F, float s, bool pos, float margin)
@@ -1057,7 +1089,7 @@ __device__ __forceinline__ ContrastAnchorSums variant_anchor_sums(const Contrast
 {
     ContrastAnchorSums r;
     r.margin = F.nu;
-    if (F.margin_mode == 1) r.margin = __fadd_rn(__fmul_rn(F.mu, ai), F.nu);
+    if (F.margin_mode == 1) r.margin = contrast_margin(F.mu, ai, F.nu);
     if (F.margin_mode == 2) {  // u, v: means over all k slots of the masked cosines (:128-130)
         float su = 0.f, sv = 0.f;
         for (int j = sub; j < k; j += 32) {
@@ -1101,11 +1133,10 @@ __global__ __launch_bounds__(256) void contrast_variant_loss_kernel(
     ContrastForm F, const float *__restrict__ sim, float *__restrict__ loss_pt)
 {
     const int sub = threadIdx.x & 31;
-    const int w = (blockIdx.x * blockDim.x + threadIdx.x) >> 5;
-    if (w >= (sel ? sel[0] : m)) return;
-    const int i = sel ? sel[1 + w] : w;
-    const float ai = a[i];
-    if (!(0.f < ai && ai <= 1.f)) {
+    int i;
+    float ai;
+    if (!contrast_anchor(sel, m, (blockIdx.x * blockDim.x + threadIdx.x) >> 5, a, i, ai)) return;
+    if (!contrast_selected(ai)) {
         if (sub == 0) loss_pt[i] = 0.f;
         return;
     }
@@ -1125,11 +1156,10 @@ __global__ __launch_bounds__(256) void contrast_variant_coef_kernel(
     const float *__restrict__ grad_out, float *__restrict__ gco)
 {
     const int sub = threadIdx.x & 31;
-    const int w = (blockIdx.x * blockDim.x + threadIdx.x) >> 5;
-    if (w >= (sel ? sel[0] : m)) return;
-    const int i = sel ? sel[1 + w] : w;
-    const float ai = a[i];
-    if (!(0.f < ai && ai <= 1.f)) return;
+    int i;
+    float ai;
+    if (!contrast_anchor(sel, m, (blockIdx.x * blockDim.x + threadIdx.x) >> 5, a, i, ai)) return;
+    if (!contrast_selected(ai)) return;
     const float *sim_i = sim + (size_t)i * k;
     const unsigned char *pm_i = posmask + (size_t)i * k;
     const ContrastAnchorSums r = variant_anchor_sums(F, k, sub, ai, sim_i, pm_i);
@@ -1166,8 +1196,7 @@ __global__ __launch_bounds__(256) void contrast_variant_coef_kernel(
     }
 }
 
-// Gradient rows from g = gco by float atomics: the walk of contrast_backward_kernel (LPA lanes per anchor, lane owns
-// channels c, c + LPA, ...; U neighbour rows in flight; no projection below the norm clamp) with the edge coefficient
+// Gradient rows from g = gco by float atomics: the walk of contrast_backward_kernel (EdgeWalk) with the edge coefficient
 // read instead of computed.  grad_f zero-initialised by the caller; C <= LPA * VPT.
 template <int LPA, int VPT>
 __global__ __launch_bounds__(256) void contrast_backward_edges_kernel(
@@ -1175,22 +1204,15 @@ __global__ __launch_bounds__(256) void contrast_backward_edges_kernel(
     const int *__restrict__ nbr, const float *__restrict__ a, const int *__restrict__ sel, const float *__restrict__ sim,
     const float *__restrict__ gco, float *__restrict__ grad_f)
 {
-    constexpr int U = VPT >= 8 ? 2 : (VPT >= 4 ? 4 : 8);  // neighbour rows in flight
     const int sub = threadIdx.x & (LPA - 1);
-    const int w = (blockIdx.x * blockDim.x + threadIdx.x) / LPA;
-    if (w >= (sel ? sel[0] : m)) return;
-    const int i = sel ? sel[1 + w] : w;
-    const float ai = a[i];
-    if (!(0.f < ai && ai <= 1.f)) return;
+    int i;
+    float ai;
+    if (!contrast_anchor(sel, m, (blockIdx.x * blockDim.x + threadIdx.x) / LPA, a, i, ai)) return;
+    if (!contrast_selected(ai)) return;
     const float ni = norm[i];
 
-    float fhi[VPT], gi[VPT];
-#pragma unroll
-    for (int v = 0; v < VPT; ++v) {
-        const int c = sub + v * LPA;
-        fhi[v] = c < C ? __fdiv_rn(f[(size_t)i * C + c], ni) : 0.f;
-        gi[v] = 0.f;
-    }
+    EdgeWalk<LPA, VPT> walk;
+    walk.begin(C, sub, f, i, ni);
     for (int j0 = 0; j0 < k; j0 += LPA) {
         // lane `sub` holds neighbour j0 + sub of this chunk of LPA neighbours
         const int j = j0 + sub;
@@ -1202,47 +1224,9 @@ __global__ __launch_bounds__(256) void contrast_backward_edges_kernel(
             g_l = gco[(size_t)i * k + j];
             nj_l = norm[nb_l];
         }
-        const int cnt = min(LPA, k - j0);
-        for (int jj = 0; jj < cnt; jj += U) {
-            int nb[U];
-            float fj[U][VPT];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int src = min(jj + u, LPA - 1);
-                const int t = __shfl(nb_l, src, LPA);
-                nb[u] = jj + u < cnt ? t : -1;
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int v = 0; v < VPT; ++v) {
-                    const int c = sub + v * LPA;
-                    fj[u][v] = (nb[u] >= 0 && c < C) ? f[(size_t)nb[u] * C + c] : 0.f;
-                }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int src = min(jj + u, LPA - 1);
-                const float g = __shfl(g_l, src, LPA), sj = __shfl(sj_l, src, LPA), nj = __shfl(nj_l, src, LPA);
-                if (nb[u] < 0) continue;
-                const float gin = g / ni, gjn = g / nj;
-                const float si = ni > 1e-8f ? sj : 0.f, sx = nj > 1e-8f ? sj : 0.f;  // (no projection below the clamp)
-#pragma unroll
-                for (int v = 0; v < VPT; ++v) {
-                    const int c = sub + v * LPA;
-                    if (c < C) {
-                        const float fhj = __fdiv_rn(fj[u][v], nj);
-                        gi[v] += gin * (fhj - si * fhi[v]);
-                        atomicAdd(grad_f + (size_t)nb[u] * C + c, gjn * (fhi[v] - sx * fhj));
-                    }
-                }
-            }
-        }
+        walk.chunk(C, sub, f, ni, min(LPA, k - j0), nb_l, sj_l, nj_l, g_l, grad_f);
     }
-#pragma unroll
-    for (int v = 0; v < VPT; ++v) {
-        const int c = sub + v * LPA;
-        if (c < C) atomicAdd(grad_f + (size_t)i * C + c, gi[v]);
-    }
+    walk.finish(C, sub, i, grad_f);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1488,40 +1472,78 @@ AMC_API int amc3d_select_anchors(int m, const float *a, int *sel, size_t sel_int
     return launch_status("amc3d_select_anchors");
 }
 
+// Width dispatch.  The unit-row and row-gather kernels are instantiated for C = 4 * LPR in {16, 32, 64, 128, 256}:
+// fn(std::integral_constant<int, LPR>) is called with the constant; false for any other width.
+template <int N> using int_c = std::integral_constant<int, N>;
+
+template <class F>
+static bool with_lpr(int C, F &&fn)
+{
+    switch (C) {
+    case 16: fn(int_c<4>{}); return true;
+    case 32: fn(int_c<8>{}); return true;
+    case 64: fn(int_c<16>{}); return true;
+    case 128: fn(int_c<32>{}); return true;
+    case 256: fn(int_c<64>{}); return true;
+    default: return false;
+    }
+}
+
+// the wide rows kernel beside them: P float4 pieces per lane cover C = 4 * C4 <= 256 * P
+template <class F>
+static void with_wide_p(int C, F &&fn)
+{
+    if (C < 256) fn(int_c<1>{});
+    else fn(int_c<2>{});
+}
+
+// the float-atomic walks: LPA lanes per anchor, VPT channels per lane, C <= LPA * VPT <= 512
+template <class F>
+static void with_lpa_vpt(int C, F &&fn)
+{
+    if (C <= 32) fn(int_c<32>{}, int_c<1>{});
+    else if (C <= 64) fn(int_c<64>{}, int_c<1>{});
+    else if (C <= 128) fn(int_c<64>{}, int_c<2>{});
+    else if (C <= 256) fn(int_c<64>{}, int_c<4>{});
+    else fn(int_c<64>{}, int_c<8>{});
+}
+
+// the forwards take the unit-row kernels (amc3d_contrast_forward and amc3d_contrast_variant_forward make the same choice:
+// their cosines then agree to the bit); the row kernels index 16-byte pieces with 32 bits: m * C / 4 < 2^32
+static bool contrast_rows_ok(const float *f, const float *unit, int m, int C)
+{
+    return unit && ((((uintptr_t)f) | ((uintptr_t)unit)) & 15) == 0 && amc3d_contrast_backward_csr_supported(C) &&
+           (long)m * C < (1L << 34);
+}
+
 // cm_b > 0: f is channel-major (cm_b, C, m / cm_b) and only the unit-row kernels apply
 static int contrast_forward_launch(int cm_b, int m, int C, int k, int nbr_stride, const float *f, const int *nbr,
                                    const unsigned char *posmask, const float *a, const int *sel, float mu, float nu,
                                    float temperature, float *norm, float *unit, float *sim, float *stats, float *loss_pt,
                                    float *mean_cnt, hipStream_t stream)
 {
-    // (the row kernels index 16-byte pieces with 32 bits: m * C / 4 < 2^32)
-    const bool rows = unit && ((((uintptr_t)f) | ((uintptr_t)unit)) & 15) == 0 && amc3d_contrast_backward_csr_supported(C) &&
-                      (long)m * C < (1L << 34);
+    const bool rows = contrast_rows_ok(f, unit, m, C);
     if (cm_b > 0 && !rows) return bad_arg("amc3d_contrast_forward_cm: C must be 16, 32, 64, 128 or 256; unit required, 16-byte aligned");
     if (!sim && !(rows && stats)) return bad_arg("amc3d_contrast_forward: sim may be NULL only with the unit-row kernels and stats");
-#define AMC_FWD(LPR)                                                                                                       \
-    do {                                                                                                                   \
-        if (cm_b > 0) {                                                                                                    \
-            constexpr int TP = LPR >= 32 ? 16 : 64;                                                                        \
-            const size_t lds = (size_t)4 * LPR * (TP + 1) * sizeof(float);                                                 \
-            hipLaunchKernelGGL((row_unit_cm_kernel<LPR, TP>), dim3(div_up(m / cm_b, TP), cm_b), dim3(256), lds, stream,    \
-                               m / cm_b, f, norm, unit);                                                                   \
-        } else                                                                                                             \
-            hipLaunchKernelGGL((row_unit_kernel<LPR>), dim3(div_up((long)m * LPR, 256)), dim3(256), 0, stream, m, f, norm, unit); \
-        hipLaunchKernelGGL((contrast_forward_unit_kernel<LPR>), dim3(div_up(m, 4)), dim3(256), 0, stream, m, k, nbr_stride, \
-                           (const float *)unit, nbr, posmask, a, sel, mu, nu, temperature, sim, stats, loss_pt);           \
-    } while (0)
-    if (rows && C == 16) AMC_FWD(4);
-    else if (rows && C == 32) AMC_FWD(8);
-    else if (rows && C == 64) AMC_FWD(16);
-    else if (rows && C == 128) AMC_FWD(32);
-    else if (rows && C == 256) AMC_FWD(64);
-    else {
+    if (rows) {
+        const bool launched = with_lpr(C, [&](auto lpr) {
+            constexpr int LPR = decltype(lpr)::value;
+            if (cm_b > 0) {
+                constexpr int TP = LPR >= 32 ? 16 : 64;
+                const size_t lds = (size_t)4 * LPR * (TP + 1) * sizeof(float);
+                hipLaunchKernelGGL((row_unit_cm_kernel<LPR, TP>), dim3(div_up(m / cm_b, TP), cm_b), dim3(256), lds, stream,
+                                   m / cm_b, f, norm, unit);
+            } else
+                hipLaunchKernelGGL((row_unit_kernel<LPR>), dim3(div_up((long)m * LPR, 256)), dim3(256), 0, stream, m, f, norm, unit);
+            hipLaunchKernelGGL((contrast_forward_unit_kernel<LPR>), dim3(div_up(m, 4)), dim3(256), 0, stream, m, k, nbr_stride,
+                               (const float *)unit, nbr, posmask, a, sel, mu, nu, temperature, sim, stats, loss_pt);
+        });
+        if (!launched) return bad_arg("amc3d_contrast_forward: no unit-row kernel for this width");
+    } else {
         hipLaunchKernelGGL(row_norm_kernel, dim3(div_up(m, 4)), dim3(256), 0, stream, m, C, f, norm);
         hipLaunchKernelGGL(contrast_forward_kernel, dim3(div_up((long)m * 32, 256)), dim3(256), 0, stream, m, C, k,
                            nbr_stride, f, norm, nbr, posmask, a, sel, mu, nu, temperature, sim, loss_pt);
     }
-#undef AMC_FWD
     // anchors the list skips never write loss_pt; masked_mean_kernel reads the selected ones only
     hipLaunchKernelGGL(masked_mean_kernel, dim3(1), dim3(1024), 0, stream, m, loss_pt, a, mean_cnt);
     return launch_status("amc3d_contrast_forward");
@@ -1563,16 +1585,11 @@ AMC_API int amc3d_contrast_backward(int m, int C, int k, int nbr_stride, const f
     if (C <= 0 || C > 512 || k <= 0 || !f || !norm || !nbr || !posmask || !a || !sim || !mean_cnt || !grad_out || !grad_f)
         return bad_arg("amc3d_contrast_backward: bad argument (C must be in 1..512)");
     hipStream_t stream = (hipStream_t)stream_;
-#define AMC_BWD(LPA, VPT)                                                                                           \
-    hipLaunchKernelGGL((contrast_backward_kernel<LPA, VPT>), dim3(div_up((long)m * LPA, 256)), dim3(256), 0, stream, \
-                       m, C, k, nbr_stride, f, norm, nbr, posmask, a, sel, mu, nu, temperature, sim, mean_cnt,       \
-                       grad_out, grad_f)
-    if (C <= 32) AMC_BWD(32, 1);
-    else if (C <= 64) AMC_BWD(64, 1);
-    else if (C <= 128) AMC_BWD(64, 2);
-    else if (C <= 256) AMC_BWD(64, 4);
-    else AMC_BWD(64, 8);
-#undef AMC_BWD
+    with_lpa_vpt(C, [&](auto lpa, auto vpt) {
+        constexpr int LPA = decltype(lpa)::value, VPT = decltype(vpt)::value;
+        hipLaunchKernelGGL((contrast_backward_kernel<LPA, VPT>), dim3(div_up((long)m * LPA, 256)), dim3(256), 0, stream, m, C, k,
+                           nbr_stride, f, norm, nbr, posmask, a, sel, mu, nu, temperature, sim, mean_cnt, grad_out, grad_f);
+    });
     return launch_status("amc3d_contrast_backward");
 }
 
@@ -1589,21 +1606,15 @@ static void contrast_rows_launch(int m, int C, int k, int nbr_stride, const floa
                                  const float *a, const int *rev, const float *sim, const float *gco, float *grad_f,
                                  hipStream_t stream)
 {
-#define AMC_BWD(LPR)                                                                                                  \
-    hipLaunchKernelGGL((contrast_backward_rows_kernel<LPR>), dim3(div_up(m, 4)), dim3(256), 0, stream, m, k, nbr_stride, f, \
-                       norm, nbr, a, rev, sim, gco, grad_f)
-#define AMC_BWD_WIDE(P)                                                                                               \
-    hipLaunchKernelGGL((contrast_backward_rows_wide_kernel<P>), dim3(div_up(m, 4)), dim3(256), 0, stream, m, C / 4, k,  \
-                       nbr_stride, f, norm, nbr, a, rev, sim, gco, grad_f)
-    if (C == 16) AMC_BWD(4);
-    else if (C == 32) AMC_BWD(8);
-    else if (C == 64) AMC_BWD(16);
-    else if (C == 128) AMC_BWD(32);
-    else if (C == 256) AMC_BWD(64);
-    else if (C < 256) AMC_BWD_WIDE(1);
-    else AMC_BWD_WIDE(2);
-#undef AMC_BWD_WIDE
-#undef AMC_BWD
+    const bool narrow = with_lpr(C, [&](auto lpr) {
+        hipLaunchKernelGGL((contrast_backward_rows_kernel<decltype(lpr)::value>), dim3(div_up(m, 4)), dim3(256), 0, stream, m, k,
+                           nbr_stride, f, norm, nbr, a, rev, sim, gco, grad_f);
+    });
+    if (!narrow)
+        with_wide_p(C, [&](auto p) {
+            hipLaunchKernelGGL((contrast_backward_rows_wide_kernel<decltype(p)::value>), dim3(div_up(m, 4)), dim3(256), 0, stream,
+                               m, C / 4, k, nbr_stride, f, norm, nbr, a, rev, sim, gco, grad_f);
+        });
 }
 
 AMC_API int amc3d_contrast_backward_csr(int m, int C, int k, int nbr_stride, const float *f, const float *norm,
@@ -1641,26 +1652,19 @@ AMC_API int amc3d_contrast_variant_forward(int m, int C, int k, int nbr_stride, 
         return bad_arg("amc3d_contrast_variant_forward: bad argument (margin_mode 0..2, db 0..2, method 1..2, has_temperature 0..1)");
     hipStream_t stream = (hipStream_t)stream_;
     const ContrastForm F{margin_mode, db, method, has_temperature, mu, nu, temperature};
-    // (the same choice of kernels as amc3d_contrast_forward makes: the cosines then agree with its to the bit)
-    const bool rows = unit && ((((uintptr_t)f) | ((uintptr_t)unit)) & 15) == 0 && amc3d_contrast_backward_csr_supported(C) &&
-                      (long)m * C < (1L << 34);
-#define AMC_SIM(LPR)                                                                                                       \
-    do {                                                                                                                   \
-        hipLaunchKernelGGL((row_unit_kernel<LPR>), dim3(div_up((long)m * LPR, 256)), dim3(256), 0, stream, m, f, norm, unit); \
-        hipLaunchKernelGGL((contrast_sim_unit_kernel<LPR>), dim3(div_up(m, 4)), dim3(256), 0, stream, m, k, nbr_stride,    \
-                           (const float *)unit, nbr, a, sel, sim);                                                         \
-    } while (0)
-    if (rows && C == 16) AMC_SIM(4);
-    else if (rows && C == 32) AMC_SIM(8);
-    else if (rows && C == 64) AMC_SIM(16);
-    else if (rows && C == 128) AMC_SIM(32);
-    else if (rows && C == 256) AMC_SIM(64);
-    else {
+    if (contrast_rows_ok(f, unit, m, C)) {
+        const bool launched = with_lpr(C, [&](auto lpr) {
+            constexpr int LPR = decltype(lpr)::value;
+            hipLaunchKernelGGL((row_unit_kernel<LPR>), dim3(div_up((long)m * LPR, 256)), dim3(256), 0, stream, m, f, norm, unit);
+            hipLaunchKernelGGL((contrast_sim_unit_kernel<LPR>), dim3(div_up(m, 4)), dim3(256), 0, stream, m, k, nbr_stride,
+                               (const float *)unit, nbr, a, sel, sim);
+        });
+        if (!launched) return bad_arg("amc3d_contrast_variant_forward: no unit-row kernel for this width");
+    } else {
         hipLaunchKernelGGL(row_norm_kernel, dim3(div_up(m, 4)), dim3(256), 0, stream, m, C, f, norm);
         hipLaunchKernelGGL(contrast_sim_kernel, dim3(div_up((long)m * 32, 256)), dim3(256), 0, stream, m, C, k, nbr_stride, f,
                            (const float *)norm, nbr, a, sel, sim);
     }
-#undef AMC_SIM
     hipLaunchKernelGGL(contrast_variant_loss_kernel, dim3(div_up((long)m * 32, 256)), dim3(256), 0, stream, m, k, posmask, a, sel,
                        F, (const float *)sim, loss_pt);
     hipLaunchKernelGGL(masked_mean_kernel, dim3(1), dim3(1024), 0, stream, m, loss_pt, a, mean_cnt);
@@ -1687,15 +1691,11 @@ AMC_API int amc3d_contrast_variant_backward(int m, int C, int k, int nbr_stride,
     if (rev) {
         contrast_rows_launch(m, C, k, nbr_stride, f, norm, nbr, a, rev, sim, gco, grad_f, stream);
     } else {
-#define AMC_BWD(LPA, VPT)                                                                                                 \
-    hipLaunchKernelGGL((contrast_backward_edges_kernel<LPA, VPT>), dim3(div_up((long)m * LPA, 256)), dim3(256), 0, stream, \
-                       m, C, k, nbr_stride, f, norm, nbr, a, sel, sim, (const float *)gco, grad_f)
-        if (C <= 32) AMC_BWD(32, 1);
-        else if (C <= 64) AMC_BWD(64, 1);
-        else if (C <= 128) AMC_BWD(64, 2);
-        else if (C <= 256) AMC_BWD(64, 4);
-        else AMC_BWD(64, 8);
-#undef AMC_BWD
+        with_lpa_vpt(C, [&](auto lpa, auto vpt) {
+            constexpr int LPA = decltype(lpa)::value, VPT = decltype(vpt)::value;
+            hipLaunchKernelGGL((contrast_backward_edges_kernel<LPA, VPT>), dim3(div_up((long)m * LPA, 256)), dim3(256), 0, stream,
+                               m, C, k, nbr_stride, f, norm, nbr, a, sel, sim, (const float *)gco, grad_f);
+        });
     }
     return launch_status("amc3d_contrast_variant_backward");
 }
@@ -1724,15 +1724,11 @@ AMC_API int amc3d_contrast_backward_mutual(int m, int C, int k, int nbr_stride, 
     else
         hipLaunchKernelGGL(contrast_record_kernel, dim3(div_up((long)m * 32, 256)), dim3(256), 0, stream, m, k, norm, posmask, a, mu, nu,
                            temperature, sim, mean_cnt, grad_out, rec);
-#define AMC_BWD(LPR)                                                                                                    \
-    hipLaunchKernelGGL((contrast_backward_mutual_kernel<LPR>), dim3(div_up(m, 4)), dim3(256), 0, stream, m, k, nbr_stride, unit, \
-                       nbr, posmask, mutual, rev, (const ContrastRecord *)rec, temperature, grad_f)
-    if (C == 16) AMC_BWD(4);
-    else if (C == 32) AMC_BWD(8);
-    else if (C == 64) AMC_BWD(16);
-    else if (C == 128) AMC_BWD(32);
-    else AMC_BWD(64);
-#undef AMC_BWD
+    const bool launched = with_lpr(C, [&](auto lpr) {
+        hipLaunchKernelGGL((contrast_backward_mutual_kernel<decltype(lpr)::value>), dim3(div_up(m, 4)), dim3(256), 0, stream, m, k,
+                           nbr_stride, unit, nbr, posmask, mutual, rev, (const ContrastRecord *)rec, temperature, grad_f);
+    });
+    if (!launched) return bad_arg("amc3d_contrast_backward_mutual: no row kernel for this width");
     return launch_status("amc3d_contrast_backward_mutual");
 }
 

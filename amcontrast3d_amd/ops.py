@@ -656,6 +656,76 @@ def contrast_mutual(neighbor_idx, a, dist2=None):
     return mutual, rev
 
 
+def _contrast_inputs(f, m, neighbor_idx, posmask, a, anchors=None, rev=None, mutual=None, name="features"):
+    """What every contrast entry point requires of the inputs they share, before any launch: f the contiguous fp32
+    embeddings of m points (rows (m, C), or channel-major (B, C, n) with m = B * n), posmask (m, k) bool, a (m) fp32, both
+    contiguous (the library reads them through raw pointers), and the plan tensors as select_anchors / contrast_csr /
+    contrast_mutual return them.  -> _nbr_view(neighbor_idx)"""
+    _need_gpu(f, neighbor_idx, posmask, a, *(t for t in (anchors, rev, mutual) if t is not None))
+    _need_dtype(torch.float32, **{name: f}, a=a)
+    _need_dtype(torch.int32, anchors=anchors, rev=rev)
+    _need_dtype(torch.uint8, mutual=mutual)
+    view = _nbr_view(neighbor_idx)
+    k, dev = view[1], f.device
+    assert neighbor_idx.shape[0] == m and posmask.dtype == torch.bool and posmask.is_contiguous() and posmask.shape == (m, k)
+    assert a.shape == (m,) and a.is_contiguous()
+    if anchors is not None:
+        assert anchors.is_contiguous() and anchors.numel() >= m + 1 and anchors.device == dev
+    if rev is not None:
+        assert anchors is not None and rev.is_contiguous() and rev.numel() == m + 1 + m * k and rev.device == dev
+    if mutual is not None:  # rev then holds the non-mutual edges only (contrast_mutual)
+        assert rev is not None and mutual.is_contiguous() and mutual.shape == (m, k) and mutual.device == dev
+    return view
+
+
+def _contrast_buffers(m, C, k, dev, unit, per_slot):
+    """norm (m), unit (m, C: the rows f_i / |f_i| the row-gather kernels read, forward and mutual-edge backward; None where
+    `unit` is false), sim (m, k: the cosines) or, per_slot false, stats (m, 2: the two sums of exponentials per anchor --
+    the positives', the negatives' -- the backward's records need when the cosines are not stored), loss_pt (m), mean_cnt (2)"""
+    e = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+    return e(m), (e(m, C) if unit else None), e(m, k if per_slot else 2), e(m), e(2)
+
+
+def _contrast_grad_out(grad_out):
+    """the upstream gradient of the scalar loss as the one-element fp32 tensor the library reads"""
+    return grad_out.detach().to(torch.float32).reshape(1).contiguous()
+
+
+def _contrast_backward_route(C, aligned, det, has_rev, has_mutual, has_unit, csr_supported, rows_supported):
+    """'mutual' (gather over mutual edges), 'rows' (gather over the reverse lists of all edges) or 'atomic' (float atomics).
+    The gathers need 16-byte aligned rows f (a misaligned f also left the forward without unit rows); default mode keeps the
+    atomic form at the widths without a power-of-two row kernel (the wide one is unmeasured there)."""
+    if has_mutual and has_unit and aligned:
+        return "mutual"
+    if has_rev and aligned and (csr_supported(C) or (det and rows_supported(C))):
+        return "rows"
+    return "atomic"
+
+
+def _contrast_route_and_lists(op, ctx, f, nbr, a, anchors, rev, mutual=None, unit=None):
+    """-> (route, anchors, rev) of a backward over rows f.  Deterministic mode has no atomic route: where the stage's plan
+    has no reverse lists of all edges (none, or contrast_mutual's, which hold the non-mutual edges only) it builds them
+    here, and raises for rows the gathers cannot read (misaligned, or no multiple of 4, or above 512 channels)."""
+    lib = _lib.load()
+    C, aligned, all_edges = f.shape[1], f.data_ptr() % 16 == 0, rev is not None and mutual is None
+    route = _contrast_backward_route(C, aligned, ctx.det, all_edges, mutual is not None, unit is not None,
+                                     lib.amc3d_contrast_backward_csr_supported, lib.amc3d_contrast_backward_rows_supported)
+    if route == "mutual" or not ctx.det:
+        return route, anchors, rev
+    if not aligned:
+        raise _no_route(op, "the reverse-list backward needs 16-byte aligned rows")
+    if not lib.amc3d_contrast_backward_rows_supported(C):
+        raise _no_route(op, f"the reverse-list backward does not cover {C} channels")
+    if not all_edges:
+        anchors = select_anchors(a) if anchors is None else anchors
+        rev = contrast_csr(nbr, anchors)
+    return "rows", anchors, rev
+
+
+def _opt(t):
+    return _ptr(t) if t is not None else None
+
+
 class ContrastStage(Function):
     """Stage loss of ContrastHead.point_contrast_margin (MarginContrast.py:250-257): mean over the
     anchors with 0 < a <= 1 of the margin soft-NN loss on cosine similarities.  anchors: select_anchors(a) of
@@ -665,35 +735,16 @@ class ContrastStage(Function):
 
     @staticmethod
     def forward(ctx, features, neighbor_idx, posmask, a, mu, nu, temperature, anchors=None, rev=None, mutual=None):
-        _need_gpu(features, neighbor_idx, posmask, a)
         f = features.contiguous()
-        assert f.dtype == torch.float32 and posmask.dtype == torch.bool and posmask.is_contiguous()
-        if anchors is not None:
-            _need_dtype(torch.int32, anchors=anchors)
-            assert anchors.is_contiguous() and anchors.numel() >= f.shape[0] + 1 and anchors.device == f.device
-        nptr, k, stride, keep = _nbr_view(neighbor_idx)
         m, C = f.shape
-        dev = f.device
-        norm = torch.empty(m, dtype=torch.float32, device=dev)
+        nptr, k, stride, keep = _contrast_inputs(f, m, neighbor_idx, posmask, a, anchors, rev, mutual)
         lib = _lib.load()
-        # the unit rows f_i / |f_i| the row-gather kernels read (forward, and the mutual-edge backward instead of f)
-        unit = torch.empty_like(f) if lib.amc3d_contrast_backward_csr_supported(C) else None
-        sim = torch.empty(m, k, dtype=torch.float32, device=dev)
-        loss_pt = torch.empty(m, dtype=torch.float32, device=dev)
-        mean_cnt = torch.empty(2, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev), timing.span("contrast_forward", m * C * 4 + m * k * 9 + m * 12, moved=m * C * 4 * (3 + k) + m * k * 9 + m * 12):
-            _lib.check(lib.amc3d_contrast_forward(m, C, k, stride, _ptr(f), nptr, _ptr(posmask), _ptr(a),
-                                                  _ptr(anchors) if anchors is not None else None,
-                                                  float(mu), float(nu), float(temperature), _ptr(norm),
-                                                  _ptr(unit) if unit is not None else None,
+        norm, unit, sim, loss_pt, mean_cnt = _contrast_buffers(m, C, k, f.device, lib.amc3d_contrast_backward_csr_supported(C), True)
+        with torch.cuda.device(f.device), timing.span("contrast_forward", m * C * 4 + m * k * 9 + m * 12, moved=m * C * 4 * (3 + k) + m * k * 9 + m * 12):
+            _lib.check(lib.amc3d_contrast_forward(m, C, k, stride, _ptr(f), nptr, _ptr(posmask), _ptr(a), _opt(anchors),
+                                                  float(mu), float(nu), float(temperature), _ptr(norm), _opt(unit),
                                                   _ptr(sim), None, _ptr(loss_pt), _ptr(mean_cnt), _stream(f)),
                        "contrast_forward")
-        if rev is not None:
-            _need_dtype(torch.int32, rev=rev)
-            assert anchors is not None and rev.is_contiguous() and rev.numel() == m + 1 + m * k and rev.device == dev
-        if mutual is not None:  # rev then holds the non-mutual edges only (contrast_mutual)
-            _need_dtype(torch.uint8, mutual=mutual)
-            assert rev is not None and mutual.is_contiguous() and mutual.shape == (m, k) and mutual.device == dev
         ctx.save_for_backward(f, norm, keep, posmask, a, sim, mean_cnt, anchors, rev, mutual, unit)
         ctx.args = (float(mu), float(nu), float(temperature), k, stride)
         ctx.det = deterministic()
@@ -704,10 +755,11 @@ class ContrastStage(Function):
         f, norm, nbr, posmask, a, sim, mean_cnt, anchors, rev, mutual, unit = ctx.saved_tensors
         mu, nu, temperature, k, stride = ctx.args
         m, C = f.shape
-        g = grad_out.detach().to(torch.float32).reshape(1).contiguous()
+        g = _contrast_grad_out(grad_out)
         nptr = _ptr(nbr)  # data_ptr includes the offset of an idx[:, 1:] view: the first used column
         lib = _lib.load()
-        if mutual is not None and unit is not None:
+        route, anchors, rev = _contrast_route_and_lists("contrast_backward", ctx, f, nbr, a, anchors, rev, mutual, unit)
+        if route == "mutual":
             grad_f = torch.empty_like(f)  # every row is written
             wb = int(lib.amc3d_contrast_backward_mutual_workspace_bytes(m))
             work = torch.empty(wb, dtype=torch.uint8, device=f.device)
@@ -717,14 +769,7 @@ class ContrastStage(Function):
                                                               _ptr(mutual), _ptr(rev), mu, nu, temperature, _ptr(sim), None,
                                                               _ptr(mean_cnt), _ptr(g), _ptr(work), wb, _ptr(grad_f), _stream(f)),
                            "contrast_backward_mutual")
-            return (grad_f,) + (None,) * 9
-        if mutual is not None:
-            rev = None  # (a width the row kernels do not cover: the atomic form below; rev holds non-mutual edges only)
-        if ctx.det:
-            anchors, rev = _contrast_lists("contrast_backward", C, nbr, a, anchors, rev)
-        # (default mode keeps the atomic form at the widths without a power-of-two row kernel; the wide one is unmeasured there)
-        if rev is not None and (lib.amc3d_contrast_backward_csr_supported(C)
-                                or (ctx.det and lib.amc3d_contrast_backward_rows_supported(C))):
+        elif route == "rows":
             grad_f = torch.empty_like(f)  # every row is written
             gco = torch.empty(m * k, dtype=torch.float32, device=f.device)
             with torch.cuda.device(f.device), timing.span("contrast_backward_csr", m * C * 8 + m * k * 17, moved=m * C * 4 * (2 + 2 * k) + m * k * 17):
@@ -732,26 +777,13 @@ class ContrastStage(Function):
                                                            _ptr(a), _ptr(anchors), _ptr(rev), mu, nu, temperature,
                                                            _ptr(sim), _ptr(mean_cnt), _ptr(g), _ptr(gco), _ptr(grad_f),
                                                            _stream(f)), "contrast_backward_csr")
-            return (grad_f,) + (None,) * 9
-        grad_f = torch.zeros_like(f)
-        with torch.cuda.device(f.device), timing.span("contrast_backward", m * C * 8 + m * k * 9 + m * 8, moved=m * C * 4 * (1 + 2 * k) + m * k * 9):
-            _lib.check(_lib.load().amc3d_contrast_backward(m, C, k, stride, _ptr(f), _ptr(norm), nptr, _ptr(posmask),
-                                                           _ptr(a), _ptr(anchors) if anchors is not None else None,
-                                                           mu, nu, temperature, _ptr(sim), _ptr(mean_cnt),
-                                                           _ptr(g), _ptr(grad_f), _stream(f)), "contrast_backward")
+        else:
+            grad_f = torch.zeros_like(f)
+            with torch.cuda.device(f.device), timing.span("contrast_backward", m * C * 8 + m * k * 9 + m * 8, moved=m * C * 4 * (1 + 2 * k) + m * k * 9):
+                _lib.check(lib.amc3d_contrast_backward(m, C, k, stride, _ptr(f), _ptr(norm), nptr, _ptr(posmask), _ptr(a),
+                                                       _opt(anchors), mu, nu, temperature, _ptr(sim), _ptr(mean_cnt),
+                                                       _ptr(g), _ptr(grad_f), _stream(f)), "contrast_backward")
         return (grad_f,) + (None,) * 9
-
-
-def _contrast_lists(op, C, nbr, a, anchors, rev):
-    """deterministic mode: the (anchors, reverse lists of all their edges) a gathering contrast backward needs, built here
-    where the stage's plan has none; a width without row kernels (no multiple of 4, or above 512) has only the atomic form"""
-    if not _lib.load().amc3d_contrast_backward_rows_supported(C):
-        raise _no_route(op, f"the reverse-list backward does not cover {C} channels")
-    if rev is None:
-        if anchors is None:
-            anchors = select_anchors(a)
-        rev = contrast_csr(nbr, anchors)
-    return anchors, rev
 
 
 contrast_stage = ContrastStage.apply
@@ -783,31 +815,18 @@ def contrast_variant_forward(features, neighbor_idx, posmask, a, form, mu, nu, a
     width has no row kernels), sim (m,k: the cosines of the visited anchors, the bits contrast_stage's forward stores),
     loss_pt (m: the per-anchor loss of the selected anchors; the rest of it is not written when `anchors` is given),
     mean_cnt (2: stage loss, number of selected anchors), nbr (the index tensor the pointers refer to), k, stride."""
-    _need_gpu(features, neighbor_idx, posmask, a)
     f = features.contiguous()
-    assert f.dtype == torch.float32 and posmask.dtype == torch.bool and posmask.is_contiguous()
-    _need_dtype(torch.float32, a=a)
-    if anchors is not None:
-        _need_dtype(torch.int32, anchors=anchors)
-        assert anchors.is_contiguous() and anchors.numel() >= f.shape[0] + 1 and anchors.device == f.device
-    nptr, k, stride, keep = _nbr_view(neighbor_idx)
     m, C = f.shape
-    assert posmask.shape == (m, k) and a.shape == (m,) and a.is_contiguous() and neighbor_idx.shape[0] == m
-    dev = f.device
+    nptr, k, stride, keep = _contrast_inputs(f, m, neighbor_idx, posmask, a, anchors)
     lib = _lib.load()
-    norm = torch.empty(m, dtype=torch.float32, device=dev)
-    unit = torch.empty_like(f) if lib.amc3d_contrast_backward_csr_supported(C) else None
-    sim = torch.empty(m, k, dtype=torch.float32, device=dev)
-    loss_pt = torch.empty(m, dtype=torch.float32, device=dev)
-    mean_cnt = torch.empty(2, dtype=torch.float32, device=dev)
+    norm, unit, sim, loss_pt, mean_cnt = _contrast_buffers(m, C, k, f.device, lib.amc3d_contrast_backward_csr_supported(C), True)
     mode, dbv, method, has_t, T = form
-    with torch.cuda.device(dev), timing.span("contrast_variant_forward", m * C * 4 + m * k * 13 + m * 12,
+    with torch.cuda.device(f.device), timing.span("contrast_variant_forward", m * C * 4 + m * k * 13 + m * 12,
                                              moved=m * C * 4 * (3 + k) + m * k * 13 + m * 12):
-        _lib.check(lib.amc3d_contrast_variant_forward(m, C, k, stride, _ptr(f), nptr, _ptr(posmask), _ptr(a),
-                                                      _ptr(anchors) if anchors is not None else None,
+        _lib.check(lib.amc3d_contrast_variant_forward(m, C, k, stride, _ptr(f), nptr, _ptr(posmask), _ptr(a), _opt(anchors),
                                                       mode, dbv, method, has_t, float(mu), float(nu), T, _ptr(norm),
-                                                      _ptr(unit) if unit is not None else None, _ptr(sim), _ptr(loss_pt),
-                                                      _ptr(mean_cnt), _stream(f)), "contrast_variant_forward")
+                                                      _opt(unit), _ptr(sim), _ptr(loss_pt), _ptr(mean_cnt), _stream(f)),
+                   "contrast_variant_forward")
     return {"f": f, "norm": norm, "unit": unit, "sim": sim, "loss_pt": loss_pt, "mean_cnt": mean_cnt, "nbr": keep, "k": k,
             "stride": stride}
 
@@ -823,14 +842,11 @@ class ContrastStageVariant(Function):
     @staticmethod
     def forward(ctx, features, neighbor_idx, posmask, a, margin, db, supervisedCL, mu, nu, temperature, anchors=None, rev=None):
         form = contrast_form(margin, db, supervisedCL, temperature)
-        b = contrast_variant_forward(features, neighbor_idx, posmask, a, form, mu, nu, anchors)
-        f, k = b["f"], b["k"]
-        m = f.shape[0]
-        if rev is not None:
-            _need_dtype(torch.int32, rev=rev)
-            assert anchors is not None and rev.is_contiguous() and rev.numel() == m + 1 + m * k and rev.device == f.device
-        ctx.save_for_backward(f, b["norm"], b["nbr"], posmask, a, b["sim"], b["mean_cnt"], anchors, rev)
-        ctx.args = (form, float(mu), float(nu), k, b["stride"])
+        f = features.contiguous()
+        _contrast_inputs(f, f.shape[0], neighbor_idx, posmask, a, anchors, rev)  # (rev: the forward itself does not take it)
+        b = contrast_variant_forward(f, neighbor_idx, posmask, a, form, mu, nu, anchors)
+        ctx.save_for_backward(b["f"], b["norm"], b["nbr"], posmask, a, b["sim"], b["mean_cnt"], anchors, rev)
+        ctx.args = (form, float(mu), float(nu), b["k"], b["stride"])
         ctx.det = deterministic()
         return b["mean_cnt"][0].clone()
 
@@ -839,22 +855,17 @@ class ContrastStageVariant(Function):
         f, norm, nbr, posmask, a, sim, mean_cnt, anchors, rev = ctx.saved_tensors
         (mode, dbv, method, has_t, T), mu, nu, k, stride = ctx.args
         m, C = f.shape
-        g = grad_out.detach().to(torch.float32).reshape(1).contiguous()
+        g = _contrast_grad_out(grad_out)
         lib = _lib.load()
-        if ctx.det:
-            if f.data_ptr() % 16:
-                raise _no_route("contrast_variant_backward", "the reverse-list backward needs 16-byte aligned rows")
-            anchors, rev = _contrast_lists("contrast_variant_backward", C, nbr, a, anchors, rev)
-        gather = (rev is not None and f.data_ptr() % 16 == 0 and bool(
-            lib.amc3d_contrast_backward_csr_supported(C) or (ctx.det and lib.amc3d_contrast_backward_rows_supported(C))))
+        route, anchors, rev = _contrast_route_and_lists("contrast_variant_backward", ctx, f, nbr, a, anchors, rev)
+        gather = route == "rows"
         grad_f = torch.empty_like(f) if gather else torch.zeros_like(f)  # (the gather writes every row)
         gco = torch.empty(m * k, dtype=torch.float32, device=f.device)
         name = "contrast_variant_backward_csr" if gather else "contrast_variant_backward"
         with torch.cuda.device(f.device), timing.span(name, m * C * 8 + m * k * 17, moved=m * C * 4 * (2 + 2 * k) + m * k * 17):
             _lib.check(lib.amc3d_contrast_variant_backward(m, C, k, stride, _ptr(f), _ptr(norm), _ptr(nbr), _ptr(posmask), _ptr(a),
-                                                           _ptr(anchors) if anchors is not None else None,
-                                                           _ptr(rev) if gather else None, mode, dbv, method, has_t, mu, nu, T,
-                                                           _ptr(sim), _ptr(mean_cnt), _ptr(g), _ptr(gco), _ptr(grad_f),
+                                                           _opt(anchors), _ptr(rev) if gather else None, mode, dbv, method, has_t,
+                                                           mu, nu, T, _ptr(sim), _ptr(mean_cnt), _ptr(g), _ptr(gco), _ptr(grad_f),
                                                            _stream(f)), name)
         return (grad_f,) + (None,) * 11
 
@@ -870,30 +881,18 @@ class ContrastStageChannelMajor(Function):
     first (pointnext_AA.py:518-519).  The point-major copy of f is never made: the forward writes the unit rows f_i / |f_i|
     through an LDS tile, the mutual-edge backward reads only those; its gradient rows go back through one tiled transpose.
     Needs the mutual-edge plan (anchors, rev, mutual) and C in {16, 32, 64, 128, 256}: contrast_stage_supported_cm() -- and,
-    with that plan, a posmask that is symmetric on mutual edges (label-derived: posmask_from_labels; see contrast_mutual)."""
+    with that plan, a posmask that is symmetric on mutual edges (label-derived: posmask_from_labels; see contrast_mutual).
+    The cosines are not stored (the backward recomputes the ones it needs from the unit rows it fetches anyway)."""
 
     @staticmethod
     def forward(ctx, f_cm, neighbor_idx, posmask, a, mu, nu, temperature, anchors, rev, mutual):
-        _need_gpu(f_cm, neighbor_idx, posmask, a, anchors, rev, mutual)
-        _need_dtype(torch.float32, f_cm=f_cm)
-        _need_dtype(torch.int32, anchors=anchors, rev=rev)
-        _need_dtype(torch.uint8, mutual=mutual)
+        assert anchors is not None and rev is not None and mutual is not None
         f_cm = f_cm.contiguous()
         B, C, n = f_cm.shape
         m = B * n
-        nptr, k, stride, keep = _nbr_view(neighbor_idx)
-        assert posmask.dtype == torch.bool and posmask.is_contiguous() and neighbor_idx.shape[0] == m
-        assert anchors.is_contiguous() and anchors.numel() >= m + 1 and rev.is_contiguous() and rev.numel() == m + 1 + m * k
-        assert mutual.is_contiguous() and mutual.shape == (m, k)
-        dev = f_cm.device
-        norm = torch.empty(m, dtype=torch.float32, device=dev)
-        unit = torch.empty(m, C, dtype=torch.float32, device=dev)
-        # two sums of exponentials per anchor (the positives', the negatives'), kept for the backward's records; the cosines
-        # themselves are not stored (the mutual-edge backward recomputes the ones it needs from the unit rows it fetches anyway)
-        stats = torch.empty(m, 2, dtype=torch.float32, device=dev)
-        loss_pt = torch.empty(m, dtype=torch.float32, device=dev)
-        mean_cnt = torch.empty(2, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev), timing.span("contrast_forward", m * C * 4 + m * k * 5 + m * 20, moved=m * C * 4 * (2 + k) + m * k * 5 + m * 20):
+        nptr, k, stride, keep = _contrast_inputs(f_cm, m, neighbor_idx, posmask, a, anchors, rev, mutual, "f_cm")
+        norm, unit, stats, loss_pt, mean_cnt = _contrast_buffers(m, C, k, f_cm.device, True, False)
+        with torch.cuda.device(f_cm.device), timing.span("contrast_forward", m * C * 4 + m * k * 5 + m * 20, moved=m * C * 4 * (2 + k) + m * k * 5 + m * 20):
             _lib.check(_lib.load().amc3d_contrast_forward_cm(B, C, n, k, stride, _ptr(f_cm), nptr, _ptr(posmask), _ptr(a), _ptr(anchors),
                                                              float(mu), float(nu), float(temperature), _ptr(norm), _ptr(unit),
                                                              None, _ptr(stats), _ptr(loss_pt), _ptr(mean_cnt), _stream(f_cm)),
@@ -907,7 +906,7 @@ class ContrastStageChannelMajor(Function):
         norm, nbr, posmask, a, stats, mean_cnt, rev, mutual, unit = ctx.saved_tensors
         mu, nu, temperature, k, stride, B, C, n = ctx.args
         m = B * n
-        g = grad_out.detach().to(torch.float32).reshape(1).contiguous()
+        g = _contrast_grad_out(grad_out)
         lib = _lib.load()
         grad_rows = torch.empty_like(unit)  # every row is written
         grad_cm = torch.empty(B, C, n, dtype=torch.float32, device=unit.device)

@@ -1,5 +1,5 @@
 """contrast_stage forward / backward on the loss stages of one synthetic S3DIS-like batch (8 x 24000), per stage, HIP-event
-times; AMC3D_LIB selects a diagnostic build of the library (see scratch/contrast_diag.sh).
+times; AMC3D_LIB selects another build of the library with the same C ABI (an A/B against a parent commit's).
 
     python tools/contrast_bench.py                               the default (fused) stage
     python tools/contrast_bench.py --form constant,-m,Method1,0.3   another form of the loss (margin,db,method,T; T may be None):
