@@ -33,6 +33,9 @@ SIGNATURES = {
     "amc3d_three_interpolate": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "amc3d_three_interpolate_add": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "amc3d_three_interpolate_grad": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "amc3d_three_interpolate_grad_route": (_i, [_i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "amc3d_three_interpolate_grad_write": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "amc3d_three_interpolate_grad_lds": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "amc3d_knnquery_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "amc3d_knnquery_uses_grid": (_i, [_i, _i, _i, _i]),
     "amc3d_knnquery": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),

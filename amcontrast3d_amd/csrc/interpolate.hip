@@ -164,6 +164,128 @@ __global__ __launch_bounds__(256) void three_interpolate_grad_csr_kernel(int c, 
         if (k < nch) dst[(size_t)k * m] = acc[k];
 }
 
+// The same gradient summed in LDS: the destination of this scatter is small per (cloud, channel) -- grad_points[b][ch][0..m)
+// is m floats -- so a workgroup that owns cloud b and `cg` consecutive channels keeps its whole output slab acc[cg][m] in
+// LDS, streams over the cloud's n unknown points reading grad_out along its contiguous axis, adds the three products of a
+// point with a hardware LDS float add (no return) and stores the slab once.  The slab of channels c0..c0+cg is one
+// contiguous run of grad_points, so the store is a flat pass.  No global atomic, no scratch, no zero fill, no transpose;
+// the summation order is unspecified, as in the reference.  grid (channel groups, b).
+//
+// The slab is held in DOUBLE and the adds are ds_add_f64: on gfx950 ds_add_f32 retires about one lane every three clocks
+// whatever the addresses (0.79 adds/ns per CU measured, below the chip's global float-atomic rate), ds_add_f64 six to nine
+// times as many (DESIGN.md "three_interpolate backward in LDS").  Every term is still the fp32 product __fmul_rn(g, w),
+// exact as a double; the fp64 sum is rounded to fp32 once, on the way out.
+//
+// A wave takes IGL_PPL x 64 consecutive points at a time (a lane: IGL_PPL points 64 apart), holds their idx / weight in
+// registers and walks its channels four at a time, all loads of a step issued before the adds.  Where n has fewer such
+// chunks than the workgroup has waves (coarse levels), `csplit` sub-groups of the channels go to different waves.
+constexpr int IGL_PPL = 2;
+constexpr int IGL_CHUNK = 64 * IGL_PPL;
+constexpr int IGL_MAX_CG = 16;
+constexpr size_t IGL_LDS_BUDGET = 128 * 1024;  // bytes of slab a workgroup may take on the dispatched route
+constexpr size_t IGL_LDS_LIMIT = 160 * 1024;   // what the hardware allows the explicit entry
+constexpr int IGL_MIN_GROUPS = 256;            // one workgroup per CU before channels are grouped
+
+template <bool ACCUMULATE>
+__global__ __launch_bounds__(1024) void three_interpolate_grad_lds_kernel(int c, int n, int m, int cg, int csplit,
+                                                                          const float *__restrict__ grad_out,
+                                                                          const int *__restrict__ idx,
+                                                                          const float *__restrict__ weight,
+                                                                          float *__restrict__ grad_points)
+{
+    extern __shared__ double igl_acc[];  // [cnt][m]
+    const int bs = blockIdx.y;
+    const int c0 = blockIdx.x * cg;
+    const int cnt = min(cg, c - c0);
+    const int total = cnt * m;
+    for (int i = threadIdx.x; i < total; i += blockDim.x) igl_acc[i] = 0.0;
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+    const int chunks = (n + IGL_CHUNK - 1) / IGL_CHUNK;
+    const int csub = (cnt + csplit - 1) / csplit;  // channels per sub-group
+    const int *ii = idx + (size_t)bs * n * 3;
+    const float *ww = weight + (size_t)bs * n * 3;
+    const float *src = grad_out + ((size_t)bs * c + c0) * n;
+    for (int u = wave; u < chunks * csplit; u += waves) {
+        const int p0 = (u % chunks) * IGL_CHUNK + lane;
+        const int k_lo = (u / chunks) * csub, k_hi = min(cnt, k_lo + csub);
+        int pt[IGL_PPL], t[IGL_PPL][3];
+        float w[IGL_PPL][3];
+#pragma unroll
+        for (int q = 0; q < IGL_PPL; ++q) {
+            const int p = p0 + q * 64;
+            const bool live = p < n;
+            pt[q] = live ? p : 0;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                t[q][j] = ii[(size_t)pt[q] * 3 + j];
+                w[q][j] = live ? ww[(size_t)pt[q] * 3 + j] : 0.f;
+            }
+            if (!live) pt[q] = -1;
+        }
+        for (int k = k_lo; k < k_hi; k += 4) {
+            float g[4][IGL_PPL];
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+                for (int q = 0; q < IGL_PPL; ++q)
+                    g[kk][q] = (k + kk < k_hi && pt[q] >= 0) ? src[(size_t)(k + kk) * n + pt[q]] : 0.f;
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                if (k + kk < k_hi) {
+                    double *row = igl_acc + (k + kk) * m;
+#pragma unroll
+                    for (int q = 0; q < IGL_PPL; ++q)
+                        if (pt[q] >= 0) {
+#pragma unroll
+                            for (int j = 0; j < 3; ++j)
+                                (void)__hip_atomic_fetch_add(row + t[q][j], (double)__fmul_rn(g[kk][q], w[q][j]), __ATOMIC_RELAXED,
+                                                             __HIP_MEMORY_SCOPE_WORKGROUP);
+                        }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    float *dst = grad_points + ((size_t)bs * c + c0) * m;
+    for (int i = threadIdx.x; i < total; i += blockDim.x) dst[i] = (float)(ACCUMULATE ? (double)dst[i] + igl_acc[i] : igl_acc[i]);
+}
+
+// Workgroup size by n: enough waves to keep loads in flight at the fine levels, no idle waves at the coarse ones.
+static int igl_threads(int n) { return n >= 8192 ? 1024 : n >= 1024 ? 512 : 256; }
+
+// The dispatched route's channel group: the largest power of two whose slab fits the budget, halved while the grid would
+// have fewer workgroups than CUs.  0: one channel's slab does not fit (or c < 8): not an LDS shape.
+static int igl_cg(int b, int c, int m)
+{
+    if (c < 8 || m <= 0 || b > 65535) return 0;
+    const size_t fit = IGL_LDS_BUDGET / ((size_t)m * sizeof(double));
+    if (fit < 1) return 0;
+    int cg = 1;
+    while (cg * 2 <= IGL_MAX_CG && (size_t)cg * 2 <= fit && cg * 2 <= c) cg *= 2;
+    while (cg > 1 && (long)b * div_up(c, cg) < IGL_MIN_GROUPS) cg /= 2;
+    return cg;
+}
+
+static int igl_launch(int b, int c, int n, int m, int cg, int threads, bool accumulate, const float *grad_out, const int *idx,
+                      const float *weight, float *grad_points, hipStream_t stream, const char *what)
+{
+    const size_t lds = (size_t)cg * m * sizeof(double);
+    const int waves = threads / 64, chunks = n > 0 ? div_up(n, IGL_CHUNK) : 1;
+    int csplit = chunks >= waves ? 1 : waves / chunks;
+    if (csplit > cg) csplit = cg;
+    const dim3 grid(div_up(c, cg), b);
+    if (accumulate) {
+        (void)hipFuncSetAttribute((const void *)three_interpolate_grad_lds_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)IGL_LDS_LIMIT);
+        hipLaunchKernelGGL(three_interpolate_grad_lds_kernel<true>, grid, dim3(threads), lds, stream, c, n, m, cg, csplit, grad_out, idx, weight, grad_points);
+    } else {
+        (void)hipFuncSetAttribute((const void *)three_interpolate_grad_lds_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)IGL_LDS_LIMIT);
+        hipLaunchKernelGGL(three_interpolate_grad_lds_kernel<false>, grid, dim3(threads), lds, stream, c, n, m, cg, csplit, grad_out, idx, weight, grad_points);
+    }
+    return launch_status(what);
+}
+
 }  // namespace amc
 
 using namespace amc;
@@ -230,12 +352,53 @@ AMC_API int amc3d_three_interpolate_grad(int b, int c, int n, int m, const float
 {
     if (b <= 0 || c <= 0 || n <= 0) return 0;
     if (!grad_out || !idx || !weight || !grad_points) return bad_arg("amc3d_three_interpolate_grad: null pointer");
+    if (const int cg = igl_cg(b, c, m))
+        return igl_launch(b, c, n, m, cg, igl_threads(n), true, grad_out, idx, weight, grad_points, (hipStream_t)stream,
+                          "amc3d_three_interpolate_grad");
     if (workspace && workspace_bytes >= (size_t)b * c * m * sizeof(float) && c >= 8)
         return scatter_add_pm(3, b, c, m, n, grad_out, idx, weight, grad_points, (float *)workspace,
                               (hipStream_t)stream, "amc3d_three_interpolate_grad");
     hipLaunchKernelGGL(three_interpolate_grad_kernel, dim3(div_up(n, 256), b), dim3(256), 0, (hipStream_t)stream, c, n,
                        m, grad_out, idx, weight, grad_points);
     return launch_status("amc3d_three_interpolate_grad");
+}
+
+// Which way amc3d_three_interpolate_grad takes for this shape: 0 one global atomic per term (c < 8), 1 point-major global
+// atomics (needs the workspace; 0 without it), 2 summed in LDS.  cg / threads (optional): the LDS route's channel group
+// and workgroup size, 0 on the other routes.
+AMC_API int amc3d_three_interpolate_grad_route(int b, int c, int n, int m, int *cg, int *threads)
+{
+    const int g = (b > 0 && c > 0 && n > 0) ? igl_cg(b, c, m) : 0;
+    if (cg) *cg = g;
+    if (threads) *threads = g ? igl_threads(n) : 0;
+    return g ? 2 : c >= 8 ? 1 : 0;
+}
+
+// The LDS route in overwrite form: every element of grad_points (b,c,m) is written (a known point that no unknown point
+// names gets +0.0f), so the caller neither zero-fills nor passes a workspace.  Only for shapes whose route is 2.
+AMC_API int amc3d_three_interpolate_grad_write(int b, int c, int n, int m, const float *grad_out, const int *idx,
+                                               const float *weight, float *grad_points, void *stream)
+{
+    if (b <= 0 || c <= 0 || m <= 0) return 0;
+    const int cg = igl_cg(b, c, m);
+    if (n < 0 || (n > 0 && (!grad_out || !idx || !weight)) || !grad_points || !cg)
+        return bad_arg("amc3d_three_interpolate_grad_write: bad argument, or not a shape of the LDS route");
+    return igl_launch(b, c, n, m, cg, igl_threads(n), false, grad_out, idx, weight, grad_points, (hipStream_t)stream,
+                      "amc3d_three_interpolate_grad_write");
+}
+
+// The LDS kernel with the channel group and the workgroup size given (tools/interp_grad_bench.py sweeps them; the tests
+// reach every kernel path at small shapes).  cg * m doubles must fit the 160 KiB of a CU; threads 256, 512 or 1024.
+AMC_API int amc3d_three_interpolate_grad_lds(int b, int c, int n, int m, int cg, int threads, int accumulate,
+                                             const float *grad_out, const int *idx, const float *weight, float *grad_points,
+                                             void *stream)
+{
+    if (b <= 0 || c <= 0 || m <= 0) return 0;
+    if (n < 0 || (n > 0 && (!grad_out || !idx || !weight)) || !grad_points || b > 65535 || cg < 1 ||
+        (size_t)cg * m * sizeof(double) > IGL_LDS_LIMIT || (threads != 256 && threads != 512 && threads != 1024))
+        return bad_arg("amc3d_three_interpolate_grad_lds: bad argument");
+    return igl_launch(b, c, n, m, cg, threads, accumulate != 0, grad_out, idx, weight, grad_points, (hipStream_t)stream,
+                      "amc3d_three_interpolate_grad_lds");
 }
 
 // amc3d_three_interpolate_grad without atomics: rev_start (b*m + 1) / rev_edge (b*n*3) = amc3d_group_csr(b, m, n, 3, idx).

@@ -381,15 +381,25 @@ class ThreeInterpolate(Function):
         B, c, n = grad_out.size()
         if ctx.det:
             return _three_interpolate_grad_csr(grad_out.detach().contiguous(), idx, weight, m, ctx.csr), None, None, None
-        grad_features = torch.zeros(B, c, m, dtype=torch.float32, device=grad_out.device)
-        grad_out_data = grad_out.detach().contiguous()
-        with torch.cuda.device(grad_out.device), timing.span("three_interpolate_grad", grad_out_data.numel() * 4 + idx.numel() * 8 + grad_features.numel() * 4):
+        return _three_interpolate_grad(grad_out.detach().contiguous(), idx, weight, m), None, None, None
+
+
+def _three_interpolate_grad(grad_out, idx, weight, m):
+    """grad of three_interpolate, default mode: summed in LDS and written whole where the shape takes that route, else
+    global float atomics into a zeroed output through a point-major workspace"""
+    B, c, n = grad_out.size()
+    lib = _lib.load()
+    lds = lib.amc3d_three_interpolate_grad_route(B, c, n, m, None, None) == 2
+    grad_features = (torch.empty if lds else torch.zeros)(B, c, m, dtype=torch.float32, device=grad_out.device)
+    with torch.cuda.device(grad_out.device), timing.span("three_interpolate_grad", grad_out.numel() * 4 + idx.numel() * 8 + grad_features.numel() * 4):
+        if lds:
+            _lib.check(lib.amc3d_three_interpolate_grad_write(B, c, n, m, _ptr(grad_out), _ptr(idx), _ptr(weight),
+                                                              _ptr(grad_features), _stream(grad_out)), "three_interpolate_grad")
+        else:
             work = torch.empty(B * c * m, dtype=torch.float32, device=grad_out.device)
-            _lib.check(_lib.load().amc3d_three_interpolate_grad(B, c, n, m, _ptr(grad_out_data), _ptr(idx),
-                                                                _ptr(weight), _ptr(grad_features), _ptr(work),
-                                                                work.numel() * 4, _stream(grad_out)),
-                       "three_interpolate_grad")
-        return grad_features, None, None, None
+            _lib.check(lib.amc3d_three_interpolate_grad(B, c, n, m, _ptr(grad_out), _ptr(idx), _ptr(weight), _ptr(grad_features),
+                                                        _ptr(work), work.numel() * 4, _stream(grad_out)), "three_interpolate_grad")
+    return grad_features
 
 
 def _three_interpolate_grad_csr(grad_out, idx, weight, m, csr):
@@ -438,13 +448,7 @@ class ThreeInterpolateAdd(Function):
         grad_out_data = grad_out.detach().contiguous()
         if ctx.det:
             return _three_interpolate_grad_csr(grad_out_data, idx, weight, m, ctx.csr), None, None, grad_out, None
-        grad_features = torch.zeros(B, c, m, dtype=torch.float32, device=grad_out.device)
-        with torch.cuda.device(grad_out.device), timing.span("three_interpolate_grad", grad_out_data.numel() * 4 + idx.numel() * 8 + grad_features.numel() * 4):
-            work = torch.empty(B * c * m, dtype=torch.float32, device=grad_out.device)
-            _lib.check(_lib.load().amc3d_three_interpolate_grad(B, c, n, m, _ptr(grad_out_data), _ptr(idx), _ptr(weight),
-                                                                _ptr(grad_features), _ptr(work), work.numel() * 4,
-                                                                _stream(grad_out)), "three_interpolate_grad")
-        return grad_features, None, None, grad_out, None
+        return _three_interpolate_grad(grad_out_data, idx, weight, m), None, None, grad_out, None
 
 
 three_interpolate_add = ThreeInterpolateAdd.apply

@@ -125,6 +125,18 @@ int amc3d_three_interpolate_add(int b, int c, int m, int n, const float *points,
 int amc3d_three_interpolate_grad(int b, int c, int n, int m, const float *grad_out,
                                  const int *idx, const float *weight, float *grad_points,
                                  void *workspace, size_t workspace_bytes, void *stream);
+/* Where one channel's slab of m doubles fits the LDS budget (m <= 16384) and c >= 8, the gradient is summed in LDS by a workgroup per
+ * (cloud, group of cg channels): no global atomics, and the workspace is not touched.  amc3d_three_interpolate_grad_route
+ * says which way a shape goes: 0 one global atomic per term, 1 point-major global atomics (with the workspace), 2 LDS;
+ * cg / threads (may be NULL) receive the LDS route's channel group and workgroup size, 0 otherwise. */
+int amc3d_three_interpolate_grad_route(int b, int c, int n, int m, int *cg, int *threads);
+/* Route 2 in overwrite form: writes every element of grad_points (b,c,m) -- +0.0f where no unknown point names the known
+ * point -- so the caller neither zero-initialises nor passes a workspace.  An error for shapes whose route is not 2. */
+int amc3d_three_interpolate_grad_write(int b, int c, int n, int m, const float *grad_out, const int *idx,
+                                       const float *weight, float *grad_points, void *stream);
+/* The LDS kernel with cg and threads (256, 512, 1024) given; cg * m doubles <= 160 KiB.  accumulate != 0: grad_points +=. */
+int amc3d_three_interpolate_grad_lds(int b, int c, int n, int m, int cg, int threads, int accumulate, const float *grad_out,
+                                     const int *idx, const float *weight, float *grad_points, void *stream);
 /* The same gradient without atomics (deterministic mode), from the reverse lists of idx seen as a query of n points with 3
  * samples into the m known points: rev_start (b*m + 1), rev_edge (b*n*3) = amc3d_group_csr(b, m, n, 3, idx, ...).
  * SUMMATION ORDER (part of the contract, shared by the three *_csr gathers of deterministic mode): every target takes its
