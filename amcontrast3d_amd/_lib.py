@@ -54,6 +54,9 @@ SIGNATURES = {
     "amc3d_contrast_backward_mutual_workspace_bytes": (_sz, [_i]),
     "amc3d_contrast_backward_mutual": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz,
                                             _vp, _vp]),
+    "amc3d_contrast_stages_forward_cm": (_i, [_i, _vp, _f, _f, _f, _f, _vp, _vp]),
+    "amc3d_contrast_stages_backward_cm_workspace_bytes": (_sz, [_i, _vp]),
+    "amc3d_contrast_stages_backward_cm": (_i, [_i, _vp, _f, _f, _f, _f, _vp, _vp, _sz, _vp]),
     "amc3d_contrast_variant_forward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp,
                                             _vp, _vp]),
     "amc3d_contrast_variant_backward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp,
@@ -178,6 +181,16 @@ SIGNATURES = {
     "amc3d_bn_backward_sums": (_i, [_i, _i, _l, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_bn_backward_synced": (_i, [_i, _i, _l, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+
+
+CONTRAST_MAX_STAGES = 8  # AMC_CONTRAST_MAX_STAGES
+
+
+class ContrastStageDesc(ctypes.Structure):
+    """AmcContrastStage of include/amc3d.h"""
+    _fields_ = ([(n, _i) for n in ("b", "C", "n", "k", "nbr_stride")]
+                + [(n, _vp) for n in ("f_cm", "nbr", "posmask", "a", "sel", "mutual", "rev", "norm", "unit", "stats", "loss_pt",
+                                      "mean_cnt", "rec", "grad_cm")])
 
 
 def build(force=False):

@@ -16,6 +16,7 @@
 #include "common.h"
 
 #include <type_traits>
+#include <utility>
 
 namespace amc {
 
@@ -156,13 +157,15 @@ __global__ __launch_bounds__(256) void row_unit_kernel(int m, const float *__res
 // the same from CHANNEL-major embeddings f_cm (B, C, n), as the decoder leaves them (pointnext_AA.py:518-519 makes the
 // point-major copy the loss reads with flatten(transpose)): a 64-point tile goes through LDS, the row-major f is never
 // written.  Same arithmetic and summation order as row_unit_kernel.
-template <int LPR, int TP>  // TP points per tile (16 at the wide, short stages: a cloud of 375 points is 24 tiles, not 6)
-__global__ __launch_bounds__(256) void row_unit_cm_kernel(int n, const float *__restrict__ f_cm, float *__restrict__ norm,
-                                                          float *__restrict__ unit)
+// TP points per tile (16 at the wide, short stages: a cloud of 375 points is 24 tiles, not 6)
+template <int LPR> constexpr int unit_tile_points() { return LPR >= 32 ? 16 : 64; }
+
+// one tile: the points n0 .. n0 + TP of cloud b; s_tile = [C][TP + 1] floats of LDS
+template <int LPR, int TP>
+__device__ __forceinline__ void row_unit_cm_tile(float *s_tile, int n, int b, int n0, const float *__restrict__ f_cm,
+                                                 float *__restrict__ norm, float *__restrict__ unit)
 {
     constexpr int C = 4 * LPR, TS = TP + 1;
-    extern __shared__ float s_tile[];  // [C][TP + 1]
-    const int b = blockIdx.y, n0 = blockIdx.x * TP;
     for (int e = threadIdx.x; e < C * TP; e += 256) {
         const int ch = e / TP, pt = e - ch * TP;
         s_tile[ch * TS + pt] = n0 + pt < n ? f_cm[((size_t)b * C + ch) * n + n0 + pt] : 0.f;
@@ -186,6 +189,14 @@ __global__ __launch_bounds__(256) void row_unit_cm_kernel(int n, const float *__
             if (q == 0) norm[i] = nv;
         }
     }
+}
+
+template <int LPR, int TP>
+__global__ __launch_bounds__(256) void row_unit_cm_kernel(int n, const float *__restrict__ f_cm, float *__restrict__ norm,
+                                                          float *__restrict__ unit)
+{
+    extern __shared__ float s_tile[];  // [C][TP + 1]
+    row_unit_cm_tile<LPR, TP>(s_tile, n, blockIdx.y, blockIdx.x * TP, f_cm, norm, unit);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -496,9 +507,10 @@ __global__ __launch_bounds__(256) void select_write_kernel(int m, const float *_
 // Same per-element arithmetic as contrast_forward_kernel below (u_c / n_i * (v_c / n_x), channel order of the tree).
 // sel == nullptr: every anchor is visited and tested.
 // ---------------------------------------------------------------------------------------------
+// the wave of anchor group w (w = 4 * block + wave of the block)
 template <int LPR>
-__global__ __launch_bounds__(256) void contrast_forward_unit_kernel(
-    int m, int k, int nbr_stride, const float *__restrict__ unit, const int *__restrict__ nbr,
+__device__ __forceinline__ void contrast_forward_unit_wave(
+    int w, int m, int k, int nbr_stride, const float *__restrict__ unit, const int *__restrict__ nbr,
     const unsigned char *__restrict__ posmask, const float *__restrict__ a, const int *__restrict__ sel, float mu, float nu,
     float temperature, float *__restrict__ sim, float *__restrict__ stats, float *__restrict__ loss_pt)
 {
@@ -506,7 +518,7 @@ __global__ __launch_bounds__(256) void contrast_forward_unit_kernel(
     const int lane = threadIdx.x & 63, q = lane & (LPR - 1), r = lane / LPR;
     int i;
     float ai;
-    if (!contrast_anchor(sel, m, blockIdx.x * 4 + (threadIdx.x >> 6), a, i, ai)) return;
+    if (!contrast_anchor(sel, m, w, a, i, ai)) return;
     if (!contrast_selected(ai)) {
         if (lane == 0) loss_pt[i] = 0.f;
         return;
@@ -543,6 +555,16 @@ __global__ __launch_bounds__(256) void contrast_forward_unit_kernel(
         loss_pt[i] = -logf(__fadd_rn(__fdiv_rn(psum, tsum), 1e-12f));
         if (stats) { stats[(size_t)i * 2] = psum; stats[(size_t)i * 2 + 1] = nsum; }  // what the backward's records need of this pass
     }
+}
+
+template <int LPR>
+__global__ __launch_bounds__(256) void contrast_forward_unit_kernel(
+    int m, int k, int nbr_stride, const float *__restrict__ unit, const int *__restrict__ nbr,
+    const unsigned char *__restrict__ posmask, const float *__restrict__ a, const int *__restrict__ sel, float mu, float nu,
+    float temperature, float *__restrict__ sim, float *__restrict__ stats, float *__restrict__ loss_pt)
+{
+    contrast_forward_unit_wave<LPR>(blockIdx.x * 4 + (threadIdx.x >> 6), m, k, nbr_stride, unit, nbr, posmask, a, sel, mu, nu,
+                                    temperature, sim, stats, loss_pt);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -595,11 +617,10 @@ __global__ __launch_bounds__(256) void contrast_forward_kernel(
 // mean of loss_pt over the selected anchors, deterministically (one workgroup, fixed order):
 // out[0] = sum / count, out[1] = count.  torch.mean of an empty selection is NaN in the
 // reference; so is 0/0 here.
-__global__ __launch_bounds__(1024) void masked_mean_kernel(int m, const float *__restrict__ loss_pt,
-                                                           const float *__restrict__ a, float *__restrict__ out)
+// (the 1024 threads of one workgroup; thread 0 returns out[0], the others 0)
+__device__ __forceinline__ float masked_mean_block(double (&s_sum)[16], int (&s_cnt)[16], int m, const float *__restrict__ loss_pt,
+                                                   const float *__restrict__ a, float *__restrict__ out)
 {
-    __shared__ double s_sum[16];
-    __shared__ int s_cnt[16];
     double sum = 0.0;
     int cnt = 0;
     // one workgroup (fixed order, no workspace): keep many 16-byte loads in flight per thread instead of a
@@ -632,13 +653,24 @@ __global__ __launch_bounds__(1024) void masked_mean_kernel(int m, const float *_
     }
     if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6] = sum; s_cnt[threadIdx.x >> 6] = cnt; }
     __syncthreads();
+    float mean = 0.f;
     if (threadIdx.x == 0) {
         double t = 0.0;
         int c = 0;
         for (int w = 0; w < 16; ++w) { t += s_sum[w]; c += s_cnt[w]; }
-        out[0] = (float)(t / (double)c);
+        mean = (float)(t / (double)c);
+        out[0] = mean;
         out[1] = (float)c;
     }
+    return mean;
+}
+
+__global__ __launch_bounds__(1024) void masked_mean_kernel(int m, const float *__restrict__ loss_pt,
+                                                           const float *__restrict__ a, float *__restrict__ out)
+{
+    __shared__ double s_sum[16];
+    __shared__ int s_cnt[16];
+    masked_mean_block(s_sum, s_cnt, m, loss_pt, a, out);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -901,18 +933,18 @@ __global__ __launch_bounds__(256) void contrast_record_kernel(
 
 // the same records from the two sums the forward pass kept per anchor (stats[2 i] = sum of the positives' exponentials,
 // stats[2 i + 1] = sum of the negatives'): nothing to recompute, no similarities to read; one thread per anchor
-__global__ __launch_bounds__(256) void contrast_record_stats_kernel(int m, const float *__restrict__ norm, const float *__restrict__ a,
-                                                                    float mu, float nu, float temperature,
-                                                                    const float *__restrict__ stats, const float *__restrict__ mean_cnt,
-                                                                    const float *__restrict__ grad_out, ContrastRecord *__restrict__ rec)
+// (the record of anchor i; g = the gradient of the stage's mean)
+__device__ __forceinline__ void contrast_record_stats_anchor(int i, int m, const float *__restrict__ norm, const float *__restrict__ a,
+                                                             float mu, float nu, float temperature, const float *__restrict__ stats,
+                                                             const float *__restrict__ mean_cnt, float g,
+                                                             ContrastRecord *__restrict__ rec)
 {
-    const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= m) return;
     const float ai = a[i];
     const bool selected = contrast_selected(ai);  // (the forward visited the selected anchors only: the others' stats are unwritten)
     const float psum = selected ? stats[(size_t)i * 2] : 0.f, nsum = selected ? stats[(size_t)i * 2 + 1] : 1.f;
     const float tsum = __fadd_rn(psum, nsum);
-    const float scale = grad_out[0] / mean_cnt[1];
+    const float scale = g / mean_cnt[1];
     ContrastRecord o;
     o.norm = norm[i];
     o.coef = (selected && psum != 0.f) ? contrast_coef(scale, psum, tsum, temperature) : 0.f;
@@ -920,20 +952,27 @@ __global__ __launch_bounds__(256) void contrast_record_stats_kernel(int m, const
     rec[i] = o;
 }
 
+__global__ __launch_bounds__(256) void contrast_record_stats_kernel(int m, const float *__restrict__ norm, const float *__restrict__ a,
+                                                                    float mu, float nu, float temperature,
+                                                                    const float *__restrict__ stats, const float *__restrict__ mean_cnt,
+                                                                    const float *__restrict__ grad_out, ContrastRecord *__restrict__ rec)
+{
+    contrast_record_stats_anchor(blockIdx.x * 256 + threadIdx.x, m, norm, a, mu, nu, temperature, stats, mean_cnt, grad_out[0], rec);
+}
+
 // The mutual-edge gather (unit rows, see row_unit_kernel: hx = f_x / n_x is fetched, not recomputed; lane q < UNIT_U of a row
 // decodes and evaluates the row's slot of round q -- index, mask, mutual count, the record of x, the two exponentials --
-// once, and hands x down to / the finished coefficient back to the row's lanes by shuffles)
+// once, and hands x down to / the finished coefficient back to the row's lanes by shuffles).  One wave: row n < m of the
+// gradient, every lane returns piece q of it.
 template <int LPR>
-__global__ __launch_bounds__(256) void contrast_backward_mutual_kernel(
-    int m, int k, int nbr_stride, const float *__restrict__ unit, const int *__restrict__ nbr,
+__device__ __forceinline__ float4 contrast_mutual_row(
+    int lane, int n, int m, int k, int nbr_stride, const float *__restrict__ unit, const int *__restrict__ nbr,
     const unsigned char *__restrict__ posmask, const unsigned char *__restrict__ mutual, const int *__restrict__ rev,
-    const ContrastRecord *__restrict__ rec, float temperature, float *__restrict__ grad_f)
+    const ContrastRecord *__restrict__ rec, float temperature)
 {
     constexpr int R = 64 / LPR;  // rows per round
     constexpr int U = UNIT_U;    // rounds in flight
-    const int lane = threadIdx.x & 63, q = lane & (LPR - 1), r = lane / LPR, row0 = lane & ~(LPR - 1);
-    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= m) return;
+    const int q = lane & (LPR - 1), r = lane / LPR, row0 = lane & ~(LPR - 1);
     const float4 *h4 = reinterpret_cast<const float4 *>(unit);
     const float4 *rec4 = reinterpret_cast<const float4 *>(rec);
     const float4 rn0 = rec4[(size_t)n * 2];       // norm, coef, (tsum: not read here), psum
@@ -1004,7 +1043,155 @@ __global__ __launch_bounds__(256) void contrast_backward_mutual_kernel(
         acc.z += __shfl_xor(acc.z, d, 64);
         acc.w += __shfl_xor(acc.w, d, 64);
     }
-    if (r == 0) reinterpret_cast<float4 *>(grad_f)[(size_t)n * LPR + q] = acc;
+    return acc;
+}
+
+template <int LPR>
+__global__ __launch_bounds__(256) void contrast_backward_mutual_kernel(
+    int m, int k, int nbr_stride, const float *__restrict__ unit, const int *__restrict__ nbr,
+    const unsigned char *__restrict__ posmask, const unsigned char *__restrict__ mutual, const int *__restrict__ rev,
+    const ContrastRecord *__restrict__ rec, float temperature, float *__restrict__ grad_f)
+{
+    const int lane = threadIdx.x & 63;
+    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= m) return;
+    const float4 acc = contrast_mutual_row<LPR>(lane, n, m, k, nbr_stride, unit, nbr, posmask, mutual, rev, rec, temperature);
+    if (lane < LPR) reinterpret_cast<float4 *>(grad_f)[(size_t)n * LPR + lane] = acc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// All stages of the loss per launch (amc3d_contrast_stages_forward_cm / _backward_cm).  The descriptors travel by value; a
+// kernel's grid is the concatenation of the stages' grids, first[s] = the first block of stage s (first[nstages] = the
+// grid).  A block finds its stage by a scan that is uniform across the workgroup, and its width by a switch that calls the
+// body the single-stage kernel of that width calls: the arithmetic of a stage does not know which launch it runs in.
+// ---------------------------------------------------------------------------------------------
+struct ContrastStages {
+    int nstages;
+    int first[AMC_CONTRAST_MAX_STAGES + 1];
+    AmcContrastStage st[AMC_CONTRAST_MAX_STAGES];
+};
+
+// -> the stage of block blk, and blk as the block's index within that stage
+__device__ __forceinline__ int contrast_stage_of_block(const ContrastStages &S, int &blk)
+{
+    int s = 0;
+    while (s + 1 < S.nstages && blk >= S.first[s + 1]) ++s;
+    blk -= S.first[s];
+    return s;
+}
+
+template <int N> using int_c = std::integral_constant<int, N>;
+
+// fn(int_c<C / 4>) for the widths of amc3d_contrast_backward_csr_supported (the entry points admit no other)
+template <class F>
+__device__ __forceinline__ void device_with_lpr(int C, F &&fn)
+{
+    switch (C) {
+    case 16: fn(int_c<4>{}); break;
+    case 32: fn(int_c<8>{}); break;
+    case 64: fn(int_c<16>{}); break;
+    case 128: fn(int_c<32>{}); break;
+    case 256: fn(int_c<64>{}); break;
+    default: break;
+    }
+}
+
+// Points per tile of the channel-major gradient store (contrast_stages_backward_kernel): a tile is [C][TP + 1] floats of
+// LDS and is written as runs of TP floats.  A wave walks TP / 4 rows one after the other, and the wide stages are short (375
+// points per cloud at 256 channels): the small tiles keep as many waves on their rows as the row-major kernel has, and
+// that outweighs the short runs (profiles/contrast_stages_tile_sweep.txt: the best of 4 .. 64 points per width)
+template <int LPR> constexpr int grad_tile_points() { return LPR >= 64 ? 4 : LPR >= 32 ? 8 : 16; }
+
+__global__ __launch_bounds__(256) void contrast_stages_unit_kernel(const ContrastStages S)
+{
+    extern __shared__ float s_tile[];
+    int blk = blockIdx.x;
+    const AmcContrastStage &st = S.st[contrast_stage_of_block(S, blk)];
+    device_with_lpr(st.C, [&](auto lpr) {
+        constexpr int LPR = decltype(lpr)::value, TP = unit_tile_points<LPR>();
+        const int tiles = (st.n + TP - 1) / TP;
+        row_unit_cm_tile<LPR, TP>(s_tile, st.n, blk / tiles, (blk % tiles) * TP, st.f_cm, st.norm, st.unit);
+    });
+}
+
+__global__ __launch_bounds__(256) void contrast_stages_forward_kernel(const ContrastStages S, float mu, float nu, float temperature)
+{
+    int blk = blockIdx.x;
+    const AmcContrastStage &st = S.st[contrast_stage_of_block(S, blk)];
+    device_with_lpr(st.C, [&](auto lpr) {
+        contrast_forward_unit_wave<decltype(lpr)::value>(blk * 4 + (threadIdx.x >> 6), st.b * st.n, st.k, st.nbr_stride, st.unit, st.nbr,
+                                                         st.posmask, st.a, st.sel, mu, nu, temperature, nullptr, st.stats, st.loss_pt);
+    });
+}
+
+// One workgroup: masked_mean_kernel's sums stage by stage, then total = scale * (((l0 + l1) + l2) + ...), the chain the
+// per-stage route leaves to the caller's additions
+__global__ __launch_bounds__(1024) void contrast_stages_mean_kernel(const ContrastStages S, float scale, float *__restrict__ total)
+{
+    __shared__ double s_sum[16];
+    __shared__ int s_cnt[16];
+    __shared__ float s_mean[AMC_CONTRAST_MAX_STAGES];
+#pragma unroll 1
+    for (int s = 0; s < S.nstages; ++s) {
+        const AmcContrastStage &st = S.st[s];
+        const float l = masked_mean_block(s_sum, s_cnt, st.b * st.n, st.loss_pt, st.a, st.mean_cnt);
+        if (threadIdx.x == 0) s_mean[s] = l;
+        __syncthreads();  // (s_sum, s_cnt are free again)
+    }
+    if (threadIdx.x == 0) {
+        float t = s_mean[0];
+        for (int s = 1; s < S.nstages; ++s) t = __fadd_rn(t, s_mean[s]);
+        total[0] = __fmul_rn(scale, t);
+    }
+}
+
+__global__ __launch_bounds__(256) void contrast_stages_record_kernel(const ContrastStages S, float mu, float nu, float temperature,
+                                                                     float scale, const float *__restrict__ grad_out)
+{
+    int blk = blockIdx.x;
+    const AmcContrastStage &st = S.st[contrast_stage_of_block(S, blk)];
+    contrast_record_stats_anchor(blk * 256 + threadIdx.x, st.b * st.n, st.norm, st.a, mu, nu, temperature, st.stats, st.mean_cnt,
+                                 __fmul_rn(grad_out[0], scale), (ContrastRecord *)st.rec);
+}
+
+// The mutual-edge gather storing CHANNEL-major: a workgroup owns the points n0 .. n0 + TP of one cloud, its waves take those
+// rows in turn (contrast_mutual_row: the accumulators and their order are the single-stage kernel's), a finished row goes
+// from its lanes into the tile, and after one barrier the tile leaves as runs of TP floats of grad_cm[b][c][n0 ...].
+template <int LPR, int TP>
+__device__ __forceinline__ void contrast_mutual_tile_cm(float *s_tile, const AmcContrastStage &st, int blk, float temperature)
+{
+    constexpr int C = 4 * LPR, TS = TP + 1;
+    const int tiles = (st.n + TP - 1) / TP;
+    const int b = blk / tiles, n0 = (blk % tiles) * TP;
+    const int np = min(TP, st.n - n0);  // points of this tile
+    int lane = threadIdx.x & 63;
+    for (int pl = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); pl < np; pl += 4) {  // (a scalar: the row is the wave's)
+        asm volatile("" : "+v"(lane));  // (what derives from the lane is formed per row, not kept across the rows)
+        const float4 acc = contrast_mutual_row<LPR>(lane, b * st.n + n0 + pl, st.b * st.n, st.k, st.nbr_stride, st.unit, st.nbr, st.posmask,
+                                                    st.mutual, st.rev, (const ContrastRecord *)st.rec, temperature);
+        if (lane < LPR) {
+            s_tile[(4 * lane) * TS + pl] = acc.x;
+            s_tile[(4 * lane + 1) * TS + pl] = acc.y;
+            s_tile[(4 * lane + 2) * TS + pl] = acc.z;
+            s_tile[(4 * lane + 3) * TS + pl] = acc.w;
+        }
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < C * TP; e += 256) {
+        const int ch = e / TP, pt = e - ch * TP;
+        if (pt < np) st.grad_cm[((size_t)b * C + ch) * st.n + n0 + pt] = s_tile[ch * TS + pt];
+    }
+}
+
+__global__ __launch_bounds__(256) void contrast_stages_backward_kernel(const ContrastStages S, float temperature)
+{
+    extern __shared__ float s_tile[];
+    int blk = blockIdx.x;
+    const AmcContrastStage &st = S.st[contrast_stage_of_block(S, blk)];
+    device_with_lpr(st.C, [&](auto lpr) {
+        constexpr int LPR = decltype(lpr)::value;
+        contrast_mutual_tile_cm<LPR, grad_tile_points<LPR>()>(s_tile, st, blk, temperature);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1474,7 +1661,6 @@ AMC_API int amc3d_select_anchors(int m, const float *a, int *sel, size_t sel_int
 
 // Width dispatch.  The unit-row and row-gather kernels are instantiated for C = 4 * LPR in {16, 32, 64, 128, 256}:
 // fn(std::integral_constant<int, LPR>) is called with the constant; false for any other width.
-template <int N> using int_c = std::integral_constant<int, N>;
 
 template <class F>
 static bool with_lpr(int C, F &&fn)
@@ -1730,6 +1916,136 @@ AMC_API int amc3d_contrast_backward_mutual(int m, int C, int k, int nbr_stride, 
     });
     if (!launched) return bad_arg("amc3d_contrast_backward_mutual: no row kernel for this width");
     return launch_status("amc3d_contrast_backward_mutual");
+}
+
+// what the single-stage entries require, of every stage, before anything is launched
+static bool contrast_stages_ok(int nstages, const AmcContrastStage *stages, bool backward)
+{
+    if (nstages < 0 || nstages > AMC_CONTRAST_MAX_STAGES || !stages) return false;
+    for (int s = 0; s < nstages; ++s) {
+        const AmcContrastStage &t = stages[s];
+        if (t.b <= 0 || t.n <= 0 || (long)t.b * t.n > 0x7fffffffL || !amc3d_contrast_backward_csr_supported(t.C) || t.k <= 0 ||
+            t.nbr_stride < t.k || (long)t.b * t.n * t.C >= (1L << 34) || !t.nbr || !t.posmask || !t.a || !t.norm || !t.unit ||
+            !t.stats || !t.mean_cnt || (((uintptr_t)t.unit) & 15))
+            return false;
+        if (backward ? (!t.mutual || !t.rev || !t.grad_cm) : (!t.f_cm || !t.sel || !t.loss_pt || (((uintptr_t)t.f_cm) & 15)))
+            return false;
+    }
+    return true;
+}
+
+// The kernel argument of one launch: blocks(stage) blocks per stage, one after the other.  False where the grid leaves 31 bits.
+// fewest_first: the stages with the fewest blocks lead the grid (the order of S.st is the kernel's own business) -- in the
+// gather a short, wide stage is a few hundred workgroups whose waves each walk several rows one after the other; at the end
+// of the grid that chain would run alone, at its head it runs beside the bulk of the fine stages.
+template <class F>
+static bool contrast_stages_grid(ContrastStages &S, F &&blocks, bool fewest_first = false)
+{
+    long count[AMC_CONTRAST_MAX_STAGES];
+    for (int s = 0; s < S.nstages; ++s) count[s] = blocks(S.st[s]);
+    if (fewest_first)
+        for (int s = 1; s < S.nstages; ++s)  // (insertion sort, stable)
+            for (int t = s; t > 0 && count[t] < count[t - 1]; --t) {
+                std::swap(count[t], count[t - 1]);
+                std::swap(S.st[t], S.st[t - 1]);
+            }
+    long total = 0;
+    for (int s = 0; s < S.nstages; ++s) {
+        S.first[s] = (int)total;
+        total += count[s];
+        if (total > 0x7fffffffL) return false;
+    }
+    for (int s = S.nstages; s <= AMC_CONTRAST_MAX_STAGES; ++s) S.first[s] = (int)total;
+    return true;
+}
+
+// (tile points of the width C, as the kernels' switch chooses them) -> blocks and LDS bytes of a tiled stage
+template <class TileOf>
+static void contrast_stage_tiles(const AmcContrastStage &t, TileOf &&tile_of, long &blocks, size_t &lds)
+{
+    with_lpr(t.C, [&](auto lpr) {
+        const int TP = tile_of(lpr);
+        blocks = (long)t.b * div_up(t.n, TP);
+        lds = (size_t)t.C * (TP + 1) * sizeof(float);
+    });
+}
+
+static ContrastStages contrast_stages_arg(int nstages, const AmcContrastStage *stages)
+{
+    ContrastStages S{};
+    S.nstages = nstages;
+    for (int s = 0; s < nstages; ++s) S.st[s] = stages[s];
+    return S;
+}
+
+AMC_API int amc3d_contrast_stages_forward_cm(int nstages, const AmcContrastStage *stages, float mu, float nu, float temperature,
+                                             float scale, float *total, void *stream_)
+{
+    if (nstages == 0) return 0;
+    if (!contrast_stages_ok(nstages, stages, false) || !total)
+        return bad_arg("amc3d_contrast_stages_forward_cm: bad argument (1..8 stages; C must be 16, 32, 64, 128 or 256; f_cm and unit 16-byte aligned)");
+    hipStream_t stream = (hipStream_t)stream_;
+    ContrastStages tiles = contrast_stages_arg(nstages, stages), waves = tiles;
+    size_t lds = 0;
+    auto unit_blocks = [&](const AmcContrastStage &t) {
+        long blocks = 0;
+        size_t bytes = 0;
+        contrast_stage_tiles(t, [](auto lpr) { return unit_tile_points<decltype(lpr)::value>(); }, blocks, bytes);
+        lds = bytes > lds ? bytes : lds;
+        return blocks;
+    };
+    if (!contrast_stages_grid(tiles, unit_blocks) ||
+        !contrast_stages_grid(waves, [](const AmcContrastStage &t) { return (long)div_up((long)t.b * t.n, 4); }))
+        return bad_arg("amc3d_contrast_stages_forward_cm: the stages' blocks do not fit one grid");
+    hipLaunchKernelGGL(contrast_stages_unit_kernel, dim3(tiles.first[nstages]), dim3(256), lds, stream, tiles);
+    hipLaunchKernelGGL(contrast_stages_forward_kernel, dim3(waves.first[nstages]), dim3(256), 0, stream, waves, mu, nu, temperature);
+    hipLaunchKernelGGL(contrast_stages_mean_kernel, dim3(1), dim3(1024), 0, stream, waves, scale, total);
+    return launch_status("amc3d_contrast_stages_forward_cm");
+}
+
+// the records of stage s start at rec_offset(s) bytes of the workspace (64-byte steps)
+static size_t contrast_stages_rec_bytes(const AmcContrastStage &t) { return ((size_t)t.b * t.n * sizeof(ContrastRecord) + 63) / 64 * 64; }
+
+AMC_API size_t amc3d_contrast_stages_backward_cm_workspace_bytes(int nstages, const AmcContrastStage *stages)
+{
+    size_t bytes = 64;
+    if (nstages < 0 || nstages > AMC_CONTRAST_MAX_STAGES || !stages) return bytes;
+    for (int s = 0; s < nstages; ++s)
+        if (stages[s].b > 0 && stages[s].n > 0) bytes += contrast_stages_rec_bytes(stages[s]);
+    return bytes;
+}
+
+AMC_API int amc3d_contrast_stages_backward_cm(int nstages, const AmcContrastStage *stages, float mu, float nu, float temperature,
+                                              float scale, const float *grad_out, void *workspace, size_t workspace_bytes,
+                                              void *stream_)
+{
+    if (nstages == 0) return 0;
+    if (!contrast_stages_ok(nstages, stages, true) || !grad_out || !workspace || (((uintptr_t)workspace) & 15) ||
+        workspace_bytes < amc3d_contrast_stages_backward_cm_workspace_bytes(nstages, stages))
+        return bad_arg("amc3d_contrast_stages_backward_cm: bad argument (1..8 stages; C must be 16, 32, 64, 128 or 256; unit and workspace 16-byte aligned)");
+    hipStream_t stream = (hipStream_t)stream_;
+    ContrastStages anchors = contrast_stages_arg(nstages, stages);
+    size_t at = 0;
+    for (int s = 0; s < nstages; ++s) {
+        anchors.st[s].rec = (char *)workspace + at;
+        at += contrast_stages_rec_bytes(anchors.st[s]);
+    }
+    ContrastStages tiles = anchors;
+    size_t lds = 0;
+    auto grad_blocks = [&](const AmcContrastStage &t) {
+        long blocks = 0;
+        size_t bytes = 0;
+        contrast_stage_tiles(t, [](auto lpr) { return grad_tile_points<decltype(lpr)::value>(); }, blocks, bytes);
+        lds = bytes > lds ? bytes : lds;
+        return blocks;
+    };
+    if (!contrast_stages_grid(anchors, [](const AmcContrastStage &t) { return (long)div_up((long)t.b * t.n, 256); }) ||
+        !contrast_stages_grid(tiles, grad_blocks, true))
+        return bad_arg("amc3d_contrast_stages_backward_cm: the stages' blocks do not fit one grid");
+    hipLaunchKernelGGL(contrast_stages_record_kernel, dim3(anchors.first[nstages]), dim3(256), 0, stream, anchors, mu, nu, temperature,
+                       scale, grad_out);
+    hipLaunchKernelGGL(contrast_stages_backward_kernel, dim3(tiles.first[nstages]), dim3(256), lds, stream, tiles, temperature);
+    return launch_status("amc3d_contrast_stages_backward_cm");
 }
 
 // ---------------------------------------------------------------------------------------------

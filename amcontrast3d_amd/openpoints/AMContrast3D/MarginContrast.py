@@ -10,7 +10,8 @@ The similarity / loss pair the configs reach is implemented (dist_cos + contrast
 cfgs/*/AMContrast3D-AA.yaml:6-30), with every value of the knobs contrast_softnn_margin reads from
 ambiguity_args: margin constant / adaptive / learned, db -m / +m / none, supervisedCL Method1 / Method2,
 temperature a number or null.  The shipped combination (adaptive, -m, Method1, a temperature) runs on the
-fused stage kernels (ops.contrast_stage, ops.contrast_stage_cm), every other one on ops.contrast_stage_variant;
+fused stage kernels (ops.contrast_stages_cm: every stage that holds a channel-major embedding of a row-kernel width, in
+one call; ops.contrast_stage_cm / ops.contrast_stage for a stage on its own), every other one on ops.contrast_stage_variant;
 on CPU tensors the torch composition below evaluates them.  The reference's other similarity and loss
 functions (contrast_softnn_temperature, ...) are unreachable from its configs and not carried over.
 """
@@ -107,6 +108,7 @@ class ContrastHead(nn.Module):
         self.contrast_func = self.contrast_softnn_margin
         self.posmask_func = self.posmask_cnt
         self.main_contrast = self.point_contrast_margin
+        self._forward_plans = None  # stage -> plan while forward() runs
 
     def dist_cos(self, features, neighbor_feature):
         """(m,C), (m,k,C) -> cosine similarity (m,k)"""
@@ -159,21 +161,38 @@ class ContrastHead(nn.Module):
             return [plan_stage(ambiguity_args.stages, i, stageACE_list, target.flatten(), self.nstride, num_classes,
                                ignore_index, ambiguity_args, self.ftype) for i in range(ambiguity_args.stages_num)]
 
-    def point_contrast_margin(self, n, i, stageACE_list, target, num_classes, ignore_index, ambiguity_args):
+    def _plan_once(self, n, i, stageACE_list, target, num_classes, ignore_index, ambiguity_args):
+        """the plan of stage i; inside forward() a stage is planned once, whoever asks first"""
+        plans = getattr(self, "_forward_plans", None)
+        if plans is not None and i in plans:
+            return plans[i]
+        g = _stage_plan(n, i, stageACE_list, target, self.nstride, num_classes, ignore_index, ambiguity_args, self.ftype)
+        if plans is not None:
+            plans[i] = g
+        return g
+
+    def _stage_channel_major(self, n, i, stageACE_list, target, num_classes, ignore_index, ambiguity_args):
+        """-> (plan of stage i, default form?, its channel-major embedding where the fused channel-major route takes the
+        stage, else None)"""
         from amcontrast3d_amd import ops
-        g = _stage_plan(n, i, stageACE_list, target, self.nstride, num_classes, ignore_index, ambiguity_args,
-                        self.ftype)
-        neighbor_idx, posmask, ambiguity_soft = g['neighbor_idx'], g['posmask'], g['ambiguity']
-        target_ai = ambiguity_soft
-        output_ai = stageACE_list['ambiguity'][i].flatten() if 'ambiguity' in stageACE_list.keys() else None
+        g = self._plan_once(n, i, stageACE_list, target, num_classes, ignore_index, ambiguity_args)
         fused = (ambiguity_args.margin == 'adaptive' and ambiguity_args.db == '-m'
                  and ambiguity_args.supervisedCL == 'Method1' and ambiguity_args.temperature is not None)
         # the decoder's channel-major embedding, where the stage entry still holds it: the fused stage reads it as it is and
         # the (B*n, C) copy of pointnext_AA.py:518-519 is not made
         stage = stageACE_list[n][i]
         f_cm = stage.channel_major() if fused and hasattr(stage, 'channel_major') else None
-        if (f_cm is not None
-                and ops.contrast_stage_supported_cm(f_cm, g.get('anchors'), g.get('rev'), g.get('mutual'))):
+        if f_cm is not None and not ops.contrast_stage_supported_cm(f_cm, g.get('anchors'), g.get('rev'), g.get('mutual')):
+            f_cm = None
+        return g, fused, f_cm
+
+    def point_contrast_margin(self, n, i, stageACE_list, target, num_classes, ignore_index, ambiguity_args):
+        from amcontrast3d_amd import ops
+        g, fused, f_cm = self._stage_channel_major(n, i, stageACE_list, target, num_classes, ignore_index, ambiguity_args)
+        neighbor_idx, posmask, ambiguity_soft = g['neighbor_idx'], g['posmask'], g['ambiguity']
+        target_ai = ambiguity_soft
+        output_ai = stageACE_list['ambiguity'][i].flatten() if 'ambiguity' in stageACE_list.keys() else None
+        if f_cm is not None:
             loss = ops.contrast_stage_cm(f_cm, neighbor_idx, posmask, ambiguity_soft, ambiguity_args.mu, ambiguity_args.nu,
                                          ambiguity_args.temperature, g['anchors'], g['rev'], g['mutual'])
             return loss, output_ai, target_ai
@@ -205,12 +224,47 @@ class ContrastHead(nn.Module):
         loss = self.contrast_func(dist, posmask[keep], ambiguity_soft[keep], ambiguity_args)
         return torch.mean(loss), output_ai, target_ai
 
-    def forward(self, output, target, stageACE_list, num_classes, ignore_index, ambiguity_args):
+    def _merged_stages(self, target, stageACE_list, num_classes, ignore_index, ambiguity_args):
+        """The longest prefix of the stages that the fused channel-major route takes, as (plan, f_cm) pairs: one call of
+        ops.contrast_stages_cm evaluates them all."""
+        from amcontrast3d_amd import _lib
+        merged = []
+        if self.main_contrast != self.point_contrast_margin:
+            return merged
+        for i in range(min(ambiguity_args.stages_num, _lib.CONTRAST_MAX_STAGES)):
+            g, _, f_cm = self._stage_channel_major(ambiguity_args.stages, i, stageACE_list, target, num_classes, ignore_index,
+                                                   ambiguity_args)
+            if f_cm is None:
+                break
+            merged.append((g, f_cm))
+        return merged
+
+    def forward(self, output, target, stageACE_list, num_classes, ignore_index, ambiguity_args, scale=None):
+        """-> (sum of the stage losses, the ambiguities concatenated, the ambiguities per stage).  scale: the loss weight; with
+        it the first result is scale * sum (where one call takes every stage, the kernels form that product)."""
+        self._forward_plans = {}
+        try:
+            return self._forward(target, stageACE_list, num_classes, ignore_index, ambiguity_args, scale)
+        finally:
+            self._forward_plans = None
+
+    def _forward(self, target, stageACE_list, num_classes, ignore_index, ambiguity_args, scale):
         loss_sum = 0
         target_ai_list = []
-        for i in range(ambiguity_args.stages_num):
+        merged = self._merged_stages(target, stageACE_list, num_classes, ignore_index, ambiguity_args)
+        whole = len(merged) == ambiguity_args.stages_num
+        if merged:
+            from amcontrast3d_amd import ops
+            # the kernel's additions are these in this order: ((l0 + l1) + l2) + ..., and the stages after the prefix go on
+            loss_sum, _ = ops.contrast_stages_cm(
+                [(f_cm, g['neighbor_idx'], g['posmask'], g['ambiguity'], g['anchors'], g['rev'], g['mutual']) for g, f_cm in merged],
+                ambiguity_args.mu, ambiguity_args.nu, ambiguity_args.temperature, scale if whole and scale is not None else 1.0)
+            target_ai_list = [g['ambiguity'] for g, _ in merged]
+        for i in range(len(merged), ambiguity_args.stages_num):
             loss, _, target_ai = self.main_contrast(ambiguity_args.stages, i, stageACE_list, target, num_classes,
                                                     ignore_index, ambiguity_args)
-            loss_sum += loss
+            loss_sum = loss_sum + loss
             target_ai_list.append(target_ai)
+        if scale is not None and not (merged and whole):
+            loss_sum = scale * loss_sum
         return loss_sum, torch.cat(target_ai_list), target_ai_list

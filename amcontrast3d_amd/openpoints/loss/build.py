@@ -78,8 +78,10 @@ class CrossEntropyAce(torch.nn.Module):
 
     def forward(self, logit, target, stageACE_list, num_classes, ignore_index, ambiguity_args):
         ce, target = _cross_entropy(self.creterion, logit, target)
-        contrast, _, _ = self.contrast_head(logit, target, stageACE_list, num_classes, ignore_index, ambiguity_args)
-        return ambiguity_args.w1 * ce + ambiguity_args.w2 * contrast
+        # (w2 * contrast: the head applies the weight, in the loss kernels where one call takes every stage)
+        contrast, _, _ = self.contrast_head(logit, target, stageACE_list, num_classes, ignore_index, ambiguity_args,
+                                            scale=ambiguity_args.w2)
+        return ambiguity_args.w1 * ce + contrast
 
 
 @LOSS.register_module()
@@ -99,11 +101,10 @@ class CrossEntropyAcePre(torch.nn.Module):
     def forward(self, logit, target, stageACE_list, num_classes, ignore_index, ambiguity_args):
         ce, target = _cross_entropy(self.creterion, logit, target)
         contrast, target_ai, _ = self.contrast_head(logit, target, stageACE_list, num_classes, ignore_index,
-                                                    ambiguity_args)
+                                                    ambiguity_args, scale=ambiguity_args.w2)  # = w2 * contrast
         logits_ai = torch.cat(stageACE_list['ambiguity']).flatten()
         regression = _l1_mean(self.MAE, logits_ai, target_ai)
         ce = ambiguity_args.w1 * ce
-        contrast = ambiguity_args.w2 * contrast
         regression = ambiguity_args.w3 * regression
         return ce + contrast, ce, contrast, regression
 

@@ -934,6 +934,98 @@ def contrast_stage_supported_cm(f_cm, anchors, rev, mutual):
 
 contrast_stage_cm = ContrastStageChannelMajor.apply
 
+_STAGE_TENSORS = 7  # per stage: f_cm, neighbor_idx, posmask, a, anchors, rev, mutual
+
+
+def _contrast_stage_descs(stages):
+    """-> the AmcContrastStage array of include/amc3d.h over `stages`, dicts of sizes (ints) and tensors (pointers)"""
+    descs = (_lib.ContrastStageDesc * len(stages))()
+    for d, st in zip(descs, stages):
+        for name, v in st.items():
+            setattr(d, name, _ptr(v) if torch.is_tensor(v) else v)
+    return descs
+
+
+class ContrastStagesChannelMajor(Function):
+    """Every stage of the loss in one call: what contrast_stage_cm computes per stage, their sum in the order of
+    ContrastHead.forward and the loss weight, in three launches forward and two backward for ALL stages
+    (amc3d_contrast_stages_forward_cm / _backward_cm).  apply(mu, nu, temperature, scale, f_cm_0, neighbor_idx_0, posmask_0,
+    a_0, anchors_0, rev_0, mutual_0, f_cm_1, ...) -> (total, means): total = scale * (((l_0 + l_1) + l_2) + ...) rounded as the
+    per-stage route rounds it, means (stages, 2) = each stage's {loss, number of selected anchors}, without a gradient.
+    The backward writes each stage's gradient channel-major, (B, C, n), straight from the gather: no row-major gradient, no
+    transpose.  Every stage must satisfy contrast_stage_supported_cm()."""
+
+    @staticmethod
+    def forward(ctx, mu, nu, temperature, scale, *tensors):
+        assert tensors and len(tensors) % _STAGE_TENSORS == 0
+        lib, dev = _lib.load(), tensors[0].device
+        nst = len(tensors) // _STAGE_TENSORS
+        if nst > _lib.CONTRAST_MAX_STAGES:
+            raise ValueError(f"contrast_stages_cm: at most {_lib.CONTRAST_MAX_STAGES} stages per call (got {nst})")
+        means = torch.empty(nst, 2, dtype=torch.float32, device=dev)
+        total = torch.empty((), dtype=torch.float32, device=dev)
+        stages, keep, nbytes, moved = [], [], 0, 0
+        for s in range(nst):
+            f_cm, neighbor_idx, posmask, a, anchors, rev, mutual = tensors[s * _STAGE_TENSORS:(s + 1) * _STAGE_TENSORS]
+            assert anchors is not None and rev is not None and mutual is not None and f_cm.dim() == 3 and f_cm.device == dev
+            f_cm = f_cm.contiguous()
+            B, C, n = f_cm.shape
+            m = B * n
+            nptr, k, stride, nbr = _contrast_inputs(f_cm, m, neighbor_idx, posmask, a, anchors, rev, mutual, "f_cm")
+            norm, unit, stats, loss_pt, _ = _contrast_buffers(m, C, k, dev, True, False)
+            stages.append(dict(b=B, C=C, n=n, k=k, nbr_stride=stride, f_cm=f_cm, nbr=nptr, posmask=posmask, a=a, sel=anchors,
+                               mutual=mutual, rev=rev, norm=norm, unit=unit, stats=stats, loss_pt=loss_pt, mean_cnt=means[s]))
+            keep += [nbr, posmask, a, rev, mutual, norm, unit, stats]
+            nbytes += m * C * 4 + m * k * 5 + m * 20
+            moved += m * C * 4 * (2 + k) + m * k * 5 + m * 20
+        with torch.cuda.device(dev), timing.span("contrast_forward", nbytes, moved=moved):
+            _lib.check(lib.amc3d_contrast_stages_forward_cm(nst, _contrast_stage_descs(stages), float(mu), float(nu),
+                                                            float(temperature), float(scale), _ptr(total), _stream(total)),
+                       "contrast_stages_forward_cm")
+        timing.note("contrast_forward", nst - 1)  # (count_calls: one per stage)
+        timing.note("contrast_stages_forward")
+        ctx.save_for_backward(means, *keep)
+        ctx.args = (float(mu), float(nu), float(temperature), float(scale),
+                    [{key: st[key] for key in ("b", "C", "n", "k", "nbr_stride")} for st in stages])
+        ctx.mark_non_differentiable(means)
+        ctx.set_materialize_grads(False)
+        return total, means
+
+    @staticmethod
+    def backward(ctx, grad_total, _grad_means):
+        mu, nu, temperature, scale, sizes = ctx.args
+        nst = len(sizes)
+        if grad_total is None:
+            return (None,) * (4 + nst * _STAGE_TENSORS)
+        means, saved = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        lib, dev = _lib.load(), means.device
+        g = _contrast_grad_out(grad_total)
+        stages, grads, nbytes, moved = [], [], 0, 0
+        for s, sz in enumerate(sizes):
+            nbr, posmask, a, rev, mutual, norm, unit, stats = saved[s * 8:(s + 1) * 8]
+            m, C, k = sz["b"] * sz["n"], sz["C"], sz["k"]
+            grad_cm = torch.empty(sz["b"], C, sz["n"], dtype=torch.float32, device=dev)  # every element is written
+            stages.append(dict(sz, nbr=nbr, posmask=posmask, a=a, mutual=mutual, rev=rev, norm=norm, unit=unit, stats=stats,
+                               mean_cnt=means[s], grad_cm=grad_cm))
+            grads += [grad_cm] + [None] * (_STAGE_TENSORS - 1)
+            nbytes += m * C * 8 + m * k * 10 + m * 8
+            moved += m * C * 4 * (2 + k) + m * k * 42 + m * 40
+        descs = _contrast_stage_descs(stages)
+        wb = int(lib.amc3d_contrast_stages_backward_cm_workspace_bytes(nst, descs))
+        work = torch.empty(wb, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev), timing.span("contrast_backward", nbytes, moved=moved):
+            _lib.check(lib.amc3d_contrast_stages_backward_cm(nst, descs, mu, nu, temperature, scale, _ptr(g), _ptr(work), wb,
+                                                             _stream(means)), "contrast_stages_backward_cm")
+        timing.note("contrast_backward", nst - 1)
+        timing.note("contrast_stages_backward")
+        return (None,) * 4 + tuple(grads)
+
+
+def contrast_stages_cm(stages, mu, nu, temperature, scale=1.0):
+    """stages: one (f_cm, neighbor_idx, posmask, a, anchors, rev, mutual) per stage -> (total, means) of
+    ContrastStagesChannelMajor"""
+    return ContrastStagesChannelMajor.apply(mu, nu, temperature, scale, *(t for st in stages for t in st))
+
 
 # ----------------------------------------------------------------------------------------------
 # training-mode BatchNorm fused with ReLU / neighbourhood max-pool (csrc/bn.hip)

@@ -49,10 +49,11 @@ def enabled():
     return _enabled
 
 
-def note(name):
-    """count a dispatch that is not a C-ABI launch of its own (e.g. a library GEMM) while count_calls() is active"""
+def note(name, n=1):
+    """count a dispatch that is not a C-ABI launch of its own (e.g. a library GEMM) while count_calls() is active; n: an entry
+    point that evaluates several stages in one launch sequence counts one per stage under the per-stage operator's name"""
     if calls is not None:
-        calls[name] += 1
+        calls[name] += n
 
 
 class span:

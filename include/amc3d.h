@@ -280,6 +280,40 @@ int amc3d_contrast_backward_mutual(int m, int C, int k, int nbr_stride, const fl
                                    const float *mean_cnt, const float *grad_out, void *workspace, size_t workspace_bytes,
                                    float *grad_f, void *stream);
 
+/* All stages of the loss in one call, on channel-major embeddings: what amc3d_contrast_forward_cm (with stats, without sim) and
+ * amc3d_contrast_backward_mutual compute per stage, in three launches forward (unit rows, the anchors' losses, one workgroup
+ * of means) and two backward (records, gather) for ALL stages, with the gradient stored channel-major.  A stage:
+ *   sizes    b clouds of n points (m = b * n anchors, cloud-major), C in {16, 32, 64, 128, 256}, k <= nbr_stride
+ *   inputs   f_cm (b, C, n); nbr, posmask, a, sel, mutual, rev as the single-stage entries take them
+ *   buffers  norm (m), unit (m, C), stats (m, 2), loss_pt (m), mean_cnt (2) written by the forward and read by the backward;
+ *            grad_cm (b, C, n), every element written by the backward; rec is the library's (it points the backward's
+ *            records into `workspace`; what the caller puts there is not read)
+ * f_cm and unit 16-byte aligned, m * C < 2^34.  A stage that fails a check makes the call return an error before anything is
+ * launched; nstages == 0 does nothing, more than AMC_CONTRAST_MAX_STAGES is an error.
+ * forward:  every mean_cnt as amc3d_contrast_forward_cm writes it, and total[0] = scale * (((l_0 + l_1) + l_2) + ...), l_s the
+ *           stage losses, each operation rounded to fp32 (the caller's additions and its loss weight).
+ * backward: grad_cm_s = (grad_out[0] * scale) * d l_s / d f_cm_s; grad_out a device scalar.  A gradient element has the bits
+ *           amc3d_contrast_backward_mutual leaves in the row-major gradient. */
+#define AMC_CONTRAST_MAX_STAGES 8
+typedef struct AmcContrastStage {
+    int b, C, n, k, nbr_stride;
+    const float *f_cm;
+    const int *nbr;
+    const unsigned char *posmask;
+    const float *a;
+    const int *sel;
+    const unsigned char *mutual;
+    const int *rev;
+    float *norm, *unit, *stats, *loss_pt, *mean_cnt;
+    void *rec;
+    float *grad_cm;
+} AmcContrastStage;
+int amc3d_contrast_stages_forward_cm(int nstages, const AmcContrastStage *stages, float mu, float nu, float temperature,
+                                     float scale, float *total, void *stream);
+size_t amc3d_contrast_stages_backward_cm_workspace_bytes(int nstages, const AmcContrastStage *stages);
+int amc3d_contrast_stages_backward_cm(int nstages, const AmcContrastStage *stages, float mu, float nu, float temperature,
+                                      float scale, const float *grad_out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* The other forms of the loss, openpoints/AMContrast3D/MarginContrast.py:117-174 as a whole (what the ambiguity_args knobs
  * margin / db / supervisedCL / temperature select) on the stage of :250-257; the entry points above are the one form the
  * shipped configs use.  A form is four integers, passed at run time:

@@ -1,7 +1,9 @@
 """contrast_stage forward / backward on the loss stages of one synthetic S3DIS-like batch (8 x 24000), per stage, HIP-event
 times; AMC3D_LIB selects another build of the library with the same C ABI (an A/B against a parent commit's).
 
-    python tools/contrast_bench.py                               the default (fused) stage
+    python tools/contrast_bench.py                               the default (fused) stage, then all four stages of the batch on
+        channel-major embeddings: ops.contrast_stage_cm per stage with the head's additions and the loss weight (the route one
+        call replaces, glue included), and ops.contrast_stages_cm, the one call
     python tools/contrast_bench.py --form constant,-m,Method1,0.3   another form of the loss (margin,db,method,T; T may be None):
         ops.contrast_stage_variant with reverse lists (gather), without (float atomics), the torch composition of
         ContrastHead.point_contrast_margin's CPU branch run on the device (with its peak memory), and the default stage for scale
@@ -37,15 +39,18 @@ torch.manual_seed(0)
 
 
 def timed(f, fwd):
-    """-> (forward ms, backward ms): medians over opt.repeats after opt.warmup untimed passes"""
+    """-> (forward ms, backward ms): medians over opt.repeats after opt.warmup untimed passes; f: the leaf or leaves"""
+    leaves = f if isinstance(f, (list, tuple)) else [f]
     for _ in range(opt.warmup):
-        f.grad = None
+        for x in leaves:
+            x.grad = None
         fwd().backward()
     torch.cuda.synchronize()
     e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
     tf, tb = [], []
     for _ in range(opt.repeats):
-        f.grad = None
+        for x in leaves:
+            x.grad = None
         e[0].record(); l = fwd(); e[1].record(); l.backward(); e[2].record(); torch.cuda.synchronize()
         tf.append(e[0].elapsed_time(e[1])); tb.append(e[1].elapsed_time(e[2]))
     return sorted(tf)[len(tf) // 2], sorted(tb)[len(tb) // 2]
@@ -87,3 +92,50 @@ for i, (g, C) in enumerate(zip(plan["loss"], (32, 64, 128, 256))):
     tf, tb = timed(f, fwd_t)
     peak = (torch.cuda.max_memory_allocated() - base) / 1e6
     print(f"form {opt.form} stage {i}: m={m} C={C} selected={sel}  torch-composition  fwd {tf*1e3:.0f} us  bwd {tb*1e3:.0f} us  total {(tf+tb)*1e3:.0f} us  peak +{peak:.0f} MB")
+
+if form is None:
+    widths = (32, 64, 128, 256)
+    fs = [torch.randn(8, C, g["neighbor_idx"].shape[0] // 8, device=dev, requires_grad=True) for g, C in zip(plan["loss"], widths)]
+    plans = [(g["neighbor_idx"], g["posmask"], g["ambiguity"], g["anchors"], g["rev"], g["mutual"]) for g in plan["loss"]]
+
+    def fwd_loop():
+        loss_sum = 0
+        for f, (nidx, posmask, a, anchors, rev, mutual) in zip(fs, plans):
+            loss_sum += ops.contrast_stage_cm(f, nidx, posmask, a, aa.mu, aa.nu, aa.temperature, anchors, rev, mutual)
+        return aa.w2 * loss_sum
+    tf, tb = timed(fs, fwd_loop)
+    print(f"four stages, channel-major, one call per stage + additions + weight: fwd {tf*1e3:.0f} us  bwd {tb*1e3:.0f} us  total {(tf+tb)*1e3:.0f} us")
+    if hasattr(ops, "contrast_stages_cm"):
+        def fwd_merged():
+            return ops.contrast_stages_cm([(f, *p) for f, p in zip(fs, plans)], aa.mu, aa.nu, aa.temperature, aa.w2)[0]
+        tf, tb = timed(fs, fwd_merged)
+        print(f"four stages, channel-major, one call (contrast_stages_cm): fwd {tf*1e3:.0f} us  bwd {tb*1e3:.0f} us  total {(tf+tb)*1e3:.0f} us")
+        # the backward entry per width, one stage per call, opt.repeats calls back to back between two events: what a build
+        # with another gradient tile changes (profiles/contrast_stages_tile_sweep.txt)
+        from amcontrast3d_amd import _lib
+        lib, P = _lib.load(), ops._ptr
+        sts = []
+        for f, (nidx, posmask, a, anchors, rev, mutual) in zip(fs, plans):
+            b, C, n = f.shape
+            e = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+            sts.append(dict(b=b, C=C, n=n, k=nidx.shape[1], nbr_stride=nidx.stride(0), f_cm=f.detach(), nbr=nidx, posmask=posmask,
+                            a=a, sel=anchors, mutual=mutual, rev=rev, norm=e(b * n), unit=e(b * n, C), stats=e(b * n, 2),
+                            loss_pt=e(b * n), mean_cnt=e(2), grad_cm=e(b, C, n)))
+        prm = (float(aa.mu), float(aa.nu), float(aa.temperature), float(aa.w2))
+        total, g = torch.empty(1, device=dev), torch.ones(1, device=dev)
+        for group in [[st] for st in sts] + [sts]:
+            descs = ops._contrast_stage_descs(group)
+            wb = int(lib.amc3d_contrast_stages_backward_cm_workspace_bytes(len(group), descs))
+            work = torch.empty(wb, dtype=torch.uint8, device=dev)
+            _lib.check(lib.amc3d_contrast_stages_forward_cm(len(group), descs, *prm, P(total), ops._stream(total)), "forward")
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            for _ in range(2):  # (the second pass is the timed one)
+                ev[0].record()
+                for _ in range(opt.repeats):
+                    _lib.check(lib.amc3d_contrast_stages_backward_cm(len(group), descs, *prm, P(g), P(work), wb, ops._stream(total)),
+                               "backward")
+                ev[1].record(); torch.cuda.synchronize()
+            what = f"C={group[0]['C']} n={group[0]['n']}" if len(group) == 1 else "the four stages in one call"
+            print(f"backward entry alone, {what}: {ev[0].elapsed_time(ev[1]) / opt.repeats * 1e3:.1f} us per call (records + gather)")
+    else:
+        print("four stages, channel-major, one call (contrast_stages_cm): not in this build")

@@ -9,6 +9,9 @@ of tests/test_gpu_contrast_fp64.py: spatially coherent labels, ambiguities with 
 a negative value).  Graph B: 257 points, k = 33 (the second chunk of every 32-wide loop).  Only what the kernels write is
 hashed: sim, loss_pt and stats are torch.empty and filled for the selected anchors, so they are indexed by the selection
 first.  The float-atomic routes are left out: their sums are unordered by design.
+The `stages` lines are the five widths of a graph as five stages of one loss: by ops.contrast_stages_cm where the build
+has it, otherwise by ops.contrast_stage_cm per stage, the head's additions and the weight as a Python product -- the same
+lines from both, so the two builds' files are compared whole.
 """
 import hashlib
 import os
@@ -87,6 +90,27 @@ def stage_grad(G, f, *plan):
     return loss.detach(), fg.grad
 
 
+def stages(G, widths, scale=0.9):
+    """total, per-stage loss and channel-major gradient of the stages (G, C), C in widths"""
+    fs = [G.features(C).view(G.B, G.m // G.B, C).transpose(1, 2).contiguous().requires_grad_(True) for C in widths]
+    plan = (G.nidx, G.posmask, G.a, G.anchors, G.rev_m, G.mutual)
+    if hasattr(ops, "contrast_stages_cm"):
+        total, means = ops.contrast_stages_cm([(f, *plan) for f in fs], *PRM, scale)
+        losses = [means[i, 0] for i in range(len(fs))]
+    else:
+        loss_sum, losses = 0, []
+        for f in fs:
+            loss = ops.contrast_stage_cm(f, G.nidx, G.posmask, G.a, *PRM, G.anchors, G.rev_m, G.mutual)
+            losses.append(loss.detach().clone())
+            loss_sum += loss
+        total = scale * loss_sum
+    total.backward(torch.tensor(0.7, device=DEV))
+    emit(f"graph={G.name} stages total", total)
+    for C, loss, f in zip(widths, losses, fs):
+        emit(f"graph={G.name} stages C={C} loss", loss)
+        emit(f"graph={G.name} stages C={C} grad_cm", f.grad)
+
+
 def variant(G, f, form, tag, grad=True):
     b = ops.contrast_variant_forward(f, G.nidx, G.posmask, G.a, ops.contrast_form(*form), PRM[0], PRM[1], G.anchors)
     emit(f"{tag} sim", b["sim"][G.keep])
@@ -119,6 +143,8 @@ def main():
             (loss * 0.9).backward()
             emit(f"{tag} cm loss", loss.detach())
             emit(f"{tag} grad_cm", f_cm.grad)
+        stages(G, (16, 32, 64, 128, 256))
+        stages(G, (256, 64))
         for C in (5, 33):  # the general forward kernels
             f = G.features(C)
             emit(f"graph={G.name} C={C} default stage loss", stage_grad(G, f, G.anchors)[0])
