@@ -33,12 +33,20 @@ inline int bad_arg(const char *what)
 
 inline int div_up(long a, long b) { return (int)((a + b - 1) / b); }
 
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }  // workspace sections start on 256-byte boundaries
+
 // The reference's squared distance, evaluated as written (no contraction):
 // (qx-x)*(qx-x) + (qy-y)*(qy-y) + (qz-z)*(qz-z)
 __device__ __forceinline__ float dist2_ref(float qx, float qy, float qz, float x, float y, float z)
 {
     const float dx = __fsub_rn(qx, x), dy = __fsub_rn(qy, y), dz = __fsub_rn(qz, z);
     return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+}
+
+__device__ __forceinline__ double dist2_ref(double qx, double qy, double qz, double x, double y, double z)
+{
+    const double dx = __dsub_rn(qx, x), dy = __dsub_rn(qy, y), dz = __dsub_rn(qz, z);
+    return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
 }
 
 // Zero-fill as an ordinary kernel.  The library never uses hipMemsetAsync: under hipGraph replay a

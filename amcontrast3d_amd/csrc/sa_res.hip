@@ -265,8 +265,6 @@ __global__ __launch_bounds__(256 * KG) void sa_res_bwd_data_kernel(int nb, int c
 // k-groups per tile: none where the K axis is one or two chunks or the tiles already fill the chip
 static int sr_kgroups(int k, long tiles) { return (k <= 2 * SR_KC || tiles >= 1024) ? 1 : (k <= 4 * SR_KC || tiles >= 512) ? 2 : 4; }
 
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace amc
 
 using namespace amc;

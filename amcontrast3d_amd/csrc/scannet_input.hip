@@ -20,7 +20,7 @@
 // Per-room parameter record (ScanNetRoom, 16 doubles):
 //   rot[9] row-major R (pos' = pos @ R), scale[3] (= scale * mirror per axis), contrast (0/1), w_keep = f32(1 - blend),
 //   w_contrast = f32(blend) (NEP 50: numpy rounds the Python-double weights to float32 first), drop (0/1)
-#include "common.h"
+#include "room_common.h"
 
 namespace amc {
 
@@ -46,16 +46,6 @@ __device__ __forceinline__ float contrast_drop(float x, float lo, float hi, cons
         x = __fadd_rn(__fmul_rn((float)p.w_keep, x), __fmul_rn((float)p.w_contrast, __fmul_rn(__fsub_rn(x, lo), sc)));
     }
     return p.drop != 0.0 ? 0.f : x;
-}
-
-__device__ __forceinline__ int room_of(int b, const long long *__restrict__ off, long long i)
-{
-    int lo = 0, hi = b - 1;  // the last room whose first point is <= i
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
 }
 
 // pass 1: per (room, workgroup) partial min / max of the input colours -> part[(b * kStatBlocks + blk) * 6 + {lo0..2, hi0..2}]
@@ -147,7 +137,7 @@ __global__ __launch_bounds__(256) void scannet_transform_kernel(int b, long long
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
-    const int r = room_of(b, off, i);
+    const int r = room_seg<long long>(b, off, i);
     const ScanNetRoom &p = par[r];
     const double p0 = (double)coord[i * 3], p1 = (double)coord[i * 3 + 1], p2 = (double)coord[i * 3 + 2];
 #pragma unroll
@@ -181,29 +171,15 @@ __global__ __launch_bounds__(1024) void scannet_crop_tail_kernel(int n, int g, c
 {
     __shared__ double s_mn[16][3];
     __shared__ double s_corner[3];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // crop_pc's last `coord -= coord.min(0)` (data_util.py:173): the min corner of the cropped cloud, in double (the
     // shuffle does not change the set, so the loop runs in crop order)
-    double mn[3] = {1.7e308, 1.7e308, 1.7e308};
+    double mn[3] = {kHuge<double>, kHuge<double>, kHuge<double>};
     for (int k = threadIdx.x; k < n; k += 1024) {
         const int s = tail_src(k, sel, crop, nullptr);
 #pragma unroll
         for (int j = 0; j < 3; ++j) mn[j] = fmin(mn[j], coord[(size_t)s * 3 + j]);
     }
-    for (int d = 32; d >= 1; d >>= 1) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) mn[j] = fmin(mn[j], __shfl_xor(mn[j], d, 64));
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) s_mn[wave][j] = mn[j];
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        double v = s_mn[0][threadIdx.x];
-        for (int w = 1; w < 16; ++w) v = fmin(v, s_mn[w][threadIdx.x]);
-        s_corner[threadIdx.x] = v;
-    }
+    block_min3<double, 1024>(mn, s_mn, s_corner);
     __syncthreads();
     const double c0 = s_corner[0], c1 = s_corner[1], c2 = s_corner[2];
     for (int k = threadIdx.x; k < n; k += 1024) {
@@ -221,8 +197,6 @@ __global__ __launch_bounds__(1024) void scannet_crop_tail_kernel(int n, int g, c
         y_out[k] = y[s];
     }
 }
-
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace amc
 

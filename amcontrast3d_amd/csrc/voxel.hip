@@ -15,7 +15,7 @@
 // floor(coord / voxel), distances ((dx^2 + dy^2) + dz^2) in double, sorted on their 64-bit patterns).
 #include "cub_kernel_memset.h"  // hipCUB with its memsets as kernels (graph-safe)
 
-#include "common.h"
+#include "room_common.h"
 
 namespace amc {
 
@@ -69,32 +69,17 @@ __global__ void voxel_select_kernel(int nvox, const int *__restrict__ start, con
     if (v < nvox) out[v] = idx_sort[start[v] + rnd[v] % count[v]];
 }
 
-__global__ void crop_d2_kernel(int n, const float *__restrict__ coord, int init, float *__restrict__ d2, unsigned *__restrict__ bits,
+// C = float or double: distances in C, their bit patterns (non-negative values order like them) as 32- or 64-bit keys
+template <typename C, typename K>
+__global__ void crop_d2_kernel(int n, const C *__restrict__ coord, int init, C *__restrict__ d2, K *__restrict__ bits,
                                int *__restrict__ iota)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float dx = __fsub_rn(coord[(size_t)i * 3], coord[(size_t)init * 3]);
-    const float dy = __fsub_rn(coord[(size_t)i * 3 + 1], coord[(size_t)init * 3 + 1]);
-    const float dz = __fsub_rn(coord[(size_t)i * 3 + 2], coord[(size_t)init * 3 + 2]);
-    const float d = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+    const size_t p = (size_t)i * 3, q = (size_t)init * 3;
+    const C d = dist2_ref(coord[p], coord[p + 1], coord[p + 2], coord[q], coord[q + 1], coord[q + 2]);
     d2[i] = d;
-    bits[i] = __float_as_uint(d);  // non-negative floats order like their bit patterns
-    iota[i] = i;
-}
-
-// the double version of crop_d2_kernel: float64 distances, their bit patterns (non-negative doubles order like them) as keys
-__global__ void crop_d2_f64_kernel(int n, const double *__restrict__ coord, int init, double *__restrict__ d2,
-                                   unsigned long long *__restrict__ bits, int *__restrict__ iota)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double dx = __dsub_rn(coord[(size_t)i * 3], coord[(size_t)init * 3]);
-    const double dy = __dsub_rn(coord[(size_t)i * 3 + 1], coord[(size_t)init * 3 + 1]);
-    const double dz = __dsub_rn(coord[(size_t)i * 3 + 2], coord[(size_t)init * 3 + 2]);
-    const double d = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
-    d2[i] = d;
-    bits[i] = (unsigned long long)__double_as_longlong(d);
+    bits[i] = order_bits(d);
     iota[i] = i;
 }
 
@@ -103,8 +88,6 @@ __global__ void copy_i32_kernel(int n, const int *__restrict__ src, int *__restr
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = src[i];
 }
-
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 static size_t sort64_temp(int n)
 {
@@ -202,29 +185,6 @@ AMC_API size_t amc3d_crop_nearest_workspace_bytes(int n)
     return 4 * align256((size_t)n * 4) + sort32_temp(n) + 256;  // bits | sorted bits | iota | sorted idx | temp
 }
 
-// crop_pc's nearest-N crop (data_util.py:157-160): d2 (n) = squared distance of every point to coord[init_idx];
-// crop_idx (keep) = the keep nearest points in ascending distance (stable among equal distances)
-AMC_API int amc3d_crop_nearest(int n, const float *coord, int init_idx, int keep, float *d2, int *crop_idx, void *workspace,
-                               size_t workspace_bytes, void *stream_)
-{
-    if (n <= 0 || keep <= 0) return 0;
-    if (!coord || init_idx < 0 || init_idx >= n || keep > n || !d2 || !crop_idx || !workspace ||
-        workspace_bytes < amc3d_crop_nearest_workspace_bytes(n))
-        return bad_arg("amc3d_crop_nearest: bad argument");
-    hipStream_t stream = (hipStream_t)stream_;
-    char *w = (char *)workspace;
-    unsigned *bits = (unsigned *)w; w += align256((size_t)n * 4);
-    unsigned *sbits = (unsigned *)w; w += align256((size_t)n * 4);
-    int *iota = (int *)w; w += align256((size_t)n * 4);
-    int *sidx = (int *)w; w += align256((size_t)n * 4);
-    size_t temp = sort32_temp(n);
-    hipLaunchKernelGGL(crop_d2_kernel, dim3(div_up(n, 256)), dim3(256), 0, stream, n, coord, init_idx, d2, bits, iota);
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(w, temp, (const unsigned *)bits, sbits, (const int *)iota, sidx, n, 0, 32, stream);
-    if (e != hipSuccess) { set_error("amc3d_crop_nearest: radix sort: %s", hipGetErrorString(e)); return (int)e; }
-    hipLaunchKernelGGL(copy_i32_kernel, dim3(div_up(keep, 256)), dim3(256), 0, stream, keep, (const int *)sidx, crop_idx);
-    return launch_status("amc3d_crop_nearest");
-}
-
 AMC_API size_t amc3d_crop_nearest_f64_workspace_bytes(int n)
 {
     if (n <= 0) return 0;
@@ -232,25 +192,45 @@ AMC_API size_t amc3d_crop_nearest_f64_workspace_bytes(int n)
     return 2 * align256((size_t)n * 8) + 2 * align256((size_t)n * 4) + sort64_temp(n) + 256;
 }
 
-// crop_pc's crop on float64 coordinates: d2 (n) double, crop_idx (keep) as amc3d_crop_nearest
-AMC_API int amc3d_crop_nearest_f64(int n, const double *coord, int init_idx, int keep, double *d2, int *crop_idx, void *workspace,
-                                   size_t workspace_bytes, void *stream_)
+// K: the key type, unsigned for float and unsigned long long for double coordinates
+template <typename C, typename K>
+static int crop_nearest_impl(const char *what, int n, const C *coord, int init_idx, int keep, C *d2, int *crop_idx, void *workspace,
+                             size_t workspace_bytes, hipStream_t stream)
 {
     if (n <= 0 || keep <= 0) return 0;
-    if (!coord || init_idx < 0 || init_idx >= n || keep > n || !d2 || !crop_idx || !workspace ||
-        workspace_bytes < amc3d_crop_nearest_f64_workspace_bytes(n))
-        return bad_arg("amc3d_crop_nearest_f64: bad argument");
-    hipStream_t stream = (hipStream_t)stream_;
+    const bool k32 = sizeof(K) == 4;
+    const size_t need = k32 ? amc3d_crop_nearest_workspace_bytes(n) : amc3d_crop_nearest_f64_workspace_bytes(n);
+    size_t temp = k32 ? sort32_temp(n) : sort64_temp(n);
+    if (!coord || init_idx < 0 || init_idx >= n || keep > n || !d2 || !crop_idx || !workspace || workspace_bytes < need) {
+        set_error("%s: bad argument", what);
+        return (int)hipErrorInvalidValue;
+    }
     char *w = (char *)workspace;
-    unsigned long long *bits = (unsigned long long *)w; w += align256((size_t)n * 8);
-    unsigned long long *sbits = (unsigned long long *)w; w += align256((size_t)n * 8);
+    K *bits = (K *)w; w += align256((size_t)n * sizeof(K));
+    K *sbits = (K *)w; w += align256((size_t)n * sizeof(K));
     int *iota = (int *)w; w += align256((size_t)n * 4);
     int *sidx = (int *)w; w += align256((size_t)n * 4);
-    size_t temp = sort64_temp(n);
-    hipLaunchKernelGGL(crop_d2_f64_kernel, dim3(div_up(n, 256)), dim3(256), 0, stream, n, coord, init_idx, d2, bits, iota);
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(w, temp, (const unsigned long long *)bits, sbits, (const int *)iota, sidx, n, 0,
-                                                      64, stream);
-    if (e != hipSuccess) { set_error("amc3d_crop_nearest_f64: radix sort: %s", hipGetErrorString(e)); return (int)e; }
+    hipLaunchKernelGGL((crop_d2_kernel<C, K>), dim3(div_up(n, 256)), dim3(256), 0, stream, n, coord, init_idx, d2, bits, iota);
+    hipError_t e = hipcub::DeviceRadixSort::SortPairs(w, temp, (const K *)bits, sbits, (const int *)iota, sidx, n, 0,
+                                                      8 * (int)sizeof(K), stream);
+    if (e != hipSuccess) { set_error("%s: radix sort: %s", what, hipGetErrorString(e)); return (int)e; }
     hipLaunchKernelGGL(copy_i32_kernel, dim3(div_up(keep, 256)), dim3(256), 0, stream, keep, (const int *)sidx, crop_idx);
-    return launch_status("amc3d_crop_nearest_f64");
+    return launch_status(what);
+}
+
+// crop_pc's nearest-N crop (data_util.py:157-160): d2 (n) = squared distance of every point to coord[init_idx];
+// crop_idx (keep) = the keep nearest points in ascending distance (stable among equal distances)
+AMC_API int amc3d_crop_nearest(int n, const float *coord, int init_idx, int keep, float *d2, int *crop_idx, void *workspace,
+                               size_t workspace_bytes, void *stream)
+{
+    return crop_nearest_impl<float, unsigned>("amc3d_crop_nearest", n, coord, init_idx, keep, d2, crop_idx, workspace, workspace_bytes,
+                                              (hipStream_t)stream);
+}
+
+// crop_pc's crop on float64 coordinates: d2 (n) double, crop_idx (keep) as amc3d_crop_nearest
+AMC_API int amc3d_crop_nearest_f64(int n, const double *coord, int init_idx, int keep, double *d2, int *crop_idx, void *workspace,
+                                   size_t workspace_bytes, void *stream)
+{
+    return crop_nearest_impl<double, unsigned long long>("amc3d_crop_nearest_f64", n, coord, init_idx, keep, d2, crop_idx, workspace,
+                                                         workspace_bytes, (hipStream_t)stream);
 }

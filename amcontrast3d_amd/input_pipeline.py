@@ -14,8 +14,8 @@ numbers the reference drew.  numpy's argsort is not stable, so WHICH point of a 
 (and the order of equidistant points in the crop) is unspecified by the reference itself; the stable order is used here.
 
 Batch-level calls: scannet_train_batch (ScanNet's training item, room by room after the transform), scannet_train_rooms /
-ScanNetTrainFeed (the same item for the whole batch at once on csrc/scannet_rooms.hip, one read-back per batch),
-s3dis_train_batch / S3DISTrainFeed (S3DIS's training item for a whole batch of raw rooms on csrc/s3dis_input.hip, one read-back
+ScanNetTrainFeed (the same item for the whole batch at once on csrc/room_input.hip, one read-back per batch),
+s3dis_train_batch / S3DISTrainFeed (S3DIS's training item for a whole batch of raw rooms on csrc/room_input.hip, one read-back
 per batch), and the validation / whole-room testing items.
 """
 import ctypes
@@ -572,134 +572,180 @@ def _s3dis_augment(t, pos, colour, d):
     return pos_out, x_out, heights
 
 
-def _s3dis_batch(raw, src, sizes, transform, voxel_size, voxel_max, variable, shuffle, generator, draws, gravity_dim):
-    """s3dis_train_batch on rooms that are row ranges [src[b], src[b] + sizes[b]) of one (rows,7) GPU array"""
-    who = "s3dis_train_batch"
-    B, dev, total = len(sizes), raw.device, sum(sizes)
+def _opt(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _check_rooms_args(who, voxel_size, voxel_max, gravity_dim, total, hint=""):
     if voxel_max is None or int(voxel_max) <= 0:
-        raise ValueError(f"{who}: voxel_max is the size of a training cloud (validation goes through s3dis_val_cloud)")
+        raise ValueError(f"{who}: voxel_max is the size of a training cloud{hint}")
     if gravity_dim not in (0, 1, 2) or not float(voxel_size) > 0:
         raise ValueError(f"{who}: gravity_dim is 0, 1 or 2 and voxel_size is positive")
     if total >= 2 ** 31:
         raise ValueError(f"{who}: {total} points in one batch (at most 2^31 - 1)")
-    voxel_max = int(voxel_max)
-    lib = _lib.load()
-    P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    f64 = int(raw.dtype == torch.float64)
-    offsets = [0]
-    for n in sizes:
-        offsets.append(offsets[-1] + n)
-    table = _upload(list(src) + offsets, torch.int64, dev)
-    src_t, off_t = table[:B], table[B:]
-    coord = torch.empty(total, 3, dtype=torch.float32, device=dev)
-    key = torch.empty(total, dtype=torch.int64, device=dev)  # uint64 bit patterns
-    idx_sort = torch.empty(total, dtype=torch.int32, device=dev)
-    start = torch.empty(total + 1, dtype=torch.int32, device=dev)
-    count = torch.empty(total, dtype=torch.int32, device=dev)
-    small = torch.empty(2 * B + 1, dtype=torch.int32, device=dev)
-    vbase, cmax = small[:B + 1], small[B + 1:]
-    corner = torch.empty(B, 3, dtype=torch.float32, device=dev)
-    wb = int(lib.amc3d_s3dis_voxelize_workspace_bytes(B, total))
-    work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.amc3d_s3dis_voxelize_rooms(B, total, f64, P(raw), P(src_t), P(off_t), ctypes.c_double(float(voxel_size)),
-                                                  P(coord), P(key), P(idx_sort), P(start), P(count), P(vbase), P(cmax), P(corner),
-                                                  P(work), wb, stream), "s3dis_voxelize_rooms")
-    vb = vbase.tolist()  # the batch's one read-back: the voxel counts size everything after the voxelisation
-    nv = [vb[b + 1] - vb[b] for b in range(B)]
-    nvt = vb[B]
-    outs = [voxel_max if (n >= voxel_max or not variable) else n for n in nv]
-    n_out = outs[0]
-    if any(n != n_out for n in outs):
-        raise ValueError(f"{who}: the rooms came out with different sizes {outs} (variable=True); the collate stacks them")
-    cropped = [n >= voxel_max for n in nv]
-    padded = [n < n_out for n in nv]
 
-    d = dict(draws or {})
+
+def _pop_per_room(d, B, who):
+    """the per-room lists "rnd", "init_idx", "pad", "perm" taken out of the draws d (an entry or a whole list may be None)"""
     per_room = {}
     for k in ("rnd", "init_idx", "pad", "perm"):
         v = d.pop(k, None)
         per_room[k] = list(v) if v is not None else [None] * B
         if len(per_room[k]) != B:
             raise ValueError(f"{who}: per-room draws need one entry per room")
-    given = lambda v: torch.as_tensor(v).to(dev)  # noqa: E731
-    # voxelize's randint(0, count.max(), nvox)
-    rnd_t = rnd_u = None
-    if any(r is not None for r in per_room["rnd"]):
-        rnd_t = torch.full((nvt,), -1, dtype=torch.int32, device=dev)
-        for b, r in enumerate(per_room["rnd"]):
-            if r is not None:
-                r = given(r)
-                if r.shape != (nv[b],) or r.is_floating_point() or bool((r < 0).any()):
-                    raise ValueError(f"{who}: room {b}: rnd must hold {nv[b]} non-negative draws")
-                rnd_t[vb[b]:vb[b + 1]] = r
+    return per_room
+
+
+class _RoomVoxels:
+    """the voxel tables of a ragged batch of B rooms (csrc/room_input.hip), coordinates of `dtype`: allocated here and filled by
+    amc3d_<which>_voxelize_rooms, whose arguments between the sizes and voxel_size are `source`"""
+
+    def __init__(self, which, dtype, B, total, voxel_size, dev, source):
+        self.which, self.dtype, self.B, self.dev = which, dtype, B, dev
+        self.lib = lib = _lib.load()
+        self.stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        self.coord = torch.empty(total, 3, dtype=dtype, device=dev)
+        key = torch.empty(total, dtype=torch.int64, device=dev)  # uint64 bit patterns
+        self.idx_sort = torch.empty(total, dtype=torch.int32, device=dev)
+        self.start = torch.empty(total + 1, dtype=torch.int32, device=dev)
+        self.count = torch.empty(total, dtype=torch.int32, device=dev)
+        small = torch.empty(2 * B + 1, dtype=torch.int32, device=dev)
+        self.vbase, self.cmax = small[:B + 1], small[B + 1:]
+        corner = torch.empty(B, 3, dtype=dtype, device=dev)
+        wb = int(getattr(lib, f"amc3d_{which}_voxelize_workspace_bytes")(B, total))
+        work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(getattr(lib, f"amc3d_{which}_voxelize_rooms")(
+                B, total, *source, ctypes.c_double(float(voxel_size)), _opt(self.coord), _opt(key), _opt(self.idx_sort),
+                _opt(self.start), _opt(self.count), _opt(self.vbase), _opt(self.cmax), _opt(corner), _opt(work), wb, self.stream),
+                f"{which}_voxelize_rooms")
+
+    def read_back(self, voxel_max, variable, who):
+        """the batch's one read-back: the voxel counts size everything after the voxelisation"""
+        B = self.B
+        self.vb = vb = self.vbase.tolist()
+        self.nv = nv = [vb[b + 1] - vb[b] for b in range(B)]
+        self.nvt = vb[B]
+        outs = [voxel_max if (n >= voxel_max or not variable) else n for n in nv]
+        self.n_out = outs[0]
+        if any(n != self.n_out for n in outs):
+            raise ValueError(f"{who}: the rooms came out with different sizes {outs} (variable=True); the collate stacks them")
+        self.cropped = [n >= voxel_max for n in nv]
+        self.padded = [n < self.n_out for n in nv]
+
+    def nv_column(self):
+        return (self.vbase[1:] - self.vbase[:-1]).view(self.B, 1)
+
+    def given(self, per_room, pad_t, perm_t, shuffle, who):
+        """validates the per-room draws that were passed in and scatters them into the batch's tables -> rnd_t (-1 where the
+        device draws), init_t, pad_t, perm_t.  pad_t / perm_t: what the caller drew for the rooms without given ones, or None"""
+        B, dev, vb, nv, n_out = self.B, self.dev, self.vb, self.nv, self.n_out
+        given = lambda v: torch.as_tensor(v).to(dev)  # noqa: E731
+        rnd_t = init_t = None
+        if any(r is not None for r in per_room["rnd"]):  # voxelize's randint(0, count.max(), nvox)
+            rnd_t = torch.full((self.nvt,), -1, dtype=torch.int32, device=dev)
+            for b, r in enumerate(per_room["rnd"]):
+                if r is not None:
+                    r = given(r)
+                    if r.shape != (nv[b],) or r.is_floating_point() or bool((r < 0).any()):
+                        raise ValueError(f"{who}: room {b}: rnd must hold {nv[b]} non-negative draws")
+                    rnd_t[vb[b]:vb[b + 1]] = r
+        if any(self.cropped):  # crop_pc's randint(N)
+            inits = []
+            for b, v in enumerate(per_room["init_idx"]):
+                v = -1 if (v is None or not self.cropped[b]) else int(v)
+                if per_room["init_idx"][b] is not None and self.cropped[b] and not 0 <= v < nv[b]:
+                    raise ValueError(f"{who}: room {b}: init_idx {v} out of range")
+                inits.append(v)
+            if any(v >= 0 for v in inits):
+                init_t = _upload(inits, torch.int32, dev)
+        if any(self.padded):  # its np.random.choice(N, voxel_max - N)
+            if pad_t is None:
+                pad_t = torch.zeros(B, n_out, dtype=torch.int32, device=dev)
+            for b, v in enumerate(per_room["pad"]):
+                if v is not None and self.padded[b]:
+                    v = given(v)
+                    if v.shape != (n_out - nv[b],) or v.is_floating_point() or bool(((v < 0) | (v >= nv[b])).any()):
+                        raise ValueError(f"{who}: room {b}: pad must hold {n_out - nv[b]} indices below {nv[b]}")
+                    pad_t[b, nv[b]:] = v
+        if shuffle:  # its permutation
+            if perm_t is None:
+                perm_t = torch.empty(B, n_out, dtype=torch.int32, device=dev)
+            for b, v in enumerate(per_room["perm"]):
+                if v is not None:
+                    v = given(v)
+                    if (v.shape != (n_out,) or v.is_floating_point()
+                            or not bool((v.sort().values == torch.arange(n_out, device=dev)).all())):
+                        raise ValueError(f"{who}: room {b}: perm must be a permutation of {n_out}")
+                    perm_t[b] = v
+        return rnd_t, init_t, pad_t, perm_t
+
+    def select_crop(self, voxel_max, rnd_t, rnd_u, init_t, init_u):
+        """one point per voxel and, where a room has voxel_max voxels or more, its crop order -> sel, order (or None)"""
+        dev, nvt, any_crop = self.dev, self.nvt, any(self.cropped)
+        sel = torch.empty(max(nvt, 1), dtype=torch.int32, device=dev)
+        d2 = order = work = None
+        wb = 0
+        if any_crop:
+            d2 = torch.empty(nvt, dtype=self.dtype, device=dev)
+            order = torch.empty(nvt, dtype=torch.int32, device=dev)
+            wb = int(getattr(self.lib, f"amc3d_{self.which}_crop_workspace_bytes")(nvt))
+            work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(getattr(self.lib, f"amc3d_{self.which}_select_crop")(
+                self.B, nvt, voxel_max, int(any_crop), _opt(self.coord), _opt(self.idx_sort), _opt(self.start), _opt(self.count),
+                _opt(self.vbase), _opt(self.cmax), _opt(rnd_t), _opt(rnd_u), _opt(init_t), _opt(init_u), _opt(sel), _opt(d2),
+                _opt(order), _opt(work), wb, self.stream), f"{self.which}_select_crop")
+        return sel, order
+
+
+def _s3dis_batch(raw, src, sizes, transform, voxel_size, voxel_max, variable, shuffle, generator, draws, gravity_dim):
+    """s3dis_train_batch on rooms that are row ranges [src[b], src[b] + sizes[b]) of one (rows,7) GPU array"""
+    who = "s3dis_train_batch"
+    B, dev, total = len(sizes), raw.device, sum(sizes)
+    _check_rooms_args(who, voxel_size, voxel_max, gravity_dim, total, " (validation goes through s3dis_val_cloud)")
+    voxel_max = int(voxel_max)
+    f64 = int(raw.dtype == torch.float64)
+    offsets = [0]
+    for n in sizes:
+        offsets.append(offsets[-1] + n)
+    table = _upload(list(src) + offsets, torch.int64, dev)
+    src_t, off_t = table[:B], table[B:]
+    v = _RoomVoxels("s3dis", torch.float32, B, total, voxel_size, dev, (f64, _opt(raw), _opt(src_t), _opt(off_t)))
+    v.read_back(voxel_max, variable, who)
+    n_out = v.n_out
+
+    d = dict(draws or {})
+    per_room = _pop_per_room(d, B, who)
+    # the device's own draws, at the sizes the voxel counts give: voxelize's randint, crop_pc's randint(N), its
+    # np.random.choice(N, voxel_max - N) and its permutation, in this order
+    rnd_u = init_u = pad_t = perm_t = None
     if any(r is None for r in per_room["rnd"]):
-        rnd_u = torch.rand(nvt, dtype=torch.float64, device=dev, generator=generator)
-    # crop_pc's randint(N)
-    init_t = init_u = None
-    if any(cropped):
-        inits = []
-        for b, v in enumerate(per_room["init_idx"]):
-            v = -1 if (v is None or not cropped[b]) else int(v)
-            if per_room["init_idx"][b] is not None and cropped[b] and not 0 <= v < nv[b]:
-                raise ValueError(f"{who}: room {b}: init_idx {v} out of range")
-            inits.append(v)
-        if any(v >= 0 for v in inits):
-            init_t = _upload(inits, torch.int32, dev)
-        if any(v < 0 and c for v, c in zip(inits, cropped)):
-            init_u = torch.rand(B, dtype=torch.float64, device=dev, generator=generator)
-    # its np.random.choice(N, voxel_max - N) and its permutation
-    pad_t = perm_t = None
-    if any(padded):
-        if any(p and per_room["pad"][b] is None for b, p in enumerate(padded)):
-            nvd = (vbase[1:] - vbase[:-1]).view(B, 1)
-            pad_t = (torch.rand(B, n_out, dtype=torch.float64, device=dev, generator=generator) * nvd).int()
-        else:
-            pad_t = torch.zeros(B, n_out, dtype=torch.int32, device=dev)
-        for b, v in enumerate(per_room["pad"]):
-            if v is not None and padded[b]:
-                v = given(v)
-                if v.shape != (n_out - nv[b],) or v.is_floating_point() or bool(((v < 0) | (v >= nv[b])).any()):
-                    raise ValueError(f"{who}: room {b}: pad must hold {n_out - nv[b]} indices below {nv[b]}")
-                pad_t[b, nv[b]:] = v
-    if shuffle:
-        if any(v is None for v in per_room["perm"]):
-            perm_t = torch.rand(B, n_out, device=dev, generator=generator).argsort(dim=1).int()
-        else:
-            perm_t = torch.empty(B, n_out, dtype=torch.int32, device=dev)
-        for b, v in enumerate(per_room["perm"]):
-            if v is not None:
-                v = given(v)
-                if v.shape != (n_out,) or v.is_floating_point() or not bool((v.sort().values == torch.arange(n_out, device=dev)).all()):
-                    raise ValueError(f"{who}: room {b}: perm must be a permutation of {n_out}")
-                perm_t[b] = v
+        rnd_u = torch.rand(v.nvt, dtype=torch.float64, device=dev, generator=generator)
+    if any(c and i is None for c, i in zip(v.cropped, per_room["init_idx"])):
+        init_u = torch.rand(B, dtype=torch.float64, device=dev, generator=generator)
+    if any(p and per_room["pad"][b] is None for b, p in enumerate(v.padded)):
+        pad_t = (torch.rand(B, n_out, dtype=torch.float64, device=dev, generator=generator) * v.nv_column()).int()
+    if shuffle and any(p is None for p in per_room["perm"]):
+        perm_t = torch.rand(B, n_out, device=dev, generator=generator).argsort(dim=1).int()
+    rnd_t, init_t, pad_t, perm_t = v.given(per_room, pad_t, perm_t, shuffle, who)
     # the transform's draws (S3DISTrainAugment.draw's keys)
     if any(k not in d for k in list(_S3DIS_TRANSFORM_KEYS) + ["noise"]):
-        for k, v in _s3dis_transform_draws(transform, B, n_out, dev, generator).items():
-            d.setdefault(k, v)
+        for k, t in _s3dis_transform_draws(transform, B, n_out, dev, generator).items():
+            d.setdefault(k, t)
     for k, shape in list(_S3DIS_TRANSFORM_KEYS.items()) + [("noise", (n_out, 3))]:
-        d[k] = given(d[k])
+        d[k] = torch.as_tensor(d[k]).to(dev)
         if d[k].shape != (B,) + shape:
             raise ValueError(f"{who}: draws[{k!r}] has shape {tuple(d[k].shape)}, not {(B,) + shape}")
 
-    sel = torch.empty(max(nvt, 1), dtype=torch.int32, device=dev)
-    d2 = order = work2 = None
-    wb2 = 0
-    if any(cropped):
-        d2 = torch.empty(nvt, dtype=torch.float32, device=dev)
-        order = torch.empty(nvt, dtype=torch.int32, device=dev)
-        wb2 = int(lib.amc3d_s3dis_crop_workspace_bytes(nvt))
-        work2 = torch.empty(max(wb2, 8), dtype=torch.uint8, device=dev)
+    sel, order = v.select_crop(voxel_max, rnd_t, rnd_u, init_t, init_u)
     pos0 = torch.empty(B, n_out, 3, dtype=torch.float32, device=dev)
     colour = torch.empty(B, n_out, 3, dtype=torch.float32, device=dev)
     y = torch.empty(B, n_out, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.amc3d_s3dis_select_crop(B, nvt, voxel_max, int(any(cropped)), P(coord), P(idx_sort), P(start), P(count),
-                                               P(vbase), P(cmax), P(rnd_t), P(rnd_u), P(init_t), P(init_u), P(sel), P(d2), P(order),
-                                               P(work2), wb2, stream), "s3dis_select_crop")
-        _lib.check(lib.amc3d_s3dis_crop_tail(B, n_out, voxel_max, f64, P(raw), P(src_t), P(off_t), P(coord), P(vbase), P(sel),
-                                             P(order), P(pad_t), P(perm_t), P(pos0), P(colour), P(y), stream), "s3dis_crop_tail")
+        _lib.check(v.lib.amc3d_s3dis_crop_tail(B, n_out, voxel_max, f64, _opt(raw), _opt(src_t), _opt(off_t), _opt(v.coord),
+                                               _opt(v.vbase), _opt(sel), _opt(order), _opt(pad_t), _opt(perm_t), _opt(pos0),
+                                               _opt(colour), _opt(y), v.stream), "s3dis_crop_tail")
     pos, x, heights = _s3dis_augment(transform, pos0, colour, d)
     if gravity_dim != transform.g:
         heights = pos0[:, :, gravity_dim:gravity_dim + 1].contiguous()
@@ -720,7 +766,7 @@ def _s3dis_rooms(rooms, who):
 def s3dis_train_batch(rooms, transform, voxel_size=0.04, voxel_max=24000, variable=False, shuffle=True, generator=None,
                       draws=None, gravity_dim=2):
     """S3DIS.__getitem__ for training with presample=False (dataset/s3dis/s3dis.py:122-144) plus the default collate, for a
-    batch of raw rooms on the GPU (csrc/s3dis_input.hip): every room cast to float32, xyz -= min, crop_pc (min-corner shift,
+    batch of raw rooms on the GPU (csrc/room_input.hip): every room cast to float32, xyz -= min, crop_pc (min-corner shift,
     voxelize mode 0, the voxel_max representatives nearest to representative init_idx or, with variable=False, padding by
     repetition, shuffle, min-corner shift), then `transform` (augment.S3DISTrainAugment) on the cropped clouds; heights is the
     gravity coordinate of the cropped cloud before the transforms.  Bit for bit what crop_pc per room, torch.stack and
@@ -830,135 +876,55 @@ def _scannet_batch(coord, feat, label, sizes, transform, voxel_size, voxel_max, 
                    who="scannet_train_rooms"):
     """scannet_train_rooms on rooms that are already concatenated: coord (T,3) fp32, feat (T,3) fp32, label (T) int64"""
     B, dev, total = len(sizes), coord.device, sum(sizes)
-    if voxel_max is None or int(voxel_max) <= 0:
-        raise ValueError(f"{who}: voxel_max is the size of a training cloud")
-    if gravity_dim not in (0, 1, 2) or not float(voxel_size) > 0:
-        raise ValueError(f"{who}: gravity_dim is 0, 1 or 2 and voxel_size is positive")
-    if total >= 2 ** 31:
-        raise ValueError(f"{who}: {total} points in one batch (at most 2^31 - 1)")
+    _check_rooms_args(who, voxel_size, voxel_max, gravity_dim, total)
     voxel_max = int(voxel_max)
     d = dict(draws or {})
-    per_room = {}
-    for k in ("rnd", "init_idx", "pad", "perm"):
-        v = d.pop(k, None)
-        per_room[k] = list(v) if v is not None else [None] * B
-        if len(per_room[k]) != B:
-            raise ValueError(f"{who}: per-room draws need one entry per room")
+    per_room = _pop_per_room(d, B, who)
     if any(k not in d for k in _SCANNET_TRANSFORM_KEYS) or ("angle" not in d and "R" not in d):
-        for k, v in transform.draw(B, generator, dev).items():  # a read-back when the generator lives on the device
-            d.setdefault(k, v)
-    lib = _lib.load()
-    P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        for k, t in transform.draw(B, generator, dev).items():  # a read-back when the generator lives on the device
+            d.setdefault(k, t)
     offsets = [0]
     for n in sizes:
         offsets.append(offsets[-1] + n)
     off_t = _upload(offsets, torch.int64, dev)
     pos64, x = _scannet_transform(transform, coord, feat, off_t, d)
-    p = torch.empty(total, 3, dtype=torch.float64, device=dev)
-    key = torch.empty(total, dtype=torch.int64, device=dev)  # uint64 bit patterns
-    idx_sort = torch.empty(total, dtype=torch.int32, device=dev)
-    start = torch.empty(total + 1, dtype=torch.int32, device=dev)
-    count = torch.empty(total, dtype=torch.int32, device=dev)
-    small = torch.empty(2 * B + 1, dtype=torch.int32, device=dev)
-    vbase, cmax = small[:B + 1], small[B + 1:]
-    corner = torch.empty(B, 3, dtype=torch.float64, device=dev)
-    wb = int(lib.amc3d_scannet_voxelize_workspace_bytes(B, total))
-    work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.amc3d_scannet_voxelize_rooms(B, total, P(pos64), P(off_t), ctypes.c_double(float(voxel_size)), P(p), P(key),
-                                                    P(idx_sort), P(start), P(count), P(vbase), P(cmax), P(corner), P(work), wb,
-                                                    stream), "scannet_voxelize_rooms")
+    v = _RoomVoxels("scannet", torch.float64, B, total, voxel_size, dev, (_opt(pos64), _opt(off_t)))
     # the device's own draws, enqueued before the read-back in tables sized by the point count (a room has at most as many
     # voxels as points), so the stream does not depend on the voxel counts: voxelize's randint, crop_pc's randint(N), its
     # np.random.choice(N, voxel_max - N) and its permutation, in this order
     rnd_u = init_u = pad_t = perm_t = None
     if any(r is None for r in per_room["rnd"]):
         rnd_u = torch.rand(total, dtype=torch.float64, device=dev, generator=generator)
-    if any(v is None for v in per_room["init_idx"]):
+    if any(i is None for i in per_room["init_idx"]):
         init_u = torch.rand(B, dtype=torch.float64, device=dev, generator=generator)
     if not variable:
-        if any(v is None for v in per_room["pad"]):
-            nvd = (vbase[1:] - vbase[:-1]).view(B, 1)
-            pad_t = (torch.rand(B, voxel_max, dtype=torch.float64, device=dev, generator=generator) * nvd).int()
-        if any(v is None for v in per_room["perm"]):
+        if any(p is None for p in per_room["pad"]):
+            pad_t = (torch.rand(B, voxel_max, dtype=torch.float64, device=dev, generator=generator) * v.nv_column()).int()
+        if any(p is None for p in per_room["perm"]):
             perm_t = torch.rand(B, voxel_max, device=dev, generator=generator).argsort(dim=1).int()
-    vb = vbase.tolist()  # the batch's one read-back: the voxel counts size everything after the voxelisation
-    nv = [vb[b + 1] - vb[b] for b in range(B)]
-    nvt = vb[B]
-    outs = [voxel_max if (n >= voxel_max or not variable) else n for n in nv]
-    n_out = outs[0]
-    if any(n != n_out for n in outs):
-        raise ValueError(f"{who}: the rooms came out with different sizes {outs} (variable=True); the collate stacks them")
-    cropped = [n >= voxel_max for n in nv]
-    padded = [n < n_out for n in nv]
-    given = lambda v: torch.as_tensor(v).to(dev)  # noqa: E731
-    rnd_t = None
-    if any(r is not None for r in per_room["rnd"]):
-        rnd_t = torch.full((nvt,), -1, dtype=torch.int32, device=dev)
-        for b, r in enumerate(per_room["rnd"]):
-            if r is not None:
-                r = given(r)
-                if r.shape != (nv[b],) or r.is_floating_point() or bool((r < 0).any()):
-                    raise ValueError(f"{who}: room {b}: rnd must hold {nv[b]} non-negative draws")
-                rnd_t[vb[b]:vb[b + 1]] = r
-    init_t = None
-    if any(cropped):
-        inits = []
-        for b, v in enumerate(per_room["init_idx"]):
-            v = -1 if (v is None or not cropped[b]) else int(v)
-            if per_room["init_idx"][b] is not None and cropped[b] and not 0 <= v < nv[b]:
-                raise ValueError(f"{who}: room {b}: init_idx {v} out of range")
-            inits.append(v)
-        if any(v >= 0 for v in inits):
-            init_t = _upload(inits, torch.int32, dev)
-    if any(padded):
-        if pad_t is None:
-            pad_t = torch.zeros(B, n_out, dtype=torch.int32, device=dev)
-        for b, v in enumerate(per_room["pad"]):
-            if v is not None and padded[b]:
-                v = given(v)
-                if v.shape != (n_out - nv[b],) or v.is_floating_point() or bool(((v < 0) | (v >= nv[b])).any()):
-                    raise ValueError(f"{who}: room {b}: pad must hold {n_out - nv[b]} indices below {nv[b]}")
-                pad_t[b, nv[b]:] = v
-    if perm_t is None:
-        if any(v is None for v in per_room["perm"]):  # variable=True: the size of the shuffle is the voxel count
-            perm_t = torch.rand(B, n_out, device=dev, generator=generator).argsort(dim=1).int()
-        else:
-            perm_t = torch.empty(B, n_out, dtype=torch.int32, device=dev)
-    for b, v in enumerate(per_room["perm"]):
-        if v is not None:
-            v = given(v)
-            if v.shape != (n_out,) or v.is_floating_point() or not bool((v.sort().values == torch.arange(n_out, device=dev)).all()):
-                raise ValueError(f"{who}: room {b}: perm must be a permutation of {n_out}")
-            perm_t[b] = v
-    sel = torch.empty(max(nvt, 1), dtype=torch.int32, device=dev)
-    d2 = order = work2 = None
-    wb2 = 0
-    if any(cropped):
-        d2 = torch.empty(nvt, dtype=torch.float64, device=dev)
-        order = torch.empty(nvt, dtype=torch.int32, device=dev)
-        wb2 = int(lib.amc3d_scannet_crop_workspace_bytes(nvt))
-        work2 = torch.empty(max(wb2, 8), dtype=torch.uint8, device=dev)
-    wb3 = int(lib.amc3d_scannet_crop_tail_workspace_bytes(B))
-    work3 = torch.empty(max(wb3, 8) // 8, dtype=torch.float64, device=dev)
+    v.read_back(voxel_max, variable, who)
+    n_out = v.n_out
+    if perm_t is None and any(p is None for p in per_room["perm"]):  # variable=True: the size of the shuffle is the voxel count
+        perm_t = torch.rand(B, n_out, device=dev, generator=generator).argsort(dim=1).int()
+    rnd_t, init_t, pad_t, perm_t = v.given(per_room, pad_t, perm_t, True, who)
+    sel, order = v.select_crop(voxel_max, rnd_t, rnd_u, init_t, init_u)
+    wb = int(v.lib.amc3d_scannet_crop_tail_workspace_bytes(B))
+    work = torch.empty(max(wb, 8) // 8, dtype=torch.float64, device=dev)
     out = {"pos": torch.empty(B, n_out, 3, dtype=torch.float32, device=dev),
            "x": torch.empty(B, n_out, 3, dtype=torch.float32, device=dev),
            "heights": torch.empty(B, n_out, 1, dtype=torch.float32, device=dev),
            "y": torch.empty(B, n_out, dtype=torch.int64, device=dev)}
     with torch.cuda.device(dev):
-        _lib.check(lib.amc3d_scannet_select_crop(B, nvt, voxel_max, int(any(cropped)), P(p), P(idx_sort), P(start), P(count),
-                                                 P(vbase), P(cmax), P(rnd_t), P(rnd_u), P(init_t), P(init_u), P(sel), P(d2), P(order),
-                                                 P(work2), wb2, stream), "scannet_select_crop")
-        _lib.check(lib.amc3d_scannet_crop_tail_rooms(B, n_out, voxel_max, int(gravity_dim), P(p), P(x), P(label), P(vbase), P(sel),
-                                                     P(order), P(pad_t), P(perm_t), P(out["pos"]), P(out["x"]), P(out["heights"]),
-                                                     P(out["y"]), P(work3), wb3, stream), "scannet_crop_tail_rooms")
+        _lib.check(v.lib.amc3d_scannet_crop_tail_rooms(B, n_out, voxel_max, int(gravity_dim), _opt(v.coord), _opt(x), _opt(label),
+                                                       _opt(v.vbase), _opt(sel), _opt(order), _opt(pad_t), _opt(perm_t),
+                                                       _opt(out["pos"]), _opt(out["x"]), _opt(out["heights"]), _opt(out["y"]),
+                                                       _opt(work), wb, v.stream), "scannet_crop_tail_rooms")
     return out
 
 
 def scannet_train_rooms(rooms, transform, voxel_size=0.02, voxel_max=64000, variable=False, generator=None, draws=None,
                         gravity_dim=2):
-    """scannet_train_batch with everything after the transform chain done for the whole batch at once (csrc/scannet_rooms.hip):
+    """scannet_train_batch with everything after the transform chain done for the whole batch at once (csrc/room_input.hip):
     the same arguments, the same `draws` dictionary -- the transform's keys, "R" included, and the per-room lists "rnd",
     "init_idx", "pad", "perm" (entries may be None) -- and the same return value.  For the same draws every output equals
     scannet_train_batch's bit for bit, in about twenty launches for the batch instead of about twenty per room.

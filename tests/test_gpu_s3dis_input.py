@@ -1,4 +1,4 @@
-"""S3DIS training input on the device for a batch of raw rooms (csrc/s3dis_input.hip, input_pipeline.s3dis_train_batch,
+"""S3DIS training input on the device for a batch of raw rooms (csrc/room_input.hip, input_pipeline.s3dis_train_batch,
 input_pipeline.S3DISTrainFeed): against what the reference's own S3DIS.__getitem__ returned for the same raw rooms and draws
 (tests/golden/s3dis_input.npz, through the numpy restatement tests/s3dis_input_ref.py), and bit for bit against the per-room
 route -- input_pipeline.crop_pc on the shifted float32 room, torch.stack, augment.S3DISTrainAugment -- on the same draws."""

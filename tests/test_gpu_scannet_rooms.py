@@ -1,4 +1,4 @@
-"""ScanNet's training input for a whole batch of rooms per call (csrc/scannet_rooms.hip, input_pipeline.scannet_train_rooms,
+"""ScanNet's training input for a whole batch of rooms per call (csrc/room_input.hip, input_pipeline.scannet_train_rooms,
 input_pipeline.ScanNetTrainFeed): against the per-room route scannet_train_batch on the same draws and against the numpy
 restatement (tests/scannet_input_ref.py, pinned to the reference's run by tests/golden/scannet_input.npz), bit for bit: there
 are no tolerances here.  The small helpers are those of tests/test_gpu_scannet_input.py."""

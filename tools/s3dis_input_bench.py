@@ -1,7 +1,7 @@
 """S3DIS training input for one batch of raw rooms, three ways, in one process:  python tools/s3dis_input_bench.py [rooms=8]
 [points=1000000] -> one JSON line.
 
-  batched     input_pipeline.s3dis_train_batch on the list of rooms (csrc/s3dis_input.hip; includes the concatenation)
+  batched     input_pipeline.s3dis_train_batch on the list of rooms (csrc/room_input.hip; includes the concatenation)
   feed        the same through input_pipeline.S3DISTrainFeed, which keeps the rooms concatenated: what an epoch pays per batch
   per_room    the route without it: S3DIS.__getitem__'s cast and shift in torch, input_pipeline.crop_pc per room, torch.stack,
               augment.S3DISTrainAugment

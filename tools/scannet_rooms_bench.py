@@ -2,7 +2,7 @@
 -> one JSON line.
 
   per_room    input_pipeline.scannet_train_batch: the transform for the batch, then voxelise / select / crop / tail room by room
-  joint       input_pipeline.scannet_train_rooms on the list of rooms (csrc/scannet_rooms.hip; includes the concatenation)
+  joint       input_pipeline.scannet_train_rooms on the list of rooms (csrc/room_input.hip; includes the concatenation)
   feed        input_pipeline.ScanNetTrainFeed on the same rooms kept resident: one epoch of `calls` batches per window, so the
               epoch's own two read-backs and the per-batch concatenation of the picked slices are in the figure
 
