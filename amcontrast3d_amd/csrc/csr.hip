@@ -264,7 +264,7 @@ __global__ __launch_bounds__(CSR_BS, 1) void csr_collapse_kernel(int C, int n, l
         const int k = t / 5, v = t - k * 5;
         double sum = 0.0;
         for (int gq = 0; gq < GROUPS; ++gq) sum += red[gq][k][v];
-        partial[((size_t)blockIdx.x * C + c0 + k) * 5 + v] = sum;
+        partial[((size_t)(c0 + k) * gridDim.x + blockIdx.x) * 5 + v] = sum;  // [channel][workgroup][5]: lagg_sum_records
     }
 }
 
@@ -351,7 +351,7 @@ __global__ __launch_bounds__(256) void csr_collapse_shfl_kernel(int C, int n, lo
         const int k = t / 5, v = t - k * 5;
         double sum = 0.0;
         for (int gq = 0; gq < GROUPS; ++gq) sum += red[gq][k][v];
-        partial[((size_t)blockIdx.x * C + c0 + k) * 5 + v] = sum;
+        partial[((size_t)(c0 + k) * gridDim.x + blockIdx.x) * 5 + v] = sum;  // [channel][workgroup][5]: lagg_sum_records
     }
 }
 
@@ -456,7 +456,7 @@ __global__ __launch_bounds__(256) void csr_collapse_stream_kernel(int C, long P,
         const int k = t / 5, v = t - k * 5;
         double sum = 0.0;
         for (int gq = 0; gq < GROUPS; ++gq) sum += red[gq][k][v];
-        partial[((size_t)blockIdx.x * C + c0 + k) * 5 + v] = sum;
+        partial[((size_t)(c0 + k) * gridDim.x + blockIdx.x) * 5 + v] = sum;  // [channel][workgroup][5]: lagg_sum_records
     }
 }
 
@@ -813,7 +813,7 @@ size_t csr_partials(int b, int cout, int n)
 }  // namespace amc
 
 // stage 1 of amc3d_grouped_conv_bn_backward without atomics: Q (b,n,cout) and the per-workgroup partial sums
-// [nparts][cout][5] doubles from the POSITION-major gradient dx1_pm (b, npoints*nsample, cout); the caller finishes with the
+// [cout][nparts][5] doubles from the POSITION-major gradient dx1_pm (b, npoints*nsample, cout); the caller finishes with the
 // finalize / apply kernels of lagg.hip (amc3d_grouped_conv_bn_backward does all of it when given rev lists)
 namespace amc {
 int csr_collapse(int b, int cout, int n, int npoints, int nsample, int relu, const float *dx1_pm, const float *g_pm,

@@ -363,21 +363,25 @@ size_t gemm_conv_backward_data_workspace_bytes(int b, int cin, int cout, long P)
     return sp > 1 ? (size_t)b * sp * cin * P * sizeof(float) : 0;
 }
 
+// y_pm: y as (b,P,cout) rows (no bias); the split-K partials then have that layout too and their sum is elementwise -- the same
+// accumulators and the same order of the partial sums as the channel-major form, so the rows equal its transpose bit for bit
 int gemm_conv_forward(int b, int cin, int cout, long P, const float *x, const float *w, long ldw, const float *bias, float *y,
-                      float *partial, hipStream_t stream)
+                      int y_pm, float *partial, hipStream_t stream)
 {
+    if (y_pm && bias) return bad_arg("gemm_conv_forward: rows take no bias");
     GemmView A{w, ldw, 1}, B{x, 1, P};  // A(m=co,k=ci) k-contiguous; B(n=p,k=ci) at x[k*P + n]: n-contiguous
     const int va = cin % 4 == 0 && ldw % 4 == 0 && aligned16(w), vb = P % 4 == 0 && aligned16(x);
     const int sp = partial ? gemm_short_splits(b, cout, P, cin) : 1;
     if (sp > 1) {
         const long kper = (((long)cin + sp - 1) / sp + GM_KC - 1) / GM_KC * GM_KC;
-        gm_launch<true, false>(cout, (int)P, cin, b, sp, kper, A, 0, B, (long)cin * P, partial, (long)cout * P, P, va, vb, stream);
+        gm_launch<true, false>(cout, (int)P, cin, b, sp, kper, A, 0, B, (long)cin * P, partial, (long)cout * P, P, va, vb, stream,
+                               y_pm);
         const long total = (long)cout * P;
         hipLaunchKernelGGL(gm_split_reduce_kernel, dim3(div_up(total, 256), b), dim3(256), 0, stream, total, P, sp,
                            (const float *)partial, bias, y);
         return launch_status("gemm_conv_forward");
     }
-    gm_launch<true, false>(cout, (int)P, cin, b, 1, cin, A, 0, B, (long)cin * P, y, (long)cout * P, P, va, vb, stream);
+    gm_launch<true, false>(cout, (int)P, cin, b, 1, cin, A, 0, B, (long)cin * P, y, (long)cout * P, P, va, vb, stream, y_pm);
     if (bias) {
         const long total = (long)cout * P;
         hipLaunchKernelGGL(gm_bias_kernel, dim3(div_up(total, 256), b), dim3(256), 0, stream, total, P, bias, y);

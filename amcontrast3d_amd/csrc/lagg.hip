@@ -32,8 +32,7 @@ constexpr double LAGG_FX_D = 68719476736.0;   // 2^36: fixed point of the per-po
 constexpr double LAGG_FX_M = 1073741824.0;    // 2^30: fixed point of the global moments (block partials in double)
 constexpr int LAGG_MT = 32;                   // centroids per workgroup tile (8 per wave)
 constexpr int LAGG_CT = 128;                  // channels per workgroup (pool / scatter kernels)
-constexpr int LAGG_NT = 64;                   // points per tile (statistics / apply kernels)
-constexpr int LAGG_TILES = 4;                 // tiles per workgroup in the partial-sum kernels
+constexpr int LAGG_TILES = 4;                 // tiles per workgroup of the backward scatter kernel on large grids
 
 struct LaggMoments {  // views into the opaque moments buffer of amc3d_group_moments
     const long long *mom;   // [9 (+7 pad)] S1[3], S2[(0,0),(0,1),(0,2),(1,1),(1,2),(2,2)]
@@ -94,48 +93,114 @@ __global__ __launch_bounds__(256) void lagg_geom_kernel(int n, long P, const int
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// forward statistics: per channel  sum_n cnt G,  sum_n cnt G^2,  sum_n G D_j  (j = 0..2)  + the point-major copy of G
-// grid (n-tile groups, channel chunks of 64, b)
+// forward statistics: per channel  sum_n cnt G,  sum_n cnt G^2,  sum_n G D_j  (j = 0..2)  from the rows of G (b*n, C)
+// grid (point ranges, channel chunks of 4 * LPR <= 64).  The b*n points are one axis.  LPR lanes share a row, 16 bytes (four
+// channels) each, so a wave instruction fetches 64 / LPR rows -- no idle lanes at 8, 16 or 32 channels -- and up to four such
+// instructions are in flight before the first is used.  A wave takes 64 points at a time: lane l loads and converts cnt / D of
+// point l once and leaves them in LDS for the row phase.  The partial sums go out as partial[channel][workgroup][5]: a fixed
+// partition of the points and a fixed order inside it, so the sums have the same bits on every run.
 // ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void lagg_stats_kernel(int C, int n, const float *__restrict__ g_cm, float *__restrict__ g_pm,
-                                                         LaggMoments gm, double *__restrict__ partial, int nparts_per_b,
-                                                         int tiles_per_wg)
+constexpr int LAGG_SP = 256;  // points per workgroup pass (64 per wave)
+
+template <int LPR>
+__global__ __launch_bounds__(256) void lagg_stats_rows_kernel(int C, long G, const float *__restrict__ g_pm, LaggMoments gm,
+                                                              double *__restrict__ partial, int pts_per_wg)
 {
-    __shared__ float tile[64][LAGG_NT + 1];
-    __shared__ double red[4][64][5];
-    const int b = blockIdx.z, c0 = blockIdx.y * 64;
+    constexpr int CT = 4 * LPR, R = 64 / LPR, U = LPR < 4 ? LPR : 4;
+    __shared__ double pt[4][64][4];  // cnt, D_x, D_y, D_z of the wave's 64 points
+    __shared__ double red[4][CT][5];
+    const int c0 = blockIdx.y * CT;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c = c0 + lane;
-    double a[5] = {0, 0, 0, 0, 0};
-    for (int tt = 0; tt < tiles_per_wg; ++tt) {
-        const int n0 = (blockIdx.x * tiles_per_wg + tt) * LAGG_NT;
-        if (n0 >= n) break;
+    const int q = lane % LPR, r = lane / LPR;
+    double a[4][5];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int v = 0; v < 5; ++v) a[j][v] = 0.0;
+    const long gbeg = (long)blockIdx.x * pts_per_wg, gend = min(G, gbeg + pts_per_wg);
+    for (long g0 = gbeg; g0 < gend; g0 += LAGG_SP) {  // (the trip count is the same for the four waves)
+        const long gw = g0 + wave * 64;
         __syncthreads();
-        for (int r = wave; r < 64; r += 4) {  // r: channel of the chunk, lane: point
-            const int ch = c0 + r, nn = n0 + lane;
-            tile[r][lane] = (ch < C && nn < n) ? g_cm[((size_t)b * C + ch) * n + nn] : 0.f;
+        {
+            double cn = 0.0, dx = 0.0, dy = 0.0, dz = 0.0;
+            if (gw + lane < gend) {
+                const long long *df = gm.dfx + (size_t)(gw + lane) * 3;
+                const long long fx = df[0], fy = df[1], fz = df[2];
+                cn = (double)gm.cnt[gw + lane];
+                dx = (double)fx * (1.0 / LAGG_FX_D); dy = (double)fy * (1.0 / LAGG_FX_D); dz = (double)fz * (1.0 / LAGG_FX_D);
+            }
+            pt[wave][lane][0] = cn; pt[wave][lane][1] = dx; pt[wave][lane][2] = dy; pt[wave][lane][3] = dz;
         }
         __syncthreads();
-        for (int i = 0; i < 16; ++i) {
-            const int nl = wave * 16 + i, nn = n0 + nl;
-            if (nn >= n) break;  // wave-uniform
-            const float g = tile[lane][nl];
-            if (c < C) g_pm[((size_t)b * n + nn) * C + c] = g;
-            const double cn = (double)gm.cnt[(size_t)b * n + nn];
-            const long long *df = gm.dfx + ((size_t)b * n + nn) * 3;
-            const double dx = (double)df[0] * (1.0 / LAGG_FX_D), dy = (double)df[1] * (1.0 / LAGG_FX_D),
-                         dz = (double)df[2] * (1.0 / LAGG_FX_D);
-            const double gd = g;
-            a[0] += cn * gd; a[1] += cn * gd * gd; a[2] += gd * dx; a[3] += gd * dy; a[4] += gd * dz;
+#pragma unroll 1  // (unrolled, the 16-step form held every step's point values at once: 314 registers)
+        for (int i0 = 0; i0 < LPR; i0 += U) {
+            float4 g[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const long gg = gw + (i0 + u) * R + r;
+                g[u] = gg < gend ? *reinterpret_cast<const float4 *>(g_pm + (size_t)gg * C + c0 + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const double *pp = pt[wave][(i0 + u) * R + r];  // (zeros past the end of the range)
+                const double cn = pp[0], dx = pp[1], dy = pp[2], dz = pp[3];
+                const float gs[4] = {g[u].x, g[u].y, g[u].z, g[u].w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const double gd = gs[j], cg = cn * gd;
+                    a[j][0] += cg; a[j][1] += cg * gd; a[j][2] += gd * dx; a[j][3] += gd * dy; a[j][4] += gd * dz;
+                }
+            }
         }
     }
+    // combine the row slots (lanes q, q + LPR, ...), then the four waves
 #pragma unroll
-    for (int j = 0; j < 5; ++j) red[wave][lane][j] = a[j];
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int v = 0; v < 5; ++v) {
+            double x = a[j][v];
+#pragma unroll
+            for (int s = LPR; s < 64; s <<= 1) x += __shfl_xor(x, s, 64);
+            a[j][v] = x;
+        }
+    if (r == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int v = 0; v < 5; ++v) red[wave][4 * q + j][v] = a[j][v];
+    }
     __syncthreads();
-    if (wave == 0 && c < C) {
-        double *out = partial + (((size_t)b * nparts_per_b + blockIdx.x) * C + c) * 5;
+    for (int t = threadIdx.x; t < CT * 5; t += 256) {
+        const int cl = t / 5, v = t - cl * 5;
+        partial[((size_t)(c0 + cl) * gridDim.x + blockIdx.x) * 5 + v] = (red[0][cl][v] + red[1][cl][v]) + (red[2][cl][v] + red[3][cl][v]);
+    }
+}
+
+// The sum of one channel's partial records rec[nparts][5] (contiguous doubles) by a workgroup of LAGG_FT threads, left in
+// red[0..4].  LAGG_FT is a multiple of 5, so thread t only ever meets sum t % 5: its loads are 8 bytes, contiguous over the
+// workgroup, eight of them in flight; the sub-sums are then added in a fixed tree whose strides are multiples of 5 too.
+// (One record per thread at a stride of C * 40 bytes, one or four in flight, took 8-24 us for 3000-8192 partials.)
+constexpr int LAGG_FT = 640;
+constexpr int LAGG_FU = 8;  // loads in flight per thread: one pass of the unrolled loop consumes LAGG_FT * LAGG_FU / 5 = 1024 records
+
+__device__ __forceinline__ void lagg_sum_records(const double *__restrict__ rec, int nparts, double *red)
+{
+    const int total = nparts * 5, t = threadIdx.x;
+    double s[LAGG_FU];
 #pragma unroll
-        for (int j = 0; j < 5; ++j) out[j] = (red[0][lane][j] + red[1][lane][j]) + (red[2][lane][j] + red[3][lane][j]);
+    for (int u = 0; u < LAGG_FU; ++u) s[u] = 0.0;
+    int i = t;
+    for (; i + (LAGG_FU - 1) * LAGG_FT < total; i += LAGG_FU * LAGG_FT) {
+#pragma unroll
+        for (int u = 0; u < LAGG_FU; ++u) s[u] += rec[i + u * LAGG_FT];
+    }
+    for (; i < total; i += LAGG_FT) s[0] += rec[i];
+    red[t] = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
+    __syncthreads();
+#pragma unroll
+    for (int h = LAGG_FT / 2; h >= 5; h >>= 1) {  // 320, 160, ..., 5
+        if (t < h) red[t] += red[t + h];
+        __syncthreads();
     }
 }
 
@@ -143,7 +208,7 @@ __global__ __launch_bounds__(256) void lagg_stats_kernel(int C, int n, const flo
 // mode 0: everything from this rank's sums.  Statistics over several ranks (torch.nn.SyncBatchNorm semantics,
 // main_AA.py:146-148): mode 1 writes this rank's {sum y, sum y^2} per channel and its position count to sums (2C + 1
 // doubles) for the caller to all-reduce, mode 2 derives mean / invstd from the reduced sums.
-__global__ __launch_bounds__(256) void lagg_stats_finalize_kernel(int C, int nparts, double count, float eps, float momentum,
+__global__ __launch_bounds__(LAGG_FT) void lagg_stats_finalize_kernel(int C, int nparts, double count, float eps, float momentum,
                                                                   const double *__restrict__ partial, const long long *__restrict__ mom,
                                                                   WDp w_dp, float *__restrict__ mean,
                                                                   float *__restrict__ invstd, float *__restrict__ var_unbiased,
@@ -151,30 +216,26 @@ __global__ __launch_bounds__(256) void lagg_stats_finalize_kernel(int C, int npa
                                                                   float *__restrict__ running_var, long long *__restrict__ tracked,
                                                                   int mode, double *__restrict__ sums)
 {
-    __shared__ double red[4][5];
+    __shared__ double red[LAGG_FT];
     const int c = blockIdx.x;
+    // what thread 0's formula reads besides the sums: requested before the records, so it arrives behind them
+    long long mi[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double w0 = 0.0, w1 = 0.0, w2 = 0.0;
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int j = 0; j < 9; ++j) mi[j] = mom[j];
+        w0 = w_dp.at(c, 0); w1 = w_dp.at(c, 1); w2 = w_dp.at(c, 2);
+    }
     double a[5] = {0, 0, 0, 0, 0};
-    if (mode == 2) nparts = 0;
-    for (int k = threadIdx.x; k < nparts; k += 256) {
-        const double *p = partial + ((size_t)k * C + c) * 5;
-#pragma unroll
-        for (int j = 0; j < 5; ++j) a[j] += p[j];
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        double v = a[j];
-        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) red[wave][j] = v;
-    }
-    __syncthreads();
+    if (mode != 2) lagg_sum_records(partial + (size_t)c * nparts * 5, nparts, red);  // (mode is the same for every thread)
     if (threadIdx.x != 0) return;
+    if (mode != 2) {
 #pragma unroll
-    for (int j = 0; j < 5; ++j) a[j] = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]);
+        for (int j = 0; j < 5; ++j) a[j] = red[j];
+    }
     double m[9];
 #pragma unroll
-    for (int j = 0; j < 9; ++j) m[j] = (double)mom[j] * (1.0 / LAGG_FX_M);
-    const double w0 = w_dp.at(c, 0), w1 = w_dp.at(c, 1), w2 = w_dp.at(c, 2);
+    for (int j = 0; j < 9; ++j) m[j] = (double)mi[j] * (1.0 / LAGG_FX_M);
     const double sy = a[0] + w0 * m[0] + w1 * m[1] + w2 * m[2];
     const double quad = w0 * w0 * m[3] + w1 * w1 * m[6] + w2 * w2 * m[8] + 2.0 * (w0 * w1 * m[4] + w0 * w2 * m[5] + w1 * w2 * m[7]);
     double sy2 = a[1] + 2.0 * (w0 * a[2] + w1 * a[3] + w2 * a[4]) + quad, sy1 = sy;
@@ -403,7 +464,7 @@ __global__ __launch_bounds__(256) void lagg_bwd_scatter_kernel(int C, int n, int
         const int cl = t / 5, j = t - cl * 5;
         const double v = (red[((size_t)0 * ct + cl) * 5 + j] + red[((size_t)1 * ct + cl) * 5 + j]) +
                          (red[((size_t)2 * ct + cl) * 5 + j] + red[((size_t)3 * ct + cl) * 5 + j]);
-        partial[(((size_t)b * nparts_per_b + blockIdx.x) * C + c0 + cl) * 5 + j] = v;
+        partial[((size_t)(c0 + cl) * gridDim.z * nparts_per_b + (size_t)b * nparts_per_b + blockIdx.x) * 5 + j] = v;
     }
 }
 
@@ -447,9 +508,10 @@ __global__ __launch_bounds__(256) void lagg_bwd_gather_kernel(int C, int n, int 
 
 // dgamma, dbeta, dW_dp and the per-channel coefficients of dG: coef[c] = {g*is, ma, mb*is, mu}
 // mode 0: one rank.  mode 1: reduce this rank's partials, publish {sum dq, sum dq xhat} to dsums (2C doubles) for the
-// all-reduce, keep the five local sums in partial slot 0; mode 2: coefficients from the reduced dsums and the global count
-// (*count_dev), dW_dp from the local sums (parameter gradients stay rank-local, as torch's SyncBatchNorm leaves them)
-__global__ __launch_bounds__(256) void lagg_bwd_finalize_kernel(int C, int nparts, double count, double *__restrict__ partial,
+// all-reduce, keep the five local sums in the channel's first record; mode 2 (same nparts): coefficients from the reduced dsums
+// and the global count (*count_dev), dW_dp from the local sums (parameter gradients stay rank-local, as torch's SyncBatchNorm
+// leaves them).  partial[channel][nparts][5], summed by lagg_sum_records.
+__global__ __launch_bounds__(LAGG_FT) void lagg_bwd_finalize_kernel(int C, int nparts, double count, double *__restrict__ partial,
                                                                 const long long *__restrict__ mom, const double *__restrict__ gd,
                                                                 WDp w_dp, const float *__restrict__ mean,
                                                                 const float *__restrict__ invstd, const float *__restrict__ gamma,
@@ -457,59 +519,43 @@ __global__ __launch_bounds__(256) void lagg_bwd_finalize_kernel(int C, int npart
                                                                 float *__restrict__ dw_dp, long lddw, float *__restrict__ coef, int mode,
                                                                 double *__restrict__ dsums, const double *__restrict__ count_dev)
 {
-    __shared__ double red[4][5];
+    __shared__ double red[LAGG_FT];
     const int c = blockIdx.x;
-    double a[5] = {0, 0, 0, 0, 0};
-    if (mode == 2) nparts = 1;  // slot 0 holds this rank's reduced sums
-    {   // four partials in flight per thread (the reverse-list collapse writes up to 8192 of them: a chain of 32 dependent
-        // round trips per thread otherwise); four interleaved sub-sums added in a fixed order
-        double a1[5] = {0, 0, 0, 0, 0}, a2[5] = {0, 0, 0, 0, 0}, a3[5] = {0, 0, 0, 0, 0};
-        int k = threadIdx.x;
-        for (; k + 768 < nparts; k += 1024) {
-            const double *p0 = partial + ((size_t)k * C + c) * 5, *p1 = p0 + (size_t)256 * C * 5, *p2 = p1 + (size_t)256 * C * 5,
-                         *p3 = p2 + (size_t)256 * C * 5;
+    double *rec = partial + (size_t)c * nparts * 5;  // this channel's records; the first holds the rank's reduced sums after mode 1
+    // what thread 0's formula reads besides the sums: requested before the records, so it arrives behind them
+    long long mi[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double w[3] = {0, 0, 0}, gdc[3] = {0, 0, 0}, mu = 0.0, is = 0.0, g = 0.0, sa2 = 0.0, sb2 = 0.0;
+    if (threadIdx.x == 0) {
 #pragma unroll
-            for (int j = 0; j < 5; ++j) { a[j] += p0[j]; a1[j] += p1[j]; a2[j] += p2[j]; a3[j] += p3[j]; }
-        }
-        for (; k < nparts; k += 256) {
-            const double *p = partial + ((size_t)k * C + c) * 5;
+        for (int j = 0; j < 9; ++j) mi[j] = mom[j];
 #pragma unroll
-            for (int j = 0; j < 5; ++j) a[j] += p[j];
-        }
-#pragma unroll
-        for (int j = 0; j < 5; ++j) a[j] = (a[j] + a1[j]) + (a2[j] + a3[j]);
+        for (int j = 0; j < 3; ++j) { w[j] = w_dp.at(c, j); gdc[j] = gd[c * 3 + j]; }
+        mu = mean[c]; is = invstd[c]; g = gamma[c];
+        if (mode == 2) { sa2 = dsums[2 * c]; sb2 = dsums[2 * c + 1]; count = *count_dev; }
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        double v = a[j];
-        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) red[wave][j] = v;
-    }
-    __syncthreads();
+    lagg_sum_records(rec, mode == 2 ? 1 : nparts, red);
     if (threadIdx.x != 0) return;
+    double a[5];
 #pragma unroll
-    for (int j = 0; j < 5; ++j) a[j] = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]);
+    for (int j = 0; j < 5; ++j) a[j] = red[j];
     double m[9];
 #pragma unroll
-    for (int j = 0; j < 9; ++j) m[j] = (double)mom[j] * (1.0 / LAGG_FX_M);
+    for (int j = 0; j < 9; ++j) m[j] = (double)mi[j] * (1.0 / LAGG_FX_M);
     const double S2[3][3] = {{m[3], m[4], m[5]}, {m[4], m[6], m[7]}, {m[5], m[7], m[8]}};
-    const double mu = mean[c], is = invstd[c], g = gamma[c];
     if (mode != 2) { dbeta[c] = (float)a[0]; dgamma[c] = (float)a[1]; }
     if (mode == 1) {
 #pragma unroll
-        for (int j = 0; j < 5; ++j) partial[(size_t)c * 5 + j] = a[j];
+        for (int j = 0; j < 5; ++j) rec[j] = a[j];
         dsums[2 * c] = a[0]; dsums[2 * c + 1] = a[1];
         return;
     }
     double sa = a[0], sb = a[1];
-    if (mode == 2) { sa = dsums[2 * c]; sb = dsums[2 * c + 1]; count = *count_dev; }
+    if (mode == 2) { sa = sa2; sb = sb2; }
     const double ma = sa / count, mb = sb / count, gi = g * is;
-    const double w[3] = {w_dp.at(c, 0), w_dp.at(c, 1), w_dp.at(c, 2)};
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         // sum_p xhat_p dp_p[j] = is * ( sum_n G D_j + sum_j' w_j' S2[j'][j] - mu S1[j] )
-        const double sxd = is * (gd[c * 3 + j] + w[0] * S2[0][j] + w[1] * S2[1][j] + w[2] * S2[2][j] - mu * m[j]);
+        const double sxd = is * (gdc[j] + w[0] * S2[0][j] + w[1] * S2[1][j] + w[2] * S2[2][j] - mu * m[j]);
         dw_dp[c * lddw + j] = (float)(gi * (a[2 + j] - ma * m[j] - mb * sxd));
     }
     coef[c * 4 + 0] = (float)gi; coef[c * 4 + 1] = (float)ma; coef[c * 4 + 2] = (float)(mb * is); coef[c * 4 + 3] = (float)mu;
@@ -517,39 +563,70 @@ __global__ __launch_bounds__(256) void lagg_bwd_finalize_kernel(int C, int npart
 
 // ---------------------------------------------------------------------------------------------------------------
 // backward 2: dG[b,c,n] = gi * ( Q - cnt*ma - mbis * ( cnt*(G - mu) + W_dp . D ) ), written channel-major
-// grid (n tiles of 64, channel chunks of 64, b)
+// grid (n tiles of NT, channel chunks of CT = 4 * LPR <= 64, b), NT = 4096 / CT up to 256.  Rows as in lagg_stats_rows_kernel:
+// LPR lanes share a row of Q and of G, 16 bytes each, 64 / LPR rows per wave instruction, all of a wave's loads (at most four
+// instructions per operand) in flight at once; cnt / D of a point are loaded and converted by one thread and read from LDS.
+// The tile is turned in LDS; a wave then stores 256 contiguous bytes of one channel row.
 // ---------------------------------------------------------------------------------------------------------------
+template <int LPR>
 __global__ __launch_bounds__(256) void lagg_bwd_apply_kernel(int C, int n, const float *__restrict__ Q, const float *__restrict__ g_pm,
                                                              LaggMoments gm, WDp w_dp,
                                                              const float *__restrict__ coef, float *__restrict__ dg_cm)
 {
-    __shared__ float tile[64][LAGG_NT + 1];
-    const int b = blockIdx.z, c0 = blockIdx.y * 64, n0 = blockIdx.x * LAGG_NT;
+    constexpr int CT = 4 * LPR, R = 64 / LPR, NT = 4096 / CT < 256 ? 4096 / CT : 256, STEPS = NT / 4 / R;
+    __shared__ float tile[CT][NT + 1];  // odd stride: the (channel quad, point) writes are at most 2-way
+    __shared__ float4 pt[NT];           // cnt, D_x, D_y, D_z of the tile's points
+    const int b = blockIdx.z, c0 = blockIdx.y * CT, n0 = blockIdx.x * NT;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c = c0 + lane;
-    float gi = 0.f, ma = 0.f, mbis = 0.f, mu = 0.f, w0 = 0.f, w1 = 0.f, w2 = 0.f;
-    if (c < C) {
-        gi = coef[c * 4 + 0]; ma = coef[c * 4 + 1]; mbis = coef[c * 4 + 2]; mu = coef[c * 4 + 3];
-        w0 = w_dp.at(c, 0); w1 = w_dp.at(c, 1); w2 = w_dp.at(c, 2);
-    }
-    for (int i = 0; i < 16; ++i) {
-        const int nl = wave * 16 + i, nn = n0 + nl;
-        float v = 0.f;
-        if (nn < n && c < C) {
-            const size_t o = ((size_t)b * n + nn) * C + c;
-            const float cn = (float)gm.cnt[(size_t)b * n + nn];
-            const long long *df = gm.dfx + ((size_t)b * n + nn) * 3;
-            const float dx = (float)((double)df[0] * (1.0 / LAGG_FX_D)), dy = (float)((double)df[1] * (1.0 / LAGG_FX_D)),
-                        dz = (float)((double)df[2] * (1.0 / LAGG_FX_D));
-            const float wd = w0 * dx + w1 * dy + w2 * dz;
-            v = gi * (Q[o] - cn * ma - mbis * (cn * (g_pm[o] - mu) + wd));
+    const int q = lane % LPR, r = lane / LPR;
+    const int cq = c0 + 4 * q;
+    for (int t = threadIdx.x; t < NT; t += 256) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (n0 + t < n) {
+            const size_t gg = (size_t)b * n + n0 + t;
+            const long long *df = gm.dfx + gg * 3;
+            const long long fx = df[0], fy = df[1], fz = df[2];
+            v.x = (float)gm.cnt[gg];
+            v.y = (float)((double)fx * (1.0 / LAGG_FX_D)); v.z = (float)((double)fy * (1.0 / LAGG_FX_D));
+            v.w = (float)((double)fz * (1.0 / LAGG_FX_D));
         }
-        tile[lane][nl] = v;
+        pt[t] = v;
+    }
+    float gi[4], ma[4], mbis[4], mu[4], w[4][3];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = cq + j;
+        gi[j] = coef[c * 4 + 0]; ma[j] = coef[c * 4 + 1]; mbis[j] = coef[c * 4 + 2]; mu[j] = coef[c * 4 + 3];
+        w[j][0] = w_dp.at(c, 0); w[j][1] = w_dp.at(c, 1); w[j][2] = w_dp.at(c, 2);
+    }
+    float4 qv[STEPS], gv[STEPS];
+#pragma unroll
+    for (int i = 0; i < STEPS; ++i) {
+        const int nl = wave * (NT / 4) + i * R + r;
+        qv[i] = gv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (n0 + nl < n) {
+            const size_t o = ((size_t)b * n + n0 + nl) * C + cq;
+            qv[i] = *reinterpret_cast<const float4 *>(Q + o);
+            gv[i] = *reinterpret_cast<const float4 *>(g_pm + o);
+        }
     }
     __syncthreads();
-    for (int r = wave; r < 64; r += 4) {
-        const int ch = c0 + r, nn = n0 + lane;
-        if (ch < C && nn < n) dg_cm[((size_t)b * C + ch) * n + nn] = tile[r][lane];
+#pragma unroll
+    for (int i = 0; i < STEPS; ++i) {
+        const int nl = wave * (NT / 4) + i * R + r;
+        const float4 p = pt[nl];
+        const float cn = p.x, dx = p.y, dy = p.z, dz = p.w;
+        const float qs[4] = {qv[i].x, qv[i].y, qv[i].z, qv[i].w}, gs[4] = {gv[i].x, gv[i].y, gv[i].z, gv[i].w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float wd = w[j][0] * dx + w[j][1] * dy + w[j][2] * dz;
+            tile[4 * q + j][nl] = gi[j] * (qs[j] - cn * ma[j] - mbis[j] * (cn * (gs[j] - mu[j]) + wd));
+        }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < CT * NT; t += 256) {
+        const int cl = t / NT, pp = t - cl * NT;
+        if (n0 + pp < n) dg_cm[((size_t)b * C + c0 + cl) * n + n0 + pp] = tile[cl][pp];
     }
 }
 
@@ -717,7 +794,7 @@ __global__ __launch_bounds__(256) void lagg_collapse_kernel(int C, int n, long P
     __syncthreads();
     for (int t = threadIdx.x; t < CT * 5; t += 256) {
         const int cl2 = t / 5, v = t - cl2 * 5;
-        partial[(((size_t)b * nparts_per_b + blockIdx.x) * C + c0 + cl2) * 5 + v] =
+        partial[((size_t)(c0 + cl2) * gridDim.z * nparts_per_b + (size_t)b * nparts_per_b + blockIdx.x) * 5 + v] =
             (red[0][cl2][v] + red[1][cl2][v]) + (red[2][cl2][v] + red[3][cl2][v]);
     }
 }
@@ -730,15 +807,8 @@ static bool lagg_supported(int C, int K)
     return (lpr & (lpr - 1)) == 0 && C % ct == 0;  // 8,16,32,64,128 and multiples of 128
 }
 
-// tiles per workgroup of the statistics kernel: one while that still leaves the grid small (latency-bound kernel)
-static int lagg_stats_tiles(int b, int C, int n)
-{
-    const long wgs1 = (long)b * div_up(n, LAGG_NT) * div_up(C, 64);
-    return wgs1 <= 8192 ? 1 : LAGG_TILES;
-}
-
-// ... and of the backward scatter kernel (its workgroups walk their centroids serially: a few dozen of them took 50-100 us
-// on the coarse stages of PointNeXt-L)
+// tiles per workgroup of the backward scatter kernel: one while that still leaves the grid small (its workgroups walk their
+// centroids serially: a few dozen of them took 50-100 us on the coarse stages of PointNeXt-L)
 static int lagg_scatter_tiles(int b, int C, int M)
 {
     const long wgs1 = (long)b * div_up(M, LAGG_MT) * div_up(C, LAGG_CT);
@@ -747,7 +817,7 @@ static int lagg_scatter_tiles(int b, int C, int M)
 
 static size_t lagg_partial_bytes(int b, int C, int n, int M)
 {
-    const size_t pf = (size_t)b * div_up(div_up(n, LAGG_NT), lagg_stats_tiles(b, C, n)),
+    const size_t pf = (size_t)b * div_up(n, LAGG_SP),  // the statistics: at most one partial per 256-point pass (lagg_stats_pts)
                  pb = (size_t)b * div_up(div_up(M, LAGG_MT), lagg_scatter_tiles(b, C, M));
     const size_t pc = (size_t)b * div_up((long)M * 32, LAGG_PT);  // collapse kernel (K = 32), at most one partial per tile
     size_t m = pf > pb ? pf : pb;
@@ -762,6 +832,53 @@ static bool lagg_expand_supported(int C, int K)
     const int ct = C < LAGG_XC ? C : LAGG_XC;
     const int lpr = ct / 4;
     return (lpr & (lpr - 1)) == 0 && C % ct == 0;
+}
+
+size_t csr_partials(int b, int cout, int n);  // csr.hip
+constexpr int LAGG_CTILES = 2;  // tiles per workgroup of lagg_collapse_kernel (1, 2, 4 measured alike: the kernel runs at the float-atomic rate)
+
+// points per workgroup of lagg_stats_rows_kernel: whole 256-point passes, about 1024 workgroups over the chip.  At most
+// ceil(b * n / 256) partials per channel, which lagg_partial_bytes() reserves
+static int lagg_stats_pts(long G, int C)
+{
+    const int chunks = C <= 64 ? 1 : C / 64;
+    const long target = 1024 / chunks > 1 ? 1024 / chunks : 1;
+    const long passes = (G + LAGG_SP - 1) / LAGG_SP;
+    return (int)((passes + target - 1) / target) * LAGG_SP;
+}
+
+// batch statistics of the layer from the rows of G: the partial sums (phases 0, 1), then mean / invstd / gd / running buffers
+static int lagg_statistics(int b, int cout, int n, int npoints, int nsample, float eps, float momentum, const float *g_pm,
+                           const LaggMoments &gm, WDp w_dp, float *mean, float *invstd, float *var_unbiased, double *gd,
+                           float *running_mean, float *running_var, long long *num_batches_tracked, int phase, double *sums,
+                           double *partial, hipStream_t stream)
+{
+    const long G = (long)b * n;
+    const int ct = cout < 64 ? cout : 64;
+    const int per = lagg_stats_pts(G, cout), nparts = div_up(G, per);
+    if (phase != 2) {
+#define AMC_STATS(L)                                                                                                           \
+    hipLaunchKernelGGL(lagg_stats_rows_kernel<L>, dim3(nparts, cout / ct), dim3(256), 0, stream, cout, G, g_pm, gm, partial, per)
+        switch (ct / 4) { case 2: AMC_STATS(2); break; case 4: AMC_STATS(4); break; case 8: AMC_STATS(8); break; default: AMC_STATS(16); }
+#undef AMC_STATS
+    }
+    hipLaunchKernelGGL(lagg_stats_finalize_kernel, dim3(cout), dim3(LAGG_FT), 0, stream, cout, nparts,
+                       (double)b * (double)npoints * (double)nsample, eps, momentum, (const double *)partial, gm.mom, w_dp, mean,
+                       invstd, var_unbiased, gd, running_mean, running_var, num_batches_tracked, phase, sums);
+    return 0;
+}
+
+// dG (b, cout, n) channel-major from Q, the rows of G and the coefficients of lagg_bwd_finalize_kernel
+static void lagg_apply(int b, int cout, int n, const float *Q, const float *g_pm, const LaggMoments &gm, WDp w_dp, const float *coef,
+                       float *dg_cm, hipStream_t stream)
+{
+    const int ct = cout < 64 ? cout : 64;
+    const int nt = 4096 / ct < 256 ? 4096 / ct : 256;
+#define AMC_APPLY(L)                                                                                                           \
+    hipLaunchKernelGGL(lagg_bwd_apply_kernel<L>, dim3(div_up(n, nt), cout / ct, b), dim3(256), 0, stream, cout, n, Q, g_pm, gm,  \
+                       w_dp, coef, dg_cm)
+    switch (ct / 4) { case 2: AMC_APPLY(2); break; case 4: AMC_APPLY(4); break; case 8: AMC_APPLY(8); break; default: AMC_APPLY(16); }
+#undef AMC_APPLY
 }
 
 }  // namespace amc
@@ -807,6 +924,19 @@ AMC_API size_t amc3d_local_aggregation_workspace_q_offset(int b, int cout, int n
     return lagg_partial_bytes(b, cout, n, npoints);
 }
 
+// how many partial records per channel each producer leaves for the finalize kernels at this shape (tests and tools):
+// counts[0] the forward statistics, [1] the pooled layer's backward scatter, [2] the atomic collapse, [3] the reverse-list collapse
+AMC_API int amc3d_local_aggregation_partial_counts(int b, int cout, int n, int npoints, int nsample, int *counts)
+{
+    if (!counts || b <= 0 || cout <= 0 || n <= 0 || npoints <= 0 || nsample <= 0)
+        return bad_arg("amc3d_local_aggregation_partial_counts: bad argument");
+    counts[0] = div_up((long)b * n, lagg_stats_pts((long)b * n, cout));
+    counts[1] = b * div_up(div_up(npoints, LAGG_MT), lagg_scatter_tiles(b, cout, npoints));
+    counts[2] = b * div_up(div_up((long)npoints * nsample, LAGG_PT), LAGG_CTILES);
+    counts[3] = (int)csr_partials(b, cout, n);
+    return 0;
+}
+
 AMC_API size_t amc3d_local_aggregation_workspace_bytes(int b, int cout, int n, int npoints)
 {
     if (b <= 0 || cout <= 0 || n <= 0 || npoints <= 0) return 0;
@@ -814,11 +944,12 @@ AMC_API size_t amc3d_local_aggregation_workspace_bytes(int b, int cout, int n, i
     return lagg_partial_bytes(b, cout, n, npoints) + (size_t)b * n * cout * sizeof(float) + (size_t)cout * 4 * sizeof(float) + 64;
 }
 
-// g_cm (b,cout,n) = W_f . f, computed by the caller (amc3d_pointwise_conv_forward).  Outputs: g_pm (b,n,cout) the
-// point-major copy (kept for backward), pooled / ystar (b,cout,npoints) fp32, arg (b,cout,npoints) bytes, mean / invstd /
+// G = W_f . f comes from the caller: as rows g_pm (b,n,cout) (rows = true: amc3d_pointwise_conv_forward_rows wrote them, g_cm is
+// unused), or channel-major g_cm (b,cout,n), which is first turned into g_pm.  g_pm is kept for backward.  Outputs:
+// pooled / ystar (b,cout,npoints) fp32, arg (b,cout,npoints) bytes, mean / invstd /
 // var_unbiased (cout), gd (cout,3) doubles.  training == 0: mean / invstd are INPUTS (running statistics), no statistics pass.
 static int local_aggregation_forward_impl(int b, int cout, int n, int npoints, int nsample, int training,
-                                              int relu, float eps, float momentum, const float *g_cm,
+                                              int relu, float eps, float momentum, const float *g_cm, bool rows,
                                               const int *idx, const float *dp, WDp w_dp, const void *moments,
                                               const float *gamma, const float *beta, float *g_pm, float *pooled,
                                               unsigned char *arg, float *ystar, float *mean, float *invstd,
@@ -830,28 +961,22 @@ static int local_aggregation_forward_impl(int b, int cout, int n, int npoints, i
 {
     if (training && phase != 0 && !sums) return bad_arg("amc3d_local_aggregation_forward: phase 1 / 2 need the sums buffer");
     if (b <= 0 || npoints <= 0) return 0;
-    if (!lagg_supported(cout, nsample) || n <= 0 || !g_cm || !idx || !dp || !w_dp || !gamma || !beta || !g_pm || !pooled || !arg ||
-        !ystar || !mean || !invstd || (training && (!moments || !var_unbiased || !gd || !workspace ||
+    if (!lagg_supported(cout, nsample) || n <= 0 || (!rows && !g_cm) || !idx || !dp || !w_dp || !gamma || !beta || !g_pm || ((uintptr_t)g_pm & 15) ||
+        !pooled || !arg || !ystar || !mean || !invstd || (training && (!moments || !var_unbiased || !gd || !workspace ||
         workspace_bytes < amc3d_local_aggregation_workspace_bytes(b, cout, n, npoints))) ||
         (running_mean && (!running_var || !num_batches_tracked)))
-        return bad_arg("amc3d_local_aggregation_forward: unsupported shape, null pointer or workspace too small");
+        return bad_arg("amc3d_local_aggregation_forward: unsupported shape, null or misaligned pointer or workspace too small");
     hipStream_t stream = (hipStream_t)stream_;
     LaggMoments gm{};
     if (moments) gm = lagg_views(moments, b, n);
-    const int stiles = lagg_stats_tiles(b, cout, n);
-    const int nparts_b = div_up(div_up(n, LAGG_NT), stiles);
-    double *partial = (double *)workspace;
-    if (training) {
-        if (phase != 2)
-            hipLaunchKernelGGL(lagg_stats_kernel, dim3(nparts_b, div_up(cout, 64), b), dim3(256), 0, stream, cout, n, g_cm, g_pm, gm,
-                               partial, nparts_b, stiles);
-        hipLaunchKernelGGL(lagg_stats_finalize_kernel, dim3(cout), dim3(256), 0, stream, cout, nparts_b * b,
-                           (double)b * (double)npoints * (double)nsample, eps, momentum, (const double *)partial, gm.mom, w_dp,
-                           mean, invstd, var_unbiased, gd, running_mean, running_var, num_batches_tracked, phase, sums);
-        if (phase == 1) return launch_status("amc3d_local_aggregation_forward");
-    } else {
-        // eval mode: only the point-major copy is needed
+    // the entries that take G channel-major: its rows first (phase 2 finds them where phase 1 left them)
+    if (!rows && !(training && phase == 2))
         if (int st = amc3d_transpose_cn(b, cout, n, g_cm, g_pm, stream_)) return st;
+    if (training) {
+        if (int st = lagg_statistics(b, cout, n, npoints, nsample, eps, momentum, g_pm, gm, w_dp, mean, invstd, var_unbiased, gd,
+                                     running_mean, running_var, num_batches_tracked, phase, sums, (double *)workspace, stream))
+            return st;
+        if (phase == 1) return launch_status("amc3d_local_aggregation_forward");
     }
     const int ct = cout < LAGG_CT ? cout : LAGG_CT;
     // centroids per wave: 8, fewer where that leaves the chip with under ~2 workgroups per CU (the coarse stages)
@@ -876,7 +1001,7 @@ AMC_API int amc3d_local_aggregation_forward(int b, int cout, int n, int npoints,
                                             float *running_var, long long *num_batches_tracked, int phase, double *sums,
                                             void *workspace, size_t workspace_bytes, void *stream_)
 {
-    return local_aggregation_forward_impl(b, cout, n, npoints, nsample, training, relu, eps, momentum, g_cm, idx, dp, WDp{w_dp, 3}, moments, gamma,
+    return local_aggregation_forward_impl(b, cout, n, npoints, nsample, training, relu, eps, momentum, g_cm, false, idx, dp, WDp{w_dp, 3}, moments, gamma,
         beta, g_pm, pooled, arg, ystar, mean, invstd, var_unbiased, gd, running_mean, running_var,
         num_batches_tracked, phase, sums, workspace, workspace_bytes, stream_);
 }
@@ -894,9 +1019,25 @@ AMC_API int amc3d_local_aggregation_forward_strided(int b, int cout, int n, int 
                                                     void *workspace, size_t workspace_bytes, void *stream_)
 {
     if (ldw < 3) return bad_arg("amc3d_local_aggregation_forward_strided: row stride below 3");
-    return local_aggregation_forward_impl(b, cout, n, npoints, nsample, training, relu, eps, momentum, g_cm, idx, dp, WDp{w_dp, ldw}, moments,
+    return local_aggregation_forward_impl(b, cout, n, npoints, nsample, training, relu, eps, momentum, g_cm, false, idx, dp, WDp{w_dp, ldw}, moments,
         gamma, beta, g_pm, pooled, arg, ystar, mean, invstd, var_unbiased, gd, running_mean, running_var,
         num_batches_tracked, phase, sums, workspace, workspace_bytes, stream_);
+}
+
+// the strided form with G handed over as rows: g_pm (b,n,cout), 16-byte aligned, is an INPUT (amc3d_pointwise_conv_forward_rows
+// writes it) and there is no channel-major G.  training == 0 launches the max-pool alone.
+AMC_API int amc3d_local_aggregation_forward_rows(int b, int cout, int n, int npoints, int nsample, int training, int relu,
+                                                 float eps, float momentum, const float *g_pm, const int *idx, const float *dp,
+                                                 const float *w_dp, long ldw, const void *moments, const float *gamma,
+                                                 const float *beta, float *pooled, unsigned char *arg, float *ystar, float *mean,
+                                                 float *invstd, float *var_unbiased, double *gd, float *running_mean,
+                                                 float *running_var, long long *num_batches_tracked, int phase, double *sums,
+                                                 void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (ldw < 3) return bad_arg("amc3d_local_aggregation_forward_rows: row stride below 3");
+    return local_aggregation_forward_impl(b, cout, n, npoints, nsample, training, relu, eps, momentum, nullptr, true, idx, dp,
+        WDp{w_dp, ldw}, moments, gamma, beta, const_cast<float *>(g_pm), pooled, arg, ystar, mean, invstd, var_unbiased, gd,
+        running_mean, running_var, num_batches_tracked, phase, sums, workspace, workspace_bytes, stream_);
 }
 
 // dg_cm (b,cout,n): gradient w.r.t. G = W_f . f (the caller runs the pointwise conv's backward on it);
@@ -916,7 +1057,7 @@ static int local_aggregation_backward_impl(int b, int cout, int n, int npoints, 
     const bool lists = rev_start != nullptr;
     if (phase != 0 && (!dsums || (phase == 2 && !count_dev))) return bad_arg("amc3d_local_aggregation_backward: phase 1 / 2 need dsums (and the count)");
     if (!lagg_supported(cout, nsample) || n <= 0 || !dpooled || !ystar || !arg || !g_pm || !idx || !dp || !w_dp || !moments || !gd ||
-        !mean || !invstd || !gamma || !beta || !dg_cm || !dw_dp || !dgamma || !dbeta || !workspace || (lists && !rev_edge) ||
+        !mean || !invstd || !gamma || !beta || !dg_cm || !dw_dp || !dgamma || !dbeta || !workspace || (((uintptr_t)workspace | (uintptr_t)g_pm) & 15) || (lists && !rev_edge) ||
         workspace_bytes < (lists ? amc3d_local_aggregation_csr_workspace_bytes(b, cout, n, npoints)
                                  : amc3d_local_aggregation_workspace_bytes(b, cout, n, npoints)) ||
         (lists && ((long)b * n * cout >= (1L << 39) || (long)npoints * nsample >= (1L << 31))))
@@ -953,12 +1094,11 @@ static int local_aggregation_backward_impl(int b, int cout, int n, int npoints, 
                                (float *)nullptr, (unsigned char *)nullptr);
         }
     }
-    hipLaunchKernelGGL(lagg_bwd_finalize_kernel, dim3(cout), dim3(256), 0, stream, cout, nparts_b * b,
+    hipLaunchKernelGGL(lagg_bwd_finalize_kernel, dim3(cout), dim3(LAGG_FT), 0, stream, cout, nparts_b * b,
                        (double)b * (double)npoints * (double)nsample, partial, gm.mom, gd, w_dp, mean, invstd,
                        gamma, dgamma, dbeta, dw_dp, lddw, coef, phase, dsums, count_dev);
     if (phase == 1) return launch_status("amc3d_local_aggregation_backward");
-    hipLaunchKernelGGL(lagg_bwd_apply_kernel, dim3(div_up(n, LAGG_NT), div_up(cout, 64), b), dim3(256), 0, stream, cout, n,
-                       (const float *)Q, g_pm, gm, w_dp, (const float *)coef, dg_cm);
+    lagg_apply(b, cout, n, Q, g_pm, gm, w_dp, coef, dg_cm, stream);
     return launch_status("amc3d_local_aggregation_backward");
 }
 
@@ -1032,7 +1172,7 @@ AMC_API int amc3d_grouped_conv_bn_supported(int cout, int nsample) { return lagg
 
 // x1 (b,cout,npoints,32) = [relu](bn(G[idx] + W_dp . dp)); other arguments as amc3d_local_aggregation_forward
 static int grouped_conv_bn_forward_impl(int b, int cout, int n, int npoints, int nsample, int training,
-                                            int relu, float eps, float momentum, const float *g_cm,
+                                            int relu, float eps, float momentum, const float *g_cm, bool rows,
                                             const int *idx, const float *dp, WDp w_dp, const void *moments,
                                             const float *gamma, const float *beta, float *g_pm, float *x1,
                                             float *mean, float *invstd, float *var_unbiased, double *gd,
@@ -1043,26 +1183,22 @@ static int grouped_conv_bn_forward_impl(int b, int cout, int n, int npoints, int
 {
     if (training && phase != 0 && !sums) return bad_arg("amc3d_grouped_conv_bn_forward: phase 1 / 2 need the sums buffer");
     if (b <= 0 || npoints <= 0) return 0;
-    if (!lagg_expand_supported(cout, nsample) || n <= 0 || !g_cm || !idx || !dp || !w_dp || !gamma || !beta || !g_pm || !x1 ||
-        !mean || !invstd || (training && (!moments || !var_unbiased || !gd || !workspace ||
+    if (!lagg_expand_supported(cout, nsample) || n <= 0 || (!rows && !g_cm) || !idx || !dp || !w_dp || !gamma || !beta || !g_pm ||
+        ((uintptr_t)g_pm & 15) || !x1 || !mean || !invstd || (training && (!moments || !var_unbiased || !gd || !workspace ||
         workspace_bytes < amc3d_local_aggregation_workspace_bytes(b, cout, n, npoints))) ||
         (running_mean && (!running_var || !num_batches_tracked)))
-        return bad_arg("amc3d_grouped_conv_bn_forward: unsupported shape, null pointer or workspace too small");
+        return bad_arg("amc3d_grouped_conv_bn_forward: unsupported shape, null or misaligned pointer or workspace too small");
     hipStream_t stream = (hipStream_t)stream_;
     LaggMoments gm{};
     if (moments) gm = lagg_views(moments, b, n);
-    const int stiles = lagg_stats_tiles(b, cout, n);
-    const int nparts_b = div_up(div_up(n, LAGG_NT), stiles);
+    // the entries that take G channel-major: its rows first (phase 2 finds them where phase 1 left them)
+    if (!rows && !(training && phase == 2))
+        if (int st = amc3d_transpose_cn(b, cout, n, g_cm, g_pm, stream_)) return st;
     if (training) {
-        if (phase != 2)
-            hipLaunchKernelGGL(lagg_stats_kernel, dim3(nparts_b, div_up(cout, 64), b), dim3(256), 0, stream, cout, n, g_cm, g_pm, gm,
-                               (double *)workspace, nparts_b, stiles);
-        hipLaunchKernelGGL(lagg_stats_finalize_kernel, dim3(cout), dim3(256), 0, stream, cout, nparts_b * b,
-                           (double)b * (double)npoints * (double)nsample, eps, momentum, (const double *)workspace, gm.mom, w_dp,
-                           mean, invstd, var_unbiased, gd, running_mean, running_var, num_batches_tracked, phase, sums);
+        if (int st = lagg_statistics(b, cout, n, npoints, nsample, eps, momentum, g_pm, gm, w_dp, mean, invstd, var_unbiased, gd,
+                                     running_mean, running_var, num_batches_tracked, phase, sums, (double *)workspace, stream))
+            return st;
         if (phase == 1) return launch_status("amc3d_grouped_conv_bn_forward");
-    } else if (int st = amc3d_transpose_cn(b, cout, n, g_cm, g_pm, stream_)) {
-        return st;
     }
     const long P = (long)npoints * nsample;
     const int ct = cout < LAGG_XC ? cout : LAGG_XC;
@@ -1081,7 +1217,7 @@ AMC_API int amc3d_grouped_conv_bn_forward(int b, int cout, int n, int npoints, i
                                           float *running_var, long long *num_batches_tracked, int phase, double *sums,
                                           void *workspace, size_t workspace_bytes, void *stream_)
 {
-    return grouped_conv_bn_forward_impl(b, cout, n, npoints, nsample, training, relu, eps, momentum, g_cm, idx, dp, WDp{w_dp, 3}, moments, gamma,
+    return grouped_conv_bn_forward_impl(b, cout, n, npoints, nsample, training, relu, eps, momentum, g_cm, false, idx, dp, WDp{w_dp, 3}, moments, gamma,
         beta, g_pm, x1, mean, invstd, var_unbiased, gd, running_mean, running_var, num_batches_tracked, phase,
         sums, workspace, workspace_bytes, stream_);
 }
@@ -1098,9 +1234,25 @@ AMC_API int amc3d_grouped_conv_bn_forward_strided(int b, int cout, int n, int np
                                                   void *stream_)
 {
     if (ldw < 3) return bad_arg("amc3d_grouped_conv_bn_forward_strided: row stride below 3");
-    return grouped_conv_bn_forward_impl(b, cout, n, npoints, nsample, training, relu, eps, momentum, g_cm, idx, dp, WDp{w_dp, ldw}, moments,
+    return grouped_conv_bn_forward_impl(b, cout, n, npoints, nsample, training, relu, eps, momentum, g_cm, false, idx, dp, WDp{w_dp, ldw}, moments,
         gamma, beta, g_pm, x1, mean, invstd, var_unbiased, gd, running_mean, running_var, num_batches_tracked,
         phase, sums, workspace, workspace_bytes, stream_);
+}
+
+// the strided form with G handed over as rows: g_pm (b,n,cout), 16-byte aligned, is an INPUT and there is no channel-major G.
+// training == 0 launches the expand kernel alone.
+AMC_API int amc3d_grouped_conv_bn_forward_rows(int b, int cout, int n, int npoints, int nsample, int training, int relu,
+                                               float eps, float momentum, const float *g_pm, const int *idx, const float *dp,
+                                               const float *w_dp, long ldw, const void *moments, const float *gamma,
+                                               const float *beta, float *x1, float *mean, float *invstd, float *var_unbiased,
+                                               double *gd, float *running_mean, float *running_var,
+                                               long long *num_batches_tracked, int phase, double *sums, void *workspace,
+                                               size_t workspace_bytes, void *stream_)
+{
+    if (ldw < 3) return bad_arg("amc3d_grouped_conv_bn_forward_rows: row stride below 3");
+    return grouped_conv_bn_forward_impl(b, cout, n, npoints, nsample, training, relu, eps, momentum, nullptr, true, idx, dp,
+        WDp{w_dp, ldw}, moments, gamma, beta, const_cast<float *>(g_pm), x1, mean, invstd, var_unbiased, gd, running_mean,
+        running_var, num_batches_tracked, phase, sums, workspace, workspace_bytes, stream_);
 }
 
 // from dx1 (b,cout,npoints,32): dg_cm (b,cout,n), dw_dp (cout,3), dgamma, dbeta
@@ -1116,7 +1268,7 @@ static int grouped_conv_bn_backward_impl(int b, int cout, int n, int npoints, in
     if (b <= 0 || npoints <= 0) return 0;
     if (phase != 0 && (!dsums || (phase == 2 && !count_dev))) return bad_arg("amc3d_grouped_conv_bn_backward: phase 1 / 2 need dsums (and the count)");
     if (!lagg_expand_supported(cout, nsample) || n <= 0 || !dx1 || !g_pm || !idx || !dp || !w_dp || !moments || !gd || !mean ||
-        !invstd || !gamma || !beta || !dg_cm || !dw_dp || !dgamma || !dbeta || !workspace ||
+        !invstd || !gamma || !beta || !dg_cm || !dw_dp || !dgamma || !dbeta || !workspace || (((uintptr_t)workspace | (uintptr_t)g_pm) & 15) ||
         workspace_bytes < amc3d_local_aggregation_workspace_bytes(b, cout, n, npoints))
         return bad_arg("amc3d_grouped_conv_bn_backward: unsupported shape, null pointer or workspace too small");
     hipStream_t stream = (hipStream_t)stream_;
@@ -1126,7 +1278,7 @@ static int grouped_conv_bn_backward_impl(int b, int cout, int n, int npoints, in
     float *coef = Q + (size_t)b * n * cout;
     const long P = (long)npoints * nsample;
     const int ct = cout < LAGG_XC ? cout : LAGG_XC;
-    const int ctiles = 2;  // tiles per workgroup (1, 2, 4 measured alike: the kernel runs at the float-atomic rate)
+    const int ctiles = LAGG_CTILES;
     const int nparts_b = div_up(div_up(P, LAGG_PT), ctiles);
     if (phase != 2) {
     if (int st = fill_i32((int *)Q, 0, (size_t)b * n * cout, stream)) return st;
@@ -1136,12 +1288,11 @@ static int grouped_conv_bn_backward_impl(int b, int cout, int n, int npoints, in
     switch (ct / 4) { case 2: AMC_COLLAPSE(2); break; case 4: AMC_COLLAPSE(4); break; case 8: AMC_COLLAPSE(8); break; default: AMC_COLLAPSE(16); }
 #undef AMC_COLLAPSE
     }
-    hipLaunchKernelGGL(lagg_bwd_finalize_kernel, dim3(cout), dim3(256), 0, stream, cout, nparts_b * b,
+    hipLaunchKernelGGL(lagg_bwd_finalize_kernel, dim3(cout), dim3(LAGG_FT), 0, stream, cout, nparts_b * b,
                        (double)b * (double)npoints * (double)nsample, partial, gm.mom, gd, w_dp, mean, invstd,
                        gamma, dgamma, dbeta, dw_dp, lddw, coef, phase, dsums, count_dev);
     if (phase == 1) return launch_status("amc3d_grouped_conv_bn_backward");
-    hipLaunchKernelGGL(lagg_bwd_apply_kernel, dim3(div_up(n, LAGG_NT), div_up(cout, 64), b), dim3(256), 0, stream, cout, n,
-                       (const float *)Q, g_pm, gm, w_dp, (const float *)coef, dg_cm);
+    lagg_apply(b, cout, n, Q, g_pm, gm, w_dp, coef, dg_cm, stream);
     return launch_status("amc3d_grouped_conv_bn_backward");
 }
 
@@ -1206,7 +1357,7 @@ static int grouped_conv_bn_backward_csr_impl(int b, int cout, int n, int npoints
     if (b <= 0 || npoints <= 0) return 0;
     if (phase != 0 && (!dsums || (phase == 2 && !count_dev))) return bad_arg("amc3d_grouped_conv_bn_backward_csr: phase 1 / 2 need dsums (and the count)");
     if (!lagg_expand_supported(cout, nsample) || n <= 0 || !dx1 || !g_pm || !rev_start || !rev_edge || !dp || !w_dp || !moments ||
-        !gd || !mean || !invstd || !gamma || !beta || !dg_cm || !dw_dp || !dgamma || !dbeta || !workspace ||
+        !gd || !mean || !invstd || !gamma || !beta || !dg_cm || !dw_dp || !dgamma || !dbeta || !workspace || (((uintptr_t)workspace | (uintptr_t)g_pm) & 15) ||
         workspace_bytes < amc3d_grouped_conv_bn_csr_workspace_bytes(b, cout, n, npoints, nsample))
         return bad_arg("amc3d_grouped_conv_bn_backward_csr: unsupported shape, null pointer or workspace too small");
     hipStream_t stream = (hipStream_t)stream_;
@@ -1231,12 +1382,11 @@ static int grouped_conv_bn_backward_csr_impl(int b, int cout, int n, int npoints
                                   gamma, beta, Q, partial, &nparts, stream))
             return st;
     }
-    hipLaunchKernelGGL(lagg_bwd_finalize_kernel, dim3(cout), dim3(256), 0, stream, cout, nparts,
+    hipLaunchKernelGGL(lagg_bwd_finalize_kernel, dim3(cout), dim3(LAGG_FT), 0, stream, cout, nparts,
                        (double)b * (double)npoints * (double)nsample, partial, gm.mom, gd, w_dp, mean, invstd,
                        gamma, dgamma, dbeta, dw_dp, lddw, coef, phase, dsums, count_dev);
     if (phase == 1) return launch_status("amc3d_grouped_conv_bn_backward_csr");
-    hipLaunchKernelGGL(lagg_bwd_apply_kernel, dim3(div_up(n, LAGG_NT), div_up(cout, 64), b), dim3(256), 0, stream, cout, n,
-                       (const float *)Q, g_pm, gm, w_dp, (const float *)coef, dg_cm);
+    lagg_apply(b, cout, n, Q, g_pm, gm, w_dp, coef, dg_cm, stream);
     return launch_status("amc3d_grouped_conv_bn_backward_csr");
 }
 

@@ -337,7 +337,7 @@ static void launch_pw_wgrad(const PwSplit &s, int M, int K, long P, const float 
 // gemm.hip: the MFMA-bound variant for layers with >= 64 channels on both sides
 bool gemm_conv_pays(int cin, int cout);
 int gemm_conv_forward(int b, int cin, int cout, long P, const float *x, const float *w, long ldw, const float *bias, float *y,
-                      float *partial, hipStream_t stream);
+                      int y_pm, float *partial, hipStream_t stream);
 bool gemm_conv_short(int b, int rows, long P);
 // the 128 x 128-tile GEMM (gemm.hip) instead of the streaming kernel above: deep layers without a bias, and -- with or without
 // one -- deep layers so short that the streaming kernel's one-workgroup-per-tile walk of the whole K axis leaves the chip empty
@@ -359,17 +359,18 @@ int gemm_conv_backward_weight(int b, int cin, int cout, long P, const float *x, 
 using namespace amc;
 
 // forward with a row stride for the weight (ldw >= cin): a column block of a wider matrix is an operand where it lies
+// y_pm != 0: y as (b,P,cout) rows, no bias -- the same route, accumulators and sums as the channel-major form
 static int pw_forward(const char *what, int b, int cin, int cout, long P, const float *x, const float *weight, long ldw,
-                      const float *bias, float *y, void *workspace, size_t workspace_bytes, hipStream_t stream)
+                      const float *bias, float *y, void *workspace, size_t workspace_bytes, hipStream_t stream, int y_pm = 0)
 {
     if (b <= 0 || P <= 0 || cout <= 0) return 0;
-    if (cin <= 0 || !x || !weight || !y || ldw < cin) return bad_arg(what);
+    if (cin <= 0 || !x || !weight || !y || ldw < cin || (y_pm && bias)) return bad_arg(what);
     if (pw_forward_deep(b, cin, cout, P, bias != nullptr)) {
         const size_t need = gemm_conv_forward_workspace_bytes(b, cin, cout, P);
-        return gemm_conv_forward(b, cin, cout, P, x, weight, ldw, bias, y,
+        return gemm_conv_forward(b, cin, cout, P, x, weight, ldw, bias, y, y_pm,
                                  (need && workspace && workspace_bytes >= need) ? (float *)workspace : nullptr, stream);
     }
-    pw_gemm(b, cout, cin, P, weight, ldw, 1, bias, x, y, 0, stream);
+    pw_gemm(b, cout, cin, P, weight, ldw, 1, bias, x, y, y_pm, stream);
     return launch_status(what);
 }
 
@@ -412,6 +413,21 @@ AMC_API int amc3d_pointwise_conv_forward_strided(int b, int cin, int cout, long 
     }
     return pw_forward("amc3d_pointwise_conv_forward_strided: bad argument", b, cin, cout, P, x, weight, ldw, bias, y, workspace,
                       workspace_bytes, (hipStream_t)stream);
+}
+
+// the strided form without a bias, y written as position-major rows (b,P,cout): what the neighbourhood layers gather from
+// (amc3d_local_aggregation_forward_rows, amc3d_grouped_conv_bn_forward_rows).  Equal to the channel-major output transposed, bit
+// for bit.  Workspace: amc3d_pointwise_conv_forward_workspace_bytes(b, cin, cout, P, 0).  A y that is not 16-byte aligned, or
+// cout % 4 != 0, takes 4-byte stores.
+AMC_API int amc3d_pointwise_conv_forward_rows(int b, int cin, int cout, long P, const float *x, const float *weight, long ldw,
+                                              float *y_pm, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (b > 0 && P > 0 && cin > 0 && cout > 0) {
+        const size_t need = amc3d_pointwise_conv_forward_workspace_bytes(b, cin, cout, P, 0);
+        if (need && (!workspace || workspace_bytes < need)) return bad_arg("amc3d_pointwise_conv_forward_rows: workspace too small");
+    }
+    return pw_forward("amc3d_pointwise_conv_forward_rows: bad argument", b, cin, cout, P, x, weight, ldw, nullptr, y_pm, workspace,
+                      workspace_bytes, (hipStream_t)stream, 1);
 }
 
 AMC_API size_t amc3d_pointwise_conv_workspace_bytes(int b, int cin, int cout, long P)

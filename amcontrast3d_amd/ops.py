@@ -132,6 +132,15 @@ def _pw_forward(lib, bf16, B, Cin, Cout, P, x, w2, bias, y, what="pointwise_conv
     _lib.check(_pw(lib, bf16)[0](B, Cin, Cout, P, _ptr(x), _ptr(w2), bptr, _ptr(y), _stream(x)), what)
 
 
+def _pw_forward_rows(lib, B, Cin, Cout, P, x, w2, y_pm, what="pointwise_conv_forward"):
+    """y_pm (B,P,Cout) = (w2 . x) as position-major rows, fp32, no bias: the conv of a neighbourhood layer on its source
+    points, stored the way the layer gathers it (the same bits as _pw_forward's output, transposed)"""
+    wsf = int(lib.amc3d_pointwise_conv_forward_workspace_bytes(B, Cin, Cout, P, 0))
+    work = torch.empty(wsf, dtype=torch.uint8, device=x.device) if wsf else None
+    _lib.check(lib.amc3d_pointwise_conv_forward_rows(B, Cin, Cout, P, _ptr(x), _ptr(w2), _ld(w2), _ptr(y_pm),
+                                                     _ptr(work) if wsf else None, wsf, _stream(x)), what)
+
+
 def _ld(w2):
     """row stride of a (rows, cols) weight view with unit column stride (one row: no stride to speak of)"""
     return w2.stride(0) if w2.shape[0] > 1 else w2.shape[1]
@@ -1543,7 +1552,8 @@ class LocalAggregationFused(Function):
         ctx.bf16 = mixed_precision() and min(Cin, C) >= 64 and B * N >= 4096  # the conv on the source points on the bf16 MFMA
         w2 = weight.detach().reshape(C, Cin + 3).contiguous()
         w_dp, ldw, w_f = _dp_f_blocks(w2, ctx.bf16)
-        g_cm = torch.empty(B, C, N, dtype=torch.float32, device=dev)
+        # fp32: the conv writes G as the rows the layer gathers; the bf16-compute conv writes it channel-major and the layer turns it
+        g_cm = torch.empty(B, C, N, dtype=torch.float32, device=dev) if ctx.bf16 else None
         g_pm = torch.empty(B, N, C, dtype=torch.float32, device=dev)
         pooled = torch.empty(B, C, M, dtype=torch.float32, device=dev)
         ystar = torch.empty_like(pooled)
@@ -1556,6 +1566,13 @@ class LocalAggregationFused(Function):
         mom, rm, rv, nbt = _bn_running_args(bn)
 
         def call(phase):
+            if g_cm is None:
+                _lib.check(lib.amc3d_local_aggregation_forward_rows(
+                    B, C, N, M, K, 1, int(bool(relu)), float(eps), mom, _ptr(g_pm), _ptr(idx), _ptr(dp), _ptr(w_dp), ldw,
+                    _ptr(moments), _ptr(gamma), _ptr(beta), _ptr(pooled), _ptr(arg), _ptr(ystar), _ptr(mean), _ptr(invstd),
+                    _ptr(var_u), _ptr(gd), rm, rv, nbt, phase, _ptr(sums), _ptr(work), wb, _stream(f)),
+                    "local_aggregation_forward")
+                return
             _lib.check(lib.amc3d_local_aggregation_forward_strided(
                 B, C, N, M, K, 1, int(bool(relu)), float(eps), mom, _ptr(g_cm), _ptr(idx), _ptr(dp), _ptr(w_dp), ldw,
                 _ptr(moments), _ptr(gamma), _ptr(beta), _ptr(g_pm), _ptr(pooled), _ptr(arg), _ptr(ystar), _ptr(mean),
@@ -1564,10 +1581,14 @@ class LocalAggregationFused(Function):
 
         with torch.cuda.device(dev):
             with timing.span("pointwise_conv_forward", 4 * B * N * (Cin + C), 2.0 * B * N * Cin * C):
-                _pw_forward(lib, ctx.bf16, B, Cin, C, N, f, w_f, None, g_cm)
-            # algorithmic bytes: G read (statistics) + the gathered rows, idx, dp + the pooled outputs
+                if g_cm is None:
+                    _pw_forward_rows(lib, B, Cin, C, N, f, w_f, g_pm)
+                else:
+                    _pw_forward(lib, True, B, Cin, C, N, f, w_f, None, g_cm)
+            # algorithmic bytes: G read (statistics) + the gathered rows, idx, dp + the pooled outputs; a channel-major G is
+            # read once more and written as rows
             with timing.span("local_aggregation_forward", 4 * B * N * C + 16 * B * M * K + 5 * B * M * C,
-                             moved=8 * B * N * C + B * M * K * (4 * C + 16) + 9 * B * M * C):
+                             moved=(4 if g_cm is None else 12) * B * N * C + B * M * K * (4 * C + 16) + 9 * B * M * C):
                 if group is None:
                     call(0)
                 else:
@@ -1664,7 +1685,7 @@ class GroupedConvBN(Function):
         ctx.bf16 = mixed_precision() and min(Cin, C) >= 64 and B * N >= 4096
         w2 = weight.detach().reshape(C, Cin + 3).contiguous()
         w_dp, ldw, w_f = _dp_f_blocks(w2, ctx.bf16)
-        g_cm = torch.empty(B, C, N, dtype=torch.float32, device=dev)
+        g_cm = torch.empty(B, C, N, dtype=torch.float32, device=dev) if ctx.bf16 else None  # (as LocalAggregationFused)
         g_pm = torch.empty(B, N, C, dtype=torch.float32, device=dev)
         x1 = torch.empty(B, C, M, K, dtype=torch.float32, device=dev)
         mean, invstd, var_u = _bn_stat_bufs(C, dev)
@@ -1675,6 +1696,12 @@ class GroupedConvBN(Function):
         mom, rm, rv, nbt = _bn_running_args(bn)
 
         def call(phase):
+            if g_cm is None:
+                _lib.check(lib.amc3d_grouped_conv_bn_forward_rows(
+                    B, C, N, M, K, 1, int(bool(relu)), float(eps), mom, _ptr(g_pm), _ptr(idx), _ptr(dp), _ptr(w_dp), ldw,
+                    _ptr(moments), _ptr(gamma), _ptr(beta), _ptr(x1), _ptr(mean), _ptr(invstd), _ptr(var_u), _ptr(gd), rm, rv,
+                    nbt, phase, _ptr(sums), _ptr(work), wb, _stream(f)), "grouped_conv_bn_forward")
+                return
             _lib.check(lib.amc3d_grouped_conv_bn_forward_strided(
                 B, C, N, M, K, 1, int(bool(relu)), float(eps), mom, _ptr(g_cm), _ptr(idx), _ptr(dp), _ptr(w_dp), ldw,
                 _ptr(moments), _ptr(gamma), _ptr(beta), _ptr(g_pm), _ptr(x1), _ptr(mean), _ptr(invstd), _ptr(var_u),
@@ -1682,8 +1709,12 @@ class GroupedConvBN(Function):
 
         with torch.cuda.device(dev):
             with timing.span("pointwise_conv_forward", 4 * B * N * (Cin + C), 2.0 * B * N * Cin * C):
-                _pw_forward(lib, ctx.bf16, B, Cin, C, N, f, w_f, None, g_cm)
-            with timing.span("grouped_conv_bn_forward", 4 * B * N * C + B * M * K * (4 * C + 16), moved=8 * B * N * C + B * M * K * (8 * C + 16)):
+                if g_cm is None:
+                    _pw_forward_rows(lib, B, Cin, C, N, f, w_f, g_pm)
+                else:
+                    _pw_forward(lib, True, B, Cin, C, N, f, w_f, None, g_cm)
+            with timing.span("grouped_conv_bn_forward", 4 * B * N * C + B * M * K * (4 * C + 16),
+                             moved=(4 if g_cm is None else 12) * B * N * C + B * M * K * (8 * C + 16)):
                 if group is None:
                     call(0)
                 else:
@@ -1767,15 +1798,14 @@ def grouped_conv_bn_eval(f, dp, idx, weight, bn, relu):
     lib = _lib.load()
     w2 = weight.detach().reshape(C, Cin + 3).contiguous()
     w_dp, ldw, w_f = _dp_f_blocks(w2, False)
-    g_cm = torch.empty(B, C, N, dtype=torch.float32, device=dev)
     g_pm = torch.empty(B, N, C, dtype=torch.float32, device=dev)
     x1 = torch.empty(B, C, M, K, dtype=torch.float32, device=dev)
     invstd = torch.rsqrt(bn.running_var + bn.eps)
     with torch.cuda.device(dev):
-        _pw_forward(lib, False, B, Cin, C, N, f, w_f, None, g_cm)
-        _lib.check(lib.amc3d_grouped_conv_bn_forward_strided(
-            B, C, N, M, K, 0, int(bool(relu)), float(bn.eps), 0.0, _ptr(g_cm), _ptr(idx), _ptr(dp), _ptr(w_dp), ldw, None,
-            _ptr(bn.weight), _ptr(bn.bias), _ptr(g_pm), _ptr(x1), _ptr(bn.running_mean), _ptr(invstd), None, None, None,
+        _pw_forward_rows(lib, B, Cin, C, N, f, w_f, g_pm)
+        _lib.check(lib.amc3d_grouped_conv_bn_forward_rows(
+            B, C, N, M, K, 0, int(bool(relu)), float(bn.eps), 0.0, _ptr(g_pm), _ptr(idx), _ptr(dp), _ptr(w_dp), ldw, None,
+            _ptr(bn.weight), _ptr(bn.bias), _ptr(x1), _ptr(bn.running_mean), _ptr(invstd), None, None, None,
             None, None, 0, None, None, 0, _stream(f)), "grouped_conv_bn_forward")
     return x1
 
@@ -1795,17 +1825,16 @@ def local_aggregation_eval(f, dp, idx, weight, bn, relu):
     lib = _lib.load()
     w2 = weight.detach().reshape(C, Cin + 3).contiguous()
     w_dp, ldw, w_f = _dp_f_blocks(w2, False)
-    g_cm = torch.empty(B, C, N, dtype=torch.float32, device=dev)
     g_pm = torch.empty(B, N, C, dtype=torch.float32, device=dev)
     pooled = torch.empty(B, C, M, dtype=torch.float32, device=dev)
     ystar = torch.empty_like(pooled)
     arg = torch.empty(B, C, M, dtype=torch.uint8, device=dev)
     invstd = torch.rsqrt(bn.running_var + bn.eps)
     with torch.cuda.device(dev):
-        _pw_forward(lib, False, B, Cin, C, N, f, w_f, None, g_cm)
-        _lib.check(lib.amc3d_local_aggregation_forward_strided(
-            B, C, N, M, K, 0, int(bool(relu)), float(bn.eps), 0.0, _ptr(g_cm), _ptr(idx), _ptr(dp), _ptr(w_dp), ldw, None,
-            _ptr(bn.weight), _ptr(bn.bias), _ptr(g_pm), _ptr(pooled), _ptr(arg), _ptr(ystar), _ptr(bn.running_mean),
+        _pw_forward_rows(lib, B, Cin, C, N, f, w_f, g_pm)
+        _lib.check(lib.amc3d_local_aggregation_forward_rows(
+            B, C, N, M, K, 0, int(bool(relu)), float(bn.eps), 0.0, _ptr(g_pm), _ptr(idx), _ptr(dp), _ptr(w_dp), ldw, None,
+            _ptr(bn.weight), _ptr(bn.bias), _ptr(pooled), _ptr(arg), _ptr(ystar), _ptr(bn.running_mean),
             _ptr(invstd), None, None, None, None, None, 0, None, None, 0, _stream(f)), "local_aggregation_forward")
     return pooled
 

@@ -430,6 +430,13 @@ int amc3d_pointwise_conv_forward_strided(int b, int cin, int cout, long P, const
 int amc3d_pointwise_conv_backward_strided(int b, int cin, int cout, long P, const float *x, const float *weight, long ldw,
                                           const float *dy, float *dx, int dx_position_major, float *dweight, long lddw,
                                           void *workspace, size_t workspace_bytes, void *stream);
+/* The strided forward without a bias, y_pm written as position-major rows (b,P,cout): the layout the neighbourhood layers
+ * gather from (amc3d_local_aggregation_forward_rows, amc3d_grouped_conv_bn_forward_rows).  Same route, accumulators and sums
+ * as amc3d_pointwise_conv_forward_strided: y_pm equals its output transposed, bit for bit.  A lane stores four consecutive
+ * channels of its position as 16 bytes (y_pm 16-byte aligned and cout % 4 == 0), as four 4-byte stores otherwise.
+ * workspace: amc3d_pointwise_conv_forward_workspace_bytes(b, cin, cout, P, 0) bytes. */
+int amc3d_pointwise_conv_forward_rows(int b, int cin, int cout, long P, const float *x, const float *weight, long ldw,
+                                      float *y_pm, void *workspace, size_t workspace_bytes, void *stream);
 
 /* a weight matrix cut into two column blocks / two gradient blocks joined (the [W_dp | W_f] weight of a neighbourhood layer,
  * the [W_skip | W_up] weight of a FeaturePropagation conv): w (rows, c1 + c2) <-> a (rows, c1), b (rows, c2), one launch */
@@ -613,6 +620,28 @@ int amc3d_grouped_conv_bn_forward_strided(int b, int cout, int n, int npoints, i
                                           float *running_mean, float *running_var, long long *num_batches_tracked,
                                           int phase, double *sums, void *workspace, size_t workspace_bytes,
                                           void *stream);
+/* The two strided forwards with G = W_f . f handed over as rows: g_pm (b,n,cout), 16-byte aligned, is an INPUT (written by
+ * amc3d_pointwise_conv_forward_rows) and no channel-major G exists.  The statistics read the rows; their partial sums are taken
+ * over a fixed partition of the b*n points in a fixed order (the same bits on every run).  training == 0 launches nothing but
+ * the max-pool / expand kernel.  The forms that take g_cm are amc3d_transpose_cn followed by these. */
+int amc3d_local_aggregation_forward_rows(int b, int cout, int n, int npoints, int nsample, int training, int relu,
+                                         float eps, float momentum, const float *g_pm, const int *idx, const float *dp,
+                                         const float *w_dp, long ldw, const void *moments, const float *gamma,
+                                         const float *beta, float *pooled, unsigned char *arg, float *ystar, float *mean,
+                                         float *invstd, float *var_unbiased, double *gd, float *running_mean,
+                                         float *running_var, long long *num_batches_tracked, int phase, double *sums,
+                                         void *workspace, size_t workspace_bytes, void *stream);
+int amc3d_grouped_conv_bn_forward_rows(int b, int cout, int n, int npoints, int nsample, int training, int relu,
+                                       float eps, float momentum, const float *g_pm, const int *idx, const float *dp,
+                                       const float *w_dp, long ldw, const void *moments, const float *gamma,
+                                       const float *beta, float *x1, float *mean, float *invstd, float *var_unbiased,
+                                       double *gd, float *running_mean, float *running_var,
+                                       long long *num_batches_tracked, int phase, double *sums, void *workspace,
+                                       size_t workspace_bytes, void *stream);
+/* how many partial records per channel each producer leaves for the finalize kernels at this shape (a fixed function of the
+ * shape): counts[0] the forward statistics, [1] the pooled layer's backward scatter, [2] the atomic collapse of
+ * amc3d_grouped_conv_bn_backward, [3] its reverse-list collapse.  counts: 4 ints on the host. */
+int amc3d_local_aggregation_partial_counts(int b, int cout, int n, int npoints, int nsample, int *counts);
 int amc3d_grouped_conv_bn_backward_strided(int b, int cout, int n, int npoints, int nsample, int relu,
                                            const float *dx1, const float *g_pm, const int *idx, const float *dp,
                                            const float *w_dp, long ldw, const void *moments, const double *gd,
