@@ -1597,6 +1597,241 @@ __global__ __launch_bounds__(CE_THREADS) void ce_general_backward_kernel(int C, 
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The rest of openpoints.loss (loss/build.py:14-257) as two form-generic families on the same layout as ce_general_*: one
+// thread per point, class planes read coalesced along N, any C >= 1, expf / logf / powf, per-point terms in fp32 combined
+// and summed in fp64 in the fixed order of the kernels above (wave shuffle tree, the block's waves in order, pl_finalize_kernel
+// over the blocks' partials).  No atomics and nothing zero-filled.  A class is a handful of run-time numbers (PlSoftmax /
+// PlSigmoid), filled in by the C entry points from the arguments include/amc3d.h documents.
+// ---------------------------------------------------------------------------------------------
+enum { PL_DEN_COUNT = 0, PL_DEN_WSUM = 1, PL_DEN_ONE = 2 };
+
+struct PlSoftmax {
+    const long long *remap;  // label -> class table of remap_len entries, or null
+    int remap_len;
+    long long ignore;
+    int has_ignore;
+    const int *mask;         // (B,N): a point counts iff its entry == 1, or null
+    const float *weight;     // (C) or null
+    int weight_per_class;    // 1: w[c] inside the sum over the classes; 0: w[y] on the whole term
+    float a_hot, a_off;      // the target distribution: q[y] = a_hot, q[c != y] = a_off
+    float gamma;             // focal exponent of the detached (1 - p[y]); 0: none
+    const float *alpha;      // (C) focal alpha table or null
+    float poly;              // + poly * (1 - p[y]), attached
+    int den_mode;
+};
+
+// the class of point (b, n) after the ignore test, the mask and the remap; -1: the point is left out
+__device__ inline int pl_class(const PlSoftmax &f, int C, long long t, size_t at)
+{
+    if (f.has_ignore && t == f.ignore) return -1;
+    if (f.mask && f.mask[at] != 1) return -1;
+    if (f.remap) {
+        if (t < 0 || t >= f.remap_len) return -1;
+        t = f.remap[t];
+    }
+    return (t >= 0 && t < C) ? (int)t : -1;
+}
+
+// block sum of (num, den) in the fixed order -> partial[2 * block]
+__device__ inline void pl_block_sum(double num, double den, double *__restrict__ partial)
+{
+    __shared__ double s_num[CE_THREADS / 64], s_den[CE_THREADS / 64];
+    for (int s = 32; s >= 1; s >>= 1) {
+        num += __shfl_xor(num, s, 64);
+        den += __shfl_xor(den, s, 64);
+    }
+    if ((threadIdx.x & 63) == 0) { s_num[threadIdx.x >> 6] = num; s_den[threadIdx.x >> 6] = den; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0, d = 0.0;
+        for (int w = 0; w < CE_THREADS / 64; ++w) { t += s_num[w]; d += s_den[w]; }
+        const size_t slot = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+        partial[slot * 2] = t;
+        partial[slot * 2 + 1] = d;
+    }
+}
+
+// out[0] = sum / den, out[1] = den; den = the summed denominators, or 1 for reduction 'sum' (0/0 = NaN, as torch's mean over nothing)
+__global__ __launch_bounds__(1024) void pl_finalize_kernel(int nparts, const double *__restrict__ partial, int den_mode,
+                                                           float *__restrict__ out)
+{
+    __shared__ double s_sum[16], s_den[16];
+    double t = 0.0, c = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += 1024) { t += partial[(size_t)i * 2]; c += partial[(size_t)i * 2 + 1]; }
+    for (int s = 32; s >= 1; s >>= 1) {
+        t += __shfl_xor(t, s, 64);
+        c += __shfl_xor(c, s, 64);
+    }
+    if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6] = t; s_den[threadIdx.x >> 6] = c; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tt = 0.0, cc = 0.0;
+        for (int w = 0; w < 16; ++w) { tt += s_sum[w]; cc += s_den[w]; }
+        if (den_mode == PL_DEN_ONE) cc = 1.0;
+        out[0] = (float)(tt / cc);
+        out[1] = (float)cc;
+    }
+}
+
+// Softmax family.  With y the point's class (pl_class), Q[c] = q[c] * (weight_per_class ? w[c] : 1) and
+// m = (weight_per_class ? 1 : w[y]) * alpha[y] * (1 - p[y])^gamma:   term = m * sum_c Q[c] (-lp[c]) + poly * (1 - p[y])
+__global__ __launch_bounds__(CE_THREADS) void pl_softmax_forward_kernel(int C, long N, const float *__restrict__ logits,
+                                                                        const long long *__restrict__ target, PlSoftmax f,
+                                                                        float *__restrict__ lse, double *__restrict__ partial)
+{
+    const int b = blockIdx.y;
+    const long n = (long)blockIdx.x * CE_THREADS + threadIdx.x;
+    double num = 0.0, den = 0.0;
+    if (n < N) {
+        const size_t at = (size_t)b * N + n;
+        const float *x = logits + (size_t)b * C * N + n;
+        float mx = -__builtin_inff();
+        for (int c = 0; c < C; ++c) mx = fmaxf(mx, x[(size_t)c * N]);
+        float se = 0.f;
+        for (int c = 0; c < C; ++c) se += expf(x[(size_t)c * N] - mx);
+        const float l = mx + logf(se);
+        lse[at] = l;
+        const int y = pl_class(f, C, target[at], at);
+        if (y >= 0) {
+            const float wy = f.weight ? f.weight[y] : 1.f;
+            const float lpy = x[(size_t)y * N] - l;
+            float m = f.weight_per_class ? 1.f : wy;
+            if (f.alpha) m *= f.alpha[y];
+            if (f.gamma != 0.f) m *= powf(1.f - expf(lpy), f.gamma);
+            double term = (double)(f.a_hot - f.a_off) * (double)((f.weight_per_class ? wy : 1.f) * -lpy);
+            if (f.a_off != 0.f) {
+                float sm = 0.f;  // sum_c w[c] * (-lp[c])
+                for (int c = 0; c < C; ++c) {
+                    const float nlp = l - x[(size_t)c * N];
+                    sm += (f.weight && f.weight_per_class) ? f.weight[c] * nlp : nlp;
+                }
+                term += (double)f.a_off * (double)sm;
+            }
+            num = (double)m * term;
+            if (f.poly != 0.f) num += (double)f.poly * (double)(1.f - expf(lpy));
+            den = f.den_mode == PL_DEN_WSUM ? (double)wy : 1.0;
+        }
+    }
+    pl_block_sum(num, den, partial);
+}
+
+// dlogits[c] = g / den * [ m (p[c] sum_c Q - Q[c]) + poly p[y] (p[c] - [c == y]) ] for counted points ((1 - p[y])^gamma is a
+// constant: FocalLoss detaches pt), zero rows otherwise; den = loss_den[1]
+__global__ __launch_bounds__(CE_THREADS) void pl_softmax_backward_kernel(int C, long N, const float *__restrict__ logits,
+                                                                         const long long *__restrict__ target, PlSoftmax f,
+                                                                         const float *__restrict__ lse,
+                                                                         const float *__restrict__ loss_den,
+                                                                         const float *__restrict__ grad_out,
+                                                                         float *__restrict__ dlogits)
+{
+    const int b = blockIdx.y;
+    const long n = (long)blockIdx.x * CE_THREADS + threadIdx.x;
+    if (n >= N) return;
+    const size_t at = (size_t)b * N + n;
+    const float *x = logits + (size_t)b * C * N + n;
+    float *d = dlogits + (size_t)b * C * N + n;
+    const int y = pl_class(f, C, target[at], at);
+    if (y < 0) {
+        for (int c = 0; c < C; ++c) d[(size_t)c * N] = 0.f;
+        return;
+    }
+    const bool per_class = f.weight && f.weight_per_class;
+    const float l = lse[at];
+    const float wy = f.weight ? f.weight[y] : 1.f;
+    const float py = expf(x[(size_t)y * N] - l);
+    float m = f.weight_per_class ? 1.f : wy;
+    if (f.alpha) m *= f.alpha[y];
+    if (f.gamma != 0.f) m *= powf(1.f - py, f.gamma);
+    const float hot = (f.a_hot - f.a_off) * (per_class ? wy : 1.f);  // Q[y] - a_off w[y]
+    float sq = hot;
+    if (f.a_off != 0.f) {
+        float wsum = (float)C;
+        if (per_class) {
+            wsum = 0.f;
+            for (int c = 0; c < C; ++c) wsum += f.weight[c];
+        }
+        sq += f.a_off * wsum;
+    }
+    const float scale = grad_out[0] / loss_den[1];
+    const float pp = f.poly * py;
+    for (int c = 0; c < C; ++c) {
+        const float p = expf(x[(size_t)c * N] - l);
+        const float is_y = c == y ? 1.f : 0.f;
+        const float qc = f.a_off * (per_class ? f.weight[c] : 1.f) + is_y * hot;
+        d[(size_t)c * N] = scale * (m * (p * sq - qc) + pp * (p - is_y));
+    }
+}
+
+struct PlSigmoid {
+    const float *weight, *pos_weight;  // (C) or null: BCEWithLogitsLoss's, per class
+    float alpha;                       // >= 0: alpha_t = t ? alpha : 1 - alpha
+    float gamma, poly;
+    int den_mode;                      // PL_DEN_COUNT: the elements of the counted points; PL_DEN_ONE
+};
+
+// one element of the sigmoid family: logit x, one-hot target bit t.  z = t ? -x : x, u = sigmoid(z) = 1 - pt,
+// ce = softplus(z) = max(x,0) - x t + log1p(exp(-|x|)) = -log(pt):   value = a ce u^gamma + poly u^(gamma+1),
+// a = w[c] (t ? pos_weight[c] : 1) alpha_t;  *dx = d value / d x
+__device__ inline float pl_sigmoid_element(const PlSigmoid &f, int c, float x, bool t, float *dx)
+{
+    const float z = t ? -x : x;
+    const float e = expf(-fabsf(z));
+    const float ce = fmaxf(z, 0.f) + log1pf(e);
+    const float u = (z >= 0.f ? 1.f : e) / (1.f + e);
+    float a = f.weight ? f.weight[c] : 1.f;
+    if (t && f.pos_weight) a *= f.pos_weight[c];
+    if (f.alpha >= 0.f) a *= t ? f.alpha : 1.f - f.alpha;
+    const float ug = f.gamma != 0.f ? powf(u, f.gamma) : 1.f;
+    if (dx) {
+        const float dz = ug * (a * (u + ce * f.gamma * (1.f - u)) + f.poly * (f.gamma + 1.f) * u * (1.f - u));
+        *dx = t ? -dz : dz;
+    }
+    return a * ce * ug + f.poly * ug * u;
+}
+
+__global__ __launch_bounds__(CE_THREADS) void pl_sigmoid_forward_kernel(int C, long N, const float *__restrict__ logits,
+                                                                        const long long *__restrict__ target, PlSigmoid f,
+                                                                        double *__restrict__ partial)
+{
+    const int b = blockIdx.y;
+    const long n = (long)blockIdx.x * CE_THREADS + threadIdx.x;
+    double num = 0.0, den = 0.0;
+    if (n < N) {
+        const long long t = target[(size_t)b * N + n];
+        if (t >= 0 && t < C) {
+            const float *x = logits + (size_t)b * C * N + n;
+            for (int c = 0; c < C; ++c) num += (double)pl_sigmoid_element(f, c, x[(size_t)c * N], c == (int)t, nullptr);
+            den = (double)C;
+        }
+    }
+    pl_block_sum(num, den, partial);
+}
+
+__global__ __launch_bounds__(CE_THREADS) void pl_sigmoid_backward_kernel(int C, long N, const float *__restrict__ logits,
+                                                                         const long long *__restrict__ target, PlSigmoid f,
+                                                                         const float *__restrict__ loss_den,
+                                                                         const float *__restrict__ grad_out,
+                                                                         float *__restrict__ dlogits)
+{
+    const int b = blockIdx.y;
+    const long n = (long)blockIdx.x * CE_THREADS + threadIdx.x;
+    if (n >= N) return;
+    const float *x = logits + (size_t)b * C * N + n;
+    float *d = dlogits + (size_t)b * C * N + n;
+    const long long t = target[(size_t)b * N + n];
+    if (t < 0 || t >= C) {
+        for (int c = 0; c < C; ++c) d[(size_t)c * N] = 0.f;
+        return;
+    }
+    const float scale = grad_out[0] / loss_den[1];
+    for (int c = 0; c < C; ++c) {
+        float dx;
+        pl_sigmoid_element(f, c, x[(size_t)c * N], c == (int)t, &dx);
+        d[(size_t)c * N] = scale * dx;
+    }
+}
+
 }  // namespace amc
 
 using namespace amc;
@@ -2161,4 +2396,97 @@ AMC_API int amc3d_cross_entropy_general_backward(int B, int C, long N, const flo
     hipLaunchKernelGGL(ce_general_backward_kernel, dim3(div_up(N, CE_THREADS), B), dim3(CE_THREADS), 0, (hipStream_t)stream, C, N,
                        logits, target, ignore_index, has_ignore, label_smoothing, weight, lse, loss_den, grad_out, dlogits);
     return launch_status("amc3d_cross_entropy_general_backward");
+}
+
+AMC_API size_t amc3d_point_loss_softmax_workspace_bytes(int B, long N) { return amc3d_cross_entropy_workspace_bytes(B, N); }
+AMC_API size_t amc3d_point_loss_sigmoid_workspace_bytes(int B, long N) { return amc3d_cross_entropy_workspace_bytes(B, N); }
+
+// the form of a softmax-family call from the C-ABI's arguments; false: an argument is out of range
+static bool pl_softmax_form(int C, const long long *remap, int remap_len, long long ignore_index, int has_ignore, const int *mask,
+                            const float *weight, int weight_per_class, float eps, int eps_rule, float gamma, const float *alpha,
+                            float poly, int den_mode, PlSoftmax *f)
+{
+    if (!(eps >= 0.f && eps < 1.f) || eps_rule < 0 || eps_rule > 1 || den_mode < PL_DEN_COUNT || den_mode > PL_DEN_ONE ||
+        !(gamma >= 0.f) || (remap && remap_len <= 0))
+        return false;
+    float a_hot = 1.f, a_off = 0.f;
+    if (eps > 0.f && eps_rule == 0) {  // torch: eps / C on every class
+        a_off = eps / (float)C;
+        a_hot = 1.f - eps + a_off;
+    } else if (eps > 0.f) {            // the reference: eps / (C - 1) on the others (C = 1: 0 * eps / 0 = NaN there, and here)
+        a_off = eps / (float)(C - 1);
+        a_hot = C > 1 ? 1.f - eps : __builtin_nanf("");
+    }
+    *f = PlSoftmax{remap, remap ? remap_len : 0, ignore_index, has_ignore, mask, weight, weight ? weight_per_class : 0, a_hot, a_off,
+                   gamma, alpha, poly, den_mode};
+    return true;
+}
+
+AMC_API int amc3d_point_loss_softmax_forward(int B, int C, long N, const float *logits, const long long *target,
+                                             const long long *remap, int remap_len, long long ignore_index, int has_ignore,
+                                             const int *mask, const float *weight, int weight_per_class, float eps, int eps_rule,
+                                             float gamma, const float *alpha, float poly, int den_mode, float *lse, float *loss_den,
+                                             void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (B <= 0 || N <= 0) return 0;
+    PlSoftmax f;
+    if (C <= 0 || !logits || !target || !lse || !loss_den || !workspace ||
+        workspace_bytes < amc3d_point_loss_softmax_workspace_bytes(B, N) ||
+        !pl_softmax_form(C, remap, remap_len, ignore_index, has_ignore, mask, weight, weight_per_class, eps, eps_rule, gamma, alpha,
+                         poly, den_mode, &f))
+        return bad_arg("amc3d_point_loss_softmax_forward: bad argument (eps in [0, 1), gamma >= 0, den_mode in 0..2)");
+    hipStream_t stream = (hipStream_t)stream_;
+    const int gx = div_up(N, CE_THREADS);
+    hipLaunchKernelGGL(pl_softmax_forward_kernel, dim3(gx, B), dim3(CE_THREADS), 0, stream, C, N, logits, target, f, lse,
+                       (double *)workspace);
+    hipLaunchKernelGGL(pl_finalize_kernel, dim3(1), dim3(1024), 0, stream, gx * B, (const double *)workspace, den_mode, loss_den);
+    return launch_status("amc3d_point_loss_softmax_forward");
+}
+
+AMC_API int amc3d_point_loss_softmax_backward(int B, int C, long N, const float *logits, const long long *target,
+                                              const long long *remap, int remap_len, long long ignore_index, int has_ignore,
+                                              const int *mask, const float *weight, int weight_per_class, float eps, int eps_rule,
+                                              float gamma, const float *alpha, float poly, int den_mode, const float *lse,
+                                              const float *loss_den, const float *grad_out, float *dlogits, void *stream)
+{
+    if (B <= 0 || N <= 0) return 0;
+    PlSoftmax f;
+    if (C <= 0 || !logits || !target || !lse || !loss_den || !grad_out || !dlogits ||
+        !pl_softmax_form(C, remap, remap_len, ignore_index, has_ignore, mask, weight, weight_per_class, eps, eps_rule, gamma, alpha,
+                         poly, den_mode, &f))
+        return bad_arg("amc3d_point_loss_softmax_backward: bad argument (eps in [0, 1), gamma >= 0, den_mode in 0..2)");
+    hipLaunchKernelGGL(pl_softmax_backward_kernel, dim3(div_up(N, CE_THREADS), B), dim3(CE_THREADS), 0, (hipStream_t)stream, C, N,
+                       logits, target, f, lse, loss_den, grad_out, dlogits);
+    return launch_status("amc3d_point_loss_softmax_backward");
+}
+
+AMC_API int amc3d_point_loss_sigmoid_forward(int B, int C, long N, const float *logits, const long long *target,
+                                             const float *weight, const float *pos_weight, float alpha, float gamma, float poly, int den_mode, float *loss_den, void *workspace,
+                                             size_t workspace_bytes, void *stream_)
+{
+    if (B <= 0 || N <= 0) return 0;
+    if (C <= 0 || !logits || !target || !loss_den || !workspace || !(gamma >= 0.f) || !(alpha <= 1.f) ||
+        (den_mode != PL_DEN_COUNT && den_mode != PL_DEN_ONE) || workspace_bytes < amc3d_point_loss_sigmoid_workspace_bytes(B, N))
+        return bad_arg("amc3d_point_loss_sigmoid_forward: bad argument (gamma >= 0, alpha <= 1, den_mode 0 or 2)");
+    hipStream_t stream = (hipStream_t)stream_;
+    const PlSigmoid f{weight, pos_weight, alpha, gamma, poly, den_mode};
+    const int gx = div_up(N, CE_THREADS);
+    hipLaunchKernelGGL(pl_sigmoid_forward_kernel, dim3(gx, B), dim3(CE_THREADS), 0, stream, C, N, logits, target, f,
+                       (double *)workspace);
+    hipLaunchKernelGGL(pl_finalize_kernel, dim3(1), dim3(1024), 0, stream, gx * B, (const double *)workspace, den_mode, loss_den);
+    return launch_status("amc3d_point_loss_sigmoid_forward");
+}
+
+AMC_API int amc3d_point_loss_sigmoid_backward(int B, int C, long N, const float *logits, const long long *target,
+                                              const float *weight, const float *pos_weight, float alpha, float gamma, float poly, int den_mode, const float *loss_den,
+                                              const float *grad_out, float *dlogits, void *stream)
+{
+    if (B <= 0 || N <= 0) return 0;
+    if (C <= 0 || !logits || !target || !loss_den || !grad_out || !dlogits || !(gamma >= 0.f) || !(alpha <= 1.f) ||
+        (den_mode != PL_DEN_COUNT && den_mode != PL_DEN_ONE))
+        return bad_arg("amc3d_point_loss_sigmoid_backward: bad argument (gamma >= 0, alpha <= 1, den_mode 0 or 2)");
+    const PlSigmoid f{weight, pos_weight, alpha, gamma, poly, den_mode};
+    hipLaunchKernelGGL(pl_sigmoid_backward_kernel, dim3(div_up(N, CE_THREADS), B), dim3(CE_THREADS), 0, (hipStream_t)stream, C, N,
+                       logits, target, f, loss_den, grad_out, dlogits);
+    return launch_status("amc3d_point_loss_sigmoid_backward");
 }

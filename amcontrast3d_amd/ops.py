@@ -2305,6 +2305,135 @@ def cross_entropy_general(logits, target, ignore_index=-100, label_smoothing=0.0
     return CrossEntropyGeneral.apply(logits, target, ignore_index, label_smoothing, weight)
 
 
+_POINT_LOSS_DEN = {"count": 0, "weight": 1, "one": 2}
+
+
+def _opt_ptr(t):
+    return _ptr(t) if t is not None else None
+
+
+def _class_table(t, C, name, dtype=torch.float32):
+    """an optional per-class table of the point losses: contiguous, one entry per class"""
+    if t is None:
+        return None
+    _need_gpu(t)
+    _need_dtype(dtype, **{name: t})
+    assert t.shape == (C,), f"{name} must hold one value per class: {tuple(t.shape)} for {C} classes"
+    return t.contiguous()
+
+
+class PointLossSoftmax(Function):
+    """The softmax family of csrc/loss.hip (pl_softmax_*; formulas in include/amc3d.h) on channel-major logits (B, C, N) with
+    targets (B, N): SmoothCrossEntropy, MaskedCrossEntropy, FocalLoss and Poly1CrossEntropyLoss of openpoints.loss are forms of
+    it.  Two launches forward, one backward; the saved lse (B, N) spares the backward the two reduction walks."""
+
+    @staticmethod
+    def forward(ctx, logits, target, remap, ignore_index, mask, weight, weight_per_class, eps, eps_rule, gamma, alpha, poly, den):
+        _need_gpu(logits, target)
+        _need_dtype(torch.float32, logits=logits)
+        _need_dtype(torch.int64, target=target)
+        logits = logits.contiguous()
+        B, C = logits.shape[0], logits.shape[1]
+        N = logits[0, 0].numel()
+        target = target.reshape(B, N).contiguous()
+        weight, alpha = _class_table(weight, C, "weight"), _class_table(alpha, C, "alpha")
+        if remap is not None:
+            _need_gpu(remap)
+            _need_dtype(torch.int64, remap=remap)
+            remap = remap.contiguous()
+        if mask is not None:
+            _need_gpu(mask)
+            _need_dtype(torch.int32, mask=mask)
+            mask = mask.reshape(B, N).contiguous()
+        dev = logits.device
+        lse = torch.empty(B, N, dtype=torch.float32, device=dev)
+        loss_den = torch.empty(2, dtype=torch.float32, device=dev)
+        lib = _lib.load()
+        wb = int(lib.amc3d_point_loss_softmax_workspace_bytes(B, N))
+        work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
+        ctx.form = lambda: (_opt_ptr(remap), 0 if remap is None else remap.numel(), int(ignore_index if ignore_index is not None else 0),
+                            int(ignore_index is not None), _opt_ptr(mask), _opt_ptr(weight), int(bool(weight_per_class)), float(eps),
+                            int(eps_rule), float(gamma), _opt_ptr(alpha), float(poly), _POINT_LOSS_DEN[den])
+        walks = 3 if eps else 2
+        with torch.cuda.device(dev), timing.span("point_loss_softmax_forward", B * N * (4 * C + 12 + (4 if mask is not None else 0)),
+                                                 moved=B * N * (4 * C * walks + 12 + (4 if mask is not None else 0))):
+            _lib.check(lib.amc3d_point_loss_softmax_forward(B, C, N, _ptr(logits), _ptr(target), *ctx.form(), _ptr(lse), _ptr(loss_den),
+                                                            _ptr(work), wb, _stream(logits)), "point_loss_softmax_forward")
+        ctx.save_for_backward(logits, target, lse, loss_den)
+        return loss_den[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, lse, loss_den = ctx.saved_tensors
+        B, C = logits.shape[0], logits.shape[1]
+        N = logits[0, 0].numel()
+        g = g.contiguous().to(torch.float32)
+        d = torch.empty_like(logits)
+        with torch.cuda.device(logits.device), timing.span("point_loss_softmax_backward", B * N * (8 * C + 12)):
+            _lib.check(_lib.load().amc3d_point_loss_softmax_backward(B, C, N, _ptr(logits), _ptr(target), *ctx.form(), _ptr(lse),
+                                                                     _ptr(loss_den), _ptr(g), _ptr(d), _stream(logits)),
+                       "point_loss_softmax_backward")
+        return (d,) + (None,) * 12
+
+
+def point_loss_softmax(logits, target, *, remap=None, ignore_index=None, mask=None, weight=None, weight_per_class=False,
+                       eps=0.0, eps_rule=0, gamma=0.0, alpha=None, poly=0.0, den="count"):
+    """logits (B, C, N) fp32, target (B, N) int64 -> the scalar loss.  remap: int64 label -> class table; ignore_index None: no
+    target is ignored; mask (B, N) int32, a point counts iff its entry is 1; weight / alpha (C) fp32; eps_rule 0: torch's
+    eps / C on every class, 1: SmoothCrossEntropy's eps / (C - 1) on the others; den 'count', 'weight' (sum of w[y]) or 'one'
+    (a sum).  No table takes a gradient.  Safe under ops.deterministic_mode() and graph capture: fixed-order sums, no atomics."""
+    return PointLossSoftmax.apply(logits, target, remap, ignore_index, mask, weight, weight_per_class, eps, eps_rule, gamma, alpha,
+                                  poly, den)
+
+
+class PointLossSigmoid(Function):
+    """The sigmoid family of csrc/loss.hip (pl_sigmoid_*; formulas in include/amc3d.h): elementwise over (B, C, N) against the
+    one-hot of target (B, N), formed on the fly -- BCELogits and Poly1FocalLoss of openpoints.loss.  Two launches forward, one
+    backward; the backward recomputes each element from the logits (nothing per element is saved)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, pos_weight, alpha, gamma, poly, den):
+        _need_gpu(logits, target)
+        _need_dtype(torch.float32, logits=logits)
+        _need_dtype(torch.int64, target=target)
+        logits = logits.contiguous()
+        B, C = logits.shape[0], logits.shape[1]
+        N = logits[0, 0].numel()
+        target = target.reshape(B, N).contiguous()
+        weight, pos_weight = _class_table(weight, C, "weight"), _class_table(pos_weight, C, "pos_weight")
+        dev = logits.device
+        loss_den = torch.empty(2, dtype=torch.float32, device=dev)
+        lib = _lib.load()
+        wb = int(lib.amc3d_point_loss_sigmoid_workspace_bytes(B, N))
+        work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
+        ctx.form = lambda: (_opt_ptr(weight), _opt_ptr(pos_weight), float(-1.0 if alpha is None else alpha), float(gamma), float(poly),
+                            _POINT_LOSS_DEN[den])
+        with torch.cuda.device(dev), timing.span("point_loss_sigmoid_forward", B * N * (4 * C + 8)):
+            _lib.check(lib.amc3d_point_loss_sigmoid_forward(B, C, N, _ptr(logits), _ptr(target), *ctx.form(), _ptr(loss_den),
+                                                            _ptr(work), wb, _stream(logits)), "point_loss_sigmoid_forward")
+        ctx.save_for_backward(logits, target, loss_den)
+        return loss_den[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, loss_den = ctx.saved_tensors
+        B, C = logits.shape[0], logits.shape[1]
+        N = logits[0, 0].numel()
+        g = g.contiguous().to(torch.float32)
+        d = torch.empty_like(logits)
+        with torch.cuda.device(logits.device), timing.span("point_loss_sigmoid_backward", B * N * (8 * C + 8)):
+            _lib.check(_lib.load().amc3d_point_loss_sigmoid_backward(B, C, N, _ptr(logits), _ptr(target), *ctx.form(), _ptr(loss_den),
+                                                                     _ptr(g), _ptr(d), _stream(logits)), "point_loss_sigmoid_backward")
+        return (d,) + (None,) * 7
+
+
+def point_loss_sigmoid(logits, target, *, weight=None, pos_weight=None, alpha=None, gamma=0.0, poly=0.0, den="count"):
+    """logits (B, C, N) fp32, target (B, N) int64 -> the scalar loss over the elements of the counted points (target in
+    [0, C)): mean (den 'count') or sum (den 'one').  weight / pos_weight (C) fp32 per class; alpha None or negative: no
+    alpha_t.  Safe under ops.deterministic_mode() and graph capture."""
+    return PointLossSigmoid.apply(logits, target, weight, pos_weight, alpha, gamma, poly, den)
+
+
 class SATail(Function):
     """pooled (B,C2,M) = max_k [relu2](bn2(conv2(relu(bn1(y1)))))  -- the tail of a two-layer SetAbstraction block
     (pointnext_AA.py:104-127, 164-166) from the first conv's raw output y1 (B,C1,M,32), with batch statistics for both

@@ -83,11 +83,16 @@ def train_one_epoch(model, train_loader, criterion, optimizer, scheduler, scaler
     A criterion without a `contrast_head` selects the plain PointNeXt step (examples/segmentation/main.py:338-390):
     `logits = model(data); loss = criterion(logits, target)` with a model that returns the logits alone (BaseSeg); cfg then
     needs no ambiguity_args, no loss geometry is planned, and everything else -- the captured pipeline, its eager fallbacks,
-    the return value -- is the same."""
+    the return value -- is the same.  Such a criterion whose config name (cfg.criterion_args.NAME, or its class name without
+    one) contains 'mask' is called as `criterion(logits, target, data['mask'])` (main.py:357-360: MaskedCrossEntropy); the
+    pipeline copies 'mask' into its static buffers like every tensor key of the batch."""
     if getattr(criterion, "contrast_head", None) is None:
+        name = _cfg(_cfg(cfg, "criterion_args", None) or {}, "NAME", None) or type(criterion).__name__
+        masked = "mask" in name.lower()
+
         def step_loss(data, target):
             logits = model(data)
-            return logits, criterion(logits, target), ()
+            return logits, (criterion(logits, target, data["mask"]) if masked else criterion(logits, target)), ()
     else:
         def step_loss(data, target):
             logits, stage = model(data)

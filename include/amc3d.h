@@ -399,6 +399,49 @@ int amc3d_cross_entropy_general_backward(int B, int C, long N, const float *logi
                                          long long ignore_index, int has_ignore, float label_smoothing,
                                          const float *weight, const float *lse, const float *loss_den,
                                          const float *grad_out, float *dlogits, void *stream);
+/* The rest of openpoints.loss (loss/build.py:14-257) as two form-generic families on the same layout, summation order and launch
+ * counts as cross_entropy_general (two launches forward, one backward, no atomics, nothing zero-filled, any C >= 1).  A point
+ * whose class falls outside [0, C) is left out and gets a zero gradient row; with nothing counted a mean is 0/0 = NaN and
+ * dlogits all zero.  loss_den[2] = {loss, den}; den_mode 0: den = the counted points (softmax) or their elements (sigmoid),
+ * 1: den = sum of w[y] (softmax only), 2: den = 1 (reduction 'sum').
+ *
+ * Softmax family.  A point is dropped when has_ignore and target == ignore_index, or when mask (B,N) int32 is given and its
+ * entry != 1; then y = remap[target] when remap (remap_len int64 entries) is given, target otherwise.  lp = log_softmax,
+ * p = softmax, w = weight (C) or ones.  eps in [0, 1) smooths the target distribution q: eps_rule 0 is torch's
+ * (q[y] = 1 - eps + eps/C, q[c != y] = eps/C), eps_rule 1 SmoothCrossEntropy's (q[y] = 1 - eps, q[c != y] = eps/(C-1); NaN at
+ * C = 1 as there).  weight_per_class 1: Q[c] = q[c] w[c], m0 = 1;  0: Q[c] = q[c], m0 = w[y].  alpha (C) or NULL, gamma >= 0:
+ *   m = m0 alpha[y] (1 - p[y])^gamma                    (0^0 = 1; m is a constant of the backward: FocalLoss detaches pt)
+ *   term_i = m sum_c Q[c] (-lp_i[c]) + poly (1 - p_i[y])
+ *   loss = sum_i term_i / den
+ *   dlogits_i[c] = grad_out[0] / den * [ m (p_i[c] sum_c Q[c] - Q[c]) + poly p_i[y] (p_i[c] - [c == y]) ]
+ * SmoothCrossEntropy: eps_rule 1, weight_per_class 1, den_mode 0 (eps = 0: weight_per_class 0, den_mode 1);  MaskedCrossEntropy:
+ * mask, eps_rule 0;  FocalLoss: gamma, alpha, den_mode 0 or 2;  Poly1CrossEntropyLoss: poly, weight_per_class 0, den_mode 0 or 2.
+ * lse (B,N) out (saved for backward).
+ *
+ * Sigmoid family: elementwise over (B,C,N) against the one-hot of target, formed on the fly.  For logit x and target bit t:
+ * z = t ? -x : x, u = sigmoid(z) = 1 - pt, ce = max(x,0) - x t + log1p(exp(-|x|)) = -log(pt),
+ *   a = w[c] (t ? pos_weight[c] : 1) (alpha >= 0 ? (t ? alpha : 1 - alpha) : 1)
+ *   value = a ce u^gamma + poly u^(gamma+1)
+ *   d value / d z = u^gamma [ a (u + ce gamma (1 - u)) + poly (gamma + 1) u (1 - u) ],  d z / d x = t ? -1 : 1
+ * BCELogits: weight / pos_weight (C) or NULL, alpha < 0, gamma = poly = 0;  Poly1FocalLoss: alpha, gamma, poly, no weights. */
+size_t amc3d_point_loss_softmax_workspace_bytes(int B, long N);
+int amc3d_point_loss_softmax_forward(int B, int C, long N, const float *logits, const long long *target,
+                                     const long long *remap, int remap_len, long long ignore_index, int has_ignore,
+                                     const int *mask, const float *weight, int weight_per_class, float eps, int eps_rule,
+                                     float gamma, const float *alpha, float poly, int den_mode, float *lse, float *loss_den,
+                                     void *workspace, size_t workspace_bytes, void *stream);
+int amc3d_point_loss_softmax_backward(int B, int C, long N, const float *logits, const long long *target,
+                                      const long long *remap, int remap_len, long long ignore_index, int has_ignore,
+                                      const int *mask, const float *weight, int weight_per_class, float eps, int eps_rule,
+                                      float gamma, const float *alpha, float poly, int den_mode, const float *lse,
+                                      const float *loss_den, const float *grad_out, float *dlogits, void *stream);
+size_t amc3d_point_loss_sigmoid_workspace_bytes(int B, long N);
+int amc3d_point_loss_sigmoid_forward(int B, int C, long N, const float *logits, const long long *target, const float *weight,
+                                     const float *pos_weight, float alpha, float gamma, float poly, int den_mode, float *loss_den,
+                                     void *workspace, size_t workspace_bytes, void *stream);
+int amc3d_point_loss_sigmoid_backward(int B, int C, long N, const float *logits, const long long *target, const float *weight,
+                                      const float *pos_weight, float alpha, float gamma, float poly, int den_mode,
+                                      const float *loss_den, const float *grad_out, float *dlogits, void *stream);
 
 /* ---- pointwise (1x1) convolution on fp32 MFMA -----------------------------------------------------
  * Replaces the nn.Conv1d / nn.Conv2d (kernel size 1) layers of the path, which the reference builds in
