@@ -4,6 +4,7 @@ Layout
     csrc/         hand-written gfx950 HIP kernels + the C-ABI (include/amc3d.h) -> libamc3d_hip.so
     _lib.py       ctypes loader (no fallback: missing library == ImportError)
     ops.py        torch.autograd front-ends mirroring the reference's wrappers
+    offset_ops.py the offset-layout (ragged batch) pointops operators: sampling, ball query, grouping, aggregation, ...
     compat.py     module objects shaped like the reference's pybind11 extensions
     openpoints/   drop-in for the reference's openpoints.{models,loss,AMContrast3D,utils.registry}
     synthetic.py  seeded S3DIS-shaped scenes for tests / bench

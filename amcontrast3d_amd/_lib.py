@@ -39,6 +39,17 @@ SIGNATURES = {
     "amc3d_knnquery_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "amc3d_knnquery_uses_grid": (_i, [_i, _i, _i, _i]),
     "amc3d_knnquery": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
+    "amc3d_pointops_ballquery": (_i, [_i, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "amc3d_pointops_furthestsampling": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "amc3d_pointops_grouping_forward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "amc3d_pointops_grouping_backward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "amc3d_pointops_interpolation_forward": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "amc3d_pointops_interpolation_backward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "amc3d_pointops_subtraction_forward": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "amc3d_pointops_subtraction_backward": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "amc3d_pointops_aggregation_forward": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "amc3d_pointops_aggregation_backward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "amc3d_pointops_scatter_csr": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "amc3d_vote_labels": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     "amc3d_posmask": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     "amc3d_ambiguity_workspace_bytes": (_sz, [_i]),

@@ -2643,3 +2643,9 @@ def expand_parts(logits, tables):
                                                   _ptr(t["idx_sort"].contiguous()), _ptr(t["voxel_idx"].contiguous()),
                                                   _ptr(voted), _ptr(pred), _stream(logits)), "expand_parts")
     return voted, pred
+
+
+# the offset-layout (ragged-batch) operators of the pointops surface -- furthest sampling, ball query, grouping,
+# subtraction, aggregation, interpolation -- live in offset_ops.py (ops.offset_ops.Grouping, ...): this file's BallQuery and
+# friends are the dense (B,N,.) forms of the same names
+from . import offset_ops  # noqa: E402,F401

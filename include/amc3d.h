@@ -170,6 +170,86 @@ int amc3d_knnquery(int m, int nsample, int n, int nbatch, const float *xyz, cons
                    const int *offset, const int *new_offset, int *idx, float *dist2,
                    void *workspace, size_t workspace_bytes, int reuse_grid, void *stream);
 
+/* The other ten entry points of pointops_api.cpp:14-24 (csrc/pointops.hip).  Layouts: xyz (n,3), new_xyz (m,3), features
+ * channel-last (rows of c floats), idx (rows, nsample) int32 GLOBAL row ids, offset / new_offset cumulative segment ends
+ * with nbatch entries.  Arithmetic as the reference writes it, left to right, fp32, no FMA.  Every product of sizes that
+ * indexes an array must fit in 31 bits (otherwise hipErrorInvalidValue).  The kernels trust idx, as the reference does.
+ * `accumulate`: 0 = every output element is written (the sum starts from +0.0f, what the reference computes into its
+ * caller's zero-filled buffer); 1 = the reference's `+=` into whatever the buffer holds.
+ * Row-local gradients -- grad_input1 of the subtraction, grad_position and grad_weight of the aggregation -- are sequential
+ * sums without atomics (the reference uses atomicAdd for two of them): bit-reproducible in either mode.
+ * The four scatters -- grouping, interpolation, subtraction's grad_input2, aggregation's grad_input -- use float atomics
+ * into a caller-zeroed buffer, as the reference does; deterministic mode replaces them with the scatter_csr gather below. */
+
+/* replaces ballquery_cuda -> ballquery_launcher (pointops/src/ballquery/ballquery_cuda_kernel.cu:26-78).
+ * Query q belongs to the first segment s with q < new_offset[s] (a bounded binary search; a query past the last end
+ * counts to the last segment); its support is [offset[s-1], offset[s]).  idx row = the first nsample support rows,
+ * ascending, with d2 < radius*radius (strict), padded with the first hit; a row with no hit is written as zeros (row 0
+ * of the whole batch, not the segment's start: the reference leaves the caller's zero-fill). */
+int amc3d_pointops_ballquery(int m, float radius, int nsample, int n, int nbatch, const float *xyz, const float *new_xyz,
+                             const int *offset, const int *new_offset, int *idx, void *stream);
+
+/* replaces furthestsampling_cuda (pointops/src/sampling/sampling_cuda_kernel.cu:14-171).  One workgroup per segment:
+ * idx[new_start] = start, every later pick the arg-max of the running minimum distance to the earlier picks.  tmp (n) is
+ * read as the initial minima (the reference's caller fills it with 1e10) and receives the final ones.  Ties resolve as the
+ * reference's strided scan + shared-memory tree does: smallest bit-reversed (k - start) mod block, then lowest k.
+ * n_max is the reference's `n` argument (the longest segment; it fixes the reference's block size for all segments): it
+ * does not change a pick -- the key is evaluated over 10 bits, whose order refines that of every smaller block; it only
+ * selects how many points per thread (4, 8 or 12) keep their running minima in registers, and a segment beyond that budget
+ * (longer than 12288, or longer than n_max promised) keeps them in tmp.  n = rows of xyz / tmp (segment ends are clamped to it).  A segment with no
+ * sample (new_offset[s] == new_offset[s-1]) or no point writes nothing. */
+int amc3d_pointops_furthestsampling(int nbatch, int n_max, int n, const float *xyz, const int *offset,
+                                    const int *new_offset, float *tmp, int *idx, void *stream);
+
+/* replaces grouping_forward_cuda / grouping_backward_cuda (grouping_cuda_kernel.cu:5-14, 16-25): input (n,c), idx
+ * (m,nsample) -> output[i,j,:] = input[idx[i,j],:]; grad_input[idx[i,j],:] += grad_output[i,j,:] (caller zero-fills) */
+int amc3d_pointops_grouping_forward(int m, int nsample, int c, int n, const float *input, const int *idx, float *output,
+                                    void *stream);
+int amc3d_pointops_grouping_backward(int m, int nsample, int c, int n, const float *grad_output, const int *idx,
+                                     float *grad_input, void *stream);
+
+/* replaces interpolation_forward_cuda / interpolation_backward_cuda (interpolation_cuda_kernel.cu:5-18, 20-33): input
+ * (m,c), idx / weight (n,k) -> output[i,ch] = ((input[idx[i,0],ch]*weight[i,0]) + input[idx[i,1],ch]*weight[i,1]) + ...;
+ * grad_input[idx[i,t],ch] += grad_output[i,ch]*weight[i,t] (caller zero-fills) */
+int amc3d_pointops_interpolation_forward(int n, int c, int k, int m, int accumulate, const float *input, const int *idx,
+                                         const float *weight, float *output, void *stream);
+int amc3d_pointops_interpolation_backward(int n, int c, int k, int m, const float *grad_output, const int *idx,
+                                          const float *weight, float *grad_input, void *stream);
+
+/* replaces subtraction_forward_cuda / subtraction_backward_cuda (subtraction_cuda_kernel.cu:5-16, 18-30): input1, input2
+ * (n,c), idx (n,nsample) -> output[i,j,:] = input1[i,:] - input2[idx[i,j],:].  Backward: grad_input1[i,ch] = sum over j
+ * ascending of grad_output[i,j,ch], sequential from +0.0f, WRITTEN; grad_input2[idx[i,j],ch] += -grad_output[i,j,ch]
+ * (caller zero-fills; NULL = skip it, for the scatter_csr route) */
+int amc3d_pointops_subtraction_forward(int n, int nsample, int c, const float *input1, const float *input2,
+                                       const int *idx, float *output, void *stream);
+int amc3d_pointops_subtraction_backward(int n, int nsample, int c, const int *idx, const float *grad_output,
+                                        float *grad_input1, float *grad_input2, void *stream);
+
+/* replaces aggregation_forward_cuda / aggregation_backward_cuda (aggregation_cuda_kernel.cu:5-20, 22-39): input (n,c),
+ * position (n,nsample,c), weight (n,nsample,w_c), idx (n,nsample) -> output[i,ch] = sum over j ascending of
+ * (input[idx[i,j],ch] + position[i,j,ch]) * weight[i,j,ch % w_c].  Backward: grad_position[i,j,ch] = grad_output[i,ch] *
+ * weight[i,j,ch % w_c] and grad_weight[i,j,wc] = sum over ch = wc, wc + w_c, ... ascending of grad_output[i,ch] *
+ * (input[idx[i,j],ch] + position[i,j,ch]), both WRITTEN; grad_input[idx[i,j],ch] += grad_position[i,j,ch] (caller
+ * zero-fills; NULL = skip it, for the scatter_csr route) */
+int amc3d_pointops_aggregation_forward(int n, int nsample, int c, int w_c, int accumulate, const float *input,
+                                       const float *position, const float *weight, const int *idx, float *output,
+                                       void *stream);
+int amc3d_pointops_aggregation_backward(int n, int nsample, int c, int w_c, const float *input, const float *position,
+                                        const float *weight, const int *idx, const float *grad_output, float *grad_input,
+                                        float *grad_position, float *grad_weight, void *stream);
+
+/* The four scatters without atomics (deterministic mode; no counterpart in the reference), as one gather over the
+ * reverse lists of idx seen as one flat cloud: rev_start (n_targets + 1), rev_edge (positions) from amc3d_group_csr
+ * with b = 1.  out (n_targets,c): every element is written under the SUMMATION ORDER contract stated at
+ * amc3d_three_interpolate_grad_csr (ascending position, sequential __fadd_rn from +0.0f, products rounded first by
+ * __fmul_rn, exactly +0.0f for a target nobody names).  The term of position p, channel ch, by kind:
+ *   0  g[p,ch]                              grouping:      g = grad_output (m*nsample,c)
+ *   1  g[p / per,ch] * w[p]                 interpolation: g = grad_output (n,c), w = weight (n*k), per = k
+ *   2  -g[p,ch]                             subtraction:   g = grad_output (n*nsample,c)
+ *   3  g[p / per,ch] * w[p, ch % w_c]       aggregation:   g = grad_output (n,c), w = weight (n*nsample,w_c), per = nsample */
+int amc3d_pointops_scatter_csr(int kind, int n_targets, int c, int per, int w_c, const float *g, const float *w,
+                               const int *rev_start, const int *rev_edge, float *out, void *stream);
+
 /* ---- adaptive-margin contrastive loss -------------------------------------------
  * The reference has no native code here: it evaluates this part with torch ops and a Python
  * loop.  These entry points replace, per decoder stage,
