@@ -22,6 +22,7 @@ SIGNATURES = {
     "amc3d_reserve_scratch": (_i, [_i, _vp, _vp]),
     "amc3d_stream_destroy": (_i, [_vp]),
     "amc3d_grid_search_workspace_bytes": (_sz, [_i, _i, _i]),
+    "amc3d_grid_search_pays": (_i, [_i, _i, _i]),
     "amc3d_ball_query": (_i, [_i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_group_points": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "amc3d_group_points_grad": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -1401,6 +1401,9 @@ AMC_API int amc3d_knnquery_uses_grid(int m, int nsample, int n, int nbatch)
     return (nsample <= KG_MAXK && (long)n * m >= (1L << 22) && n >= 4 * KG_SAMPLES && nbatch <= 64) ? 1 : 0;
 }
 
+// 1 when amc3d_ball_query (support n, queries m) / amc3d_three_nn (support = known) search the cell grid, given a workspace
+AMC_API int amc3d_grid_search_pays(int b, int n, int m) { return grid_search_pays(b, n, m) ? 1 : 0; }
+
 AMC_API int amc3d_knnquery(int m, int nsample, int n, int nbatch, const float *xyz, const float *new_xyz,
                            const int *offset, const int *new_offset, int *idx, float *dist2, void *workspace,
                            size_t workspace_bytes, int reuse_grid, void *stream_)

@@ -65,6 +65,9 @@ int amc3d_stream_destroy(void *stream);
  * edge >= radius (27 cells per query instead of all n points); NULL / too small = the all-pairs scan.
  * Both give the reference's result exactly. */
 size_t amc3d_grid_search_workspace_bytes(int b, int n_support, int m_queries);
+/* 1: with that workspace (and, for the ball query, nsample <= 64 and radius > 0) this problem size is searched on the
+ * grid; 0: the all-pairs scan answers.  For amc3d_three_nn the support is `known`: (b, m, n). */
+int amc3d_grid_search_pays(int b, int n_support, int m_queries);
 int amc3d_ball_query(int b, int n, int m, float radius, int nsample,
                      const float *new_xyz, const float *xyz, int *idx,
                      void *workspace, size_t workspace_bytes, void *stream);

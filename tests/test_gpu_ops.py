@@ -1,7 +1,9 @@
 """HIP kernels (through the C-ABI, via amcontrast3d_amd.ops / compat) against the oracle's C
 restatement on identical seeded inputs, against the golden fixture, and -- at benchmark size --
 through size-independent properties.  Indices must be bit-exact; fp32 values that involve no
-reassociation must be bit-exact too; scatter-add gradients (atomics) get 1e-5."""
+reassociation must be bit-exact too; scatter-add gradients (atomics) get 1e-5.
+The clouds here (`clouds`) are all about 2 units wide and next to the origin; clouds far from the origin, planar, collinear,
+coincident or clustered, and queries outside the support's box, are in test_gpu_geometry_edges.py."""
 import numpy as np
 import pytest
 import torch
