@@ -125,6 +125,11 @@ SIGNATURES = {
     "amc3d_index_duplicates": (_i, [_i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_augment_workspace_bytes": (_sz, [_i]),
     "amc3d_augment_clouds": (_i, [_i, _i, _i, _f, _f] + [_vp] * 10 + [_sz, _vp]),
+    "amc3d_transform_max_ops": (_i, []),
+    "amc3d_transform_max_phases": (_i, []),
+    "amc3d_transform_program_bytes": (_i, []),
+    "amc3d_transform_workspace_bytes": (_sz, [_i, _ll, _i]),
+    "amc3d_transform_chain": (_i, [_i, _ll, _i, _vp, _vp, _vp, ctypes.POINTER(_vp), _i] + [_vp] * 6 + [_sz, _vp]),
     "amc3d_voxelize_workspace_bytes": (_sz, [_i]),
     "amc3d_voxelize": (_i, [_i, _vp, ctypes.c_double] + [_vp] * 7 + [_sz, _vp]),
     "amc3d_voxel_select": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -153,6 +153,29 @@ def _voxel_select_i32(start, count, idx_sort, rnd):
     return out
 
 
+def _is_chain(t):
+    from .transforms import TransformChain
+    return isinstance(t, TransformChain)
+
+
+def _chain_draws(t, d, sizes, dev, generator):
+    """the keys of a transforms.TransformChain out of the draws d; what is missing is drawn on the device"""
+    own = {k: v for k, v in d.items() if k in t.spec() or k.endswith(".R")}
+    given_R = {k.split(".", 1)[0] for k, v in own.items() if k.endswith(".R") and v is not None}
+    if any(k not in own and not (k.split(".", 1)[0] in given_R and k.split(".", 1)[1] in ("angle", "theta", "order"))
+           for k in t.spec()):
+        for k, v in t.draw(sizes, dev, generator).items():
+            own.setdefault(k, v)
+    return own
+
+
+def _chain_rooms(t, coord, feat, off_t, sizes, d):
+    """a TransformChain on whole raw ScanNet rooms: colours (feat + 1) * 127.5 first; the positions float64 for crop_pc (a chain
+    that leaves them float32 is cast, exactly)"""
+    out = t({"pos": coord, "x": feat, "offsets": off_t, "sizes": sizes}, draws=d, scannet_colour=True, want_heights=False)
+    return (out["pos"] if out["pos"].dtype == torch.float64 else out["pos"].double()), out["x"]
+
+
 def scannet_train_batch(rooms, transform, voxel_size=0.02, voxel_max=64000, variable=False, generator=None, draws=None,
                         gravity_dim=2):
     """ScanNet.__getitem__ for training (dataset/scannetv2/scannet.py:140-176) plus the default collate, for a batch of raw
@@ -180,17 +203,21 @@ def scannet_train_batch(rooms, transform, voxel_size=0.02, voxel_max=64000, vari
         if c.dim() != 2 or c.shape[1] != 3 or f.shape != c.shape or l.numel() != c.shape[0] or c.shape[0] == 0:
             raise ValueError("scannet_train_batch: every room needs coord (n,3), feat (n,3), label (n,) with n > 0")
     d = dict(draws or {})
+    sizes = [int(c.shape[0]) for c, _, _ in rooms]
     keys = ("scale", "mirror_u", "contrast_u", "blend", "drop_u")
-    if any(k not in d for k in keys) or ("angle" not in d and "R" not in d):
+    if not _is_chain(transform) and (any(k not in d for k in keys) or ("angle" not in d and "R" not in d)):
         for k, v in transform.draw(B, generator, dev).items():
             d.setdefault(k, v)
     per_room = {k: list(d.get(k) or [None] * B) for k in ("rnd", "init_idx", "pad", "perm")}
     if any(len(v) != B for v in per_room.values()):
         raise ValueError("scannet_train_batch: per-room draws need one entry per room")
-    sizes = [int(c.shape[0]) for c, _, _ in rooms]
     offsets = torch.tensor([0] + sizes, dtype=torch.int64).cumsum(0).to(dev)
-    pos64, x, _ = transform(torch.cat([c for c, _, _ in rooms]), torch.cat([f for _, f, _ in rooms]), offsets, draws=d,
-                            generator=generator)
+    if _is_chain(transform):  # a transforms.TransformChain: any configured list, its draws under its own keys
+        pos64, x = _chain_rooms(transform, torch.cat([c for c, _, _ in rooms]), torch.cat([f for _, f, _ in rooms]), offsets, sizes,
+                                _chain_draws(transform, d, sizes, dev, generator))
+    else:
+        pos64, x, _ = transform(torch.cat([c for c, _, _ in rooms]), torch.cat([f for _, f, _ in rooms]), offsets, draws=d,
+                                generator=generator)
     u_init = None
     plans = []
     beg = 0
@@ -729,11 +756,14 @@ def _s3dis_batch(raw, src, sizes, transform, voxel_size, voxel_max, variable, sh
     if shuffle and any(p is None for p in per_room["perm"]):
         perm_t = torch.rand(B, n_out, device=dev, generator=generator).argsort(dim=1).int()
     rnd_t, init_t, pad_t, perm_t = v.given(per_room, pad_t, perm_t, shuffle, who)
+    chain = _is_chain(transform)
+    if chain:  # a transforms.TransformChain: any configured list, its draws under its own keys
+        cd = _chain_draws(transform, d, [n_out] * B, dev, generator)
     # the transform's draws (S3DISTrainAugment.draw's keys)
-    if any(k not in d for k in list(_S3DIS_TRANSFORM_KEYS) + ["noise"]):
+    if not chain and any(k not in d for k in list(_S3DIS_TRANSFORM_KEYS) + ["noise"]):
         for k, t in _s3dis_transform_draws(transform, B, n_out, dev, generator).items():
             d.setdefault(k, t)
-    for k, shape in list(_S3DIS_TRANSFORM_KEYS.items()) + [("noise", (n_out, 3))]:
+    for k, shape in [] if chain else list(_S3DIS_TRANSFORM_KEYS.items()) + [("noise", (n_out, 3))]:
         d[k] = torch.as_tensor(d[k]).to(dev)
         if d[k].shape != (B,) + shape:
             raise ValueError(f"{who}: draws[{k!r}] has shape {tuple(d[k].shape)}, not {(B,) + shape}")
@@ -746,6 +776,12 @@ def _s3dis_batch(raw, src, sizes, transform, voxel_size, voxel_max, variable, sh
         _lib.check(v.lib.amc3d_s3dis_crop_tail(B, n_out, voxel_max, f64, _opt(raw), _opt(src_t), _opt(off_t), _opt(v.coord),
                                                _opt(v.vbase), _opt(sel), _opt(order), _opt(pad_t), _opt(perm_t), _opt(pos0),
                                                _opt(colour), _opt(y), v.stream), "s3dis_crop_tail")
+    if chain:
+        out = transform({"pos": pos0, "x": colour}, draws=cd)
+        pos, x, heights = out["pos"], out["x"], out["heights"]
+        if gravity_dim != transform.gravity_dim:
+            heights = pos0[:, :, gravity_dim:gravity_dim + 1].contiguous()
+        return {"pos": pos, "x": x, "heights": heights, "y": y}
     pos, x, heights = _s3dis_augment(transform, pos0, colour, d)
     if gravity_dim != transform.g:
         heights = pos0[:, :, gravity_dim:gravity_dim + 1].contiguous()
@@ -880,14 +916,18 @@ def _scannet_batch(coord, feat, label, sizes, transform, voxel_size, voxel_max, 
     voxel_max = int(voxel_max)
     d = dict(draws or {})
     per_room = _pop_per_room(d, B, who)
-    if any(k not in d for k in _SCANNET_TRANSFORM_KEYS) or ("angle" not in d and "R" not in d):
+    chain = _is_chain(transform)
+    if not chain and (any(k not in d for k in _SCANNET_TRANSFORM_KEYS) or ("angle" not in d and "R" not in d)):
         for k, t in transform.draw(B, generator, dev).items():  # a read-back when the generator lives on the device
             d.setdefault(k, t)
     offsets = [0]
     for n in sizes:
         offsets.append(offsets[-1] + n)
     off_t = _upload(offsets, torch.int64, dev)
-    pos64, x = _scannet_transform(transform, coord, feat, off_t, d)
+    if chain:  # a transforms.TransformChain: its draws are made on the device, nothing is read back for them
+        pos64, x = _chain_rooms(transform, coord, feat, off_t, sizes, _chain_draws(transform, d, sizes, dev, generator))
+    else:
+        pos64, x = _scannet_transform(transform, coord, feat, off_t, d)
     v = _RoomVoxels("scannet", torch.float64, B, total, voxel_size, dev, (_opt(pos64), _opt(off_t)))
     # the device's own draws, enqueued before the read-back in tables sized by the point count (a room has at most as many
     # voxels as points), so the stream does not depend on the voxel counts: voxelize's randint, crop_pc's randint(N), its
@@ -984,7 +1024,8 @@ class ScanNetTrainFeed:
     def __iter__(self):
         items, dev = len(self.sizes) * self.loop, self.coord.device
         ids = torch.randperm(items, device=dev, generator=self.generator).tolist() if self.shuffle else list(range(items))
-        room_draws = self.transform.draw(items, self.generator, dev)  # host tensors, one row per item in the epoch's order
+        # host tensors, one row per item in the epoch's order; a TransformChain draws per batch, on the device
+        room_draws = {} if _is_chain(self.transform) else self.transform.draw(items, self.generator, dev)
         for i, pick in enumerate(feed_picks(ids, len(self.sizes), self.batch_size, self.drop_last)):
             lo = i * self.batch_size
             d = {k: v[lo:lo + len(pick)] for k, v in room_draws.items()}

@@ -993,6 +993,28 @@ int amc3d_augment_clouds(int b, int n, int gravity_dim, float jitter_sigma, floa
                          const float *color_std, float *pos_out, float *x_out, float *heights, void *workspace,
                          size_t workspace_bytes, void *stream);
 
+/* ---- any chain of the reference's training transforms as one compiled program (amcontrast3d_amd/transforms.py compiles a
+ * `datatransforms.train` list; csrc/transforms.hip interprets it).  Clouds are ragged: points concatenated, offsets (b+1)
+ * int64 in device memory, no empty cloud.  program: device memory, program_bytes long = {int n_ops, n_phases, stride,
+ * gravity_dim, phase_mask[4] (bit 0: position statistics, bit 1: colour statistics)} then max_ops records of 64 bytes {int
+ * code, phase (the reduction phase whose statistics the op reads, -1: none), slot (offset into the cloud's row of table),
+ * iarg (bit 0: keep float64 / has mean and std; bits 8..: per-point tensor, axis or channel mask); float f[8]; double d[2]}.
+ * table (b, stride) doubles: the per-cloud draws, already turned into what the op multiplies or adds (a float32 value is stored
+ * exactly).  noise: HOST array of 4 device pointers to the per-point draws ((total,3) float64 for the numpy classes, (total,3)
+ * or (total) float32 for the torch classes; unused entries NULL).  flags: bit 0 pos is float64, bit 1 x is ScanNet's [-1, 1]
+ * colour and becomes (x + 1) * 127.5 first, bit 2 pos_out is float64.  pos (total,3), x (total,3) fp32 -> pos_out (total,3),
+ * x_out (total,3) fp32, heights (total) fp32 or NULL (the gravity coordinate before the chain unless an op sets it).
+ * 1 + n_phases launches of one kernel: launch k replays the ops that need phases < k from the input and reduces the state each
+ * stream has at its first op of phase k (per-workgroup partials, folded in a fixed order by the next launch: no atomics, the
+ * same bits on every run); the last launch writes the outputs.  No intermediate of the batch's size is stored. */
+int amc3d_transform_max_ops(void);
+int amc3d_transform_max_phases(void);
+int amc3d_transform_program_bytes(void);
+size_t amc3d_transform_workspace_bytes(int b, long long total, int n_phases);
+int amc3d_transform_chain(int b, long long total, int n_phases, const long long *offsets, const void *program, const double *table,
+                          const void *const *noise, int flags, const void *pos, const float *x, void *pos_out, float *x_out,
+                          float *heights, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- ScanNet training input for a batch of RAW rooms (dataset/scannetv2/scannet.py:140-176: colours (feat + 1) * 127.5, the
  * chain RandomRotateZ, RandomScale, ChromaticAutoContrast, RandomDropFeature, NumpyChromaticNormalize -- transforms/
  * point_transform_cpu.py:43-92,192-209,304-332 -- on the whole room, then crop_pc and `heights`).  Rooms are ragged: points
