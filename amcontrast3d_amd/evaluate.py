@@ -266,6 +266,43 @@ def scannet_benchmark_ids(pred):
     return np.asarray(SCANNET_VALID_CLASS_IDS, dtype=pred.dtype)[pred]
 
 
+def _test_room(model, rp, make_batch, vote, label, num_classes, ignore_index, nsample, miou_B_I, batch):
+    """the sub-cloud loop of test_room_scannet / test_room_s3dis: make_batch(rows of rp["parts"]) -> the model -> the
+    boundary split per sub-cloud, then vote(logits (P,C,nvox), rp) -> (voted, pred) and the three matrices"""
+    P, nvox = rp["parts"].shape
+    cm = cm_b = cm_i = None
+    if label is not None:
+        cm, cm_b, cm_i = _matrices(num_classes, ignore_index)
+    step = max(1, int(batch))
+    logits_all = torch.empty(P, num_classes, nvox, dtype=torch.float32, device=rp["parts"].device)
+    pb, pi, tb, ti = [], [], [], []
+    for j0 in range(0, P, step):
+        data = make_batch(rp["parts"][j0:j0 + step])
+        logits = _logits(model(data))
+        logits_all[j0:j0 + step] = logits
+        if miou_B_I:
+            b = boundary_masks_stacked(data["pos"], data["y"], nsample, num_classes, ignore_index)
+            pred_stack = logits.argmax(dim=1)
+            pb.append(pred_stack[b]); pi.append(pred_stack[~b]); tb.append(data["y"][b]); ti.append(data["y"][~b])
+    voted, pred = vote(logits_all, rp)
+    if label is not None:
+        cm.update(pred, label)
+    if miou_B_I:
+        cm_b.update(torch.cat(pb), torch.cat(tb))
+        cm_i.update(torch.cat(pi), torch.cat(ti))
+    return {"pred": pred, "logits": voted, "cm": cm, "cm_b": cm_b, "cm_i": cm_i}
+
+
+def _batch_options(gravity_dim, feature_keys, color_mean, color_std):
+    """the keyword arguments of part_batch / s3dis_part_batch; None keeps the dataset's own colour constants"""
+    kw = {"gravity_dim": gravity_dim, "feature_keys": feature_keys}
+    if color_mean is not None:
+        kw["color_mean"] = color_mean
+    if color_std is not None:
+        kw["color_std"] = color_std
+    return kw
+
+
 @torch.no_grad()
 def test_room_scannet(model, coord, feat, label, voxel_size, num_classes, ignore_index, nsample,
                       feature_keys="pos,x,heights", color_mean=None, color_std=None, gravity_dim=2, miou_B_I=False,
@@ -294,33 +331,9 @@ def test_room_scannet(model, coord, feat, label, voxel_size, num_classes, ignore
         raise ValueError("test_room_scannet: the boundary / inner split needs labels")
     coord = coord - coord.min(0).values  # load_data: coord -= coord.min(0), in the array's own precision
     rp = ip.room_parts(coord, voxel_size, perm=perm, generator=generator)
-    P, nvox = rp["parts"].shape
-    kw = {"gravity_dim": gravity_dim, "feature_keys": feature_keys}
-    if color_mean is not None:
-        kw["color_mean"] = color_mean
-    if color_std is not None:
-        kw["color_std"] = color_std
-    cm = cm_b = cm_i = None
-    if label is not None:
-        cm, cm_b, cm_i = _matrices(num_classes, ignore_index)
-    step = max(1, int(batch))
-    logits_all = torch.empty(P, num_classes, nvox, dtype=torch.float32, device=dev)
-    pb, pi, tb, ti = [], [], [], []
-    for j0 in range(0, P, step):
-        data = ip.part_batch(rp["parts"][j0:j0 + step], coord, feat, label, "test", **kw)
-        logits = _logits(model(data))
-        logits_all[j0:j0 + step] = logits
-        if miou_B_I:
-            b = boundary_masks_stacked(data["pos"], data["y"], nsample, num_classes, ignore_index)
-            pred_stack = logits.argmax(dim=1)
-            pb.append(pred_stack[b]); pi.append(pred_stack[~b]); tb.append(data["y"][b]); ti.append(data["y"][~b])
-    voted, pred = ops.vote_parts(logits_all, rp)
-    if label is not None:
-        cm.update(pred, label)
-    if miou_B_I:
-        cm_b.update(torch.cat(pb), torch.cat(tb))
-        cm_i.update(torch.cat(pi), torch.cat(ti))
-    return {"pred": pred, "logits": voted, "cm": cm, "cm_b": cm_b, "cm_i": cm_i}
+    kw = _batch_options(gravity_dim, feature_keys, color_mean, color_std)
+    return _test_room(model, rp, lambda rows: ip.part_batch(rows, coord, feat, label, "test", **kw), ops.vote_parts, label,
+                      num_classes, ignore_index, nsample, miou_B_I, batch)
 
 
 @torch.no_grad()
@@ -357,33 +370,9 @@ def test_room_s3dis(model, cdata, voxel_size, num_classes, ignore_index, nsample
     coord = cdata[:, :3] - cdata[:, :3].min(0).values  # load_data: coord -= coord.min(0), in the file's own precision
     colour = cdata[:, 3:6].contiguous()
     if test_mode == "nearest_neighbor":
-        rp = ip.room_representatives(coord, voxel_size, rnd=rnd, perm=perm, generator=generator)
+        rp, vote = ip.room_representatives(coord, voxel_size, rnd=rnd, perm=perm, generator=generator), ops.expand_parts
     else:
-        rp = ip.room_parts(coord, voxel_size, perm=perm, generator=generator)
-    P, nvox = rp["parts"].shape
-    kw = {"gravity_dim": gravity_dim, "feature_keys": feature_keys}
-    if color_mean is not None:
-        kw["color_mean"] = color_mean
-    if color_std is not None:
-        kw["color_std"] = color_std
-    cm = cm_b = cm_i = None
-    if label is not None:
-        cm, cm_b, cm_i = _matrices(num_classes, ignore_index)
-    step = max(1, int(batch))
-    logits_all = torch.empty(P, num_classes, nvox, dtype=torch.float32, device=dev)
-    pb, pi, tb, ti = [], [], [], []
-    for j0 in range(0, P, step):
-        data = ip.s3dis_part_batch(rp["parts"][j0:j0 + step], coord, colour, label, "test", **kw)
-        logits = _logits(model(data))
-        logits_all[j0:j0 + step] = logits
-        if miou_B_I:
-            b = boundary_masks_stacked(data["pos"], data["y"], nsample, num_classes, ignore_index)
-            pred_stack = logits.argmax(dim=1)
-            pb.append(pred_stack[b]); pi.append(pred_stack[~b]); tb.append(data["y"][b]); ti.append(data["y"][~b])
-    voted, pred = ops.expand_parts(logits_all, rp) if test_mode == "nearest_neighbor" else ops.vote_parts(logits_all, rp)
-    if label is not None:
-        cm.update(pred, label)
-    if miou_B_I:
-        cm_b.update(torch.cat(pb), torch.cat(tb))
-        cm_i.update(torch.cat(pi), torch.cat(ti))
-    return {"pred": pred, "logits": voted, "cm": cm, "cm_b": cm_b, "cm_i": cm_i}
+        rp, vote = ip.room_parts(coord, voxel_size, perm=perm, generator=generator), ops.vote_parts
+    kw = _batch_options(gravity_dim, feature_keys, color_mean, color_std)
+    return _test_room(model, rp, lambda rows: ip.s3dis_part_batch(rows, coord, colour, label, "test", **kw), vote, label,
+                      num_classes, ignore_index, nsample, miou_B_I, batch)

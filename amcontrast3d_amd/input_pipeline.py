@@ -348,25 +348,23 @@ def room_parts(coord, voxel_size, perm=None, generator=None, tables=None):
     return {"idx_sort": idx_sort, "voxel_idx": voxel_idx, "start": start, "count": count, "parts": parts, "where": where}
 
 
-def part_batch(idx, coord, feat, label=None, mode="test", color_mean=SCANNET_COLOR_MEAN, color_std=SCANNET_COLOR_STD,
-               gravity_dim=2, feature_keys="pos,x,heights"):
-    """Sub-clouds of a room as a model batch (csrc/room_eval.hip).  idx (R,n) int32 rows of point indices into coord (N,3)
-    fp32, feat (N,3) fp32 in [-1, 1] (the .pth colours), label (N) int64 or None.  Per row: pos = coordinate minus the
-    row's minimum corner; colours `mode` 'test' clip((f + 1) / 2, 0, 1) (`load_data`) or 'val' (f + 1) * 127.5
-    (ScanNet.__getitem__), then NumpyChromaticNormalize per row; heights = pos[..., gravity_dim]; x assembled channel-major
-    from `feature_keys` (get_features_by_keys).  Returns {pos (R,n,3), x (R,Cx,n), heights (R,n,1)[, y (R,n) int64]}."""
-    _need_gpu(idx, coord, feat)
-    _need_dtype(torch.int32, idx=idx)
-    _need_dtype(torch.float32, coord=coord, feat=feat)
+def _part_batch(who, idx, coord, colour, label, mode, color_mean, color_std, gravity_dim, feature_keys, centre=None, s3dis=False):
+    """the body of part_batch and s3dis_part_batch after their dtype checks: the refusals, the outputs, the workspace and the
+    call of amc3d_<who>; `s3dis` adds what only that entry point takes: coord's dtype, a given centre, the centre output"""
     if mode not in ("test", "val"):
-        raise ValueError(f"part_batch: mode {mode!r} (test or val)")
+        raise ValueError(f"{who}: mode {mode!r} (test or val)")
+    f64 = coord.dtype == torch.float64
+    if mode == "val" and f64:
+        raise ValueError(f"{who}: the val item is float32 (S3DIS casts the room when it loads it)")
     keys = [k.strip() for k in feature_keys.split(",")]
     if not 1 <= len(keys) <= 3 or any(k not in _SEG_KINDS for k in keys):
-        raise ValueError(f"part_batch: feature_keys {feature_keys!r}: up to three of pos, x, heights")
-    if idx.dim() != 2 or coord.dim() != 2 or coord.shape[1] != 3 or feat.shape != coord.shape:
-        raise ValueError("part_batch: idx (R,n), coord (N,3), feat (N,3)")
+        raise ValueError(f"{who}: feature_keys {feature_keys!r}: up to three of pos, x, heights")
+    if idx.dim() != 2 or coord.dim() != 2 or coord.shape[1] != 3 or colour.shape != coord.shape:
+        raise ValueError(f"{who}: idx (R,n), coord (N,3), {'colour' if s3dis else 'feat'} (N,3)")
+    if s3dis and gravity_dim not in (0, 1, 2):
+        raise ValueError(f"{who}: gravity_dim is 0, 1 or 2")
     dev = coord.device
-    idx, coord, feat = idx.contiguous(), coord.contiguous(), feat.contiguous()
+    idx, coord, colour = idx.contiguous(), coord.contiguous(), colour.contiguous()
     R, n = idx.shape
     N = coord.shape[0]
     cx = sum(1 if k == "heights" else 3 for k in keys)
@@ -378,20 +376,42 @@ def part_batch(idx, coord, feat, label=None, mode="test", color_mean=SCANNET_COL
         _need_gpu(label)
         label = label.reshape(-1).to(torch.int64).contiguous()
         if label.shape[0] != N:
-            raise ValueError("part_batch: one label per room point")
+            raise ValueError(f"{who}: one label per room point")
         y = out["y"] = torch.empty(R, n, dtype=torch.int64, device=dev)
+    if centre is not None:
+        _need_gpu(centre)
+        _need_dtype(torch.float32, centre=centre)
+        if centre.shape != (R, 3):
+            raise ValueError(f"{who}: centre (R,3)")
+        centre = centre.contiguous()
     lib = _lib.load()
-    wb = int(lib.amc3d_part_batch_workspace_bytes(R))
-    work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
+    wb = int(getattr(lib, f"amc3d_{who}_workspace_bytes")(R))
+    work = torch.empty(max(wb, 8) // 8, dtype=torch.float64, device=dev)
     kinds = (ctypes.c_int * 3)(*([_SEG_KINDS[k] for k in keys] + [0] * (3 - len(keys))))
-    mean, std = _colour_constants(tuple(float(v) for v in color_mean), tuple(float(v) for v in color_std), dev)
+    mean, std = _colour_constants(tuple(float(v) for v in color_mean), tuple(float(v) for v in color_std), dev, who)
     P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    ins = [int(gravity_dim), len(keys), ctypes.cast(kinds, ctypes.c_void_p), P(idx), P(coord), P(colour), P(label), P(mean), P(std)]
+    outs = [P(out["pos"]), P(out["x"]), P(out["heights"]), P(y)]
+    if s3dis:
+        out["centre"] = torch.empty(R, 3, dtype=torch.float32, device=dev)
+        ins = [int(f64)] + ins + [P(centre)]
+        outs.append(P(out["centre"]))
     with torch.cuda.device(dev):
-        _lib.check(lib.amc3d_part_batch(R, n, N, 1 if mode == "val" else 0, int(gravity_dim), len(keys),
-                                        ctypes.cast(kinds, ctypes.c_void_p), P(idx), P(coord), P(feat), P(label), P(mean), P(std),
-                                        P(out["pos"]), P(out["x"]), P(out["heights"]), P(y), P(work), wb, _stream(coord)),
-                   "part_batch")
+        _lib.check(getattr(lib, f"amc3d_{who}")(R, n, N, 1 if mode == "val" else 0, *ins, *outs, P(work), wb, _stream(coord)), who)
     return out
+
+
+def part_batch(idx, coord, feat, label=None, mode="test", color_mean=SCANNET_COLOR_MEAN, color_std=SCANNET_COLOR_STD,
+               gravity_dim=2, feature_keys="pos,x,heights"):
+    """Sub-clouds of a room as a model batch (csrc/room_eval.hip).  idx (R,n) int32 rows of point indices into coord (N,3)
+    fp32, feat (N,3) fp32 in [-1, 1] (the .pth colours), label (N) int64 or None.  Per row: pos = coordinate minus the
+    row's minimum corner; colours `mode` 'test' clip((f + 1) / 2, 0, 1) (`load_data`) or 'val' (f + 1) * 127.5
+    (ScanNet.__getitem__), then NumpyChromaticNormalize per row; heights = pos[..., gravity_dim]; x assembled channel-major
+    from `feature_keys` (get_features_by_keys).  Returns {pos (R,n,3), x (R,Cx,n), heights (R,n,1)[, y (R,n) int64]}."""
+    _need_gpu(idx, coord, feat)
+    _need_dtype(torch.int32, idx=idx)
+    _need_dtype(torch.float32, coord=coord, feat=feat)
+    return _part_batch("part_batch", idx, coord, feat, label, mode, color_mean, color_std, gravity_dim, feature_keys)
 
 
 def scannet_val_cloud(room, voxel_size=0.02, rnd=None, generator=None, color_mean=SCANNET_COLOR_MEAN,
@@ -417,7 +437,7 @@ S3DIS_COLOR_STD = (0.18308958, 0.18415008, 0.19252081)
 def s3dis_part_batch(idx, coord, colour, label=None, mode="test", color_mean=S3DIS_COLOR_MEAN, color_std=S3DIS_COLOR_STD,
                      gravity_dim=2, feature_keys="x,heights", centre=None):
     """Sub-clouds of an S3DIS room as a model batch with the config's evaluation transforms `[PointsToTensor,
-    PointCloudXYZAlign, ChromaticNormalize]` (csrc/s3dis_eval.hip).  idx (R,n) int32 rows of point indices into coord (N,3),
+    PointCloudXYZAlign, ChromaticNormalize]` (csrc/room_eval.hip).  idx (R,n) int32 rows of point indices into coord (N,3),
     fp32 or fp64 and already at the room's minimum corner, colour (N,3) raw 0..255 in coord's dtype, label (N) or None.
     mode 'test' (`load_data` + the sub-cloud loop, main.py:73, 563-576): colour clip(f / 255, 0, 1) and coordinates minus the
     row's minimum corner, both in coord's dtype, then float32; 'val' (S3DIS.__getitem__, fp32 only): both as they are.
@@ -432,53 +452,8 @@ def s3dis_part_batch(idx, coord, colour, label=None, mode="test", color_mean=S3D
     _need_dtype(torch.int32, idx=idx)
     if coord.dtype not in (torch.float32, torch.float64) or colour.dtype != coord.dtype:
         raise RuntimeError(f"s3dis_part_batch: coord and colour are both float32 or both float64, got {coord.dtype} and {colour.dtype}")
-    if mode not in ("test", "val"):
-        raise ValueError(f"s3dis_part_batch: mode {mode!r} (test or val)")
-    f64 = coord.dtype == torch.float64
-    if mode == "val" and f64:
-        raise ValueError("s3dis_part_batch: the val item is float32 (S3DIS casts the room when it loads it)")
-    keys = [k.strip() for k in feature_keys.split(",")]
-    if not 1 <= len(keys) <= 3 or any(k not in _SEG_KINDS for k in keys):
-        raise ValueError(f"s3dis_part_batch: feature_keys {feature_keys!r}: up to three of pos, x, heights")
-    if idx.dim() != 2 or coord.dim() != 2 or coord.shape[1] != 3 or colour.shape != coord.shape:
-        raise ValueError("s3dis_part_batch: idx (R,n), coord (N,3), colour (N,3)")
-    if gravity_dim not in (0, 1, 2):
-        raise ValueError("s3dis_part_batch: gravity_dim is 0, 1 or 2")
-    dev = coord.device
-    idx, coord, colour = idx.contiguous(), coord.contiguous(), colour.contiguous()
-    R, n = idx.shape
-    N = coord.shape[0]
-    cx = sum(1 if k == "heights" else 3 for k in keys)
-    out = {"pos": torch.empty(R, n, 3, dtype=torch.float32, device=dev),
-           "x": torch.empty(R, cx, n, dtype=torch.float32, device=dev),
-           "heights": torch.empty(R, n, 1, dtype=torch.float32, device=dev)}
-    y = None
-    if label is not None:
-        _need_gpu(label)
-        label = label.reshape(-1).to(torch.int64).contiguous()
-        if label.shape[0] != N:
-            raise ValueError("s3dis_part_batch: one label per room point")
-        y = out["y"] = torch.empty(R, n, dtype=torch.int64, device=dev)
-    if centre is not None:
-        _need_gpu(centre)
-        _need_dtype(torch.float32, centre=centre)
-        if centre.shape != (R, 3):
-            raise ValueError("s3dis_part_batch: centre (R,3)")
-        centre = centre.contiguous()
-    out["centre"] = torch.empty(R, 3, dtype=torch.float32, device=dev)
-    lib = _lib.load()
-    wb = int(lib.amc3d_s3dis_part_batch_workspace_bytes(R))
-    work = torch.empty(max(wb, 8) // 8, dtype=torch.float64, device=dev)
-    kinds = (ctypes.c_int * 3)(*([_SEG_KINDS[k] for k in keys] + [0] * (3 - len(keys))))
-    mean, std = _colour_constants(tuple(float(v) for v in color_mean), tuple(float(v) for v in color_std), dev,
-                                  "s3dis_part_batch")
-    P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-    with torch.cuda.device(dev):
-        _lib.check(lib.amc3d_s3dis_part_batch(R, n, N, 1 if mode == "val" else 0, int(f64), int(gravity_dim), len(keys),
-                                              ctypes.cast(kinds, ctypes.c_void_p), P(idx), P(coord), P(colour), P(label), P(mean),
-                                              P(std), P(centre), P(out["pos"]), P(out["x"]), P(out["heights"]), P(y),
-                                              P(out["centre"]), P(work), wb, _stream(coord)), "s3dis_part_batch")
-    return out
+    return _part_batch("s3dis_part_batch", idx, coord, colour, label, mode, color_mean, color_std, gravity_dim, feature_keys,
+                       centre, s3dis=True)
 
 
 def room_representatives(coord, voxel_size, rnd=None, perm=None, generator=None, tables=None):

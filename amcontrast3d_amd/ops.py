@@ -2621,7 +2621,7 @@ def vote_parts(logits, parts_tables):
 
 def expand_parts(logits, tables):
     """`test_mode: nearest_neighbor` (main.py:605, all_logits[reverse_idx_part][voxel_idx][reverse_idx]) as one gather
-    (csrc/s3dis_eval.hip): logits (1,C,nvox) fp32, the model output of the single sub-cloud of
+    (csrc/room_eval.hip): logits (1,C,nvox) fp32, the model output of the single sub-cloud of
     input_pipeline.room_representatives, whose result is `tables` -> (voted (N,C) fp32, pred (N) int64).  Every room point
     takes the logits of its voxel's representative; pred = argmax as torch.argmax (first maximum, NaN counts as maximum)."""
     t = tables

@@ -1047,7 +1047,7 @@ int amc3d_scannet_crop_tail(int n, int gravity_dim, const double *coord, const f
  * coordinate - the row's fp32 minimum corner; colours by mode (0 test: clip((f + 1) / 2, 0, 1); 1 val: (f + 1) * 127.5), / 255
  * when the row's maximum exceeds 1 (NaN propagates: then not), (x - mean) / std; heights (rows,n) = pos[..., gravity_dim];
  * x (rows,Cx,n) channel-major = nseg <= 3 segments in the caller's order, seg_kinds[i] in {0 pos, 1 x, 2 heights}
- * (get_features_by_keys); y (rows,n) int64 when y_out is not NULL.  Two launches through the workspace.
+ * (get_features_by_keys); y (rows,n) int64 when y_out is not NULL.  Two launches through the workspace (8-byte aligned).
  * vote_parts: logits (p,num_classes,nvox) = the stacked model outputs -> voted (npts,num_classes) = the mean over the parts that
  * hold the point (rank r of count c: parts r, r + c, ... < p), summed in ascending part order in fp32 and divided by their
  * number; pred (npts) int64 = the first maximum, a NaN counting as the maximum (torch.argmax).  No atomics: reproducible bits. */

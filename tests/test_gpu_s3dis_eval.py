@@ -1,4 +1,4 @@
-"""S3DIS validation and whole-room testing on the device (csrc/s3dis_eval.hip; input_pipeline.s3dis_part_batch /
+"""S3DIS validation and whole-room testing on the device (csrc/room_eval.hip; input_pipeline.s3dis_part_batch /
 room_representatives / s3dis_val_cloud, ops.expand_parts, evaluate.test_room_s3dis) against what the reference's own code
 returned for the same rooms (tests/golden/s3dis_eval.npz, recorded by tests/tools/gen_golden_s3dis_eval.py) and against the
 numpy restatements of tests/s3dis_eval_ref.py, which tests/test_s3dis_eval_host.py pins to that fixture.

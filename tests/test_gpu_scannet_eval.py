@@ -160,6 +160,106 @@ def test_part_batch_feature_keys_against_torch(g, keys, mode):
         ip.part_batch(rp["parts"].cpu(), shifted, feat, None, mode)
 
 
+def _same(got, want, msg=""):
+    """bit-equal float32 arrays (a NaN equals a NaN)"""
+    got = got.cpu().numpy()
+    assert got.shape == want.shape and got.dtype == want.dtype == np.float32, msg
+    np.testing.assert_array_equal(got, want, err_msg=msg)  # NaN == NaN here, -0.0 == 0.0
+    assert not (np.signbit(got) != np.signbit(want))[~np.isnan(want)].any(), msg
+
+
+N_DARK = 500  # the first points of the synthetic room: (f + 1) * 127.5 <= 1 for every colour
+
+
+def _synthetic(n, R, seed, dark_last_row=False):
+    """a room of 9000 fp32 points, colours in [-1, 1], and R rows of n indices into it (with repeats); the last row draws from
+    the dark points alone when asked to"""
+    rng = np.random.default_rng(seed)
+    N = 9000
+    coord = (rng.uniform(0, 6, (N, 3)) + np.array([0.0, 0.0, 0.5])).astype(np.float32)
+    feat = rng.uniform(-1, 1, (N, 3)).astype(np.float32)
+    feat[:N_DARK] = (-1 + rng.uniform(0, 0.9 / 127.5, (N_DARK, 3))).astype(np.float32)
+    label = rng.integers(0, 20, N).astype(np.int64)
+    idx = rng.integers(N_DARK, N - 2, (R, n))  # the last two points are kept for the NaN rows
+    if dark_last_row:
+        idx[R - 1] = rng.integers(0, N_DARK, n)
+    return coord, feat, label, idx
+
+
+def _shape_case(n, R, g_dim, mode):
+    """the inputs of test_part_batch_shapes_against_the_restatement: with R = 3, row 0 holds a NaN coordinate in the gravity
+    column, row 1 a NaN colour, and in val mode row 2 only dark points"""
+    coord, feat, label, idx = _synthetic(n, R, 1000 * n + R, dark_last_row=R == 3 and mode == "val")
+    N = len(coord)
+    if R == 3:
+        coord[N - 1, g_dim] = np.nan
+        feat[N - 2, 1] = np.nan
+        idx[0, n // 2] = N - 1
+        idx[1, n // 3] = N - 2
+    return coord, feat, label, idx
+
+
+def _divides(feat, row, mode):
+    """whether NumpyChromaticNormalize divides the row by 255 (a NaN maximum: not)"""
+    x = np.clip((feat[row] + 1) / 2., 0, 1) if mode == "test" else (feat[row] + 1) * 127.5
+    return bool(x.max() > 1)
+
+
+_SHAPE_CASES = [(1, 0, "heights,pos", "val"), (3, 2, "pos,x,heights", "test"), (3, 1, "x", "val")]
+
+
+@pytest.mark.parametrize("n", [37, 257, 8200])
+@pytest.mark.parametrize("R,g_dim,keys,mode", _SHAPE_CASES)
+def test_part_batch_shapes_against_the_restatement(n, R, g_dim, keys, mode):
+    """n = 37: less than a wave; 257: one thread into the second workgroup; 8200: more than one trip of the 32 x 256 strided
+    statistics pass.  With R = 3, row 0 holds a NaN coordinate and row 1 a NaN colour: NaN where numpy makes it NaN, and row 2
+    does not notice.  In val mode both arms of the `/ 255` test run: bright rows divide, the NaN row and the dark row do not."""
+    from amcontrast3d_amd import input_pipeline as ip
+    coord, feat, label, idx = _shape_case(n, R, g_dim, mode)
+    out = ip.part_batch(_dev(idx, torch.int32), _dev(coord), _dev(feat), _dev(label), mode, gravity_dim=g_dim, feature_keys=keys)
+    cx = sum(1 if k == "heights" else 3 for k in keys.split(","))
+    assert out["pos"].shape == (R, n, 3) and out["x"].shape == (R, cx, n) and out["heights"].shape == (R, n, 1)
+    for r in range(R):
+        pos, x, heights = ref.sub_cloud(coord, feat, idx[r], mode, gravity_dim=g_dim)
+        _same(out["pos"][r], pos, f"pos row {r}")
+        _same(out["heights"][r], heights, f"heights row {r}")
+        _same(out["x"][r], ref.assemble(pos, x, heights, keys), f"input row {r}")
+        np.testing.assert_array_equal(out["y"][r].cpu().numpy(), label[idx[r]])
+    divides = [_divides(feat, idx[r], mode) for r in range(R)]
+    assert divides == {(1, "val"): [True], (3, "test"): [False] * 3, (3, "val"): [True, False, False]}[R, mode]
+    if R == 3:
+        pos0, x1 = out["pos"][0].cpu().numpy(), out["x"][1].cpu().numpy()
+        assert np.isnan(pos0[:, g_dim]).all()
+        others = [c for c in range(3) if c != g_dim]
+        assert np.isfinite(pos0[:, others]).all() and np.isfinite(out["pos"][1:].cpu().numpy()).all()
+        assert np.isfinite(out["x"][2].cpu().numpy()).all() and np.isfinite(out["heights"][1:].cpu().numpy()).all()
+        if "x" in keys.split(","):
+            assert np.isnan(x1).sum() == 1  # NaN > 1 is false: the row does not divide, and only the element stays NaN
+
+
+def test_part_batch_never_reads_outside_the_room():
+    """an index outside [0, N) is skipped: nothing is read, and the row's other points are what they are without it"""
+    from amcontrast3d_amd import input_pipeline as ip
+    coord, feat, label, idx = _synthetic(300, 2, 5)
+    N = len(coord)
+    bad = idx.copy()
+    holes = np.array([0, 17, 255, 256, 299])
+    bad[0, holes] = [N, -1, 2 ** 31 - 1, -2 ** 31, N + 1]
+    out = ip.part_batch(_dev(bad, torch.int32), _dev(coord), _dev(feat), _dev(label), "test")
+    torch.cuda.synchronize()
+    keep = np.setdiff1d(np.arange(300), holes)
+    pos, x, heights = ref.sub_cloud(coord, feat, idx[0][keep], "test")
+    _same(out["pos"][0][keep], pos)
+    _same(out["heights"][0][keep], heights)
+    _same(out["x"][0][:, keep], ref.assemble(pos, x, heights))
+    np.testing.assert_array_equal(out["y"][0][keep].cpu().numpy(), label[idx[0][keep]])
+    pos, x, heights = ref.sub_cloud(coord, feat, idx[1], "test")
+    _same(out["pos"][1], pos)
+    _same(out["heights"][1], heights)
+    _same(out["x"][1], ref.assemble(pos, x, heights))
+    np.testing.assert_array_equal(out["y"][1].cpu().numpy(), label[idx[1]])
+
+
 @pytest.mark.parametrize("tag", ["a", "b"])
 def test_scannet_val_cloud(g, tag):
     """the val item with the logged randint draw.  Which point of a voxel the draw lands on follows the order inside the voxel,
