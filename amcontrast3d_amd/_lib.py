@@ -40,6 +40,9 @@ SIGNATURES = {
     "amc3d_knnquery_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "amc3d_knnquery_uses_grid": (_i, [_i, _i, _i, _i]),
     "amc3d_knnquery": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
+    "amc3d_knn_batch_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "amc3d_knn_batch": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _sz, _i, _vp]),
+    "amc3d_knn_group_dp": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "amc3d_pointops_ballquery": (_i, [_i, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "amc3d_pointops_furthestsampling": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "amc3d_pointops_grouping_forward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),

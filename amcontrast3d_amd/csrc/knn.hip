@@ -1404,9 +1404,10 @@ AMC_API int amc3d_knnquery_uses_grid(int m, int nsample, int n, int nbatch)
 // 1 when amc3d_ball_query (support n, queries m) / amc3d_three_nn (support = known) search the cell grid, given a workspace
 AMC_API int amc3d_grid_search_pays(int b, int n, int m) { return grid_search_pays(b, n, m) ? 1 : 0; }
 
-AMC_API int amc3d_knnquery(int m, int nsample, int n, int nbatch, const float *xyz, const float *new_xyz,
-                           const int *offset, const int *new_offset, int *idx, float *dist2, void *workspace,
-                           size_t workspace_bytes, int reuse_grid, void *stream_)
+// The search behind amc3d_knnquery and amc3d_knn_batch: argument checks, route (all-pairs heap or cell grid), launches.
+static int knn_search(int m, int nsample, int n, int nbatch, const float *xyz, const float *new_xyz,
+                      const int *offset, const int *new_offset, int *idx, float *dist2, void *workspace,
+                      size_t workspace_bytes, int reuse_grid, void *stream_)
 {
     if (m <= 0) return 0;
     if (nsample <= 0 || nsample > KNN_MAXK) return bad_arg("amc3d_knnquery: nsample must be in 1..100");
@@ -1461,4 +1462,116 @@ AMC_API int amc3d_knnquery(int m, int nsample, int n, int nbatch, const float *x
                        new_offset, idx, dist2, (const int *)fb_list, (const int *)fb_count, (const GridParams *)gp,
                        (const int *)cell_start, (const float4 *)sorted);
     return launch_status("amc3d_knnquery");
+}
+
+AMC_API int amc3d_knnquery(int m, int nsample, int n, int nbatch, const float *xyz, const float *new_xyz,
+                           const int *offset, const int *new_offset, int *idx, float *dist2, void *workspace,
+                           size_t workspace_bytes, int reuse_grid, void *stream_)
+{
+    return knn_search(m, nsample, n, nbatch, xyz, new_xyz, offset, new_offset, idx, dist2, workspace, workspace_bytes,
+                      reuse_grid, stream_);
+}
+
+// ---- batched (B, N, 3) k-NN around the same search -----------------------------------------------------
+namespace amc {
+
+constexpr int KB_QT = 64;  // queries per workgroup of the epilogue
+
+struct KnnBatchWorkspace {  // the search's own layout first (so a kept grid stays where it was), then this entry's
+    size_t grid_bytes, off_s, off_q, idx, dist2, total;
+};
+
+static KnnBatchWorkspace knn_batch_layout(int b, int n, int m, int ksearch)
+{
+    KnnBatchWorkspace w;
+    w.grid_bytes = knn_layout(b * n, b * m).total;
+    w.off_s = w.grid_bytes;
+    w.off_q = align256(w.off_s + (size_t)b * 4);
+    w.idx = align256(w.off_q + (size_t)b * 4);
+    w.dist2 = align256(w.idx + (size_t)b * m * ksearch * 4);
+    w.total = align256(w.dist2 + (size_t)b * m * ksearch * 4);
+    return w;
+}
+
+// Epilogue of amc3d_knn_batch.  The search leaves (b*m, ksearch) rows of global support rows and squared distances; this
+// keeps columns 0, d, 2d, ... of them, makes the indices cloud-local and takes the root.  A workgroup serves KB_QT
+// consecutive queries of one cloud.  idx and the (b,m,k) distances are row-major in the query, so the lanes run along
+// the flattened (query, column) pair and a wave stores 64 consecutive words.  The (b,k,m) layout is contiguous in the
+// query instead: its roots go through an LDS tile (row stride odd: conflict-free both ways) and are stored with the lanes
+// running along the queries, again 64 consecutive words per wave.
+__global__ __launch_bounds__(256) void knn_batch_epilogue_kernel(int n, int m, int ksearch, int dilation, int kout,
+                                                                 const int *__restrict__ raw_idx,
+                                                                 const float *__restrict__ raw_d2, int *__restrict__ idx,
+                                                                 float *__restrict__ dist, int dist_layout)
+{
+    extern __shared__ float kb_tile[];  // KB_QT x (kout | 1), only for the (b,k,m) layout
+    const int bi = blockIdx.y;
+    const int q0 = blockIdx.x * KB_QT;
+    const int nq = min(KB_QT, m - q0);
+    const int ld = kout | 1;
+    const size_t row0 = (size_t)bi * m + q0;
+    const int first = bi * n;
+    for (int e = threadIdx.x; e < nq * kout; e += 256) {
+        const int ql = e / kout, j = e - ql * kout;
+        const size_t src = (row0 + ql) * ksearch + (size_t)j * dilation;
+        idx[row0 * kout + e] = raw_idx[src] - first;
+        if (dist) {
+            const float v = sqrtf(raw_d2[src]);  // IEEE: hipcc rounds sqrtf correctly by default, __fsqrt_rn is the native approximation
+            if (dist_layout == AMC_KNN_DIST_BMK) dist[row0 * kout + e] = v;
+            else kb_tile[ql * ld + j] = v;
+        }
+    }
+    if (!dist || dist_layout == AMC_KNN_DIST_BMK) return;  // uniform over the workgroup
+    __syncthreads();
+    for (int e = threadIdx.x; e < kout * KB_QT; e += 256) {
+        const int j = e / KB_QT, ql = e % KB_QT;
+        if (ql < nq) dist[((size_t)bi * kout + j) * m + q0 + ql] = kb_tile[ql * ld + j];
+    }
+}
+
+}  // namespace amc
+
+static bool knn_batch_sizes_ok(int b, int n, int m, int ksearch)
+{
+    const long lim = 0x7fffffffL;
+    return b > 0 && n > 0 && m > 0 && ksearch > 0 && ksearch <= KNN_MAXK && (long)b * n <= lim && (long)b * m <= lim &&
+           (long)b * m * ksearch <= lim && b <= 65535;
+}
+
+AMC_API size_t amc3d_knn_batch_workspace_bytes(int b, int n, int m, int ksearch)
+{
+    if (!knn_batch_sizes_ok(b, n, m, ksearch)) return 0;
+    return knn_batch_layout(b, n, m, ksearch).total;
+}
+
+AMC_API int amc3d_knn_batch(int b, int n, int m, int ksearch, int dilation, const float *support, const float *query,
+                            int *idx, float *dist, int dist_layout, void *workspace, size_t workspace_bytes,
+                            int reuse_grid, void *stream_)
+{
+    if (b <= 0 || m <= 0) return 0;
+    if (!knn_batch_sizes_ok(b, n, m, ksearch)) return bad_arg("amc3d_knn_batch: sizes out of range (ksearch in 1..100, int32 products)");
+    if (ksearch > n) return bad_arg("amc3d_knn_batch: ksearch exceeds the number of support points");
+    if (dilation <= 0 || ksearch % dilation != 0) return bad_arg("amc3d_knn_batch: dilation must divide ksearch");
+    if (!support || !query || !idx) return bad_arg("amc3d_knn_batch: null pointer");
+    if (dist && dist_layout != AMC_KNN_DIST_BMK && dist_layout != AMC_KNN_DIST_BKM)
+        return bad_arg("amc3d_knn_batch: unknown dist_layout");
+    const KnnBatchWorkspace w = knn_batch_layout(b, n, m, ksearch);
+    if (!workspace || workspace_bytes < w.total) return bad_arg("amc3d_knn_batch: workspace too small");
+    hipStream_t stream = (hipStream_t)stream_;
+    char *base = (char *)workspace;
+    int *off_s = (int *)(base + w.off_s);
+    // one tensor for both clouds: one offset array too, which is what the search takes for its self-search path
+    int *off_q = (query == support && m == n) ? off_s : (int *)(base + w.off_q);
+    int *raw_idx = (int *)(base + w.idx);
+    float *raw_d2 = (float *)(base + w.dist2);
+    hipLaunchKernelGGL(kg_uniform_offsets_kernel, dim3(div_up(b, 64)), dim3(64), 0, stream, b, n, m, off_s, off_q);
+    if (int st = knn_search(b * m, ksearch, b * n, b, support, query, off_s, off_q, raw_idx, raw_d2, workspace, w.grid_bytes,
+                            reuse_grid, stream_))
+        return st;
+    const int kout = ksearch / dilation;
+    const bool tile = dist && dist_layout == AMC_KNN_DIST_BKM;
+    hipLaunchKernelGGL(knn_batch_epilogue_kernel, dim3(div_up(m, KB_QT), b), dim3(256),
+                       tile ? (size_t)KB_QT * (kout | 1) * sizeof(float) : 0, stream, n, m, ksearch, dilation, kout,
+                       (const int *)raw_idx, (const float *)raw_d2, idx, dist, dist_layout);
+    return launch_status("amc3d_knn_batch");
 }

@@ -12,6 +12,12 @@ convolutions hides it completely (bench.py does this inside the captured graph).
 import torch
 
 
+def plan_key(grouper):
+    """Blocks of one stage whose groupers agree in this key share one self-query.  The grouper's class is part of it:
+    a k-NN block and a ball-query block with equal nsample never share a plan."""
+    return (type(grouper), getattr(grouper, "radius", None), getattr(grouper, "nsample", None))
+
+
 def _unwrap(model):
     return model.module if hasattr(model, "module") else model
 
@@ -47,7 +53,7 @@ def precompute_sampling(model, data, aux_stream=None, join=True):
             cache = {}
             for blk in list(stage)[1:]:  # blocks of one stage share one self-query per (radius, nsample)
                 grouper = blk.convs.grouper
-                key = (getattr(grouper, "radius", None), getattr(grouper, "nsample", None))
+                key = plan_key(grouper)
                 if key not in cache:
                     cache[key] = blk.plan(p[i + 1])
                 enc[i].append(cache[key])
@@ -97,7 +103,7 @@ def precompute_rest(model, contrast_head, data, fps, num_classes, ignore_index, 
         p.append(g["new_p"])
         for blk in list(stage)[1:]:
             grouper = blk.convs.grouper
-            key = (getattr(grouper, "radius", None), getattr(grouper, "nsample", None))
+            key = plan_key(grouper)
             if key not in cache:
                 cache[key] = blk.plan(p[i + 1])
             blocks.append(cache[key])

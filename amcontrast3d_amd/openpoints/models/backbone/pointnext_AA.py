@@ -24,6 +24,7 @@ from typing import List
 import torch
 import torch.nn as nn
 
+from amcontrast3d_amd.geometry import plan_key
 from amcontrast3d_amd.ops import point_major_rows
 
 from ..build import MODELS
@@ -215,7 +216,7 @@ class PointNextEncoder_AMContrast3D(nn.Module):
                     p = g['new_p']
                 else:
                     grouper = blk.convs.grouper
-                    key = (getattr(grouper, 'radius', None), getattr(grouper, 'nsample', None))
+                    key = plan_key(grouper)
                     if key not in cache:
                         cache[key] = blk.plan(p)
                     g = cache[key]

@@ -547,6 +547,84 @@ def knnquery_squared(nsample, xyz, new_xyz, offset, new_offset):
         _knn_squared = prev
 
 
+KNN_BATCH_MAX = 100  # the search's heap (amc3d_knnquery: nsample <= 100)
+_KNN_DIST_LAYOUT = {"bmk": 0, "bkm": 1}  # AMC_KNN_DIST_BMK / AMC_KNN_DIST_BKM
+
+
+@torch.no_grad()
+def knn_batch(k, support, query=None, dilation=1, dist=None):
+    """support (B,N,3), query (B,M,3) (None: the support itself) -> (dist or None, idx): idx (B,M,k) int32 cloud-local,
+    column j the (j*dilation)-th of the k*dilation nearest support points, in amc3d_knnquery's order; dist the euclidean
+    distances of those columns as (B,M,k) ('bmk') or (B,k,M) ('bkm').  Coordinates carry no gradient."""
+    if query is None:
+        query = support
+    assert support.is_contiguous() and query.is_contiguous()
+    _need_gpu(support, query)
+    _need_dtype(torch.float32, support=support, query=query)
+    if support.dim() != 3 or query.dim() != 3 or support.shape[2] != 3 or query.shape[2] != 3 or support.shape[0] != query.shape[0]:
+        raise RuntimeError(f"knn_batch: expected (B,N,3) and (B,M,3), got {tuple(support.shape)} and {tuple(query.shape)}")
+    k, dilation = int(k), int(dilation)
+    ksearch = k * dilation
+    B, N, _ = support.shape
+    M = query.shape[1]
+    if k <= 0 or dilation <= 0 or ksearch > KNN_BATCH_MAX:
+        raise RuntimeError(f"knn_batch: k * dilation must be in 1..{KNN_BATCH_MAX}, got {k} * {dilation}")
+    if ksearch > N:
+        raise RuntimeError(f"knn_batch: k * dilation = {ksearch} out of range for {N} support points")
+    if dist is not None and dist not in _KNN_DIST_LAYOUT:
+        raise ValueError(f"knn_batch: dist must be None, 'bmk' or 'bkm', got {dist!r}")
+    dev = support.device
+    idx = torch.empty(B, M, k, dtype=torch.int32, device=dev)
+    out = None if dist is None else torch.empty((B, M, k) if dist == "bmk" else (B, k, M), dtype=torch.float32, device=dev)
+    if B == 0 or M == 0:
+        return out, idx
+    lib = _lib.load()
+    wbytes = int(lib.amc3d_knn_batch_workspace_bytes(B, N, M, ksearch))
+    if wbytes == 0:
+        raise RuntimeError("knn_batch: sizes out of range for 32-bit indices")
+    # inside `with knn_grid_reuse():` searches over the same support share one cell grid (KNNQuery's key; the uniform
+    # segment ends live in the workspace, so the points per cloud stand in for the offset tensor)
+    key = (support.data_ptr(), B * N, ("uniform", N), B, _stream(support).value)
+    cached = _grid_cache.get(key) if _grid_cache is not None else None
+    gridded = bool(lib.amc3d_knnquery_uses_grid(B * M, ksearch, B * N, B))
+    reuse = gridded and cached is not None and cached.numel() >= wbytes
+    work = cached if reuse else torch.empty(wbytes, dtype=torch.uint8, device=dev)
+    if _grid_cache is not None and gridded and not reuse:
+        _grid_cache[key] = work
+    same = query.data_ptr() == support.data_ptr() and M == N
+    with torch.cuda.device(dev), timing.span("knn_batch", B * (N + M) * 12 + idx.numel() * (4 if out is None else 8),
+                                             moved=B * (N + M) * 12 + B * M * ksearch * 16 + idx.numel() * 8):
+        _lib.check(lib.amc3d_knn_batch(B, N, M, ksearch, dilation, _ptr(support), _ptr(support if same else query), _ptr(idx),
+                                       _ptr(out) if out is not None else None, _KNN_DIST_LAYOUT.get(dist, 0), _ptr(work),
+                                       work.numel(), int(reuse), _stream(support)), "knn_batch")
+    return out, idx
+
+
+@torch.no_grad()
+def knn_group_dp(idx, query, support, relative=True, normalize=False):
+    """idx (B,M,K) int32 cloud-local, query (B,M,3), support (B,N,3) -> dp (B,3,M,K) = support[idx] (- query if relative);
+    normalize: every cloud divided by its largest sqrt((x*x + y*y) + z*z) over (M,K), taken after the subtraction
+    (KNNGroup, group.py:310-315).  Coordinates carry no gradient.  There is no grid here, so nothing of
+    knn_grid_reuse() applies."""
+    assert idx.is_contiguous() and query.is_contiguous() and support.is_contiguous()
+    _need_gpu(idx, query, support)
+    _need_dtype(torch.float32, query=query, support=support)
+    _need_dtype(torch.int32, idx=idx)
+    B, M, K = idx.shape
+    N = support.shape[1]
+    if support.shape != (B, N, 3) or query.shape != (B, M, 3):
+        raise RuntimeError(f"knn_group_dp: idx {tuple(idx.shape)}, query {tuple(query.shape)}, support {tuple(support.shape)}")
+    dev = support.device
+    dp = torch.empty(B, 3, M, K, dtype=torch.float32, device=dev)
+    cloud_max = torch.empty(B, dtype=torch.float32, device=dev) if normalize else None
+    with torch.cuda.device(dev), timing.span("knn_group_dp", idx.numel() * (4 + 12 + 12) + B * M * 12,
+                                             moved=idx.numel() * (4 + 12 + 12 + (24 if normalize else 0)) + B * M * 12):
+        _lib.check(_lib.load().amc3d_knn_group_dp(B, N, M, K, _ptr(support), _ptr(query), _ptr(idx), int(bool(relative)),
+                                                  int(bool(normalize)), _ptr(dp), _ptr(cloud_max) if normalize else None,
+                                                  _stream(support)), "knn_group_dp")
+    return dp
+
+
 # ----------------------------------------------------------------------------------------------
 # adaptive-margin contrastive loss (no native counterpart in the reference: it runs these as
 # torch ops + a Python loop -- AMContrast3D/MarginContrast.py, AEF/ambiguity.py, AEF/utils.py)

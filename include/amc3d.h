@@ -173,6 +173,27 @@ int amc3d_knnquery(int m, int nsample, int n, int nbatch, const float *xyz, cons
                    const int *offset, const int *new_offset, int *idx, float *dist2,
                    void *workspace, size_t workspace_bytes, int reuse_grid, void *stream);
 
+/* k-NN over (b,n,3) / (b,m,3) batches, for models/layers/knn.py and group.py's KNN / DilatedKNN / KNNGroup (the reference
+ * composes cdist + topk).  The search is amc3d_knnquery's over uniform segments: same distances, same order of equal
+ * distances.  support (b,n,3), query (b,m,3) -> idx (b,m,ksearch/dilation) int32, CLOUD-LOCAL, columns 0, d, 2d, ... of
+ * the ksearch nearest; dist NULL, or the EUCLIDEAN distances of those columns as fp32 (b,m,k) [AMC_KNN_DIST_BMK] or
+ * (b,k,m) [AMC_KNN_DIST_BKM, what group.py's KNN returns].  dilation divides ksearch; ksearch <= 100 and <= n.
+ * query == support (with m == n) takes the search's self-search path.  reuse_grid as for amc3d_knnquery: the workspace
+ * was last used by this entry with the same support.  No allocation, no synchronisation, no memset node. */
+#define AMC_KNN_DIST_BMK 0
+#define AMC_KNN_DIST_BKM 1
+size_t amc3d_knn_batch_workspace_bytes(int b, int n, int m, int ksearch);
+int amc3d_knn_batch(int b, int n, int m, int ksearch, int dilation, const float *support, const float *query,
+                    int *idx, float *dist, int dist_layout, void *workspace, size_t workspace_bytes,
+                    int reuse_grid, void *stream);
+
+/* KNNGroup's coordinates (group.py:310-315): dp (b,3,m,k) = support[idx] (- query when `relative`); with `normalize`
+ * every cloud is then divided by its own max over (m,k) of sqrt((x*x + y*y) + z*z), taken after the subtraction, which
+ * is left in cloud_max (b) (an integer atomic max on the bit pattern: order-independent).  idx (b,m,k) int32
+ * cloud-local, clamped to the cloud.  query may be NULL without `relative`, cloud_max without `normalize`. */
+int amc3d_knn_group_dp(int b, int n, int m, int k, const float *support, const float *query, const int *idx,
+                       int relative, int normalize, float *dp, float *cloud_max, void *stream);
+
 /* The other ten entry points of pointops_api.cpp:14-24 (csrc/pointops.hip).  Layouts: xyz (n,3), new_xyz (m,3), features
  * channel-last (rows of c floats), idx (rows, nsample) int32 GLOBAL row ids, offset / new_offset cumulative segment ends
  * with nbatch entries.  Arithmetic as the reference writes it, left to right, fp32, no FMA.  Every product of sizes that

@@ -4,6 +4,14 @@ as in the training step.  Prints every search's time (device events, mean of `re
 trace of one pass over the seven, the time per kernel family (kg_query*, knn_exact_list, the grid build).
 
     python tools/knn_bench.py [reps=20]
+
+    python tools/knn_bench.py --batched B N M k [dilation=1]
+
+the k-NN grouper instead: the kernel route (ops.knn_batch, group.py's KNN layout) against the torch composition the
+reference writes (cdist + topk + strided pick), and KNNGroup.forward (normalize_dp, with features) against
+grouping_operation + subtract + amax + divide on the same indices.  Queries are an FPS pick of the support (M < N) or the
+support itself (M == N).  Both sides warmed up, then timed alternately in five rounds of device-event windows of at least
+0.3 s each; the median and the spread over the rounds are printed.
 """
 import collections
 import os
@@ -14,6 +22,71 @@ import torch
 from amcontrast3d_amd import ops, synthetic
 
 dev = torch.device("cuda:0")
+
+
+def batched(B, N, M, k, dilation=1):
+    import statistics
+    import amcontrast3d_amd
+    amcontrast3d_amd.activate()
+    from openpoints.models.layers.group import KNNGroup, grouping_operation
+    assert torch.cuda.is_available(), "timings need the GPU"
+    sup = torch.from_numpy(synthetic.make_batch(B, N)["pos"]).to(dev)
+    if M == N:
+        qry = sup
+    else:
+        pick = ops.furthest_point_sample(sup, M).long()
+        qry = torch.gather(sup, 1, pick.unsqueeze(-1).expand(-1, -1, 3)).contiguous()
+    feat = torch.randn(B, 32, N, device=dev)
+    grouper = KNNGroup(k, normalize_dp=True)
+
+    def kernel_search():
+        return ops.knn_batch(k, sup, qry, dilation=dilation, dist="bkm")
+
+    def torch_search():
+        kd = torch.cdist(sup, qry).topk(k=k * dilation, dim=1, largest=False)
+        return kd.values, kd.indices.transpose(1, 2)[:, :, ::dilation].contiguous().int()
+
+    def kernel_group():
+        return grouper(qry, sup, feat)
+
+    def torch_group():
+        i = ops.knn_batch(k, sup, qry)[1]  # the same search on both sides: the difference is the coordinate arithmetic
+        dp = grouping_operation(sup.transpose(1, 2).contiguous(), i)
+        dp -= qry.transpose(1, 2).unsqueeze(-1)
+        dp /= torch.amax(torch.sqrt(torch.sum(dp ** 2, dim=1)), dim=(1, 2)).view(-1, 1, 1, 1)
+        return dp, grouping_operation(feat, i)
+
+    def window(fn, n):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(n):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / n * 1e3
+
+    def compare(name, new, old):
+        for fn in (new, old):
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        counts = [max(3, int(0.3e6 / max(window(fn, 3), 1.0))) for fn in (new, old)]
+        rounds = [(window(new, counts[0]), window(old, counts[1])) for _ in range(5)]
+        tn, to = [statistics.median(r[i] for r in rounds) for i in (0, 1)]
+        spread = [max(r[i] for r in rounds) - min(r[i] for r in rounds) for i in (0, 1)]
+        print(f"{name}: kernel route {tn:9.1f} us (spread {spread[0]:.1f}), torch composition {to:9.1f} us (spread {spread[1]:.1f}), "
+              f"ratio {to / tn:.2f}")
+
+    with torch.no_grad():
+        print(f"B={B} N={N} M={M} k={k} dilation={dilation} (synthetic rooms)")
+        compare("search (B,k,M) distances + (B,M,k) indices", kernel_search, torch_search)
+        compare("KNNGroup.forward, normalize_dp, 32 feature channels", kernel_group, torch_group)
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "--batched":
+    batched(*[int(v) for v in sys.argv[2:7]])
+    sys.exit(0)
+
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 B, N = 8, 24000
 pos = torch.from_numpy(synthetic.make_batch(B, N)["pos"]).to(dev)
