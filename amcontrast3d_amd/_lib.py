@@ -40,6 +40,7 @@ SIGNATURES = {
     "amc3d_knnquery_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "amc3d_knnquery_uses_grid": (_i, [_i, _i, _i, _i]),
     "amc3d_knnquery": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
+    "amc3d_knn_prefix": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
     "amc3d_knn_batch_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "amc3d_knn_batch": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _sz, _i, _vp]),
     "amc3d_knn_group_dp": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
@@ -58,6 +59,8 @@ SIGNATURES = {
     "amc3d_posmask": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     "amc3d_ambiguity_workspace_bytes": (_sz, [_i]),
     "amc3d_ambiguity": (_i, [_i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "amc3d_loss_rows_supported": (_i, [_i]),
+    "amc3d_loss_rows": (_i, [_i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_contrast_csr_workspace_bytes": (_sz, [_i]),
     "amc3d_contrast_csr": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_contrast_backward_csr_supported": (_i, [_i]),
@@ -216,6 +219,7 @@ SIGNATURES = {
 
 
 CONTRAST_MAX_STAGES = 8  # AMC_CONTRAST_MAX_STAGES
+KNN_FALLBACK_COUNT_OFFSET = 1024  # AMC_KNN_FALLBACK_COUNT_OFFSET
 
 
 class ContrastStageDesc(ctypes.Structure):

@@ -1125,9 +1125,66 @@ __global__ __launch_bounds__(1024) void knn_exact_list_kernel(
             }
             if (lane < nsample) {
                 idx[(size_t)pt * nsample + lane] = hp.id;
-                dist2[(size_t)pt * nsample + lane] = hp.d;
+                if (dist2) dist2[(size_t)pt * nsample + lane] = hp.d;  // (amc3d_knn_prefix: the caller may not want them)
             }
         }
+    }
+}
+
+// ---- k nearest as the PREFIX of a finished row (amc3d_knn_prefix) -------------------------------------------------
+// The loss votes the labels of its coarser stages over the kr = 4 / 16 nearest full-resolution points of every stage
+// point -- and a stage point IS a full-resolution point, whose 24 nearest the stage-0 self search has just stored in
+// ascending distance.  Where the first kr + 1 distances of that row are pairwise different (strictly ascending) the
+// reference's kr-heap output is determined by the distances alone (see "Exactness" above): columns 0..kr-1 of the row,
+// whichever of the search kernels or the replay wrote it.  The distances of the row are dist2_ref of the same bits.
+// 32 lanes per query: they scan the query's own grid cell for the support points with equal coordinates (exactly one
+// must match: with coincident points the row found need not be the query's in the reference's tie order, and the rows
+// of both carry a zero-distance tie anyway), check the row, and copy; everything else goes to the replay list.
+// Every cross-lane operation is wave-wide; a group without a query is predicated off.
+__global__ __launch_bounds__(256) void kg_prefix_kernel(int m, int kr, int nb, int row_stride, const float *__restrict__ new_xyz,
+                                                        const int *__restrict__ new_offset, const GridParams *__restrict__ gp,
+                                                        const int *__restrict__ cell_start, const float4 *__restrict__ sorted,
+                                                        const int *__restrict__ rows_idx, const float *__restrict__ rows_d2,
+                                                        int *__restrict__ idx, float *__restrict__ dist2,
+                                                        int *__restrict__ fb_list, int *__restrict__ fb_count)
+{
+    const int lane = threadIdx.x & 63, gl = lane & 31;
+    const long qg = ((long)blockIdx.x * 256 + threadIdx.x) >> 5;
+    const bool act = qg < m;
+    const int q = act ? (int)qg : 0;
+    const GridParams g = *gp;
+    const int seg = nb > 1 ? seg_of(q, new_offset, nb) : 0;
+    const float qx = new_xyz[(size_t)q * 3], qy = new_xyz[(size_t)q * 3 + 1], qz = new_xyz[(size_t)q * 3 + 2];
+    const int cx = cell_coord(qx, g.minx, g.inv_h, g.nx), cy = cell_coord(qy, g.miny, g.inv_h, g.ny),
+              cz = cell_coord(qz, g.minz, g.inv_h, g.nz);
+    const size_t cell = (size_t)seg * g.ncell + ((size_t)cz * g.ny + cy) * g.nx + cx;
+    const int b = cell_start[cell];
+    const int len = act ? cell_start[cell + 1] - b : 0;
+    const int wave_len = max(len, __shfl_xor(len, 32, 64));
+    int found = 0, cnt = 0;
+    for (int c0 = 0; c0 < wave_len; c0 += 32) {  // (a few points per cell)
+        const int c = c0 + gl;
+        const bool valid = c < len;
+        const float4 pt = sorted[valid ? b + c : 0];
+        const bool match = valid && pt.x == qx && pt.y == qy && pt.z == qz;
+        const unsigned bits = grp_bits<32>(__ballot(match), lane);
+        cnt += (int)__popc(bits);
+        const int v = __shfl(__float_as_int(pt.w), (lane & 32) + (bits ? (int)__builtin_ctz(bits) : 0), 64);
+        if (bits) found = v;
+    }
+    const bool one = act && cnt == 1;
+    const size_t row = one ? (size_t)found * row_stride : 0;
+    const float d = gl <= kr ? rows_d2[row + gl] : 0.f;  // kr <= 31: columns 0..kr sit in the group's lanes
+    const float dnext = __shfl_down(d, 1, 64);
+    const bool bad = (gl < kr && !(d < dnext)) || (gl == kr && !(d < 1e10f));
+    const bool use = one && grp_bits<32>(__ballot(bad), lane) == 0;
+    if (use) {
+        if (gl < kr) {
+            idx[(size_t)q * kr + gl] = rows_idx[row + gl];
+            if (dist2) dist2[(size_t)q * kr + gl] = d;
+        }
+    } else if (act && gl == 0) {
+        fb_list[atomicAdd(fb_count, 1)] = q;
     }
 }
 
@@ -1470,6 +1527,37 @@ AMC_API int amc3d_knnquery(int m, int nsample, int n, int nbatch, const float *x
 {
     return knn_search(m, nsample, n, nbatch, xyz, new_xyz, offset, new_offset, idx, dist2, workspace, workspace_bytes,
                       reuse_grid, stream_);
+}
+
+AMC_API int amc3d_knn_prefix(int m, int kr, int n, int nbatch, const float *xyz, const float *new_xyz, const int *offset,
+                             const int *new_offset, int k0, int row_stride, const int *rows_idx, const float *rows_d2,
+                             int *idx, float *dist2, void *workspace, size_t workspace_bytes, int reuse_grid, void *stream_)
+{
+    if (m <= 0) return 0;
+    if (kr <= 0 || kr >= k0 || kr >= 32 || row_stride < k0 || nbatch <= 0 || nbatch > 64 || n <= 0 || !xyz || !new_xyz ||
+        !offset || !new_offset || !rows_idx || !rows_d2 || !idx)
+        return bad_arg("amc3d_knn_prefix: bad argument (0 < kr < k0 <= row_stride, kr <= 31, nbatch <= 64)");
+    if (!reuse_grid && n < 4 * KG_SAMPLES) return bad_arg("amc3d_knn_prefix: too few support points to build a grid");
+    hipStream_t stream = (hipStream_t)stream_;
+    const KnnWorkspace w = knn_layout(n, m);
+    if (!workspace || workspace_bytes < w.total) return bad_arg("amc3d_knn_prefix: workspace too small");
+    char *base = (char *)workspace;
+    static_assert(AMC_KNN_FALLBACK_COUNT_OFFSET == 1024, "knn_layout: fb_count");
+    if (reuse_grid) {  // as amc3d_knnquery: the grid of this support stays, the replay counter is reset
+        hipLaunchKernelGGL(kg_init_kernel, dim3(1), dim3(64), 0, stream, (int *)(base + w.bbox), (int *)(base + w.fb_count));
+    } else if (int st = kg_build(w, base, n, m, nbatch, xyz, new_xyz, offset, new_offset, (kr + 3) / 4, 4, 0.7f, 0.f, stream)) {
+        return st;
+    }
+    const GridParams *gp = (const GridParams *)(base + w.params);
+    int *fb_count = (int *)(base + w.fb_count);
+    const int *cell_start = (const int *)(base + w.cell_start);
+    const float4 *sorted = (const float4 *)(base + w.sorted);
+    int *fb_list = (int *)(base + w.fb_list);
+    hipLaunchKernelGGL(kg_prefix_kernel, dim3(div_up((long)m * 32, 256)), dim3(256), 0, stream, m, kr, nbatch, row_stride, new_xyz,
+                       new_offset, gp, cell_start, sorted, rows_idx, rows_d2, idx, dist2, fb_list, fb_count);
+    hipLaunchKernelGGL(knn_exact_list_kernel, dim3(256), dim3(1024), 0, stream, kr, nbatch, xyz, new_xyz, offset, new_offset,
+                       idx, dist2, (const int *)fb_list, (const int *)fb_count, gp, cell_start, sorted);
+    return launch_status("amc3d_knn_prefix");
 }
 
 // ---- batched (B, N, 3) k-NN around the same search -----------------------------------------------------

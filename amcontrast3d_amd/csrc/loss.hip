@@ -96,6 +96,81 @@ __global__ __launch_bounds__(256) void ambiguity_stats_kernel(int m, int k, int 
     if ((threadIdx.x & 63) == 0 && w > 0) atomicMax(max_npos, w);
 }
 
+// posmask_kernel and ambiguity_stats_kernel as ONE pass over the neighbour rows.  The stats kernel runs a thread per point:
+// a wave instruction then reads 64 different rows, 96 bytes apart, and gathers 64 unrelated coordinates, k times in a row,
+// after posmask_kernel has read the same rows and gathered the same neighbours' labels.  Here a workgroup takes LR_PTS
+// consecutive points and the lanes run along their flattened (point, slot) pairs: a wave reads consecutive words of nbr
+// (one gap per row where nbr_stride > k), gathers label and coordinates of neighbour x once, stores the mask byte and
+// leaves the edge's term in LDS.  Then one lane per point adds its k terms in ascending slot order from 0.f -- the
+// expressions and the order of ambiguity_stats_kernel, so n+, d+, d- and the mask carry the same bits.
+constexpr int LR_PTS = 128;  // points per workgroup (LDS: 5 bytes per edge, 20 per point)
+
+__global__ __launch_bounds__(256) void loss_rows_kernel(int m, int k, int nbr_stride, int mode, const int *__restrict__ labels,
+                                                        const float *__restrict__ p, const int *__restrict__ nbr,
+                                                        unsigned char *__restrict__ posmask, int *__restrict__ n_pos,
+                                                        float *__restrict__ d_pos, float *__restrict__ d_neg,
+                                                        int *__restrict__ max_npos)
+{
+    extern __shared__ float lr_lds[];  // [LR_PTS * k] edge terms | [LR_PTS * 4] x, y, z, |p|^2 | [LR_PTS] labels | mask bytes
+    float *s_dd = lr_lds;
+    float *s_pt = s_dd + LR_PTS * k;
+    int *s_lab = (int *)(s_pt + LR_PTS * 4);
+    unsigned char *s_pm = (unsigned char *)(s_lab + LR_PTS);
+    const int i0 = blockIdx.x * LR_PTS;
+    const int npts = min(LR_PTS, m - i0);
+    if ((int)threadIdx.x < npts) {
+        const size_t i = (size_t)i0 + threadIdx.x;
+        const float px = p[i * 3], py = p[i * 3 + 1], pz = p[i * 3 + 2];
+        s_pt[threadIdx.x * 4] = px;
+        s_pt[threadIdx.x * 4 + 1] = py;
+        s_pt[threadIdx.x * 4 + 2] = pz;
+        s_pt[threadIdx.x * 4 + 3] = __fadd_rn(__fadd_rn(__fmul_rn(px, px), __fmul_rn(py, py)), __fmul_rn(pz, pz));
+        s_lab[threadIdx.x] = labels[i];
+    }
+    __syncthreads();
+    const int nedge = npts * k;
+    for (int e = threadIdx.x; e < nedge; e += 256) {
+        const int il = e / k, j = e - il * k;
+        const int nb = nbr[((size_t)i0 + il) * nbr_stride + j];
+        const bool pos = labels[nb] == s_lab[il];
+        float dd = 0.f;
+        if (mode != 1) {  // (Method1 stores the constant 5: ambiguity.py:24-25)
+            const float px = s_pt[il * 4], py = s_pt[il * 4 + 1], pz = s_pt[il * 4 + 2], ss = s_pt[il * 4 + 3];
+            const float qx = p[(size_t)nb * 3], qy = p[(size_t)nb * 3 + 1], qz = p[(size_t)nb * 3 + 2];
+            const float dot = __fadd_rn(__fadd_rn(__fmul_rn(px, qx), __fmul_rn(py, qy)), __fmul_rn(pz, qz));
+            const float sd = __fadd_rn(__fadd_rn(__fmul_rn(qx, qx), __fmul_rn(qy, qy)), __fmul_rn(qz, qz));
+            dd = __fadd_rn(__fadd_rn(__fmul_rn(-2.f, dot), ss), sd);
+            if (mode == 3) dd = sqrtf(__fadd_rn(fabsf(dd), 1e-12f));  // ambiguity.py:49
+        }
+        posmask[(size_t)i0 * k + e] = pos ? 1 : 0;
+        s_dd[e] = dd;
+        s_pm[e] = pos ? 1 : 0;
+    }
+    __syncthreads();
+    if (threadIdx.x >= LR_PTS) return;  // (whole waves: LR_PTS is a multiple of 64)
+    int np = 0;
+    if ((int)threadIdx.x < npts) {
+        const float *dd_i = s_dd + threadIdx.x * k;
+        const unsigned char *pm_i = s_pm + threadIdx.x * k;
+        float dp = 0.f, dn = 0.f;
+        for (int j = 0; j < k; ++j) {
+            const float dd = dd_i[j];
+            const bool pos = pm_i[j] != 0;
+            np += pos ? 1 : 0;
+            dp = __fadd_rn(dp, pos ? dd : 0.f);
+            dn = __fadd_rn(dn, pos ? 0.f : dd);
+        }
+        const size_t i = (size_t)i0 + threadIdx.x;
+        n_pos[i] = np;
+        d_pos[i] = mode == 1 ? 5.f : dp;
+        d_neg[i] = mode == 1 ? 5.f : dn;
+    }
+    // wave max, then one atomic per wave
+    int w = np;
+    for (int s = 32; s >= 1; s >>= 1) w = max(w, __shfl_xor(w, s, 64));
+    if ((threadIdx.x & 63) == 0 && w > 0) atomicMax(max_npos, w);
+}
+
 // a_i (ambiguity.py:13-14, 56-61, 71): |n+ - max|/max; for 0 < n+ < max:
 // 1 / (1 + e^(beta * (n+/d+ - n-/d-)))  with e = fp32(math.e) raised by pow as torch does
 __global__ void ambiguity_kernel(int m, int k, float beta, const int *__restrict__ n_pos,
@@ -1878,6 +1953,31 @@ AMC_API int amc3d_ambiguity(int m, int k, int nbr_stride, int mode, float beta, 
     hipLaunchKernelGGL(ambiguity_kernel, dim3(div_up(m, 256)), dim3(256), 0, stream, m, k, beta, n_pos, d_pos, d_neg,
                        max_npos, a);
     return launch_status("amc3d_ambiguity");
+}
+
+AMC_API int amc3d_loss_rows_supported(int k) { return (k >= 1 && k <= 64) ? 1 : 0; }
+
+AMC_API int amc3d_loss_rows(int m, int k, int nbr_stride, int mode, float beta, const int *labels, const float *p,
+                            const int *nbr, unsigned char *posmask, float *a, void *workspace, size_t workspace_bytes,
+                            void *stream_)
+{
+    if (m <= 0) return 0;
+    if (!amc3d_loss_rows_supported(k) || nbr_stride < k || mode < 1 || mode > 3 || !labels || !p || !nbr || !posmask ||
+        !workspace || workspace_bytes < amc3d_ambiguity_workspace_bytes(m))
+        return bad_arg("amc3d_loss_rows: bad argument (k must be in 1..64)");
+    hipStream_t stream = (hipStream_t)stream_;
+    int *max_npos = (int *)workspace;  // amc3d_ambiguity's layout
+    int *n_pos = (int *)((char *)workspace + 64);
+    float *d_pos = (float *)(n_pos + m);
+    float *d_neg = d_pos + m;
+    if (int st = fill_i32(max_npos, 0, 1, stream)) return st;
+    const size_t lds = (size_t)LR_PTS * (5 * (size_t)k + 20);
+    hipLaunchKernelGGL(loss_rows_kernel, dim3(div_up(m, LR_PTS)), dim3(256), lds, stream, m, k, nbr_stride, mode, labels, p,
+                       nbr, posmask, n_pos, d_pos, d_neg, max_npos);
+    if (a)
+        hipLaunchKernelGGL(ambiguity_kernel, dim3(div_up(m, 256)), dim3(256), 0, stream, m, k, beta, n_pos, d_pos, d_neg,
+                           max_npos, a);
+    return launch_status("amc3d_loss_rows");
 }
 
 AMC_API size_t amc3d_select_anchors_ints(int m) { return (size_t)(m > 0 ? m : 0) + 1 + (size_t)div_up(m > 0 ? m : 1, 256); }

@@ -22,7 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from openpoints.cpp.pointops.functions import pointops
-from .AEF.ambiguity import ambiguity_function
+from .AEF.ambiguity import _LazyShares, ambiguity_function
 from .AEF.function import _eps
 from .AEF.utils import fetch_pxo, get_ftype, get_subscene_class, get_subscene_label_CBL  # noqa: F401
 
@@ -43,9 +43,15 @@ def plan_stage(n, i, stageACE_list, target, nstride, num_classes, ignore_index, 
     knn = ops.knnquery_squared if p.is_cuda else pointops.knnquery  # (distances: any monotone image serves contrast_mutual)
     neighbor_idx, neighbor_d2 = knn(ambiguity_args.nsample, p, p, o, o)
     neighbor_idx = neighbor_idx[..., 1:]  # drop the self match: a strided view, no copy
-    posmask = ops.posmask_from_labels(labels, neighbor_idx)
-    a, shares = ambiguity_function(p, posmask, neighbor_idx.shape[1], neighbor_idx, ambiguity_args.cctype,
-                                   ambiguity_args.ccbeta, ambiguity_args.vis, ambiguity_args.nu)
+    if (not ambiguity_args.vis and ambiguity_args.cctype in ('Method1', 'Method2', 'Method3')
+            and ops.loss_rows_supported(p, labels, neighbor_idx)):
+        # mask and neighbourhood statistics in one pass over the neighbour rows: the same bits as the two calls below
+        posmask, a = ops.posmask_and_ambiguity(labels, p.contiguous(), neighbor_idx, ambiguity_args.cctype, ambiguity_args.ccbeta)
+        shares = _LazyShares(a, ambiguity_args.nu)
+    else:
+        posmask = ops.posmask_from_labels(labels, neighbor_idx)
+        a, shares = ambiguity_function(p, posmask, neighbor_idx.shape[1], neighbor_idx, ambiguity_args.cctype,
+                                       ambiguity_args.ccbeta, ambiguity_args.vis, ambiguity_args.nu)
     # the anchors the loss keeps (0 < a <= 1, :250-252) as a compact list for the fused contrast kernels
     anchors = ops.select_anchors(a) if a.is_cuda and a.dtype == torch.float32 else None
     # Reverse structure for the loss backward, so that it GATHERS every gradient row instead of scattering rows with float

@@ -473,6 +473,7 @@ def three_interpolation(unknown_xyz, known_xyz, know_feat):
 
 
 _grid_cache = None  # {(support ptr, n, offset ptr, segments, stream): workspace} while knn_grid_reuse() is active
+#                    and {("rows", support ptr, ...): (idx, dist2)} of a self search over that grid (knn_of_support_points)
 
 
 class knn_grid_reuse:
@@ -522,6 +523,8 @@ class KNNQuery(Function):
             _lib.check(lib.amc3d_knnquery(m, nsample, n, nb, _ptr(xyz), _ptr(new_xyz), _ptr(offset),
                                           _ptr(new_offset), _ptr(idx), _ptr(dist2), _ptr(work), work.numel(),
                                           int(reuse), _stream(xyz)), "knnquery")
+        if _grid_cache is not None and gridded and m == n and new_xyz.data_ptr() == xyz.data_ptr() and new_offset.data_ptr() == offset.data_ptr():
+            _grid_cache[("rows",) + key] = (idx, dist2)  # a finished self search: knn_of_support_points() reads prefixes of it
         ctx.mark_non_differentiable(idx)
         if _knn_squared:  # knnquery_squared(): the plan code wants no root (one elementwise launch per search on the geometry queue)
             return idx, dist2
@@ -545,6 +548,62 @@ def knnquery_squared(nsample, xyz, new_xyz, offset, new_offset):
         return KNNQuery.apply(nsample, xyz, new_xyz, offset, new_offset)
     finally:
         _knn_squared = prev
+
+
+KNN_PREFIX_MAX = 31  # amc3d_knn_prefix: kr + 1 columns of a row in 32 lanes
+
+
+@torch.no_grad()
+def knn_prefix(kr, xyz, new_xyz, offset, new_offset, rows_idx, rows_d2, work=None, want_dist=True):
+    """knnquery_squared(kr, xyz, new_xyz, offset, new_offset) read off the rows (n, k0) of a finished self search of the
+    support, knnquery_squared(k0, xyz, xyz, offset, offset) with k0 > kr: a query that is a support point (equal
+    coordinates, exactly one such point in its segment) and whose row ascends strictly through column kr takes the row's
+    first kr columns; every other query is searched (csrc/knn.hip amc3d_knn_prefix).  Same bits as the search.
+    work: the workspace that holds the support's cell grid; None: the one an enclosing knn_grid_reuse() block keeps for this
+    support, else a grid is built.
+    -> (idx (m,kr) int32, dist2 (m,kr) or None, count: int32 tensor (1), how many queries were searched)"""
+    assert xyz.is_contiguous() and new_xyz.is_contiguous() and rows_idx.is_contiguous() and rows_d2.is_contiguous()
+    _need_gpu(xyz, new_xyz, offset, new_offset, rows_idx, rows_d2)
+    _need_dtype(torch.float32, xyz=xyz, new_xyz=new_xyz, rows_d2=rows_d2)
+    _need_dtype(torch.int32, offset=offset, new_offset=new_offset, rows_idx=rows_idx)
+    kr = int(kr)
+    n, m, nb = xyz.shape[0], new_xyz.shape[0], offset.shape[0]
+    k0 = rows_idx.shape[1]
+    if rows_idx.shape != (n, k0) or rows_d2.shape != (n, k0) or not 0 < kr < k0 or kr > KNN_PREFIX_MAX:
+        raise RuntimeError(f"knn_prefix: rows {tuple(rows_idx.shape)} / {tuple(rows_d2.shape)} for {n} support points, kr = {kr}")
+    lib = _lib.load()
+    wbytes = int(lib.amc3d_knnquery_workspace_bytes(n, m, kr, nb))
+    offset, new_offset = offset.contiguous(), new_offset.contiguous()
+    if work is None and _grid_cache is not None:
+        kept = _grid_cache.get((xyz.data_ptr(), n, offset.data_ptr(), nb, _stream(xyz).value))
+        work = kept if kept is not None and kept.numel() >= wbytes else None
+    reuse = work is not None
+    if reuse and work.numel() < wbytes:
+        raise RuntimeError("knn_prefix: the kept workspace is too small for these queries")
+    if not reuse:
+        work = torch.empty(wbytes, dtype=torch.uint8, device=xyz.device)
+    idx = torch.empty(m, kr, dtype=torch.int32, device=xyz.device)
+    dist2 = torch.empty(m, kr, dtype=torch.float32, device=xyz.device) if want_dist else None
+    with torch.cuda.device(xyz.device), timing.span("knn_prefix", m * (12 + (kr + 1) * 4 + kr * (12 if want_dist else 8))):
+        _lib.check(lib.amc3d_knn_prefix(m, kr, n, nb, _ptr(xyz), _ptr(new_xyz), _ptr(offset), _ptr(new_offset), k0,
+                                        rows_idx.stride(0), _ptr(rows_idx), _ptr(rows_d2), _ptr(idx),
+                                        _ptr(dist2) if want_dist else None, _ptr(work), work.numel(), int(reuse),
+                                        _stream(xyz)), "knn_prefix")
+    count = work[_lib.KNN_FALLBACK_COUNT_OFFSET:_lib.KNN_FALLBACK_COUNT_OFFSET + 4].view(torch.int32)
+    return idx, dist2, count
+
+
+def knn_of_support_points(kr, xyz, new_xyz, offset, new_offset):
+    """The indices of knnquery(kr, xyz, new_xyz, offset, new_offset) for queries that are (mostly) points of the support,
+    as the loss's label votes are: inside `with knn_grid_reuse():`, after a self search of the same support tensor and
+    offsets with more than kr columns, they are prefixes of its rows (knn_prefix); otherwise the search runs."""
+    key = (xyz.data_ptr(), xyz.shape[0], offset.data_ptr(), offset.shape[0], _stream(xyz).value)
+    rows = _grid_cache.get(("rows",) + key) if _grid_cache is not None and offset.is_contiguous() else None
+    work = _grid_cache.get(key) if rows is not None else None
+    if (work is not None and kr <= KNN_PREFIX_MAX and kr < rows[0].shape[1] and offset.shape[0] <= 64 and new_xyz.dtype == torch.float32
+            and work.numel() >= int(_lib.load().amc3d_knnquery_workspace_bytes(xyz.shape[0], new_xyz.shape[0], kr, offset.shape[0]))):
+        return knn_prefix(kr, xyz, new_xyz, offset, new_offset, rows[0], rows[1], work=work, want_dist=False)[0]
+    return knnquery_squared(kr, xyz, new_xyz, offset, new_offset)[0]
 
 
 KNN_BATCH_MAX = 100  # the search's heap (amc3d_knnquery: nsample <= 100)
@@ -663,6 +722,36 @@ def posmask_from_labels(labels, neighbor_idx):
 
 
 _CCTYPE = {"Method1": 1, "Method2": 2, "Method3": 3}
+
+
+def loss_rows_supported(p, labels, neighbor_idx):
+    """fp32 coordinates on the GPU and at most 64 neighbours: posmask_and_ambiguity takes the stage"""
+    return (p.is_cuda and p.dtype == torch.float32 and labels.dtype == torch.int32 and neighbor_idx.dtype == torch.int32
+            and bool(_lib.load().amc3d_loss_rows_supported(neighbor_idx.shape[1])))
+
+
+def posmask_and_ambiguity(labels, p, neighbor_idx, cctype, beta, stats=False):
+    """posmask_from_labels(labels, neighbor_idx) and ambiguity(p, posmask, neighbor_idx, cctype, beta) in one pass over the
+    neighbour rows (csrc/loss.hip amc3d_loss_rows): the same bits.  -> (posmask (m,k) bool, a (m) fp32); stats: also the
+    workspace's (max n+ (1) int32, n+ (m) int32, d+ (m), d- (m))."""
+    _need_gpu(labels, p, neighbor_idx)
+    _need_dtype(torch.float32, p=p)
+    _need_dtype(torch.int32, labels=labels)
+    assert p.is_contiguous() and labels.is_contiguous()
+    nptr, k, stride, keep = _nbr_view(neighbor_idx)
+    m = p.shape[0]
+    lib = _lib.load()
+    wbytes = int(lib.amc3d_ambiguity_workspace_bytes(m))
+    work = torch.empty(wbytes, dtype=torch.uint8, device=p.device)
+    posmask = torch.empty(m, k, dtype=torch.bool, device=p.device)
+    a = torch.empty(m, dtype=torch.float32, device=p.device)
+    with torch.cuda.device(p.device), timing.span("loss_rows", m * (12 + 4 + 4) + m * k * (4 + 1), moved=m * 20 + m * k * (4 + 1 + 4 + 12)):
+        _lib.check(lib.amc3d_loss_rows(m, k, stride, _CCTYPE[cctype], float(beta), _ptr(labels), _ptr(p), nptr, _ptr(posmask),
+                                       _ptr(a), _ptr(work), wbytes, _stream(p)), "loss_rows")
+    if not stats:
+        return posmask, a
+    return posmask, a, (work[:4].view(torch.int32), work[64:64 + 4 * m].view(torch.int32),
+                        work[64 + 4 * m:64 + 8 * m].view(torch.float32), work[64 + 8 * m:64 + 12 * m].view(torch.float32))
 
 
 def ambiguity(p, posmask, neighbor_idx, cctype, beta):

@@ -173,6 +173,19 @@ int amc3d_knnquery(int m, int nsample, int n, int nbatch, const float *xyz, cons
                    const int *offset, const int *new_offset, int *idx, float *dist2,
                    void *workspace, size_t workspace_bytes, int reuse_grid, void *stream);
 
+/* amc3d_knnquery(m, kr, ...) answered from the rows of a FINISHED self search of the support (k0 columns, kr < k0,
+ * kr <= 31): rows_idx / rows_d2 are the (n, row_stride) outputs of amc3d_knnquery(n, k0, n, ..., xyz, xyz, offset, offset).
+ * A query whose coordinates equal those of exactly one support point j of its segment (found in the query's grid cell),
+ * and whose row j ascends strictly through column kr with no unfilled slot there, takes columns 0..kr-1 of that row; every
+ * other query (no or several such points, a tie, a 1e10 slot) is searched as amc3d_knnquery searches its tied queries.
+ * idx (m,kr) and dist2 (m,kr; NULL: not wanted) hold the bits amc3d_knnquery would store.  The workspace is
+ * amc3d_knnquery's for (n, m); reuse_grid as there (0: the grid is built here, which needs n >= 256 and nbatch <= 64).
+ * Afterwards the int at byte AMC_KNN_FALLBACK_COUNT_OFFSET of the workspace is the number of searched queries. */
+#define AMC_KNN_FALLBACK_COUNT_OFFSET 1024
+int amc3d_knn_prefix(int m, int kr, int n, int nbatch, const float *xyz, const float *new_xyz, const int *offset,
+                     const int *new_offset, int k0, int row_stride, const int *rows_idx, const float *rows_d2, int *idx,
+                     float *dist2, void *workspace, size_t workspace_bytes, int reuse_grid, void *stream);
+
 /* k-NN over (b,n,3) / (b,m,3) batches, for models/layers/knn.py and group.py's KNN / DilatedKNN / KNNGroup (the reference
  * composes cdist + topk).  The search is amc3d_knnquery's over uniform segments: same distances, same order of equal
  * distances.  support (b,n,3), query (b,m,3) -> idx (b,m,ksearch/dilation) int32, CLOUD-LOCAL, columns 0, d, 2d, ... of
@@ -300,6 +313,14 @@ size_t amc3d_ambiguity_workspace_bytes(int m);
 int amc3d_ambiguity(int m, int k, int nbr_stride, int mode, float beta, const float *p,
                     const unsigned char *posmask, const int *nbr, float *a, void *workspace,
                     size_t workspace_bytes, void *stream);
+
+/* amc3d_posmask followed by amc3d_ambiguity as one pass over the neighbour rows (k <= 64: amc3d_loss_rows_supported):
+ * posmask (m,k) and a (m) carry the bits those two calls produce.  The workspace has amc3d_ambiguity's size and layout
+ * (int max n+ at byte 0; from byte 64: n+ (m) int, d+ (m), d- (m)); a == NULL stops after those statistics. */
+int amc3d_loss_rows_supported(int k);
+int amc3d_loss_rows(int m, int k, int nbr_stride, int mode, float beta, const int *labels, const float *p,
+                    const int *nbr, unsigned char *posmask, float *a, void *workspace, size_t workspace_bytes,
+                    void *stream);
 
 /* The anchors that enter the stage loss, 0 < a <= 1 (MarginContrast.py:250-252: the boolean-mask indexing
  * features[mask], neighbor_feature[mask], ...), as a compact ascending list built once per stage plan:

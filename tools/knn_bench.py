@@ -1,7 +1,8 @@
 """The loss's seven k-NN searches at the benchmark shape (8 x 24000 synthetic rooms, one segment): four self searches
 (k = 24) over the stage clouds and the three label votes (k = 4, 16, 64) over the finest cloud, whose grid they reuse
-as in the training step.  Prints every search's time (device events, mean of `reps` calls) and then, from a kernel
-trace of one pass over the seven, the time per kernel family (kg_query*, knn_exact_list, the grid build).
+as in the training step (the k = 4 and 16 votes as prefixes of stage 0's rows, ops.knn_of_support_points).  Prints
+every search's time (device events, mean of `reps` calls) and then, from a kernel trace of one pass over the seven, the
+time per kernel family (kg_query*, kg_prefix, knn_exact_list, the grid build).
 
     python tools/knn_bench.py [reps=20]
 
@@ -112,7 +113,10 @@ def run(which):
     with ops.knn_grid_reuse():
         for j in which:
             _, k, s, q = searches[j]
-            ops.knnquery_squared(k, stages[s], stages[q], offs[s], offs[q])
+            if s == q:
+                ops.knnquery_squared(k, stages[s], stages[q], offs[s], offs[q])
+            else:  # a vote (AEF/utils.py get_subscene_class): prefixes of stage 0's rows where k allows, else the search
+                ops.knn_of_support_points(k, stages[s], stages[q], offs[s], offs[q])
 
 
 def timed(fn):
@@ -147,7 +151,7 @@ with profile(activities=[ProfilerActivity.CUDA]) as prof:
     for _ in range(reps):
         run(range(7))
     torch.cuda.synchronize()
-fam = collections.OrderedDict((f, [0, 0.0]) for f in ("kg_query_group_kernel", "kg_query_kernel", "knn_exact_list_kernel",
+fam = collections.OrderedDict((f, [0, 0.0]) for f in ("kg_query_group_kernel", "kg_query_kernel", "kg_prefix_kernel", "knn_exact_list_kernel",
                                                       "knn_exact_kernel", "grid build (other kg_*)", "other"))
 for ev in prof.key_averages():
     t = getattr(ev, "device_time_total", None)
@@ -156,7 +160,7 @@ for ev in prof.key_averages():
     if not t:
         continue
     name = ev.key
-    f = next((f for f in list(fam)[:4] if f in name), None)
+    f = next((f for f in list(fam)[:5] if f in name), None)
     if f is None:
         f = "grid build (other kg_*)" if ("kg_" in name or "fill_i32" in name) else "other"
     fam[f][0] += ev.count
@@ -167,8 +171,8 @@ for f, (cnt, t) in fam.items():
 # the query kernel of every search: launch j of a pass belongs to search j
 from torch.autograd import DeviceType
 
-for pat in ("kg_query", "knn_exact_list"):
-    launches = sorted((e for e in prof.events() if e.device_type == DeviceType.CUDA and pat in e.name),
+for pat in (("kg_query", "kg_prefix"), ("knn_exact_list",)):
+    launches = sorted((e for e in prof.events() if e.device_type == DeviceType.CUDA and any(s in e.name for s in pat)),
                       key=lambda e: e.time_range.start)
     if len(launches) != reps * len(searches):
         print(f"  ({len(launches)} {pat} launches traced, {reps * len(searches)} expected: no per-search table)")
