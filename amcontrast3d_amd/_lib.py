@@ -114,6 +114,8 @@ SIGNATURES = {
     "amc3d_pointwise_conv_forward_strided": (_i, [_i, _i, _i, _l, _vp, _vp, _l, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_pointwise_conv_forward_rows": (_i, [_i, _i, _i, _l, _vp, _vp, _l, _vp, _vp, _sz, _vp]),
     "amc3d_pointwise_conv_backward_strided": (_i, [_i, _i, _i, _l, _vp, _vp, _l, _vp, _vp, _i, _vp, _l, _vp, _sz, _vp]),
+    "amc3d_gemm_tile_for": (_i, [_i, _i, _i, _i]),
+    "amc3d_gemm_probe": (_i, [_i, _i, _i, _i, _i, _l, _l, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_bn_residual_forward": (_i, [_i, _i, _l, _f, _f] + [_vp] * 11 + [_vp, _sz, _vp]),
     "amc3d_bn_residual_backward": (_i, [_i, _i, _l] + [_vp] * 11 + [_vp, _sz, _vp]),
     "amc3d_split_columns": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),

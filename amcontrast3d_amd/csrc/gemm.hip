@@ -8,7 +8,8 @@
 // the layer is HBM-bound (few channels, many positions); with >= 64 channels the MFMA pipe is the limit and that
 // kernel's single-buffered 32-position wave tiles leave it half idle.  Here:
 //   * 128 x 128 output tile per workgroup, 2 x 2 waves of 64 x 64 (four 32x32 accumulators: every A and B
-//     fragment feeds two v_mfma_f32_32x32x2_f32);
+//     fragment feeds two v_mfma_f32_32x32x2_f32), or 64 x 128 / 64 x 64 with two / one accumulators per wave: the
+//     launch's workgroup count chooses (gm_tile_for), and the K walk below is the same for all three;
 //   * K in chunks of 16, double-buffered in LDS; the next chunk's global loads are issued before the current
 //     chunk's MFMAs and written to the other buffer after them: one barrier per chunk;
 //   * an operand that is contiguous along k in global memory is kept [row][k] in LDS (row stride 20 floats:
@@ -25,10 +26,9 @@ namespace amc {
 
 typedef float gm_f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int GM_T = 128;    // tile edge (M and N)
+constexpr int GM_T = 128;    // the largest tile edge (M and N): what the split-K rules count tiles in
 constexpr int GM_KC = 16;    // K chunk
 constexpr int GM_S = 20;     // LDS row stride in floats
-constexpr int GM_STAGE = 2 * GM_T * GM_S;  // floats per stage (A then B)
 
 int reduce_partials(int total, int nparts, const float *partial, float *out, hipStream_t stream);  // gcc.hip
 int reduce_partials_rows(int rows, int cols, long ld, int nparts, const float *partial, float *out, hipStream_t stream);
@@ -38,18 +38,20 @@ struct GemmView {  // element (r, k) of an operand at base[r * sr + k * sk]; exa
     long sr, sk;
 };
 
-// registers of one chunk of one operand: 128 rows x 16 k = 512 float4, two per thread
+// registers of one chunk of one operand: ROWS rows x 16 k = ROWS * 4 float4, ROWS / 64 per thread
+template <int ROWS>
 struct GmRegs {
-    float4 v[2];
+    float4 v[ROWS / 64];
 };
 
 // KCONT: the operand is contiguous along k in global memory (natural); otherwise along its row index
-template <bool KCONT>
-__device__ __forceinline__ void gm_load(GmRegs &r, const GemmView &g, int row0, int nrows, long k0, long kend, bool vec)
+template <int ROWS, bool KCONT>
+__device__ __forceinline__ void gm_load(GmRegs<ROWS> &r, const GemmView &g, int row0, int nrows, long k0, long kend, bool vec)
 {
+    constexpr int R4 = ROWS / 4;  // float4 per k-row of a row-contiguous operand
     const int t = threadIdx.x;
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
+    for (int j = 0; j < ROWS / 64; ++j) {
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (KCONT) {
             const int row = t / 4 + 64 * j, c4 = t % 4;
@@ -60,7 +62,7 @@ __device__ __forceinline__ void gm_load(GmRegs &r, const GemmView &g, int row0, 
                 else { v.x = p[0]; if (k + 1 < kend) v.y = p[1]; if (k + 2 < kend) v.z = p[2]; if (k + 3 < kend) v.w = p[3]; }
             }
         } else {
-            const int krow = t / 32 + 8 * j, r4 = t % 32;
+            const int krow = t / R4 + (256 / R4) * j, r4 = t % R4;
             const long k = k0 + krow;
             const int row = r4 * 4;
             if (k < kend && row < nrows) {
@@ -73,113 +75,117 @@ __device__ __forceinline__ void gm_load(GmRegs &r, const GemmView &g, int row0, 
     }
 }
 
-template <bool KCONT>
-__device__ __forceinline__ void gm_store(const GmRegs &r, float *lds)
+template <int ROWS, bool KCONT>
+__device__ __forceinline__ void gm_store(const GmRegs<ROWS> &r, float *lds)
 {
+    constexpr int R4 = ROWS / 4;
     const int t = threadIdx.x;
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
+    for (int j = 0; j < ROWS / 64; ++j) {
         if (KCONT) {
             const int row = t / 4 + 64 * j, c4 = t % 4;
             *reinterpret_cast<float4 *>(lds + row * GM_S + c4 * 4) = r.v[j];
         } else {
-            const int krow = t / 32 + 8 * j, row = (t % 32) * 4;
-            *reinterpret_cast<float4 *>(lds + krow * GM_T + row) = r.v[j];
+            const int krow = t / R4 + (256 / R4) * j, row = (t % R4) * 4;
+            *reinterpret_cast<float4 *>(lds + krow * ROWS + row) = r.v[j];
         }
     }
 }
 
+// this lane's 8 k-values (k = kh*8 + t) of operand row `row` of a stage image
+template <int ROWS, bool KCONT>
+__device__ __forceinline__ void gm_fragment(float (&f)[8], const float *img, int row, int kh)
+{
+    if (KCONT) {
+        const float4 lo = *reinterpret_cast<const float4 *>(img + row * GM_S + kh * 8);
+        const float4 hi = *reinterpret_cast<const float4 *>(img + row * GM_S + kh * 8 + 4);
+        f[0] = lo.x; f[1] = lo.y; f[2] = lo.z; f[3] = lo.w;
+        f[4] = hi.x; f[5] = hi.y; f[6] = hi.z; f[7] = hi.w;
+    } else {
+#pragma unroll
+        for (int t = 0; t < 8; ++t) f[t] = img[(kh * 8 + t) * ROWS + row];
+    }
+}
+
+// One TM x TN output tile per workgroup (TM, TN in {64, 128}): 2 x 2 waves of (TM/2) x (TN/2), that is TM/64 x TN/64
+// accumulators of 32 x 32 per wave.  The K walk -- chunks of 16 in sequence, step t pairing k = t with k = 8 + t -- is the same
+// for every tile, so an output element has the same bits whichever tile computed it.  LDS: two stages of (TM + TN) * GM_S.
 // grid: (N tiles, M tiles, batch * splits).  Per z: batch b = z / splits, split s = z % splits owns K range
 // [s * kper, min(K, (s+1) * kper)).  Output C = cbase + z * czstride (forward/backward-data: splits = 1 and
 // czstride = M * ldc; backward-weight: one partial (M, N) per z).  pm != 0: C is stored transposed, C[n][m] with row length M
 // (backward-data as position-major rows): the four consecutive rows of an accumulator's (r >> 2) group are one 16-byte store
 // when pm == 2 (M % 4 == 0, aligned base), four 4-byte stores otherwise.
-template <bool A_KCONT, bool B_KCONT>
+template <int TM, int TN, bool A_KCONT, bool B_KCONT>
 __global__ __launch_bounds__(256) void gm_gemm_kernel(int M, int N, long K, int splits, long kper, GemmView A, long a_bstride,
                                                       GemmView B, long b_bstride, float *__restrict__ cbase, long czstride,
                                                       long ldc, int vec_a, int vec_b, int pm)
 {
+    constexpr int WTM = TM / 2, WTN = TN / 2, IM = WTM / 32, JN = WTN / 32;
+    constexpr int STAGE = (TM + TN) * GM_S;  // floats per stage (A then B)
     extern __shared__ __attribute__((aligned(16))) float gm_smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, pl = lane & 31, kh = lane >> 5;
     const int wm = wave >> 1, wn = wave & 1;
-    const int m0 = blockIdx.y * GM_T, n0 = blockIdx.x * GM_T;
+    const int m0 = blockIdx.y * TM, n0 = blockIdx.x * TN;
     const int z = blockIdx.z, bz = z / splits, sp = z - bz * splits;
     const long kbeg = (long)sp * kper, kend = min(K, kbeg + kper);
     A.base += (long)bz * a_bstride;
     B.base += (long)bz * b_bstride;
-    const int mrows = min(GM_T, M - m0), ncols = min(GM_T, N - n0);
+    const int mrows = min(TM, M - m0), ncols = min(TN, N - n0);
 
-    gm_f32x16 acc[2][2];
+    gm_f32x16 acc[IM][JN];
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < IM; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = gm_f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (int j = 0; j < JN; ++j) acc[i][j] = gm_f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
-    GmRegs ra, rb;
+    GmRegs<TM> ra;
+    GmRegs<TN> rb;
     const long nchunks = (kend - kbeg + GM_KC - 1) / GM_KC;
     if (nchunks > 0) {
-        gm_load<A_KCONT>(ra, A, m0, mrows, kbeg, kend, vec_a);
-        gm_load<B_KCONT>(rb, B, n0, ncols, kbeg, kend, vec_b);
-        gm_store<A_KCONT>(ra, gm_smem);
-        gm_store<B_KCONT>(rb, gm_smem + GM_T * GM_S);
+        gm_load<TM, A_KCONT>(ra, A, m0, mrows, kbeg, kend, vec_a);
+        gm_load<TN, B_KCONT>(rb, B, n0, ncols, kbeg, kend, vec_b);
+        gm_store<TM, A_KCONT>(ra, gm_smem);
+        gm_store<TN, B_KCONT>(rb, gm_smem + TM * GM_S);
     }
     __syncthreads();
     for (long c = 0; c < nchunks; ++c) {
-        const float *as = gm_smem + (c & 1) * GM_STAGE, *bs = as + GM_T * GM_S;
+        const float *as = gm_smem + (c & 1) * STAGE, *bs = as + TM * GM_S;
         const bool more = c + 1 < nchunks;
         if (more) {  // in flight while this chunk is multiplied
-            gm_load<A_KCONT>(ra, A, m0, mrows, kbeg + (c + 1) * GM_KC, kend, vec_a);
-            gm_load<B_KCONT>(rb, B, n0, ncols, kbeg + (c + 1) * GM_KC, kend, vec_b);
+            gm_load<TM, A_KCONT>(ra, A, m0, mrows, kbeg + (c + 1) * GM_KC, kend, vec_a);
+            gm_load<TN, B_KCONT>(rb, B, n0, ncols, kbeg + (c + 1) * GM_KC, kend, vec_b);
         }
-        // this lane's 8 k-values (k = kh*8 + t) of its two A rows and two B columns
-        float av[2][8], bv[2][8];
+        // this lane's 8 k-values (k = kh*8 + t) of its IM A rows and JN B columns
+        float av[IM][8], bv[JN][8];
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int ar = wm * 64 + i * 32 + pl, br = wn * 64 + i * 32 + pl;
-            if (A_KCONT) {
-                const float4 lo = *reinterpret_cast<const float4 *>(as + ar * GM_S + kh * 8);
-                const float4 hi = *reinterpret_cast<const float4 *>(as + ar * GM_S + kh * 8 + 4);
-                av[i][0] = lo.x; av[i][1] = lo.y; av[i][2] = lo.z; av[i][3] = lo.w;
-                av[i][4] = hi.x; av[i][5] = hi.y; av[i][6] = hi.z; av[i][7] = hi.w;
-            } else {
+        for (int i = 0; i < IM; ++i) gm_fragment<TM, A_KCONT>(av[i], as, wm * WTM + i * 32 + pl, kh);
 #pragma unroll
-                for (int t = 0; t < 8; ++t) av[i][t] = as[(kh * 8 + t) * GM_T + ar];
-            }
-            if (B_KCONT) {
-                const float4 lo = *reinterpret_cast<const float4 *>(bs + br * GM_S + kh * 8);
-                const float4 hi = *reinterpret_cast<const float4 *>(bs + br * GM_S + kh * 8 + 4);
-                bv[i][0] = lo.x; bv[i][1] = lo.y; bv[i][2] = lo.z; bv[i][3] = lo.w;
-                bv[i][4] = hi.x; bv[i][5] = hi.y; bv[i][6] = hi.z; bv[i][7] = hi.w;
-            } else {
-#pragma unroll
-                for (int t = 0; t < 8; ++t) bv[i][t] = bs[(kh * 8 + t) * GM_T + br];
-            }
-        }
+        for (int j = 0; j < JN; ++j) gm_fragment<TN, B_KCONT>(bv[j], bs, wn * WTN + j * 32 + pl, kh);
 #pragma unroll
         for (int t = 0; t < 8; ++t)
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
+            for (int i = 0; i < IM; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i][t], bv[j][t], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < JN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i][t], bv[j][t], acc[i][j], 0, 0, 0);
         if (more) {
-            float *nas = gm_smem + ((c + 1) & 1) * GM_STAGE;
-            gm_store<A_KCONT>(ra, nas);
-            gm_store<B_KCONT>(rb, nas + GM_T * GM_S);
+            float *nas = gm_smem + ((c + 1) & 1) * STAGE;
+            gm_store<TM, A_KCONT>(ra, nas);
+            gm_store<TN, B_KCONT>(rb, nas + TM * GM_S);
         }
         __syncthreads();
     }
     // accumulator layout: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
     float *C = cbase + (long)z * czstride;
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < IM; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int n = n0 + wn * 64 + j * 32 + pl;
+        for (int j = 0; j < JN; ++j) {
+            const int n = n0 + wn * WTN + j * 32 + pl;
             if (n < N && pm) {
                 float *row = C + (long)n * M;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const int m = m0 + wm * 64 + i * 32 + 8 * g + 4 * kh;
+                    const int m = m0 + wm * WTM + i * 32 + 8 * g + 4 * kh;
                     if (pm == 2) {
                         if (m < M)
                             *reinterpret_cast<float4 *>(row + m) =
@@ -193,7 +199,7 @@ __global__ __launch_bounds__(256) void gm_gemm_kernel(int M, int N, long K, int 
             } else if (n < N) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                    const int m = m0 + wm * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
                     if (m < M) C[(long)m * ldc + n] = acc[i][j][r];
                 }
             }
@@ -304,14 +310,51 @@ __global__ __launch_bounds__(256) void gw_wgrad_kernel(int M, int N, long P, int
 
 static int aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
+// The tiles of gm_gemm_kernel, largest first.
+constexpr int GM_NTILES = 3;
+static const int gm_tiles[GM_NTILES][2] = {{128, 128}, {64, 128}, {64, 64}};
+
+static long gm_workgroups(int tile, int M, int N, int batch, int splits)
+{
+    return (long)div_up(M, gm_tiles[tile][0]) * div_up(N, gm_tiles[tile][1]) * batch * splits;
+}
+
+// THE dispatch rule, read from profiles/gemm_tiles_sweep.txt (channel counts 64-512, 1500-48000 positions, 8 clouds):
+//   * 64 x 128 is the tile of a launch that fills the chip: it gives at least GM_FILL workgroups (two per CU of the 256), and a
+//     CU holds five of them by registers and LDS (128 x 128: three);
+//   * 128 x 128 only where all its workgroups are resident at once (GM_FILL .. GM_RESIDENT = 3 per CU) and M leaves no 64-row
+//     half of its tiles empty: there it is 1-3 % ahead, one round of the larger tiles against a round and a tail; with more
+//     rounds than that the 64 x 128 tile is level or up to 15 % ahead;
+//   * 64 x 64 where 64 x 128 gives fewer than GM_FILL workgroups: the short layers and the weight gradients.
+// A function of the launch's shape only -- the same choice eager and captured, on every rank -- and free to change: every tile
+// walks K alike, so the choice never shows in a result.
+constexpr long GM_FILL = 512, GM_RESIDENT = 768;
+static int gm_tile_for(int M, int N, int batch, int splits)
+{
+    const long big = gm_workgroups(0, M, N, batch, splits);
+    if (big >= GM_FILL && big <= GM_RESIDENT && div_up(M, 64) == 2 * div_up(M, 128)) return 0;
+    return gm_workgroups(1, M, N, batch, splits) >= GM_FILL ? 1 : 2;
+}
+
+template <int TM, int TN, bool AK, bool BK>
+static void gm_launch_tile(int M, int N, long K, int batch, int splits, long kper, GemmView A, long abs_, GemmView B, long bbs,
+                           float *c, long czs, long ldc, int va, int vb, hipStream_t stream, int pm)
+{
+    const size_t lds = 2 * (TM + TN) * GM_S * sizeof(float);
+    hipLaunchKernelGGL((gm_gemm_kernel<TM, TN, AK, BK>), dim3(div_up(N, TN), div_up(M, TM), batch * splits), dim3(256), lds, stream,
+                       M, N, K, splits, kper, A, abs_, B, bbs, c, czs, ldc, va, vb, pm);
+}
+
+// tile < 0: the rule's choice (every product call); 0 .. GM_NTILES - 1: that tile (amc3d_gemm_probe)
 template <bool AK, bool BK>
 static void gm_launch(int M, int N, long K, int batch, int splits, long kper, GemmView A, long abs_, GemmView B, long bbs,
-                      float *c, long czs, long ldc, int va, int vb, hipStream_t stream, int pm = 0)
+                      float *c, long czs, long ldc, int va, int vb, hipStream_t stream, int pm = 0, int tile = -1)
 {
-    const size_t lds = 2 * GM_STAGE * sizeof(float);
     if (pm) pm = (M % 4 == 0 && aligned16(c) && czs % 4 == 0) ? 2 : 1;
-    hipLaunchKernelGGL((gm_gemm_kernel<AK, BK>), dim3(div_up(N, GM_T), div_up(M, GM_T), batch * splits), dim3(256), lds, stream, M,
-                       N, K, splits, kper, A, abs_, B, bbs, c, czs, ldc, va, vb, pm);
+    if (tile < 0) tile = gm_tile_for(M, N, batch, splits);
+    if (tile == 0) gm_launch_tile<128, 128, AK, BK>(M, N, K, batch, splits, kper, A, abs_, B, bbs, c, czs, ldc, va, vb, stream, pm);
+    else if (tile == 1) gm_launch_tile<64, 128, AK, BK>(M, N, K, batch, splits, kper, A, abs_, B, bbs, c, czs, ldc, va, vb, stream, pm);
+    else gm_launch_tile<64, 64, AK, BK>(M, N, K, batch, splits, kper, A, abs_, B, bbs, c, czs, ldc, va, vb, stream, pm);
 }
 
 bool gemm_conv_pays(int cin, int cout) { return cin >= 64 && cout >= 64; }
@@ -365,8 +408,9 @@ size_t gemm_conv_backward_data_workspace_bytes(int b, int cin, int cout, long P)
 
 // y_pm: y as (b,P,cout) rows (no bias); the split-K partials then have that layout too and their sum is elementwise -- the same
 // accumulators and the same order of the partial sums as the channel-major form, so the rows equal its transpose bit for bit
-int gemm_conv_forward(int b, int cin, int cout, long P, const float *x, const float *w, long ldw, const float *bias, float *y,
-                      int y_pm, float *partial, hipStream_t stream)
+// tile: see gm_launch
+static int gm_conv_forward(int b, int cin, int cout, long P, const float *x, const float *w, long ldw, const float *bias, float *y,
+                           int y_pm, float *partial, hipStream_t stream, int tile)
 {
     if (y_pm && bias) return bad_arg("gemm_conv_forward: rows take no bias");
     GemmView A{w, ldw, 1}, B{x, 1, P};  // A(m=co,k=ci) k-contiguous; B(n=p,k=ci) at x[k*P + n]: n-contiguous
@@ -375,13 +419,14 @@ int gemm_conv_forward(int b, int cin, int cout, long P, const float *x, const fl
     if (sp > 1) {
         const long kper = (((long)cin + sp - 1) / sp + GM_KC - 1) / GM_KC * GM_KC;
         gm_launch<true, false>(cout, (int)P, cin, b, sp, kper, A, 0, B, (long)cin * P, partial, (long)cout * P, P, va, vb, stream,
-                               y_pm);
+                               y_pm, tile);
         const long total = (long)cout * P;
         hipLaunchKernelGGL(gm_split_reduce_kernel, dim3(div_up(total, 256), b), dim3(256), 0, stream, total, P, sp,
                            (const float *)partial, bias, y);
         return launch_status("gemm_conv_forward");
     }
-    gm_launch<true, false>(cout, (int)P, cin, b, 1, cin, A, 0, B, (long)cin * P, y, (long)cout * P, P, va, vb, stream, y_pm);
+    gm_launch<true, false>(cout, (int)P, cin, b, 1, cin, A, 0, B, (long)cin * P, y, (long)cout * P, P, va, vb, stream, y_pm,
+                           tile);
     if (bias) {
         const long total = (long)cout * P;
         hipLaunchKernelGGL(gm_bias_kernel, dim3(div_up(total, 256), b), dim3(256), 0, stream, total, P, bias, y);
@@ -389,10 +434,16 @@ int gemm_conv_forward(int b, int cin, int cout, long P, const float *x, const fl
     return launch_status("gemm_conv_forward");
 }
 
+int gemm_conv_forward(int b, int cin, int cout, long P, const float *x, const float *w, long ldw, const float *bias, float *y,
+                      int y_pm, float *partial, hipStream_t stream)
+{
+    return gm_conv_forward(b, cin, cout, P, x, w, ldw, bias, y, y_pm, partial, stream, -1);
+}
+
 // dx (b,cin,P) = W^T . dy (b,cout,P)
 // dx_pm: dx as (b,P,cin) rows; the split-K partials then have that layout too and their sum is elementwise
-int gemm_conv_backward_data(int b, int cin, int cout, long P, const float *dy, const float *w, long ldw, float *dx, int dx_pm,
-                            float *partial, hipStream_t stream)
+static int gm_conv_backward_data(int b, int cin, int cout, long P, const float *dy, const float *w, long ldw, float *dx, int dx_pm,
+                                 float *partial, hipStream_t stream, int tile)
 {
     GemmView A{w, 1, ldw}, B{dy, 1, P};  // A(m=ci,k=co) = w[k*ldw + m]: m-contiguous
     const int va = cin % 4 == 0 && ldw % 4 == 0 && aligned16(w), vb = P % 4 == 0 && aligned16(dy);
@@ -400,14 +451,21 @@ int gemm_conv_backward_data(int b, int cin, int cout, long P, const float *dy, c
     if (sp > 1) {
         const long kper = (((long)cout + sp - 1) / sp + GM_KC - 1) / GM_KC * GM_KC;
         gm_launch<false, false>(cin, (int)P, cout, b, sp, kper, A, 0, B, (long)cout * P, partial, (long)cin * P, P, va, vb, stream,
-                                dx_pm);
+                                dx_pm, tile);
         const long total = (long)cin * P;
         hipLaunchKernelGGL(gm_split_reduce_kernel, dim3(div_up(total, 256), b), dim3(256), 0, stream, total, P, sp,
                            (const float *)partial, (const float *)nullptr, dx);
         return launch_status("gemm_conv_backward_data");
     }
-    gm_launch<false, false>(cin, (int)P, cout, b, 1, cout, A, 0, B, (long)cout * P, dx, (long)cin * P, P, va, vb, stream, dx_pm);
+    gm_launch<false, false>(cin, (int)P, cout, b, 1, cout, A, 0, B, (long)cout * P, dx, (long)cin * P, P, va, vb, stream, dx_pm,
+                            tile);
     return launch_status("gemm_conv_backward_data");
+}
+
+int gemm_conv_backward_data(int b, int cin, int cout, long P, const float *dy, const float *w, long ldw, float *dx, int dx_pm,
+                            float *partial, hipStream_t stream)
+{
+    return gm_conv_backward_data(b, cin, cout, P, dy, w, ldw, dx, dx_pm, partial, stream, -1);
 }
 
 static bool gw_streaming(int b, int cin, int cout, long P) { return P % 4 == 0 && P >= 4 * GW_KC; }
@@ -447,12 +505,13 @@ size_t gemm_conv_wgrad_workspace_bytes(int b, int cin, int cout, long P)
 }
 
 // dw (cout,cin) = sum_b dy[b] . x[b]^T, deterministic (partials summed in a fixed order)
-int gemm_conv_backward_weight(int b, int cin, int cout, long P, const float *x, const float *dy, float *dw, long lddw,
-                              float *partial, hipStream_t stream)
+// tile >= 0: the generic kernel with that tile, whatever the shape (amc3d_gemm_probe)
+static int gm_conv_backward_weight(int b, int cin, int cout, long P, const float *x, const float *dy, float *dw, long lddw,
+                                   float *partial, hipStream_t stream, int tile)
 {
     long kper;
     const int s = gemm_wgrad_splits(b, cin, cout, P, &kper);
-    if (gw_streaming(b, cin, cout, P) && aligned16(dy) && aligned16(x)) {
+    if (tile < 0 && gw_streaming(b, cin, cout, P) && aligned16(dy) && aligned16(x)) {
         if (cin <= 64) {
             const size_t lds = 2 * (GW_TM + 64) * GW_S * sizeof(float);
             hipLaunchKernelGGL(gw_wgrad_kernel<64>, dim3(div_up(cin, 64), div_up(cout, GW_TM), b * s), dim3(256), lds, stream, cout,
@@ -469,9 +528,44 @@ int gemm_conv_backward_weight(int b, int cin, int cout, long P, const float *x, 
     GemmView A{dy, P, 1}, B{x, P, 1};  // A(m=co,k=p), B(n=ci,k=p): both k-contiguous
     const int va = P % 4 == 0 && aligned16(dy), vb = P % 4 == 0 && aligned16(x);
     gm_launch<true, true>(cout, cin, P, b, s, kper, A, (long)cout * P, B, (long)cin * P, partial, (long)cout * cin, cin, va, vb,
-                          stream);
+                          stream, 0, tile);
     if (int st = launch_status("gemm_conv_backward_weight")) return st;
     return reduce_partials_rows(cout, cin, lddw, b * s, partial, dw, stream);
 }
 
+int gemm_conv_backward_weight(int b, int cin, int cout, long P, const float *x, const float *dy, float *dw, long lddw,
+                              float *partial, hipStream_t stream)
+{
+    return gm_conv_backward_weight(b, cin, cout, P, x, dy, dw, lddw, partial, stream, -1);
+}
+
 }  // namespace amc
+
+using namespace amc;
+
+// ---- test and measurement entries: neither is called by the product path ----------------------------------------------------
+AMC_API int amc3d_gemm_tile_for(int M, int N, int batch, int splits)
+{
+    if (M <= 0 || N <= 0 || batch <= 0 || splits <= 0) return -1;
+    return gm_tile_for(M, N, batch, splits);
+}
+
+AMC_API int amc3d_gemm_probe(int tile_id, int product, int b, int cin, int cout, long P, long ldw, int pm, const float *x_or_dy,
+                             const float *w, float *out, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (b <= 0 || P <= 0) return 0;
+    if (tile_id < 0 || tile_id >= GM_NTILES || product < 0 || product > 2 || cin <= 0 || cout <= 0 || P >= (1L << 31) || ldw < cin ||
+        !x_or_dy || !w || !out || (product == 2 && pm))
+        return bad_arg("amc3d_gemm_probe: bad argument");
+    if (product == 2) {
+        if (!workspace || workspace_bytes < gemm_conv_wgrad_workspace_bytes(b, cin, cout, P))
+            return bad_arg("amc3d_gemm_probe: workspace too small");
+        return gm_conv_backward_weight(b, cin, cout, P, w, x_or_dy, out, ldw, (float *)workspace, (hipStream_t)stream, tile_id);
+    }
+    const size_t need = product == 0 ? gemm_conv_forward_workspace_bytes(b, cin, cout, P)
+                                     : gemm_conv_backward_data_workspace_bytes(b, cin, cout, P);
+    float *partial = (need && workspace && workspace_bytes >= need) ? (float *)workspace : nullptr;
+    if (product == 0)
+        return gm_conv_forward(b, cin, cout, P, x_or_dy, w, ldw, nullptr, out, pm, partial, (hipStream_t)stream, tile_id);
+    return gm_conv_backward_data(b, cin, cout, P, x_or_dy, w, ldw, out, pm, partial, (hipStream_t)stream, tile_id);
+}

@@ -605,6 +605,19 @@ int amc3d_pointwise_conv_backward_strided(int b, int cin, int cout, long P, cons
  * workspace: amc3d_pointwise_conv_forward_workspace_bytes(b, cin, cout, P, 0) bytes. */
 int amc3d_pointwise_conv_forward_rows(int b, int cin, int cout, long P, const float *x, const float *weight, long ldw,
                                       float *y_pm, void *workspace, size_t workspace_bytes, void *stream);
+/* Test and measurement entries of the deep layers' MFMA GEMM (csrc/gemm.hip); the product path calls neither.
+ * amc3d_gemm_tile_for: the output tile the dispatch rule gives a launch of M x N outputs per (batch * splits) slice:
+ * 0 = 128 x 128, 1 = 64 x 128, 2 = 64 x 64 (-1 for a non-positive argument).  A function of its four arguments only.
+ * amc3d_gemm_probe: ONE product on that kernel with tile tile_id FORCED, whatever the channel counts, with the K split of the
+ * real route.  product 0: forward, out (b,cout,P) = w (cout,cin; row stride ldw) . x_or_dy (b,cin,P); 1: backward-data,
+ * out (b,cin,P) = w^T . x_or_dy (b,cout,P); for both pm != 0 writes out as position-major rows, and the K axis is split when the
+ * workspace holds amc3d_pointwise_conv_forward_workspace_bytes(b,cin,cout,P,0) bytes (forward; the route's own rule for
+ * backward-data, at most amc3d_pointwise_conv_workspace_bytes).  product 2: the generic weight gradient, out (cout,cin; row
+ * stride ldw) = sum x_or_dy (b,cout,P) . w (b,cin,P)^T, pm = 0, workspace of amc3d_pointwise_conv_workspace_bytes.  Every
+ * tile gives the same bits. */
+int amc3d_gemm_tile_for(int M, int N, int batch, int splits);
+int amc3d_gemm_probe(int tile_id, int product, int b, int cin, int cout, long P, long ldw, int pm, const float *x_or_dy,
+                     const float *w, float *out, void *workspace, size_t workspace_bytes, void *stream);
 
 /* a weight matrix cut into two column blocks / two gradient blocks joined (the [W_dp | W_f] weight of a neighbourhood layer,
  * the [W_skip | W_up] weight of a FeaturePropagation conv): w (rows, c1 + c2) <-> a (rows, c1), b (rows, c2), one launch */
