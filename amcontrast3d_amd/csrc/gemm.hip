@@ -11,7 +11,8 @@
 //     fragment feeds two v_mfma_f32_32x32x2_f32), or 64 x 128 / 64 x 64 with two / one accumulators per wave: the
 //     launch's workgroup count chooses (gm_tile_for), and the K walk below is the same for all three;
 //   * K in chunks of 16, double-buffered in LDS; the next chunk's global loads are issued before the current
-//     chunk's MFMAs and written to the other buffer after them: one barrier per chunk;
+//     chunk's MFMAs and written to the other buffer after them: one barrier per chunk.  A chunk that lies inside both
+//     operands is loaded by straight-line code in a loop of its own (gm_load_whole), the chunks at an edge by guarded loads;
 //   * an operand that is contiguous along k in global memory is kept [row][k] in LDS (row stride 20 floats:
 //     8 consecutive rows x 16 bytes cover the 32 banks once) and a lane fetches its 8 k-values of a chunk with
 //     two ds_read_b128; an operand contiguous along m / n is kept as it arrives, [k][row], and read with eight
@@ -19,6 +20,8 @@
 // MFMA operand convention (v_mfma_f32_32x32x2_f32): lane l supplies A[i = l & 31][kk = l >> 5] and
 // B[kk = l >> 5][j = l & 31]; step t of a chunk pairs k = t (lanes 0-31) with k = 8 + t (lanes 32-63) in both
 // operands -- any pairing is a valid order of the K sum as long as A and B agree.
+
+#include <type_traits>
 
 #include "common.h"
 
@@ -72,6 +75,25 @@ __device__ __forceinline__ void gm_load(GmRegs<ROWS> &r, const GemmView &g, int 
             }
         }
         r.v[j] = v;
+    }
+}
+
+// The same registers for a chunk that lies wholly inside the operand (all ROWS rows, all 16 k): no lane tests anything.  In
+// gm_load a register's value depends on which guarded branch ran (zero, the float4, one to four scalars), and the compiler joins
+// those branches by waiting for the loads: vmcnt(0) after the A operand, again after each float4 of B, so a chunk paid two or
+// three memory latencies in a row before its first MFMA.  Here the loads are straight-line code, and the caller keeps them in a
+// copy of the loop body of their own, so the registers meet no other definition before gm_store reads them.
+template <int ROWS, bool KCONT>
+__device__ __forceinline__ void gm_load_whole(GmRegs<ROWS> &r, const GemmView &g, int row0, long k0, bool vec)
+{
+    constexpr int R4 = ROWS / 4;
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < ROWS / 64; ++j) {
+        const float *p = KCONT ? g.base + (long)(row0 + t / 4 + 64 * j) * g.sr + k0 + (t % 4) * 4
+                               : g.base + (k0 + t / R4 + (256 / R4) * j) * g.sk + (row0 + (t % R4) * 4);
+        if (vec) r.v[j] = *reinterpret_cast<const float4 *>(p);
+        else r.v[j] = make_float4(p[0], p[1], p[2], p[3]);
     }
 }
 
@@ -141,17 +163,30 @@ __global__ __launch_bounds__(256) void gm_gemm_kernel(int M, int N, long K, int 
     GmRegs<TM> ra;
     GmRegs<TN> rb;
     const long nchunks = (kend - kbeg + GM_KC - 1) / GM_KC;
-    if (nchunks > 0) {
+    const bool inside = mrows == TM && ncols == TN;  // every row of both tiles exists
+    if (inside && kbeg + GM_KC <= kend) {
+        gm_load_whole<TM, A_KCONT>(ra, A, m0, kbeg, vec_a);
+        gm_load_whole<TN, B_KCONT>(rb, B, n0, kbeg, vec_b);
+        gm_store<TM, A_KCONT>(ra, gm_smem);
+        gm_store<TN, B_KCONT>(rb, gm_smem + TM * GM_S);
+    } else if (nchunks > 0) {
         gm_load<TM, A_KCONT>(ra, A, m0, mrows, kbeg, kend, vec_a);
         gm_load<TN, B_KCONT>(rb, B, n0, ncols, kbeg, kend, vec_b);
         gm_store<TM, A_KCONT>(ra, gm_smem);
         gm_store<TN, B_KCONT>(rb, gm_smem + TM * GM_S);
     }
     __syncthreads();
-    for (long c = 0; c < nchunks; ++c) {
+    // One chunk: the next chunk's global loads, this chunk's MFMAs, the next chunk's LDS image, a barrier.  WHOLE: the next chunk
+    // exists and lies inside both operands.  The order of the sum is that of the chunks, whichever copy of the body runs them.
+    auto chunk = [&](auto whole, long c) {
+        constexpr bool WHOLE = decltype(whole)::value;
         const float *as = gm_smem + (c & 1) * STAGE, *bs = as + TM * GM_S;
-        const bool more = c + 1 < nchunks;
-        if (more) {  // in flight while this chunk is multiplied
+        const bool more = WHOLE || c + 1 < nchunks;
+        if (WHOLE) {  // in flight while this chunk is multiplied
+            gm_load_whole<TM, A_KCONT>(ra, A, m0, kbeg + (c + 1) * GM_KC, vec_a);
+            gm_load_whole<TN, B_KCONT>(rb, B, n0, kbeg + (c + 1) * GM_KC, vec_b);
+            __builtin_amdgcn_sched_barrier(0);  // issued here: the scheduler would sink them to their first use, after the MFMAs
+        } else if (more) {
             gm_load<TM, A_KCONT>(ra, A, m0, mrows, kbeg + (c + 1) * GM_KC, kend, vec_a);
             gm_load<TN, B_KCONT>(rb, B, n0, ncols, kbeg + (c + 1) * GM_KC, kend, vec_b);
         }
@@ -173,7 +208,12 @@ __global__ __launch_bounds__(256) void gm_gemm_kernel(int M, int N, long K, int 
             gm_store<TN, B_KCONT>(rb, nas + TM * GM_S);
         }
         __syncthreads();
-    }
+    };
+    // two loops, not one loop with a branch: each keeps the accumulators in place over its iterations
+    long c = 0;
+    if (inside)
+        for (; kbeg + (c + 2) * GM_KC <= kend; ++c) chunk(std::true_type{}, c);
+    for (; c < nchunks; ++c) chunk(std::false_type{}, c);  // the chunks before an edge of K, or every chunk of an edge tile
     // accumulator layout: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
     float *C = cbase + (long)z * czstride;
 #pragma unroll
@@ -326,6 +366,11 @@ static long gm_workgroups(int tile, int M, int N, int batch, int splits)
 //     half of its tiles empty: there it is 1-3 % ahead, one round of the larger tiles against a round and a tail; with more
 //     rounds than that the 64 x 128 tile is level or up to 15 % ahead;
 //   * 64 x 64 where 64 x 128 gives fewer than GM_FILL workgroups: the short layers and the weight gradients.
+// With the interior chunks' loads in flight during the MFMAs (gm_load_whole) the sweep, alone on the chip, moved: 64 x 64 is then
+// 3-10 % ahead up to 1504 workgroups of 128 x 128 and 128 x 128 from 6000 up (profiles/gemm_core_sweep.txt).  The thresholds
+// stayed all the same: in the train step, where two other queues share the CUs, eight 64 x 64 workgroups per CU (all of its LDS)
+// on the filled launches cost the neighbours more than the GEMMs gain -- the step is 0.02-0.03 ms slower with "64 x 64 up to
+// 4096, 128 x 128 above" than with this rule (profiles/gemm_core_ab.json).
 // A function of the launch's shape only -- the same choice eager and captured, on every rank -- and free to change: every tile
 // walks K alike, so the choice never shows in a result.
 constexpr long GM_FILL = 512, GM_RESIDENT = 768;
