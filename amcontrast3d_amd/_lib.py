@@ -217,6 +217,11 @@ SIGNATURES = {
     "amc3d_bn_forward_synced": (_i, [_i, _i, _l, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "amc3d_bn_backward_sums": (_i, [_i, _i, _l, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_bn_backward_synced": (_i, [_i, _i, _l, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "amc3d_sphere_workspace_bytes": (_sz, [_i]),
+    "amc3d_sphere_minima": (_i, [_i] + [_vp] * 4 + [_vp]),
+    "amc3d_sphere_schedule": (_i, [_i] * 6 + [ctypes.c_double] + [_vp] * 13 + [_vp, _sz, _vp]),
+    "amc3d_sphere_query": (_i, [_i] * 5 + [ctypes.c_double] + [_vp] * 9 + [_vp, _sz, _vp]),
+    "amc3d_sphere_tail": (_i, [_i] * 4 + [_vp] * 18 + [_vp]),
 }
 
 

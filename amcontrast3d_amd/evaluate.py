@@ -15,6 +15,7 @@ files; what they compute is restated here on arrays the caller already holds:
     scannet_benchmark_ids       main.py:652-659 (the label ids of the benchmark's submission files)
     test_room_s3dis             the same iteration for a raw S3DIS room with the config's evaluation transforms, on the device
     summarize                   main_AA.py:484-506 / 746-770 (get_mious over the accumulated matrices)
+    validate_sphere             main.py:436-483 (S3DISSphere batches: logits of overlapping spheres averaged per sub-point)
 
 The model runs with model.eval(): BatchNorm uses its running statistics on the fused inference kernels
 (ops.bn_eval), FPS / ball query / grouped convolutions / 3-NN are the same HIP kernels as in training.
@@ -376,3 +377,57 @@ def test_room_s3dis(model, cdata, voxel_size, num_classes, ignore_index, nsample
     kw = _batch_options(gravity_dim, feature_keys, color_mean, color_std)
     return _test_room(model, rp, lambda rows: ip.s3dis_part_batch(rows, coord, colour, label, "test", **kw), vote, label,
                       num_classes, ignore_index, nsample, miou_B_I, batch)
+
+
+@torch.no_grad()
+def vote_spheres(logits, input_inds, n_sub):
+    """validate_sphere's `scatter(all_logits, idx_points, dim=0, reduce='mean')` (main.py:461-468) without atomics: logits
+    (M,C) float32 rows in (batch, slot) order, input_inds (M) -> (voted (n_sub,C), visits (n_sub) int32).  A gather over the
+    reverse lists of input_inds (amc3d_group_csr with b = 1, then amc3d_pointops_scatter_csr's summation-order contract): per
+    sub-point the float32 sum of its rows in ascending (batch, slot) order from +0, divided by their number -- the same bits on
+    every run.  A sub-point no sphere visited gets zero logits."""
+    from . import ops
+    from .offset_ops import _scatter_csr_lists
+    flat = logits.contiguous()
+    idx = input_inds.reshape(1, -1, 1).to(torch.int32).contiguous()
+    rev_start, rev_edge = ops.group_csr(idx, int(n_sub))
+    total = _scatter_csr_lists(0, rev_start, rev_edge, int(n_sub), flat.shape[1], 1, 1, flat, None)
+    visits = rev_start[1:] - rev_start[:-1]
+    # the float32 quotient through float64: 53 bits round once more to the correctly rounded float32 division (53 >= 2 * 24 + 2)
+    return (total.double() / visits.clamp(min=1).double().unsqueeze(1)).float(), visits
+
+
+@torch.no_grad()
+def validate_sphere(model, batches, n_sub, projections, labels, num_classes, ignore_index=None, feature_keys="x,heights",
+                    distributed=False, details=False):
+    """The reference's validate_sphere (examples/segmentation/main.py:436-483) on S3DISSphere batches of ONE cloud (the
+    reference validates cloud 0 only): every batch {pos, x, heights, input_inds, ...} goes through the model in eval mode, the
+    logits of all slots of all batches -- padding duplicates included, the reference applies no mask here -- are averaged per
+    sub-point (vote_spheres), then argmax, then pred[projections] against the raw points' labels into one confusion matrix.
+    n_sub: the cloud's number of sub-points; projections (n_raw): input_pipeline.sphere_projections or the reference's own;
+    labels (n_raw).  Differences from the reference: the vote adds in ascending (batch, slot) order instead of atomics, and a
+    sub-point no sphere visited has zero logits (class 0) where the reference's shorter scatter output would raise on
+    projection.  distributed=True all-reduces the confusion vectors only (the reference's all_reduce of logits and indices
+    is not built).  Returns summarize(cm): (miou, macc, oa, ious, accs); details=True: dict(logits (n_sub,C) voted, pred (n_sub),
+    cm) instead, before any cross-rank sum."""
+    from .train import get_features_by_keys
+    model.eval()
+    cm = _matrices(num_classes, ignore_index)[0]
+    dev = next(model.parameters()).device
+    all_logits, inds = [], []
+    for data in batches:
+        data = dict(data)
+        data["x"] = get_features_by_keys(data, feature_keys)
+        logits = _logits(model(data))
+        all_logits.append(logits.transpose(1, 2).reshape(-1, num_classes))
+        inds.append(data["input_inds"].reshape(-1))
+    if not all_logits:
+        raise ValueError("validate_sphere: no batches")
+    voted, _ = vote_spheres(torch.cat(all_logits, dim=0), torch.cat(inds), n_sub)
+    pred = voted.argmax(dim=1)
+    projections = torch.as_tensor(projections).to(dev).long().reshape(-1)
+    labels = torch.as_tensor(labels).to(dev).long().reshape(-1)
+    cm.update(pred[projections], labels)
+    if details:
+        return {"logits": voted, "pred": pred, "cm": cm}
+    return summarize(cm, distributed=distributed)

@@ -16,7 +16,8 @@ numbers the reference drew.  numpy's argsort is not stable, so WHICH point of a 
 Batch-level calls: scannet_train_batch (ScanNet's training item, room by room after the transform), scannet_train_rooms /
 ScanNetTrainFeed (the same item for the whole batch at once on csrc/room_input.hip, one read-back per batch),
 s3dis_train_batch / S3DISTrainFeed (S3DIS's training item for a whole batch of raw rooms on csrc/room_input.hip, one read-back
-per batch), and the validation / whole-room testing items.
+per batch), the validation / whole-room testing items, and S3DISSphere's potential-picked spheres (SpherePotentials,
+s3dis_sphere_batch, S3DISSphereFeed, sphere_projections on csrc/sphere.hip: no read-back per batch).
 """
 import ctypes
 
@@ -1008,3 +1009,290 @@ class ScanNetTrainFeed:
                              torch.cat([t[self.starts[j]:self.starts[j] + self.sizes[j]] for j in pick]))
             yield _scannet_batch(cut(self.coord), cut(self.feat), cut(self.label), [self.sizes[j] for j in pick], self.transform,
                                  self.voxel_size, self.voxel_max, False, self.generator, d, 2, "ScanNetTrainFeed")
+
+
+# ---- S3DISSphere: potential-picked spheres out of whole sub-sampled Areas (dataset/s3dis/s3dis_sphere.py, csrc/sphere.hip) ----
+_POT_BLOCK = 1024  # kPotBlock of csrc/sphere.hip: potentials per entry of the minima table
+
+
+class SpherePotentials:
+    """The resident state of S3DISSphere's schedule (s3dis_sphere.py:214-247): the sub-clouds of a split, concatenated, the
+    float64 potentials of their points and the table of block minima the centre pick runs over.
+
+    clouds: list of (sub_points (n,3) float32, sub_colors (n,3), sub_labels (n)) GPU tensors -- an Area after
+    crop_pc(points, colors, labels, voxel_size=voxel_size); colours are kept as float32, labels as int64.
+    potentials: list of (n) float64 tensors or arrays, one per cloud (the tests pass the reference's own); None draws the
+    reference's rand(n) * 1e-3 per cloud on the device from `generator`.
+    advance(steps) runs the next `steps` schedule steps on the device -- five launches each, counting the library sort as one,
+    nothing read back -- and returns (cloud_ind (steps) int64, point_ind (steps) int64, noise (steps,3) float64): because step s
+    depends only on the steps before it, the concatenation over calls is the table the reference precomputes for
+    num_epochs * num_steps steps from the same draws.
+    Arithmetic: the reference's with numpy >= 2 (the Tukey weights and their comparison are float64 there; numpy 1.x keeps them
+    float32).  Equal distances inside a sphere are listed in ascending point order and a tied potential minimum is the first
+    one (the reference: sklearn's unspecified order, numpy's first minimum).  A sphere without any point (a noise draw of about
+    ten sigma; the reference raises inside np.random.choice) updates nothing."""
+
+    def __init__(self, clouds, in_radius, num_points, potentials=None, generator=None):
+        clouds = list(clouds)
+        if len(clouds) == 0:
+            raise ValueError("SpherePotentials: no clouds")
+        for p, c, l in clouds:
+            _need_gpu(p, c, l)
+            _need_dtype(torch.float32, sub_points=p)
+            if p.dim() != 2 or p.shape[1] != 3 or p.shape[0] == 0 or c.shape != p.shape or l.numel() != p.shape[0] \
+                    or p.device != clouds[0][0].device:
+                raise ValueError("SpherePotentials: every cloud needs sub_points (n,3), sub_colors (n,3), sub_labels (n) with n > 0, "
+                                 "on one GPU")
+        if not float(in_radius) > 0 or int(num_points) <= 0:
+            raise ValueError("SpherePotentials: in_radius and num_points are positive")
+        self.in_radius, self.num_points, self.generator = float(in_radius), int(num_points), generator
+        self.dev = dev = clouds[0][0].device
+        self.sizes = [int(p.shape[0]) for p, _, _ in clouds]
+        self.offsets = [0]
+        for n in self.sizes:
+            self.offsets.append(self.offsets[-1] + n)
+        self.total = self.offsets[-1]
+        if self.total >= 2 ** 31:
+            raise ValueError(f"SpherePotentials: {self.total} points (at most 2^31 - 1)")
+        one = len(clouds) == 1
+        self.points = clouds[0][0].contiguous() if one else torch.cat([p for p, _, _ in clouds])
+        self.colors = torch.cat([c.to(torch.float32) for _, c, _ in clouds]).contiguous()
+        self.labels = torch.cat([l.reshape(-1).to(torch.int64) for _, _, l in clouds]).contiguous()
+        self.cloud_off = torch.tensor(self.offsets, dtype=torch.int32).to(dev)
+        self.n_max = max(self.sizes)
+        self.nb_max = max((self.offsets[c + 1] - 1) // _POT_BLOCK - self.offsets[c] // _POT_BLOCK + 1 for c in range(len(clouds)))
+        if potentials is None:
+            self.potentials = torch.cat([torch.rand(n, dtype=torch.float64, device=dev, generator=generator) for n in self.sizes]) * 1e-3
+        else:
+            potentials = [torch.as_tensor(p).to(device=dev, dtype=torch.float64).reshape(-1) for p in potentials]
+            if [int(p.shape[0]) for p in potentials] != self.sizes:
+                raise ValueError("SpherePotentials: one potential per point of every cloud")
+            self.potentials = torch.cat(potentials).contiguous()
+        nblk = -(-self.total // _POT_BLOCK)
+        self.blk_val = torch.empty(nblk, dtype=torch.float64, device=dev)
+        self.blk_idx = torch.empty(nblk, dtype=torch.int32, device=dev)
+        self.touched = torch.empty(nblk, dtype=torch.int32, device=dev)
+        self.lib = lib = _lib.load()
+        self.wb = int(lib.amc3d_sphere_workspace_bytes(self.n_max))
+        self.work = torch.empty(max(self.wb, 8), dtype=torch.uint8, device=dev)
+        self.steps_done = 0
+        with torch.cuda.device(dev):
+            _lib.check(lib.amc3d_sphere_minima(self.total, _opt(self.potentials), _opt(self.blk_val), _opt(self.blk_idx),
+                                               _opt(self.touched), _stream(self.points)), "sphere_minima")
+
+    def cloud_potentials(self):
+        """the potentials per cloud (views)"""
+        return [self.potentials[self.offsets[c]:self.offsets[c + 1]] for c in range(len(self.sizes))]
+
+    def _noise(self, steps, noise):
+        if noise is None:  # np.random.normal(scale=in_radius / 10, size=(1, 3)) per step
+            return torch.randn(steps, 3, dtype=torch.float64, device=self.dev, generator=self.generator) * (self.in_radius / 10)
+        noise = torch.as_tensor(noise).to(device=self.dev, dtype=torch.float64).reshape(-1, 3).contiguous()
+        if noise.shape[0] != steps:
+            raise ValueError(f"SpherePotentials: noise holds {noise.shape[0]} rows for {steps} spheres")
+        return noise
+
+    def _lists(self, n):
+        dev = self.dev
+        return (torch.empty(n, 3, dtype=torch.float64, device=dev), torch.empty(n, self.num_points, dtype=torch.int32, device=dev),
+                torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+
+    def advance(self, steps, noise=None, lists=False):
+        """the next `steps` schedule steps -> (cloud_ind, point_ind, noise) on the device; lists=True adds the dictionary of
+        every step's query (centre (steps,3) float64, order (steps,num_points) int32, cur, count (steps) int32), which is the
+        query its item repeats in the reference"""
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError("SpherePotentials.advance: steps is not negative")
+        noise = self._noise(steps, noise)
+        cloud = torch.empty(steps, dtype=torch.int32, device=self.dev)
+        point = torch.empty(steps, dtype=torch.int32, device=self.dev)
+        centre, order, cur, count = self._lists(steps)
+        if steps:
+            with torch.cuda.device(self.dev):
+                _lib.check(self.lib.amc3d_sphere_schedule(
+                    len(self.sizes), self.total, self.n_max, self.nb_max, steps, self.num_points, ctypes.c_double(self.in_radius),
+                    _opt(self.points), _opt(self.cloud_off), _opt(self.potentials), _opt(self.blk_val), _opt(self.blk_idx),
+                    _opt(self.touched), _opt(noise), _opt(cloud), _opt(point), _opt(centre), _opt(order) if lists else None,
+                    _opt(cur), _opt(count), _opt(self.work), self.wb, _stream(self.points)), "sphere_schedule")
+        self.steps_done += steps
+        out = (cloud.long(), point.long(), noise)
+        if lists:
+            return out + ({"cloud": cloud, "point": point, "centre": centre, "order": order, "cur": cur, "count": count},)
+        return out
+
+    def query(self, cloud_ind, point_ind, noise):
+        """the radius query of given centres (three launches each, counting the sort as one; the potentials are not touched) ->
+        {cloud, point (B) int32, centre (B,3) float64, order (B,num_points) int32 (-1 beyond count), cur, count (B) int32}"""
+        cloud = torch.as_tensor(cloud_ind).to(device=self.dev, dtype=torch.int32).reshape(-1).contiguous()
+        point = torch.as_tensor(point_ind).to(device=self.dev, dtype=torch.int32).reshape(-1).contiguous()
+        B = int(cloud.shape[0])
+        if point.shape[0] != B:
+            raise ValueError("SpherePotentials.query: one point per cloud index")
+        noise = self._noise(B, noise)
+        centre, order, cur, count = self._lists(B)
+        if B:
+            with torch.cuda.device(self.dev):
+                _lib.check(self.lib.amc3d_sphere_query(
+                    len(self.sizes), self.total, self.n_max, B, self.num_points, ctypes.c_double(self.in_radius), _opt(self.points),
+                    _opt(self.cloud_off), _opt(cloud), _opt(point), _opt(noise), _opt(centre), _opt(order), _opt(cur), _opt(count),
+                    _opt(self.work), self.wb, _stream(self.points)), "sphere_query")
+        return {"cloud": cloud, "point": point, "centre": centre, "order": order, "cur": cur, "count": count}
+
+
+def _sphere_draw_table(given, B, N, count, pad, who):
+    """per-sphere draws that were passed in -> ((B,N) int32 table, -1 where the device draws; one read-back: the counts size
+    them).  perm[b]: a permutation of count[b]; pad[b]: N - count[b] indices below count[b], stored in slots count[b].."""
+    dev = count.device
+    given = list(given)
+    if len(given) != B:
+        raise ValueError(f"{who}: per-sphere draws need one entry per sphere")
+    cnt = count.tolist()
+    table = torch.full((B, N), -1, dtype=torch.int32, device=dev)
+    for b, v in enumerate(given):
+        if v is None:
+            continue
+        v = torch.as_tensor(v).to(dev)
+        c = cnt[b]
+        if pad:
+            if v.shape != (N - c,) or v.is_floating_point() or (v.numel() and bool(((v < 0) | (v >= c)).any())):
+                raise ValueError(f"{who}: sphere {b}: pad must hold {N - c} indices below {c}")
+            table[b, c:] = v
+        else:
+            if v.shape != (c,) or v.is_floating_point() or not bool((v.sort().values == torch.arange(c, device=dev)).all()):
+                raise ValueError(f"{who}: sphere {b}: perm must be a permutation of {c}")
+            table[b, :c] = v
+    return table
+
+
+def _sphere_tail(state, q, perm_t, pad_t, pad_u, gravity_dim):
+    B, N, dev = int(q["cloud"].shape[0]), state.num_points, state.dev
+    out = {"pos": torch.empty(B, N, 3, dtype=torch.float32, device=dev), "x": torch.empty(B, N, 3, dtype=torch.float32, device=dev),
+           "heights": torch.empty(B, N, 1, dtype=torch.float32, device=dev), "y": torch.empty(B, N, dtype=torch.int64, device=dev),
+           "mask": torch.empty(B, N, dtype=torch.int32, device=dev), "cloud_index": q["cloud"].long(),
+           "input_inds": torch.empty(B, N, dtype=torch.int64, device=dev)}
+    with torch.cuda.device(dev):
+        _lib.check(state.lib.amc3d_sphere_tail(
+            len(state.sizes), B, N, int(gravity_dim), _opt(state.points), _opt(state.colors), _opt(state.labels), _opt(state.cloud_off),
+            _opt(q["cloud"]), _opt(q["point"]), _opt(q["centre"]), _opt(q["order"]), _opt(q["count"]), _opt(perm_t), _opt(pad_t),
+            _opt(pad_u), _opt(out["input_inds"]), _opt(out["mask"]), _opt(out["pos"]), _opt(out["x"]), _opt(out["y"]),
+            _opt(out["heights"]), _stream(state.points)), "sphere_tail")
+    return out
+
+
+def s3dis_sphere_batch(state, steps_or_B, transform=None, draws=None, generator=None, gravity_dim=2):
+    """S3DISSphere.__getitem__ (s3dis_sphere.py:288-347) plus the default collate for B spheres of `state` (a SpherePotentials).
+    steps_or_B: an int B -- the next B schedule steps, whose potentials are updated (state.advance) -- or the (cloud_ind,
+    point_ind, noise) of B steps already advanced, which are queried again as the reference's item does.
+    transform: an augment.S3DISTrainAugment, a transforms.TransformChain or None, applied to pos = point - pick and the colours.
+    Returns {pos (B,N,3) fp32, x (B,N,3) fp32, heights (B,N,1) fp32, y (B,N) int64, mask (B,N) int32, cloud_index (B) int64,
+    input_inds (B,N) int64, cloud-local}, N = num_points.  heights follows the reference's `if 'heights' not in data` rule: the
+    chain's value where its list holds a PointCloudCenterAndNormalize (the only reference transform that writes one), otherwise
+    the point's own gravity coordinate, before the centring.
+    Per sphere, count = min(cur, N): slots below count are the query's first count points shuffled, the others repeat draws
+    among them; mask is 1 below count.  cur == 0: every slot is the centre's own point and mask is 0.
+    draws: "perm" / "pad" as per-sphere lists (entries may be None) of the reference's np.random.permutation (count entries)
+    and np.random.choice(cur, N - cur), "centre_noise" (B,3) for the B steps an int advances (the schedule's
+    np.random.normal), plus the transform's keys.  Device draws: the shuffle is the argsort of uniforms
+    restricted to the first count slots, the padding floor(u * count) of float64 uniforms -- both enqueued without knowing
+    count.  Host synchronisation: none with generator draws; passed-in perm / pad are validated against the counts, which
+    reads them back."""
+    who = "s3dis_sphere_batch"
+    if not isinstance(state, SpherePotentials):
+        raise TypeError(f"{who}: state is a SpherePotentials")
+    if gravity_dim not in (0, 1, 2):
+        raise ValueError(f"{who}: gravity_dim is 0, 1 or 2")
+    generator = generator if generator is not None else state.generator
+    d = dict(draws or {})
+    centre_noise = d.pop("centre_noise", None)
+    if isinstance(steps_or_B, int):
+        q = state.advance(steps_or_B, noise=centre_noise, lists=True)[3]
+    else:
+        q = state.query(*steps_or_B)
+    B, N, dev = int(q["cloud"].shape[0]), state.num_points, state.dev
+    if B == 0:
+        raise ValueError(f"{who}: no spheres")
+    perm_g, pad_g = d.pop("perm", None), d.pop("pad", None)
+    count = q["count"]
+    perm_t = pad_t = pad_u = None
+    if perm_g is not None:
+        perm_t = _sphere_draw_table(perm_g, B, N, count, False, who)
+    if perm_g is None or any(v is None for v in perm_g):
+        u = torch.rand(B, N, device=dev, generator=generator)
+        slot = torch.arange(N, device=dev, dtype=torch.int32).view(1, N)
+        drawn = torch.where(slot < count.view(B, 1), u, 2.0).argsort(dim=1, stable=True).int()
+        given = torch.tensor([v is not None for v in perm_g], device=dev).view(B, 1) if perm_g is not None else None
+        perm_t = drawn if given is None else torch.where(given, perm_t, drawn)
+    if pad_g is not None:
+        pad_t = _sphere_draw_table(pad_g, B, N, count, True, who)
+    if pad_g is None or any(v is None for v in pad_g):
+        pad_u = torch.rand(B, N, dtype=torch.float64, device=dev, generator=generator)
+    out = _sphere_tail(state, q, perm_t.contiguous(), pad_t, pad_u, gravity_dim)
+    if transform is None:
+        return out
+    if _is_chain(transform):
+        t = transform({"pos": out["pos"], "x": out["x"]}, draws=_chain_draws(transform, d, [N] * B, dev, generator))
+        out["pos"], out["x"] = t["pos"], t["x"]
+        if "PointCloudCenterAndNormalize" in transform.names:
+            out["heights"] = t["heights"]
+        return out
+    if any(k not in d for k in list(_S3DIS_TRANSFORM_KEYS) + ["noise"]):
+        for k, t in _s3dis_transform_draws(transform, B, N, dev, generator).items():
+            d.setdefault(k, t)
+    for k, shape in list(_S3DIS_TRANSFORM_KEYS.items()) + [("noise", (N, 3))]:
+        d[k] = torch.as_tensor(d[k]).to(dev)
+        if d[k].shape != (B,) + shape:
+            raise ValueError(f"{who}: draws[{k!r}] has shape {tuple(d[k].shape)}, not {(B,) + shape}")
+    out["pos"], out["x"], _ = _s3dis_augment(transform, out["pos"], out["x"], d)
+    return out
+
+
+class S3DISSphereFeed:
+    """An epoch of S3DISSphere batches from sub-clouds resident on the device: what DataLoader(S3DISSphere(...), batch_size,
+    shuffle=shuffle, drop_last=True) yields, `mask` and `input_inds` included.  len = num_steps // batch_size.  Every `iter` is
+    the next epoch of the schedule (the reference's `epoch * num_steps` offset into its precomputed table): with shuffle=False
+    batch i advances the schedule by its own batch_size steps at the moment the consumer asks for it, and the steps a last,
+    incomplete batch would hold are advanced at the end; shuffle=True advances the epoch's whole schedule first, permutes its
+    items on the device and queries every batch's centres again.  Nothing is read back.  train.train_one_epoch takes it as
+    `train_loader` (with a criterion whose name contains 'mask' the loop passes data['mask'] on)."""
+
+    def __init__(self, clouds, transform, batch_size, in_radius, num_points, num_steps, shuffle=False, potentials=None,
+                 generator=None, gravity_dim=2):
+        if int(batch_size) <= 0 or int(num_steps) < 0:
+            raise ValueError("S3DISSphereFeed: batch_size is positive and num_steps is not negative")
+        self.state = SpherePotentials(clouds, in_radius, num_points, potentials=potentials, generator=generator)
+        self.transform, self.batch_size, self.num_steps = transform, int(batch_size), int(num_steps)
+        self.shuffle, self.generator, self.gravity_dim = bool(shuffle), generator, gravity_dim
+        self.epoch = 0
+
+    def __len__(self):
+        return self.num_steps // self.batch_size
+
+    def __iter__(self):
+        B, n = self.batch_size, len(self)
+        self.epoch += 1
+        if self.shuffle:
+            cloud, point, noise = self.state.advance(self.num_steps)
+            ids = torch.randperm(self.num_steps, device=self.state.dev, generator=self.generator)
+            for i in range(n):
+                pick = ids[i * B:(i + 1) * B]
+                yield s3dis_sphere_batch(self.state, (cloud[pick], point[pick], noise[pick]), self.transform,
+                                         generator=self.generator, gravity_dim=self.gravity_dim)
+        else:
+            for i in range(n):
+                yield s3dis_sphere_batch(self.state, B, self.transform, generator=self.generator, gravity_dim=self.gravity_dim)
+            self.state.advance(self.num_steps - n * B)
+
+
+def sphere_projections(points, sub_points):
+    """S3DISSphere's validation projections (s3dis_sphere.py:255-266): per raw point the index of its nearest sub-point, (n)
+    int64, on the k-NN search with k = 1.  The reference asks sklearn's KD-tree, float64; here the distance is the search's
+    float32 ((dx*dx + dy*dy) + dz*dz) of the direct differences with its own order of equal distances, so a raw point with two
+    sub-points at one float32 distance may take the other one."""
+    _need_gpu(points, sub_points)
+    _need_dtype(torch.float32, points=points, sub_points=sub_points)
+    if points.dim() != 2 or points.shape[1] != 3 or sub_points.dim() != 2 or sub_points.shape[1] != 3 or sub_points.shape[0] == 0:
+        raise ValueError("sphere_projections: points (n,3) and sub_points (m,3) with m > 0")
+    from . import ops
+    _, idx = ops.knn_batch(1, sub_points.contiguous().unsqueeze(0), points.contiguous().unsqueeze(0))
+    return idx.reshape(-1).long()

@@ -132,8 +132,13 @@ def _index(idx, rows, name="idx"):
 def _scatter_csr(kind, idx, n_targets, c, per, w_c, g, w):
     """out (n_targets,c): the scatter of `kind` as a gather over the reverse lists of idx (every element written)"""
     rev_start, rev_edge = _o.group_csr(idx.view(1, idx.shape[0], idx.shape[1]), n_targets)
+    return _scatter_csr_lists(kind, rev_start, rev_edge, n_targets, c, per, w_c, g, w)
+
+
+def _scatter_csr_lists(kind, rev_start, rev_edge, n_targets, c, per, w_c, g, w):
+    """_scatter_csr over reverse lists the caller already holds (ops.group_csr with b = 1)"""
     out = torch.empty(n_targets, c, dtype=torch.float32, device=g.device)
-    with torch.cuda.device(g.device), timing.span("pointops_scatter_csr", g.numel() * 4 + idx.numel() * 8 + out.numel() * 4):
+    with torch.cuda.device(g.device), timing.span("pointops_scatter_csr", g.numel() * 4 + rev_edge.numel() * 8 + out.numel() * 4):
         _lib.check(_lib.load().amc3d_pointops_scatter_csr(kind, n_targets, c, per, w_c, _ptr(g), _ptr(w) if w is not None else None,
                                                           _ptr(rev_start), _ptr(rev_edge), _ptr(out), _o._stream(g)),
                    "pointops_scatter_csr")

@@ -1215,6 +1215,46 @@ int amc3d_scannet_crop_tail_rooms(int rooms, int n, int voxel_max, int gravity_d
                                   const int *perm, float *pos_out, float *x_out, float *heights, long long *y_out,
                                   void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- S3DISSphere: spheres cut out of whole voxel-subsampled Areas, centres picked by a running potential
+ * (dataset/s3dis/s3dis_sphere.py:214-247 the schedule, :288-347 the item; csrc/sphere.hip).  The sub-clouds are concatenated:
+ * points (total,3) fp32, colours (total,3) fp32, labels (total) int64, cloud c = points [cloud_off[c], cloud_off[c+1])
+ * (cloud_off (clouds+1) int32, device memory, no empty cloud, total < 2^31); n_max = the largest cloud's size.  point indices
+ * are cloud-local.  potentials (total) fp64; blk_val / blk_idx / touched (ceil(total / 1024)): the first minimum of every 1024
+ * consecutive potentials (value, global index) and a mark "stale", all three written by sphere_minima.
+ * The radius query of a centre (cloud, point, noise (3) fp64): pick = points[point] + noise in fp64, as the reference forms it
+ * from the KD-tree's float64 copy of the coordinates (centre (.,3) fp64, written); d2 = ((dx*dx + dy*dy) + dz*dz) in fp64, no
+ * contraction, as sklearn's KDTree evaluates it; the points with
+ * d2 <= radius*radius in ascending (d2, point) order -- equal distances in ascending point order, which sklearn leaves
+ * unspecified (one stable device-wide radix sort of n_max pairs).  cur = their number, count = min(cur, num_points), order
+ * (.,num_points) = the first num_points of them, -1 beyond.
+ * sphere_schedule, per step s: cloud = argmin over the clouds' minima, point = argmin of its potentials, first minimum in both
+ * (cloud_ind[s], point_ind[s], written); the query with noise[s]; potentials[q] += t for the count listed points, t =
+ * (1 - d32 / r^2)^2 and 0 where d32 > r^2, d32 = ((x*x + y*y) + z*z) in fp32 of the fp64 differences point - pick rounded to
+ * fp32, and everything after it in fp64 (numpy >= 2: np.square(python float) is a float64 scalar and promotes); then the stale table entries of that cloud.
+ * Points of one sphere are distinct: no atomics, the same bits on every run.  Five launches per step counting the sort as
+ * one; nb_max = the most table entries one cloud spans.  order may be NULL.  An empty sphere (cur = 0) updates nothing.
+ * sphere_query: the query alone for given centres (three launches per sphere counting the sort as one).
+ * sphere_tail, one launch for all spheres: slot k < count takes list entry perm[k] (perm (spheres,num_points), its first count
+ * entries a permutation of them; NULL: identity), slot k >= count entry perm[pad[k]] (pad (spheres,num_points), only those
+ * slots read; negative or NULL: (int)(pad_u[k] * count)); input_inds (int64, cloud-local), mask (int32, 1 below count), pos =
+ * fl32(point - pick), the difference in fp64, x = colours, y = label, heights = the point's own gravity coordinate.  An empty sphere gives the
+ * centre's point in every slot and mask 0 (the reference raises there).  Draws out of range are clamped.
+ * No entry allocates, synchronises or reads back, and no memset node appears under capture. */
+size_t amc3d_sphere_workspace_bytes(int n_max);
+int amc3d_sphere_minima(int total, const double *potentials, double *blk_val, int *blk_idx, int *touched, void *stream);
+int amc3d_sphere_schedule(int clouds, int total, int n_max, int nb_max, int steps, int num_points, double radius,
+                          const float *points, const int *cloud_off, double *potentials, double *blk_val, int *blk_idx,
+                          int *touched, const double *noise, int *cloud_ind, int *point_ind, double *centre, int *order,
+                          int *cur, int *count, void *workspace, size_t workspace_bytes, void *stream);
+int amc3d_sphere_query(int clouds, int total, int n_max, int spheres, int num_points, double radius, const float *points,
+                       const int *cloud_off, const int *cloud_ind, const int *point_ind, const double *noise, double *centre,
+                       int *order, int *cur, int *count, void *workspace, size_t workspace_bytes, void *stream);
+int amc3d_sphere_tail(int clouds, int spheres, int num_points, int gravity_dim, const float *points, const float *colours,
+                      const long long *labels, const int *cloud_off, const int *cloud_ind, const int *point_ind,
+                      const double *centre, const int *order, const int *count, const int *perm, const int *pad,
+                      const double *pad_u, long long *input_inds, int *mask, float *pos, float *x, long long *y,
+                      float *heights, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
