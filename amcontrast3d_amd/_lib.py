@@ -181,6 +181,7 @@ SIGNATURES = {
     "amc3d_local_aggregation_csr_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "amc3d_local_aggregation_workspace_q_offset": (_sz, [_i, _i, _i, _i]),
     "amc3d_local_aggregation_partial_counts": (_i, [_i, _i, _i, _i, _i, _vp]),
+    "amc3d_local_aggregation_pool_centroids": (_i, [_i, _i, _i]),
     "amc3d_local_aggregation_backward_csr": (_i, [_i] * 6 + [_vp] * 19 + [_i, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_local_aggregation_backward_csr_strided": (_i, [_i] * 6 + [_vp] * 7 + [_l] + [_vp] * 10 + [_l] + [_vp] * 2 + [_i, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_three_interpolate_grad_csr": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

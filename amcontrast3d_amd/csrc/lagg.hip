@@ -815,6 +815,15 @@ static int lagg_scatter_tiles(int b, int C, int M)
     return wgs1 <= 8192 ? 1 : LAGG_TILES;
 }
 
+// centroids per wave of the max-pool kernel: 8, fewer where that leaves the chip with under ~2 workgroups per CU (the coarse stages)
+static int lagg_pool_cpw(int b, int cout, int npoints)
+{
+    const int ct = cout < LAGG_CT ? cout : LAGG_CT;
+    int cpw = 8;
+    while (cpw > 1 && (long)div_up(npoints, 4 * cpw) * (cout / ct) * b < 1024) cpw >>= 1;
+    return cpw;
+}
+
 static size_t lagg_partial_bytes(int b, int C, int n, int M)
 {
     const size_t pf = (size_t)b * div_up(n, LAGG_SP),  // the statistics: at most one partial per 256-point pass (lagg_stats_pts)
@@ -937,6 +946,14 @@ AMC_API int amc3d_local_aggregation_partial_counts(int b, int cout, int n, int n
     return 0;
 }
 
+// centroids per wave the forward's max-pool launch takes at this shape (8, 4, 2 or 1: a workgroup pools 4 times as many); -1:
+// not a shape of the layer (tests and tools)
+AMC_API int amc3d_local_aggregation_pool_centroids(int b, int cout, int npoints)
+{
+    if (b <= 0 || npoints <= 0 || !lagg_supported(cout, 1)) return -1;
+    return lagg_pool_cpw(b, cout, npoints);
+}
+
 AMC_API size_t amc3d_local_aggregation_workspace_bytes(int b, int cout, int n, int npoints)
 {
     if (b <= 0 || cout <= 0 || n <= 0 || npoints <= 0) return 0;
@@ -979,9 +996,7 @@ static int local_aggregation_forward_impl(int b, int cout, int n, int npoints, i
         if (phase == 1) return launch_status("amc3d_local_aggregation_forward");
     }
     const int ct = cout < LAGG_CT ? cout : LAGG_CT;
-    // centroids per wave: 8, fewer where that leaves the chip with under ~2 workgroups per CU (the coarse stages)
-    int cpw = 8;
-    while (cpw > 1 && (long)div_up(npoints, 4 * cpw) * (cout / ct) * b < 1024) cpw >>= 1;
+    const int cpw = lagg_pool_cpw(b, cout, npoints);
     const size_t lds = (size_t)3 * ct * (4 * cpw + 1) * sizeof(float);
 #define AMC_POOL(L)                                                                                                            \
     hipLaunchKernelGGL(lagg_pool_kernel<L>, dim3(div_up(npoints, 4 * cpw), cout / ct, b), dim3(256), lds, stream, cout, n, npoints, \

@@ -823,6 +823,9 @@ int amc3d_grouped_conv_bn_forward_rows(int b, int cout, int n, int npoints, int 
  * shape): counts[0] the forward statistics, [1] the pooled layer's backward scatter, [2] the atomic collapse of
  * amc3d_grouped_conv_bn_backward, [3] its reverse-list collapse.  counts: 4 ints on the host. */
 int amc3d_local_aggregation_partial_counts(int b, int cout, int n, int npoints, int nsample, int *counts);
+/* centroids per wave of the forward's max-pool launch at this shape: 8, or 4, 2, 1 where 8 would leave the grid below 1024
+ * workgroups (a workgroup of four waves pools 4 times as many).  The launch itself uses this rule.  -1: not a shape of the layer. */
+int amc3d_local_aggregation_pool_centroids(int b, int cout, int npoints);
 int amc3d_grouped_conv_bn_backward_strided(int b, int cout, int n, int npoints, int nsample, int relu,
                                            const float *dx1, const float *g_pm, const int *idx, const float *dp,
                                            const float *w_dp, long ldw, const void *moments, const double *gd,
