@@ -173,34 +173,24 @@ SIGNATURES = {
     "amc3d_group_moments_bytes": (_sz, [_i, _i]),
     "amc3d_group_moments": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_local_aggregation_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "amc3d_local_aggregation_forward": (_i, [_i] * 7 + [_f, _f] + [_vp] * 18 + [_i, _vp, _vp, _sz, _vp]),
-    "amc3d_local_aggregation_forward_strided": (_i, [_i] * 7 + [_f, _f] + [_vp] * 4 + [_l] + [_vp] * 14 + [_i, _vp, _vp, _sz, _vp]),
-    "amc3d_local_aggregation_forward_rows": (_i, [_i] * 7 + [_f, _f] + [_vp] * 4 + [_l] + [_vp] * 13 + [_i, _vp, _vp, _sz, _vp]),
-    "amc3d_local_aggregation_backward": (_i, [_i] * 6 + [_vp] * 17 + [_i, _vp, _vp, _vp, _sz, _vp]),
-    "amc3d_local_aggregation_backward_strided": (_i, [_i] * 6 + [_vp] * 7 + [_l] + [_vp] * 8 + [_l] + [_vp] * 2 + [_i, _vp, _vp, _vp, _sz, _vp]),
+    "amc3d_local_aggregation_forward": (_i, [_i] * 7 + [_f, _f] + [_vp] * 4 + [_l] + [_vp] * 14 + [_i, _vp, _vp, _sz, _vp]),
+    "amc3d_local_aggregation_backward": (_i, [_i] * 6 + [_vp] * 7 + [_l] + [_vp] * 10 + [_l] + [_vp] * 2 + [_i, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_local_aggregation_csr_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "amc3d_local_aggregation_workspace_q_offset": (_sz, [_i, _i, _i, _i]),
     "amc3d_local_aggregation_partial_counts": (_i, [_i, _i, _i, _i, _i, _vp]),
     "amc3d_local_aggregation_pool_centroids": (_i, [_i, _i, _i]),
-    "amc3d_local_aggregation_backward_csr": (_i, [_i] * 6 + [_vp] * 19 + [_i, _vp, _vp, _vp, _sz, _vp]),
-    "amc3d_local_aggregation_backward_csr_strided": (_i, [_i] * 6 + [_vp] * 7 + [_l] + [_vp] * 10 + [_l] + [_vp] * 2 + [_i, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_three_interpolate_grad_csr": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "amc3d_masked_refine_backward_csr": (_i, [_i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "amc3d_pointwise_conv_forward_bf16": (_i, [_i, _i, _i, _l, _vp, _vp, _vp, _vp, _vp]),
     "amc3d_pointwise_conv_workspace_bytes_bf16": (_sz, [_i, _i, _i, _l]),
     "amc3d_pointwise_conv_backward_bf16": (_i, [_i, _i, _i, _l, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_grouped_conv_bn_supported": (_i, [_i, _i]),
-    "amc3d_grouped_conv_bn_forward": (_i, [_i] * 7 + [_f, _f] + [_vp] * 16 + [_i, _vp, _vp, _sz, _vp]),
-    "amc3d_grouped_conv_bn_forward_strided": (_i, [_i] * 7 + [_f, _f] + [_vp] * 4 + [_l] + [_vp] * 12 + [_i, _vp, _vp, _sz, _vp]),
-    "amc3d_grouped_conv_bn_forward_rows": (_i, [_i] * 7 + [_f, _f] + [_vp] * 4 + [_l] + [_vp] * 11 + [_i, _vp, _vp, _sz, _vp]),
-    "amc3d_grouped_conv_bn_backward": (_i, [_i] * 6 + [_vp] * 15 + [_i, _vp, _vp, _vp, _sz, _vp]),
-    "amc3d_grouped_conv_bn_backward_strided": (_i, [_i] * 6 + [_vp] * 5 + [_l] + [_vp] * 8 + [_l] + [_vp] * 2 + [_i, _vp, _vp, _vp, _sz, _vp]),
+    "amc3d_grouped_conv_bn_forward": (_i, [_i] * 7 + [_f, _f] + [_vp] * 4 + [_l] + [_vp] * 12 + [_i, _vp, _vp, _sz, _vp]),
+    "amc3d_grouped_conv_bn_backward": (_i, [_i] * 6 + [_vp, _i] + [_vp] * 7 + [_l] + [_vp] * 8 + [_l] + [_vp] * 2 + [_i, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_group_csr_workspace_bytes": (_sz, [_i, _i, _i]),
     "amc3d_group_csr": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_group_moments_csr": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_grouped_conv_bn_csr_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "amc3d_grouped_conv_bn_backward_csr": (_i, [_i] * 6 + [_vp, _i] + [_vp] * 16 + [_i, _vp, _vp, _vp, _sz, _vp]),
-    "amc3d_grouped_conv_bn_backward_csr_strided": (_i, [_i] * 6 + [_vp, _i] + [_vp] * 6 + [_l] + [_vp] * 8 + [_l] + [_vp] * 2 + [_i, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_group_csr_dp": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     "amc3d_sa_tail_supported": (_i, [_i, _i, _i]),
     "amc3d_sa_tail_pays": (_i, [_i, _i]),

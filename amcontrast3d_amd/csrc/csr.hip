@@ -9,7 +9,7 @@
 // bit-reproducible results:
 //   amc3d_group_csr            idx (b,m,k) -> rev_start (b*n + 1), rev_edge (b*m*k) positions ordered by (target, position)
 //   amc3d_group_moments_csr    the geometry moments of lagg.hip from the lists (no scattered atomics, exact in-degree)
-//   amc3d_grouped_conv_bn_backward_csr   the collapse pass of the first SetAbstraction layer as a gather
+//   amc3d_grouped_conv_bn_backward with lists   the collapse pass of the first SetAbstraction layer as a gather
 #include "cub_kernel_memset.h"  // hipCUB with its memsets as kernels (graph-safe)
 
 
@@ -692,7 +692,7 @@ __global__ void csr_edge_dp_kernel(long P, long E, const int *__restrict__ rev_e
 
 // rev_dp (b*npoints*nsample, 4) fp32: for every edge of the reverse lists of amc3d_group_csr, in list order, the relative
 // position dp (b,3,npoints,nsample) of its position p and p itself (its int32 bits in the fourth float) -- what the collapse
-// of amc3d_grouped_conv_bn_backward_csr then reads as ONE 16-byte stream instead of an edge id and three 4-byte gathers
+// of amc3d_grouped_conv_bn_backward with lists then reads as ONE 16-byte stream instead of an edge id and three 4-byte gathers
 AMC_API int amc3d_group_csr_dp(int b, int npoints, int nsample, const int *rev_edge, const float *dp, float *rev_dp, void *stream)
 {
     const long P = (long)npoints * nsample, E = (long)b * P;

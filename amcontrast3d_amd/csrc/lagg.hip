@@ -362,7 +362,7 @@ __global__ __launch_bounds__(256) void lagg_pool_kernel(int C, int n, int M, int
 // backward 1: per (b,c,m): dq = dpooled * [relu: bn(ystar) > 0], scatter into Q[b, idx[b,m,arg], c]; per-channel partial sums
 //   {sum dq, sum dq xhat, sum dq dp_j}.  grid (m-tile groups, channel chunks of 128, b)
 // ---------------------------------------------------------------------------------------------------------------
-// LISTS: the deterministic form (amc3d_local_aggregation_backward_csr).  No atomics: the masked gradient dq and its arg go out
+// LISTS: the deterministic form (amc3d_local_aggregation_backward with rev_start).  No atomics: the masked gradient dq and its arg go out
 // point-major -- dq_pm (b, M, C) floats behind Q, arg_pm (b, M, C) bytes -- for lagg_bwd_gather_kernel, which forms Q from the
 // reverse lists; the tile is already transposed in LDS here, so both stores are contiguous over the channels of a wave.
 template <bool LISTS>
@@ -918,7 +918,7 @@ AMC_API int amc3d_group_moments(int b, int n, int npoints, int nsample, const in
 // coef (cout, 4) floats, rounded up so that what follows it in the workspace stays 16-byte aligned
 static size_t lagg_coef_floats(int cout) { return ((size_t)cout * 4 + 3) & ~(size_t)3; }
 
-// the workspace of amc3d_local_aggregation_backward_csr: that of the atomic form | dq_pm (b, npoints, cout) floats | arg_pm bytes
+// the workspace of amc3d_local_aggregation_backward with lists: that of the atomic form | dq_pm (b, npoints, cout) floats | arg_pm bytes
 AMC_API size_t amc3d_local_aggregation_csr_workspace_bytes(int b, int cout, int n, int npoints)
 {
     if (b <= 0 || cout <= 0 || n <= 0 || npoints <= 0) return 0;
@@ -961,40 +961,107 @@ AMC_API size_t amc3d_local_aggregation_workspace_bytes(int b, int cout, int n, i
     return lagg_partial_bytes(b, cout, n, npoints) + (size_t)b * n * cout * sizeof(float) + (size_t)cout * 4 * sizeof(float) + 64;
 }
 
-// G = W_f . f comes from the caller: as rows g_pm (b,n,cout) (rows = true: amc3d_pointwise_conv_forward_rows wrote them, g_cm is
-// unused), or channel-major g_cm (b,cout,n), which is first turned into g_pm.  g_pm is kept for backward.  Outputs:
-// pooled / ystar (b,cout,npoints) fp32, arg (b,cout,npoints) bytes, mean / invstd /
-// var_unbiased (cout), gd (cout,3) doubles.  training == 0: mean / invstd are INPUTS (running statistics), no statistics pass.
-static int local_aggregation_forward_impl(int b, int cout, int n, int npoints, int nsample, int training,
-                                              int relu, float eps, float momentum, const float *g_cm, bool rows,
-                                              const int *idx, const float *dp, WDp w_dp, const void *moments,
-                                              const float *gamma, const float *beta, float *g_pm, float *pooled,
-                                              unsigned char *arg, float *ystar, float *mean, float *invstd,
-                                              float *var_unbiased, double *gd, float *running_mean,
-                                              float *running_var, long long *num_batches_tracked, int phase,
-                                              double *sums, void *workspace, size_t workspace_bytes,
-                                              void *stream_)
-
+static int lagg_bad(const char *entry, const char *what)
 {
-    if (training && phase != 0 && !sums) return bad_arg("amc3d_local_aggregation_forward: phase 1 / 2 need the sums buffer");
+    set_error("%s: %s", entry, what);
+    return (int)hipErrorInvalidValue;
+}
+
+// What both layers' forwards do before their own launch.  G = W_f . f comes from the caller: as rows g_pm (b,n,cout)
+// (g_cm == NULL: amc3d_pointwise_conv_forward_rows wrote them), or channel-major g_cm (b,cout,n), which is first turned into
+// g_pm.  g_pm is kept for backward.  Then the batch statistics: mean / invstd / var_unbiased (cout), gd (cout,3) doubles.
+// training == 0: mean / invstd are INPUTS (running statistics), no statistics pass.
+// *done: the caller launches nothing more (an empty batch; phase 1, which ends with this rank's sums)
+static int lagg_forward_begin(const char *entry, bool (*supported)(int, int), int b, int cout, int n, int npoints, int nsample,
+                              int training, float eps, float momentum, const float *g_cm, const int *idx, const float *dp,
+                              WDp w_dp, const void *moments, const float *gamma, const float *beta, float *g_pm, float *mean,
+                              float *invstd, float *var_unbiased, double *gd, float *running_mean, float *running_var,
+                              long long *num_batches_tracked, int phase, double *sums, void *workspace, size_t workspace_bytes,
+                              void *stream_, bool *done)
+{
+    *done = true;
+    if (w_dp.ld < 3) return lagg_bad(entry, "row stride below 3");
+    if (training && phase != 0 && !sums) return lagg_bad(entry, "phase 1 / 2 need the sums buffer");
     if (b <= 0 || npoints <= 0) return 0;
-    if (!lagg_supported(cout, nsample) || n <= 0 || (!rows && !g_cm) || !idx || !dp || !w_dp || !gamma || !beta || !g_pm || ((uintptr_t)g_pm & 15) ||
-        !pooled || !arg || !ystar || !mean || !invstd || (training && (!moments || !var_unbiased || !gd || !workspace ||
+    if (!supported(cout, nsample) || n <= 0 || !idx || !dp || !w_dp || !gamma || !beta || !g_pm || ((uintptr_t)g_pm & 15) ||
+        !mean || !invstd || (training && (!moments || !var_unbiased || !gd || !workspace ||
         workspace_bytes < amc3d_local_aggregation_workspace_bytes(b, cout, n, npoints))) ||
         (running_mean && (!running_var || !num_batches_tracked)))
-        return bad_arg("amc3d_local_aggregation_forward: unsupported shape, null or misaligned pointer or workspace too small");
-    hipStream_t stream = (hipStream_t)stream_;
+        return lagg_bad(entry, "unsupported shape, null or misaligned pointer or workspace too small");
     LaggMoments gm{};
     if (moments) gm = lagg_views(moments, b, n);
-    // the entries that take G channel-major: its rows first (phase 2 finds them where phase 1 left them)
-    if (!rows && !(training && phase == 2))
+    // G channel-major: its rows first (phase 2 finds them where phase 1 left them)
+    if (g_cm && !(training && phase == 2))
         if (int st = amc3d_transpose_cn(b, cout, n, g_cm, g_pm, stream_)) return st;
     if (training) {
         if (int st = lagg_statistics(b, cout, n, npoints, nsample, eps, momentum, g_pm, gm, w_dp, mean, invstd, var_unbiased, gd,
-                                     running_mean, running_var, num_batches_tracked, phase, sums, (double *)workspace, stream))
+                                     running_mean, running_var, num_batches_tracked, phase, sums, (double *)workspace,
+                                     (hipStream_t)stream_))
             return st;
-        if (phase == 1) return launch_status("amc3d_local_aggregation_forward");
+        if (phase == 1) return launch_status(entry);
     }
+    *done = false;
+    return 0;
+}
+
+// The checks both layers' backwards share; dy is the incoming gradient, need_bytes the workspace of the form that runs.
+// *done: an empty batch, nothing to launch
+static int lagg_backward_begin(const char *entry, bool (*supported)(int, int), int b, int cout, int n, int npoints, int nsample,
+                               const float *dy, const float *g_pm, const float *dp, WDp w_dp, const void *moments,
+                               const double *gd, const float *mean, const float *invstd, const float *gamma, const float *beta,
+                               const float *dg_cm, const float *dw_dp, long lddw, const float *dgamma, const float *dbeta,
+                               int phase, const double *dsums, const double *count_dev, const void *workspace,
+                               size_t workspace_bytes, size_t need_bytes, bool *done)
+{
+    *done = true;
+    if (w_dp.ld < 3 || lddw < 3) return lagg_bad(entry, "row stride below 3");
+    if (b <= 0 || npoints <= 0) return 0;
+    if (phase != 0 && (!dsums || (phase == 2 && !count_dev))) return lagg_bad(entry, "phase 1 / 2 need dsums (and the count)");
+    if (!supported(cout, nsample) || n <= 0 || !dy || !g_pm || !dp || !w_dp || !moments || !gd || !mean || !invstd || !gamma ||
+        !beta || !dg_cm || !dw_dp || !dgamma || !dbeta || !workspace || (((uintptr_t)workspace | (uintptr_t)g_pm) & 15) ||
+        workspace_bytes < need_bytes)
+        return lagg_bad(entry, "unsupported shape, null pointer or workspace too small");
+    *done = false;
+    return 0;
+}
+
+// The end of both layers' backwards, from what the first stage left: `nparts` partial records per channel and Q (b,n,cout).
+// BatchNorm's coefficients and dw_dp (cout,3 at lddw), dgamma, dbeta (cout); phase 1 ends there, with this rank's dsums.  Then
+// dg_cm (b,cout,n), the gradient w.r.t. G = W_f . f (the caller runs the pointwise conv's backward on it)
+static int lagg_backward_finish(const char *entry, int b, int cout, int n, int npoints, int nsample, int nparts,
+                                double *partial, const float *Q, float *coef, const float *g_pm, const void *moments,
+                                const double *gd, WDp w_dp, const float *mean, const float *invstd, const float *gamma,
+                                float *dg_cm, float *dw_dp, long lddw, float *dgamma, float *dbeta, int phase, double *dsums,
+                                const double *count_dev, hipStream_t stream)
+{
+    const LaggMoments gm = lagg_views(moments, b, n);
+    hipLaunchKernelGGL(lagg_bwd_finalize_kernel, dim3(cout), dim3(LAGG_FT), 0, stream, cout, nparts,
+                       (double)b * (double)npoints * (double)nsample, partial, gm.mom, gd, w_dp, mean, invstd,
+                       gamma, dgamma, dbeta, dw_dp, lddw, coef, phase, dsums, count_dev);
+    if (phase == 1) return launch_status(entry);
+    lagg_apply(b, cout, n, Q, g_pm, gm, w_dp, coef, dg_cm, stream);
+    return launch_status(entry);
+}
+
+// Outputs besides those of lagg_forward_begin: pooled / ystar (b,cout,npoints) fp32, arg (b,cout,npoints) bytes
+AMC_API int amc3d_local_aggregation_forward(int b, int cout, int n, int npoints, int nsample, int training, int relu, float eps,
+                                            float momentum, const float *g_cm, const int *idx, const float *dp,
+                                            const float *w_dp_, long ldw, const void *moments, const float *gamma,
+                                            const float *beta, float *g_pm, float *pooled, unsigned char *arg, float *ystar,
+                                            float *mean, float *invstd, float *var_unbiased, double *gd, float *running_mean,
+                                            float *running_var, long long *num_batches_tracked, int phase, double *sums,
+                                            void *workspace, size_t workspace_bytes, void *stream_)
+{
+    const char *entry = "amc3d_local_aggregation_forward";
+    const WDp w_dp{w_dp_, ldw};
+    if (b > 0 && npoints > 0 && (!pooled || !arg || !ystar)) return lagg_bad(entry, "null output");
+    bool done;
+    if (int st = lagg_forward_begin(entry, lagg_supported, b, cout, n, npoints, nsample, training, eps, momentum, g_cm, idx, dp, w_dp,
+                                    moments, gamma, beta, g_pm, mean, invstd, var_unbiased, gd, running_mean, running_var,
+                                    num_batches_tracked, phase, sums, workspace, workspace_bytes, stream_, &done))
+        return st;
+    if (done) return 0;
+    hipStream_t stream = (hipStream_t)stream_;
     const int ct = cout < LAGG_CT ? cout : LAGG_CT;
     const int cpw = lagg_pool_cpw(b, cout, npoints);
     const size_t lds = (size_t)3 * ct * (4 * cpw + 1) * sizeof(float);
@@ -1005,80 +1072,33 @@ static int local_aggregation_forward_impl(int b, int cout, int n, int npoints, i
     switch (ct / 4) { case 2: AMC_POOL(2); break; case 4: AMC_POOL(4); break; case 8: AMC_POOL(8); break; case 16: AMC_POOL(16); break;
                       default: AMC_POOL(32); }
 #undef AMC_POOL
-    return launch_status("amc3d_local_aggregation_forward");
+    return launch_status(entry);
 }
 
-AMC_API int amc3d_local_aggregation_forward(int b, int cout, int n, int npoints, int nsample, int training, int relu, float eps,
-                                            float momentum, const float *g_cm, const int *idx, const float *dp,
-                                            const float *w_dp, const void *moments, const float *gamma, const float *beta,
-                                            float *g_pm, float *pooled, unsigned char *arg, float *ystar, float *mean,
-                                            float *invstd, float *var_unbiased, double *gd, float *running_mean,
-                                            float *running_var, long long *num_batches_tracked, int phase, double *sums,
-                                            void *workspace, size_t workspace_bytes, void *stream_)
+// Q by float atomics (rev_start == NULL), or from the reverse lists of idx (amc3d_group_csr): bit-reproducible.  Summation
+// order of Q: see lagg_bwd_gather_kernel and include/amc3d.h
+AMC_API int amc3d_local_aggregation_backward(int b, int cout, int n, int npoints, int nsample, int relu, const float *dpooled,
+                                             const float *ystar, const unsigned char *arg, const float *g_pm, const int *idx,
+                                             const float *dp, const float *w_dp_, long ldw, const void *moments,
+                                             const double *gd, const float *mean, const float *invstd, const float *gamma,
+                                             const float *beta, const int *rev_start, const int *rev_edge, float *dg_cm,
+                                             float *dw_dp, long lddw, float *dgamma, float *dbeta, int phase, double *dsums,
+                                             const double *count_dev, void *workspace, size_t workspace_bytes, void *stream_)
 {
-    return local_aggregation_forward_impl(b, cout, n, npoints, nsample, training, relu, eps, momentum, g_cm, false, idx, dp, WDp{w_dp, 3}, moments, gamma,
-        beta, g_pm, pooled, arg, ystar, mean, invstd, var_unbiased, gd, running_mean, running_var,
-        num_batches_tracked, phase, sums, workspace, workspace_bytes, stream_);
-}
-
-// the same with w_dp addressed at a row stride (floats): the dp columns inside the layer's own (cout, cin + 3) weight
-AMC_API int amc3d_local_aggregation_forward_strided(int b, int cout, int n, int npoints, int nsample,
-                                                    int training, int relu, float eps, float momentum,
-                                                    const float *g_cm, const int *idx, const float *dp,
-                                                    const float *w_dp, long ldw, const void *moments,
-                                                    const float *gamma, const float *beta, float *g_pm,
-                                                    float *pooled, unsigned char *arg, float *ystar, float *mean,
-                                                    float *invstd, float *var_unbiased, double *gd,
-                                                    float *running_mean, float *running_var,
-                                                    long long *num_batches_tracked, int phase, double *sums,
-                                                    void *workspace, size_t workspace_bytes, void *stream_)
-{
-    if (ldw < 3) return bad_arg("amc3d_local_aggregation_forward_strided: row stride below 3");
-    return local_aggregation_forward_impl(b, cout, n, npoints, nsample, training, relu, eps, momentum, g_cm, false, idx, dp, WDp{w_dp, ldw}, moments,
-        gamma, beta, g_pm, pooled, arg, ystar, mean, invstd, var_unbiased, gd, running_mean, running_var,
-        num_batches_tracked, phase, sums, workspace, workspace_bytes, stream_);
-}
-
-// the strided form with G handed over as rows: g_pm (b,n,cout), 16-byte aligned, is an INPUT (amc3d_pointwise_conv_forward_rows
-// writes it) and there is no channel-major G.  training == 0 launches the max-pool alone.
-AMC_API int amc3d_local_aggregation_forward_rows(int b, int cout, int n, int npoints, int nsample, int training, int relu,
-                                                 float eps, float momentum, const float *g_pm, const int *idx, const float *dp,
-                                                 const float *w_dp, long ldw, const void *moments, const float *gamma,
-                                                 const float *beta, float *pooled, unsigned char *arg, float *ystar, float *mean,
-                                                 float *invstd, float *var_unbiased, double *gd, float *running_mean,
-                                                 float *running_var, long long *num_batches_tracked, int phase, double *sums,
-                                                 void *workspace, size_t workspace_bytes, void *stream_)
-{
-    if (ldw < 3) return bad_arg("amc3d_local_aggregation_forward_rows: row stride below 3");
-    return local_aggregation_forward_impl(b, cout, n, npoints, nsample, training, relu, eps, momentum, nullptr, true, idx, dp,
-        WDp{w_dp, ldw}, moments, gamma, beta, const_cast<float *>(g_pm), pooled, arg, ystar, mean, invstd, var_unbiased, gd,
-        running_mean, running_var, num_batches_tracked, phase, sums, workspace, workspace_bytes, stream_);
-}
-
-// dg_cm (b,cout,n): gradient w.r.t. G = W_f . f (the caller runs the pointwise conv's backward on it);
-// dw_dp (cout,3), dgamma, dbeta (cout)
-static int local_aggregation_backward_impl(int b, int cout, int n, int npoints, int nsample, int relu,
-                                               const float *dpooled, const float *ystar, const unsigned char *arg,
-                                               const float *g_pm, const int *idx, const float *dp, WDp w_dp,
-                                               const void *moments, const double *gd, const float *mean,
-                                               const float *invstd, const float *gamma, const float *beta,
-                                               float *dg_cm, float *dw_dp, long lddw, float *dgamma, float *dbeta,
-                                               int phase, double *dsums, const double *count_dev, void *workspace,
-                                               size_t workspace_bytes, void *stream_, const int *rev_start = nullptr,
-                                               const int *rev_edge = nullptr)
-
-{
-    if (b <= 0 || npoints <= 0) return 0;
+    const char *entry = "amc3d_local_aggregation_backward";
+    const WDp w_dp{w_dp_, ldw};
     const bool lists = rev_start != nullptr;
-    if (phase != 0 && (!dsums || (phase == 2 && !count_dev))) return bad_arg("amc3d_local_aggregation_backward: phase 1 / 2 need dsums (and the count)");
-    if (!lagg_supported(cout, nsample) || n <= 0 || !dpooled || !ystar || !arg || !g_pm || !idx || !dp || !w_dp || !moments || !gd ||
-        !mean || !invstd || !gamma || !beta || !dg_cm || !dw_dp || !dgamma || !dbeta || !workspace || (((uintptr_t)workspace | (uintptr_t)g_pm) & 15) || (lists && !rev_edge) ||
-        workspace_bytes < (lists ? amc3d_local_aggregation_csr_workspace_bytes(b, cout, n, npoints)
-                                 : amc3d_local_aggregation_workspace_bytes(b, cout, n, npoints)) ||
-        (lists && ((long)b * n * cout >= (1L << 39) || (long)npoints * nsample >= (1L << 31))))
-        return bad_arg("amc3d_local_aggregation_backward: unsupported shape, null pointer or workspace too small");
+    bool done;
+    if (int st = lagg_backward_begin(entry, lagg_supported, b, cout, n, npoints, nsample, dpooled, g_pm, dp, w_dp, moments, gd, mean,
+                                     invstd, gamma, beta, dg_cm, dw_dp, lddw, dgamma, dbeta, phase, dsums, count_dev, workspace,
+                                     workspace_bytes,
+                                     lists ? amc3d_local_aggregation_csr_workspace_bytes(b, cout, n, npoints)
+                                           : amc3d_local_aggregation_workspace_bytes(b, cout, n, npoints), &done))
+        return st;
+    if (done) return 0;
+    if (!ystar || !arg || !idx || (lists && (!rev_edge || (long)b * n * cout >= (1L << 39) || (long)npoints * nsample >= (1L << 31))))
+        return lagg_bad(entry, "null pointer, or a shape beyond the reverse-list form");
     hipStream_t stream = (hipStream_t)stream_;
-    const LaggMoments gm = lagg_views(moments, b, n);
     double *partial = (double *)workspace;
     float *Q = (float *)((char *)workspace + lagg_partial_bytes(b, cout, n, npoints));
     float *coef = Q + (size_t)b * n * cout;
@@ -1109,112 +1129,31 @@ static int local_aggregation_backward_impl(int b, int cout, int n, int npoints, 
                                (float *)nullptr, (unsigned char *)nullptr);
         }
     }
-    hipLaunchKernelGGL(lagg_bwd_finalize_kernel, dim3(cout), dim3(LAGG_FT), 0, stream, cout, nparts_b * b,
-                       (double)b * (double)npoints * (double)nsample, partial, gm.mom, gd, w_dp, mean, invstd,
-                       gamma, dgamma, dbeta, dw_dp, lddw, coef, phase, dsums, count_dev);
-    if (phase == 1) return launch_status("amc3d_local_aggregation_backward");
-    lagg_apply(b, cout, n, Q, g_pm, gm, w_dp, coef, dg_cm, stream);
-    return launch_status("amc3d_local_aggregation_backward");
-}
-
-AMC_API int amc3d_local_aggregation_backward(int b, int cout, int n, int npoints, int nsample, int relu, const float *dpooled,
-                                             const float *ystar, const unsigned char *arg, const float *g_pm, const int *idx,
-                                             const float *dp, const float *w_dp, const void *moments, const double *gd,
-                                             const float *mean, const float *invstd, const float *gamma, const float *beta,
-                                             float *dg_cm, float *dw_dp, float *dgamma, float *dbeta, int phase, double *dsums,
-                                             const double *count_dev, void *workspace, size_t workspace_bytes, void *stream_)
-{
-    return local_aggregation_backward_impl(b, cout, n, npoints, nsample, relu, dpooled, ystar, arg, g_pm, idx, dp, WDp{w_dp, 3}, moments, gd, mean,
-        invstd, gamma, beta, dg_cm, dw_dp, 3, dgamma, dbeta, phase, dsums, count_dev, workspace, workspace_bytes,
-        stream_);
-}
-
-// the same with w_dp and dw_dp addressed at a row stride (floats): the dp columns inside the layer's own (cout, cin + 3) weight and its gradient
-AMC_API int amc3d_local_aggregation_backward_strided(int b, int cout, int n, int npoints, int nsample, int relu,
-                                                     const float *dpooled, const float *ystar,
-                                                     const unsigned char *arg, const float *g_pm, const int *idx,
-                                                     const float *dp, const float *w_dp, long ldw,
-                                                     const void *moments, const double *gd, const float *mean,
-                                                     const float *invstd, const float *gamma, const float *beta,
-                                                     float *dg_cm, float *dw_dp, long lddw, float *dgamma,
-                                                     float *dbeta, int phase, double *dsums,
-                                                     const double *count_dev, void *workspace,
-                                                     size_t workspace_bytes, void *stream_)
-{
-    if (ldw < 3 || lddw < 3) return bad_arg("amc3d_local_aggregation_backward_strided: row stride below 3");
-    return local_aggregation_backward_impl(b, cout, n, npoints, nsample, relu, dpooled, ystar, arg, g_pm, idx, dp, WDp{w_dp, ldw}, moments, gd, mean,
-        invstd, gamma, beta, dg_cm, dw_dp, lddw, dgamma, dbeta, phase, dsums, count_dev, workspace,
-        workspace_bytes, stream_);
-}
-
-// The same backward with Q formed from the reverse lists of idx (amc3d_group_csr) instead of float atomics: bit-reproducible.
-// Summation order of Q: see lagg_bwd_gather_kernel and include/amc3d.h.  Workspace: amc3d_local_aggregation_csr_workspace_bytes.
-AMC_API int amc3d_local_aggregation_backward_csr(int b, int cout, int n, int npoints, int nsample, int relu, const float *dpooled,
-                                                 const float *ystar, const unsigned char *arg, const float *g_pm, const int *idx,
-                                                 const float *dp, const float *w_dp, const void *moments, const double *gd,
-                                                 const float *mean, const float *invstd, const float *gamma, const float *beta,
-                                                 const int *rev_start, const int *rev_edge, float *dg_cm, float *dw_dp,
-                                                 float *dgamma, float *dbeta, int phase, double *dsums, const double *count_dev,
-                                                 void *workspace, size_t workspace_bytes, void *stream_)
-{
-    if (!rev_start || !rev_edge) return bad_arg("amc3d_local_aggregation_backward_csr: null reverse lists");
-    return local_aggregation_backward_impl(b, cout, n, npoints, nsample, relu, dpooled, ystar, arg, g_pm, idx, dp, WDp{w_dp, 3}, moments, gd, mean,
-        invstd, gamma, beta, dg_cm, dw_dp, 3, dgamma, dbeta, phase, dsums, count_dev, workspace, workspace_bytes,
-        stream_, rev_start, rev_edge);
-}
-
-AMC_API int amc3d_local_aggregation_backward_csr_strided(int b, int cout, int n, int npoints, int nsample, int relu,
-                                                         const float *dpooled, const float *ystar,
-                                                         const unsigned char *arg, const float *g_pm, const int *idx,
-                                                         const float *dp, const float *w_dp, long ldw,
-                                                         const void *moments, const double *gd, const float *mean,
-                                                         const float *invstd, const float *gamma, const float *beta,
-                                                         const int *rev_start, const int *rev_edge,
-                                                         float *dg_cm, float *dw_dp, long lddw, float *dgamma,
-                                                         float *dbeta, int phase, double *dsums,
-                                                         const double *count_dev, void *workspace,
-                                                         size_t workspace_bytes, void *stream_)
-{
-    if (ldw < 3 || lddw < 3) return bad_arg("amc3d_local_aggregation_backward_csr_strided: row stride below 3");
-    if (!rev_start || !rev_edge) return bad_arg("amc3d_local_aggregation_backward_csr_strided: null reverse lists");
-    return local_aggregation_backward_impl(b, cout, n, npoints, nsample, relu, dpooled, ystar, arg, g_pm, idx, dp, WDp{w_dp, ldw}, moments, gd, mean,
-        invstd, gamma, beta, dg_cm, dw_dp, lddw, dgamma, dbeta, phase, dsums, count_dev, workspace,
-        workspace_bytes, stream_, rev_start, rev_edge);
+    return lagg_backward_finish(entry, b, cout, n, npoints, nsample, nparts_b * b, partial, Q, coef, g_pm, moments, gd, w_dp, mean,
+                                invstd, gamma, dg_cm, dw_dp, lddw, dgamma, dbeta, phase, dsums, count_dev, stream);
 }
 
 // ---- first layer of a multi-layer SetAbstraction MLP: conv (before the gather) + BatchNorm + ReLU, x1 materialised ----
 AMC_API int amc3d_grouped_conv_bn_supported(int cout, int nsample) { return lagg_expand_supported(cout, nsample) ? 1 : 0; }
 
 // x1 (b,cout,npoints,32) = [relu](bn(G[idx] + W_dp . dp)); other arguments as amc3d_local_aggregation_forward
-static int grouped_conv_bn_forward_impl(int b, int cout, int n, int npoints, int nsample, int training,
-                                            int relu, float eps, float momentum, const float *g_cm, bool rows,
-                                            const int *idx, const float *dp, WDp w_dp, const void *moments,
-                                            const float *gamma, const float *beta, float *g_pm, float *x1,
-                                            float *mean, float *invstd, float *var_unbiased, double *gd,
-                                            float *running_mean, float *running_var,
-                                            long long *num_batches_tracked, int phase, double *sums,
-                                            void *workspace, size_t workspace_bytes, void *stream_)
-
+AMC_API int amc3d_grouped_conv_bn_forward(int b, int cout, int n, int npoints, int nsample, int training, int relu, float eps,
+                                          float momentum, const float *g_cm, const int *idx, const float *dp, const float *w_dp_,
+                                          long ldw, const void *moments, const float *gamma, const float *beta, float *g_pm,
+                                          float *x1, float *mean, float *invstd, float *var_unbiased, double *gd,
+                                          float *running_mean, float *running_var, long long *num_batches_tracked, int phase,
+                                          double *sums, void *workspace, size_t workspace_bytes, void *stream_)
 {
-    if (training && phase != 0 && !sums) return bad_arg("amc3d_grouped_conv_bn_forward: phase 1 / 2 need the sums buffer");
-    if (b <= 0 || npoints <= 0) return 0;
-    if (!lagg_expand_supported(cout, nsample) || n <= 0 || (!rows && !g_cm) || !idx || !dp || !w_dp || !gamma || !beta || !g_pm ||
-        ((uintptr_t)g_pm & 15) || !x1 || !mean || !invstd || (training && (!moments || !var_unbiased || !gd || !workspace ||
-        workspace_bytes < amc3d_local_aggregation_workspace_bytes(b, cout, n, npoints))) ||
-        (running_mean && (!running_var || !num_batches_tracked)))
-        return bad_arg("amc3d_grouped_conv_bn_forward: unsupported shape, null or misaligned pointer or workspace too small");
+    const char *entry = "amc3d_grouped_conv_bn_forward";
+    const WDp w_dp{w_dp_, ldw};
+    if (b > 0 && npoints > 0 && !x1) return lagg_bad(entry, "null output");
+    bool done;
+    if (int st = lagg_forward_begin(entry, lagg_expand_supported, b, cout, n, npoints, nsample, training, eps, momentum, g_cm, idx, dp,
+                                    w_dp, moments, gamma, beta, g_pm, mean, invstd, var_unbiased, gd, running_mean, running_var,
+                                    num_batches_tracked, phase, sums, workspace, workspace_bytes, stream_, &done))
+        return st;
+    if (done) return 0;
     hipStream_t stream = (hipStream_t)stream_;
-    LaggMoments gm{};
-    if (moments) gm = lagg_views(moments, b, n);
-    // the entries that take G channel-major: its rows first (phase 2 finds them where phase 1 left them)
-    if (!rows && !(training && phase == 2))
-        if (int st = amc3d_transpose_cn(b, cout, n, g_cm, g_pm, stream_)) return st;
-    if (training) {
-        if (int st = lagg_statistics(b, cout, n, npoints, nsample, eps, momentum, g_pm, gm, w_dp, mean, invstd, var_unbiased, gd,
-                                     running_mean, running_var, num_batches_tracked, phase, sums, (double *)workspace, stream))
-            return st;
-        if (phase == 1) return launch_status("amc3d_grouped_conv_bn_forward");
-    }
     const long P = (long)npoints * nsample;
     const int ct = cout < LAGG_XC ? cout : LAGG_XC;
 #define AMC_EXPAND(L)                                                                                                          \
@@ -1222,125 +1161,9 @@ static int grouped_conv_bn_forward_impl(int b, int cout, int n, int npoints, int
                        (const float *)g_pm, idx, dp, w_dp, (const float *)mean, (const float *)invstd, gamma, beta, x1)
     switch (ct / 4) { case 2: AMC_EXPAND(2); break; case 4: AMC_EXPAND(4); break; case 8: AMC_EXPAND(8); break; default: AMC_EXPAND(16); }
 #undef AMC_EXPAND
-    return launch_status("amc3d_grouped_conv_bn_forward");
+    return launch_status(entry);
 }
 
-AMC_API int amc3d_grouped_conv_bn_forward(int b, int cout, int n, int npoints, int nsample, int training, int relu, float eps,
-                                          float momentum, const float *g_cm, const int *idx, const float *dp, const float *w_dp,
-                                          const void *moments, const float *gamma, const float *beta, float *g_pm, float *x1,
-                                          float *mean, float *invstd, float *var_unbiased, double *gd, float *running_mean,
-                                          float *running_var, long long *num_batches_tracked, int phase, double *sums,
-                                          void *workspace, size_t workspace_bytes, void *stream_)
-{
-    return grouped_conv_bn_forward_impl(b, cout, n, npoints, nsample, training, relu, eps, momentum, g_cm, false, idx, dp, WDp{w_dp, 3}, moments, gamma,
-        beta, g_pm, x1, mean, invstd, var_unbiased, gd, running_mean, running_var, num_batches_tracked, phase,
-        sums, workspace, workspace_bytes, stream_);
-}
-
-// the same with w_dp addressed at a row stride (floats): the dp columns inside the layer's own (cout, cin + 3) weight
-AMC_API int amc3d_grouped_conv_bn_forward_strided(int b, int cout, int n, int npoints, int nsample, int training,
-                                                  int relu, float eps, float momentum, const float *g_cm,
-                                                  const int *idx, const float *dp, const float *w_dp, long ldw,
-                                                  const void *moments, const float *gamma, const float *beta,
-                                                  float *g_pm, float *x1, float *mean, float *invstd,
-                                                  float *var_unbiased, double *gd, float *running_mean,
-                                                  float *running_var, long long *num_batches_tracked, int phase,
-                                                  double *sums, void *workspace, size_t workspace_bytes,
-                                                  void *stream_)
-{
-    if (ldw < 3) return bad_arg("amc3d_grouped_conv_bn_forward_strided: row stride below 3");
-    return grouped_conv_bn_forward_impl(b, cout, n, npoints, nsample, training, relu, eps, momentum, g_cm, false, idx, dp, WDp{w_dp, ldw}, moments,
-        gamma, beta, g_pm, x1, mean, invstd, var_unbiased, gd, running_mean, running_var, num_batches_tracked,
-        phase, sums, workspace, workspace_bytes, stream_);
-}
-
-// the strided form with G handed over as rows: g_pm (b,n,cout), 16-byte aligned, is an INPUT and there is no channel-major G.
-// training == 0 launches the expand kernel alone.
-AMC_API int amc3d_grouped_conv_bn_forward_rows(int b, int cout, int n, int npoints, int nsample, int training, int relu,
-                                               float eps, float momentum, const float *g_pm, const int *idx, const float *dp,
-                                               const float *w_dp, long ldw, const void *moments, const float *gamma,
-                                               const float *beta, float *x1, float *mean, float *invstd, float *var_unbiased,
-                                               double *gd, float *running_mean, float *running_var,
-                                               long long *num_batches_tracked, int phase, double *sums, void *workspace,
-                                               size_t workspace_bytes, void *stream_)
-{
-    if (ldw < 3) return bad_arg("amc3d_grouped_conv_bn_forward_rows: row stride below 3");
-    return grouped_conv_bn_forward_impl(b, cout, n, npoints, nsample, training, relu, eps, momentum, nullptr, true, idx, dp,
-        WDp{w_dp, ldw}, moments, gamma, beta, const_cast<float *>(g_pm), x1, mean, invstd, var_unbiased, gd, running_mean,
-        running_var, num_batches_tracked, phase, sums, workspace, workspace_bytes, stream_);
-}
-
-// from dx1 (b,cout,npoints,32): dg_cm (b,cout,n), dw_dp (cout,3), dgamma, dbeta
-static int grouped_conv_bn_backward_impl(int b, int cout, int n, int npoints, int nsample, int relu,
-                                             const float *dx1, const float *g_pm, const int *idx, const float *dp,
-                                             WDp w_dp, const void *moments, const double *gd, const float *mean,
-                                             const float *invstd, const float *gamma, const float *beta,
-                                             float *dg_cm, float *dw_dp, long lddw, float *dgamma, float *dbeta,
-                                             int phase, double *dsums, const double *count_dev, void *workspace,
-                                             size_t workspace_bytes, void *stream_)
-
-{
-    if (b <= 0 || npoints <= 0) return 0;
-    if (phase != 0 && (!dsums || (phase == 2 && !count_dev))) return bad_arg("amc3d_grouped_conv_bn_backward: phase 1 / 2 need dsums (and the count)");
-    if (!lagg_expand_supported(cout, nsample) || n <= 0 || !dx1 || !g_pm || !idx || !dp || !w_dp || !moments || !gd || !mean ||
-        !invstd || !gamma || !beta || !dg_cm || !dw_dp || !dgamma || !dbeta || !workspace || (((uintptr_t)workspace | (uintptr_t)g_pm) & 15) ||
-        workspace_bytes < amc3d_local_aggregation_workspace_bytes(b, cout, n, npoints))
-        return bad_arg("amc3d_grouped_conv_bn_backward: unsupported shape, null pointer or workspace too small");
-    hipStream_t stream = (hipStream_t)stream_;
-    const LaggMoments gm = lagg_views(moments, b, n);
-    double *partial = (double *)workspace;
-    float *Q = (float *)((char *)workspace + lagg_partial_bytes(b, cout, n, npoints));
-    float *coef = Q + (size_t)b * n * cout;
-    const long P = (long)npoints * nsample;
-    const int ct = cout < LAGG_XC ? cout : LAGG_XC;
-    const int ctiles = LAGG_CTILES;
-    const int nparts_b = div_up(div_up(P, LAGG_PT), ctiles);
-    if (phase != 2) {
-    if (int st = fill_i32((int *)Q, 0, (size_t)b * n * cout, stream)) return st;
-#define AMC_COLLAPSE(L)                                                                                                        \
-    hipLaunchKernelGGL(lagg_collapse_kernel<L>, dim3(nparts_b, cout / ct, b), dim3(256), 0, stream, cout, n, P, relu, dx1, g_pm,  \
-                       idx, dp, w_dp, mean, invstd, gamma, beta, Q, partial, nparts_b, ctiles)
-    switch (ct / 4) { case 2: AMC_COLLAPSE(2); break; case 4: AMC_COLLAPSE(4); break; case 8: AMC_COLLAPSE(8); break; default: AMC_COLLAPSE(16); }
-#undef AMC_COLLAPSE
-    }
-    hipLaunchKernelGGL(lagg_bwd_finalize_kernel, dim3(cout), dim3(LAGG_FT), 0, stream, cout, nparts_b * b,
-                       (double)b * (double)npoints * (double)nsample, partial, gm.mom, gd, w_dp, mean, invstd,
-                       gamma, dgamma, dbeta, dw_dp, lddw, coef, phase, dsums, count_dev);
-    if (phase == 1) return launch_status("amc3d_grouped_conv_bn_backward");
-    lagg_apply(b, cout, n, Q, g_pm, gm, w_dp, coef, dg_cm, stream);
-    return launch_status("amc3d_grouped_conv_bn_backward");
-}
-
-AMC_API int amc3d_grouped_conv_bn_backward(int b, int cout, int n, int npoints, int nsample, int relu, const float *dx1,
-                                           const float *g_pm, const int *idx, const float *dp, const float *w_dp,
-                                           const void *moments, const double *gd, const float *mean, const float *invstd,
-                                           const float *gamma, const float *beta, float *dg_cm, float *dw_dp, float *dgamma,
-                                           float *dbeta, int phase, double *dsums, const double *count_dev, void *workspace,
-                                           size_t workspace_bytes, void *stream_)
-{
-    return grouped_conv_bn_backward_impl(b, cout, n, npoints, nsample, relu, dx1, g_pm, idx, dp, WDp{w_dp, 3}, moments, gd, mean, invstd, gamma,
-        beta, dg_cm, dw_dp, 3, dgamma, dbeta, phase, dsums, count_dev, workspace, workspace_bytes, stream_);
-}
-
-// the same with w_dp and dw_dp addressed at a row stride (floats): the dp columns inside the layer's own (cout, cin + 3) weight and its gradient
-AMC_API int amc3d_grouped_conv_bn_backward_strided(int b, int cout, int n, int npoints, int nsample, int relu,
-                                                   const float *dx1, const float *g_pm, const int *idx,
-                                                   const float *dp, const float *w_dp, long ldw,
-                                                   const void *moments, const double *gd, const float *mean,
-                                                   const float *invstd, const float *gamma, const float *beta,
-                                                   float *dg_cm, float *dw_dp, long lddw, float *dgamma,
-                                                   float *dbeta, int phase, double *dsums,
-                                                   const double *count_dev, void *workspace,
-                                                   size_t workspace_bytes, void *stream_)
-{
-    if (ldw < 3 || lddw < 3) return bad_arg("amc3d_grouped_conv_bn_backward_strided: row stride below 3");
-    return grouped_conv_bn_backward_impl(b, cout, n, npoints, nsample, relu, dx1, g_pm, idx, dp, WDp{w_dp, ldw}, moments, gd, mean, invstd, gamma,
-        beta, dg_cm, dw_dp, lddw, dgamma, dbeta, phase, dsums, count_dev, workspace, workspace_bytes, stream_);
-}
-
-// the same backward without float atomics: rev_start / rev_edge are the reverse lists of amc3d_group_csr; dx1 is first
-// transposed to position-major (workspace), then every source point sums its incoming positions in list order
-// (csrc/csr.hip): deterministic, and ~2.5x faster than the atomic scatter.  workspace: amc3d_grouped_conv_bn_csr_workspace_bytes
 namespace amc {
 int csr_collapse(int b, int cout, int n, int npoints, int nsample, int relu, const float *dx1_pm, const float *g_pm,
                  const int *rev_start, const int *rev_edge, const float *rev_dp, const float *dp, WDp w_dp,
@@ -1358,80 +1181,68 @@ AMC_API size_t amc3d_grouped_conv_bn_csr_workspace_bytes(int b, int cout, int n,
            (size_t)b * npoints * nsample * cout * sizeof(float);
 }
 
-static int grouped_conv_bn_backward_csr_impl(int b, int cout, int n, int npoints, int nsample, int relu,
-                                                 const float *dx1, int dx1_position_major, const float *g_pm,
-                                                 const int *rev_start, const int *rev_edge, const float *rev_dp,
-                                                 const float *dp, WDp w_dp, const void *moments, const double *gd,
-                                                 const float *mean, const float *invstd, const float *gamma,
-                                                 const float *beta, float *dg_cm, float *dw_dp, long lddw,
-                                                 float *dgamma, float *dbeta, int phase, double *dsums,
-                                                 const double *count_dev, void *workspace, size_t workspace_bytes,
-                                                 void *stream_)
-
+// from dx1 (b,cout,npoints,32): dg_cm (b,cout,n), dw_dp (cout,3), dgamma, dbeta.  rev_start == NULL: one pass over dx1 collapses
+// it into Q with float atomics.  With the reverse lists rev_start / rev_edge of amc3d_group_csr there are none: dx1 is first
+// transposed to position-major (workspace) unless it comes that way, then every source point sums its incoming positions in
+// list order (csrc/csr.hip): deterministic, and ~2.5x faster than the atomic scatter
+AMC_API int amc3d_grouped_conv_bn_backward(int b, int cout, int n, int npoints, int nsample, int relu, const float *dx1,
+                                           int dx1_position_major, const float *g_pm, const int *idx, const int *rev_start,
+                                           const int *rev_edge, const float *rev_dp, const float *dp, const float *w_dp_,
+                                           long ldw, const void *moments, const double *gd, const float *mean,
+                                           const float *invstd, const float *gamma, const float *beta, float *dg_cm,
+                                           float *dw_dp, long lddw, float *dgamma, float *dbeta, int phase, double *dsums,
+                                           const double *count_dev, void *workspace, size_t workspace_bytes, void *stream_)
 {
-    if (b <= 0 || npoints <= 0) return 0;
-    if (phase != 0 && (!dsums || (phase == 2 && !count_dev))) return bad_arg("amc3d_grouped_conv_bn_backward_csr: phase 1 / 2 need dsums (and the count)");
-    if (!lagg_expand_supported(cout, nsample) || n <= 0 || !dx1 || !g_pm || !rev_start || !rev_edge || !dp || !w_dp || !moments ||
-        !gd || !mean || !invstd || !gamma || !beta || !dg_cm || !dw_dp || !dgamma || !dbeta || !workspace || (((uintptr_t)workspace | (uintptr_t)g_pm) & 15) ||
-        workspace_bytes < amc3d_grouped_conv_bn_csr_workspace_bytes(b, cout, n, npoints, nsample))
-        return bad_arg("amc3d_grouped_conv_bn_backward_csr: unsupported shape, null pointer or workspace too small");
+    const char *entry = "amc3d_grouped_conv_bn_backward";
+    const WDp w_dp{w_dp_, ldw};
+    const bool lists = rev_start != nullptr;
+    bool done;
+    if (int st = lagg_backward_begin(entry, lagg_expand_supported, b, cout, n, npoints, nsample, dx1, g_pm, dp, w_dp, moments, gd,
+                                     mean, invstd, gamma, beta, dg_cm, dw_dp, lddw, dgamma, dbeta, phase, dsums, count_dev,
+                                     workspace, workspace_bytes,
+                                     lists ? amc3d_grouped_conv_bn_csr_workspace_bytes(b, cout, n, npoints, nsample)
+                                           : amc3d_local_aggregation_workspace_bytes(b, cout, n, npoints), &done))
+        return st;
+    if (done) return 0;
+    if (lists ? !rev_edge : (!idx || dx1_position_major || rev_dp))
+        return lagg_bad(entry, "lists need rev_edge; without them idx, a channel-major dx1 and no rev_dp");
     hipStream_t stream = (hipStream_t)stream_;
-    const LaggMoments gm = lagg_views(moments, b, n);
-    const size_t parts = csr_partials(b, cout, n);
+    const long P = (long)npoints * nsample;
+    const size_t parts = lists ? csr_partials(b, cout, n) : 0;
     char *w = (char *)workspace;
-    double *partial = (double *)w; w += parts * cout * 5 * sizeof(double);
+    double *partial = (double *)w; w += lists ? parts * cout * 5 * sizeof(double) : lagg_partial_bytes(b, cout, n, npoints);
     float *Q = (float *)w; w += (size_t)b * n * cout * sizeof(float);
     float *coef = (float *)w; w += (size_t)cout * 4 * sizeof(float);
-    float *dx1_pm = (float *)(((uintptr_t)w + 255) & ~(uintptr_t)255);
-    const long P = (long)npoints * nsample;
-    // (b, cout, P) -> (b, P, cout)
-    if (P >= (1L << 31)) return bad_arg("amc3d_grouped_conv_bn_backward_csr: too many positions");
-    int nparts = (int)parts;
-    if (phase != 2) {
-        if (dx1_position_major) {
-            if ((uintptr_t)dx1 & 15) return bad_arg("amc3d_grouped_conv_bn_backward_csr: position-major dx1 must be 16-byte aligned");
-            dx1_pm = const_cast<float *>(dx1);  // read only
-        } else if (int st = amc3d_transpose_cn(b, cout, (int)P, dx1, dx1_pm, stream_)) return st;
-        if (rev_dp && ((uintptr_t)rev_dp & 15)) return bad_arg("amc3d_grouped_conv_bn_backward_csr: rev_dp must be 16-byte aligned");
-        if (int st = csr_collapse(b, cout, n, npoints, nsample, relu, dx1_pm, g_pm, rev_start, rev_edge, rev_dp, dp, w_dp, mean, invstd,
-                                  gamma, beta, Q, partial, &nparts, stream))
-            return st;
+    int nparts;
+    if (lists) {
+        if (P >= (1L << 31)) return lagg_bad(entry, "too many positions");
+        nparts = (int)parts;
+        if (phase != 2) {
+            float *dx1_pm = (float *)(((uintptr_t)w + 255) & ~(uintptr_t)255);
+            if (dx1_position_major) {
+                if ((uintptr_t)dx1 & 15) return lagg_bad(entry, "position-major dx1 must be 16-byte aligned");
+                dx1_pm = const_cast<float *>(dx1);  // read only
+            } else if (int st = amc3d_transpose_cn(b, cout, (int)P, dx1, dx1_pm, stream_)) return st;  // (b, cout, P) -> (b, P, cout)
+            if (rev_dp && ((uintptr_t)rev_dp & 15)) return lagg_bad(entry, "rev_dp must be 16-byte aligned");
+            if (int st = csr_collapse(b, cout, n, npoints, nsample, relu, dx1_pm, g_pm, rev_start, rev_edge, rev_dp, dp, w_dp, mean,
+                                      invstd, gamma, beta, Q, partial, &nparts, stream))
+                return st;
+        }
+    } else {
+        const int ct = cout < LAGG_XC ? cout : LAGG_XC;
+        const int ctiles = LAGG_CTILES;
+        const int nparts_b = div_up(div_up(P, LAGG_PT), ctiles);
+        nparts = nparts_b * b;
+        if (phase != 2) {
+            if (int st = fill_i32((int *)Q, 0, (size_t)b * n * cout, stream)) return st;
+#define AMC_COLLAPSE(L)                                                                                                        \
+    hipLaunchKernelGGL(lagg_collapse_kernel<L>, dim3(nparts_b, cout / ct, b), dim3(256), 0, stream, cout, n, P, relu, dx1, g_pm,  \
+                       idx, dp, w_dp, mean, invstd, gamma, beta, Q, partial, nparts_b, ctiles)
+            switch (ct / 4) { case 2: AMC_COLLAPSE(2); break; case 4: AMC_COLLAPSE(4); break; case 8: AMC_COLLAPSE(8); break; default: AMC_COLLAPSE(16); }
+#undef AMC_COLLAPSE
+        }
     }
-    hipLaunchKernelGGL(lagg_bwd_finalize_kernel, dim3(cout), dim3(LAGG_FT), 0, stream, cout, nparts,
-                       (double)b * (double)npoints * (double)nsample, partial, gm.mom, gd, w_dp, mean, invstd,
-                       gamma, dgamma, dbeta, dw_dp, lddw, coef, phase, dsums, count_dev);
-    if (phase == 1) return launch_status("amc3d_grouped_conv_bn_backward_csr");
-    lagg_apply(b, cout, n, Q, g_pm, gm, w_dp, coef, dg_cm, stream);
-    return launch_status("amc3d_grouped_conv_bn_backward_csr");
+    return lagg_backward_finish(entry, b, cout, n, npoints, nsample, nparts, partial, Q, coef, g_pm, moments, gd, w_dp, mean, invstd,
+                                gamma, dg_cm, dw_dp, lddw, dgamma, dbeta, phase, dsums, count_dev, stream);
 }
 
-AMC_API int amc3d_grouped_conv_bn_backward_csr(int b, int cout, int n, int npoints, int nsample, int relu, const float *dx1,
-                                               int dx1_position_major, const float *g_pm, const int *rev_start, const int *rev_edge,
-                                               const float *rev_dp, const float *dp,
-                                               const float *w_dp, const void *moments, const double *gd, const float *mean,
-                                               const float *invstd, const float *gamma, const float *beta, float *dg_cm,
-                                               float *dw_dp, float *dgamma, float *dbeta, int phase, double *dsums,
-                                               const double *count_dev, void *workspace, size_t workspace_bytes, void *stream_)
-{
-    return grouped_conv_bn_backward_csr_impl(b, cout, n, npoints, nsample, relu, dx1, dx1_position_major, g_pm, rev_start, rev_edge, rev_dp, dp,
-        WDp{w_dp, 3}, moments, gd, mean, invstd, gamma, beta, dg_cm, dw_dp, 3, dgamma, dbeta, phase, dsums,
-        count_dev, workspace, workspace_bytes, stream_);
-}
-
-// the same with w_dp and dw_dp addressed at a row stride (floats): the dp columns inside the layer's own (cout, cin + 3) weight and its gradient
-AMC_API int amc3d_grouped_conv_bn_backward_csr_strided(int b, int cout, int n, int npoints, int nsample, int relu,
-                                                       const float *dx1, int dx1_position_major,
-                                                       const float *g_pm, const int *rev_start,
-                                                       const int *rev_edge, const float *rev_dp, const float *dp,
-                                                       const float *w_dp, long ldw, const void *moments,
-                                                       const double *gd, const float *mean, const float *invstd,
-                                                       const float *gamma, const float *beta, float *dg_cm,
-                                                       float *dw_dp, long lddw, float *dgamma, float *dbeta,
-                                                       int phase, double *dsums, const double *count_dev,
-                                                       void *workspace, size_t workspace_bytes, void *stream_)
-{
-    if (ldw < 3 || lddw < 3) return bad_arg("amc3d_grouped_conv_bn_backward_csr_strided: row stride below 3");
-    return grouped_conv_bn_backward_csr_impl(b, cout, n, npoints, nsample, relu, dx1, dx1_position_major, g_pm, rev_start, rev_edge, rev_dp, dp,
-        WDp{w_dp, ldw}, moments, gd, mean, invstd, gamma, beta, dg_cm, dw_dp, lddw, dgamma, dbeta, phase, dsums,
-        count_dev, workspace, workspace_bytes, stream_);
-}

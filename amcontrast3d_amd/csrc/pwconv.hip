@@ -416,7 +416,7 @@ AMC_API int amc3d_pointwise_conv_forward_strided(int b, int cin, int cout, long 
 }
 
 // the strided form without a bias, y written as position-major rows (b,P,cout): what the neighbourhood layers gather from
-// (amc3d_local_aggregation_forward_rows, amc3d_grouped_conv_bn_forward_rows).  Equal to the channel-major output transposed, bit
+// (amc3d_local_aggregation_forward, amc3d_grouped_conv_bn_forward with g_cm == NULL).  Equal to the channel-major output transposed, bit
 // for bit.  Workspace: amc3d_pointwise_conv_forward_workspace_bytes(b, cin, cout, P, 0).  A y that is not 16-byte aligned, or
 // cout % 4 != 0, takes 4-byte stores.
 AMC_API int amc3d_pointwise_conv_forward_rows(int b, int cin, int cout, long P, const float *x, const float *weight, long ldw,
@@ -486,7 +486,7 @@ AMC_API int amc3d_pointwise_conv_backward(int b, int cin, int cout, long P, cons
 
 // the same with row strides ldw / lddw (floats, >= cin) for weight and dweight -- column blocks of wider matrices; the columns
 // of dweight's rows outside the block are not touched -- and, with dx_position_major != 0, dx written as (b,P,cin) rows (the
-// layout amc3d_grouped_conv_bn_backward_csr gathers from) instead of (b,cin,P).  Same sums in the same order as above.
+// layout amc3d_grouped_conv_bn_backward with lists gathers from) instead of (b,cin,P).  Same sums in the same order as above.
 AMC_API int amc3d_pointwise_conv_backward_strided(int b, int cin, int cout, long P, const float *x, const float *weight, long ldw,
                                                   const float *dy, float *dx, int dx_position_major, float *dweight, long lddw,
                                                   void *workspace, size_t workspace_bytes, void *stream)

@@ -13,6 +13,7 @@ bookkeeping); every operator runs a hand-written gfx950 kernel.  CPU tensors are
 rejected: there is no fallback path.
 """
 import ctypes
+from types import SimpleNamespace
 
 import torch
 from torch.autograd import Function
@@ -1693,6 +1694,121 @@ def _pw_backward_blocks(lib, bf16, B, Cin, C, N, f, w_f, dg_cm, df, dw_f, lddw, 
                                                          _ptr(work2), wb2, _stream(f)), "pointwise_conv_backward")
 
 
+def _lagg_begin(ctx, f, dp, idx, moments, weight, gamma, beta, eps, relu, bn, csr):
+    """What both neighbourhood layers' forwards start from: the checked inputs, the weight's two blocks, G's buffers, the
+    statistics buffers, the workspace and the arguments of the layer's C call around its outputs: *s.head, outputs, *s.tail(phase)"""
+    _need_gpu(f, dp, idx, moments, weight, gamma, beta)
+    _need_dtype(torch.float32, f=f, dp=dp, weight=weight)
+    _need_dtype(torch.int32, idx=idx)
+    s = SimpleNamespace(f=f.contiguous(), dp=dp.contiguous(), idx=idx.contiguous(), lib=_lib.load())
+    B, Cin, N = f.shape
+    _, M, K = idx.shape
+    C = weight.shape[0]
+    assert weight.numel() == C * (Cin + 3)
+    s.shape, dev = (B, Cin, C, N, M, K), f.device
+    # deterministic mode: the backward gathers over the reverse lists of idx (csr = (rev_start, rev_edge[, group_csr_dp's
+    # stream]) of ops.group_csr from the plan, or built in backward) instead of scattering with float atomics
+    ctx.det, ctx.csr = deterministic(), csr
+    ctx.bf16 = mixed_precision() and min(Cin, C) >= 64 and B * N >= 4096  # the conv on the source points on the bf16 MFMA
+    w2 = weight.detach().reshape(C, Cin + 3).contiguous()
+    s.w_dp, ctx.ldw, s.w_f = _dp_f_blocks(w2, ctx.bf16)
+    # fp32: the conv writes G as the rows the layer gathers; the bf16-compute conv writes it channel-major and the layer turns it
+    s.g_cm = torch.empty(B, C, N, dtype=torch.float32, device=dev) if ctx.bf16 else None
+    s.g_pm = torch.empty(B, N, C, dtype=torch.float32, device=dev)
+    s.mean, s.invstd, s.var_u = mean, invstd, var_u = _bn_stat_bufs(C, dev)
+    s.gd = gd = torch.empty(C, 3, dtype=torch.float64, device=dev)
+    s.sums = sums = torch.empty(2 * C + 1, dtype=torch.float64, device=dev)
+    wb = int(s.lib.amc3d_local_aggregation_workspace_bytes(B, C, N, M))
+    work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
+    mom, rm, rv, nbt = _bn_running_args(bn)
+    s.head = (B, C, N, M, K, 1, int(bool(relu)), float(eps), mom, _ptr(s.g_cm) if ctx.bf16 else None, _ptr(s.idx), _ptr(s.dp),
+              _ptr(s.w_dp), ctx.ldw, _ptr(moments), _ptr(gamma), _ptr(beta), _ptr(s.g_pm))
+    # (the closure names no `s`: in a cycle with it every buffer here would outlive the call until the garbage collector runs)
+    s.tail = lambda phase: (_ptr(mean), _ptr(invstd), _ptr(var_u), _ptr(gd), rm, rv, nbt, phase, _ptr(sums), _ptr(work), wb,
+                            _stream(f))
+    return s
+
+
+def _lagg_finish(ctx, s, name, nbytes, moved, call, moments, weight, gamma, beta, relu, bn, group, *saved):
+    """The forward itself -- the conv on the source points, then call(phase) under the span `name`: phase 0, or 1 and 2 around
+    the all-reduce over `group` -- and its bookkeeping; `saved` follows the twelve tensors both layers keep."""
+    B, Cin, C, N, M, K = s.shape
+    with torch.cuda.device(s.f.device):
+        with timing.span("pointwise_conv_forward", 4 * B * N * (Cin + C), 2.0 * B * N * Cin * C):
+            if s.g_cm is None:
+                _pw_forward_rows(s.lib, B, Cin, C, N, s.f, s.w_f, s.g_pm)
+            else:
+                _pw_forward(s.lib, True, B, Cin, C, N, s.f, s.w_f, None, s.g_cm)
+        with timing.span(name, nbytes, moved=moved):
+            if group is None:
+                call(0)
+            else:
+                call(1)
+                _sync(group, s.sums)
+                call(2)
+    if bn is not None and bn.track_running_stats and bn.running_mean is not None and bn.momentum is None:
+        bn_update_running(bn, s.mean, s.var_u)  # cumulative average: its own launch
+    ctx.save_for_backward(s.f, s.w_f, s.w_dp, s.g_pm, s.idx, s.dp, moments, gamma, beta, s.mean, s.invstd, s.gd, *saved)
+    ctx.relu, ctx.wshape, ctx.group = bool(relu), tuple(weight.shape), group
+    ctx.shape = s.shape
+
+
+def _lagg_backward_begin(ctx, lists_given, lists_bytes):
+    """What both backwards start from: the gradients to fill, the reverse lists (deterministic mode builds those the plan did not
+    give; `lists_given`: a layer that gathers over given lists in any mode), the workspaces (`lists_bytes(lib, B, C, N, M, K)`:
+    the layer's with lists) and the arguments of the layer's C call: *s.dims, ..., *s.lists, ..., *s.mid, *s.tail(phase)"""
+    saved = ctx.saved_tensors
+    f, w_f, w_dp, g_pm, idx, dp, moments, gamma, beta, mean, invstd, gd = saved[:12]
+    sums = saved[-1]
+    B, Cin, C, N, M, K = ctx.shape
+    dev = f.device
+    s = SimpleNamespace(saved=saved, f=f, w_f=w_f, g_pm=g_pm, idx=idx, lib=_lib.load())
+    s.dg_cm = dg_cm = torch.empty(B, C, N, dtype=torch.float32, device=dev)
+    s.dw, s.dw_dp, lddw, s.dw_f, s.lddw_f = _dp_f_grad(C, Cin, dev, ctx.bf16)
+    dw_dp = s.dw_dp
+    s.dgamma, s.dbeta = dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
+    s.dsums = dsums = torch.empty(2 * C, dtype=torch.float64, device=dev)
+    count = ctypes.c_void_p(sums.data_ptr() + 16 * C)
+    s.csr = ctx.csr if ctx.det or lists_given else None
+    if s.csr is None and ctx.det:
+        s.csr = group_csr(idx, N)
+    wb = int(lists_bytes(s.lib, B, C, N, M, K) if s.csr is not None else s.lib.amc3d_local_aggregation_workspace_bytes(B, C, N, M))
+    work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
+    s.need_f = ctx.needs_input_grad[0]
+    s.df = torch.empty_like(f) if s.need_f else None
+    _, pw_wbytes, _ = _pw(s.lib, ctx.bf16)
+    s.wb2 = int(pw_wbytes(B, Cin, C, N))
+    s.work2 = torch.empty(max(s.wb2, 4), dtype=torch.uint8, device=dev)
+    s.dims = (B, C, N, M, K, int(ctx.relu))
+    s.lists = (_ptr(s.csr[0]), _ptr(s.csr[1])) if s.csr is not None else (None, None)
+    s.mid = (_ptr(dp), _ptr(w_dp), ctx.ldw, _ptr(moments), _ptr(gd), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta))
+    # (as in _lagg_begin, no `s` in the closure: autograd takes dgamma / dbeta as .grad only while nothing else holds them, and
+    # copies them otherwise)
+    s.tail = lambda phase: (_ptr(dg_cm), _ptr(dw_dp), lddw, _ptr(dgamma), _ptr(dbeta), phase, _ptr(dsums), count, _ptr(work), wb,
+                            _stream(f))
+    return s
+
+
+def _lagg_backward_finish(ctx, s, name, nbytes, moved, call):
+    """The backward itself -- call(phase) under the span `name`, then the conv's backward on the source points -- and the
+    gradients of either layer's twelve inputs."""
+    B, Cin, C, N, M, K = ctx.shape
+    need_f = s.need_f
+    with torch.cuda.device(s.f.device):
+        with timing.span(name, nbytes, moved=moved):
+            if ctx.group is None:
+                call(0)
+            else:
+                call(1)
+                _sync(ctx.group, s.dsums)
+                call(2)
+        with timing.span("pointwise_conv_backward", 4 * B * N * (Cin + C + Cin * int(need_f)),
+                         2.0 * B * N * Cin * C * (1 + int(need_f)), moved=4 * B * N * (Cin + C) * (1 + int(need_f))):
+            _pw_backward_blocks(s.lib, ctx.bf16, B, Cin, C, N, s.f, s.w_f, s.dg_cm, s.df, s.dw_f, s.lddw_f, s.work2, s.wb2)
+    dw = (_join_columns(s.dw_dp, s.dw_f) if s.dw is None else s.dw).view(ctx.wshape)
+    return s.df, None, None, None, dw, s.dgamma, s.dbeta, None, None, None, None, None
+
+
 class LocalAggregationFused(Function):
     """pooled (B,C,M) = max_k [relu](bn(conv1x1([dp ; f[idx]]))) -- grouping_operation + cat + Conv2d + BatchNorm2d (batch
     statistics) [+ ReLU] + max of LocalAggregation / single-layer SetAbstraction (pointnext_AA.py:57-63, 139-170) -- with
@@ -1703,129 +1819,40 @@ class LocalAggregationFused(Function):
 
     @staticmethod
     def forward(ctx, f, dp, idx, moments, weight, gamma, beta, eps, relu, bn=None, group=None, csr=None):
-        _need_gpu(f, dp, idx, moments, weight, gamma, beta)
-        _need_dtype(torch.float32, f=f, dp=dp, weight=weight)
-        _need_dtype(torch.int32, idx=idx)
-        f, dp, idx = f.contiguous(), dp.contiguous(), idx.contiguous()
-        B, Cin, N = f.shape
-        _, M, K = idx.shape
-        C = weight.shape[0]
-        assert weight.numel() == C * (Cin + 3)
-        dev = f.device
-        lib = _lib.load()
-        # deterministic mode: the backward gathers over the reverse lists of idx (csr = group_csr(idx, N) of the plan, or
-        # built in backward) instead of scattering with float atomics
-        ctx.det, ctx.csr = deterministic(), csr
-        ctx.bf16 = mixed_precision() and min(Cin, C) >= 64 and B * N >= 4096  # the conv on the source points on the bf16 MFMA
-        w2 = weight.detach().reshape(C, Cin + 3).contiguous()
-        w_dp, ldw, w_f = _dp_f_blocks(w2, ctx.bf16)
-        # fp32: the conv writes G as the rows the layer gathers; the bf16-compute conv writes it channel-major and the layer turns it
-        g_cm = torch.empty(B, C, N, dtype=torch.float32, device=dev) if ctx.bf16 else None
-        g_pm = torch.empty(B, N, C, dtype=torch.float32, device=dev)
-        pooled = torch.empty(B, C, M, dtype=torch.float32, device=dev)
+        s = _lagg_begin(ctx, f, dp, idx, moments, weight, gamma, beta, eps, relu, bn, csr)
+        B, Cin, C, N, M, K = s.shape
+        pooled = torch.empty(B, C, M, dtype=torch.float32, device=f.device)
         ystar = torch.empty_like(pooled)
-        arg = torch.empty(B, C, M, dtype=torch.uint8, device=dev)
-        mean, invstd, var_u = _bn_stat_bufs(C, dev)
-        gd = torch.empty(C, 3, dtype=torch.float64, device=dev)
-        sums = torch.empty(2 * C + 1, dtype=torch.float64, device=dev)
-        wb = int(lib.amc3d_local_aggregation_workspace_bytes(B, C, N, M))
-        work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
-        mom, rm, rv, nbt = _bn_running_args(bn)
+        arg = torch.empty(B, C, M, dtype=torch.uint8, device=f.device)
 
         def call(phase):
-            if g_cm is None:
-                _lib.check(lib.amc3d_local_aggregation_forward_rows(
-                    B, C, N, M, K, 1, int(bool(relu)), float(eps), mom, _ptr(g_pm), _ptr(idx), _ptr(dp), _ptr(w_dp), ldw,
-                    _ptr(moments), _ptr(gamma), _ptr(beta), _ptr(pooled), _ptr(arg), _ptr(ystar), _ptr(mean), _ptr(invstd),
-                    _ptr(var_u), _ptr(gd), rm, rv, nbt, phase, _ptr(sums), _ptr(work), wb, _stream(f)),
-                    "local_aggregation_forward")
-                return
-            _lib.check(lib.amc3d_local_aggregation_forward_strided(
-                B, C, N, M, K, 1, int(bool(relu)), float(eps), mom, _ptr(g_cm), _ptr(idx), _ptr(dp), _ptr(w_dp), ldw,
-                _ptr(moments), _ptr(gamma), _ptr(beta), _ptr(g_pm), _ptr(pooled), _ptr(arg), _ptr(ystar), _ptr(mean),
-                _ptr(invstd), _ptr(var_u), _ptr(gd), rm, rv, nbt, phase, _ptr(sums), _ptr(work), wb, _stream(f)),
-                "local_aggregation_forward")
+            _lib.check(s.lib.amc3d_local_aggregation_forward(*s.head, _ptr(pooled), _ptr(arg), _ptr(ystar), *s.tail(phase)),
+                       "local_aggregation_forward")
 
-        with torch.cuda.device(dev):
-            with timing.span("pointwise_conv_forward", 4 * B * N * (Cin + C), 2.0 * B * N * Cin * C):
-                if g_cm is None:
-                    _pw_forward_rows(lib, B, Cin, C, N, f, w_f, g_pm)
-                else:
-                    _pw_forward(lib, True, B, Cin, C, N, f, w_f, None, g_cm)
-            # algorithmic bytes: G read (statistics) + the gathered rows, idx, dp + the pooled outputs; a channel-major G is
-            # read once more and written as rows
-            with timing.span("local_aggregation_forward", 4 * B * N * C + 16 * B * M * K + 5 * B * M * C,
-                             moved=(4 if g_cm is None else 12) * B * N * C + B * M * K * (4 * C + 16) + 9 * B * M * C):
-                if group is None:
-                    call(0)
-                else:
-                    call(1)
-                    _sync(group, sums)
-                    call(2)
-        if bn is not None and bn.track_running_stats and bn.running_mean is not None and bn.momentum is None:
-            bn_update_running(bn, mean, var_u)  # cumulative average: its own launch
-        ctx.save_for_backward(f, w_f, w_dp, g_pm, idx, dp, moments, gamma, beta, mean, invstd, gd, ystar, arg, sums)
-        ctx.ldw = ldw
-        ctx.relu, ctx.wshape, ctx.group = bool(relu), tuple(weight.shape), group
+        # algorithmic bytes: G read (statistics) + the gathered rows, idx, dp + the pooled outputs; a channel-major G is
+        # read once more and written as rows
+        _lagg_finish(ctx, s, "local_aggregation_forward", 4 * B * N * C + 16 * B * M * K + 5 * B * M * C,
+                     (4 if s.g_cm is None else 12) * B * N * C + B * M * K * (4 * C + 16) + 9 * B * M * C, call,
+                     moments, weight, gamma, beta, relu, bn, group, ystar, arg, s.sums)
         if _pool_log is not None:
             _pool_log[_next_pool_seq()] = arg
         return pooled
 
     @staticmethod
     def backward(ctx, dpooled):
-        f, w_f, w_dp, g_pm, idx, dp, moments, gamma, beta, mean, invstd, gd, ystar, arg, sums = ctx.saved_tensors
-        B, Cin, N = f.shape
-        _, M, K = idx.shape
-        C = w_f.shape[0]
-        dev = f.device
-        lib = _lib.load()
+        s = _lagg_backward_begin(ctx, False, lambda lib, B, C, N, M, K: lib.amc3d_local_aggregation_csr_workspace_bytes(B, C, N, M))
+        ystar, arg = s.saved[12:14]
+        B, Cin, C, N, M, K = ctx.shape
         dpooled = dpooled.contiguous()
-        dg_cm = torch.empty(B, C, N, dtype=torch.float32, device=dev)
-        dw, dw_dp, lddw, dw_f, lddw_f = _dp_f_grad(C, Cin, dev, ctx.bf16)
-        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
-        dsums = torch.empty(2 * C, dtype=torch.float64, device=dev)
-        count = ctypes.c_void_p(sums.data_ptr() + 16 * C)
-        csr = None
-        if ctx.det:
-            csr = ctx.csr if ctx.csr is not None else group_csr(idx, N)
-        wb = int(lib.amc3d_local_aggregation_csr_workspace_bytes(B, C, N, M) if ctx.det
-                 else lib.amc3d_local_aggregation_workspace_bytes(B, C, N, M))
-        work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
-        need_f = ctx.needs_input_grad[0]
-        df = torch.empty_like(f) if need_f else None
-        _, pw_wbytes, _ = _pw(lib, ctx.bf16)
-        wb2 = int(pw_wbytes(B, Cin, C, N))
-        work2 = torch.empty(max(wb2, 4), dtype=torch.uint8, device=dev)
+        name = "local_aggregation_backward_csr" if s.csr is not None else "local_aggregation_backward"
 
         def call(phase):
-            if csr is not None:
-                _lib.check(lib.amc3d_local_aggregation_backward_csr_strided(
-                    B, C, N, M, K, int(ctx.relu), _ptr(dpooled), _ptr(ystar), _ptr(arg), _ptr(g_pm), _ptr(idx), _ptr(dp),
-                    _ptr(w_dp), ctx.ldw, _ptr(moments), _ptr(gd), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta),
-                    _ptr(csr[0]), _ptr(csr[1]), _ptr(dg_cm), _ptr(dw_dp), lddw, _ptr(dgamma), _ptr(dbeta), phase, _ptr(dsums),
-                    count, _ptr(work), wb, _stream(f)), "local_aggregation_backward_csr")
-                return
-            _lib.check(lib.amc3d_local_aggregation_backward_strided(
-                B, C, N, M, K, int(ctx.relu), _ptr(dpooled), _ptr(ystar), _ptr(arg), _ptr(g_pm), _ptr(idx), _ptr(dp),
-                _ptr(w_dp), ctx.ldw, _ptr(moments), _ptr(gd), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(dg_cm),
-                _ptr(dw_dp), lddw, _ptr(dgamma), _ptr(dbeta), phase, _ptr(dsums), count, _ptr(work), wb, _stream(f)),
-                "local_aggregation_backward")
+            _lib.check(s.lib.amc3d_local_aggregation_backward(
+                *s.dims, _ptr(dpooled), _ptr(ystar), _ptr(arg), _ptr(s.g_pm), _ptr(s.idx), *s.mid, *s.lists, *s.tail(phase)), name)
 
-        with torch.cuda.device(dev):
-            with timing.span("local_aggregation_backward_csr" if csr is not None else "local_aggregation_backward",
-                             5 * B * M * C + 8 * B * N * C + 16 * B * M * K,
-                             moved=(17 + (10 + 5 * K if csr is not None else 0)) * B * M * C + 12 * B * N * C + 16 * B * M * K):
-                if ctx.group is None:
-                    call(0)
-                else:
-                    call(1)
-                    _sync(ctx.group, dsums)
-                    call(2)
-            with timing.span("pointwise_conv_backward", 4 * B * N * (Cin + C + Cin * int(need_f)),
-                             2.0 * B * N * Cin * C * (1 + int(need_f)), moved=4 * B * N * (Cin + C) * (1 + int(need_f))):
-                _pw_backward_blocks(lib, ctx.bf16, B, Cin, C, N, f, w_f, dg_cm, df, dw_f, lddw_f, work2, wb2)
-        dw = (_join_columns(dw_dp, dw_f) if dw is None else dw).view(ctx.wshape)
-        return df, None, None, None, dw, dgamma, dbeta, None, None, None, None, None
+        return _lagg_backward_finish(
+            ctx, s, name, 5 * B * M * C + 8 * B * N * C + 16 * B * M * K,
+            (17 + (10 + 5 * K if s.csr is not None else 0)) * B * M * C + 12 * B * N * C + 16 * B * M * K, call)
 
 
 class GroupedConvBN(Function):
@@ -1837,143 +1864,68 @@ class GroupedConvBN(Function):
 
     @staticmethod
     def forward(ctx, f, dp, idx, moments, weight, gamma, beta, eps, relu, bn=None, csr=None, group=None):
-        _need_gpu(f, dp, idx, moments, weight, gamma, beta)
-        _need_dtype(torch.float32, f=f, dp=dp, weight=weight)
-        _need_dtype(torch.int32, idx=idx)
-        f, dp, idx = f.contiguous(), dp.contiguous(), idx.contiguous()
-        B, Cin, N = f.shape
-        _, M, K = idx.shape
-        C = weight.shape[0]
-        assert weight.numel() == C * (Cin + 3)
-        dev = f.device
-        lib = _lib.load()
-        ctx.csr = csr  # (rev_start, rev_edge[, group_csr_dp's stream]) of ops.group_csr, or None: backward then scatters with float atomics
-        ctx.det = deterministic()  # (deterministic mode: backward builds the lists it was not given)
-        ctx.bf16 = mixed_precision() and min(Cin, C) >= 64 and B * N >= 4096
-        w2 = weight.detach().reshape(C, Cin + 3).contiguous()
-        w_dp, ldw, w_f = _dp_f_blocks(w2, ctx.bf16)
-        g_cm = torch.empty(B, C, N, dtype=torch.float32, device=dev) if ctx.bf16 else None  # (as LocalAggregationFused)
-        g_pm = torch.empty(B, N, C, dtype=torch.float32, device=dev)
-        x1 = torch.empty(B, C, M, K, dtype=torch.float32, device=dev)
-        mean, invstd, var_u = _bn_stat_bufs(C, dev)
-        gd = torch.empty(C, 3, dtype=torch.float64, device=dev)
-        sums = torch.empty(2 * C + 1, dtype=torch.float64, device=dev)
-        wb = int(lib.amc3d_local_aggregation_workspace_bytes(B, C, N, M))
-        work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
-        mom, rm, rv, nbt = _bn_running_args(bn)
+        s = _lagg_begin(ctx, f, dp, idx, moments, weight, gamma, beta, eps, relu, bn, csr)
+        B, Cin, C, N, M, K = s.shape
+        x1 = torch.empty(B, C, M, K, dtype=torch.float32, device=f.device)
 
         def call(phase):
-            if g_cm is None:
-                _lib.check(lib.amc3d_grouped_conv_bn_forward_rows(
-                    B, C, N, M, K, 1, int(bool(relu)), float(eps), mom, _ptr(g_pm), _ptr(idx), _ptr(dp), _ptr(w_dp), ldw,
-                    _ptr(moments), _ptr(gamma), _ptr(beta), _ptr(x1), _ptr(mean), _ptr(invstd), _ptr(var_u), _ptr(gd), rm, rv,
-                    nbt, phase, _ptr(sums), _ptr(work), wb, _stream(f)), "grouped_conv_bn_forward")
-                return
-            _lib.check(lib.amc3d_grouped_conv_bn_forward_strided(
-                B, C, N, M, K, 1, int(bool(relu)), float(eps), mom, _ptr(g_cm), _ptr(idx), _ptr(dp), _ptr(w_dp), ldw,
-                _ptr(moments), _ptr(gamma), _ptr(beta), _ptr(g_pm), _ptr(x1), _ptr(mean), _ptr(invstd), _ptr(var_u),
-                _ptr(gd), rm, rv, nbt, phase, _ptr(sums), _ptr(work), wb, _stream(f)), "grouped_conv_bn_forward")
+            _lib.check(s.lib.amc3d_grouped_conv_bn_forward(*s.head, _ptr(x1), *s.tail(phase)), "grouped_conv_bn_forward")
 
-        with torch.cuda.device(dev):
-            with timing.span("pointwise_conv_forward", 4 * B * N * (Cin + C), 2.0 * B * N * Cin * C):
-                if g_cm is None:
-                    _pw_forward_rows(lib, B, Cin, C, N, f, w_f, g_pm)
-                else:
-                    _pw_forward(lib, True, B, Cin, C, N, f, w_f, None, g_cm)
-            with timing.span("grouped_conv_bn_forward", 4 * B * N * C + B * M * K * (4 * C + 16),
-                             moved=(4 if g_cm is None else 12) * B * N * C + B * M * K * (8 * C + 16)):
-                if group is None:
-                    call(0)
-                else:
-                    call(1)
-                    _sync(group, sums)
-                    call(2)
-        if bn is not None and bn.track_running_stats and bn.running_mean is not None and bn.momentum is None:
-            bn_update_running(bn, mean, var_u)
-        ctx.save_for_backward(f, w_f, w_dp, g_pm, idx, dp, moments, gamma, beta, mean, invstd, gd, sums)
-        ctx.ldw = ldw
-        ctx.relu, ctx.wshape, ctx.group = bool(relu), tuple(weight.shape), group
+        _lagg_finish(ctx, s, "grouped_conv_bn_forward", 4 * B * N * C + B * M * K * (4 * C + 16),
+                     (4 if s.g_cm is None else 12) * B * N * C + B * M * K * (8 * C + 16), call,
+                     moments, weight, gamma, beta, relu, bn, group, s.sums)
         return x1
 
     @staticmethod
     def backward(ctx, dx1):
-        f, w_f, w_dp, g_pm, idx, dp, moments, gamma, beta, mean, invstd, gd, sums = ctx.saved_tensors
-        B, Cin, N = f.shape
-        _, M, K = idx.shape
-        C = w_f.shape[0]
-        dev = f.device
-        lib = _lib.load()
+        # without lists (no plan, not deterministic mode) the backward scatters with float atomics
+        s = _lagg_backward_begin(ctx, True, lambda lib, B, C, N, M, K: lib.amc3d_grouped_conv_bn_csr_workspace_bytes(B, C, N, M, K))
+        B, Cin, C, N, M, K = ctx.shape
         # SATailActivated hands the gradient over as position-major rows (a (B,C,M,K) view of a (B,M,K,C) buffer): the
         # gather along the reverse lists reads those directly; any other layout is made channel-major and transposed
-        csr = ctx.csr
-        if csr is None and ctx.det:  # deterministic mode: always the gather, with lists built here when the plan has none
-            csr = group_csr(idx, N)
-        dx1_pm = csr is not None and dx1.dim() == 4 and dx1.permute(0, 2, 3, 1).is_contiguous() and C > 1
+        dx1_pm = s.csr is not None and dx1.dim() == 4 and dx1.permute(0, 2, 3, 1).is_contiguous() and C > 1
         if not dx1_pm:
             dx1 = dx1.contiguous()
-        dg_cm = torch.empty(B, C, N, dtype=torch.float32, device=dev)
-        dw, dw_dp, lddw, dw_f, lddw_f = _dp_f_grad(C, Cin, dev, ctx.bf16)
-        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
-        dsums = torch.empty(2 * C, dtype=torch.float64, device=dev)
-        count = ctypes.c_void_p(sums.data_ptr() + 16 * C)
-        wb = int(lib.amc3d_grouped_conv_bn_csr_workspace_bytes(B, C, N, M, K) if csr is not None
-                 else lib.amc3d_local_aggregation_workspace_bytes(B, C, N, M))
-        work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
-        need_f = ctx.needs_input_grad[0]
-        df = torch.empty_like(f) if need_f else None
-        _, pw_wbytes, _ = _pw(lib, ctx.bf16)
-        wb2 = int(pw_wbytes(B, Cin, C, N))
-        work2 = torch.empty(max(wb2, 4), dtype=torch.uint8, device=dev)
+        rev_dp = _ptr(s.csr[2]) if s.csr is not None and len(s.csr) > 2 and s.csr[2] is not None else None
 
         def call(phase):
-            if csr is not None:
-                _lib.check(lib.amc3d_grouped_conv_bn_backward_csr_strided(
-                    B, C, N, M, K, int(ctx.relu), _ptr(dx1), int(dx1_pm), _ptr(g_pm), _ptr(csr[0]), _ptr(csr[1]),
-                    _ptr(csr[2]) if len(csr) > 2 and csr[2] is not None else None, _ptr(dp), _ptr(w_dp), ctx.ldw,
-                    _ptr(moments), _ptr(gd), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(dg_cm), _ptr(dw_dp), lddw,
-                    _ptr(dgamma), _ptr(dbeta), phase, _ptr(dsums), count, _ptr(work), wb, _stream(f)),
-                    "grouped_conv_bn_backward_csr")
-            else:
-                _lib.check(lib.amc3d_grouped_conv_bn_backward_strided(
-                    B, C, N, M, K, int(ctx.relu), _ptr(dx1), _ptr(g_pm), _ptr(idx), _ptr(dp), _ptr(w_dp), ctx.ldw, _ptr(moments),
-                    _ptr(gd), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(dg_cm), _ptr(dw_dp), lddw, _ptr(dgamma),
-                    _ptr(dbeta), phase, _ptr(dsums), count, _ptr(work), wb, _stream(f)), "grouped_conv_bn_backward")
+            _lib.check(s.lib.amc3d_grouped_conv_bn_backward(
+                *s.dims, _ptr(dx1), int(dx1_pm), _ptr(s.g_pm), _ptr(s.idx), *s.lists, rev_dp, *s.mid, *s.tail(phase)),
+                "grouped_conv_bn_backward")
 
-        with torch.cuda.device(dev):
-            with timing.span("grouped_conv_bn_backward", B * M * K * (8 * C + 16) + 4 * B * N * C, moved=B * M * K * (8 * C + 16) + 12 * B * N * C):
-                if ctx.group is None:
-                    call(0)
-                else:
-                    call(1)
-                    _sync(ctx.group, dsums)
-                    call(2)
-            with timing.span("pointwise_conv_backward", 4 * B * N * (Cin + C + Cin * int(need_f)),
-                             2.0 * B * N * Cin * C * (1 + int(need_f)), moved=4 * B * N * (Cin + C) * (1 + int(need_f))):
-                _pw_backward_blocks(lib, ctx.bf16, B, Cin, C, N, f, w_f, dg_cm, df, dw_f, lddw_f, work2, wb2)
-        dw = (_join_columns(dw_dp, dw_f) if dw is None else dw).view(ctx.wshape)
-        return df, None, None, None, dw, dgamma, dbeta, None, None, None, None, None
+        return _lagg_backward_finish(ctx, s, "grouped_conv_bn_backward", B * M * K * (8 * C + 16) + 4 * B * N * C,
+                                     B * M * K * (8 * C + 16) + 12 * B * N * C, call)
+
+
+def _lagg_eval_begin(f, dp, idx, weight, bn, relu):
+    """Either layer in inference mode (running statistics): runs the conv on the source points and returns (B, C, M, K) and
+    the arguments of the layer's C call before and after its outputs"""
+    f, dp, idx = f.contiguous(), dp.contiguous(), idx.contiguous()
+    B, Cin, N = f.shape
+    _, M, K = idx.shape
+    C = weight.shape[0]
+    lib = _lib.load()
+    w2 = weight.detach().reshape(C, Cin + 3).contiguous()
+    w_dp, ldw, w_f = _dp_f_blocks(w2, False)
+    g_pm = torch.empty(B, N, C, dtype=torch.float32, device=f.device)
+    invstd = torch.rsqrt(bn.running_var + bn.eps)
+    with torch.cuda.device(f.device):
+        _pw_forward_rows(lib, B, Cin, C, N, f, w_f, g_pm)
+    # `keep`: what the pointers point into, for the caller to hold until its launch
+    keep = (f, dp, idx, w2, g_pm, invstd)
+    head = (B, C, N, M, K, 0, int(bool(relu)), float(bn.eps), 0.0, None, _ptr(idx), _ptr(dp), _ptr(w_dp), ldw, None,
+            _ptr(bn.weight), _ptr(bn.bias), _ptr(g_pm))
+    tail = (_ptr(bn.running_mean), _ptr(invstd), None, None, None, None, None, 0, None, None, 0, _stream(f))
+    return (B, C, M, K), head, tail, keep
 
 
 @torch.no_grad()
 def grouped_conv_bn_eval(f, dp, idx, weight, bn, relu):
     """GroupedConvBN in inference mode (running statistics), no gradient -> x1 (B,C,M,32)"""
-    f, dp, idx = f.contiguous(), dp.contiguous(), idx.contiguous()
-    B, Cin, N = f.shape
-    _, M, K = idx.shape
-    C = weight.shape[0]
-    dev = f.device
-    lib = _lib.load()
-    w2 = weight.detach().reshape(C, Cin + 3).contiguous()
-    w_dp, ldw, w_f = _dp_f_blocks(w2, False)
-    g_pm = torch.empty(B, N, C, dtype=torch.float32, device=dev)
-    x1 = torch.empty(B, C, M, K, dtype=torch.float32, device=dev)
-    invstd = torch.rsqrt(bn.running_var + bn.eps)
-    with torch.cuda.device(dev):
-        _pw_forward_rows(lib, B, Cin, C, N, f, w_f, g_pm)
-        _lib.check(lib.amc3d_grouped_conv_bn_forward_rows(
-            B, C, N, M, K, 0, int(bool(relu)), float(bn.eps), 0.0, _ptr(g_pm), _ptr(idx), _ptr(dp), _ptr(w_dp), ldw, None,
-            _ptr(bn.weight), _ptr(bn.bias), _ptr(x1), _ptr(bn.running_mean), _ptr(invstd), None, None, None,
-            None, None, 0, None, None, 0, _stream(f)), "grouped_conv_bn_forward")
+    (B, C, M, K), head, tail, _keep = _lagg_eval_begin(f, dp, idx, weight, bn, relu)
+    x1 = torch.empty(B, C, M, K, dtype=torch.float32, device=f.device)
+    with torch.cuda.device(f.device):
+        _lib.check(_lib.load().amc3d_grouped_conv_bn_forward(*head, _ptr(x1), *tail), "grouped_conv_bn_forward")
     return x1
 
 
@@ -1984,25 +1936,13 @@ def grouped_conv_bn_supported(cout, nsample):
 @torch.no_grad()
 def local_aggregation_eval(f, dp, idx, weight, bn, relu):
     """the same layer in inference mode (running statistics), no gradient"""
-    f, dp, idx = f.contiguous(), dp.contiguous(), idx.contiguous()
-    B, Cin, N = f.shape
-    _, M, K = idx.shape
-    C = weight.shape[0]
-    dev = f.device
-    lib = _lib.load()
-    w2 = weight.detach().reshape(C, Cin + 3).contiguous()
-    w_dp, ldw, w_f = _dp_f_blocks(w2, False)
-    g_pm = torch.empty(B, N, C, dtype=torch.float32, device=dev)
-    pooled = torch.empty(B, C, M, dtype=torch.float32, device=dev)
+    (B, C, M, K), head, tail, _keep = _lagg_eval_begin(f, dp, idx, weight, bn, relu)
+    pooled = torch.empty(B, C, M, dtype=torch.float32, device=f.device)
     ystar = torch.empty_like(pooled)
-    arg = torch.empty(B, C, M, dtype=torch.uint8, device=dev)
-    invstd = torch.rsqrt(bn.running_var + bn.eps)
-    with torch.cuda.device(dev):
-        _pw_forward_rows(lib, B, Cin, C, N, f, w_f, g_pm)
-        _lib.check(lib.amc3d_local_aggregation_forward_rows(
-            B, C, N, M, K, 0, int(bool(relu)), float(bn.eps), 0.0, _ptr(g_pm), _ptr(idx), _ptr(dp), _ptr(w_dp), ldw, None,
-            _ptr(bn.weight), _ptr(bn.bias), _ptr(pooled), _ptr(arg), _ptr(ystar), _ptr(bn.running_mean),
-            _ptr(invstd), None, None, None, None, None, 0, None, None, 0, _stream(f)), "local_aggregation_forward")
+    arg = torch.empty(B, C, M, dtype=torch.uint8, device=f.device)
+    with torch.cuda.device(f.device):
+        _lib.check(_lib.load().amc3d_local_aggregation_forward(*head, _ptr(pooled), _ptr(arg), _ptr(ystar), *tail),
+                   "local_aggregation_forward")
     return pooled
 
 

@@ -592,14 +592,14 @@ int amc3d_pointwise_conv_backward(int b, int cin, int cout, long P, const float 
  * multiple of 4) takes 4-byte loads for the weight operand only; sums and their order are those of the calls above.
  * workspace: amc3d_pointwise_conv_forward_workspace_bytes() / amc3d_pointwise_conv_workspace_bytes() bytes.
  * dx_position_major != 0: dx is written as (b,P,cin) rows instead of (b,cin,P) -- the same values, four consecutive channels
- * of a position per 16-byte store -- the layout amc3d_grouped_conv_bn_backward_csr reads with dx1_position_major = 1. */
+ * of a position per 16-byte store -- the layout amc3d_grouped_conv_bn_backward reads from its lists with dx1_position_major = 1. */
 int amc3d_pointwise_conv_forward_strided(int b, int cin, int cout, long P, const float *x, const float *weight, long ldw,
                                          const float *bias, float *y, void *workspace, size_t workspace_bytes, void *stream);
 int amc3d_pointwise_conv_backward_strided(int b, int cin, int cout, long P, const float *x, const float *weight, long ldw,
                                           const float *dy, float *dx, int dx_position_major, float *dweight, long lddw,
                                           void *workspace, size_t workspace_bytes, void *stream);
 /* The strided forward without a bias, y_pm written as position-major rows (b,P,cout): the layout the neighbourhood layers
- * gather from (amc3d_local_aggregation_forward_rows, amc3d_grouped_conv_bn_forward_rows).  Same route, accumulators and sums
+ * gather from (amc3d_local_aggregation_forward, amc3d_grouped_conv_bn_forward with g_cm == NULL).  Same route, accumulators and sums
  * as amc3d_pointwise_conv_forward_strided: y_pm equals its output transposed, bit for bit.  A lane stores four consecutive
  * channels of its position as 16 bytes (y_pm 16-byte aligned and cout % 4 == 0), as four 4-byte stores otherwise.
  * workspace: amc3d_pointwise_conv_forward_workspace_bytes(b, cin, cout, P, 0) bytes. */
@@ -689,31 +689,60 @@ int amc3d_local_aggregation_supported(int cout, int nsample);
 size_t amc3d_group_moments_bytes(int b, int n);
 int amc3d_group_moments(int b, int n, int npoints, int nsample, const int *idx, const float *dp, void *moments,
                         size_t moments_bytes, void *stream);
-size_t amc3d_local_aggregation_workspace_bytes(int b, int cout, int n, int npoints);
-/* g_cm (b,cout,n) = W_f . f from amc3d_pointwise_conv_forward; w_dp (cout,3) = the conv weight's dp columns.
+/* The pooled layer.  G = W_f . f comes from the caller in one of two layouts.  g_cm == NULL: g_pm (b,n,cout), 16-byte aligned,
+ * already holds its rows and is an INPUT (amc3d_pointwise_conv_forward_rows writes them; no channel-major G exists).
+ * Otherwise g_cm (b,cout,n) (amc3d_pointwise_conv_forward) is first transposed into g_pm (amc3d_transpose_cn).
+ * w_dp = the conv weight's dp columns at a row stride of ldw floats (>= 3): w_dp = W, ldw = cin + 3 reads them inside the
+ * layer's own (cout, cin + 3) weight, no split.
  * Outputs: pooled (b,cout,npoints), arg (b,cout,npoints) bytes = torch.max's indices, ystar = the pre-BatchNorm value at
- * arg, g_pm (b,n,cout) point-major copy of g_cm, gd (cout,3) doubles (all kept for backward), mean / invstd /
- * var_unbiased (cout) + nn.BatchNorm's running update when running_mean != NULL (momentum < 0: left to the caller).
- * training == 0 (eval): mean / invstd are inputs (running statistics); moments, gd, var_unbiased, workspace may be NULL */
-int amc3d_local_aggregation_forward(int b, int cout, int n, int npoints, int nsample, int training, int relu, float eps,
-                                    float momentum, const float *g_cm, const int *idx, const float *dp, const float *w_dp,
-                                    const void *moments, const float *gamma, const float *beta, float *g_pm, float *pooled,
-                                    unsigned char *arg, float *ystar, float *mean, float *invstd, float *var_unbiased,
-                                    double *gd, float *running_mean, float *running_var, long long *num_batches_tracked,
-                                    int phase, double *sums, void *workspace, size_t workspace_bytes, void *stream);
-/* Statistics over several ranks (the reference converts every BatchNorm to SyncBatchNorm when world_size > 1,
+ * arg, gd (cout,3) doubles (all kept for backward, with g_pm), mean / invstd / var_unbiased (cout) + nn.BatchNorm's running
+ * update when running_mean != NULL (momentum < 0: left to the caller).  The statistics read the rows; their partial sums are
+ * taken over a fixed partition of the b*n points in a fixed order (the same bits on every run).
+ * training == 0 (eval): mean / invstd are inputs (running statistics); moments, gd, var_unbiased, workspace may be NULL, and
+ * with g_cm == NULL nothing is launched but the max-pool.
+ * Statistics over several ranks (the reference converts every BatchNorm to SyncBatchNorm when world_size > 1,
  * main_AA.py:146-148): phase 0 = one rank, everything in one call.  phase 1 writes this rank's {sum y, sum y^2} per channel
  * and its position count to sums (2*cout + 1 doubles) and returns; the caller all-reduces sums; phase 2 finishes from the
  * reduced sums (same arguments, same workspace).  Backward likewise: phase 1 -> dsums (2*cout doubles: sum dq, sum dq xhat),
  * all-reduce, phase 2 with count = sums + 2*cout of the forward call; parameter gradients stay rank-local. */
-/* dg_cm (b,cout,n) = gradient w.r.t. g_cm (feed it to amc3d_pointwise_conv_backward for df and dW_f); dw_dp (cout,3),
- * dgamma, dbeta (cout).  The pooled gradient is scattered with cout * npoints float atomics (not x nsample). */
+size_t amc3d_local_aggregation_workspace_bytes(int b, int cout, int n, int npoints);
+int amc3d_local_aggregation_forward(int b, int cout, int n, int npoints, int nsample, int training, int relu, float eps,
+                                    float momentum, const float *g_cm, const int *idx, const float *dp, const float *w_dp,
+                                    long ldw, const void *moments, const float *gamma, const float *beta, float *g_pm,
+                                    float *pooled, unsigned char *arg, float *ystar, float *mean, float *invstd,
+                                    float *var_unbiased, double *gd, float *running_mean, float *running_var,
+                                    long long *num_batches_tracked, int phase, double *sums, void *workspace,
+                                    size_t workspace_bytes, void *stream);
+/* dg_cm (b,cout,n) = gradient w.r.t. G (feed it to amc3d_pointwise_conv_backward for df and dW_f); dw_dp (cout,3) at a row
+ * stride of lddw floats (>= 3): dw_dp = dW, lddw = cin + 3 writes columns 0-2 of the layer's weight gradient
+ * (amc3d_pointwise_conv_backward_strided writes columns 3 onwards), no join; dgamma, dbeta (cout).
+ * rev_start == NULL: the pooled gradient is scattered into Q with cout * npoints float atomics (not x nsample); workspace:
+ * amc3d_local_aggregation_workspace_bytes.
+ * With rev_start (b*n + 1) / rev_edge (b*npoints*nsample), the reverse lists of idx (amc3d_group_csr; rev_edge is then
+ * required), there are no float atomics (deterministic mode).  Only the scatter into Q changes:
+ * Q[b,j,c] = the sum, over the positions (m,k) of j's list in list order (ascending m*nsample + k), of dq[b,c,m] where
+ * arg[b,c,m] == k -- dq the ReLU-masked pooled gradient; of the several k at which a padded ball-query row holds j only the
+ * one that equals arg carries it -- by sequential fp32 __fadd_rn from +0.0f (the summation order stated at
+ * amc3d_three_interpolate_grad_csr).  The five per-channel fp64 partial sums, the finalize / apply passes and both
+ * SyncBatchNorm phases are those of the atomic form.  Workspace: amc3d_local_aggregation_csr_workspace_bytes (the atomic
+ * form's plus the point-major (b,npoints,cout) copies of dq and arg that the gather reads). */
+size_t amc3d_local_aggregation_csr_workspace_bytes(int b, int cout, int n, int npoints);
+/* byte offset of Q (b,n,cout) fp32 in the workspace after either backward form (phase 0 or 1): what the order above is checked on */
+size_t amc3d_local_aggregation_workspace_q_offset(int b, int cout, int n, int npoints);
 int amc3d_local_aggregation_backward(int b, int cout, int n, int npoints, int nsample, int relu, const float *dpooled,
                                      const float *ystar, const unsigned char *arg, const float *g_pm, const int *idx,
-                                     const float *dp, const float *w_dp, const void *moments, const double *gd,
+                                     const float *dp, const float *w_dp, long ldw, const void *moments, const double *gd,
                                      const float *mean, const float *invstd, const float *gamma, const float *beta,
-                                     float *dg_cm, float *dw_dp, float *dgamma, float *dbeta, int phase, double *dsums,
-                                     const double *count, void *workspace, size_t workspace_bytes, void *stream);
+                                     const int *rev_start, const int *rev_edge, float *dg_cm, float *dw_dp, long lddw,
+                                     float *dgamma, float *dbeta, int phase, double *dsums, const double *count,
+                                     void *workspace, size_t workspace_bytes, void *stream);
+/* how many partial records per channel each producer leaves for the finalize kernels at this shape (a fixed function of the
+ * shape): counts[0] the forward statistics, [1] the pooled layer's backward scatter, [2] the atomic collapse of
+ * amc3d_grouped_conv_bn_backward, [3] its reverse-list collapse.  counts: 4 ints on the host. */
+int amc3d_local_aggregation_partial_counts(int b, int cout, int n, int npoints, int nsample, int *counts);
+/* centroids per wave of the forward's max-pool launch at this shape: 8, or 4, 2, 1 where 8 would leave the grid below 1024
+ * workgroups (a workgroup of four waves pools 4 times as many).  The launch itself uses this rule.  -1: not a shape of the layer. */
+int amc3d_local_aggregation_pool_centroids(int b, int cout, int npoints);
 
 /* ---- the same three products in bf16 compute / fp32 accumulate (mixed precision: main_AA.py:389-394 wraps model and
  * criterion in autocast; BASELINE config 5).  Tensors stay fp32 in memory; operands are rounded to bf16 as they are
@@ -727,24 +756,34 @@ int amc3d_pointwise_conv_backward_bf16(int b, int cin, int cout, long P, const f
 
 /* ---- first layer of a multi-layer SetAbstraction MLP (PointNeXt-S, sa_layers = 2; pointnext_AA.py:104-127, 164-166):
  * the same convolve-before-gather conv + BatchNorm [+ ReLU], with the activation x1 (b,cout,npoints,32) materialised for
- * the layers that follow.  forward: amc3d_pointwise_conv_forward -> g_cm, then this (statistics from the moments, one
- * gather + write pass).  backward: from dx1, ONE pass masks the ReLU, scatters into the source points (row-contiguous float
- * atomics) and accumulates BatchNorm's two sums and the dp weight gradient; dg_cm then goes to
- * amc3d_pointwise_conv_backward.  Supported: nsample == 32, cout in {8,16,32} or a multiple of 64.  Workspace:
- * amc3d_local_aggregation_workspace_bytes. */
+ * the layers that follow.  Supported: nsample == 32, cout in {8,16,32} or a multiple of 64.
+ * forward: the arguments, the two layouts of G (g_cm == NULL: g_pm holds the rows and is an input), the row strides and the
+ * SyncBatchNorm phases of amc3d_local_aggregation_forward, with x1 in place of pooled / arg / ystar: statistics from the
+ * moments, one gather + write pass (training == 0 with g_cm == NULL launches the expand kernel alone).  Workspace:
+ * amc3d_local_aggregation_workspace_bytes.
+ * backward, from dx1, in one of two forms; dg_cm then goes to amc3d_pointwise_conv_backward.
+ * rev_start == NULL: ONE pass masks the ReLU, scatters into the source points (row-contiguous float atomics) and accumulates
+ * BatchNorm's two sums and the dp weight gradient.  It needs idx; dx1 (b,cout,npoints,nsample) is channel-major
+ * (dx1_position_major must be 0) and rev_dp must be NULL.  Workspace: amc3d_local_aggregation_workspace_bytes.
+ * With the reverse lists rev_start / rev_edge of amc3d_group_csr (below) the same sums are a gather over the lists: no
+ * atomics, deterministic.  idx may be NULL.  dx1 is transposed to position-major rows in the workspace first, or, with
+ * dx1_position_major, is already (b,npoints,nsample,cout), 16-byte aligned (amc3d_sa_tail_backward writes it that way) and is
+ * read in place.  rev_dp: the stream of amc3d_group_csr_dp, or NULL.  Workspace: amc3d_grouped_conv_bn_csr_workspace_bytes. */
 int amc3d_grouped_conv_bn_supported(int cout, int nsample);
 int amc3d_grouped_conv_bn_forward(int b, int cout, int n, int npoints, int nsample, int training, int relu, float eps,
                                   float momentum, const float *g_cm, const int *idx, const float *dp, const float *w_dp,
-                                  const void *moments, const float *gamma, const float *beta, float *g_pm, float *x1,
-                                  float *mean, float *invstd, float *var_unbiased, double *gd, float *running_mean,
-                                  float *running_var, long long *num_batches_tracked, int phase, double *sums,
-                                  void *workspace, size_t workspace_bytes, void *stream);
+                                  long ldw, const void *moments, const float *gamma, const float *beta, float *g_pm,
+                                  float *x1, float *mean, float *invstd, float *var_unbiased, double *gd,
+                                  float *running_mean, float *running_var, long long *num_batches_tracked, int phase,
+                                  double *sums, void *workspace, size_t workspace_bytes, void *stream);
+size_t amc3d_grouped_conv_bn_csr_workspace_bytes(int b, int cout, int n, int npoints, int nsample);
 int amc3d_grouped_conv_bn_backward(int b, int cout, int n, int npoints, int nsample, int relu, const float *dx1,
-                                   const float *g_pm, const int *idx, const float *dp, const float *w_dp,
+                                   int dx1_position_major, const float *g_pm, const int *idx, const int *rev_start,
+                                   const int *rev_edge, const float *rev_dp, const float *dp, const float *w_dp, long ldw,
                                    const void *moments, const double *gd, const float *mean, const float *invstd,
-                                   const float *gamma, const float *beta, float *dg_cm, float *dw_dp, float *dgamma,
-                                   float *dbeta, int phase, double *dsums, const double *count, void *workspace,
-                                   size_t workspace_bytes, void *stream);
+                                   const float *gamma, const float *beta, float *dg_cm, float *dw_dp, long lddw,
+                                   float *dgamma, float *dbeta, int phase, double *dsums, const double *count,
+                                   void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- reverse adjacency of a neighbourhood query: gathers instead of float atomics in backward (csrc/csr.hip) ---------
  * The reference's grouping backward scatters with atomicAdd (group_points_gpu.cu:34-51).  The edges depend on coordinates
@@ -756,120 +795,12 @@ int amc3d_group_csr(int b, int n, int npoints, int nsample, const int *idx, int 
                     size_t workspace_bytes, void *stream);
 /* rev_dp (b*npoints*nsample, 4) fp32, 16-byte aligned: per edge of the lists, in list order, the relative position
  * dp[b, :, p] of its position p and p itself (its int32 bits in the fourth float): what the gather of
- * amc3d_grouped_conv_bn_backward_csr reads as one 16-byte stream instead of an edge id and three scattered floats.
+ * amc3d_grouped_conv_bn_backward reads as one 16-byte stream instead of an edge id and three scattered floats.
  * Coordinates only: part of the plan. */
 int amc3d_group_csr_dp(int b, int npoints, int nsample, const int *rev_edge, const float *dp, float *rev_dp, void *stream);
 /* the moments buffer of amc3d_group_moments from the lists (no scattered atomics) */
 int amc3d_group_moments_csr(int b, int n, int npoints, int nsample, const int *rev_start, const int *rev_edge,
                             const float *dp, void *moments, size_t moments_bytes, void *stream);
-/* amc3d_grouped_conv_bn_backward as a gather over the lists.  dx1 (b,cout,npoints,nsample) is transposed to position-major
- * rows in the workspace first, or, with dx1_position_major, is already (b,npoints,nsample,cout) (amc3d_sa_tail_backward
- * writes it that way) and is read in place. */
-size_t amc3d_grouped_conv_bn_csr_workspace_bytes(int b, int cout, int n, int npoints, int nsample);
-int amc3d_grouped_conv_bn_backward_csr(int b, int cout, int n, int npoints, int nsample, int relu, const float *dx1,
-                                       int dx1_position_major, const float *g_pm, const int *rev_start, const int *rev_edge,
-                                       const float *rev_dp /* amc3d_group_csr_dp, or NULL */, const float *dp, const float *w_dp, const void *moments, const double *gd, const float *mean,
-                                       const float *invstd, const float *gamma, const float *beta, float *dg_cm, float *dw_dp,
-                                       float *dgamma, float *dbeta, int phase, double *dsums, const double *count,
-                                       void *workspace, size_t workspace_bytes, void *stream);
-/* The five layer calls above with w_dp (and dw_dp) addressed at a row stride in floats (>= 3): w_dp = W, ldw = cin + 3 reads
- * the dp columns inside the layer's own (cout, cin + 3) weight, and dw_dp = dW, lddw = cin + 3 writes columns 0-2 of its gradient
- * (amc3d_pointwise_conv_backward_strided writes columns 3 onwards): no split of the weight, no join of the gradient. */
-int amc3d_local_aggregation_forward_strided(int b, int cout, int n, int npoints, int nsample, int training,
-                                            int relu, float eps, float momentum, const float *g_cm,
-                                            const int *idx, const float *dp, const float *w_dp, long ldw,
-                                            const void *moments, const float *gamma, const float *beta,
-                                            float *g_pm, float *pooled, unsigned char *arg, float *ystar,
-                                            float *mean, float *invstd, float *var_unbiased, double *gd,
-                                            float *running_mean, float *running_var,
-                                            long long *num_batches_tracked, int phase, double *sums,
-                                            void *workspace, size_t workspace_bytes, void *stream);
-int amc3d_local_aggregation_backward_strided(int b, int cout, int n, int npoints, int nsample, int relu,
-                                             const float *dpooled, const float *ystar, const unsigned char *arg,
-                                             const float *g_pm, const int *idx, const float *dp,
-                                             const float *w_dp, long ldw, const void *moments, const double *gd,
-                                             const float *mean, const float *invstd, const float *gamma,
-                                             const float *beta, float *dg_cm, float *dw_dp, long lddw,
-                                             float *dgamma, float *dbeta, int phase, double *dsums,
-                                             const double *count_dev, void *workspace, size_t workspace_bytes,
-                                             void *stream);
-int amc3d_grouped_conv_bn_forward_strided(int b, int cout, int n, int npoints, int nsample, int training,
-                                          int relu, float eps, float momentum, const float *g_cm, const int *idx,
-                                          const float *dp, const float *w_dp, long ldw, const void *moments,
-                                          const float *gamma, const float *beta, float *g_pm, float *x1,
-                                          float *mean, float *invstd, float *var_unbiased, double *gd,
-                                          float *running_mean, float *running_var, long long *num_batches_tracked,
-                                          int phase, double *sums, void *workspace, size_t workspace_bytes,
-                                          void *stream);
-/* The two strided forwards with G = W_f . f handed over as rows: g_pm (b,n,cout), 16-byte aligned, is an INPUT (written by
- * amc3d_pointwise_conv_forward_rows) and no channel-major G exists.  The statistics read the rows; their partial sums are taken
- * over a fixed partition of the b*n points in a fixed order (the same bits on every run).  training == 0 launches nothing but
- * the max-pool / expand kernel.  The forms that take g_cm are amc3d_transpose_cn followed by these. */
-int amc3d_local_aggregation_forward_rows(int b, int cout, int n, int npoints, int nsample, int training, int relu,
-                                         float eps, float momentum, const float *g_pm, const int *idx, const float *dp,
-                                         const float *w_dp, long ldw, const void *moments, const float *gamma,
-                                         const float *beta, float *pooled, unsigned char *arg, float *ystar, float *mean,
-                                         float *invstd, float *var_unbiased, double *gd, float *running_mean,
-                                         float *running_var, long long *num_batches_tracked, int phase, double *sums,
-                                         void *workspace, size_t workspace_bytes, void *stream);
-int amc3d_grouped_conv_bn_forward_rows(int b, int cout, int n, int npoints, int nsample, int training, int relu,
-                                       float eps, float momentum, const float *g_pm, const int *idx, const float *dp,
-                                       const float *w_dp, long ldw, const void *moments, const float *gamma,
-                                       const float *beta, float *x1, float *mean, float *invstd, float *var_unbiased,
-                                       double *gd, float *running_mean, float *running_var,
-                                       long long *num_batches_tracked, int phase, double *sums, void *workspace,
-                                       size_t workspace_bytes, void *stream);
-/* how many partial records per channel each producer leaves for the finalize kernels at this shape (a fixed function of the
- * shape): counts[0] the forward statistics, [1] the pooled layer's backward scatter, [2] the atomic collapse of
- * amc3d_grouped_conv_bn_backward, [3] its reverse-list collapse.  counts: 4 ints on the host. */
-int amc3d_local_aggregation_partial_counts(int b, int cout, int n, int npoints, int nsample, int *counts);
-/* centroids per wave of the forward's max-pool launch at this shape: 8, or 4, 2, 1 where 8 would leave the grid below 1024
- * workgroups (a workgroup of four waves pools 4 times as many).  The launch itself uses this rule.  -1: not a shape of the layer. */
-int amc3d_local_aggregation_pool_centroids(int b, int cout, int npoints);
-int amc3d_grouped_conv_bn_backward_strided(int b, int cout, int n, int npoints, int nsample, int relu,
-                                           const float *dx1, const float *g_pm, const int *idx, const float *dp,
-                                           const float *w_dp, long ldw, const void *moments, const double *gd,
-                                           const float *mean, const float *invstd, const float *gamma,
-                                           const float *beta, float *dg_cm, float *dw_dp, long lddw,
-                                           float *dgamma, float *dbeta, int phase, double *dsums,
-                                           const double *count_dev, void *workspace, size_t workspace_bytes,
-                                           void *stream);
-int amc3d_grouped_conv_bn_backward_csr_strided(int b, int cout, int n, int npoints, int nsample, int relu,
-                                               const float *dx1, int dx1_position_major, const float *g_pm,
-                                               const int *rev_start, const int *rev_edge, const float *rev_dp,
-                                               const float *dp, const float *w_dp, long ldw, const void *moments,
-                                               const double *gd, const float *mean, const float *invstd,
-                                               const float *gamma, const float *beta, float *dg_cm, float *dw_dp,
-                                               long lddw, float *dgamma, float *dbeta, int phase, double *dsums,
-                                               const double *count_dev, void *workspace, size_t workspace_bytes,
-                                               void *stream);
-/* amc3d_local_aggregation_backward without float atomics (deterministic mode): same arguments and outputs, plus the reverse
- * lists of idx, rev_start (b*n + 1) / rev_edge (b*npoints*nsample) of amc3d_group_csr.  Only the scatter into Q changes:
- * Q[b,j,c] = the sum, over the positions (m,k) of j's list in list order (ascending m*nsample + k), of dq[b,c,m] where
- * arg[b,c,m] == k -- dq the ReLU-masked pooled gradient; of the several k at which a padded ball-query row holds j only the
- * one that equals arg carries it -- by sequential fp32 __fadd_rn from +0.0f (the summation order stated at
- * amc3d_three_interpolate_grad_csr).  The five per-channel fp64 partial sums, the finalize / apply passes and both
- * SyncBatchNorm phases are those of the atomic form.  Workspace: amc3d_local_aggregation_csr_workspace_bytes (the atomic
- * form's plus the point-major (b,npoints,cout) copies of dq and arg that the gather reads). */
-size_t amc3d_local_aggregation_csr_workspace_bytes(int b, int cout, int n, int npoints);
-/* byte offset of Q (b,n,cout) fp32 in the workspace after either backward form (phase 0 or 1): what the order above is checked on */
-size_t amc3d_local_aggregation_workspace_q_offset(int b, int cout, int n, int npoints);
-int amc3d_local_aggregation_backward_csr(int b, int cout, int n, int npoints, int nsample, int relu, const float *dpooled,
-                                         const float *ystar, const unsigned char *arg, const float *g_pm, const int *idx,
-                                         const float *dp, const float *w_dp, const void *moments, const double *gd,
-                                         const float *mean, const float *invstd, const float *gamma, const float *beta,
-                                         const int *rev_start, const int *rev_edge, float *dg_cm, float *dw_dp,
-                                         float *dgamma, float *dbeta, int phase, double *dsums, const double *count,
-                                         void *workspace, size_t workspace_bytes, void *stream);
-int amc3d_local_aggregation_backward_csr_strided(int b, int cout, int n, int npoints, int nsample, int relu,
-                                                 const float *dpooled, const float *ystar, const unsigned char *arg,
-                                                 const float *g_pm, const int *idx, const float *dp,
-                                                 const float *w_dp, long ldw, const void *moments, const double *gd,
-                                                 const float *mean, const float *invstd, const float *gamma,
-                                                 const float *beta, const int *rev_start, const int *rev_edge,
-                                                 float *dg_cm, float *dw_dp, long lddw, float *dgamma, float *dbeta,
-                                                 int phase, double *dsums, const double *count_dev, void *workspace,
-                                                 size_t workspace_bytes, void *stream);
 
 /* ---- tail of a two-layer SetAbstraction block, recomputed instead of materialised -----------------------------
  * BN1 -> ReLU -> Conv2d 1x1 (C1 -> C2) -> BN2 [-> ReLU] -> max over the K = 32 neighbours
@@ -897,7 +828,7 @@ int amc3d_sa_tail_forward(int B, int C1, int C2, int M, int K, const float *y1, 
  * terms affine in z = W2 x1, so  dx1 = W2^T Dq q - (W2^T E W2) x1 - c  and  dW2 = Dq q x1^T - E W2 (x1 x1^T) - t (x1 1)^T
  * (csrc/sa_tail.hip): one pass over x1 with a C1 x C1 product and the Gram matrix on the MFMA and C2 rank-1 terms per centroid. */
 /* dx1 (B,C1,M,32) = gradient w.r.t. relu(bn1(y1)) -- written as (B,M,32,C1) rows when dx1_position_major
- * (C1 % 4 == 0), the layout amc3d_grouped_conv_bn_backward_csr gathers from; dw2 (C2,C1) deterministic; dgamma2, dbeta2 (C2);
+ * (C1 % 4 == 0), the layout amc3d_grouped_conv_bn_backward gathers from; dw2 (C2,C1) deterministic; dgamma2, dbeta2 (C2);
  * arg_out (B,C2,M) bytes or NULL: the neighbour each pooled gradient was routed to (what torch.max returns as
  * indices, pointnext_AA.py:166) -- the parity tests hold the routing fixed with it */
 int amc3d_sa_tail_backward(int B, int C1, int C2, int M, int K, const float *y1, const float *mean1,

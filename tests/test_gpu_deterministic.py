@@ -2,7 +2,7 @@
 floats with atomics runs, and a train step has the same bits on every run.
 
 Per kernel -- the three reverse-list gathers that stand in for the float-atomic scatters (amc3d_three_interpolate_grad_csr,
-amc3d_local_aggregation_backward_csr, amc3d_masked_refine_backward_csr) -- the summation order of include/amc3d.h is restated
+amc3d_local_aggregation_backward with lists, amc3d_masked_refine_backward_csr) -- the summation order of include/amc3d.h is restated
 on the CPU: stable argsort of the targets, numpy float32 sequential adds from +0.0, the product rounded first; the kernel must
 give those bits, and the same bits from a second call.  Against the atomic entry the bound is that of two orderings of one
 fp32 sum of k terms, |a - b| <= 2 (k + 1) 2^-24 sum|terms| (each ordering is within (k - 1) 2^-24 sum|terms| of the exact sum
@@ -158,7 +158,7 @@ def _lagg_case(C, K, M, relu, N=40, B=2, Cin=8, seed=0):
 
 
 def _lagg_backward(saved, go, relu, csr):
-    """the strided C entry the layer calls, atomic (csr None) or list form -> dg_cm, dw_dp (C,3), dgamma, dbeta, Q (B,N,C)"""
+    """the C entry the layer calls, atomic (csr None) or list form -> dg_cm, dw_dp (C,3), dgamma, dbeta, Q (B,N,C)"""
     ops, _lib, lib = _ops()
     f, w_f, w_dp, g_pm, idx, dp, moments, gamma, beta, mean, invstd, gd, ystar, arg, sums = saved
     B, Cin, N = f.shape
@@ -173,10 +173,8 @@ def _lagg_backward(saved, go, relu, csr):
     head = (B, C, N, M, K, int(relu), _p(go), _p(ystar), _p(arg), _p(g_pm), _p(idx), _p(dp), _p(w_dp), ldw, _p(moments), _p(gd),
             _p(mean), _p(invstd), _p(gamma), _p(beta))
     tail = (_p(dg), _p(dw), ldw, _p(dgamma), _p(dbeta), 0, None, None, _p(work), wb, _stream())
-    if csr:
-        _lib.check(lib.amc3d_local_aggregation_backward_csr_strided(*head, _p(csr[0]), _p(csr[1]), *tail), "lagg csr")
-    else:
-        _lib.check(lib.amc3d_local_aggregation_backward_strided(*head, *tail), "lagg atomic")
+    lists = (_p(csr[0]), _p(csr[1])) if csr else (None, None)
+    _lib.check(lib.amc3d_local_aggregation_backward(*head, *lists, *tail), "lagg csr" if csr else "lagg atomic")
     off = int(lib.amc3d_local_aggregation_workspace_q_offset(B, C, N, M))
     Q = work[off:off + 4 * B * N * C].view(torch.float32).view(B, N, C).clone()
     return dg, dw[:, :3].clone(), dgamma, dbeta, Q

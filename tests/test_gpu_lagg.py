@@ -270,3 +270,33 @@ def test_reverse_lists_moments_and_gather_backward():
     with timing.count_calls() as calls:
         x1.backward(go_pm)
     assert all(torch.equal(a, t.grad) for a, t in zip(grads[1], (fr, wr, gr, br)))
+
+
+@pytest.mark.parametrize("position_major,with_rev_dp", [(1, False), (0, True)])
+def test_grouped_conv_bn_backward_without_lists_rejects_list_arguments(position_major, with_rev_dp):
+    """amc3d_grouped_conv_bn_backward with rev_start == NULL runs the atomic collapse, which reads a channel-major dx1 and no
+    edge stream: a position-major dx1 or a rev_dp is refused before anything is launched (dg_cm keeps its fill)."""
+    import ctypes
+    from amcontrast3d_amd import _lib, ops
+    lib = _lib.load()
+    B, Cin, C, N, M, K = 1, 8, 8, 64, 16, 32
+    p, idx, dp, f, w, gamma, beta, _ = _case(B, Cin, C, N, M, K, 21, True)
+    x1 = ops.GroupedConvBN.apply(f.requires_grad_(True), dp, idx, ops.group_moments(idx, dp, N), w, gamma, beta, 1e-5, True, None)
+    f_, w_f, w_dp, g_pm, idx_, dp_, moments, gamma_, beta_, mean, invstd, gd, sums = x1.grad_fn.saved_tensors
+    dev = f.device
+    P_ = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    dx1 = torch.randn(B, C, M, K, device=dev)
+    rev_dp = torch.zeros(B * M * K, 4, device=dev)
+    dg = torch.full((B, C, N), float("nan"), device=dev)
+    ldw = w_dp.shape[1]
+    dw = torch.zeros(C, ldw, device=dev)
+    dgamma, dbeta = torch.empty(C, device=dev), torch.empty(C, device=dev)
+    wb = int(lib.amc3d_local_aggregation_workspace_bytes(B, C, N, M))
+    work = torch.empty(wb, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev), pytest.raises(RuntimeError):
+        _lib.check(lib.amc3d_grouped_conv_bn_backward(
+            B, C, N, M, K, 1, P_(dx1), position_major, P_(g_pm), P_(idx_), None, None, P_(rev_dp) if with_rev_dp else None, P_(dp_),
+            P_(w_dp), ldw, P_(moments), P_(gd), P_(mean), P_(invstd), P_(gamma_), P_(beta_), P_(dg), P_(dw), ldw, P_(dgamma),
+            P_(dbeta), 0, None, None, P_(work), wb, ops._stream(f)), "grouped_conv_bn_backward")
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(dg).all())

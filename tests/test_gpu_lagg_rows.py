@@ -240,12 +240,12 @@ def test_eval_mode_equals_the_channel_major_entries(B, Cin, C, N, M):
         ops._pw_forward(lib, False, B, Cin, C, N, f, w2[:, 3:], None, g_cm)
         pooled, ystar = torch.empty(B, C, M, device=DEV), torch.empty(B, C, M, device=DEV)
         arg = torch.empty(B, C, M, dtype=torch.uint8, device=DEV)
-        _lib.check(lib.amc3d_local_aggregation_forward_strided(
+        _lib.check(lib.amc3d_local_aggregation_forward(
             B, C, N, M, K, 0, 1, float(bn.eps), 0.0, P_(g_cm), P_(idx), P_(dp), P_(w2), Cin + 3, None, P_(bn.weight), P_(bn.bias),
             P_(g_pm), P_(pooled), P_(arg), P_(ystar), P_(bn.running_mean), P_(invstd), None, None, None, None, None, 0, None,
             None, 0, S_(f)), "old pooled entry")
         x1 = torch.empty(B, C, M, K, device=DEV)
-        _lib.check(lib.amc3d_grouped_conv_bn_forward_strided(
+        _lib.check(lib.amc3d_grouped_conv_bn_forward(
             B, C, N, M, K, 0, 1, float(bn.eps), 0.0, P_(g_cm), P_(idx), P_(dp), P_(w2), Cin + 3, None, P_(bn.weight), P_(bn.bias),
             P_(g_pm), P_(x1), P_(bn.running_mean), P_(invstd), None, None, None, None, None, 0, None, None, 0, S_(f)),
             "old expand entry")
@@ -336,7 +336,7 @@ def test_channel_major_entries_still_match_the_reference(B, Cin, C, N, M):
     with torch.cuda.device(DEV):
         ops._pw_forward(lib, False, B, Cin, C, N, f, w2[:, 3:], None, g_cm)
         x1 = torch.empty(B, C, M, K, device=DEV)
-        _lib.check(lib.amc3d_grouped_conv_bn_forward_strided(
+        _lib.check(lib.amc3d_grouped_conv_bn_forward(
             B, C, N, M, K, 1, 1, 1e-5, 0.1, P_(g_cm), P_(idx), P_(dp), P_(w2), Cin + 3, P_(mom), P_(gamma), P_(beta), P_(g_pm),
             P_(x1), P_(mean), P_(invstd), P_(var_u), P_(gd), None, None, None, 0, None, P_(work), wb, S_(f)), "old expand entry")
     ref = _reference_x1(idx, dp, f, w, gamma, beta, go4)
@@ -351,7 +351,7 @@ def test_channel_major_entries_still_match_the_reference(B, Cin, C, N, M):
     arg = torch.empty(B, C, M, dtype=torch.uint8, device=DEV)
     g_pm.fill_(float("nan"))
     with torch.cuda.device(DEV):
-        _lib.check(lib.amc3d_local_aggregation_forward_strided(
+        _lib.check(lib.amc3d_local_aggregation_forward(
             B, C, N, M, K, 1, 1, 1e-5, 0.1, P_(g_cm), P_(idx), P_(dp), P_(w2), Cin + 3, P_(mom), P_(gamma), P_(beta), P_(g_pm),
             P_(pooled), P_(arg), P_(ystar), P_(mean2), P_(invstd2), P_(var_u2), P_(gd), None, None, None, 0, None, P_(work), wb,
             S_(f)), "old pooled entry")

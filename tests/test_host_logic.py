@@ -149,6 +149,33 @@ def test_c_abi_exports_every_declared_symbol():
     assert not any("torch" in n or "c10" in n for n in names), names               # well contain the digits "c10"
 
 
+def test_c_abi_argtypes_match_the_header():
+    """A miscounted `[_vp] * n` row of _lib.SIGNATURES loads without complaint and corrupts an argument at the call: every
+    row must have the header's parameter count, a pointer type where the prototype has a `*` and the matching scalar elsewhere."""
+    from amcontrast3d_amd import _lib
+    header = open(os.path.join(ROOT, "include", "amc3d.h")).read()
+    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    header = re.sub(r"//[^\n]*", " ", header)
+    protos = dict(re.findall(r"\b(amc3d_\w+)\s*\(([^()]*)\)\s*;", header))
+    assert set(protos) == set(_lib.SIGNATURES), set(protos) ^ set(_lib.SIGNATURES)
+    scalars = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long": ctypes.c_long,
+               "size_t": ctypes.c_size_t, "long long": ctypes.c_longlong, "unsigned long long": ctypes.c_ulonglong}
+
+    def is_pointer(t):
+        return t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer)
+
+    for name, params in sorted(protos.items()):
+        params = [] if params.strip() in ("", "void") else [" ".join(p.split()) for p in params.split(",")]
+        argtypes = _lib.SIGNATURES[name][1]
+        assert len(argtypes) == len(params), (name, len(argtypes), len(params))
+        for k, (p, t) in enumerate(zip(params, argtypes)):
+            if "*" in p:
+                assert is_pointer(t), (name, k, p, t)
+            else:
+                ctype = " ".join(w for w in p.split()[:-1] if w != "const")  # the declaration without its parameter name
+                assert t is scalars[ctype], (name, k, p, t)
+
+
 def test_compat_modules_have_the_reference_entry_points():
     from amcontrast3d_amd import compat
     names = ["ball_query_wrapper", "group_points_wrapper", "group_points_grad_wrapper", "gather_points_wrapper",

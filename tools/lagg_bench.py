@@ -119,23 +119,24 @@ def backward_entry(layer, saved, csr, relu):
             wb = int(lib.amc3d_grouped_conv_bn_csr_workspace_bytes(B, C, N, M, K))
             work = torch.empty(wb, dtype=torch.uint8, device=dev)
             edge_dp = P(csr[2]) if len(csr) > 2 and csr[2] is not None else None
-            return lambda: _lib.check(lib.amc3d_grouped_conv_bn_backward_csr_strided(
-                B, C, N, M, K, int(relu), P(go), 1, P(g_pm), P(csr[0]), P(csr[1]), edge_dp, P(dp), P(w_dp), ldw, P(moments), P(gd),
-                P(mean), P(invstd), P(gamma), P(beta), P(dg), P(dw), ldw, P(dgamma), P(dbeta), 0, None, None, P(work), wb, stream()),
-                "grouped_conv_bn_backward_csr")
+            return lambda: _lib.check(lib.amc3d_grouped_conv_bn_backward(
+                B, C, N, M, K, int(relu), P(go), 1, P(g_pm), P(idx), P(csr[0]), P(csr[1]), edge_dp, P(dp), P(w_dp), ldw, P(moments),
+                P(gd), P(mean), P(invstd), P(gamma), P(beta), P(dg), P(dw), ldw, P(dgamma), P(dbeta), 0, None, None, P(work), wb,
+                stream()), "grouped_conv_bn_backward with lists")
         go = go.permute(0, 3, 1, 2).contiguous()
         wb = int(lib.amc3d_local_aggregation_workspace_bytes(B, C, N, M))
         work = torch.empty(wb, dtype=torch.uint8, device=dev)
-        return lambda: _lib.check(lib.amc3d_grouped_conv_bn_backward_strided(
-            B, C, N, M, K, int(relu), P(go), P(g_pm), P(idx), P(dp), P(w_dp), ldw, P(moments), P(gd), P(mean), P(invstd), P(gamma),
-            P(beta), P(dg), P(dw), ldw, P(dgamma), P(dbeta), 0, None, None, P(work), wb, stream()), "grouped_conv_bn_backward")
+        return lambda: _lib.check(lib.amc3d_grouped_conv_bn_backward(
+            B, C, N, M, K, int(relu), P(go), 0, P(g_pm), P(idx), None, None, None, P(dp), P(w_dp), ldw, P(moments), P(gd), P(mean),
+            P(invstd), P(gamma), P(beta), P(dg), P(dw), ldw, P(dgamma), P(dbeta), 0, None, None, P(work), wb, stream()),
+            "grouped_conv_bn_backward")
     ystar, arg = saved[12], saved[13]
     go = torch.randn(B, C, M, generator=g).to(dev)
     wb = int(lib.amc3d_local_aggregation_workspace_bytes(B, C, N, M))
     work = torch.empty(wb, dtype=torch.uint8, device=dev)
-    return lambda: _lib.check(lib.amc3d_local_aggregation_backward_strided(
+    return lambda: _lib.check(lib.amc3d_local_aggregation_backward(
         B, C, N, M, K, int(relu), P(go), P(ystar), P(arg), P(g_pm), P(idx), P(dp), P(w_dp), ldw, P(moments), P(gd), P(mean),
-        P(invstd), P(gamma), P(beta), P(dg), P(dw), ldw, P(dgamma), P(dbeta), 0, None, None, P(work), wb, stream()),
+        P(invstd), P(gamma), P(beta), None, None, P(dg), P(dw), ldw, P(dgamma), P(dbeta), 0, None, None, P(work), wb, stream()),
         "local_aggregation_backward")
 
 
