@@ -213,6 +213,9 @@ SIGNATURES = {
     "amc3d_sphere_schedule": (_i, [_i] * 6 + [ctypes.c_double] + [_vp] * 13 + [_vp, _sz, _vp]),
     "amc3d_sphere_query": (_i, [_i] * 5 + [ctypes.c_double] + [_vp] * 9 + [_vp, _sz, _vp]),
     "amc3d_sphere_tail": (_i, [_i] * 4 + [_vp] * 18 + [_vp]),
+    "amc3d_assa_aggregate_forward": (_i, [_i] * 6 + [_vp] * 5 + [_vp]),
+    "amc3d_assa_aggregate_backward": (_i, [_i] * 6 + [_vp] * 5 + [_vp]),
+    "amc3d_assa_aggregate_backward_csr": (_i, [_i] * 6 + [_vp] * 6 + [_vp]),
 }
 
 

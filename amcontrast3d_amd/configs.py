@@ -93,3 +93,53 @@ def ambiguity_args(dataset='s3dis'):
 def criterion_cfg():
     # cfgs/s3dis/default.yaml:59-61 (label_smoothing is accepted and ignored by CrossEntropyAce)
     return {'NAME': 'CrossEntropyAce', 'label_smoothing': 0.2}
+
+
+_POINTNET2 = ('pointnet++', 'pointnet++msg', 'assanet', 'assanet-l')
+
+
+def model_cfg_pointnet2(variant='pointnet++', num_classes=13, in_channels=4, dropout=0.5, radius=0.1, nsample=32, width=None,
+                        blocks=None, normalize_dp=None):
+    """BaseSeg + PointNet2Encoder / PointNet2Decoder + SegHead: the PointNet++ and ASSANet baselines of the PointNeXt
+    paper's tables.  The reference ships no YAML for them; these follow the encoder's docstring (pointnetv2.py:150-176) and
+    upstream OpenPoints' cfgs/s3dis/{pointnet++,assanet,assanet-l}.yaml as far as they can be reconstructed:
+
+      'pointnet++'     single-scale grouping, three convs per stage, widths w,w,2w / 2w,2w,4w / ... (w = 32), max pooling
+      'pointnet++msg'  two scales per stage (radii r and 2r; the second scale's middle width is 1.5 x)
+      'assanet'        ASSA blocks [2,2,2,2] of width 64, stem conv + stem aggregation, query_as_support, residuals,
+                       double_last_channel False, mean reduction, relative positions divided by the radius; a stage's
+                       output concatenates its blocks, so the width doubles per stage (2.4 M parameters with the head)
+      'assanet-l'      width 128, blocks [3,3,3,3], widths tripling per stage (115.6 M parameters, the paper's figure)
+
+    `width`, `blocks`, `radius` (doubling per stage) and `nsample` override the variant's values."""
+    if variant not in _POINTNET2:
+        raise KeyError(f"{variant!r}: one of {_POINTNET2}")
+    enc = {'NAME': 'PointNet2Encoder', 'in_channels': in_channels, 'strides': [4, 4, 4, 4], 'layers': 3, 'radius': radius,
+           'num_samples': nsample, 'sampler': 'fps', 'conv_args': {'order': 'conv-norm-act'}, 'act_args': {'act': 'relu'},
+           'norm_args': {'norm': 'bn'}}
+    if variant.startswith('assanet'):
+        large = variant.endswith('-l')
+        w = width if width is not None else (128 if large else 64)
+        enc.update({'width': w, 'mlps': None, 'blocks': list(blocks if blocks is not None else ([3] * 4 if large else [2] * 4)),
+                    'width_scaling': 3 if large else 2, 'radius_scaling': 2, 'block_radius_scaling': 1, 'use_res': True,
+                    'stem_conv': True, 'stem_aggr': True, 'query_as_support': True, 'double_last_channel': False,
+                    'aggr_args': {'NAME': 'ASSA', 'feature_type': 'assa', 'reduction': 'mean'},
+                    'group_args': {'NAME': 'ballquery', 'normalize_dp': True if normalize_dp is None else normalize_dp}})
+        dec = {'NAME': 'PointNet2Decoder', 'fp_mlps': [[w, w], [w, w], [2 * w, 2 * w], [4 * w, 4 * w]]}
+    else:
+        w = width if width is not None else 32
+        if variant == 'pointnet++':
+            mlps = [[[w << i, w << i, w << (i + 1)]] for i in range(4)]
+            enc.update({'radius': radius, 'num_samples': nsample})
+        else:
+            mlps = [[[w << i, w << i, w << (i + 1)], [w << i, (w << i) * 3 // 2, w << (i + 1)]] for i in range(4)]
+            enc.update({'radius': [[radius * 2 ** i, radius * 2 ** (i + 1)] for i in range(4)],
+                        'num_samples': [[nsample, nsample] for _ in range(4)]})
+        enc.update({'width': None, 'mlps': mlps, 'use_res': False,
+                    'aggr_args': {'NAME': 'convpool', 'feature_type': 'dp_fj', 'reduction': 'max'},
+                    'group_args': {'NAME': 'ballquery', 'normalize_dp': False if normalize_dp is None else normalize_dp}})
+        dec = {'NAME': 'PointNet2Decoder', 'fp_mlps': [[4 * w, 4 * w, 4 * w], [8 * w, 4 * w], [8 * w, 8 * w], [8 * w, 8 * w]]}
+    return copy.deepcopy({
+        'NAME': 'BaseSeg', 'encoder_args': enc, 'decoder_args': dec,
+        'cls_args': {'NAME': 'SegHead', 'num_classes': num_classes, 'in_channels': None, 'norm_args': {'norm': 'bn'},
+                     'dropout': dropout}})

@@ -2,3 +2,4 @@ from .pointnext_AA import (FeaturePropogation, InvResMLP, LocalAggregation, Poin
                            PointNextEncoder_AMContrast3D, ResBlock, SetAbstraction)
 from .pointnext_MM import PointNextDecoder_M_AMContrast3D, PointNextEncoder_M_AMContrast3D
 from .pointnext import PointNextDecoder, PointNextEncoder
+from .pointnetv2 import PointNet2Decoder, PointNet2Encoder, PointNetFPModule, PointNetSAModuleMSG

@@ -192,11 +192,14 @@ def batchnorm_act(bn, y, relu, pool=False, residual=None):
     return x
 
 
-def conv1x1(conv, x, rows_grad=False):
+def conv1x1(conv, x, rows_grad=False, library=True):
     """conv(x); a plain 1x1 convolution on a contiguous fp32 GPU tensor runs on the MFMA kernels of
     csrc/pwconv.hip (same parameters, same autograd contract), anything else on the stored torch module.
     `rows_grad`: the only consumer of x's gradient reads position-major rows (wants_rows_grad): the backward-data product
-    then stores (B,*spatial,Cin) and hands over the permuted view, where the route has that form."""
+    then stores (B,*spatial,Cin) and hands over the permuted view, where the route has that form.
+    `library=False`: never the BLAS / convolution library -- this library's own kernel also where the library measured
+    faster, so that the result does not depend on which kernel that library picks in a session (ConvPool: a max over the
+    neighbours follows, and an arg-max that flips on the last bit moves the gradients by their own size)."""
     if (type(conv) in (nn.Conv1d, nn.Conv2d, Conv1d, Conv2d) and x.is_cuda and x.dtype == torch.float32
             and conv.groups == 1 and conv.padding_mode == 'zeros'
             and all(k == 1 for k in conv.kernel_size) and all(v == 1 for v in conv.stride)
@@ -205,7 +208,7 @@ def conv1x1(conv, x, rows_grad=False):
             # use_amp (main_AA.py:389-394): bf16 operands, fp32 accumulation on the bf16 MFMA; activations, BatchNorm,
             # searches and the loss stay fp32 (tensors are never stored in bf16)
             return ops.pointwise_conv(x, conv.weight, conv.bias, True)
-        if _pw_pays(conv, x):
+        if _pw_pays(conv, x) or not library:
             return ops.pointwise_conv(x, conv.weight, conv.bias, False, rows_grad)
         if (conv.bias is None and min(conv.in_channels, conv.out_channels) >= 64 and conv.in_channels % 4 == 0
                 and torch.is_grad_enabled()):
@@ -278,7 +281,7 @@ def _pw_pays(conv, x):
     return positions >= 131072 and max(cin, cout) <= 128 or (max(cin, cout) <= 64 and positions >= 32768)
 
 
-def run_convblocks(blocks, x, pool_max=False, pre=None, activated=False, residual=None):
+def run_convblocks(blocks, x, pool_max=False, pre=None, activated=False, residual=None, library=True):
     """Evaluate a stack of conv blocks (the nn.Sequential the factories above build), optionally followed by
     the max over the last (neighbour) dimension.  Where a block is conv -> BatchNorm [-> ReLU] (conv_bn_block), the conv
     takes conv1x1's route and BatchNorm, ReLU and (for the last block) the max-pool batchnorm_act's; everything else runs
@@ -286,7 +289,8 @@ def run_convblocks(blocks, x, pool_max=False, pre=None, activated=False, residua
     `pre`: the already computed output of the first block's convolution (the fused gather+conv kernel).
     `activated`: x is the activated output of a first block evaluated elsewhere (fused_first_block); `blocks` are the rest.
     `residual`: the result is relu(stack(x) + residual) -- an InvResMLP block's `f += identity; act(f)` -- inside the last
-    block's BatchNorm kernels where that block is conv -> plain training-mode BatchNorm without activation."""
+    block's BatchNorm kernels where that block is conv -> plain training-mode BatchNorm without activation.
+    `library`: conv1x1's switch, handed to every conv of the stack."""
     mods = list(blocks)
     fused = _sa_tail_activated(mods, x, pool_max) if activated else _sa_tail(mods, pool_max, pre)
     if fused is not None:
@@ -297,14 +301,14 @@ def run_convblocks(blocks, x, pool_max=False, pre=None, activated=False, residua
         m = conv_bn_block(blk)
         if m is not None:
             conv, bn, relu = m
-            y = pre if (bi == 0 and pre is not None) else conv1x1(conv, x, bi == 0 and activated and wants_rows_grad(x))
+            y = pre if (bi == 0 and pre is not None) else conv1x1(conv, x, bi == 0 and activated and wants_rows_grad(x), library)
             x = batchnorm_act(bn, y, relu, last and pool_max, residual if last else None)
             finished = last
         else:
             assert not (bi == 0 and pre is not None), "pre needs a conv -> norm block"
             sub = list(blk) if isinstance(blk, nn.Sequential) else None
             if sub is not None and len(sub) >= 1 and isinstance(sub[0], (nn.Conv1d, nn.Conv2d)):
-                x = conv1x1(sub[0], x)
+                x = conv1x1(sub[0], x, library=library)
                 for mod in sub[1:]:
                     x = mod(x)
             else:

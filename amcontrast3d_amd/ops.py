@@ -2752,6 +2752,86 @@ def expand_parts(logits, tables):
     return voted, pred
 
 
+# ----------------------------------------------------------------------------------------------
+# separable neighbourhood aggregation of ASSA (csrc/assa.hip)
+# ----------------------------------------------------------------------------------------------
+_ASSA_REDUCTION = {"mean": 0, "avg": 0, "sum": 1, "max": 2}
+
+
+def _transpose_cn(x, B, C, n):
+    """(B,C,n) -> (B,n,C) fp32, the coalesced LDS-tiled transpose of PointMajorRows"""
+    out = torch.empty(B, n, C, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().amc3d_transpose_cn(B, C, n, _ptr(x), _ptr(out), _stream(x)), "transpose_cn")
+    return out
+
+
+class SeparableAggregation(Function):
+    """out[b, d*C + c, m] = red_k dp[b,d,m,k] * f[b,c,idx[b,m,k]] (d in 0..2; reduction 'mean' / 'sum' / 'max'): the
+    aggregation between ASSA's pre- and post-convolutions (local_aggregation.py:127-131) without a (B,C,M,K) or
+    (B,3C,M,K) tensor.  f (B,C,N) fp32, idx (B,M,K) int32, dp (B,3,M,K) fp32 -> (B,3C,M), d-major.  The gradient reaches f
+    only.  csr: group_csr(idx, N) of the geometry plan or None; read in deterministic mode only, which builds the lists in
+    backward when the plan has none (the default backward scatters with float atomics and ignores them).
+    The arithmetic and its order are fixed (include/amc3d.h; tests/assa_ref.py restates them in NumPy)."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, f, idx, dp, reduction="mean", csr=None):
+        _need_gpu(f, idx, dp)
+        _need_dtype(torch.float32, f=f, dp=dp)
+        _need_dtype(torch.int32, idx=idx)
+        if reduction not in _ASSA_REDUCTION:
+            raise NotImplementedError(f"reduction {reduction} not implemented")
+        red = _ASSA_REDUCTION[reduction]
+        f, idx, dp = f.contiguous(), idx.contiguous(), dp.contiguous()
+        B, C, N = f.shape
+        _, M, K = idx.shape
+        if idx.shape[0] != B or dp.shape != (B, 3, M, K):
+            raise ValueError(f"SeparableAggregation: f {tuple(f.shape)}, idx {tuple(idx.shape)}, dp {tuple(dp.shape)} do not fit")
+        if K > 255:
+            raise ValueError("SeparableAggregation: at most 255 neighbours per query")
+        out = torch.empty(B, 3 * C, M, dtype=torch.float32, device=f.device)
+        arg = torch.empty(B, M, 3 * C, dtype=torch.uint8, device=f.device) if red == 2 else None
+        with torch.cuda.device(f.device), timing.span("assa_aggregate", f.numel() * 8 + idx.numel() * 16 + out.numel() * 4):
+            f_pm = _transpose_cn(f, B, C, N)
+            _lib.check(_lib.load().amc3d_assa_aggregate_forward(B, C, N, M, K, red, _ptr(f_pm), _ptr(idx), _ptr(dp), _ptr(out),
+                                                                _ptr(arg) if arg is not None else None, _stream(f)),
+                       "assa_aggregate_forward")
+        ctx.assa = (idx, dp, arg, csr, red, N)
+        ctx.det = deterministic()
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_out):
+        idx, dp, arg, csr, red, N = ctx.assa
+        g = grad_out.detach().contiguous()
+        B, C3, M = g.shape
+        C, K = C3 // 3, idx.shape[-1]
+        lib = _lib.load()
+        aptr = _ptr(arg) if arg is not None else None
+        gathers = ctx.det  # default mode scatters at every shape (DESIGN 5i: the lists cost a sort the gather does not win back)
+        if gathers and csr is None:
+            csr = group_csr(idx, N)
+        df_pm = torch.empty(B, N, C, dtype=torch.float32, device=g.device)  # both entries write every element
+        with torch.cuda.device(g.device), timing.span("assa_aggregate_grad", g.numel() * 8 + idx.numel() * 16 + idx.numel() * C * 4):
+            g_pm = _transpose_cn(g, B, C3, M)
+            if gathers:
+                _lib.check(lib.amc3d_assa_aggregate_backward_csr(B, C, N, M, K, red, _ptr(g_pm), _ptr(dp), aptr, _ptr(csr[0]),
+                                                                 _ptr(csr[1]), _ptr(df_pm), _stream(g)),
+                           "assa_aggregate_backward_csr")
+            else:
+                _lib.check(lib.amc3d_assa_aggregate_backward(B, C, N, M, K, red, _ptr(g_pm), _ptr(idx), _ptr(dp), aptr,
+                                                             _ptr(df_pm), _stream(g)), "assa_aggregate_backward")
+            df = torch.empty(B, C, N, dtype=torch.float32, device=g.device)
+            _lib.check(lib.amc3d_transpose_cn(B, N, C, _ptr(df_pm), _ptr(df), _stream(g)), "transpose_cn")
+        return df, None, None, None, None
+
+
+def separable_aggregation(f, idx, dp, reduction="mean", csr=None):
+    """SeparableAggregation.apply; csr = (rev_start, rev_edge) of group_csr(idx, N) where the plan has them"""
+    return SeparableAggregation.apply(f, idx, dp, reduction, csr)
+
+
 # the offset-layout (ragged-batch) operators of the pointops surface -- furthest sampling, ball query, grouping,
 # subtraction, aggregation, interpolation -- live in offset_ops.py (ops.offset_ops.Grouping, ...): this file's BallQuery and
 # friends are the dense (B,N,.) forms of the same names

@@ -10,7 +10,8 @@ What differs from the reference's loop, with identical arithmetic per batch:
     optimizer state are restored after the warm-up -- and reused by later epochs.  Loops the graphs cannot express run
     eagerly behind pipeline.GeometryPrefetcher, as before: gradient accumulation (step_per_update > 1), use_amp with a
     GradScaler, DistributedDataParallel-wrapped models, a batch whose shape differs from the first one's,
-    cfg.graph_pipeline = False or AMC3D_EAGER_TRAIN=1;
+    cfg.graph_pipeline = False or AMC3D_EAGER_TRAIN=1; a model whose encoder is not a PointNeXt stage list (PointNet++,
+    ASSANet: has_stage_list) trains eagerly without the prefetcher -- capturing its step is the next step for those models;
   * the loss is accumulated on the device and read back once per epoch (the reference calls `loss.item()` every
     iteration, main_AA.py:419, which drains the GPU each step); `print_freq` progress lines therefore show the loss of
     the last *completed* read-back;
@@ -106,6 +107,14 @@ def _cfg(cfg, key, default=None):
     return cfg.get(key, default) if hasattr(cfg, "get") else getattr(cfg, key, default)
 
 
+def has_stage_list(model):
+    """True for the PointNeXt family, whose encoder keeps its stages as `encoder.encoder`: geometry.precompute_* and
+    GraphPipeline walk that list.  A model without it (PointNet2Encoder: PointNet++, ASSANet) plans its geometry inside
+    its own forward and trains in the eager loop, without the GeometryPrefetcher."""
+    m = model.module if hasattr(model, "module") else model
+    return hasattr(getattr(m, "encoder", None), "encoder")
+
+
 def _graph_pipeline(model, criterion, optimizer, cfg, step_loss, first, clip, extras=0):
     """the GraphPipeline of this (model, optimizer, criterion, batch shape), built from batch `first` at first use"""
     import torch.distributed as tdist
@@ -169,7 +178,8 @@ def _run_epoch_body(model, train_loader, criterion, optimizer, scheduler, scaler
     n_batches = 0
     graphs_ok = (not use_amp and cfg.step_per_update == 1 and _cfg(cfg, "graph_pipeline", True)
                  and not os.environ.get("AMC3D_EAGER_TRAIN")
-                 and not isinstance(model, (torch.nn.parallel.DistributedDataParallel, torch.nn.DataParallel)))
+                 and not isinstance(model, (torch.nn.parallel.DistributedDataParallel, torch.nn.DataParallel))
+                 and has_stage_list(model))
     if graphs_ok:
         first = next(batches, None)
         if first is None:
@@ -218,7 +228,7 @@ def _run_epoch_body(model, train_loader, criterion, optimizer, scheduler, scaler
             # (in place: GraphPipeline.run points .grad at the same tensors again in the next epoch either way)
             optimizer.zero_grad(set_to_none=False)
         batches = iter(odd)
-    elif prefetch_depth > 0 and not use_amp:
+    elif prefetch_depth > 0 and not use_amp and has_stage_list(model):
         batches = GeometryPrefetcher(batches, model, head, cfg.num_classes, cfg.ignore_index, _cfg(cfg, "ambiguity_args"),
                                      depth=prefetch_depth)
     num_iter = 0

@@ -1189,6 +1189,34 @@ int amc3d_sphere_tail(int clouds, int spheres, int num_points, int gravity_dim, 
                       const double *pad_u, long long *input_inds, int *mask, float *pos, float *x, long long *y,
                       float *heights, void *stream);
 
+/* ---- separable neighbourhood aggregation (ASSA, models/layers/local_aggregation.py:127-131) ----------------------
+ * out[b, d*c + ch, m] = red over k of dp[b,d,m,k] * f[b,ch,idx[b,m,k]], d in 0..2, without the (b,c,npoints,nsample) and
+ * (b,3c,npoints,nsample) tensors of the reference's expand / multiply / reduce.  reduction: 0 mean, 1 sum, 2 max.
+ * f_pm (b,n,c): the POINT-major features (amc3d_transpose_cn), idx (b,npoints,nsample) int32 into the n support points,
+ * dp (b,3,npoints,nsample); out (b,3c,npoints), d-major as the reference's view lays it out.  nsample <= 255.
+ * ARITHMETIC (part of the contract): every product is one __fmul_rn; sum adds them by sequential __fadd_rn in ascending k
+ * from +0.0f; mean is that sum through one __fdiv_rn by (float)nsample; max keeps the FIRST maximum in k (a later product
+ * replaces the kept one only when it compares greater, or when it is the first NaN: NaN propagates as in torch.max) and
+ * writes its k to arg_pm (b,npoints,3c) bytes, point-major
+ * (required for max, ignored otherwise).  An index outside [0,n) is clamped into it.  No workspace.
+ * Backward, to f only: g_pm (b,npoints,3c) is the POINT-major gradient of out, df_pm (b,n,c) the point-major gradient of f.
+ * The term of edge (m,k) for channel ch, with s = __fdiv_rn(1, nsample) for mean and 1 otherwise:
+ *   mean, sum: __fmul_rn(s, (dp0*g[m,0*c+ch] + dp1*g[m,1*c+ch]) + dp2*g[m,2*c+ch])   (products and sums rounded one by one)
+ *   max:       the same sum with the product of d replaced by +0.0f unless arg_pm[b,m,d*c+ch] == k, s = 1.
+ * amc3d_assa_aggregate_backward zero-fills df_pm itself and scatters the terms with float atomics (one row segment of c
+ * floats per edge; max: only edges some d selected); an index outside [0,n) is skipped.
+ * amc3d_assa_aggregate_backward_csr gathers over the reverse lists rev_start (b*n + 1) / rev_edge (b*npoints*nsample) of
+ * amc3d_group_csr(b, n, npoints, nsample, idx, ...) under the SUMMATION ORDER stated at
+ * amc3d_three_interpolate_grad_csr (list order, sequential __fadd_rn from +0.0f) and writes every element of df_pm:
+ * exactly +0.0f for a support point nobody gathers.  Neither allocates, synchronises or reads back. */
+int amc3d_assa_aggregate_forward(int b, int c, int n, int npoints, int nsample, int reduction, const float *f_pm,
+                                 const int *idx, const float *dp, float *out, unsigned char *arg_pm, void *stream);
+int amc3d_assa_aggregate_backward(int b, int c, int n, int npoints, int nsample, int reduction, const float *g_pm,
+                                  const int *idx, const float *dp, const unsigned char *arg_pm, float *df_pm, void *stream);
+int amc3d_assa_aggregate_backward_csr(int b, int c, int n, int npoints, int nsample, int reduction, const float *g_pm,
+                                      const float *dp, const unsigned char *arg_pm, const int *rev_start,
+                                      const int *rev_edge, float *df_pm, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
