@@ -126,6 +126,8 @@ SIGNATURES = {
     "amc3d_bn_sigmoid_forward": (_i, [_i, _i, _l, _f, _f] + [_vp] * 10 + [_vp, _sz, _vp]),
     "amc3d_bn_sigmoid_backward": (_i, [_i, _i, _l] + [_vp] * 10 + [_vp, _sz, _vp]),
     "amc3d_bias_grad": (_i, [_i, _i, _l, _vp, _vp, _vp]),
+    "amc3d_pointwise_conv_cloud_term_forward": (_i, [_i, _i, _i, _l, _vp, _vp, _l, _vp, _vp, _vp, _sz, _vp]),
+    "amc3d_cloud_term_grad": (_i, [_i, _i, _l, _vp, _vp, _vp]),
     "amc3d_sa_residual_forward": (_i, [_i, _i, _i, _i, _i] + [_vp] * 8),
     "amc3d_sa_residual_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "amc3d_sa_residual_backward": (_i, [_i, _i, _i, _i, _i] + [_vp] * 11 + [_sz, _vp]),

@@ -95,6 +95,70 @@ def criterion_cfg():
     return {'NAME': 'CrossEntropyAce', 'label_smoothing': 0.2}
 
 
+SHAPENETPART_NUM_PARTS = [4, 2, 2, 4, 4, 3, 3, 2, 4, 2, 6, 2, 3, 3, 3, 3]  # parts per shape category, 50 in all
+_PARTSEG = ('pointnext-s', 'pointnet++', 'assanet')
+
+
+def cls2partembed(num_parts=SHAPENETPART_NUM_PARTS):
+    """(shape categories, parts) fp32 tensor: row s marks the parts of category s, which are numbered consecutively over the
+    categories (ShapeNetPart's layout) -- what `cls_map: pointnext / pointnext1` index with the shape label"""
+    import torch
+    table = torch.zeros(len(num_parts), sum(num_parts))
+    at = 0
+    for s, n in enumerate(num_parts):
+        table[s, at:at + n] = 1
+        at += n
+    return table
+
+
+def model_cfg_partseg(variant='pointnext-s', num_classes=50, in_channels=7, dropout=0.5, radius=0.1, nsample=32, width=None,
+                      cls_map='curvenet', decoder_blocks=None, head='SegHead', global_feat='max,avg', part_table=None):
+    """BasePartSeg: part segmentation with the shape category as a second input.  The reference ships no YAML for it; these
+    follow upstream OpenPoints' cfgs/shapenetpart as far as they can be reconstructed:
+
+      'pointnext-s'  PointNextEncoder at strides [1,2,2,2,2] (many small clouds), sa_layers 3, sa_use_res, radius_scaling 2.5,
+                     width 32, seven input channels (position, normal, height) + PointNextPartDecoder with `cls_map`
+                     ('curvenet' upstream; 'pointnet2', 'pointnext', 'pointnext1') and `decoder_blocks` (default [1,1,1,1])
+      'pointnet++'   PointNet2Encoder (single-scale, as model_cfg_pointnet2) + PointNet2PartDecoder
+      'assanet'      the ASSANet encoder with its widths written out as `mlps` + PointNet2PartDecoder.  (Written out because
+                     that decoder repeats the encoder's channel arithmetic from the shared arguments, and for
+                     double_last_channel False the reference's two copies scale the width at different places.)
+
+    head: 'SegHead' (num_classes part logits; train with CrossEntropy) or 'MultiSegHead' (one head per shape category; train
+    with MultiShapeCrossEntropy).  part_table: the (16, 50) tensor of cls2partembed() for the 'pointnext*' maps (default: that)."""
+    if variant not in _PARTSEG:
+        raise KeyError(f"{variant!r}: one of {_PARTSEG}")
+    if head == 'MultiSegHead':
+        cls_args = {'NAME': 'MultiSegHead', 'num_classes': num_classes, 'in_channels': None, 'norm_args': {'norm': 'bn'},
+                    'dropout': dropout}
+    else:
+        cls_args = {'NAME': 'SegHead', 'num_classes': num_classes, 'in_channels': None, 'norm_args': {'norm': 'bn'},
+                    'dropout': dropout}
+        if global_feat is not None:
+            cls_args['global_feat'] = global_feat
+    if variant == 'pointnext-s':
+        enc = {'NAME': 'PointNextEncoder', 'blocks': [1, 1, 1, 1, 1], 'strides': [1, 2, 2, 2, 2], 'sa_layers': 3,
+               'sa_use_res': True, 'width': width if width is not None else 32, 'in_channels': in_channels, 'expansion': 4,
+               'radius': radius, 'radius_scaling': 2.5, 'nsample': nsample,
+               'aggr_args': {'feature_type': 'dp_fj', 'reduction': 'max'},
+               'group_args': {'NAME': 'ballquery', 'normalize_dp': True}, 'conv_args': {'order': 'conv-norm-act'},
+               'act_args': {'act': 'relu'}, 'norm_args': {'norm': 'bn'}}
+        dec = {'NAME': 'PointNextPartDecoder', 'cls_map': cls_map}
+        if decoder_blocks is not None:
+            dec['decoder_blocks'] = list(decoder_blocks)
+        if cls_map in ('pointnext', 'pointnext1'):
+            dec['cls2partembed'] = part_table if part_table is not None else cls2partembed()
+    else:
+        base = model_cfg_pointnet2(variant, num_classes=num_classes, in_channels=in_channels, dropout=dropout, radius=radius,
+                                   nsample=nsample, width=width)
+        enc, dec = base['encoder_args'], base['decoder_args']
+        dec['NAME'] = 'PointNet2PartDecoder'
+        if variant == 'assanet':
+            w = enc['width']
+            enc['mlps'] = [[[w << i] * 3 for _ in range(b)] for i, b in enumerate(enc['blocks'])]
+    return copy.deepcopy({'NAME': 'BasePartSeg', 'encoder_args': enc, 'decoder_args': dec, 'cls_args': cls_args})
+
+
 _POINTNET2 = ('pointnet++', 'pointnet++msg', 'assanet', 'assanet-l')
 
 

@@ -33,7 +33,9 @@ int reduce_partials_rows(int rows, int cols, long ld, int nparts, const float *p
 // Y[b][m][p] = sum_k A(m,k) X[b][k][p] (+ bias[m]),  A(m,k) = a[m*sam + k*sak]
 // pm != 0: Y is written as position-major rows Y[b][p][m] (no bias): a lane holds four consecutive channels of its position per
 // (r >> 2) group -- one 16-byte store when pm == 2 (M % 4 == 0, aligned base), four 4-byte stores otherwise
-template <int NCT>
+// CT: `bias` is a per-cloud term (gridDim.z, M) instead of one row: the workgroup of cloud blockIdx.z adds its own row (a
+// workgroup's tile lies inside one cloud -- the cloud is the grid's z axis -- so no tile mixes two rows)
+template <int NCT, bool CT = false>
 __global__ __launch_bounds__(256) void pw_gemm_kernel(int M, int K, long P, const float *__restrict__ a, long sam,
                                                       long sak, const float *__restrict__ bias,
                                                       const float *__restrict__ x, float *__restrict__ y, int vec, int pm)
@@ -123,7 +125,11 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(int M, int K, long P, cons
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int m = m0 + c * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-                if (m < M) Y[(size_t)m * P + p] = bias ? acc[c][r] + bias[m] : acc[c][r];
+                if constexpr (CT) {
+                    if (m < M) Y[(size_t)m * P + p] = acc[c][r] + bias[(size_t)blockIdx.z * M + m];
+                } else {
+                    if (m < M) Y[(size_t)m * P + p] = bias ? acc[c][r] + bias[m] : acc[c][r];
+                }
             }
     }
 }
@@ -282,6 +288,14 @@ __global__ __launch_bounds__(1024) void pw_bias_grad_kernel(int nb, int C, long 
     }
 }
 
+// y[b][m][p] += c[b][m]: the per-cloud term behind the 128 x 128-tile GEMM, which -- like its bias -- adds in a pass of its own
+__global__ __launch_bounds__(256) void pw_cloud_term_add_kernel(long total, long P, int M, const float *__restrict__ c,
+                                                                float *__restrict__ y)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < total) y[(size_t)blockIdx.y * total + i] += c[(size_t)blockIdx.y * M + i / P];
+}
+
 struct PwSplit {
     int tiles_per_cloud, ntiles, tiles_per_wg, groups, mchunks, kchunks, nct, nit;
 };
@@ -332,6 +346,15 @@ static void launch_pw_wgrad(const PwSplit &s, int M, int K, long P, const float 
     const int vec = (P % 4 == 0) && (((uintptr_t)x & 15) == 0) && (((uintptr_t)dy & 15) == 0);
     hipLaunchKernelGGL((pw_wgrad_kernel<NCT, NIT>), dim3(s.groups, s.mchunks, s.kchunks), dim3(256), lds, stream, M, K, P,
                        s.tiles_per_cloud, s.ntiles, s.tiles_per_wg, dy, x, partial, vec);
+}
+
+template <int NCT>
+static void launch_pw_gemm_cloud_term(int b, int M, int K, long P, const float *w, long ldw, const float *c, const float *x,
+                                      float *y, hipStream_t stream)
+{
+    const int vec = (P % 4 == 0) && (((uintptr_t)x & 15) == 0);
+    hipLaunchKernelGGL((pw_gemm_kernel<NCT, true>), dim3(div_up(P, PW_TP), div_up(M, NCT * 32), b), dim3(256), 0, stream, M, K, P,
+                       w, ldw, 1L, c, x, y, vec, 0);
 }
 
 // gemm.hip: the MFMA-bound variant for layers with >= 64 channels on both sides
@@ -503,6 +526,65 @@ AMC_API int amc3d_bias_grad(int b, int c, long P, const float *dy, float *dbias,
     const int vec = (P % 4 == 0) && (((uintptr_t)dy & 15) == 0);
     hipLaunchKernelGGL(pw_bias_grad_kernel, dim3(c), dim3(1024), 0, (hipStream_t)stream, b, c, P, dy, dbias, vec);
     return launch_status("amc3d_bias_grad");
+}
+
+// ---- pointwise conv with a per-cloud additive term -----------------------------------------------------------------------
+// y (b,cout,P) = weight (cout,cin; row stride ldw) . x (b,cin,P) + cloud_term (b,cout) broadcast along P: the first
+// FeaturePropagation conv of the part-segmentation decoders, whose class-conditioned input channels are constant along the
+// points of a cloud (pointnext.py:628-663, pointnetv2.py:498-511), so that their product with the weight is one Cout-vector
+// per cloud.  Route, accumulators and sums of amc3d_pointwise_conv_forward_strided without a bias; the term is added in the
+// streaming kernel's epilogue, and in a pass of its own behind the 128 x 128-tile GEMM (as that route adds a bias).
+// (a launch puts the cloud on the grid's z axis: more than 65535 clouds go in runs of 65535, each with its own rows of the term)
+static int cloud_term_run(int b, int cin, int cout, long P, const float *x, const float *weight, long ldw, const float *cloud_term,
+                          float *y, void *workspace, size_t workspace_bytes, bool whole, hipStream_t s)
+{
+    const char *what = "amc3d_pointwise_conv_cloud_term_forward: bad argument";
+    if (pw_forward_deep(b, cin, cout, P, false)) {
+        const size_t need = gemm_conv_forward_workspace_bytes(b, cin, cout, P);
+        const bool have = workspace && workspace_bytes >= need;
+        // the whole batch in one run: the K split of amc3d_pointwise_conv_forward_strided, so its scratch is required; a run
+        // of a longer batch splits K only where the caller's scratch (sized for the whole batch) happens to hold it
+        if (need && !have && whole) return bad_arg("amc3d_pointwise_conv_cloud_term_forward: workspace too small");
+        if (int st = gemm_conv_forward(b, cin, cout, P, x, weight, ldw, nullptr, y, 0, (need && have) ? (float *)workspace : nullptr, s))
+            return st;
+        const long total = (long)cout * P;
+        hipLaunchKernelGGL(pw_cloud_term_add_kernel, dim3(div_up(total, 256), b), dim3(256), 0, s, total, P, cout, cloud_term, y);
+        return launch_status(what);
+    }
+    if (cout <= 32) launch_pw_gemm_cloud_term<1>(b, cout, cin, P, weight, ldw, cloud_term, x, y, s);
+    else if (cout <= 64) launch_pw_gemm_cloud_term<2>(b, cout, cin, P, weight, ldw, cloud_term, x, y, s);
+    else if (cout <= 96) launch_pw_gemm_cloud_term<3>(b, cout, cin, P, weight, ldw, cloud_term, x, y, s);
+    else launch_pw_gemm_cloud_term<4>(b, cout, cin, P, weight, ldw, cloud_term, x, y, s);
+    return launch_status(what);
+}
+
+AMC_API int amc3d_pointwise_conv_cloud_term_forward(int b, int cin, int cout, long P, const float *x, const float *weight,
+                                                    long ldw, const float *cloud_term, float *y, void *workspace,
+                                                    size_t workspace_bytes, void *stream)
+{
+    if (b <= 0 || P <= 0 || cout <= 0) return 0;
+    if (cin <= 0 || !x || !weight || !y || !cloud_term || ldw < cin)
+        return bad_arg("amc3d_pointwise_conv_cloud_term_forward: bad argument");
+    constexpr int RUN = 65535;
+    for (int b0 = 0; b0 < b; b0 += RUN) {
+        const int nb = b - b0 < RUN ? b - b0 : RUN;
+        if (int st = cloud_term_run(nb, cin, cout, P, x + (size_t)b0 * cin * P, weight, ldw, cloud_term + (size_t)b0 * cout,
+                                    y + (size_t)b0 * cout * P, workspace, workspace_bytes, b <= RUN, (hipStream_t)stream))
+            return st;
+    }
+    return 0;
+}
+
+// dterm (b,cout) = sum_p dy (b,cout,P): the gradient of the per-cloud term, one row per (cloud, channel) on the bias-gradient
+// kernel with b * cout rows of one cloud each -- 1024 threads per row whatever the shape, lane sums, then waves, in a fixed
+// order: no float atomics, the same bits on every run
+AMC_API int amc3d_cloud_term_grad(int b, int cout, long P, const float *dy, float *dterm, void *stream)
+{
+    if (b <= 0 || cout <= 0) return 0;
+    if (P < 0 || !dterm || (!dy && P > 0) || (long)b * cout > 0x7fffffffL) return bad_arg("amc3d_cloud_term_grad: bad argument");
+    const int vec = (P % 4 == 0) && (((uintptr_t)dy & 15) == 0);
+    hipLaunchKernelGGL(pw_bias_grad_kernel, dim3(b * cout), dim3(1024), 0, (hipStream_t)stream, 1, b * cout, P, dy, dterm, vec);
+    return launch_status("amc3d_cloud_term_grad");
 }
 
 // ---- a 1x1-conv weight cut into two column blocks, and the two gradient blocks joined again, one launch each ------------

@@ -1,10 +1,10 @@
 """PointNet++ (single- and multi-scale grouping) and ASSANet backbones on the gfx950 kernels.
 
 API mirror of models/backbone/pointnetv2.py: ``PointNetSAModuleMSG`` (:18-100), ``PointNetFPModule`` (:103-146),
-``PointNet2Encoder`` (:149-344) and ``PointNet2Decoder`` (:347-380), the last two in the ``MODELS`` registry, with the
-reference's constructor arguments, channel arithmetic, attribute names and module nesting (state-dict keys).  ASSANet is the
-same encoder with ``aggr_args.NAME: 'ASSA'``, ``stem_conv``, ``stem_aggr``, ``query_as_support``, ``use_res`` and
-``double_last_channel: False``.  ``PointNet2PartDecoder`` (:383-511) is not built.
+``PointNet2Encoder`` (:149-344), ``PointNet2Decoder`` (:347-380) and ``PointNet2PartDecoder`` (:383-511), the last three in the
+``MODELS`` registry, with the reference's constructor arguments, channel arithmetic, attribute names and module nesting
+(state-dict keys).  ASSANet is the same encoder with ``aggr_args.NAME: 'ASSA'``, ``stem_conv``, ``stem_aggr``,
+``query_as_support``, ``use_res`` and ``double_last_channel: False``.
 
 Geometry / feature split as in the PointNeXt blocks: every module has a coordinate-only ``plan*`` method and a forward that
 consumes the plan (``geom``) or builds it.  ``PointNet2Encoder.plan_geometry(p0)`` returns the stem's plan and, per SA module,
@@ -20,8 +20,8 @@ import torch.nn as nn
 
 from amcontrast3d_amd.geometry import plan_key
 from ..build import MODELS
-from ..layers import (LocalAggregation, create_convblock1d, feature_propagation_first_block, furthest_point_sample,
-                      random_sample, run_convblocks, three_interpolate)
+from ..layers import (LocalAggregation, create_convblock1d, expand_cloud_channels, feature_propagation_first_block,
+                      furthest_point_sample, random_sample, run_convblocks, three_interpolate)
 
 
 class PointNetSAModuleMSG(nn.Module):
@@ -117,7 +117,18 @@ class PointNetFPModule(nn.Module):
         from .pointnext_blocks import FeaturePropogation
         return FeaturePropogation.plan(unknown, known)
 
-    def forward(self, unknown, known, unknow_feats, known_feats, geom=None):
+    def forward(self, unknown, known, unknow_feats, known_feats, geom=None, cloud=None):
+        """`cloud`: e (B,E), channels constant along a cloud's points that the reference concatenates in front of
+        unknow_feats (PointNet2PartDecoder's one-hot shape category): a per-cloud term of the first conv where the block has
+        the form for it (cloud_term_route), expanded and concatenated otherwise."""
+        if cloud is not None:
+            if known is not None and len(self.convs) and unknow_feats is not None:
+                if geom is None:
+                    geom = self.plan(unknown, known)
+                first = feature_propagation_first_block(self.convs[0], unknow_feats, known_feats, geom, (cloud, cloud.shape[1]))
+                if first is not None:
+                    return run_convblocks(list(self.convs)[1:], first)
+            unknow_feats = expand_cloud_channels(cloud, unknow_feats)
         if known is None:
             up = known_feats.expand(*known_feats.size()[0:2], unknown.size(1))
         else:
@@ -301,4 +312,84 @@ class PointNet2Decoder(nn.Module):
         for i in range(-1, -(n + 1), -1):
             l_features[i - 1] = self.FP_modules[i](l_xyz[i - 1], l_xyz[i], l_features[i - 1], l_features[i],
                                                    geom=None if geom is None else geom[n + i])
+        return l_features[0]
+
+
+def shape_one_hot(cls_label, num_classes, device):
+    """(B, num_classes) fp32 one-hot rows of the shape categories cls_label (B,1) (or (B,)) int64"""
+    one_hot = torch.zeros((cls_label.shape[0], num_classes), device=device)
+    return one_hot.scatter_(1, cls_label.reshape(-1, 1).to(device), 1)
+
+
+@MODELS.register_module()
+class PointNet2PartDecoder(nn.Module):
+    """Part-segmentation decoder of PointNet++ (pointnetv2.py:383-511): PointNet2Decoder's feature propagation, with the
+    16-way one-hot of the shape category in front of the input features at the finest level.  It is built from the encoder's
+    constructor arguments and repeats its channel arithmetic (as there: double_last_channel defaults to False, and without
+    it the width is scaled BEFORE a stage's list is made).  The one-hot channels are constant along a cloud: FP_modules[0]
+    takes them as a per-cloud term of its first conv (PointNetFPModule.forward, `cloud`)."""
+
+    def __init__(self, in_channels: int, radius, num_samples, group_args: dict, conv_args: dict, norm_args: dict, act_args: dict,
+                 mlps=None, blocks: Optional[List] = None, width: Optional[int] = None, strides=[4, 4, 4, 4], layers=3,
+                 fp_mlps=None, decoder_layers=1, decocder_aggr_args=None, width_scaling=2, radius_scaling=2, nsample_scaling=1,
+                 use_res=False, stem_conv=False, double_last_channel=False, **kwargs):
+        super().__init__()
+        if kwargs:
+            logging.warning(f"kwargs: {kwargs} are not used in {__class__.__name__}")
+        stages = len(strides)
+        self.strides = strides
+        self.blocks = blocks if mlps is None else [len(mlp) for mlp in mlps]
+        self.radius = self._to_full_list(radius, self.blocks, param_scaling=radius_scaling)
+        self.num_samples = self._to_full_list(num_samples, self.blocks, param_scaling=nsample_scaling)
+        if stem_conv:
+            in_channels = width
+        if mlps is None:
+            assert width is not None
+            assert layers is not None
+            assert strides is not None
+            mlps = []
+            for i in range(stages):
+                if not double_last_channel:
+                    width = width * width_scaling if strides[i] > 1 else width
+                    mlps.append([[width] * layers] * self.blocks[i])
+                else:
+                    first = [width] * (layers - 1)
+                    width = width * 2 if strides[i] > 1 else width
+                    first += [width]
+                    mlps.append([first] + [[width] * layers] * (self.blocks[i] - 1))
+            logging.info(f'channels is modified to {mlps}')
+        self.mlps = mlps
+
+        skip_channel_list = [in_channels]
+        for k in range(stages):
+            channel_out = sum(mlp[-1] for mlp in mlps[k])  # the scales are concatenated
+            skip_channel_list.append(channel_out)
+            in_channels = channel_out
+
+        self.FP_modules = nn.ModuleList()
+        if fp_mlps is None:
+            fp_mlps = [[mlps[0][0][0]] * (decoder_layers + 1)]
+            fp_mlps += [[c] * (decoder_layers + 1) for c in skip_channel_list[1:-1]]
+        self.num_shape_classes = 16
+        skip_channel_list[0] += self.num_shape_classes
+        for k in range(len(fp_mlps)):
+            pre_channel = fp_mlps[k + 1][-1] if k + 1 < len(fp_mlps) else skip_channel_list[-1]
+            self.FP_modules.append(PointNetFPModule([pre_channel + skip_channel_list[k]] + fp_mlps[k]))
+        self.out_channels = fp_mlps[0][-1]
+
+    _to_full_list = PointNet2Encoder._to_full_list  # reads self.strides only; pads the caller's lists in place as there
+
+    @torch.no_grad()
+    def plan_geometry(self, l_xyz):
+        """3-NN indices / weights of every level: entry i serves FP_modules[i] (fine cloud l_xyz[i], coarse l_xyz[i + 1])"""
+        return [PointNetFPModule.plan(l_xyz[i], l_xyz[i + 1]) for i in range(len(self.FP_modules))]
+
+    def forward(self, l_xyz, l_features, cls_label, geom=None):
+        n = len(self.FP_modules)
+        for i in range(-1, -n, -1):
+            l_features[i - 1] = self.FP_modules[i](l_xyz[i - 1], l_xyz[i], l_features[i - 1], l_features[i],
+                                                   geom=None if geom is None else geom[n + i])
+        one_hot = shape_one_hot(cls_label, self.num_shape_classes, l_xyz[0].device)
+        l_features[0] = self.FP_modules[0](l_xyz[0], l_xyz[1], l_features[0], l_features[1],
+                                           geom=None if geom is None else geom[0], cloud=one_hot)
         return l_features[0]

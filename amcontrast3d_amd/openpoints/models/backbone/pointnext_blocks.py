@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from ..layers import (CHANNEL_MAP, create_act, create_convblock1d, create_convblock2d, create_grouper,
-                      feature_propagation_first_block,
+                      expand_cloud_channels, feature_propagation_first_block,
                       furthest_point_sample, fused_first_block, fused_first_conv, fused_local_aggregation,
                       get_aggregation_feautres,
                       random_sample, run_convblocks,
@@ -270,7 +270,10 @@ class FeaturePropogation(nn.Module):
             g['csr'] = ops.group_csr(idx, p2.shape[1])  # the interpolation's backward gathers over these (no float atomics)
         return g
 
-    def forward(self, pf1, pf2=None, geom=None):
+    def forward(self, pf1, pf2=None, geom=None, cloud=None):
+        """`cloud`: e (B,E), channels constant along the points of a cloud that the reference concatenates in front of f1
+        (the part decoder's shape-category embedding).  Taken as a per-cloud term of the first conv where the block has the
+        form for it (blocks.cloud_term_route), expanded and concatenated otherwise."""
         if pf2 is None:  # global branch (not used by the segmentation decoder)
             _, f = pf1
             g = self.linear2(self.pool(f))
@@ -279,6 +282,12 @@ class FeaturePropogation(nn.Module):
         p2, f2 = pf2
         if geom is None:
             geom = self.plan(p1, p2)
+        if cloud is not None:
+            first = (feature_propagation_first_block(self.convs[0], f1, f2, geom, (cloud, cloud.shape[1]))
+                     if len(self.convs) else None)
+            if first is not None:
+                return run_convblocks(list(self.convs)[1:], first)
+            f1 = expand_cloud_channels(cloud, f1)
         first = feature_propagation_first_block(self.convs[0], f1, f2, geom) if len(self.convs) else None
         if first is not None:  # the first conv on both branches before the interpolation: no concatenated tensor
             return run_convblocks(list(self.convs)[1:], first)

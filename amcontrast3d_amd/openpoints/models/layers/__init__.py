@@ -1,5 +1,5 @@
-from .blocks import (CHANNEL_MAP, Conv1d, Conv2d, create_act, create_convblock1d, create_convblock2d,
-                     create_norm, feature_propagation_first_block, fused_first_block, fused_first_conv,
+from .blocks import (CHANNEL_MAP, Conv1d, Conv2d, cloud_term_form, cloud_term_route, create_act, create_convblock1d, create_convblock2d,
+                     create_norm, expand_cloud_channels, feature_propagation_first_block, fused_first_block, fused_first_conv,
                      fused_local_aggregation, run_convblocks)
 from .knn import knn_point, KNN, DenseDilated, DilatedKNN
 from .group import (ball_query, create_grouper, gather_operation, get_aggregation_feautres,

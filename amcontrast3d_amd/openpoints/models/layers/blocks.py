@@ -238,13 +238,71 @@ def conv1x1_weight(x, w):
     return ops.pointwise_conv(x, w3, None)
 
 
-def feature_propagation_first_block(blk, f1, f2, geom):
+def cloud_term_form(blk, f1, f2, e):
+    """True when the first FeaturePropagation block `blk` CAN take its class-conditioned input channels e (B,E) -- constant
+    along the points of a cloud -- as a per-cloud additive term: Conv1d -> BatchNorm1d -> ReLU without bias over
+    [e ; f1 ; up(f2)], fp32 tensors on the GPU.  Pure inspection of the module and of shapes / dtypes / devices: launches
+    nothing and moves no statistics."""
+    m = conv_bn_block(blk)
+    return not (m is None or m[2] is None or type(m[0]) not in (nn.Conv1d, Conv1d) or m[0].bias is not None or f1 is None
+                or f1.dim() != 3 or e.dim() != 2 or not (f1.is_cuda and f2.is_cuda and e.is_cuda)
+                or any(t.dtype != torch.float32 for t in (f1, f2, e, m[0].weight))
+                or m[0].in_channels != e.shape[1] + f1.shape[1] + f2.shape[1])
+
+
+def cloud_term_route(blk, f1, f2, e):
+    """'cloud_term' when the block has the form for the per-cloud term (cloud_term_form) AND the term pays at its shape;
+    'composition' for anything else: the caller then expands e along the points and concatenates, as the reference does.
+    Like cloud_term_form it launches nothing.
+
+    Shape dispatch (tools/cloud_term_bench.py): the term saves E channels of concatenation forward and of dx
+    backward, and costs one more pass over dy (Cout channels) for its gradient plus a handful of small launches.  The rule
+    is E >= 32 or 2 E >= Cout: of the 30 measured shapes the term is behind forward + backward exactly where E = 16 stands
+    in front of 64 or 128 output channels (by 0.3-12 %), and one more time by 1.1 % (E = 32, Cout = 64 at 32 x 2048).  The
+    boundary lies between the measured E = 16 and E = 32 for those widths and between Cout = 32 and 64 for E = 16; nothing
+    was measured in between, nor at other E below 32."""
+    if not cloud_term_form(blk, f1, f2, e):
+        return 'composition'
+    E, cout = e.shape[1], conv_bn_block(blk)[0].out_channels
+    return 'cloud_term' if (E >= 32 or 2 * E >= cout) else 'composition'
+
+
+def cloud_term(e, w_cls):
+    """c (B,Cout) = e (B,E) @ w_cls (Cout,E)^T, in fp32 also under autocast.  Deterministic mode: products and a row sum instead
+    of the BLAS library's matmul (whose kernels are not this library's to fix), forward and backward"""
+    with torch.autocast("cuda", enabled=False):
+        if ops.deterministic():
+            return (e.unsqueeze(1) * w_cls.unsqueeze(0)).sum(-1)
+        return e @ w_cls.t()
+
+
+def feature_propagation_first_block(blk, f1, f2, geom, cloud=None, force_cloud_term=False):
     """First block of FeaturePropogation (pointnext_AA.py:210-226: interpolate f2 onto the fine cloud, concatenate with the
     skip features f1, Conv1d -> BatchNorm1d -> ReLU) with the conv applied BEFORE the interpolation:
         W . [f1 ; up(f2)] = W1 . f1 + up(W2 . f2)
     (the 3-NN interpolation is linear and mixes points, the 1x1 conv mixes channels: they commute).  The interpolated
     tensor has Cout instead of C2 channels (half at every level), its conv runs on the coarse cloud (4x fewer points), and
-    no concatenated (B, C1+C2, n) tensor exists.  -> the block's output, or None when it is not of that form."""
+    no concatenated (B, C1+C2, n) tensor exists.  -> the block's output, or None when it is not of that form.
+
+    `cloud` = (e, n_lead): the block's first n_lead input channels are e (B, n_lead) repeated along the points -- the shape
+    category embedding of the part-segmentation decoders, concatenated IN FRONT of the skip features (pointnext.py:662-663,
+    pointnetv2.py:507-510); f1 holds the skip features alone.  The weight splits into [W_cls | W_skip | W_up] and
+        W . [e ; f1 ; up(f2)] = W_skip . f1 + up(W_up . f2) + c,   c[b] = W_cls . e[b]
+    with c added inside the skip conv's kernel (ops.pointwise_conv_cloud_term): no (B, n_lead + C1, n) tensor exists and
+    that conv's reduction shrinks from n_lead + C1 to C1.  None when cloud_term_route says 'composition'.
+    `force_cloud_term`: take the term wherever the block has the form for it (cloud_term_form), whatever the shape dispatch
+    says -- for measuring the route on both sides of the dispatch rule (tools/cloud_term_bench.py)."""
+    if cloud is not None:
+        e, n_lead = cloud
+        assert e.dim() == 2 and e.shape[1] == n_lead, "cloud = (e (B, n_lead), n_lead)"
+        if not (cloud_term_form(blk, f1, f2, e) if force_cloud_term else cloud_term_route(blk, f1, f2, e) == 'cloud_term'):
+            return None
+        conv, bn, relu = conv_bn_block(blk)
+        w_cls, w_rest = ops.split_weight(conv.weight, n_lead)
+        w_skip, w_up = ops.split_weight(w_rest, f1.shape[1])
+        y1 = ops.pointwise_conv_cloud_term(f1, w_skip, cloud_term(e, w_cls))
+        y = ops.three_interpolate_add(conv1x1_weight(f2, w_up), geom['idx'], geom['weight'], y1, geom.get('csr'))
+        return batchnorm_act(bn, y, relu)
     m = conv_bn_block(blk)
     if (m is None or m[2] is None or type(m[0]) not in (nn.Conv1d, Conv1d) or f1 is None or not f1.is_cuda
             or f1.dtype != torch.float32 or f2.dtype != torch.float32):
@@ -256,6 +314,11 @@ def feature_propagation_first_block(blk, f1, f2, geom):
     w1, w2 = ops.split_weight(conv.weight, c1)
     y = ops.three_interpolate_add(conv1x1_weight(f2, w2), geom['idx'], geom['weight'], conv1x1_weight(f1, w1), geom.get('csr'))
     return batchnorm_act(bn, y, relu)
+
+
+def expand_cloud_channels(e, f1):
+    """the reference's composition: e (B,E) repeated along the points, in front of the skip features f1 (B,C1,n)"""
+    return torch.cat((e.unsqueeze(-1).expand(-1, -1, f1.shape[-1]), f1), dim=1)
 
 
 # (round 3, cfg 5 = XL + ++ at 1 x 120000: threshold 4096 -> 19.8 ms per step, 16384 -> 19.1, 65536 -> 19.4, never -> 19.3; the

@@ -5,7 +5,9 @@ Drop-in for openpoints/models/segmentation/base_seg.py:
                                      refinement -> head, returns (logits, stageACE_list, refine rate)
     BaseSeg_AMContrast3D   :97-126   encoder -> decoder -> head, returns (logits, stageACE_list)
     BaseSeg                :130-166  the plain PointNeXt baseline: encoder -> decoder -> head, returns logits
+    BasePartSeg            :169-187  part segmentation: the decoder also takes the shape category of every cloud
     SegHead                :207-267  Conv1d+BN+ReLU(+Dropout) ... Conv1d, optional global max/avg concat
+    MultiSegHead           :307-354  one small head per shape category, returns the list of their logits
 """
 import copy
 import logging
@@ -16,6 +18,7 @@ import torch.nn as nn
 
 from ..build import MODELS, build_model_from_cfg
 from ..layers import create_convblock1d, run_convblocks
+from ..layers.blocks import conv1x1
 
 
 def _build_enc_dec(self, encoder_args, decoder_args):
@@ -123,6 +126,33 @@ class BaseSeg(nn.Module):
 
 
 @MODELS.register_module()
+class BasePartSeg(BaseSeg):
+    """forward(p0, f0=None, cls0=None), or forward(data) with 'pos', 'x' and 'cls' (B,1) int64 shape categories.  A plan under
+    data['_geometry'] ('encoder' / 'decoder': the modules' plan_geometry) is passed through as BaseSeg does."""
+
+    trains_eagerly = True  # train.has_stage_list: no captured pipeline for part models yet
+
+    def __init__(self, encoder_args=None, decoder_args=None, cls_args=None, **kwargs):
+        super().__init__(encoder_args, decoder_args, cls_args, **kwargs)
+
+    def forward(self, p0, f0=None, cls0=None):
+        plan = None
+        if hasattr(p0, 'keys'):
+            plan = p0.get('_geometry', None)
+            p0, f0, cls0 = p0['pos'], p0['x'], p0['cls']
+        elif f0 is None:
+            f0 = p0.transpose(1, 2).contiguous()
+        p, f = self.encoder.forward_seg_feat({'pos': p0, 'x': f0, '_geometry': plan})
+        if self.decoder is not None:
+            f = self.decoder(p, f, cls0, None if plan is None else plan['decoder']).squeeze(-1)
+        elif isinstance(f, list):
+            f = f[-1]
+        if self.head is not None:
+            f = self.head(f)
+        return f
+
+
+@MODELS.register_module()
 class SegHead(nn.Module):
     def __init__(self, num_classes, in_channels, mlps=None, norm_args={'norm': 'bn1d'}, act_args={'act': 'relu'},
                  dropout=0.5, global_feat=None, **kwargs):
@@ -160,3 +190,39 @@ class SegHead(nn.Module):
             g = torch.cat(g, dim=1).expand(-1, -1, end_points.shape[-1])
             end_points = torch.cat((end_points, g), dim=1)
         return run_convblocks(self.head, end_points)
+
+
+@MODELS.register_module()
+class MultiSegHead(nn.Module):
+    """One head per shape category -- Conv1d + BN + ReLU (+ Dropout), then a Conv1d with bias onto that category's parts --
+    under `multi_shape_heads`; forward returns the list of the shape_classes logits tensors (B, num_parts[i], N), which
+    MultiShapeCrossEntropy indexes by each cloud's category.  As in the reference the final Conv1d is appended INSIDE the
+    layer loop (base_seg.py:337-344): with the fixed mlps [C, C, shape_classes] the loop has one pass."""
+
+    def __init__(self, num_classes, in_channels, norm_args={'norm': 'bn1d'}, act_args={'act': 'relu'}, dropout=0,
+                 shape_classes=16, num_parts=[4, 2, 2, 4, 4, 3, 3, 2, 4, 2, 6, 2, 3, 3, 3, 3], **kwargs):
+        super().__init__()
+        if kwargs:
+            logging.warning(f"kwargs: {kwargs} are not used in {__class__.__name__}")
+        mlps = [in_channels, in_channels] + [shape_classes]
+        self.num_parts = num_parts
+        self.shape_classes = shape_classes
+        self.multi_shape_heads = nn.ModuleList()
+        for i in range(shape_classes):
+            head = []
+            for j in range(len(mlps) - 2):
+                head.append(create_convblock1d(mlps[j], mlps[j + 1], norm_args=norm_args, act_args=act_args))
+                if dropout:
+                    head.append(nn.Dropout(dropout))
+                head.append(nn.Conv1d(mlps[-2], num_parts[i], kernel_size=1, bias=True))
+            self.multi_shape_heads.append(nn.Sequential(*head))
+
+    @staticmethod
+    def _run_head(head, x):
+        for mod in head:  # a bare nn.Conv1d takes conv1x1's route as a conv inside a block does
+            x = conv1x1(mod, x) if isinstance(mod, nn.Conv1d) else run_convblocks((mod,), x)
+        return x
+
+    def forward(self, end_points):
+        # one evaluation per head, as the reference: the heads' first convs are not stacked into one launch
+        return [self._run_head(self.multi_shape_heads[i], end_points) for i in range(self.shape_classes)]

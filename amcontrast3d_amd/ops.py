@@ -2015,6 +2015,74 @@ def pointwise_conv(x, weight, bias=None, bf16=False, dx_position_major=False):
     return PointwiseConv.apply(x, weight, bias, bf16, dx_position_major)
 
 
+class PointwiseConvCloudTerm(Function):
+    """y[b,:,p] = weight . x[b,:,p] + cloud_term[b,:]: a bias-free 1x1 convolution plus one Cout-vector per cloud, broadcast
+    along its points (amc3d_pointwise_conv_cloud_term_forward).  x (B,Cin,P) fp32, weight (Cout,Cin[,1]) -- a column block
+    of a wider matrix stays a view --, cloud_term (B,Cout).  The part-segmentation decoders' class-conditioned channels are
+    constant along a cloud: cloud_term = e @ W_cls.T stands for their share of the conv, and its gradient, the per-cloud
+    sums of dy (amc3d_cloud_term_grad), carries dW_cls and de through autograd on that small matmul.  dx and dweight are
+    PointwiseConv's.  Never the BLAS or convolution library; no float atomics in either direction."""
+
+    @staticmethod
+    def forward(ctx, x, weight, cloud_term):
+        _need_gpu(x, weight, cloud_term)
+        _need_dtype(torch.float32, x=x, weight=weight, cloud_term=cloud_term)
+        x = x.contiguous()
+        assert x.dim() == 3, "pointwise_conv_cloud_term takes (B, Cin, P) features"
+        B, Cin, P = x.shape
+        Cout = weight.shape[0]
+        assert weight.numel() == Cout * Cin, "pointwise_conv_cloud_term needs a 1x1 kernel"
+        assert tuple(cloud_term.shape) == (B, Cout), "cloud_term is (B, Cout)"
+        w2 = _weight_rows(weight.reshape(Cout, Cin), False)
+        c = cloud_term.contiguous()
+        y = torch.empty(B, Cout, P, dtype=torch.float32, device=x.device)
+        lib = _lib.load()
+        wsf = int(lib.amc3d_pointwise_conv_forward_workspace_bytes(B, Cin, Cout, P, 0))
+        work = torch.empty(wsf, dtype=torch.uint8, device=x.device) if wsf else None
+        with torch.cuda.device(x.device), timing.span("pointwise_conv_cloud_term_forward", 4 * B * P * (Cin + Cout),
+                                                      2.0 * B * P * Cin * Cout):
+            _lib.check(lib.amc3d_pointwise_conv_cloud_term_forward(B, Cin, Cout, P, _ptr(x), _ptr(w2), _ld(w2), _ptr(c), _ptr(y),
+                                                                   _ptr(work) if wsf else None, wsf, _stream(x)),
+                       "pointwise_conv_cloud_term_forward")
+        ctx.save_for_backward(x, w2)
+        ctx.wshape = tuple(weight.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w2 = ctx.saved_tensors
+        B, Cin, P = x.shape
+        Cout = w2.shape[0]
+        dy = dy.contiguous()
+        dev = dy.device
+        need_x, need_w, need_c = ctx.needs_input_grad
+        lib = _lib.load()
+        dx = torch.empty_like(x) if need_x else None
+        dw = torch.empty(Cout, Cin, dtype=torch.float32, device=dev) if need_w else None
+        dc = torch.empty(B, Cout, dtype=torch.float32, device=dev) if need_c else None
+        with torch.cuda.device(dev):
+            # the backward products put the cloud on the grid's z axis: more than 65535 clouds go in runs of 65535, their
+            # weight gradients added in run order (a fixed order)
+            run = 65535
+            for b0 in range(0, B if (need_x or need_w) else 0, run):
+                nb = min(run, B - b0)
+                dw_run = dw if b0 == 0 or not need_w else torch.empty_like(dw)
+                wb = int(lib.amc3d_pointwise_conv_workspace_bytes(nb, Cin, Cout, P))
+                work = torch.empty(max(wb, 4), dtype=torch.uint8, device=dev)
+                _lib.check(lib.amc3d_pointwise_conv_backward_strided(
+                    nb, Cin, Cout, P, _ptr(x[b0:]), _ptr(w2), _ld(w2), _ptr(dy[b0:]), _ptr(dx[b0:]) if need_x else None, 0,
+                    _ptr(dw_run) if need_w else None, Cin, _ptr(work), wb, _stream(dy)), "pointwise_conv_backward")
+                if need_w and b0:
+                    dw += dw_run
+            if need_c:
+                _lib.check(lib.amc3d_cloud_term_grad(B, Cout, P, _ptr(dy), _ptr(dc), _stream(dy)), "cloud_term_grad")
+        return dx, (dw.view(ctx.wshape) if need_w else None), dc
+
+
+def pointwise_conv_cloud_term(x, weight, cloud_term):
+    return PointwiseConvCloudTerm.apply(x, weight, cloud_term)
+
+
 def _split_columns(w2, c1):
     """w2 (rows, c1 + c2) fp32 on the GPU -> contiguous (rows, c1), (rows, c2) in one launch (no autograd)"""
     w2 = w2.detach().contiguous()

@@ -110,9 +110,10 @@ def _cfg(cfg, key, default=None):
 def has_stage_list(model):
     """True for the PointNeXt family, whose encoder keeps its stages as `encoder.encoder`: geometry.precompute_* and
     GraphPipeline walk that list.  A model without it (PointNet2Encoder: PointNet++, ASSANet) plans its geometry inside
-    its own forward and trains in the eager loop, without the GeometryPrefetcher."""
+    its own forward and trains in the eager loop, without the GeometryPrefetcher; so does a model that says so itself
+    (`trains_eagerly`: BasePartSeg, whose decoder also takes the batch's shape categories)."""
     m = model.module if hasattr(model, "module") else model
-    return hasattr(getattr(m, "encoder", None), "encoder")
+    return hasattr(getattr(m, "encoder", None), "encoder") and not getattr(m, "trains_eagerly", False)
 
 
 def _graph_pipeline(model, criterion, optimizer, cfg, step_loss, first, clip, extras=0):

@@ -626,6 +626,21 @@ int amc3d_join_columns(int rows, int c1, int c2, const float *a, const float *b,
 /* dbias (c) = sum_{b,p} dy (b,c,P): bias gradient of a 1x1 convolution with bias (the stem conv and the head's last conv,
  * base_seg.py:236-252, pointnext_AA.py:104-127 with is_head), summed in a fixed order */
 int amc3d_bias_grad(int b, int c, long P, const float *dy, float *dbias, void *stream);
+/* 1x1 convolution with a per-cloud additive term: y (b,cout,P) = weight (cout,cin; row stride ldw >= cin) . x (b,cin,P)
+ * + cloud_term (b,cout) broadcast along P.  The first FeaturePropagation conv of the part-segmentation decoders
+ * (pointnext.py:628-663, pointnetv2.py:498-511) convolves input channels that are constant along the points of a cloud (the
+ * shape-category embedding); their product with the weight is cloud_term = e (b,E) . W_cls^T, so no (b, E + cin, P) tensor
+ * is built.  Route, accumulators and sums of amc3d_pointwise_conv_forward_strided without a bias: with cloud_term == 0 the
+ * output equals that call's, bit for bit.  The streaming kernel adds the term in its epilogue (a workgroup's tile lies in one
+ * cloud); behind the 128 x 128-tile GEMM (>= 64 channels on both sides) it is a pass of its own, as that route's bias is.
+ * Any b >= 1: more than 65535 clouds run in launches of 65535 clouds each.
+ * workspace: amc3d_pointwise_conv_forward_workspace_bytes(b, cin, cout, P, 0) bytes.
+ * amc3d_cloud_term_grad: dterm (b,cout) = sum_p dy (b,cout,P), one workgroup of fixed size per (cloud, channel) row, summed in
+ * a fixed order without float atomics (the same bits on every run).  dx and dweight are amc3d_pointwise_conv_backward*'s. */
+int amc3d_pointwise_conv_cloud_term_forward(int b, int cin, int cout, long P, const float *x, const float *weight, long ldw,
+                                            const float *cloud_term, float *y, void *workspace, size_t workspace_bytes,
+                                            void *stream);
+int amc3d_cloud_term_grad(int b, int cout, long P, const float *dy, float *dterm, void *stream);
 
 /* ---- residual branch of a strided SetAbstraction block (openpoints/models/backbone/pointnext_AA.py:157-168, use_res):
  *     fi = torch.gather(f, -1, idx...); identity = self.skipconv(fi); ...; f = self.act(f + identity)
