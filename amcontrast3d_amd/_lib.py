@@ -95,15 +95,10 @@ SIGNATURES = {
     "amc3d_cross_entropy_workspace_bytes": (_sz, [_i, _l]),
     "amc3d_cross_entropy_forward": (_i, [_i, _i, _l, _vp, _vp, _ll, _vp, _vp, _vp, _sz, _vp]),
     "amc3d_cross_entropy_backward": (_i, [_i, _i, _l, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp]),
-    "amc3d_cross_entropy_general_workspace_bytes": (_sz, [_i, _l]),
-    "amc3d_cross_entropy_general_forward": (_i, [_i, _i, _l, _vp, _vp, _ll, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "amc3d_cross_entropy_general_backward": (_i, [_i, _i, _l, _vp, _vp, _ll, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "amc3d_point_loss_softmax_workspace_bytes": (_sz, [_i, _l]),
     "amc3d_point_loss_softmax_forward": (_i, [_i, _i, _l, _vp, _vp, _vp, _i, _ll, _i, _vp, _vp, _i, _f, _i, _f, _vp, _f, _i, _vp, _vp,
                                               _vp, _sz, _vp]),
     "amc3d_point_loss_softmax_backward": (_i, [_i, _i, _l, _vp, _vp, _vp, _i, _ll, _i, _vp, _vp, _i, _f, _i, _f, _vp, _f, _i, _vp, _vp,
                                                _vp, _vp, _vp]),
-    "amc3d_point_loss_sigmoid_workspace_bytes": (_sz, [_i, _l]),
     "amc3d_point_loss_sigmoid_forward": (_i, [_i, _i, _l, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _vp, _vp, _sz, _vp]),
     "amc3d_point_loss_sigmoid_backward": (_i, [_i, _i, _l, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _vp, _vp, _vp, _vp]),
     "amc3d_pointwise_conv_forward": (_i, [_i, _i, _i, _l, _vp, _vp, _vp, _vp, _vp]),

@@ -1492,194 +1492,22 @@ __global__ __launch_bounds__(256) void contrast_backward_edges_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------
-// Cross entropy over channel-major logits (B, C, N) with class targets (B, N), mean over the targets
-// != ignore_index: nn.CrossEntropyLoss() with its defaults, as loss/build.py:328,338 applies it after a
-// transpose + reshape copy of the logits to (B*N, C).  One thread per point walks the classes (coalesced
-// along N per class plane); the mean is reduced in two fixed-order stages (deterministic).
+// The point losses: every criterion of openpoints.loss (loss/build.py:14-257, 328-340) over channel-major logits (B, C, N)
+// with class targets (B, N), without the (B*N, C) transposed copy of the logits, as two form-generic families on one layout:
+// one thread per point, class planes read coalesced along N, any C >= 1, per-point terms in fp32 combined and summed in fp64
+// in a fixed order (wave shuffle tree, the block's waves in order, pl_finalize_kernel over the blocks' partials).  No atomics
+// and nothing zero-filled.  A class is a handful of run-time numbers (PlSoftmax / PlSigmoid), filled in by the C entry points
+// from the arguments include/amc3d.h documents.  nn.CrossEntropyLoss() with its defaults is the softmax form with only the
+// ignore value set, F.cross_entropy with weight and label_smoothing the form weight_per_class 1, eps_rule 0, den_mode 1.
 // ---------------------------------------------------------------------------------------------
 constexpr int CE_THREADS = 256;
-__global__ __launch_bounds__(CE_THREADS) void ce_forward_kernel(int C, long N, const float *__restrict__ logits,
-                                                                const long long *__restrict__ target, long long ignore,
-                                                                float *__restrict__ lse, double *__restrict__ partial)
-{
-    __shared__ double s_sum[CE_THREADS / 64];
-    __shared__ int s_cnt[CE_THREADS / 64];
-    const int b = blockIdx.y;
-    const long n = (long)blockIdx.x * CE_THREADS + threadIdx.x;
-    double term = 0.0;
-    int cnt = 0;
-    if (n < N) {
-        const float *x = logits + (size_t)b * C * N + n;
-        float mx = -__builtin_inff();
-        for (int c = 0; c < C; ++c) mx = fmaxf(mx, x[(size_t)c * N]);
-        float se = 0.f;
-        for (int c = 0; c < C; ++c) se += __expf(x[(size_t)c * N] - mx);
-        const float l = mx + __logf(se);
-        lse[(size_t)b * N + n] = l;
-        const long long t = target[(size_t)b * N + n];
-        if (t != ignore && t >= 0 && t < C) { term = (double)(l - x[(size_t)t * N]); cnt = 1; }
-    }
-    for (int s = 32; s >= 1; s >>= 1) {
-        term += __shfl_xor(term, s, 64);
-        cnt += __shfl_xor(cnt, s, 64);
-    }
-    if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6] = term; s_cnt[threadIdx.x >> 6] = cnt; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        int c = 0;
-        for (int w = 0; w < CE_THREADS / 64; ++w) { t += s_sum[w]; c += s_cnt[w]; }
-        const size_t slot = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-        partial[slot * 2] = t;
-        partial[slot * 2 + 1] = (double)c;
-    }
-}
-
-// out[0] = mean loss, out[1] = number of counted targets
-__global__ __launch_bounds__(1024) void ce_finalize_kernel(int nparts, const double *__restrict__ partial,
-                                                           float *__restrict__ out)
-{
-    __shared__ double s_sum[16], s_cnt[16];
-    double t = 0.0, c = 0.0;
-    for (int i = threadIdx.x; i < nparts; i += 1024) { t += partial[(size_t)i * 2]; c += partial[(size_t)i * 2 + 1]; }
-    for (int s = 32; s >= 1; s >>= 1) {
-        t += __shfl_xor(t, s, 64);
-        c += __shfl_xor(c, s, 64);
-    }
-    if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6] = t; s_cnt[threadIdx.x >> 6] = c; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double tt = 0.0, cc = 0.0;
-        for (int w = 0; w < 16; ++w) { tt += s_sum[w]; cc += s_cnt[w]; }
-        out[0] = (float)(tt / cc);  // 0/0 = NaN, as torch's mean over no targets
-        out[1] = (float)cc;
-    }
-}
-
-// dlogits[b,c,n] = g * (softmax_c - [c == target]) / count for counted targets, 0 otherwise
-__global__ __launch_bounds__(CE_THREADS) void ce_backward_kernel(int C, long N, const float *__restrict__ logits,
-                                                                 const long long *__restrict__ target, long long ignore,
-                                                                 const float *__restrict__ lse,
-                                                                 const float *__restrict__ mean_cnt,
-                                                                 const float *__restrict__ grad_out,
-                                                                 float *__restrict__ dlogits)
-{
-    const int b = blockIdx.y;
-    const long n = (long)blockIdx.x * CE_THREADS + threadIdx.x;
-    if (n >= N) return;
-    const float *x = logits + (size_t)b * C * N + n;
-    float *d = dlogits + (size_t)b * C * N + n;
-    const long long t = target[(size_t)b * N + n];
-    const bool counted = t != ignore && t >= 0 && t < C;
-    const float scale = counted ? grad_out[0] / mean_cnt[1] : 0.f;
-    const float l = lse[(size_t)b * N + n];
-    for (int c = 0; c < C; ++c) {
-        const float p = __expf(x[(size_t)c * N] - l);
-        d[(size_t)c * N] = scale * (p - (c == (int)t ? 1.f : 0.f));
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// The general form: F.cross_entropy(logits, target, weight, ignore_index, reduction='mean', label_smoothing=eps), what the
-// plain PointNeXt trainer builds (examples/segmentation/main.py:224-230: label_smoothing 0.2, class weights on request).
-// With lp = log_softmax over C, w = 1 without weights, V = the counted points (target in [0, C) and not ignored):
-//     loss = [ (1-eps) sum_V w[y_i] (-lp_i[y_i])  +  (eps/C) sum_V sum_c w[c] (-lp_i[c]) ] / sum_V w[y_i]
-// Same layout as the plain kernels above: one thread per point, class planes read coalesced along N, any C >= 1 (nothing
-// is held per class: one walk for the maximum, one for the sum of exponentials, one for the smoothing term when eps > 0).
-// Per point the terms are fp32 sums over the classes combined in fp64; the points are summed in fp64 in the fixed order of
-// the plain kernel (wave shuffle tree, the block's waves in order, then ce_finalize_kernel over the blocks' partials).
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(CE_THREADS) void ce_general_forward_kernel(int C, long N, const float *__restrict__ logits,
-                                                                        const long long *__restrict__ target, long long ignore,
-                                                                        int has_ignore, float eps, const float *__restrict__ weight,
-                                                                        float *__restrict__ lse, double *__restrict__ partial)
-{
-    __shared__ double s_num[CE_THREADS / 64], s_den[CE_THREADS / 64];
-    const int b = blockIdx.y;
-    const long n = (long)blockIdx.x * CE_THREADS + threadIdx.x;
-    double num = 0.0, den = 0.0;
-    if (n < N) {
-        const float *x = logits + (size_t)b * C * N + n;
-        float mx = -__builtin_inff();
-        for (int c = 0; c < C; ++c) mx = fmaxf(mx, x[(size_t)c * N]);
-        float se = 0.f;
-        for (int c = 0; c < C; ++c) se += expf(x[(size_t)c * N] - mx);
-        const float l = mx + logf(se);
-        lse[(size_t)b * N + n] = l;
-        const long long t = target[(size_t)b * N + n];
-        if (!(has_ignore && t == ignore) && t >= 0 && t < C) {
-            const float wy = weight ? weight[t] : 1.f;
-            den = (double)wy;
-            num = (1.0 - (double)eps) * (double)wy * (double)(l - x[(size_t)t * N]);
-            if (eps > 0.f) {
-                float sm = 0.f;  // sum_c w[c] * (-lp[c])
-                for (int c = 0; c < C; ++c) {
-                    const float nlp = l - x[(size_t)c * N];
-                    sm += weight ? weight[c] * nlp : nlp;
-                }
-                num += (double)eps / (double)C * (double)sm;
-            }
-        }
-    }
-    for (int s = 32; s >= 1; s >>= 1) {
-        num += __shfl_xor(num, s, 64);
-        den += __shfl_xor(den, s, 64);
-    }
-    if ((threadIdx.x & 63) == 0) { s_num[threadIdx.x >> 6] = num; s_den[threadIdx.x >> 6] = den; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0, d = 0.0;
-        for (int w = 0; w < CE_THREADS / 64; ++w) { t += s_num[w]; d += s_den[w]; }
-        const size_t slot = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-        partial[slot * 2] = t;
-        partial[slot * 2 + 1] = d;
-    }
-}
-
-// dlogits[b,c,n] = g / den * [ (1-eps) w[y] (p[c] - [c == y]) + (eps/C) (p[c] sum_c w[c] - w[c]) ] for counted targets, 0 otherwise;
-// den = loss_den[1], the forward's sum of w[y_i]
-__global__ __launch_bounds__(CE_THREADS) void ce_general_backward_kernel(int C, long N, const float *__restrict__ logits,
-                                                                         const long long *__restrict__ target, long long ignore,
-                                                                         int has_ignore, float eps, const float *__restrict__ weight,
-                                                                         const float *__restrict__ lse,
-                                                                         const float *__restrict__ loss_den,
-                                                                         const float *__restrict__ grad_out,
-                                                                         float *__restrict__ dlogits)
-{
-    const int b = blockIdx.y;
-    const long n = (long)blockIdx.x * CE_THREADS + threadIdx.x;
-    if (n >= N) return;
-    const float *x = logits + (size_t)b * C * N + n;
-    float *d = dlogits + (size_t)b * C * N + n;
-    const long long t = target[(size_t)b * N + n];
-    if ((has_ignore && t == ignore) || t < 0 || t >= C) {
-        for (int c = 0; c < C; ++c) d[(size_t)c * N] = 0.f;
-        return;
-    }
-    float wsum = (float)C;
-    if (weight) {
-        wsum = 0.f;
-        for (int c = 0; c < C; ++c) wsum += weight[c];
-    }
-    const float scale = grad_out[0] / loss_den[1];
-    const float hard = (1.f - eps) * (weight ? weight[t] : 1.f);
-    const float soft = eps / (float)C;
-    const float l = lse[(size_t)b * N + n];
-    for (int c = 0; c < C; ++c) {
-        const float p = expf(x[(size_t)c * N] - l);
-        const float wc = weight ? weight[c] : 1.f;
-        d[(size_t)c * N] = scale * (hard * (p - (c == (int)t ? 1.f : 0.f)) + soft * (p * wsum - wc));
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// The rest of openpoints.loss (loss/build.py:14-257) as two form-generic families on the same layout as ce_general_*: one
-// thread per point, class planes read coalesced along N, any C >= 1, expf / logf / powf, per-point terms in fp32 combined
-// and summed in fp64 in the fixed order of the kernels above (wave shuffle tree, the block's waves in order, pl_finalize_kernel
-// over the blocks' partials).  No atomics and nothing zero-filled.  A class is a handful of run-time numbers (PlSoftmax /
-// PlSigmoid), filled in by the C entry points from the arguments include/amc3d.h documents.
-// ---------------------------------------------------------------------------------------------
 enum { PL_DEN_COUNT = 0, PL_DEN_WSUM = 1, PL_DEN_ONE = 2 };
+
+// The one compile-time switch of the softmax kernels: the exponential and logarithm of the plain cross entropy are the
+// native instructions' (__expf / __logf), those of every other form the library's.  The plain form is the one inside the
+// captured AMContrast3D train step, whose bits are held fixed; in it every other factor of the generic arithmetic is 1 or 0.
+template <bool NATIVE> __device__ __forceinline__ float pl_exp(float v) { return NATIVE ? __expf(v) : expf(v); }
+template <bool NATIVE> __device__ __forceinline__ float pl_log(float v) { return NATIVE ? __logf(v) : logf(v); }
 
 struct PlSoftmax {
     const long long *remap;  // label -> class table of remap_len entries, or null
@@ -1751,6 +1579,7 @@ __global__ __launch_bounds__(1024) void pl_finalize_kernel(int nparts, const dou
 
 // Softmax family.  With y the point's class (pl_class), Q[c] = q[c] * (weight_per_class ? w[c] : 1) and
 // m = (weight_per_class ? 1 : w[y]) * alpha[y] * (1 - p[y])^gamma:   term = m * sum_c Q[c] (-lp[c]) + poly * (1 - p[y])
+template <bool NATIVE>
 __global__ __launch_bounds__(CE_THREADS) void pl_softmax_forward_kernel(int C, long N, const float *__restrict__ logits,
                                                                         const long long *__restrict__ target, PlSoftmax f,
                                                                         float *__restrict__ lse, double *__restrict__ partial)
@@ -1764,8 +1593,8 @@ __global__ __launch_bounds__(CE_THREADS) void pl_softmax_forward_kernel(int C, l
         float mx = -__builtin_inff();
         for (int c = 0; c < C; ++c) mx = fmaxf(mx, x[(size_t)c * N]);
         float se = 0.f;
-        for (int c = 0; c < C; ++c) se += expf(x[(size_t)c * N] - mx);
-        const float l = mx + logf(se);
+        for (int c = 0; c < C; ++c) se += pl_exp<NATIVE>(x[(size_t)c * N] - mx);
+        const float l = mx + pl_log<NATIVE>(se);
         lse[at] = l;
         const int y = pl_class(f, C, target[at], at);
         if (y >= 0) {
@@ -1773,7 +1602,7 @@ __global__ __launch_bounds__(CE_THREADS) void pl_softmax_forward_kernel(int C, l
             const float lpy = x[(size_t)y * N] - l;
             float m = f.weight_per_class ? 1.f : wy;
             if (f.alpha) m *= f.alpha[y];
-            if (f.gamma != 0.f) m *= powf(1.f - expf(lpy), f.gamma);
+            if (f.gamma != 0.f) m *= powf(1.f - pl_exp<NATIVE>(lpy), f.gamma);
             double term = (double)(f.a_hot - f.a_off) * (double)((f.weight_per_class ? wy : 1.f) * -lpy);
             if (f.a_off != 0.f) {
                 float sm = 0.f;  // sum_c w[c] * (-lp[c])
@@ -1784,7 +1613,7 @@ __global__ __launch_bounds__(CE_THREADS) void pl_softmax_forward_kernel(int C, l
                 term += (double)f.a_off * (double)sm;
             }
             num = (double)m * term;
-            if (f.poly != 0.f) num += (double)f.poly * (double)(1.f - expf(lpy));
+            if (f.poly != 0.f) num += (double)f.poly * (double)(1.f - pl_exp<NATIVE>(lpy));
             den = f.den_mode == PL_DEN_WSUM ? (double)wy : 1.0;
         }
     }
@@ -1793,6 +1622,7 @@ __global__ __launch_bounds__(CE_THREADS) void pl_softmax_forward_kernel(int C, l
 
 // dlogits[c] = g / den * [ m (p[c] sum_c Q - Q[c]) + poly p[y] (p[c] - [c == y]) ] for counted points ((1 - p[y])^gamma is a
 // constant: FocalLoss detaches pt), zero rows otherwise; den = loss_den[1]
+template <bool NATIVE>
 __global__ __launch_bounds__(CE_THREADS) void pl_softmax_backward_kernel(int C, long N, const float *__restrict__ logits,
                                                                          const long long *__restrict__ target, PlSoftmax f,
                                                                          const float *__restrict__ lse,
@@ -1814,7 +1644,7 @@ __global__ __launch_bounds__(CE_THREADS) void pl_softmax_backward_kernel(int C, 
     const bool per_class = f.weight && f.weight_per_class;
     const float l = lse[at];
     const float wy = f.weight ? f.weight[y] : 1.f;
-    const float py = expf(x[(size_t)y * N] - l);
+    const float py = pl_exp<NATIVE>(x[(size_t)y * N] - l);
     float m = f.weight_per_class ? 1.f : wy;
     if (f.alpha) m *= f.alpha[y];
     if (f.gamma != 0.f) m *= powf(1.f - py, f.gamma);
@@ -1831,7 +1661,7 @@ __global__ __launch_bounds__(CE_THREADS) void pl_softmax_backward_kernel(int C, 
     const float scale = grad_out[0] / loss_den[1];
     const float pp = f.poly * py;
     for (int c = 0; c < C; ++c) {
-        const float p = expf(x[(size_t)c * N] - l);
+        const float p = pl_exp<NATIVE>(x[(size_t)c * N] - l);
         const float is_y = c == y ? 1.f : 0.f;
         const float qc = f.a_off * (per_class ? f.weight[c] : 1.f) + is_y * hot;
         d[(size_t)c * N] = scale * (m * (p * sq - qc) + pp * (p - is_y));
@@ -2437,69 +2267,64 @@ AMC_API size_t amc3d_cross_entropy_workspace_bytes(int B, long N)
     return (size_t)(B > 0 ? B : 0) * (size_t)div_up(N > 0 ? N : 1, CE_THREADS) * 2 * sizeof(double);
 }
 
-AMC_API int amc3d_cross_entropy_forward(int B, int C, long N, const float *logits, const long long *target,
-                                        long long ignore_index, float *lse, float *mean_cnt, void *workspace,
-                                        size_t workspace_bytes, void *stream_)
+// What the forward entries of both point-loss families share: the argument check, the grid (ceil(N / 256), B), the per-point
+// kernel -- kernel(C, N, logits, target, args..., partials) -- and pl_finalize_kernel over the blocks' partials.  form_ok:
+// the entry's own arguments are present and in range; hint: those ranges, for the error text.
+template <typename Kernel, typename... Args>
+static int pl_forward(const char *what, const char *hint, Kernel kernel, bool form_ok, int B, int C, long N, const float *logits,
+                      const long long *target, int den_mode, float *loss_den, void *workspace, size_t workspace_bytes,
+                      void *stream_, Args... args)
 {
     if (B <= 0 || N <= 0) return 0;
-    if (C <= 0 || !logits || !target || !lse || !mean_cnt || !workspace ||
-        workspace_bytes < amc3d_cross_entropy_workspace_bytes(B, N))
-        return bad_arg("amc3d_cross_entropy_forward: bad argument");
+    if (C <= 0 || !logits || !target || !loss_den || !workspace || !form_ok ||
+        workspace_bytes < amc3d_cross_entropy_workspace_bytes(B, N)) {
+        set_error("%s: bad argument%s", what, hint);
+        return (int)hipErrorInvalidValue;
+    }
     hipStream_t stream = (hipStream_t)stream_;
     const int gx = div_up(N, CE_THREADS);
-    hipLaunchKernelGGL(ce_forward_kernel, dim3(gx, B), dim3(CE_THREADS), 0, stream, C, N, logits, target, ignore_index, lse,
-                       (double *)workspace);
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(1024), 0, stream, gx * B, (const double *)workspace, mean_cnt);
-    return launch_status("amc3d_cross_entropy_forward");
+    hipLaunchKernelGGL(kernel, dim3(gx, B), dim3(CE_THREADS), 0, stream, C, N, logits, target, args..., (double *)workspace);
+    hipLaunchKernelGGL(pl_finalize_kernel, dim3(1), dim3(1024), 0, stream, gx * B, (const double *)workspace, den_mode, loss_den);
+    return launch_status(what);
+}
+
+// the backward entries: kernel(C, N, logits, target, args..., loss_den, grad_out, dlogits) on the same grid
+template <typename Kernel, typename... Args>
+static int pl_backward(const char *what, const char *hint, Kernel kernel, bool form_ok, int B, int C, long N, const float *logits,
+                       const long long *target, const float *loss_den, const float *grad_out, float *dlogits, void *stream,
+                       Args... args)
+{
+    if (B <= 0 || N <= 0) return 0;
+    if (C <= 0 || !logits || !target || !loss_den || !grad_out || !dlogits || !form_ok) {
+        set_error("%s: bad argument%s", what, hint);
+        return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(kernel, dim3(div_up(N, CE_THREADS), B), dim3(CE_THREADS), 0, (hipStream_t)stream, C, N, logits, target,
+                       args..., loss_den, grad_out, dlogits);
+    return launch_status(what);
+}
+
+// nn.CrossEntropyLoss() with its defaults: the softmax form with nothing but the ignore value set
+static PlSoftmax pl_plain_form(long long ignore_index)
+{
+    return PlSoftmax{nullptr, 0, ignore_index, 1, nullptr, nullptr, 0, 1.f, 0.f, 0.f, nullptr, 0.f, PL_DEN_COUNT};
+}
+
+AMC_API int amc3d_cross_entropy_forward(int B, int C, long N, const float *logits, const long long *target,
+                                        long long ignore_index, float *lse, float *mean_cnt, void *workspace,
+                                        size_t workspace_bytes, void *stream)
+{
+    return pl_forward("amc3d_cross_entropy_forward", "", pl_softmax_forward_kernel<true>, lse != nullptr, B, C, N, logits, target,
+                      PL_DEN_COUNT, mean_cnt, workspace, workspace_bytes, stream, pl_plain_form(ignore_index), lse);
 }
 
 AMC_API int amc3d_cross_entropy_backward(int B, int C, long N, const float *logits, const long long *target,
                                          long long ignore_index, const float *lse, const float *mean_cnt,
                                          const float *grad_out, float *dlogits, void *stream)
 {
-    if (B <= 0 || N <= 0) return 0;
-    if (C <= 0 || !logits || !target || !lse || !mean_cnt || !grad_out || !dlogits)
-        return bad_arg("amc3d_cross_entropy_backward: bad argument");
-    hipLaunchKernelGGL(ce_backward_kernel, dim3(div_up(N, CE_THREADS), B), dim3(CE_THREADS), 0, (hipStream_t)stream, C, N,
-                       logits, target, ignore_index, lse, mean_cnt, grad_out, dlogits);
-    return launch_status("amc3d_cross_entropy_backward");
+    return pl_backward("amc3d_cross_entropy_backward", "", pl_softmax_backward_kernel<true>, lse != nullptr, B, C, N, logits, target,
+                       mean_cnt, grad_out, dlogits, stream, pl_plain_form(ignore_index), lse);
 }
-
-AMC_API size_t amc3d_cross_entropy_general_workspace_bytes(int B, long N) { return amc3d_cross_entropy_workspace_bytes(B, N); }
-
-AMC_API int amc3d_cross_entropy_general_forward(int B, int C, long N, const float *logits, const long long *target,
-                                                long long ignore_index, int has_ignore, float label_smoothing,
-                                                const float *weight, float *lse, float *loss_den, void *workspace,
-                                                size_t workspace_bytes, void *stream_)
-{
-    if (B <= 0 || N <= 0) return 0;
-    if (C <= 0 || !logits || !target || !lse || !loss_den || !workspace || !(label_smoothing >= 0.f && label_smoothing < 1.f) ||
-        workspace_bytes < amc3d_cross_entropy_general_workspace_bytes(B, N))
-        return bad_arg("amc3d_cross_entropy_general_forward: bad argument (label_smoothing must be in [0, 1))");
-    hipStream_t stream = (hipStream_t)stream_;
-    const int gx = div_up(N, CE_THREADS);
-    hipLaunchKernelGGL(ce_general_forward_kernel, dim3(gx, B), dim3(CE_THREADS), 0, stream, C, N, logits, target, ignore_index,
-                       has_ignore, label_smoothing, weight, lse, (double *)workspace);
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(1024), 0, stream, gx * B, (const double *)workspace, loss_den);
-    return launch_status("amc3d_cross_entropy_general_forward");
-}
-
-AMC_API int amc3d_cross_entropy_general_backward(int B, int C, long N, const float *logits, const long long *target,
-                                                 long long ignore_index, int has_ignore, float label_smoothing,
-                                                 const float *weight, const float *lse, const float *loss_den,
-                                                 const float *grad_out, float *dlogits, void *stream)
-{
-    if (B <= 0 || N <= 0) return 0;
-    if (C <= 0 || !logits || !target || !lse || !loss_den || !grad_out || !dlogits ||
-        !(label_smoothing >= 0.f && label_smoothing < 1.f))
-        return bad_arg("amc3d_cross_entropy_general_backward: bad argument (label_smoothing must be in [0, 1))");
-    hipLaunchKernelGGL(ce_general_backward_kernel, dim3(div_up(N, CE_THREADS), B), dim3(CE_THREADS), 0, (hipStream_t)stream, C, N,
-                       logits, target, ignore_index, has_ignore, label_smoothing, weight, lse, loss_den, grad_out, dlogits);
-    return launch_status("amc3d_cross_entropy_general_backward");
-}
-
-AMC_API size_t amc3d_point_loss_softmax_workspace_bytes(int B, long N) { return amc3d_cross_entropy_workspace_bytes(B, N); }
-AMC_API size_t amc3d_point_loss_sigmoid_workspace_bytes(int B, long N) { return amc3d_cross_entropy_workspace_bytes(B, N); }
 
 // the form of a softmax-family call from the C-ABI's arguments; false: an argument is out of range
 static bool pl_softmax_form(int C, const long long *remap, int remap_len, long long ignore_index, int has_ignore, const int *mask,
@@ -2522,25 +2347,19 @@ static bool pl_softmax_form(int C, const long long *remap, int remap_len, long l
     return true;
 }
 
+static const char *const PL_SOFTMAX_HINT = " (eps in [0, 1), gamma >= 0, den_mode in 0..2)";
+
 AMC_API int amc3d_point_loss_softmax_forward(int B, int C, long N, const float *logits, const long long *target,
                                              const long long *remap, int remap_len, long long ignore_index, int has_ignore,
                                              const int *mask, const float *weight, int weight_per_class, float eps, int eps_rule,
                                              float gamma, const float *alpha, float poly, int den_mode, float *lse, float *loss_den,
-                                             void *workspace, size_t workspace_bytes, void *stream_)
+                                             void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (B <= 0 || N <= 0) return 0;
     PlSoftmax f;
-    if (C <= 0 || !logits || !target || !lse || !loss_den || !workspace ||
-        workspace_bytes < amc3d_point_loss_softmax_workspace_bytes(B, N) ||
-        !pl_softmax_form(C, remap, remap_len, ignore_index, has_ignore, mask, weight, weight_per_class, eps, eps_rule, gamma, alpha,
-                         poly, den_mode, &f))
-        return bad_arg("amc3d_point_loss_softmax_forward: bad argument (eps in [0, 1), gamma >= 0, den_mode in 0..2)");
-    hipStream_t stream = (hipStream_t)stream_;
-    const int gx = div_up(N, CE_THREADS);
-    hipLaunchKernelGGL(pl_softmax_forward_kernel, dim3(gx, B), dim3(CE_THREADS), 0, stream, C, N, logits, target, f, lse,
-                       (double *)workspace);
-    hipLaunchKernelGGL(pl_finalize_kernel, dim3(1), dim3(1024), 0, stream, gx * B, (const double *)workspace, den_mode, loss_den);
-    return launch_status("amc3d_point_loss_softmax_forward");
+    const bool ok = pl_softmax_form(C, remap, remap_len, ignore_index, has_ignore, mask, weight, weight_per_class, eps, eps_rule,
+                                    gamma, alpha, poly, den_mode, &f);
+    return pl_forward("amc3d_point_loss_softmax_forward", PL_SOFTMAX_HINT, pl_softmax_forward_kernel<false>, ok && lse, B, C, N,
+                      logits, target, den_mode, loss_den, workspace, workspace_bytes, stream, f, lse);
 }
 
 AMC_API int amc3d_point_loss_softmax_backward(int B, int C, long N, const float *logits, const long long *target,
@@ -2549,44 +2368,34 @@ AMC_API int amc3d_point_loss_softmax_backward(int B, int C, long N, const float 
                                               float gamma, const float *alpha, float poly, int den_mode, const float *lse,
                                               const float *loss_den, const float *grad_out, float *dlogits, void *stream)
 {
-    if (B <= 0 || N <= 0) return 0;
     PlSoftmax f;
-    if (C <= 0 || !logits || !target || !lse || !loss_den || !grad_out || !dlogits ||
-        !pl_softmax_form(C, remap, remap_len, ignore_index, has_ignore, mask, weight, weight_per_class, eps, eps_rule, gamma, alpha,
-                         poly, den_mode, &f))
-        return bad_arg("amc3d_point_loss_softmax_backward: bad argument (eps in [0, 1), gamma >= 0, den_mode in 0..2)");
-    hipLaunchKernelGGL(pl_softmax_backward_kernel, dim3(div_up(N, CE_THREADS), B), dim3(CE_THREADS), 0, (hipStream_t)stream, C, N,
-                       logits, target, f, lse, loss_den, grad_out, dlogits);
-    return launch_status("amc3d_point_loss_softmax_backward");
+    const bool ok = pl_softmax_form(C, remap, remap_len, ignore_index, has_ignore, mask, weight, weight_per_class, eps, eps_rule,
+                                    gamma, alpha, poly, den_mode, &f);
+    return pl_backward("amc3d_point_loss_softmax_backward", PL_SOFTMAX_HINT, pl_softmax_backward_kernel<false>, ok && lse, B, C, N,
+                       logits, target, loss_den, grad_out, dlogits, stream, f, lse);
+}
+
+static const char *const PL_SIGMOID_HINT = " (gamma >= 0, alpha <= 1, den_mode 0 or 2)";
+
+static bool pl_sigmoid_ok(float alpha, float gamma, int den_mode)
+{
+    return gamma >= 0.f && alpha <= 1.f && (den_mode == PL_DEN_COUNT || den_mode == PL_DEN_ONE);
 }
 
 AMC_API int amc3d_point_loss_sigmoid_forward(int B, int C, long N, const float *logits, const long long *target,
-                                             const float *weight, const float *pos_weight, float alpha, float gamma, float poly, int den_mode, float *loss_den, void *workspace,
-                                             size_t workspace_bytes, void *stream_)
+                                             const float *weight, const float *pos_weight, float alpha, float gamma, float poly,
+                                             int den_mode, float *loss_den, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (B <= 0 || N <= 0) return 0;
-    if (C <= 0 || !logits || !target || !loss_den || !workspace || !(gamma >= 0.f) || !(alpha <= 1.f) ||
-        (den_mode != PL_DEN_COUNT && den_mode != PL_DEN_ONE) || workspace_bytes < amc3d_point_loss_sigmoid_workspace_bytes(B, N))
-        return bad_arg("amc3d_point_loss_sigmoid_forward: bad argument (gamma >= 0, alpha <= 1, den_mode 0 or 2)");
-    hipStream_t stream = (hipStream_t)stream_;
-    const PlSigmoid f{weight, pos_weight, alpha, gamma, poly, den_mode};
-    const int gx = div_up(N, CE_THREADS);
-    hipLaunchKernelGGL(pl_sigmoid_forward_kernel, dim3(gx, B), dim3(CE_THREADS), 0, stream, C, N, logits, target, f,
-                       (double *)workspace);
-    hipLaunchKernelGGL(pl_finalize_kernel, dim3(1), dim3(1024), 0, stream, gx * B, (const double *)workspace, den_mode, loss_den);
-    return launch_status("amc3d_point_loss_sigmoid_forward");
+    return pl_forward("amc3d_point_loss_sigmoid_forward", PL_SIGMOID_HINT, pl_sigmoid_forward_kernel,
+                      pl_sigmoid_ok(alpha, gamma, den_mode), B, C, N, logits, target, den_mode, loss_den, workspace, workspace_bytes,
+                      stream, PlSigmoid{weight, pos_weight, alpha, gamma, poly, den_mode});
 }
 
 AMC_API int amc3d_point_loss_sigmoid_backward(int B, int C, long N, const float *logits, const long long *target,
-                                              const float *weight, const float *pos_weight, float alpha, float gamma, float poly, int den_mode, const float *loss_den,
-                                              const float *grad_out, float *dlogits, void *stream)
+                                              const float *weight, const float *pos_weight, float alpha, float gamma, float poly,
+                                              int den_mode, const float *loss_den, const float *grad_out, float *dlogits, void *stream)
 {
-    if (B <= 0 || N <= 0) return 0;
-    if (C <= 0 || !logits || !target || !loss_den || !grad_out || !dlogits || !(gamma >= 0.f) || !(alpha <= 1.f) ||
-        (den_mode != PL_DEN_COUNT && den_mode != PL_DEN_ONE))
-        return bad_arg("amc3d_point_loss_sigmoid_backward: bad argument (gamma >= 0, alpha <= 1, den_mode 0 or 2)");
-    const PlSigmoid f{weight, pos_weight, alpha, gamma, poly, den_mode};
-    hipLaunchKernelGGL(pl_sigmoid_backward_kernel, dim3(div_up(N, CE_THREADS), B), dim3(CE_THREADS), 0, (hipStream_t)stream, C, N,
-                       logits, target, f, loss_den, grad_out, dlogits);
-    return launch_status("amc3d_point_loss_sigmoid_backward");
+    return pl_backward("amc3d_point_loss_sigmoid_backward", PL_SIGMOID_HINT, pl_sigmoid_backward_kernel,
+                       pl_sigmoid_ok(alpha, gamma, den_mode), B, C, N, logits, target, loss_den, grad_out, dlogits, stream,
+                       PlSigmoid{weight, pos_weight, alpha, gamma, poly, den_mode});
 }

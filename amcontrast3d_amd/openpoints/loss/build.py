@@ -26,9 +26,7 @@ class CrossEntropy(CrossEntropyLoss):
     class themselves and never come here."""
 
     def forward(self, input, target):
-        if ((self.label_smoothing > 0.0 or self.weight is not None) and self.reduction == 'mean' and input.is_cuda
-                and input.dtype == torch.float32 and input.dim() == 3 and input.is_contiguous()
-                and target.dtype == torch.int64 and target.shape == (input.shape[0], input.shape[2])
+        if ((self.label_smoothing > 0.0 or self.weight is not None) and self.reduction == 'mean' and _kernel_route(input, target)
                 and (self.weight is None or (self.weight.is_cuda and self.weight.dtype == torch.float32))):
             from amcontrast3d_amd.ops import cross_entropy_general
             return cross_entropy_general(input, target, self.ignore_index, self.label_smoothing, self.weight)

@@ -2384,102 +2384,6 @@ def confusion_update(cm, invalid, logits, target, ignore_index=None):
                    "confusion_update")
 
 
-class CrossEntropyMean(Function):
-    """nn.CrossEntropyLoss()(logits.transpose(1, 2).reshape(-1, C), target.flatten()) -- default arguments: mean
-    over the targets != ignore_index -- on the channel-major logits (B, C, N) as the model returns them
-    (loss/build.py:328,338-340), in one pass forward and one backward."""
-
-    @staticmethod
-    def forward(ctx, logits, target, ignore_index):
-        _need_gpu(logits, target)
-        logits = logits.contiguous()
-        B, C = logits.shape[0], logits.shape[1]
-        N = logits[0, 0].numel()
-        target = target.reshape(B, N).contiguous()
-        assert target.dtype == torch.int64 and logits.dtype == torch.float32
-        dev = logits.device
-        lse = torch.empty(B, N, dtype=torch.float32, device=dev)
-        mean_cnt = torch.empty(2, dtype=torch.float32, device=dev)
-        lib = _lib.load()
-        wb = int(lib.amc3d_cross_entropy_workspace_bytes(B, N))
-        work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev), timing.span("cross_entropy_forward", B * N * (4 * C + 12)):
-            _lib.check(lib.amc3d_cross_entropy_forward(B, C, N, _ptr(logits), _ptr(target), int(ignore_index), _ptr(lse),
-                                                       _ptr(mean_cnt), _ptr(work), wb, _stream(logits)), "cross_entropy_forward")
-        ctx.save_for_backward(logits, target, lse, mean_cnt)
-        ctx.ignore_index = int(ignore_index)
-        return mean_cnt[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        logits, target, lse, mean_cnt = ctx.saved_tensors
-        B, C = logits.shape[0], logits.shape[1]
-        N = logits[0, 0].numel()
-        g = g.contiguous().to(torch.float32)
-        d = torch.empty_like(logits)
-        with torch.cuda.device(logits.device), timing.span("cross_entropy_backward", B * N * (8 * C + 12)):
-            _lib.check(_lib.load().amc3d_cross_entropy_backward(B, C, N, _ptr(logits), _ptr(target), ctx.ignore_index,
-                                                                _ptr(lse), _ptr(mean_cnt), _ptr(g), _ptr(d),
-                                                                _stream(logits)), "cross_entropy_backward")
-        return d, None, None
-
-
-def cross_entropy_mean(logits, target, ignore_index=-100):
-    return CrossEntropyMean.apply(logits, target, ignore_index)
-
-
-class CrossEntropyGeneral(Function):
-    """F.cross_entropy(logits, target, weight, ignore_index=..., reduction='mean', label_smoothing=...) on channel-major
-    logits (B, C, N) with targets (B, N): the plain PointNeXt trainer's criterion (examples/segmentation/main.py:224-230),
-    one pass forward and one backward (csrc/loss.hip, ce_general_*)."""
-
-    @staticmethod
-    def forward(ctx, logits, target, ignore_index, label_smoothing, weight):
-        _need_gpu(logits, target, *([weight] if weight is not None else []))
-        _need_dtype(torch.float32, logits=logits, **({"weight": weight} if weight is not None else {}))
-        _need_dtype(torch.int64, target=target)
-        logits = logits.contiguous()
-        B, C = logits.shape[0], logits.shape[1]
-        N = logits[0, 0].numel()
-        target = target.reshape(B, N).contiguous()
-        if weight is not None:
-            weight = weight.contiguous()
-            assert weight.shape == (C,), f"weight must hold one value per class: {tuple(weight.shape)} for {C} classes"
-        dev = logits.device
-        lse = torch.empty(B, N, dtype=torch.float32, device=dev)
-        loss_den = torch.empty(2, dtype=torch.float32, device=dev)
-        lib = _lib.load()
-        wb = int(lib.amc3d_cross_entropy_general_workspace_bytes(B, N))
-        work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
-        ctx.args = (int(ignore_index if ignore_index is not None else 0), int(ignore_index is not None), float(label_smoothing))
-        with torch.cuda.device(dev), timing.span("cross_entropy_general_forward", B * N * (4 * C * (3 if label_smoothing else 2) + 12)):
-            _lib.check(lib.amc3d_cross_entropy_general_forward(B, C, N, _ptr(logits), _ptr(target), *ctx.args,
-                                                               _ptr(weight) if weight is not None else None, _ptr(lse),
-                                                               _ptr(loss_den), _ptr(work), wb, _stream(logits)),
-                       "cross_entropy_general_forward")
-        ctx.save_for_backward(logits, target, lse, loss_den, weight)
-        return loss_den[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        logits, target, lse, loss_den, weight = ctx.saved_tensors
-        B, C = logits.shape[0], logits.shape[1]
-        N = logits[0, 0].numel()
-        g = g.contiguous().to(torch.float32)
-        d = torch.empty_like(logits)
-        with torch.cuda.device(logits.device), timing.span("cross_entropy_general_backward", B * N * (8 * C + 12)):
-            _lib.check(_lib.load().amc3d_cross_entropy_general_backward(B, C, N, _ptr(logits), _ptr(target), *ctx.args,
-                                                                        _ptr(weight) if weight is not None else None,
-                                                                        _ptr(lse), _ptr(loss_den), _ptr(g), _ptr(d),
-                                                                        _stream(logits)), "cross_entropy_general_backward")
-        return d, None, None, None, None
-
-
-def cross_entropy_general(logits, target, ignore_index=-100, label_smoothing=0.0, weight=None):
-    """ignore_index None: no target is ignored.  The class weights take no gradient."""
-    return CrossEntropyGeneral.apply(logits, target, ignore_index, label_smoothing, weight)
-
-
 _POINT_LOSS_DEN = {"count": 0, "weight": 1, "one": 2}
 
 
@@ -2497,20 +2401,86 @@ def _class_table(t, C, name, dtype=torch.float32):
     return t.contiguous()
 
 
-class PointLossSoftmax(Function):
-    """The softmax family of csrc/loss.hip (pl_softmax_*; formulas in include/amc3d.h) on channel-major logits (B, C, N) with
-    targets (B, N): SmoothCrossEntropy, MaskedCrossEntropy, FocalLoss and Poly1CrossEntropyLoss of openpoints.loss are forms of
-    it.  Two launches forward, one backward; the saved lse (B, N) spares the backward the two reduction walks."""
+def _ploss_begin(logits, target):
+    """What every point-loss forward starts from: fp32 logits (B, C, *) and int64 targets on the GPU, the logits contiguous,
+    the targets as (B, N) -> logits, target, (B, C, N)."""
+    _need_gpu(logits, target)
+    _need_dtype(torch.float32, logits=logits)
+    _need_dtype(torch.int64, target=target)
+    logits = logits.contiguous()
+    B, C = logits.shape[0], logits.shape[1]
+    N = logits[0, 0].numel()
+    return logits, target.reshape(B, N).contiguous(), (B, C, N)
+
+
+def _ploss_finish(ctx, op, span, nbytes, moved, logits, target, form, with_lse=True):
+    """The rest of the forward: the lse (B, N) where the family saves one, {loss, den}, the workspace, the timing span, the call
+    amc3d_<op>_forward(B, C, N, logits, target, *form(), [lse,] loss_den, workspace, bytes, stream) and what the backward reads.
+    form() -> the entry's own arguments; the closure keeps its tables alive.  span: the stem of the span's name, stated by the
+    caller (cross_entropy_general runs the softmax family's entries under its own)."""
+    B, C = logits.shape[0], logits.shape[1]
+    N = target.shape[1]
+    dev = logits.device
+    lse = [torch.empty(B, N, dtype=torch.float32, device=dev)] if with_lse else []
+    loss_den = torch.empty(2, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    wb = int(lib.amc3d_cross_entropy_workspace_bytes(B, N))
+    work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev), timing.span(span + "_forward", nbytes, moved=moved):
+        _lib.check(getattr(lib, f"amc3d_{op}_forward")(B, C, N, _ptr(logits), _ptr(target), *form(), *map(_ptr, lse), _ptr(loss_den),
+                                                       _ptr(work), wb, _stream(logits)), span + "_forward")
+    ctx.save_for_backward(logits, target, *lse, loss_den)
+    ctx.op, ctx.span, ctx.form = op, span, form
+    return loss_den[0]
+
+
+def _ploss_backward(ctx, g, n_args):
+    """dlogits by amc3d_<op>_backward(B, C, N, logits, target, *form(), [lse,] loss_den, g, dlogits, stream), and a None for
+    each of the forward's n_args other arguments."""
+    logits, target, *lse, loss_den = ctx.saved_tensors
+    B, C = logits.shape[0], logits.shape[1]
+    N = target.shape[1]
+    g = g.contiguous().to(torch.float32)
+    d = torch.empty_like(logits)
+    with torch.cuda.device(logits.device), timing.span(ctx.span + "_backward", B * N * (8 * C + 8 + 4 * len(lse))):
+        _lib.check(getattr(_lib.load(), f"amc3d_{ctx.op}_backward")(B, C, N, _ptr(logits), _ptr(target), *ctx.form(), *map(_ptr, lse),
+                                                                    _ptr(loss_den), _ptr(g), _ptr(d), _stream(logits)),
+                   ctx.span + "_backward")
+    return (d,) + (None,) * n_args
+
+
+class CrossEntropyMean(Function):
+    """nn.CrossEntropyLoss()(logits.transpose(1, 2).reshape(-1, C), target.flatten()) -- default arguments: mean
+    over the targets != ignore_index -- on the channel-major logits (B, C, N) as the model returns them
+    (loss/build.py:328,338-340), in one pass forward and one backward: the softmax family's form with only the ignore value
+    set, on the native exp / log instructions (csrc/loss.hip)."""
 
     @staticmethod
-    def forward(ctx, logits, target, remap, ignore_index, mask, weight, weight_per_class, eps, eps_rule, gamma, alpha, poly, den):
-        _need_gpu(logits, target)
-        _need_dtype(torch.float32, logits=logits)
-        _need_dtype(torch.int64, target=target)
-        logits = logits.contiguous()
-        B, C = logits.shape[0], logits.shape[1]
-        N = logits[0, 0].numel()
-        target = target.reshape(B, N).contiguous()
+    def forward(ctx, logits, target, ignore_index):
+        logits, target, (B, C, N) = _ploss_begin(logits, target)
+        ignore_index = int(ignore_index)
+        return _ploss_finish(ctx, "cross_entropy", "cross_entropy", B * N * (4 * C + 12), None, logits, target,
+                             lambda: (ignore_index,))
+
+    @staticmethod
+    def backward(ctx, g):
+        return _ploss_backward(ctx, g, 2)
+
+
+def cross_entropy_mean(logits, target, ignore_index=-100):
+    return CrossEntropyMean.apply(logits, target, ignore_index)
+
+
+class PointLossSoftmax(Function):
+    """The softmax family of csrc/loss.hip (pl_softmax_*; formulas in include/amc3d.h) on channel-major logits (B, C, N) with
+    targets (B, N): F.cross_entropy with weight and label_smoothing, SmoothCrossEntropy, MaskedCrossEntropy, FocalLoss and
+    Poly1CrossEntropyLoss of openpoints.loss are forms of it.  Two launches forward, one backward; the saved lse (B, N) spares
+    the backward the two reduction walks."""
+
+    @staticmethod
+    def forward(ctx, logits, target, remap, ignore_index, mask, weight, weight_per_class, eps, eps_rule, gamma, alpha, poly, den,
+                span="point_loss_softmax"):
+        logits, target, (B, C, N) = _ploss_begin(logits, target)
         weight, alpha = _class_table(weight, C, "weight"), _class_table(alpha, C, "alpha")
         if remap is not None:
             _need_gpu(remap)
@@ -2520,35 +2490,16 @@ class PointLossSoftmax(Function):
             _need_gpu(mask)
             _need_dtype(torch.int32, mask=mask)
             mask = mask.reshape(B, N).contiguous()
-        dev = logits.device
-        lse = torch.empty(B, N, dtype=torch.float32, device=dev)
-        loss_den = torch.empty(2, dtype=torch.float32, device=dev)
-        lib = _lib.load()
-        wb = int(lib.amc3d_point_loss_softmax_workspace_bytes(B, N))
-        work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
-        ctx.form = lambda: (_opt_ptr(remap), 0 if remap is None else remap.numel(), int(ignore_index if ignore_index is not None else 0),
-                            int(ignore_index is not None), _opt_ptr(mask), _opt_ptr(weight), int(bool(weight_per_class)), float(eps),
-                            int(eps_rule), float(gamma), _opt_ptr(alpha), float(poly), _POINT_LOSS_DEN[den])
-        walks = 3 if eps else 2
-        with torch.cuda.device(dev), timing.span("point_loss_softmax_forward", B * N * (4 * C + 12 + (4 if mask is not None else 0)),
-                                                 moved=B * N * (4 * C * walks + 12 + (4 if mask is not None else 0))):
-            _lib.check(lib.amc3d_point_loss_softmax_forward(B, C, N, _ptr(logits), _ptr(target), *ctx.form(), _ptr(lse), _ptr(loss_den),
-                                                            _ptr(work), wb, _stream(logits)), "point_loss_softmax_forward")
-        ctx.save_for_backward(logits, target, lse, loss_den)
-        return loss_den[0]
+        form = lambda: (_opt_ptr(remap), 0 if remap is None else remap.numel(), int(ignore_index if ignore_index is not None else 0),
+                        int(ignore_index is not None), _opt_ptr(mask), _opt_ptr(weight), int(bool(weight_per_class)), float(eps),
+                        int(eps_rule), float(gamma), _opt_ptr(alpha), float(poly), _POINT_LOSS_DEN[den])
+        extra = 12 + (4 if mask is not None else 0)
+        return _ploss_finish(ctx, "point_loss_softmax", span, B * N * (4 * C + extra), B * N * (4 * C * (3 if eps else 2) + extra),
+                             logits, target, form)
 
     @staticmethod
     def backward(ctx, g):
-        logits, target, lse, loss_den = ctx.saved_tensors
-        B, C = logits.shape[0], logits.shape[1]
-        N = logits[0, 0].numel()
-        g = g.contiguous().to(torch.float32)
-        d = torch.empty_like(logits)
-        with torch.cuda.device(logits.device), timing.span("point_loss_softmax_backward", B * N * (8 * C + 12)):
-            _lib.check(_lib.load().amc3d_point_loss_softmax_backward(B, C, N, _ptr(logits), _ptr(target), *ctx.form(), _ptr(lse),
-                                                                     _ptr(loss_den), _ptr(g), _ptr(d), _stream(logits)),
-                       "point_loss_softmax_backward")
-        return (d,) + (None,) * 12
+        return _ploss_backward(ctx, g, 13)
 
 
 def point_loss_softmax(logits, target, *, remap=None, ignore_index=None, mask=None, weight=None, weight_per_class=False,
@@ -2561,6 +2512,14 @@ def point_loss_softmax(logits, target, *, remap=None, ignore_index=None, mask=No
                                   poly, den)
 
 
+def cross_entropy_general(logits, target, ignore_index=-100, label_smoothing=0.0, weight=None):
+    """F.cross_entropy(logits, target, weight, ignore_index=..., reduction='mean', label_smoothing=...) on channel-major
+    logits (B, C, N) with targets (B, N): the plain PointNeXt trainer's criterion (examples/segmentation/main.py:224-230), a form
+    of the softmax family under spans of its own.  ignore_index None: no target is ignored.  The class weights take no gradient."""
+    return PointLossSoftmax.apply(logits, target, None, ignore_index, None, weight, True, label_smoothing, 0, 0.0, None, 0.0,
+                                  "weight", "cross_entropy_general")
+
+
 class PointLossSigmoid(Function):
     """The sigmoid family of csrc/loss.hip (pl_sigmoid_*; formulas in include/amc3d.h): elementwise over (B, C, N) against the
     one-hot of target (B, N), formed on the fly -- BCELogits and Poly1FocalLoss of openpoints.loss.  Two launches forward, one
@@ -2568,38 +2527,16 @@ class PointLossSigmoid(Function):
 
     @staticmethod
     def forward(ctx, logits, target, weight, pos_weight, alpha, gamma, poly, den):
-        _need_gpu(logits, target)
-        _need_dtype(torch.float32, logits=logits)
-        _need_dtype(torch.int64, target=target)
-        logits = logits.contiguous()
-        B, C = logits.shape[0], logits.shape[1]
-        N = logits[0, 0].numel()
-        target = target.reshape(B, N).contiguous()
+        logits, target, (B, C, N) = _ploss_begin(logits, target)
         weight, pos_weight = _class_table(weight, C, "weight"), _class_table(pos_weight, C, "pos_weight")
-        dev = logits.device
-        loss_den = torch.empty(2, dtype=torch.float32, device=dev)
-        lib = _lib.load()
-        wb = int(lib.amc3d_point_loss_sigmoid_workspace_bytes(B, N))
-        work = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
-        ctx.form = lambda: (_opt_ptr(weight), _opt_ptr(pos_weight), float(-1.0 if alpha is None else alpha), float(gamma), float(poly),
-                            _POINT_LOSS_DEN[den])
-        with torch.cuda.device(dev), timing.span("point_loss_sigmoid_forward", B * N * (4 * C + 8)):
-            _lib.check(lib.amc3d_point_loss_sigmoid_forward(B, C, N, _ptr(logits), _ptr(target), *ctx.form(), _ptr(loss_den),
-                                                            _ptr(work), wb, _stream(logits)), "point_loss_sigmoid_forward")
-        ctx.save_for_backward(logits, target, loss_den)
-        return loss_den[0]
+        form = lambda: (_opt_ptr(weight), _opt_ptr(pos_weight), float(-1.0 if alpha is None else alpha), float(gamma), float(poly),
+                        _POINT_LOSS_DEN[den])
+        return _ploss_finish(ctx, "point_loss_sigmoid", "point_loss_sigmoid", B * N * (4 * C + 8), None, logits, target, form,
+                             with_lse=False)
 
     @staticmethod
     def backward(ctx, g):
-        logits, target, loss_den = ctx.saved_tensors
-        B, C = logits.shape[0], logits.shape[1]
-        N = logits[0, 0].numel()
-        g = g.contiguous().to(torch.float32)
-        d = torch.empty_like(logits)
-        with torch.cuda.device(logits.device), timing.span("point_loss_sigmoid_backward", B * N * (8 * C + 8)):
-            _lib.check(_lib.load().amc3d_point_loss_sigmoid_backward(B, C, N, _ptr(logits), _ptr(target), *ctx.form(), _ptr(loss_den),
-                                                                     _ptr(g), _ptr(d), _stream(logits)), "point_loss_sigmoid_backward")
-        return (d,) + (None,) * 7
+        return _ploss_backward(ctx, g, 7)
 
 
 def point_loss_sigmoid(logits, target, *, weight=None, pos_weight=None, alpha=None, gamma=0.0, poly=0.0, den="count"):

@@ -494,41 +494,14 @@ int amc3d_grouped_conv_backward(int b, int cin, int cout, int n, int npoints, in
 int amc3d_confusion_update(int B, int C, long N, const float *logits, const long long *target, long long ignore,
                            int has_ignore, long long *cm, long long *invalid, void *stream);
 
-/* ---- cross entropy over channel-major logits -----------------------------------------------------
- * nn.CrossEntropyLoss() with its defaults (mean over targets != ignore_index) as CrossEntropyAce applies it
- * (openpoints/loss/build.py:328,338-340), without the (B*N, C) transposed copy of the logits.
- * logits (B,C,N) fp32, target (B,N) int64, lse (B,N) out (saved for backward), mean_cnt[2] = {loss, count}. */
-size_t amc3d_cross_entropy_workspace_bytes(int B, long N);
-int amc3d_cross_entropy_forward(int B, int C, long N, const float *logits, const long long *target,
-                                long long ignore_index, float *lse, float *mean_cnt, void *workspace,
-                                size_t workspace_bytes, void *stream);
-/* dlogits (B,C,N) = grad_out[0] * (softmax - onehot) / count, zero rows for ignored targets */
-int amc3d_cross_entropy_backward(int B, int C, long N, const float *logits, const long long *target,
-                                 long long ignore_index, const float *lse, const float *mean_cnt,
-                                 const float *grad_out, float *dlogits, void *stream);
-/* The general form, torch.nn.functional.cross_entropy(logits, target, weight, ignore_index, reduction='mean',
- * label_smoothing) -- the criterion of the plain PointNeXt trainer (examples/segmentation/main.py:224-230, label_smoothing 0.2
- * and class weights on request).  weight (C) fp32 or NULL (all ones); label_smoothing eps in [0, 1); has_ignore = 0: no target
- * is ignored.  V = the points whose target is in [0, C) and not ignored, lp = log_softmax over C, p = softmax:
- *   loss = [ (1-eps) sum_V w[y_i] (-lp_i[y_i]) + (eps/C) sum_V sum_c w[c] (-lp_i[c]) ] / sum_V w[y_i]
- *   dlogits_i[c] = grad_out[0] / den * [ (1-eps) w[y_i] (p_i[c] - [c == y_i]) + (eps/C) (p_i[c] sum_c w[c] - w[c]) ], zero rows outside V
- * loss_den[2] = {loss, den = sum_V w[y_i]}; lse (B,N) out (saved for backward).  Any C >= 1.  Two launches forward, one
- * backward; fixed summation order (fp64 over the points), so equal inputs give equal bits.  With V empty the loss is
- * 0/0 = NaN, as torch's, and dlogits is all zero (torch's is too: no row is counted). */
-size_t amc3d_cross_entropy_general_workspace_bytes(int B, long N);
-int amc3d_cross_entropy_general_forward(int B, int C, long N, const float *logits, const long long *target,
-                                        long long ignore_index, int has_ignore, float label_smoothing,
-                                        const float *weight, float *lse, float *loss_den, void *workspace,
-                                        size_t workspace_bytes, void *stream);
-int amc3d_cross_entropy_general_backward(int B, int C, long N, const float *logits, const long long *target,
-                                         long long ignore_index, int has_ignore, float label_smoothing,
-                                         const float *weight, const float *lse, const float *loss_den,
-                                         const float *grad_out, float *dlogits, void *stream);
-/* The rest of openpoints.loss (loss/build.py:14-257) as two form-generic families on the same layout, summation order and launch
- * counts as cross_entropy_general (two launches forward, one backward, no atomics, nothing zero-filled, any C >= 1).  A point
- * whose class falls outside [0, C) is left out and gets a zero gradient row; with nothing counted a mean is 0/0 = NaN and
- * dlogits all zero.  loss_den[2] = {loss, den}; den_mode 0: den = the counted points (softmax) or their elements (sigmoid),
- * 1: den = sum of w[y] (softmax only), 2: den = 1 (reduction 'sum').
+/* ---- point losses over channel-major logits -------------------------------------------------------
+ * The criteria of openpoints.loss (loss/build.py:14-257, 328-340) without the (B*N, C) transposed copy of the logits, as two
+ * form-generic families on one layout and summation order (two launches forward, one backward, no atomics, nothing zero-filled,
+ * any C >= 1; fixed-order fp64 sum over the points, so equal inputs give equal bits).  logits (B,C,N) fp32, target (B,N) int64.
+ * A point whose class falls outside [0, C) is left out and gets a zero gradient row; with nothing counted a mean is 0/0 = NaN,
+ * as torch's, and dlogits all zero.  loss_den[2] = {loss, den}; den_mode 0: den = the counted points (softmax) or their
+ * elements (sigmoid), 1: den = sum of w[y] (softmax only), 2: den = 1 (reduction 'sum').  One workspace query serves every
+ * forward entry below.
  *
  * Softmax family.  A point is dropped when has_ignore and target == ignore_index, or when mask (B,N) int32 is given and its
  * entry != 1; then y = remap[target] when remap (remap_len int64 entries) is given, target otherwise.  lp = log_softmax,
@@ -539,9 +512,13 @@ int amc3d_cross_entropy_general_backward(int B, int C, long N, const float *logi
  *   term_i = m sum_c Q[c] (-lp_i[c]) + poly (1 - p_i[y])
  *   loss = sum_i term_i / den
  *   dlogits_i[c] = grad_out[0] / den * [ m (p_i[c] sum_c Q[c] - Q[c]) + poly p_i[y] (p_i[c] - [c == y]) ]
- * SmoothCrossEntropy: eps_rule 1, weight_per_class 1, den_mode 0 (eps = 0: weight_per_class 0, den_mode 1);  MaskedCrossEntropy:
- * mask, eps_rule 0;  FocalLoss: gamma, alpha, den_mode 0 or 2;  Poly1CrossEntropyLoss: poly, weight_per_class 0, den_mode 0 or 2.
- * lse (B,N) out (saved for backward).
+ * lse (B,N) out (saved for backward).  The forms:
+ *   nn.CrossEntropyLoss() with its defaults, as CrossEntropyAce applies it: amc3d_cross_entropy_forward / _backward, the form
+ *     with nothing but ignore_index set (mean_cnt = loss_den), on the native exp / log instructions; every other form uses expf / logf
+ *   F.cross_entropy with weight and label_smoothing: weight_per_class 1, eps_rule 0, den_mode 1
+ *   SmoothCrossEntropy: eps_rule 1, weight_per_class 1, den_mode 0 (eps = 0: weight_per_class 0, den_mode 1)
+ *   MaskedCrossEntropy: mask, eps_rule 0;  FocalLoss: gamma, alpha, den_mode 0 or 2
+ *   Poly1CrossEntropyLoss: poly, weight_per_class 0, den_mode 0 or 2
  *
  * Sigmoid family: elementwise over (B,C,N) against the one-hot of target, formed on the fly.  For logit x and target bit t:
  * z = t ? -x : x, u = sigmoid(z) = 1 - pt, ce = max(x,0) - x t + log1p(exp(-|x|)) = -log(pt),
@@ -549,7 +526,13 @@ int amc3d_cross_entropy_general_backward(int B, int C, long N, const float *logi
  *   value = a ce u^gamma + poly u^(gamma+1)
  *   d value / d z = u^gamma [ a (u + ce gamma (1 - u)) + poly (gamma + 1) u (1 - u) ],  d z / d x = t ? -1 : 1
  * BCELogits: weight / pos_weight (C) or NULL, alpha < 0, gamma = poly = 0;  Poly1FocalLoss: alpha, gamma, poly, no weights. */
-size_t amc3d_point_loss_softmax_workspace_bytes(int B, long N);
+size_t amc3d_cross_entropy_workspace_bytes(int B, long N);
+int amc3d_cross_entropy_forward(int B, int C, long N, const float *logits, const long long *target,
+                                long long ignore_index, float *lse, float *mean_cnt, void *workspace,
+                                size_t workspace_bytes, void *stream);
+int amc3d_cross_entropy_backward(int B, int C, long N, const float *logits, const long long *target,
+                                 long long ignore_index, const float *lse, const float *mean_cnt,
+                                 const float *grad_out, float *dlogits, void *stream);
 int amc3d_point_loss_softmax_forward(int B, int C, long N, const float *logits, const long long *target,
                                      const long long *remap, int remap_len, long long ignore_index, int has_ignore,
                                      const int *mask, const float *weight, int weight_per_class, float eps, int eps_rule,
@@ -560,7 +543,6 @@ int amc3d_point_loss_softmax_backward(int B, int C, long N, const float *logits,
                                       const int *mask, const float *weight, int weight_per_class, float eps, int eps_rule,
                                       float gamma, const float *alpha, float poly, int den_mode, const float *lse,
                                       const float *loss_den, const float *grad_out, float *dlogits, void *stream);
-size_t amc3d_point_loss_sigmoid_workspace_bytes(int B, long N);
 int amc3d_point_loss_sigmoid_forward(int B, int C, long N, const float *logits, const long long *target, const float *weight,
                                      const float *pos_weight, float alpha, float gamma, float poly, int den_mode, float *loss_den,
                                      void *workspace, size_t workspace_bytes, void *stream);

@@ -285,6 +285,45 @@ def test_cross_entropy_matches_torch(B, C, N, ignored):
     assert float((lg.grad - lr.grad).abs().max()) <= 1e-6 * max(1.0, float(lr.grad.abs().max()) * 10)
 
 
+@pytest.mark.parametrize("ignored", [0.0, 0.3, 1.0])
+def test_plain_cross_entropy_is_the_softmax_family_form(ignored):
+    """ops.cross_entropy_mean (the native exp / log instantiation of the softmax point-loss kernels) against
+    ops.point_loss_softmax with only ignore_index set (the library instantiation): one formula, so value within
+    1e-5 max(1, |want|) and gradient within 1e-6 max(1, 10 max|grad|) -- the family's bounds against torch, which cover native
+    against library exp / log -- NaN with an all-zero gradient on both when nothing is counted, and the same all-zero gradient
+    rows.  Sizes around the wave (64) and the workgroup (256), one and several clouds, C = 1; every case with more than one
+    point carries one label outside [0, C) that is not the ignore value (the single-point case runs with and without it).
+    The zero rows are exactly the dropped points wherever C >= 2; at C = 1 softmax - onehot is 0 on every row."""
+    from amcontrast3d_amd import ops
+    for B in (1, 3):
+        for C in (1, 2, 13):
+            for N, stray in [(1, False), (1, True), (63, True), (64, True), (65, True), (257, True)]:
+                case = f"B={B} C={C} N={N} ignored={ignored} stray={stray}"
+                g = torch.Generator().manual_seed(1000 * B + 100 * C + N)
+                logits = (torch.randn(B, C, N, generator=g) * 3).to(DEV)
+                target = torch.randint(0, C, (B, N), generator=g)
+                target[torch.rand(B, N, generator=g) < ignored] = -100
+                if stray:
+                    target[B - 1, N - 1] = C + 3
+                target = target.to(DEV)
+                dropped = (target < 0) | (target >= C)
+                xa, xb = logits.clone().requires_grad_(True), logits.clone().requires_grad_(True)
+                got = ops.cross_entropy_mean(xa, target, -100)
+                want = ops.point_loss_softmax(xb, target, ignore_index=-100)
+                (got * 0.7).backward()
+                (want * 0.7).backward()
+                zero_a, zero_b = (xa.grad == 0).all(dim=1), (xb.grad == 0).all(dim=1)
+                if bool(dropped.all()):
+                    assert torch.isnan(got) and torch.isnan(want), case
+                    assert bool(zero_a.all()) and bool(zero_b.all()), case
+                    continue
+                assert abs(float(got) - float(want)) <= 1e-5 * max(1.0, abs(float(want))), (case, float(got), float(want))
+                err, top = float((xa.grad - xb.grad).abs().max()), float(xb.grad.abs().max())
+                assert err <= 1e-6 * max(1.0, 10 * top), (case, err, top)
+                assert torch.equal(zero_a, zero_b), case
+                assert torch.equal(zero_a, dropped if C >= 2 else torch.ones_like(dropped)), case
+
+
 @pytest.mark.parametrize("B,C,N,ignore", [(8, 13, 24000, None), (2, 20, 5000, -100), (1, 13, 77, None), (3, 5, 1000, 255)])
 def test_confusion_matrix_from_logits_is_update_of_the_argmax(B, C, N, ignore):
     """ConfusionMatrix.update_from_logits (one launch: csrc/loss.hip confusion_kernel) == update(logits.argmax(dim=1), target),

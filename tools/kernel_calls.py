@@ -1,8 +1,9 @@
 """every launch of the kernels whose name contains <pattern> in the last step of a rocprofv3 rocpd database, in launch order,
-with grid / workgroup size and duration:  python kernel_calls.py db pattern [marker=ce_forward_kernel]"""
+with grid / workgroup size and duration:  python kernel_calls.py db pattern [marker=pl_softmax_forward_kernel<true>]
+(the default marker is the plain cross entropy's forward launch, the native instantiation of the softmax point-loss kernel)"""
 import sqlite3, sys
 db, pat = sys.argv[1], sys.argv[2]
-marker = sys.argv[3] if len(sys.argv) > 3 else "ce_forward_kernel"
+marker = sys.argv[3] if len(sys.argv) > 3 else "pl_softmax_forward_kernel<true>"
 c = sqlite3.connect(db)
 cols = [r[1] for r in c.execute("pragma table_info(kernels)")]
 want = [k for k in ("grid_x", "grid_y", "grid_z", "workgroup_x", "grid_size_x", "grid_size_y", "grid_size_z", "workgroup_size_x", "lds_size", "lds_block_size") if k in cols]

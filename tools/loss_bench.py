@@ -1,5 +1,5 @@
-"""Each plain criterion of openpoints.loss, forward + backward, on the point-loss kernels against the torch composition of the
-same module on the same inputs (the route CPU tensors and (M, C) rows take, here run on the device), at 8 x 13 x 24000 and
+"""Each plain criterion of openpoints.loss (the registry's CrossEntropy with smoothing / weights among them), forward +
+backward, on the point-loss kernels against the torch composition of the same module on the same inputs (the route CPU tensors and (M, C) rows take, here run on the device), at 8 x 13 x 24000 and
 2 x 20 x 64000 logits: device-event times, median of --repeats calls after --warmup untimed ones.
 
     python tools/loss_bench.py [--repeats 50] [--warmup 5]
@@ -28,7 +28,9 @@ dev = torch.device("cuda:0")
 
 def forms(C):
     w = 0.5 + 1.5 * ((np.arange(C) * 7) % 5) / 4.0
-    return [("SmoothCrossEntropy", {}), ("SmoothCrossEntropy eps=0 weight", {"label_smoothing": 0, "weight": w}),
+    return [("CrossEntropy label_smoothing=0.2", {"label_smoothing": 0.2}),
+            ("CrossEntropy label_smoothing=0.2 weight", {"label_smoothing": 0.2, "weight": torch.tensor(w, dtype=torch.float32)}),
+            ("SmoothCrossEntropy", {}), ("SmoothCrossEntropy eps=0 weight", {"label_smoothing": 0, "weight": w}),
             ("SmoothCrossEntropy ignore_index=3 weight", {"ignore_index": 3, "num_classes": C, "weight": w}),
             ("MaskedCrossEntropy", {}), ("BCELogits", {}), ("FocalLoss gamma=2", {"gamma": 2}),
             ("FocalLoss gamma=0.5 alpha", {"gamma": 0.5, "alpha": [0.5] * C}), ("Poly1CrossEntropyLoss", {"num_classes": C}),

@@ -1,10 +1,11 @@
 """Summarise a rocprofv3 --pmc pass (rocpd sqlite) into per-kernel sums over the LAST nsteps train steps (the window between
 launches of a once-per-step marker kernel; warm-up steps -- MIOpen find mode, allocator growth -- lie before it):
-python pmc_extract.py db counter out.csv [nsteps=3] [marker=ce_forward_kernel]"""
+python pmc_extract.py db counter out.csv [nsteps=3] [marker=pl_softmax_forward_kernel<true>]
+(the default marker is the plain cross entropy's forward launch, the native instantiation of the softmax point-loss kernel)"""
 import csv, sqlite3, sys
 db, counter, out = sys.argv[1:4]
 nsteps = int(sys.argv[4]) if len(sys.argv) > 4 else 3
-marker = sys.argv[5] if len(sys.argv) > 5 else "ce_forward_kernel"
+marker = sys.argv[5] if len(sys.argv) > 5 else "pl_softmax_forward_kernel<true>"
 c = sqlite3.connect(db)
 tabs = [r[0] for r in c.execute("select name from sqlite_master where type in ('table','view')")]
 view = "counters_collection" if "counters_collection" in tabs else None

@@ -1,10 +1,11 @@
 """Per-kernel statistics of the steady-state train step from a rocprofv3 --kernel-trace rocpd database of
-`bench.py --lean` (the process ends right after the timed loop):  python steady2.py db out.csv [nsteps=5] [marker=ce_forward_kernel]
-The window is the last nsteps steps, delimited by launches of a kernel that runs exactly once per step."""
+`bench.py --lean` (the process ends right after the timed loop):  python steady2.py db out.csv [nsteps=5] [marker=pl_softmax_forward_kernel<true>]
+The window is the last nsteps steps, delimited by launches of a kernel that runs exactly once per step (the default: the plain
+cross entropy's forward launch, the native instantiation of the softmax point-loss kernel)."""
 import collections, csv, sqlite3, sys
 db, out = sys.argv[1], sys.argv[2]
 n = int(sys.argv[3]) if len(sys.argv) > 3 else 5
-marker = sys.argv[4] if len(sys.argv) > 4 else "ce_forward_kernel"
+marker = sys.argv[4] if len(sys.argv) > 4 else "pl_softmax_forward_kernel<true>"
 c = sqlite3.connect(db)
 ks = c.execute("select start,end,name,stream_id from kernels order by start").fetchall()
 g = [k for k in ks if marker in k[2]]
