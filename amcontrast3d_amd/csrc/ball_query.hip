@@ -16,6 +16,7 @@
 // L2 once per 16 queries.  A wave stops testing a query once it has nsample
 // hits; the block leaves the scan when all its queries are full.
 #include "common.h"
+#include "grid_search.h"
 
 namespace amc {
 
@@ -135,13 +136,6 @@ __global__ void group_points_grad_kernel(int c, int n, int ps, const float *__re
 }  // namespace amc
 
 using namespace amc;
-
-namespace amc {
-bool grid_search_pays(int b, int n, int m);
-size_t grid_search_workspace_bytes(int b, int n, int m);
-int ball_query_grid(int b, int n, int m, float radius, int nsample, const float *new_xyz, const float *xyz, int *idx,
-                    void *workspace, hipStream_t stream);
-}
 
 AMC_API size_t amc3d_grid_search_workspace_bytes(int b, int n_support, int m_queries)
 {

@@ -1,6 +1,7 @@
 // three_nn / three_interpolate (+grad) for gfx950.
 // Reference: pointnet2_batch/src/interpolate_gpu.cu:16-59, 84-104, 127-149.
 #include "common.h"
+#include "grid_search.h"
 
 namespace amc {
 
@@ -289,13 +290,6 @@ static int igl_launch(int b, int c, int n, int m, int cg, int threads, bool accu
 }  // namespace amc
 
 using namespace amc;
-
-namespace amc {
-bool grid_search_pays(int b, int n, int m);
-size_t grid_search_workspace_bytes(int b, int n, int m);
-int three_nn_grid(int b, int n, int m, const float *unknown, const float *known, float *dist2, int *idx, void *workspace,
-                  hipStream_t stream);
-}
 
 AMC_API int amc3d_three_nn(int b, int n, int m, const float *unknown, const float *known, float *dist2,
                            int *idx, void *workspace, size_t workspace_bytes, void *stream)

@@ -40,6 +40,14 @@ __device__ __forceinline__ void reheap(float *dist, int *idx, int k)
     }
 }
 
+// segment of point/query `i` given cumulative ends (knnquery_cuda_kernel.cu:51-62,74-80)
+__device__ __forceinline__ int seg_of(int i, const int *__restrict__ ends, int nb)
+{
+    int s = 0;
+    while (s < nb - 1 && !(i < ends[s])) ++s;
+    return s;
+}
+
 // queries: either all of 0..m-1 (qlist == nullptr) or the first *qcount entries of qlist
 __global__ __launch_bounds__(KNN_WAVES * 64) void knn_exact_kernel(
     int m, int nsample, int nbatch, const float *__restrict__ xyz, const float *__restrict__ new_xyz,
@@ -58,11 +66,9 @@ __global__ __launch_bounds__(KNN_WAVES * 64) void knn_exact_kernel(
         const int qi = base + wave;
         const bool live = qi < total;
         const int pt = live ? (qlist ? qlist[qi] : qi) : 0;
-        // knnquery_cuda_kernel.cu:51-62,74-80: segment of this query
         int start = 0, end = 0;
         if (live) {
-            int bt = 0;
-            while (bt < nbatch - 1 && !(pt < new_offset[bt])) bt++;
+            const int bt = seg_of(pt, new_offset, nbatch);
             start = bt == 0 ? 0 : offset[bt - 1];
             end = offset[bt];
         }
@@ -131,35 +137,54 @@ __global__ __launch_bounds__(KNN_WAVES * 64) void knn_exact_kernel(
 // around it, then shells of growing Chebyshev radius R, until its current k-th distance is
 // provably smaller than the distance to anything outside the scanned block.
 //
-// Exactness.  One wavefront owns one query and keeps its k best candidates in lanes 0..k-1,
-// sorted ascending (insertion = one ballot + a lane shift).  When the k+1 smallest distances of a
+// The walk (QueryCell, shell_pair_runs).  A query's cell (cx,cy,cz) is its clamped cell coordinate in its
+// segment's grid.  Shell R is walked as its (2R+1)^2 (dz,dy) pairs; x is the fastest cell axis, so a pair's cells
+// are one run [b, e) of sorted[].  A pair on the shell's rim contributes the full x-run [cx-R, cx+R], an interior
+// pair only its two end cells (the cells between belong to smaller shells); for R == 1 every pair contributes the
+// full run: the whole 3x3x3 block.  Rows outside the grid contribute nothing.  The replay's pruning set and ball
+// query take the whole (2R+1)^3 block at once: the full run of every pair.
+//
+// The stop rule (shell_unseen_bound, shell_closed).  After shell R everything unseen lies beyond one of the six faces
+// of the block [c-R, c+R]^3; a face that coincides with the grid's boundary imposes nothing (there are no points
+// beyond it), and a block that covers the whole grid ends the search.  The nearest remaining face is `dmin` away;
+// cell coordinates are formed in fp32, so `margin` (kg_params_kernel) is taken off, and the search ends once
+// k-th < (dmin - margin)^2 * 0.99999.  Every kernel that walks shells takes both from these helpers: exactness
+// rests on this arithmetic.
+//
+// Exactness.  kg_query_kernel (k in 33..64): one wavefront owns one query and keeps its k best candidates in lanes
+// 0..k-1, sorted ascending (insertion = one ballot + a lane shift).  kg_query_group_kernel<32> (k <= 32): a wavefront
+// serves two queries, 32 lanes each: same search, same lists.  When the k+1 smallest distances of a
 // query are pairwise different, the reference's max-heap + heap-sort output is fully determined:
 // those k indices in ascending distance -- independent of scan order -- which is what the lane
 // list holds.  When two of them are EQUAL the reference's output depends on its heap history
-// (index scan order); such queries are detected (adjacent equal values in the list, or the best
-// rejected distance equal to the k-th) and recomputed by knn_exact_kernel, which replays the
-// reference's heap.  Distances are always the reference's expression (dist2_ref).  For k <= 32 a wavefront serves
-// two queries, 32 lanes each (kg_query_group_kernel, further down): same search, same lists.
+// (index scan order); such queries are detected (list_tied: adjacent equal values in the list, or the best
+// rejected distance equal to the k-th), listed, and recomputed by knn_exact_list_kernel, which replays the
+// reference's heap over a prefix of the segment that the grid prunes.  (knn_exact_kernel, the all-pairs replay,
+// answers the calls that build no grid: k > 64 and small problems.)  Distances are always the reference's
+// expression (dist2_ref).
 //
 // Cell size.  h is calibrated on the data, per call: 64 sample queries get an estimate of their k-th
 // neighbour distance from a brute-force scan of every 4th support point (one workgroup each), and
 // h = 0.7 * the 80th percentile, so that the 3x3x3 block holds a few k candidates whatever the density or
 // dimensionality of the cloud (surfaces, volumes, 8 overlapping clouds in one segment...); queries whose k-th
-// neighbour lies beyond the block go on to the next shell.  (Sub-sampling step and scale: swept on the loss's
-// seven searches with scratch/knn_sweep.sh, see amc3d_knnquery.)
-// h steers speed only; any h gives the same results.
+// neighbour lies beyond the block go on to the next shell.  (Sub-sampling step 4 and scale 0.7 came out of a sweep
+// of both over the loss's seven searches at 8 x 24000 points, the shape of tools/knn_bench.py; the sweep script is
+// not kept.)  h steers speed only; any h gives the same results.
 // =============================================================================================
 constexpr int KG_SAMPLES = 64;
 constexpr int KG_MAXK = 64;
 constexpr int KGG_MAXK = 32;  // up to here a wavefront serves two queries (kg_query_group_kernel<32>)
+constexpr int KG_SCAN_TILE = 4096;  // cells per workgroup of the cell-count scan (256 threads x 16)
 
 struct GridParams {
     float minx, miny, minz, h, inv_h, margin;
     int nx, ny, nz, ncell;  // per segment
 };
 
+constexpr int KG_MAX_BATCH = 64;  // segments of a grid search (amc3d_knnquery_uses_grid, grid_search_pays)
+
 struct KnnWorkspace {           // byte offsets into the caller's workspace
-    size_t params, bbox, samples, fb_count, tile_sums, cell_start, cursor, sorted, fb_list, total;
+    size_t params, bbox, samples, off_s, fb_count, tile_sums, off_q, cell_start, cursor, sorted, fb_list, total;
 };
 
 __host__ __device__ inline int knn_cell_cap(int n)
@@ -175,12 +200,21 @@ static KnnWorkspace knn_layout(int n, int m)
     KnnWorkspace w;
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t cap = (size_t)knn_cell_cap(n);
+    // the fixed head; off_s / off_q (ball query's and 3-NN's uniform segment ends, KG_MAX_BATCH ints each) sit in
+    // the gaps behind samples and tile_sums
+    constexpr size_t samples = 512, off_s = 768, fb_count = 1024, tile_sums = 2048, off_q = 6400, cell_start = 8192;
+    constexpr size_t max_tiles = ((size_t)1 << 22) / KG_SCAN_TILE;  // knn_cell_cap: at most 2^22 cells
+    static_assert(samples + KG_SAMPLES * 4 <= off_s && off_s + KG_MAX_BATCH * 4 <= fb_count, "knn_layout: off_s");
+    static_assert(tile_sums + (max_tiles + 1) * 4 <= off_q && off_q + KG_MAX_BATCH * 4 <= cell_start, "knn_layout: off_q");
+    static_assert(fb_count == AMC_KNN_FALLBACK_COUNT_OFFSET, "knn_layout: fb_count");
     w.params = 0;
     w.bbox = 256;
-    w.samples = 512;
-    w.fb_count = 1024;
-    w.tile_sums = 2048;  // 1025 ints
-    w.cell_start = 8192;
+    w.samples = samples;
+    w.off_s = off_s;
+    w.fb_count = fb_count;
+    w.tile_sums = tile_sums;
+    w.off_q = off_q;
+    w.cell_start = cell_start;
     w.cursor = up(w.cell_start + (cap + 1) * 4);
     w.sorted = up(w.cursor + (cap + 1) * 4);
     w.fb_list = up(w.sorted + (size_t)n * 16);
@@ -234,14 +268,6 @@ __global__ __launch_bounds__(256) void kg_bbox_kernel(int n, const float *__rest
         atomicMin(bbox + c, f2ord(l));
         atomicMax(bbox + 3 + c, f2ord(h));
     }
-}
-
-// segment [start,end) of point/query `i` given cumulative ends (knnquery_cuda_kernel.cu:51-62,74-80)
-__device__ __forceinline__ int seg_of(int i, const int *__restrict__ ends, int nb)
-{
-    int s = 0;
-    while (s < nb - 1 && !(i < ends[s])) ++s;
-    return s;
 }
 
 // ---- a wavefront's sorted list of its k best candidates (lanes 0..k-1) ---------------------------
@@ -321,6 +347,21 @@ __device__ __forceinline__ void ll_sort_first(LaneList &l, int k, int lane, bool
     l.id = id;
     l.tau = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k - 1));
     if (k < 64) rej_uni = fminf(rej_uni, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k)));  // best dropped
+}
+
+// Ties among the k+1 smallest distances of a finished list of G lanes (gl: the lane within it) -> the reference's order
+// depends on its heap history.  Two adjacent equal values in the list, or the best rejected distance (rl per lane,
+// ru list-uniform) equal to the k-th.  True in the lane that sees the tie: the caller ballots.
+template <int G>
+__device__ __forceinline__ bool list_tied(const LaneList &l, int k, int gl, float rl, float ru)
+{
+#pragma unroll
+    for (int s = G / 2; s >= 1; s >>= 1) rl = fminf(rl, __shfl_xor(rl, s, 64));
+    const float rej = fminf(rl, ru);
+    const float nextv = __shfl_down(l.v, 1, G);
+    const bool tie_in = gl < k - 1 && l.v == nextv && l.v < 1e10f;
+    const bool tie_edge = gl == k - 1 && l.v < 1e10f && rej == l.v;
+    return tie_in || tie_edge;
 }
 
 // ---- calibration: k-th neighbour distance of KG_SAMPLES queries, estimated on every 8th support point
@@ -404,6 +445,75 @@ __device__ __forceinline__ int cell_coord(float v, float mn, float inv_h, int di
     return min(max(c, 0), dim - 1);
 }
 
+// ---- the walk and the stop rule ("Grid-accelerated path" above), shared by every kernel that searches the grid ----
+struct QueryCell {
+    float qx, qy, qz;  // the query
+    int cx, cy, cz;    // its (clamped) cell
+    const int *cs;     // cell_start of its segment's grid
+};
+
+__device__ __forceinline__ QueryCell query_cell(const GridParams &g, const float *__restrict__ new_xyz, int q, int seg,
+                                                const int *__restrict__ cell_start)
+{
+    QueryCell h;
+    h.qx = new_xyz[(size_t)q * 3]; h.qy = new_xyz[(size_t)q * 3 + 1]; h.qz = new_xyz[(size_t)q * 3 + 2];
+    h.cx = cell_coord(h.qx, g.minx, g.inv_h, g.nx);
+    h.cy = cell_coord(h.qy, g.miny, g.inv_h, g.ny);
+    h.cz = cell_coord(h.qz, g.minz, g.inv_h, g.nz);
+    h.cs = cell_start + (size_t)seg * g.ncell;
+    return h;
+}
+
+// The x-runs [bA, eA) and [bB, eB) of sorted[] that row (dz,dy) of shell R contributes: the full run where the row is
+// on the rim (or R == 1, or the caller wants the whole block), else the two end cells; empty outside the grid.
+__device__ __forceinline__ void shell_row_runs(const GridParams &g, const int *__restrict__ cs, int cx, int cy, int cz, int R,
+                                               int dz, int dy, bool whole_block, int &bA, int &eA, int &bB, int &eB)
+{
+    bA = 0; eA = 0; bB = 0; eB = 0;
+    const int z = cz + dz, y = cy + dy;
+    if (z < 0 || z >= g.nz || y < 0 || y >= g.ny) return;
+    const int row = (z * g.ny + y) * g.nx;
+    if (whole_block || R == 1 || dz == -R || dz == R || dy == -R || dy == R) {
+        bA = cs[row + max(cx - R, 0)];
+        eA = cs[row + min(cx + R, g.nx - 1) + 1];
+    } else {
+        if (cx - R >= 0) { bA = cs[row + cx - R]; eA = cs[row + cx - R + 1]; }
+        if (cx + R < g.nx) { bB = cs[row + cx + R]; eB = cs[row + cx + R + 1]; }
+    }
+}
+
+// the same for pair pi = (dz + R) * (2R+1) + (dy + R) of the shell; pi >= (2R+1)^2 gives empty runs
+__device__ __forceinline__ void shell_pair_runs(const GridParams &g, const int *__restrict__ cs, int cx, int cy, int cz, int R,
+                                                int pi, bool whole_block, int &bA, int &eA, int &bB, int &eB)
+{
+    const int side = 2 * R + 1;
+    if (pi < side * side) shell_row_runs(g, cs, cx, cy, cz, R, pi / side - R, pi % side - R, whole_block, bA, eA, bB, eB);
+    else { bA = 0; eA = 0; bB = 0; eB = 0; }
+}
+
+// dmin - margin: nothing outside the block [c-R, c+R]^3 is nearer to the query; `whole`: the block covers the grid
+__device__ __forceinline__ float shell_unseen_bound(const GridParams &g, const QueryCell &h, int R, bool &whole)
+{
+    float dmin = 3.4e38f;
+    whole = true;
+    if (h.cx - R > 0) { dmin = fminf(dmin, h.qx - (g.minx + (float)(h.cx - R) * g.h)); whole = false; }
+    if (h.cx + R + 1 < g.nx) { dmin = fminf(dmin, (g.minx + (float)(h.cx + R + 1) * g.h) - h.qx); whole = false; }
+    if (h.cy - R > 0) { dmin = fminf(dmin, h.qy - (g.miny + (float)(h.cy - R) * g.h)); whole = false; }
+    if (h.cy + R + 1 < g.ny) { dmin = fminf(dmin, (g.miny + (float)(h.cy + R + 1) * g.h) - h.qy); whole = false; }
+    if (h.cz - R > 0) { dmin = fminf(dmin, h.qz - (g.minz + (float)(h.cz - R) * g.h)); whole = false; }
+    if (h.cz + R + 1 < g.nz) { dmin = fminf(dmin, (g.minz + (float)(h.cz + R + 1) * g.h) - h.qz); whole = false; }
+    return dmin - g.margin;
+}
+
+// squared distance below which a candidate is strictly nearer than anything unseen (0: no such distance)
+__device__ __forceinline__ float shell_safe_d2(float bound) { return bound > 0.f ? bound * bound * 0.99999f : 0.f; }
+
+// the search may end: the k-th (worst kept) squared distance `kth` is strictly nearer than anything unseen
+__device__ __forceinline__ bool shell_closed(float bound, bool whole, float kth)
+{
+    return whole || kth < shell_safe_d2(bound);  // (kth >= 0: a bound <= 0 closes nothing)
+}
+
 __global__ void kg_count_kernel(int n, int nb, const float *__restrict__ xyz, const int *__restrict__ offset,
                                 const GridParams *__restrict__ gp, int *__restrict__ cell_count)
 {
@@ -421,8 +531,6 @@ __global__ void kg_count_kernel(int n, int nb, const float *__restrict__ xyz, co
 // KG_SCAN_TILE cells: per-tile sums, scan of the (<= 1024) tile sums, per-tile scan + offset.
 // The cell count is only known on the device, so the grid is sized for the cell budget and
 // surplus workgroups return.
-constexpr int KG_SCAN_TILE = 4096;  // cells per workgroup (256 threads x 16)
-
 __device__ __forceinline__ int block_excl_scan_256(int v, int *s_part, int &block_total)
 {
     // exclusive scan of one int per thread across a 256-thread workgroup
@@ -508,32 +616,50 @@ __global__ void kg_scatter_kernel(int n, int nb, const float *__restrict__ xyz, 
 }
 
 // ---- queries --------------------------------------------------------------------------------------
-__device__ __forceinline__ void kg_scan_packed(LaneList &l, int k, int lane, int b, int len, float qx, float qy, float qz,
-                                               const float4 *__restrict__ sorted, float &rl, float &ru, bool &fresh,
-                                               int start)
+// Packed runs.  The x-runs of a shell are short (a few points per cell), so a wavefront feeds them PACKED, 64 candidates
+// per step, instead of one partly filled step per run: lane r owns run [b, b + len) of sorted[], an exclusive scan of
+// the run lengths gives every candidate slot c its run (the last non-empty one whose first slot is <= c) and its
+// place in it.
+// -> number of slots (wave-uniform); excl: this lane's first slot
+__device__ __forceinline__ int packed_scan(int len, int lane, int &excl)
 {
     int incl = len;
     for (int s = 1; s < 64; s <<= 1) {
         const int o = __shfl_up(incl, s, 64);
         if (lane >= s) incl += o;
     }
-    const int total = __builtin_amdgcn_readlane(incl, 63);
-    const int excl = incl - len;
+    excl = incl - len;
+    return __builtin_amdgcn_readlane(incl, 63);
+}
+
+// position in sorted[] of slot c of the step [c0, c0 + 64); runs = __ballot(len > 0)
+__device__ __forceinline__ int packed_slot_source(int c, int c0, unsigned long long runs, int excl, int b)
+{
+    int base = 0;
+    while (runs) {
+        const int src = (int)__builtin_ctzll(runs);
+        runs &= runs - 1;
+        const int e0 = __builtin_amdgcn_readlane(excl, src);
+        if (e0 >= c0 + 64) break;  // later runs start beyond this step (wave-uniform)
+        const int b0 = __builtin_amdgcn_readlane(b, src);
+        base = c >= e0 ? b0 - e0 : base;
+    }
+    return base + c;
+}
+
+// `fresh`: nothing is in the list yet (wave-uniform)
+__device__ __forceinline__ void kg_scan_packed(LaneList &l, int k, int lane, int b, int len, float qx, float qy, float qz,
+                                               const float4 *__restrict__ sorted, float &rl, float &ru, bool &fresh,
+                                               int start)
+{
+    int excl;
+    const int total = packed_scan(len, lane, excl);
     const unsigned long long runs = __ballot(len > 0);
     for (int c0 = 0; c0 < total; c0 += 64) {
         const int c = c0 + lane;
-        int base = 0;
-        unsigned long long rm = runs;
-        while (rm) {
-            const int src = (int)__builtin_ctzll(rm);
-            rm &= rm - 1;
-            const int e0 = __builtin_amdgcn_readlane(excl, src);
-            if (e0 >= c0 + 64) break;  // later runs start beyond this step (wave-uniform)
-            const int b0 = __builtin_amdgcn_readlane(b, src);
-            base = c >= e0 ? b0 - e0 : base;
-        }
+        const int src = packed_slot_source(c, c0, runs, excl, b);
         const bool valid = c < total;
-        const float4 p = sorted[valid ? base + c : __builtin_amdgcn_readfirstlane(base + c)];
+        const float4 p = sorted[valid ? src : __builtin_amdgcn_readfirstlane(src)];
         const float d2 = dist2_ref(qx, qy, qz, p.x, p.y, p.z);
         if (fresh) {  // wave-uniform: nothing in the list yet
             ll_sort_first(l, k, lane, valid, d2, __float_as_int(p.w), start, ru);
@@ -561,67 +687,27 @@ __global__ __launch_bounds__(256) void kg_query_kernel(int m, int k, int nb, int
         const int q = self ? __float_as_int(sorted[t].w) : t;
         const int seg = nb > 1 ? seg_of(q, new_offset, nb) : 0;
         const int start = seg == 0 ? 0 : offset[seg - 1];
-        const float qx = new_xyz[(size_t)q * 3], qy = new_xyz[(size_t)q * 3 + 1], qz = new_xyz[(size_t)q * 3 + 2];
-        const int cx = cell_coord(qx, g.minx, g.inv_h, g.nx), cy = cell_coord(qy, g.miny, g.inv_h, g.ny),
-                  cz = cell_coord(qz, g.minz, g.inv_h, g.nz);
-        const int *cs = cell_start + (size_t)seg * g.ncell;
+        const QueryCell h = query_cell(g, new_xyz, q, seg, cell_start);
         LaneList l;
         ll_init(l, start);
         float rl = 3.4e38f, ru = 3.4e38f;
         bool fresh = true;
 
         for (int R = 1;; ++R) {
-            // (dz,dy) pairs of this shell, one per lane, in batches of 64: a pair on the shell's
-            // rim contributes the full x-run [cx-R, cx+R]; an interior pair only its two end cells
-            // (for R == 1 every pair contributes the full run: the whole 3x3x3 block)
-            const int side = 2 * R + 1, npairs = side * side;
+            // the shell's (dz,dy) pairs, one per lane, in batches of 64
+            const int npairs = (2 * R + 1) * (2 * R + 1);
             for (int p0 = 0; p0 < npairs; p0 += 64) {
-                const int pi = p0 + lane;
-                int bA = 0, eA = 0, bB = 0, eB = 0;
-                if (pi < npairs) {
-                    const int dz = pi / side - R, dy = pi % side - R;
-                    const int z = cz + dz, y = cy + dy;
-                    if (z >= 0 && z < g.nz && y >= 0 && y < g.ny) {
-                        const int row = (z * g.ny + y) * g.nx;
-                        const bool rim = R == 1 || dz == -R || dz == R || dy == -R || dy == R;
-                        if (rim) {
-                            const int x0 = max(cx - R, 0), x1 = min(cx + R, g.nx - 1);
-                            bA = cs[row + x0];
-                            eA = cs[row + x1 + 1];
-                        } else {
-                            if (cx - R >= 0) { bA = cs[row + cx - R]; eA = cs[row + cx - R + 1]; }
-                            if (cx + R < g.nx) { bB = cs[row + cx + R]; eB = cs[row + cx + R + 1]; }
-                        }
-                    }
-                }
-                // the runs are short (a few points per cell): feed them PACKED, 64 candidates per step, instead of
-                // one partly filled step per run.  Lane pi owns run pi; an exclusive scan of the run lengths gives
-                // every candidate slot c its run (the last one whose first slot is <= c) and its place in it.
-                kg_scan_packed(l, k, lane, bA, eA - bA, qx, qy, qz, sorted, rl, ru, fresh, start);
-                if (R > 1) kg_scan_packed(l, k, lane, bB, eB - bB, qx, qy, qz, sorted, rl, ru, fresh, start);
+                int bA, eA, bB, eB;
+                shell_pair_runs(g, h.cs, h.cx, h.cy, h.cz, R, p0 + lane, false, bA, eA, bB, eB);
+                kg_scan_packed(l, k, lane, bA, eA - bA, h.qx, h.qy, h.qz, sorted, rl, ru, fresh, start);
+                if (R > 1) kg_scan_packed(l, k, lane, bB, eB - bB, h.qx, h.qy, h.qz, sorted, rl, ru, fresh, start);
             }
-            // everything outside the scanned block is at least `dmin` away (sides that coincide with
-            // the grid boundary impose nothing: there are no points beyond it)
-            float dmin = 3.4e38f;
-            bool whole = true;
-            if (cx - R > 0) { dmin = fminf(dmin, qx - (g.minx + (float)(cx - R) * g.h)); whole = false; }
-            if (cx + R + 1 < g.nx) { dmin = fminf(dmin, (g.minx + (float)(cx + R + 1) * g.h) - qx); whole = false; }
-            if (cy - R > 0) { dmin = fminf(dmin, qy - (g.miny + (float)(cy - R) * g.h)); whole = false; }
-            if (cy + R + 1 < g.ny) { dmin = fminf(dmin, (g.miny + (float)(cy + R + 1) * g.h) - qy); whole = false; }
-            if (cz - R > 0) { dmin = fminf(dmin, qz - (g.minz + (float)(cz - R) * g.h)); whole = false; }
-            if (cz + R + 1 < g.nz) { dmin = fminf(dmin, (g.minz + (float)(cz + R + 1) * g.h) - qz); whole = false; }
-            if (whole) break;
-            dmin -= g.margin;
-            if (dmin > 0.f && l.tau < dmin * dmin * 0.99999f) break;
+            bool whole;
+            const float bound = shell_unseen_bound(g, h, R, whole);
+            if (shell_closed(bound, whole, l.tau)) break;
         }
 
-        // ties among the k+1 smallest distances -> the reference's order depends on its heap history
-        for (int s = 32; s >= 1; s >>= 1) rl = fminf(rl, __shfl_xor(rl, s, 64));
-        const float rej = fminf(rl, ru);
-        const float nextv = __shfl_down(l.v, 1, 64);
-        const bool tie_in = lane < k - 1 && l.v == nextv && l.v < 1e10f;
-        const bool tie_edge = lane == k - 1 && l.v < 1e10f && rej == l.v;
-        if (__ballot(tie_in || tie_edge)) {
+        if (__ballot(list_tied<64>(l, k, lane, rl, ru))) {
             if (lane == 0) fb_list[atomicAdd(fb_count, 1)] = q;
         } else if (lane < k) {
             idx[(size_t)q * k + lane] = l.id;
@@ -791,62 +877,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         const int q = self ? __float_as_int(sorted[tq].w) : tq;
         const int seg = nb > 1 ? seg_of(q, new_offset, nb) : 0;
         const int start = seg == 0 ? 0 : offset[seg - 1];
-        const float qx = new_xyz[(size_t)q * 3], qy = new_xyz[(size_t)q * 3 + 1], qz = new_xyz[(size_t)q * 3 + 2];
-        const int cx = cell_coord(qx, g.minx, g.inv_h, g.nx), cy = cell_coord(qy, g.miny, g.inv_h, g.ny),
-                  cz = cell_coord(qz, g.minz, g.inv_h, g.nz);
-        const int *cs = cell_start + (size_t)seg * g.ncell;
+        const QueryCell h = query_cell(g, new_xyz, q, seg, cell_start);
         LaneList l;
         ll_init(l, start);  // a segment with fewer than k points leaves the placeholders (1e10, start) at the tail
         float rl = 3.4e38f, ru = 3.4e38f;
         bool act = true;  // group-uniform: this group's search goes on
 
         for (int R = 1;; ++R) {
-            // the shell's (dz,dy) pairs as in kg_query_kernel, G per batch: the 9 pairs of R == 1 and the 25 of
-            // R == 2 fit one batch of 32
-            const int side = 2 * R + 1, npairs = side * side;
+            // the shell's (dz,dy) pairs, G per batch: the 9 pairs of R == 1 and the 25 of R == 2 fit one batch of 32;
+            // a finished group asks for the pair past the last, which has no runs
+            const int npairs = (2 * R + 1) * (2 * R + 1);
             for (int p0 = 0; p0 < npairs; p0 += G) {
-                const int pi = p0 + gl;
-                int bA = 0, eA = 0, bB = 0, eB = 0;
-                if (act && pi < npairs) {
-                    const int dz = pi / side - R, dy = pi % side - R;
-                    const int z = cz + dz, y = cy + dy;
-                    if (z >= 0 && z < g.nz && y >= 0 && y < g.ny) {
-                        const int row = (z * g.ny + y) * g.nx;
-                        const bool rim = R == 1 || dz == -R || dz == R || dy == -R || dy == R;
-                        if (rim) {
-                            const int x0 = max(cx - R, 0), x1 = min(cx + R, g.nx - 1);
-                            bA = cs[row + x0];
-                            eA = cs[row + x1 + 1];
-                        } else {
-                            if (cx - R >= 0) { bA = cs[row + cx - R]; eA = cs[row + cx - R + 1]; }
-                            if (cx + R < g.nx) { bB = cs[row + cx + R]; eB = cs[row + cx + R + 1]; }
-                        }
-                    }
-                }
-                gl_scan_packed<G>(l, k, lane, gl, bA, eA - bA, qx, qy, qz, sorted, rl, ru);
-                if (R > 1) gl_scan_packed<G>(l, k, lane, gl, bB, eB - bB, qx, qy, qz, sorted, rl, ru);
+                int bA, eA, bB, eB;
+                shell_pair_runs(g, h.cs, h.cx, h.cy, h.cz, R, act ? p0 + gl : npairs, false, bA, eA, bB, eB);
+                gl_scan_packed<G>(l, k, lane, gl, bA, eA - bA, h.qx, h.qy, h.qz, sorted, rl, ru);
+                if (R > 1) gl_scan_packed<G>(l, k, lane, gl, bB, eB - bB, h.qx, h.qy, h.qz, sorted, rl, ru);
             }
-            float dmin = 3.4e38f;
-            bool whole = true;
-            if (cx - R > 0) { dmin = fminf(dmin, qx - (g.minx + (float)(cx - R) * g.h)); whole = false; }
-            if (cx + R + 1 < g.nx) { dmin = fminf(dmin, (g.minx + (float)(cx + R + 1) * g.h) - qx); whole = false; }
-            if (cy - R > 0) { dmin = fminf(dmin, qy - (g.miny + (float)(cy - R) * g.h)); whole = false; }
-            if (cy + R + 1 < g.ny) { dmin = fminf(dmin, (g.miny + (float)(cy + R + 1) * g.h) - qy); whole = false; }
-            if (cz - R > 0) { dmin = fminf(dmin, qz - (g.minz + (float)(cz - R) * g.h)); whole = false; }
-            if (cz + R + 1 < g.nz) { dmin = fminf(dmin, (g.minz + (float)(cz + R + 1) * g.h) - qz); whole = false; }
-            dmin -= g.margin;
-            if (whole || (dmin > 0.f && l.tau < dmin * dmin * 0.99999f)) act = false;
+            bool whole;
+            const float bound = shell_unseen_bound(g, h, R, whole);
+            if (shell_closed(bound, whole, l.tau)) act = false;
             if (!__ballot(act)) break;  // the wave goes on while any of its groups does
         }
 
-        // ties among the k+1 smallest distances -> the reference's order depends on its heap history
-#pragma unroll
-        for (int s = G / 2; s >= 1; s >>= 1) rl = fminf(rl, __shfl_xor(rl, s, 64));
-        const float rej = fminf(rl, ru);
-        const float nextv = __shfl_down(l.v, 1, G);
-        const bool tie_in = gl < k - 1 && l.v == nextv && l.v < 1e10f;
-        const bool tie_edge = gl == k - 1 && l.v < 1e10f && rej == l.v;
-        const bool tied = grp_bits<G>(__ballot(tie_in || tie_edge), lane) != 0;
+        const bool tied = grp_bits<G>(__ballot(list_tied<G>(l, k, gl, rl, ru)), lane) != 0;
         if (live) {
             if (tied) {
                 if (gl == 0) fb_list[atomicAdd(fb_count, 1)] = q;
@@ -922,8 +975,7 @@ __global__ __launch_bounds__(1024) void knn_exact_list_kernel(
     const int total = *qcount;
     for (int qi = blockIdx.x; qi < total; qi += gridDim.x) {
         const int pt = qlist[qi];
-        int bt = 0;
-        while (bt < nbatch - 1 && !(pt < new_offset[bt])) bt++;
+        const int bt = seg_of(pt, new_offset, nbatch);
         const int start = bt == 0 ? 0 : offset[bt - 1], seg_end = offset[bt];
         const float qx = new_xyz[(size_t)pt * 3], qy = new_xyz[(size_t)pt * 3 + 1], qz = new_xyz[(size_t)pt * 3 + 2];
         __syncthreads();
@@ -936,37 +988,23 @@ __global__ __launch_bounds__(1024) void knn_exact_list_kernel(
         // ---- grid pruning: S and T -------------------------------------------------------------------
         int *s_si = (int *)(s_d2 + 1024);      // S by candidate slot: index      (s_d2[0..1023]: distance)
         int ns = 0;                            // |S| when the pruning applies, else 0
-        if (gp) {
+        if (gp) {  // (every caller brings a grid; unguarded, the loads move above the barriers and cost six registers)
             const GridParams g = *gp;
-            const int cx = cell_coord(qx, g.minx, g.inv_h, g.nx), cy = cell_coord(qy, g.miny, g.inv_h, g.ny),
-                      cz = cell_coord(qz, g.minz, g.inv_h, g.nz);
-            const int *cs = cell_start + (size_t)bt * g.ncell;
+            const QueryCell h = query_cell(g, new_xyz, pt, bt, cell_start);
             // the (2R+1)^3 block for R = 1, then 2: the first whose S holds at least k points is used
             for (int R = 1; R <= KXL_MAXR && ns == 0; ++R) {
-                const int side = 2 * R + 1, nruns = side * side;
+                const int nruns = (2 * R + 1) * (2 * R + 1);
                 __syncthreads();
                 if ((int)threadIdx.x < nruns) {
-                    int b = 0, e = 0;
-                    const int z = cz + (int)threadIdx.x / side - R, y = cy + (int)threadIdx.x % side - R;
-                    if (z >= 0 && z < g.nz && y >= 0 && y < g.ny) {
-                        const int row = (z * g.ny + y) * g.nx;
-                        b = cs[row + max(cx - R, 0)];
-                        e = cs[row + min(cx + R, g.nx - 1) + 1];
-                    }
+                    int b, e, bB, eB;  // whole block: every pair gives its full x-run, no second run
+                    shell_pair_runs(g, h.cs, h.cx, h.cy, h.cz, R, (int)threadIdx.x, true, b, e, bB, eB);
                     s_run_b[threadIdx.x] = b;
                     s_run_e[threadIdx.x] = e;
                 }
                 if (threadIdx.x == 0) s_cnt = 0;
                 __syncthreads();
-                float dmin = 3.4e38f;  // distance to the nearest face of the block that has cells beyond it
-                if (cx - R > 0) dmin = fminf(dmin, qx - (g.minx + (float)(cx - R) * g.h));
-                if (cx + R + 1 < g.nx) dmin = fminf(dmin, (g.minx + (float)(cx + R + 1) * g.h) - qx);
-                if (cy - R > 0) dmin = fminf(dmin, qy - (g.miny + (float)(cy - R) * g.h));
-                if (cy + R + 1 < g.ny) dmin = fminf(dmin, (g.miny + (float)(cy + R + 1) * g.h) - qy);
-                if (cz - R > 0) dmin = fminf(dmin, qz - (g.minz + (float)(cz - R) * g.h));
-                if (cz + R + 1 < g.nz) dmin = fminf(dmin, (g.minz + (float)(cz + R + 1) * g.h) - qz);
-                dmin -= g.margin;
-                const float r0 = dmin > 0.f ? dmin * dmin * 0.99999f : 0.f;  // nothing outside the block is nearer
+                bool whole;
+                const float r0 = shell_safe_d2(shell_unseen_bound(g, h, R, whole));  // nothing outside the block is nearer
                 int tot = 0;
                 for (int r = 0; r < nruns; ++r) tot += s_run_e[r] - s_run_b[r];
                 if (tot > 1024 * KXL_PER) break;  // workgroup-uniform: too dense for the LDS staging -> full scan
@@ -1017,10 +1055,6 @@ __global__ __launch_bounds__(1024) void knn_exact_list_kernel(
             }
         }
         const int end = s_T;  // == seg_end without pruning
-#ifdef AMC_KNN_DIAG
-        long long t_a = clock64(), t_surv = 0;
-        int n_steps = 0, n_surv = 0, n_acc = 0, n_survsteps = 0;
-#endif
 
         auto step_len = [&](int pos) { return min(1024 * KXL_PER, max(64, pos - start)); };
         float px[KXL_PER], py[KXL_PER], pz[KXL_PER];
@@ -1049,14 +1083,7 @@ __global__ __launch_bounds__(1024) void knn_exact_list_kernel(
             }
             const int npos = pos + len, nlen = step_len2(npos);
             if (npos < end) load(npos, nlen);  // in flight across the barriers below
-#ifdef AMC_KNN_DIAG
-            n_steps++;
-            long long t_s0 = clock64();
-#endif
             if (__syncthreads_or(any)) {
-#ifdef AMC_KNN_DIAG
-                n_survsteps++;
-#endif
 #pragma unroll
                 for (int j = 0; j < KXL_PER; ++j) {
                     if (j < per) s_d2[j * 1024 + threadIdx.x] = d2[j];
@@ -1081,10 +1108,6 @@ __global__ __launch_bounds__(1024) void knn_exact_list_kernel(
                             mm &= mm - 1;
                             const int o = half * 4096 + wsel * 64 + b;  // == j*1024 + w*64 + b
                             const float cd = s_d2[o];
-#ifdef AMC_KNN_DIAG
-                            n_surv++;
-                            if (cd < root) n_acc++;
-#endif
                             if (cd < root) {  // knnquery_cuda_kernel.cu:97-101
                                 lh_replace_root(hp, nsample, lane, cd, pos + o);
                                 root = lh_root(hp);
@@ -1095,18 +1118,10 @@ __global__ __launch_bounds__(1024) void knn_exact_list_kernel(
                     if (lane == 0) s_root = root;
                 }
                 __syncthreads();
-#ifdef AMC_KNN_DIAG
-                t_surv += clock64() - t_s0;
-#endif
             }
             pos = npos;
             len = nlen;
         }
-#ifdef AMC_KNN_DIAG
-        if (threadIdx.x == 0)
-            printf("replay q=%d T=%d |S|=%d steps=%d survsteps=%d surv=%d acc=%d  prefix_clk=%lld surv_clk=%lld\n", pt, end, ns,
-                   n_steps, n_survsteps, n_surv, n_acc, (long long)(clock64() - t_a), t_surv);
-#endif
         if (wave == 0) {
             // the members of S beyond the prefix, in index order (ranks nsample.. hold the indices >= T)
             float root = s_root;
@@ -1154,12 +1169,11 @@ __global__ __launch_bounds__(256) void kg_prefix_kernel(int m, int kr, int nb, i
     const int q = act ? (int)qg : 0;
     const GridParams g = *gp;
     const int seg = nb > 1 ? seg_of(q, new_offset, nb) : 0;
-    const float qx = new_xyz[(size_t)q * 3], qy = new_xyz[(size_t)q * 3 + 1], qz = new_xyz[(size_t)q * 3 + 2];
-    const int cx = cell_coord(qx, g.minx, g.inv_h, g.nx), cy = cell_coord(qy, g.miny, g.inv_h, g.ny),
-              cz = cell_coord(qz, g.minz, g.inv_h, g.nz);
-    const size_t cell = (size_t)seg * g.ncell + ((size_t)cz * g.ny + cy) * g.nx + cx;
-    const int b = cell_start[cell];
-    const int len = act ? cell_start[cell + 1] - b : 0;
+    const QueryCell h = query_cell(g, new_xyz, q, seg, cell_start);
+    const float qx = h.qx, qy = h.qy, qz = h.qz;
+    const size_t cell = ((size_t)h.cz * g.ny + h.cy) * g.nx + h.cx;
+    const int b = h.cs[cell];
+    const int len = act ? h.cs[cell + 1] - b : 0;
     const int wave_len = max(len, __shfl_xor(len, 32, 64));
     int found = 0, cnt = 0;
     for (int c0 = 0; c0 < wave_len; c0 += 32) {  // (a few points per cell)
@@ -1188,40 +1202,77 @@ __global__ __launch_bounds__(256) void kg_prefix_kernel(int m, int kr, int nb, i
     }
 }
 
+// ---- host side: the workspace as typed pointers ------------------------------------------------------------
+struct GridView {
+    GridParams *gp;
+    int *bbox;
+    float *samples;
+    int *off_s, *off_q;  // uniform segment ends of the batched (B, N, 3) searches
+    int *fb_count;       // number of entries of fb_list (AMC_KNN_FALLBACK_COUNT_OFFSET)
+    int *tile_sums, *cell_start, *cursor;
+    float4 *sorted;
+    int *fb_list;        // queries handed to the replay
+};
+
+static GridView grid_view(const KnnWorkspace &w, void *workspace)
+{
+    char *base = (char *)workspace;
+    GridView v;
+    v.gp = (GridParams *)(base + w.params);
+    v.bbox = (int *)(base + w.bbox);
+    v.samples = (float *)(base + w.samples);
+    v.off_s = (int *)(base + w.off_s);
+    v.off_q = (int *)(base + w.off_q);
+    v.fb_count = (int *)(base + w.fb_count);
+    v.tile_sums = (int *)(base + w.tile_sums);
+    v.cell_start = (int *)(base + w.cell_start);
+    v.cursor = (int *)(base + w.cursor);
+    v.sorted = (float4 *)(base + w.sorted);
+    v.fb_list = (int *)(base + w.fb_list);
+    return v;
+}
+
 // Grid construction shared by the k-NN, ball-query and 3-NN searches: bounding box, cell size (calibrated on
 // `ksample`-th neighbour distances of 64 sample queries, or `fixed_h` when > 0), counting sort of the support
 // points into cell order.  Leaves GridParams, cell_start[] and sorted[] in the workspace.
-static int kg_build(const KnnWorkspace &w, char *base, int n, int m, int nbatch, const float *xyz, const float *new_xyz,
-                    const int *offset, const int *new_offset, int ksample, int sub, float hscale, float fixed_h,
-                    hipStream_t stream)
+static int kg_build(const GridView &v, int n, int m, int nbatch, const float *xyz, const float *new_xyz, const int *offset,
+                    const int *new_offset, int ksample, int sub, float hscale, float fixed_h, hipStream_t stream)
 {
-    GridParams *gp = (GridParams *)(base + w.params);
-    int *bbox = (int *)(base + w.bbox);
-    float *samples = (float *)(base + w.samples);
-    int *fb_count = (int *)(base + w.fb_count);
-    int *cell_start = (int *)(base + w.cell_start);
-    int *cursor = (int *)(base + w.cursor);
-    float4 *sorted = (float4 *)(base + w.sorted);
     const size_t cells = (size_t)knn_cell_cap(n) + 1;
     // cell_start and cursor are neighbours in the workspace (knn_layout): one launch zeroes both and the padding between
-    if (int st = fill_i32(cell_start, 0, (size_t)(cursor - cell_start) + cells, stream)) return st;
-    hipLaunchKernelGGL(kg_init_kernel, dim3(1), dim3(64), 0, stream, bbox, fb_count);
-    hipLaunchKernelGGL(kg_bbox_kernel, dim3(min(div_up(n, 256), 64)), dim3(256), 0, stream, n, xyz, bbox);
+    if (int st = fill_i32(v.cell_start, 0, (size_t)(v.cursor - v.cell_start) + cells, stream)) return st;
+    hipLaunchKernelGGL(kg_init_kernel, dim3(1), dim3(64), 0, stream, v.bbox, v.fb_count);
+    hipLaunchKernelGGL(kg_bbox_kernel, dim3(min(div_up(n, 256), 64)), dim3(256), 0, stream, n, xyz, v.bbox);
     if (!(fixed_h > 0.f))
         hipLaunchKernelGGL(kg_sample_kernel, dim3(KG_SAMPLES), dim3(1024), 0, stream, m, ksample, nbatch, sub, xyz, new_xyz,
-                           offset, new_offset, samples);
-    hipLaunchKernelGGL(kg_params_kernel, dim3(1), dim3(64), 0, stream, n, nbatch, hscale, fixed_h, bbox, samples, gp);
-    hipLaunchKernelGGL(kg_count_kernel, dim3(div_up(n, 256)), dim3(256), 0, stream, n, nbatch, xyz, offset, gp,
-                       cell_start);
-    int *tile_sums = (int *)(base + w.tile_sums);
+                           offset, new_offset, v.samples);
+    hipLaunchKernelGGL(kg_params_kernel, dim3(1), dim3(64), 0, stream, n, nbatch, hscale, fixed_h, v.bbox, v.samples, v.gp);
+    hipLaunchKernelGGL(kg_count_kernel, dim3(div_up(n, 256)), dim3(256), 0, stream, n, nbatch, xyz, offset, v.gp,
+                       v.cell_start);
     const int ntiles = div_up(knn_cell_cap(n), KG_SCAN_TILE);  // <= 1024
-    hipLaunchKernelGGL(kg_scan_sums_kernel, dim3(ntiles), dim3(256), 0, stream, nbatch, gp, cell_start, tile_sums);
-    hipLaunchKernelGGL(kg_scan_tiles_kernel, dim3(1), dim3(1024), 0, stream, ntiles, tile_sums);
-    hipLaunchKernelGGL(kg_scan_apply_kernel, dim3(ntiles), dim3(256), 0, stream, nbatch, gp, cell_start, tile_sums,
+    hipLaunchKernelGGL(kg_scan_sums_kernel, dim3(ntiles), dim3(256), 0, stream, nbatch, v.gp, v.cell_start, v.tile_sums);
+    hipLaunchKernelGGL(kg_scan_tiles_kernel, dim3(1), dim3(1024), 0, stream, ntiles, v.tile_sums);
+    hipLaunchKernelGGL(kg_scan_apply_kernel, dim3(ntiles), dim3(256), 0, stream, nbatch, v.gp, v.cell_start, v.tile_sums,
                        ntiles);
-    hipLaunchKernelGGL(kg_scatter_kernel, dim3(div_up(n, 256)), dim3(256), 0, stream, n, nbatch, xyz, offset, gp,
-                       cell_start, cursor, sorted);
+    hipLaunchKernelGGL(kg_scatter_kernel, dim3(div_up(n, 256)), dim3(256), 0, stream, n, nbatch, xyz, offset, v.gp,
+                       v.cell_start, v.cursor, v.sorted);
     return launch_status("grid build");
+}
+
+// The grid of a k-NN call, its replay list empty.  reuse_grid: the workspace still holds the grid of this very support
+// set (xyz, offset) from an earlier call -- its cell size was calibrated for that call's k, which only steers speed --
+// and only the replay counter is reset.  Else the grid is built with cell edge = 0.7 x p80 of the ceil(k/4)-th
+// neighbour distance among every 4th support point (see "Cell size" above).
+static int grid_prepare(const GridView &v, int reuse_grid, int n, int m, int nbatch, const float *xyz, const float *new_xyz,
+                        const int *offset, const int *new_offset, int k, hipStream_t stream)
+{
+    if (reuse_grid) {
+        hipLaunchKernelGGL(kg_init_kernel, dim3(1), dim3(64), 0, stream, v.bbox, v.fb_count);
+        return 0;
+    }
+    const int kg_sub = 4;
+    const float kg_scale = 0.7f;
+    return kg_build(v, n, m, nbatch, xyz, new_xyz, offset, new_offset, (k + kg_sub - 1) / kg_sub, kg_sub, kg_scale, 0.f, stream);
 }
 
 // ---- batched (B, N, 3) searches on the same grid: ball query and 3-NN --------------------------------
@@ -1230,21 +1281,6 @@ __global__ void kg_uniform_offsets_kernel(int nb, int n_per, int m_per, int *__r
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < nb) { off_s[i] = (i + 1) * n_per; off_q[i] = (i + 1) * m_per; }
-}
-
-// The (dz,dy) x-runs of the 3x3x3 block around cell (cx,cy,cz): lane pi < 9 gets run pi as [b, e)
-__device__ __forceinline__ void kg_block_runs(const GridParams &g, const int *__restrict__ cs, int cx, int cy, int cz, int lane,
-                                              int &b, int &e)
-{
-    b = 0; e = 0;
-    if (lane < 9) {
-        const int z = cz + lane / 3 - 1, y = cy + lane % 3 - 1;
-        if (z >= 0 && z < g.nz && y >= 0 && y < g.ny) {
-            const int row = (z * g.ny + y) * g.nx;
-            b = cs[row + max(cx - 1, 0)];
-            e = cs[row + min(cx + 1, g.nx - 1) + 1];
-        }
-    }
 }
 
 // Ball query (ball_query_gpu.cu:15-51) on the grid, cell edge >= radius: every point within the radius of a query
@@ -1261,34 +1297,21 @@ __global__ __launch_bounds__(256) void bq_grid_kernel(int nq, int n, int m, floa
     const GridParams g = *gp;
     for (int q = blockIdx.x * 4 + (threadIdx.x >> 6); q < nq; q += gridDim.x * 4) {
         const int bs = q / m;
-        const float qx = new_xyz[(size_t)q * 3], qy = new_xyz[(size_t)q * 3 + 1], qz = new_xyz[(size_t)q * 3 + 2];
-        const int cx = cell_coord(qx, g.minx, g.inv_h, g.nx), cy = cell_coord(qy, g.miny, g.inv_h, g.ny),
-                  cz = cell_coord(qz, g.minz, g.inv_h, g.nz);
-        int b, e;
-        kg_block_runs(g, cell_start + (size_t)bs * g.ncell, cx, cy, cz, lane, b, e);
-        const int len = e - b;
-        int incl = len;
-        for (int s = 1; s < 16; s <<= 1) {  // only lanes 0..8 hold runs
-            const int o = __shfl_up(incl, s, 64);
-            if (lane >= s) incl += o;
-        }
-        const int total = __builtin_amdgcn_readlane(incl, 8);
-        const int excl = incl - len;
+        const QueryCell h = query_cell(g, new_xyz, q, bs, cell_start);
+        int b, e, bB, eB;  // the whole 3x3x3 block: lanes 0..8 own its nine full x-runs
+        shell_pair_runs(g, h.cs, h.cx, h.cy, h.cz, 1, lane, true, b, e, bB, eB);
+        int excl;
+        const int total = packed_scan(e - b, lane, excl);
+        const unsigned long long runs = __ballot(e > b);
         int key = 0x7fffffff;  // this lane's entry of the ascending list of the smallest hit indices
         int tau = 0x7fffffff;  // its nsample-th entry (wave-uniform)
         int have = 0;
         for (int c0 = 0; c0 < total; c0 += 64) {
             const int c = c0 + lane;
-            int base = 0;
-#pragma unroll
-            for (int r = 0; r < 9; ++r) {
-                const int e0 = __builtin_amdgcn_readlane(excl, r), b0 = __builtin_amdgcn_readlane(b, r);
-                const int l0 = __builtin_amdgcn_readlane(len, r);
-                base = (l0 > 0 && c >= e0) ? b0 - e0 : base;
-            }
+            const int src = packed_slot_source(c, c0, runs, excl, b);
             const bool valid = c < total;
-            const float4 p = sorted[valid ? base + c : __builtin_amdgcn_readfirstlane(base + c)];
-            const float d2 = dist2_ref(qx, qy, qz, p.x, p.y, p.z);
+            const float4 p = sorted[valid ? src : __builtin_amdgcn_readfirstlane(src)];
+            const float d2 = dist2_ref(h.qx, h.qy, h.qz, p.x, p.y, p.z);
             const int pi = __float_as_int(p.w);
             unsigned long long hits = __ballot(valid && d2 < radius2 && pi < tau);
             while (hits) {
@@ -1312,7 +1335,7 @@ __global__ __launch_bounds__(256) void bq_grid_kernel(int nq, int n, int m, floa
 
 // three_nn (interpolate_gpu.cu:16-59) on the grid: the 3 nearest known points of every unknown point, ties
 // resolved as the reference's ascending strict-'<' scan does (the lower index ranks first), i.e. the list is
-// ordered by (distance, index) -- exact without a replay.  Shell expansion and stopping rule as in kg_query.
+// ordered by (distance, index) -- exact without a replay.  The walk and the stop rule of "Grid-accelerated path".
 // One THREAD per query: a 3-NN query meets a dozen candidates in its 27 cells, so a wave per query (the first version of
 // this kernel: 275 us for the 192000 queries of the finest FeaturePropagation level, 104 us now) spends its time in
 // cross-lane bookkeeping; a thread keeps the three best in registers and walks the nine x-runs of its neighbourhood itself,
@@ -1328,14 +1351,11 @@ __global__ __launch_bounds__(256) void nn3_grid_thread_kernel(int nq, int n, int
     const GridParams g = *gp;
     const float inf = __builtin_inff();
     const int bs = q / n;
-    const float qx = unknown[(size_t)q * 3], qy = unknown[(size_t)q * 3 + 1], qz = unknown[(size_t)q * 3 + 2];
-    const int cx = cell_coord(qx, g.minx, g.inv_h, g.nx), cy = cell_coord(qy, g.miny, g.inv_h, g.ny),
-              cz = cell_coord(qz, g.minz, g.inv_h, g.nz);
-    const int *cs = cell_start + (size_t)bs * g.ncell;
+    const QueryCell h = query_cell(g, unknown, q, bs, cell_start);
     float d0 = inf, d1 = inf, d2 = inf;
     int i0 = bs * m, i1 = bs * m, i2 = bs * m;  // local index 0: the reference's initial besti
     auto consider = [&](const float4 p) {
-        const float cd = dist2_ref(qx, qy, qz, p.x, p.y, p.z);
+        const float cd = dist2_ref(h.qx, h.qy, h.qz, p.x, p.y, p.z);
         const int ci = __float_as_int(p.w);
         if (cd < d2 || (cd == d2 && ci < i2)) {
             if (cd < d1 || (cd == d1 && ci < i1)) {
@@ -1357,53 +1377,35 @@ __global__ __launch_bounds__(256) void nn3_grid_thread_kernel(int nq, int n, int
         }
     };
     {   // first shell: the bounds of its nine x-runs as one batch of loads (18 in flight), then the runs
-        const int xa = max(cx - 1, 0), xb = min(cx + 1, g.nx - 1) + 1;
         int rb[9], re[9];
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
-            const int z = cz + t / 3 - 1, y = cy + t % 3 - 1;
-            const bool in = z >= 0 && z < g.nz && y >= 0 && y < g.ny;
-            const int row = in ? (z * g.ny + y) * g.nx : 0;
-            rb[t] = in ? cs[row + xa] : 0;
-            re[t] = in ? cs[row + xb] : 0;
+            int bB, eB;  // R == 1: every pair is one full run
+            shell_pair_runs(g, h.cs, h.cx, h.cy, h.cz, 1, t, false, rb[t], re[t], bB, eB);
         }
 #pragma unroll
         for (int t = 0; t < 9; ++t) run(rb[t], re[t]);
     }
     for (int R = 1;; ++R) {
         for (int dz = -R; R > 1 && dz <= R; ++dz) {
-            const int z = cz + dz;
-            if (z < 0 || z >= g.nz) continue;
-            for (int dy = -R; dy <= R; ++dy) {
-                const int y = cy + dy;
-                if (y < 0 || y >= g.ny) continue;
-                const int row = (z * g.ny + y) * g.nx;
-                const bool rim = R == 1 || dz == -R || dz == R || dy == -R || dy == R;
-                if (rim) {
-                    run(cs[row + max(cx - R, 0)], cs[row + min(cx + R, g.nx - 1) + 1]);
-                } else {
-                    if (cx - R >= 0) run(cs[row + cx - R], cs[row + cx - R + 1]);
-                    if (cx + R < g.nx) run(cs[row + cx + R], cs[row + cx + R + 1]);
-                }
+            // a thin grid (nz == 1) is crossed in hundreds of rings: a z-row outside it must cost nothing
+            if (h.cz + dz < 0 || h.cz + dz >= g.nz) continue;
+            for (int dy = -R; dy <= R; ++dy) {  // (dz, dy) as they are: decoding a pair number costs two divisions
+                int bA, eA, bB, eB;
+                shell_row_runs(g, h.cs, h.cx, h.cy, h.cz, R, dz, dy, false, bA, eA, bB, eB);
+                run(bA, eA);
+                run(bB, eB);
             }
         }
-        float dmin = 3.4e38f;
-        bool whole = true;
-        if (cx - R > 0) { dmin = fminf(dmin, qx - (g.minx + (float)(cx - R) * g.h)); whole = false; }
-        if (cx + R + 1 < g.nx) { dmin = fminf(dmin, (g.minx + (float)(cx + R + 1) * g.h) - qx); whole = false; }
-        if (cy - R > 0) { dmin = fminf(dmin, qy - (g.miny + (float)(cy - R) * g.h)); whole = false; }
-        if (cy + R + 1 < g.ny) { dmin = fminf(dmin, (g.miny + (float)(cy + R + 1) * g.h) - qy); whole = false; }
-        if (cz - R > 0) { dmin = fminf(dmin, qz - (g.minz + (float)(cz - R) * g.h)); whole = false; }
-        if (cz + R + 1 < g.nz) { dmin = fminf(dmin, (g.minz + (float)(cz + R + 1) * g.h) - qz); whole = false; }
-        if (whole) break;
-        dmin -= g.margin;
-        if (dmin > 0.f && d2 < dmin * dmin * 0.99999f) break;  // strictly nearer than anything unseen
+        bool whole;
+        const float bound = shell_unseen_bound(g, h, R, whole);
+        if (shell_closed(bound, whole, d2)) break;  // the third is strictly nearer than anything unseen
     }
     dist2[(size_t)q * 3] = d0; dist2[(size_t)q * 3 + 1] = d1; dist2[(size_t)q * 3 + 2] = d2;
     idx[(size_t)q * 3] = i0 - bs * m; idx[(size_t)q * 3 + 1] = i1 - bs * m; idx[(size_t)q * 3 + 2] = i2 - bs * m;
 }
 
-bool grid_search_pays(int b, int n, int m) { return b <= 64 && (long)n * m >= (1L << 21) && (long)b * n >= 4 * KG_SAMPLES; }
+bool grid_search_pays(int b, int n, int m) { return b <= KG_MAX_BATCH && (long)n * m >= (1L << 21) && (long)b * n >= 4 * KG_SAMPLES; }
 
 size_t grid_search_workspace_bytes(int b, int n, int m) { return knn_layout(b * n, b * m).total; }
 
@@ -1411,16 +1413,14 @@ size_t grid_search_workspace_bytes(int b, int n, int m) { return knn_layout(b * 
 int ball_query_grid(int b, int n, int m, float radius, int nsample, const float *new_xyz, const float *xyz, int *idx,
                     void *workspace, hipStream_t stream)
 {
-    const KnnWorkspace w = knn_layout(b * n, b * m);
-    char *base = (char *)workspace;
-    int *off_s = (int *)(base + 768), *off_q = (int *)(base + 6400);
-    hipLaunchKernelGGL(kg_uniform_offsets_kernel, dim3(1), dim3(64), 0, stream, b, n, m, off_s, off_q);
+    const GridView v = grid_view(knn_layout(b * n, b * m), workspace);
+    hipLaunchKernelGGL(kg_uniform_offsets_kernel, dim3(1), dim3(64), 0, stream, b, n, m, v.off_s, v.off_q);
     // cell edge 1 % above the radius: a point within the radius is at most one cell away whatever fp32 does
-    if (int st = kg_build(w, base, b * n, b * m, b, xyz, new_xyz, off_s, off_q, 1, 1, 1.f, radius * 1.01f + 1e-30f, stream))
+    if (int st = kg_build(v, b * n, b * m, b, xyz, new_xyz, v.off_s, v.off_q, 1, 1, 1.f, radius * 1.01f + 1e-30f, stream))
         return st;
     hipLaunchKernelGGL(bq_grid_kernel, dim3(min(div_up((long)b * m, 4), 256 * 32)), dim3(256), 0, stream, b * m, n, m,
-                       radius * radius, nsample, new_xyz, (const GridParams *)(base + w.params),
-                       (const int *)(base + w.cell_start), (const float4 *)(base + w.sorted), idx);
+                       radius * radius, nsample, new_xyz, (const GridParams *)v.gp, (const int *)v.cell_start,
+                       (const float4 *)v.sorted, idx);
     return launch_status("amc3d_ball_query");
 }
 
@@ -1428,16 +1428,14 @@ int ball_query_grid(int b, int n, int m, float radius, int nsample, const float 
 int three_nn_grid(int b, int n, int m, const float *unknown, const float *known, float *dist2, int *idx, void *workspace,
                   hipStream_t stream)
 {
-    const KnnWorkspace w = knn_layout(b * m, b * n);
-    char *base = (char *)workspace;
-    int *off_s = (int *)(base + 768), *off_q = (int *)(base + 6400);
-    hipLaunchKernelGGL(kg_uniform_offsets_kernel, dim3(1), dim3(64), 0, stream, b, m, n, off_s, off_q);
-    // cell edge = p80 of the 2nd-neighbour distance among every 2nd known point (~ the 4th neighbour): swept in
-    // scratch/nn3_bench.py, 1.0 x that is the fastest
-    if (int st = kg_build(w, base, b * m, b * n, b, known, unknown, off_s, off_q, 2, 2, 1.0f, 0.f, stream)) return st;
+    const GridView v = grid_view(knn_layout(b * m, b * n), workspace);
+    hipLaunchKernelGGL(kg_uniform_offsets_kernel, dim3(1), dim3(64), 0, stream, b, m, n, v.off_s, v.off_q);
+    // cell edge = p80 of the 2nd-neighbour distance among every 2nd known point (~ the 4th neighbour).  Scales of 0.7,
+    // 1.0 and 1.4 x that were timed on the finest FeaturePropagation level (nn3_grid_thread_kernel's comment): 1.0 x
+    // is the fastest; the sweep script is not kept.
+    if (int st = kg_build(v, b * m, b * n, b, known, unknown, v.off_s, v.off_q, 2, 2, 1.0f, 0.f, stream)) return st;
     hipLaunchKernelGGL(nn3_grid_thread_kernel, dim3(div_up((long)b * n, 256)), dim3(256), 0, stream, b * n, n, m,
-                       unknown, (const GridParams *)(base + w.params), (const int *)(base + w.cell_start),
-                       (const float4 *)(base + w.sorted), dist2, idx);
+                       unknown, (const GridParams *)v.gp, (const int *)v.cell_start, (const float4 *)v.sorted, dist2, idx);
     return launch_status("amc3d_three_nn");
 }
 
@@ -1455,7 +1453,7 @@ AMC_API size_t amc3d_knnquery_workspace_bytes(int n, int m, int nsample, int nba
 // answers with the all-pairs heap kernel and leaves the workspace untouched
 AMC_API int amc3d_knnquery_uses_grid(int m, int nsample, int n, int nbatch)
 {
-    return (nsample <= KG_MAXK && (long)n * m >= (1L << 22) && n >= 4 * KG_SAMPLES && nbatch <= 64) ? 1 : 0;
+    return (nsample <= KG_MAXK && (long)n * m >= (1L << 22) && n >= 4 * KG_SAMPLES && nbatch <= KG_MAX_BATCH) ? 1 : 0;
 }
 
 // 1 when amc3d_ball_query (support n, queries m) / amc3d_three_nn (support = known) search the cell grid, given a workspace
@@ -1481,24 +1479,11 @@ static int knn_search(int m, int nsample, int n, int nbatch, const float *xyz, c
     }
     const KnnWorkspace w = knn_layout(n, m);
     if (!workspace || workspace_bytes < w.total) return bad_arg("amc3d_knnquery: workspace too small");
-    char *base = (char *)workspace;
-    // cell edge = scale x p80 of the ceil(k/sub)-th neighbour distance among every sub-th support point; swept on
-    // the loss's seven searches (scratch/knn_sweep.sh): speed only, any value gives the same results
-    const int kg_sub = 4;
-    const float kg_scale = 0.7f;
-    if (reuse_grid) {
-        // the workspace still holds the grid of this very support set (xyz, offset) from an earlier call: its cell
-        // size was calibrated for that call's k, which only steers speed.  Only the replay counter is reset.
-        hipLaunchKernelGGL(kg_init_kernel, dim3(1), dim3(64), 0, stream, (int *)(base + w.bbox), (int *)(base + w.fb_count));
-    } else if (int st = kg_build(w, base, n, m, nbatch, xyz, new_xyz, offset, new_offset,
-                                 (nsample + kg_sub - 1) / kg_sub, kg_sub, kg_scale, 0.f, stream)) {
-        return st;
-    }
-    GridParams *gp = (GridParams *)(base + w.params);
-    int *fb_count = (int *)(base + w.fb_count);
-    int *cell_start = (int *)(base + w.cell_start);
-    float4 *sorted = (float4 *)(base + w.sorted);
-    int *fb_list = (int *)(base + w.fb_list);
+    const GridView v = grid_view(w, workspace);
+    if (int st = grid_prepare(v, reuse_grid, n, m, nbatch, xyz, new_xyz, offset, new_offset, nsample, stream)) return st;
+    const GridParams *gp = v.gp;
+    const int *cell_start = v.cell_start;
+    const float4 *sorted = v.sorted;
     const int self = (new_xyz == xyz && m == n && new_offset == offset) ? 1 : 0;
     if (nsample <= KGG_MAXK) {
         // Two queries per wavefront, 32 lanes each, for every k <= 32 whatever m: the rule is the input's k alone.
@@ -1508,16 +1493,15 @@ static int knn_search(int m, int nsample, int n, int nbatch, const float *xyz, c
         // No shape class measured slower, so none keeps the wave-per-query kernel; k in 33..64 has no other.
         constexpr int per_wg = 4 * (64 / KGG_MAXK);
         hipLaunchKernelGGL(kg_query_group_kernel<KGG_MAXK>, dim3(min(div_up(m, per_wg), 256 * 32)), dim3(256), 0, stream, m,
-                           nsample, nbatch, self, new_xyz, offset, new_offset, gp, cell_start, sorted, idx, dist2, fb_list,
-                           fb_count);
+                           nsample, nbatch, self, new_xyz, offset, new_offset, gp, cell_start, sorted, idx, dist2, v.fb_list,
+                           v.fb_count);
     } else {
         hipLaunchKernelGGL(kg_query_kernel, dim3(min(div_up(m, 4), 256 * 32)), dim3(256), 0, stream, m, nsample, nbatch, self,
-                           new_xyz, offset, new_offset, gp, cell_start, sorted, idx, dist2, fb_list, fb_count);
+                           new_xyz, offset, new_offset, gp, cell_start, sorted, idx, dist2, v.fb_list, v.fb_count);
     }
     // queries with equal distances among their k+1 nearest: replay the reference's heap
     hipLaunchKernelGGL(knn_exact_list_kernel, dim3(256), dim3(1024), 0, stream, nsample, nbatch, xyz, new_xyz, offset,
-                       new_offset, idx, dist2, (const int *)fb_list, (const int *)fb_count, (const GridParams *)gp,
-                       (const int *)cell_start, (const float4 *)sorted);
+                       new_offset, idx, dist2, (const int *)v.fb_list, (const int *)v.fb_count, gp, cell_start, sorted);
     return launch_status("amc3d_knnquery");
 }
 
@@ -1534,29 +1518,22 @@ AMC_API int amc3d_knn_prefix(int m, int kr, int n, int nbatch, const float *xyz,
                              int *idx, float *dist2, void *workspace, size_t workspace_bytes, int reuse_grid, void *stream_)
 {
     if (m <= 0) return 0;
-    if (kr <= 0 || kr >= k0 || kr >= 32 || row_stride < k0 || nbatch <= 0 || nbatch > 64 || n <= 0 || !xyz || !new_xyz ||
+    if (kr <= 0 || kr >= k0 || kr >= 32 || row_stride < k0 || nbatch <= 0 || nbatch > KG_MAX_BATCH || n <= 0 || !xyz || !new_xyz ||
         !offset || !new_offset || !rows_idx || !rows_d2 || !idx)
         return bad_arg("amc3d_knn_prefix: bad argument (0 < kr < k0 <= row_stride, kr <= 31, nbatch <= 64)");
     if (!reuse_grid && n < 4 * KG_SAMPLES) return bad_arg("amc3d_knn_prefix: too few support points to build a grid");
     hipStream_t stream = (hipStream_t)stream_;
     const KnnWorkspace w = knn_layout(n, m);
     if (!workspace || workspace_bytes < w.total) return bad_arg("amc3d_knn_prefix: workspace too small");
-    char *base = (char *)workspace;
-    static_assert(AMC_KNN_FALLBACK_COUNT_OFFSET == 1024, "knn_layout: fb_count");
-    if (reuse_grid) {  // as amc3d_knnquery: the grid of this support stays, the replay counter is reset
-        hipLaunchKernelGGL(kg_init_kernel, dim3(1), dim3(64), 0, stream, (int *)(base + w.bbox), (int *)(base + w.fb_count));
-    } else if (int st = kg_build(w, base, n, m, nbatch, xyz, new_xyz, offset, new_offset, (kr + 3) / 4, 4, 0.7f, 0.f, stream)) {
-        return st;
-    }
-    const GridParams *gp = (const GridParams *)(base + w.params);
-    int *fb_count = (int *)(base + w.fb_count);
-    const int *cell_start = (const int *)(base + w.cell_start);
-    const float4 *sorted = (const float4 *)(base + w.sorted);
-    int *fb_list = (int *)(base + w.fb_list);
+    const GridView v = grid_view(w, workspace);
+    if (int st = grid_prepare(v, reuse_grid, n, m, nbatch, xyz, new_xyz, offset, new_offset, kr, stream)) return st;
+    const GridParams *gp = v.gp;
+    const int *cell_start = v.cell_start;
+    const float4 *sorted = v.sorted;
     hipLaunchKernelGGL(kg_prefix_kernel, dim3(div_up((long)m * 32, 256)), dim3(256), 0, stream, m, kr, nbatch, row_stride, new_xyz,
-                       new_offset, gp, cell_start, sorted, rows_idx, rows_d2, idx, dist2, fb_list, fb_count);
+                       new_offset, gp, cell_start, sorted, rows_idx, rows_d2, idx, dist2, v.fb_list, v.fb_count);
     hipLaunchKernelGGL(knn_exact_list_kernel, dim3(256), dim3(1024), 0, stream, kr, nbatch, xyz, new_xyz, offset, new_offset,
-                       idx, dist2, (const int *)fb_list, (const int *)fb_count, gp, cell_start, sorted);
+                       idx, dist2, (const int *)v.fb_list, (const int *)v.fb_count, gp, cell_start, sorted);
     return launch_status("amc3d_knn_prefix");
 }
 
