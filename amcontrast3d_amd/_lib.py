@@ -43,6 +43,8 @@ SIGNATURES = {
     "amc3d_knn_prefix": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
     "amc3d_knn_batch_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "amc3d_knn_batch": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _sz, _i, _vp]),
+    "amc3d_knn_features_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "amc3d_knn_features": (_i, [_i] * 7 + [_vp, _l, _l, _vp, _l, _l, _vp, _vp, _i, _vp, _sz, _vp]),
     "amc3d_knn_group_dp": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "amc3d_pointops_ballquery": (_i, [_i, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "amc3d_pointops_furthestsampling": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -7,3 +7,4 @@ from .group import (ball_query, create_grouper, gather_operation, get_aggregatio
 from .subsample import fps, furthest_point_sample, random_sample
 from .upsampling import three_interpolate, three_interpolation, three_nn
 from .local_aggregation import ASSA, ConvPool, LocalAggregation
+from .graph_conv import MRConv, EdgeConv, GraphConv, DynConv, ResDynBlock, DenseDynBlock

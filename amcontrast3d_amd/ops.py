@@ -661,6 +661,53 @@ def knn_batch(k, support, query=None, dilation=1, dist=None):
 
 
 @torch.no_grad()
+def knn_features(k, support, query=None, dilation=1, farthest=False, dist=None, channel_major=False):
+    """k-NN in feature space (csrc/knn_feat.hip): support (B,N,C), query (B,M,C) (None: the support itself) -- with
+    `channel_major` (B,C,N) and (B,C,M), read in place -- -> (dist or None, idx): idx (B,M,k) int32 cloud-local, column j the
+    (j*dilation)-th of the k*dilation nearest (`farthest`: farthest) support rows, ascending in (d2, index) (descending d2,
+    ascending index), d2 = (|q|^2 + |s|^2) - 2 q.s in fp32 with every sum an fmaf chain over ascending channels; dist the
+    euclidean distances of those columns as (B,M,k) ('bmk') or (B,k,M) ('bkm').  No (B,M,N) matrix exists.  Features carry no
+    gradient through the search."""
+    if query is None:
+        query = support
+    assert support.is_contiguous() and query.is_contiguous()
+    _need_gpu(support, query)
+    _need_dtype(torch.float32, support=support, query=query)
+    ca, ra = (1, 2) if channel_major else (2, 1)
+    if support.dim() != 3 or query.dim() != 3 or support.shape[ca] != query.shape[ca] or support.shape[0] != query.shape[0] \
+            or support.shape[ca] < 1:
+        want = "(B,C,N) and (B,C,M)" if channel_major else "(B,N,C) and (B,M,C)"
+        raise RuntimeError(f"knn_features: expected {want}, got {tuple(support.shape)} and {tuple(query.shape)}")
+    k, dilation = int(k), int(dilation)
+    ksearch = k * dilation
+    B, N, M, C = support.shape[0], support.shape[ra], query.shape[ra], support.shape[ca]
+    if k <= 0 or dilation <= 0 or ksearch > KNN_BATCH_MAX:
+        raise RuntimeError(f"knn_features: k * dilation must be in 1..{KNN_BATCH_MAX}, got {k} * {dilation}")
+    if ksearch > N:
+        raise RuntimeError(f"knn_features: k * dilation = {ksearch} out of range for {N} support points")
+    if dist is not None and dist not in _KNN_DIST_LAYOUT:
+        raise ValueError(f"knn_features: dist must be None, 'bmk' or 'bkm', got {dist!r}")
+    dev = support.device
+    idx = torch.empty(B, M, k, dtype=torch.int32, device=dev)
+    out = None if dist is None else torch.empty((B, M, k) if dist == "bmk" else (B, k, M), dtype=torch.float32, device=dev)
+    if B == 0 or M == 0:
+        return out, idx
+    lib = _lib.load()
+    wbytes = int(lib.amc3d_knn_features_workspace_bytes(B, N, M, C, ksearch))
+    if wbytes == 0:
+        raise RuntimeError("knn_features: sizes out of range for 32-bit indices")
+    work = torch.empty(wbytes, dtype=torch.uint8, device=dev)
+    s_strides, q_strides = ((1, N), (1, M)) if channel_major else ((C, 1), (C, 1))
+    with torch.cuda.device(dev), timing.span("knn_features", B * (N + M) * C * 4 + idx.numel() * (4 if out is None else 8),
+                                             2.0 * B * N * M * C):
+        _lib.check(lib.amc3d_knn_features(B, N, M, C, ksearch, dilation, int(bool(farthest)), _ptr(support), *s_strides,
+                                          _ptr(query), *q_strides, _ptr(idx), _ptr(out) if out is not None else None,
+                                          _KNN_DIST_LAYOUT.get(dist, 0), _ptr(work), work.numel(), _stream(support)),
+                   "knn_features")
+    return out, idx
+
+
+@torch.no_grad()
 def knn_group_dp(idx, query, support, relative=True, normalize=False):
     """idx (B,M,K) int32 cloud-local, query (B,M,3), support (B,N,3) -> dp (B,3,M,K) = support[idx] (- query if relative);
     normalize: every cloud divided by its largest sqrt((x*x + y*y) + z*z) over (M,K), taken after the subtraction

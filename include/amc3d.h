@@ -200,6 +200,21 @@ int amc3d_knn_batch(int b, int n, int m, int ksearch, int dilation, const float 
                     int *idx, float *dist, int dist_layout, void *workspace, size_t workspace_bytes,
                     int reuse_grid, void *stream);
 
+/* k-NN in FEATURE space (csrc/knn_feat.hip), for models/layers/graph_conv.py's DynConv (the reference composes cdist + topk over
+ * a (b,m,n) matrix; here no distance reaches global memory).  support: b clouds of n rows with c channels, query: b clouds of
+ * m rows; a cloud is n * c (m * c) consecutive floats and element (row, channel) of it lies at row * row_stride + channel *
+ * ch_stride: (c, 1) reads (b,n,c) tensors, (1, n) reads (b,c,n) tensors in place.  query may be support.
+ * d2(i,j) = (qq_i + ss_j) - 2 * dot_ij in fp32; dot, qq and ss are fmaf chains over the channels in ascending order from 0 (what
+ * the fp32 MFMA computes), so a point's distance to itself is exactly 0.  The list of a query is the ksearch smallest pairs
+ * (d2, index) -- farthest != 0: (-d2, index) -- in ascending order: the same bits on every run, whatever the tiling.
+ * idx (b,m,ksearch/dilation) int32 cloud-local, columns 0, d, 2d, ... of the list; dist NULL or sqrtf(max(d2, 0)) of those
+ * columns in one of the AMC_KNN_DIST_* layouts.  ksearch in 1..100 and <= n, dilation divides it, c >= 1.  NaN inputs are
+ * outside the contract.  The workspace size does not depend on n.  No allocation, no synchronisation, no memset node. */
+size_t amc3d_knn_features_workspace_bytes(int b, int n, int m, int c, int ksearch);
+int amc3d_knn_features(int b, int n, int m, int c, int ksearch, int dilation, int farthest, const float *support,
+                       long s_row_stride, long s_ch_stride, const float *query, long q_row_stride, long q_ch_stride, int *idx,
+                       float *dist, int dist_layout, void *workspace, size_t workspace_bytes, void *stream);
+
 /* KNNGroup's coordinates (group.py:310-315): dp (b,3,m,k) = support[idx] (- query when `relative`); with `normalize`
  * every cloud is then divided by its own max over (m,k) of sqrt((x*x + y*y) + z*z), taken after the subtraction, which
  * is left in cloud_max (b) (an integer atomic max on the bit pattern: order-independent).  idx (b,m,k) int32

@@ -13,6 +13,13 @@ reference writes (cdist + topk + strided pick), and KNNGroup.forward (normalize_
 grouping_operation + subtract + amax + divide on the same indices.  Queries are an FPS pick of the support (M < N) or the
 support itself (M == N).  Both sides warmed up, then timed alternately in five rounds of device-event windows of at least
 0.3 s each; the median and the spread over the rounds are printed.
+
+    python tools/knn_bench.py --features C
+
+the feature-space search of DynConv: ops.knn_features on (B,C,N) features in place (self-search) against the reference's
+composition on the same device (transposed copy, cdist, topk, strided pick), at 8 x 4096 with k = 20, 8 x 4096 with k = 16 and
+dilation 4, and 1 x 24000 with k = 16; same timing scheme, plus the achieved 2 B N^2 C FLOP rate and its share of the 157 TF
+fp32 matrix roof, and the share of indices on which the two routes agree.
 """
 import collections
 import os
@@ -84,8 +91,57 @@ def batched(B, N, M, k, dilation=1):
         compare("KNNGroup.forward, normalize_dp, 32 feature channels", kernel_group, torch_group)
 
 
+FEATURE_SHAPES = [(8, 4096, 20, 1), (8, 4096, 16, 4), (1, 24000, 16, 1)]  # (B, N, k, dilation): DGCNN, DeepGCN, one room
+
+
+def features(C, shapes=FEATURE_SHAPES):
+    """ops.knn_features on (B,C,N) features, self-search, against cdist + topk + strided pick on the same device"""
+    import statistics
+    assert torch.cuda.is_available(), "timings need the GPU"
+
+    def window(fn, n):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(n):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / n * 1e3
+
+    for B, N, k, dilation in shapes:
+        torch.manual_seed(0)
+        x = torch.randn(B, C, N, device=dev)
+        rows = x.transpose(1, 2).contiguous()
+
+        def kernel_search():
+            return ops.knn_features(k, x, dilation=dilation, channel_major=True)[1]
+
+        def torch_search():  # DilatedKNN as the reference writes it, transposed copy included
+            r = x.transpose(1, 2).contiguous()
+            return torch.cdist(r, r).topk(k=k * dilation, dim=-1, largest=False).indices[:, :, ::dilation].contiguous().int()
+
+        with torch.no_grad():
+            same = float((kernel_search() == torch_search()).float().mean())
+            assert torch.equal(kernel_search(), ops.knn_features(k, rows, dilation=dilation)[1])
+            for fn in (kernel_search, torch_search):
+                for _ in range(3):
+                    fn()
+            torch.cuda.synchronize()
+            counts = [max(3, int(0.3e6 / max(window(fn, 3), 1.0))) for fn in (kernel_search, torch_search)]
+            rounds = [(window(kernel_search, counts[0]), window(torch_search, counts[1])) for _ in range(5)]
+        tn, to = [statistics.median(r[i] for r in rounds) for i in (0, 1)]
+        spread = [max(r[i] for r in rounds) - min(r[i] for r in rounds) for i in (0, 1)]
+        flops = 2.0 * B * N * N * C
+        print(f"features C={C} B={B} N={N} k={k} dilation={dilation}: knn_features {tn:9.1f} us (spread {spread[0]:.1f}, "
+              f"{flops / tn / 1e6:6.1f} TFLOP/s = {flops / tn / 1e6 / 157 * 100:4.1f} % of the 157 TF fp32 matrix roof), "
+              f"cdist + topk {to:9.1f} us (spread {spread[1]:.1f}), ratio {to / tn:.2f}; {same:.4f} of the indices equal", flush=True)
+
+
 if len(sys.argv) > 1 and sys.argv[1] == "--batched":
     batched(*[int(v) for v in sys.argv[2:7]])
+    sys.exit(0)
+if len(sys.argv) > 2 and sys.argv[1] == "--features":
+    features(int(sys.argv[2]))
     sys.exit(0)
 
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
